@@ -10,7 +10,12 @@ north_star's roofline target is quoted on); D and logD are already resident in H
 starts.  Chains are independent: with N GPUs every rank runs its own chain (weak scaling) and the only
 collective is the final sum all-reduce of the n×n co-clustering counts (outside the timed region, reported).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with
+A plain run sets up, settles the device clocks (untimed sweeps), restarts the chain from the generating labels, runs --warmup W
+sweeps and times exactly --steps K sweeps in one window: `value` (sweeps/s) and `ms_per_step` come from that window.
+--dump-outputs DIR writes what those K sweeps handed back to a caller (chain 0's labels, cluster sizes and K) as DIR/<name>.npy.
+
+Prints ONE JSON line on rank 0.  Everything below is measured only with --full (further timed windows and legs of their own):
+  `config.windows_*` RC_BENCH_WINDOWS (5) more windows of K sweeps after the headline one, with HIP events in the dispatch;
   `roofline`      the dominant kernel of the headline workload, k_bulk_syml2 (row reduction over the 48-bit packed upper triangle
                   of D, logD derived with a table log): PHYSICAL figures only — the bytes the kernel reads ÷ its mean launch duration
                   (HIP events carried in the dispatch, on the library's own stream) ÷ the 8 TB/s HBM peak; `bound` names what
@@ -20,7 +25,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with
   `other_configs` the other single-GPU BASELINE configurations, timed in this run: config 5 (N = 32768, K = 200, 32-bit storage, built
                   from points — HBM-resident: a real HBM roofline for k_bulk_sym32) and config 2 (N = 2000, K = 20: sweeps/s and
                   rc_run_chain iterations/s for numiters = 10000);
-  `cpu_baseline`  the C restatement of the reference's loop, faithful-cost mode, one host core, bounded sample.
+  `cpu_baseline`  the C restatement of the reference's loop, faithful-cost mode, one host core, bounded sample;
+  and the incremental mode, the 512-slot capacity, the moving regime, the reference's default options and the co-clustering
+  all-reduce (see the keys of the line).
 """
 import argparse
 import json
@@ -101,8 +108,24 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every figure beside the headline (roofline, other legs and configurations, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write chain 0's state after the last timed step (labels, cluster sizes, K) as float64 DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(outdir, state):
+    """What the timed path hands its caller after its last step (rc_get_state: labels, cluster sizes, K) as float64 .npy files —
+    exact, the values are integers far below 2^53."""
+    os.makedirs(outdir, exist_ok=True)
+    clusts, sizes, K = state
+    for name, a in (("labels", clusts), ("cluster_sizes", sizes), ("num_clusters", [K])):
+        np.save(os.path.join(outdir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def launch_plan(args, environ):
@@ -348,10 +371,12 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    # Per chain: the W + K steps once BEFORE the settle phase (reported as config.sweeps_per_s_before_settle), a settle phase
-    # (untimed: a short window right after the idle set-up does not see the clocks of a running chain — tools/ramp_probe.py;
-    # RC_BENCH_SETTLE_MS=0 turns both off), then W warm-up steps and RC_BENCH_WINDOWS (5) timed windows of exactly K steps.
-    # HIP events ride in the dispatch of the row-reduction launches of the timed windows (every launch for --steps < 64).
+    # Per chain: a settle phase (untimed: a short window right after the idle set-up does not see the clocks of a running chain —
+    # tools/ramp_probe.py; RC_BENCH_SETTLE_MS=0 turns it off), the chain restarted from the generating labels (how many sweeps the
+    # settle phase ran depends on the clock; the timed sweeps and their outputs must not), then W warm-up steps and ONE timed window
+    # of exactly K steps: the headline.  --full adds the W + K steps once BEFORE the settle phase (config.sweeps_per_s_before_settle)
+    # and, after the headline, RC_BENCH_WINDOWS (5) more windows of K steps with HIP events in the dispatch of the row-reduction
+    # launches (every launch for --steps < 64): the roofline and the spread of the windows.
     results = [None] * len(ctxs)
 
     def chain_job(ci):
@@ -367,16 +392,21 @@ def main():
         c, sd = ctxs[ci], seeds[ci]
         sweep, unsettled = 0, None
         if settle_ms > 0:
-            tu, sweep = timed_windows(c, sd, r, p, args.steps, args.warmup, 1, sync_all, sweep)
-            unsettled = tu[0]
-            sweep = settle(c, sd, r, p, settle_ms, sweep)
-        for _ in range(args.warmup):
-            c.gibbs_sweep(r, p, sd, sweep, blocking=False); sweep += 1
-        c.synchronize()
-        c.kernel_timing(enable=0 if os.environ.get('RC_BENCH_NO_TIMING') else time_every)
-        tw, sweep = timed_windows(c, sd, r, p, args.steps, 0, windows, sync_all, sweep)
-        bulk_ms, bulk_launches = c.kernel_timing(enable=0)
-        results[ci] = dict(times=tw, unsettled=unsettled, bulk_ms=bulk_ms, bulk_launches=bulk_launches, sweep=sweep, stats=c.sweep_stats())
+            if args.full:
+                tu, sweep = timed_windows(c, sd, r, p, args.steps, args.warmup, 1, sync_all, sweep)
+                unsettled = tu[0]
+            settle(c, sd, r, p, settle_ms, sweep)
+            c.set_state(truth)
+        th, sweep = timed_windows(c, sd, r, p, args.steps, args.warmup, 1, sync_all)
+        res = dict(time=th[0], unsettled=unsettled, stats=c.sweep_stats())
+        if args.dump_outputs and ci == 0:
+            res["state"] = c.get_state()
+        if args.full:
+            c.kernel_timing(enable=0 if os.environ.get('RC_BENCH_NO_TIMING') else time_every)
+            res["times"], sweep = timed_windows(c, sd, r, p, args.steps, 0, windows, sync_all, sweep)
+            res["bulk_ms"], res["bulk_launches"] = c.kernel_timing(enable=0)
+        res["sweep"] = sweep
+        results[ci] = res
 
     if len(ctxs) == 1:
         chain_job(0)
@@ -387,21 +417,22 @@ def main():
         if any(x is None for x in results):
             raise SystemExit("bench.py: a chain thread failed")
     # a window's time is the MAX over the chains (threads here, ranks below)
-    win = [max(res["times"][w] for res in results) for w in range(windows)]
-    unsettled_t = max(res["unsettled"] for res in results) if settle_ms > 0 else None
+    dt = max(res["time"] for res in results)
+    win = [max(res["times"][w] for res in results) for w in range(windows)] if args.full else []
+    unsettled_t = max(res["unsettled"] for res in results) if args.full and settle_ms > 0 else None
     if distributed:
-        tmax = torch.tensor(win + [unsettled_t or 0.0], dtype=torch.float64, device="cuda")
+        tmax = torch.tensor([dt] + win + [unsettled_t or 0.0], dtype=torch.float64, device="cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         vals = [float(x) for x in tmax.tolist()]
-        win, unsettled_t = vals[:windows], (vals[windows] if settle_ms > 0 else None)
-    dt = median(win)
-    bulk_ms, bulk_launches = results[0]["bulk_ms"], results[0]["bulk_launches"]
+        dt, win, unsettled_t = vals[0], vals[1:1 + len(win)], (vals[-1] if unsettled_t is not None else None)
     stats, sweep = results[0]["stats"], results[0]["sweep"]
     chain_seed = seeds[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, results[0]["state"])
 
     # same workload in the exact incremental mode (no row reduction while labels are stable) — reported as an extra
     inc_sweeps_per_s = None
-    if not os.environ.get("RC_BENCH_NO_INCREMENTAL"):
+    if args.full and not os.environ.get("RC_BENCH_NO_INCREMENTAL"):
         ctx.set_mode("incremental")
         ti, sweep = timed_windows(ctx, chain_seed, r, p, args.steps, args.warmup, 1, lambda: None, sweep)
         inc_sweeps_per_s = args.steps / ti[0]
@@ -411,27 +442,28 @@ def main():
     # LIBRARY's communicator (rc_comm_create / rc_comm_allreduce_counts: RCCL inside libredclust_hip.so; torch.distributed
     # only carries the 128-byte unique id; all ranks agree on the path first — chains.agreed_merge).  Also at N = 1: a real
     # communicator of size 1.  Single-process mode: one communicator over all devices (ncclCommInitAll), as rc_run_chains.
-    for c in ctxs:
-        c.record_sample(False)
-    with stdout_to_stderr():   # RCCL prints a version banner on the C stdout when its first communicator comes up
-        if single:
-            comm = rc.Comm(devices)
-            try:
-                total_samples, allreduce_ms = comm.allreduce_counts(ctxs, [1] * len(ctxs))
-            finally:
-                comm.close()
-            merge_path = "libredclust_hip.so rc_comm_allreduce_counts over ncclCommInitAll (one process, one context per device)"
-            nranks = len(devices)
-        else:
-            total_samples, allreduce_ms, merge_path = rc.agreed_merge(ctx, local_rank, 1)
-            nranks = dist.get_world_size() if distributed else 1
-    # every chain recorded one sample: each point co-clusters with itself once per chain, and the matrix is symmetric
-    counts = rc.device_counts_tensor(ctx, devices[0])
-    diag_ok = (bool((counts.diagonal() == world).all().item()) and bool((counts[:, :n] == counts[:, :n].T).all().item())
-               and total_samples == world)
+    if args.full:
+        for c in ctxs:
+            c.record_sample(False)
+        with stdout_to_stderr():   # RCCL prints a version banner on the C stdout when its first communicator comes up
+            if single:
+                comm = rc.Comm(devices)
+                try:
+                    total_samples, allreduce_ms = comm.allreduce_counts(ctxs, [1] * len(ctxs))
+                finally:
+                    comm.close()
+                merge_path = "libredclust_hip.so rc_comm_allreduce_counts over ncclCommInitAll (one process, one context per device)"
+                nranks = len(devices)
+            else:
+                total_samples, allreduce_ms, merge_path = rc.agreed_merge(ctx, local_rank, 1)
+                nranks = dist.get_world_size() if distributed else 1
+        # every chain recorded one sample: each point co-clusters with itself once per chain, and the matrix is symmetric
+        counts = rc.device_counts_tensor(ctx, devices[0])
+        diag_ok = (bool((counts.diagonal() == world).all().item()) and bool((counts[:, :n] == counts[:, :n].T).all().item())
+                   and total_samples == world)
 
     # ---- the other figures: rank 0 / chain 0 only, on its own device ---------------------------------------------------
-    extras = rank == 0
+    extras = rank == 0 and args.full
     dev0 = devices[0]
     for c in ctxs[1:]:
         c.close()
@@ -613,45 +645,7 @@ def main():
         esz = BITS / 8.0
         derived = read_bytes < 1.5 * (n * (n + 1) / 2 if kernel_family != "k_bulk" else n * n) * esz
         packed48 = kernel_name.startswith("k_bulk_syml2<true, true")
-        # a sweep is priced at 2·n²·sizeof (D and logD read once each), or n²·sizeof "if the build recomputes log on
-        # the fly instead of staging logD".  This design reads less than either (symmetry, 48-bit packing), so that pricing is an
-        # EQUIVALENT-DATAFLOW rate, reported under that name and never as a fraction of a bandwidth peak.
-        survey_bytes = (1.0 if derived else 2.0) * n * n * esz
-        full_bytes = 2.0 * n * n * esz
         value = world * args.steps / dt
-        period_s = dt / args.steps
-        bulk_avg_ms = bulk_ms / max(bulk_launches, 1)
-        achieved = read_bytes / (bulk_avg_ms * 1e-3) / 1e9 if bulk_launches else None        # bytes the kernel reads ÷ its mean launch duration
-        tag = kernel_name.replace("<", "_").replace(">", "").replace(", ", "_").replace(" ", "")
-        # rocprofv3 --pmc results of this same command, collected OFFLINE (tools/prof_r04.sh) and committed: bytes at the L2's memory
-        # side per launch (FETCH_SIZE x 2 on gfx950 + WRITE_SIZE, separate passes) and the instruction counters of the kernel
-        traffic_rec, traffic_source = profile_json(f"pmc_traffic_n{n}_{tag}.json", f"pmc_traffic_n{n}_{kernel_family}.json") if BITS == 64 else (None, None)
-        counters, counters_source = profile_json(f"counters_n{n}_{tag}.json") if BITS == 64 else (None, None)
-        working_set_fits_mall = read_bytes <= 256 * 2 ** 20
-        if kernel_name.startswith("k_bulk_syml2") and working_set_fits_mall:
-            bound = "valu_issue+memory_side_atomics"
-            served = ("Infinity Cache: the %.0f MB the kernel reads per launch stay resident in the 256 MiB last-level cache from one sweep to the next "
-                      "(FETCH_SIZE counts those hits at the L2's memory side); HBM itself is close to idle" % (read_bytes / 1e6))
-        else:
-            bound = "hbm"
-            served = "HBM" if not working_set_fits_mall else "Infinity Cache / HBM"
-        compute = None
-        if counters and bulk_launches:
-            # VALU issue time of one launch: wave instructions x measured cycles per instruction and SIMD ÷ (SIMDs x clock)
-            # (tools/valu_rate.hip: 1.9 cycles for 32-bit ALU ops with >= 3 waves per SIMD, 3.0-3.9 for 64-bit integer, FP64, DPP
-            # and conversion instructions; the kernel's mix is priced at the figure the counters file states)
-            simds = 4 * 256
-            issue_s = counters["SQ_INSTS_VALU"] * counters["cycles_per_valu_inst"] / (simds * counters["clock_ghz"] * 1e9)
-            compute = {"valu_wave_insts_per_launch": counters["SQ_INSTS_VALU"], "salu_wave_insts_per_launch": counters.get("SQ_INSTS_SALU"),
-                       "lds_bank_conflict_rate": (counters["SQ_LDS_BANK_CONFLICT"] / counters["SQ_LDS_IDX_ACTIVE"]) if counters.get("SQ_LDS_IDX_ACTIVE") else None,
-                       "atomic_bytes_per_launch": counters.get("WRITE_SIZE_bytes"), "cycles_per_valu_inst": counters["cycles_per_valu_inst"],
-                       "simds": simds, "clock_ghz": counters["clock_ghz"], "valu_issue_us_per_launch": issue_s * 1e6,
-                       "frac_of_launch": issue_s / (bulk_avg_ms * 1e-3), "source": counters_source}
-        ceiling = None
-        try:   # also against a streaming-read ceiling measured on this box, now (2 GiB: HBM, not the cache)
-            ceiling = rc.measure_read_ceiling(dev0, 2048, 5)
-        except Exception:   # noqa: BLE001
-            pass
         dtype = (f"u48-packed fixed-point D (quantum 2^-47 of the largest entry; the {BITS}-bit master copy stays in HBM), logD = degree-4 table log of it "
                  "rounded to fixed point (|error| <= 2^-eL + 2.6e-13 + entry rounding), i64 exact sums, f64 scores") if packed48 else \
                 f"i{BITS} fixed-point storage of D" + (" (logD derived: table log)" if derived else " and logD") + ", i64 exact sums, f64 scores"
@@ -664,44 +658,90 @@ def main():
                                    "numMH=0 Gibbs sweep, init = generating labels (stationary), r=1 p=0.5",
                        "chains": world, "n": n, "K": K, "parallelism": f"chains x{world}",
                        "launch": {"rank": "one process per GPU (torch.distributed.run)", "single": "one process, one host thread + context per GPU (RC_BENCH_SINGLE_PROCESS=1)"}["single" if single else "rank"] if world > 1 else "one process, one GPU",
-                       "rccl_ranks": nranks,
                        "slot_capacity": kcap_info, "slot_capacity_note": "kcap = 0 at rc_create (the library default, what runsampler and the Julia glue pass): sized from the first state, grows on demand" if kcap == 0 else f"RC_BENCH_KCAP={kcap}",
-                       "value_is": f"median of {windows} windows of exactly {args.steps} steps (each bracketed by barrier + device synchronize)",
-                       "windows_sweeps_per_s": [world * args.steps / x for x in win],
-                       "windows_min_max_sweeps_per_s": [world * args.steps / max(win), world * args.steps / min(win)],
-                       "timed_region_s": sum(win),
-                       "settle_ms": settle_ms, "sweeps_per_s_before_settle": (world * args.steps / unsettled_t) if unsettled_t else None,
-                       "settle_note": "untimed sweeps of the same workload before the warm-up steps (device clocks of a running chain; RC_BENCH_SETTLE_MS=0 disables)"},
+                       "value_is": f"one window of exactly {args.steps} steps after {args.warmup} warm-up steps (bracketed by barrier + device synchronize)",
+                       "timed_region_s": dt,
+                       "settle_ms": settle_ms,
+                       "settle_note": "untimed sweeps of the same workload before the warm-up steps (device clocks of a running chain; RC_BENCH_SETTLE_MS=0 disables); "
+                                      "the chain then restarts from the generating labels"},
             "logD": "derived on the fly (table log of the fixed-point D)" if derived else "stored",
-            "kcap512_sweeps_per_s": kcap512,
             "label_changes_last_sweep": stats["n_changes"], "K_final": stats["K"],
-            "moving_regime": moving,
-            "reference_default_options": defaults,
-            "other_configs": other,
-            "incremental_mode_sweeps_per_s_rank0": inc_sweeps_per_s,
-            "coclustering_allreduce_ms": allreduce_ms, "coclustering_merge_path": merge_path, "coclustering_diag_ok": diag_ok,
-            # Roofline of the dominant kernel — physical figures only.  achieved = the bytes this kernel reads per launch ÷ its mean
-            # launch duration; frac = achieved ÷ the 8 TB/s HBM peak (<= 1 by construction, reproducible from the rocprofv3 kernel
-            # stats under profiles/); `bound` names what limits the kernel; `served_from` the memory level its bytes come from.
-            "roofline": {"kernel": kernel_name, "bound": bound, "served_from": served,
-                         "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": (achieved / HBM_PEAK_GBPS) if achieved else None,
-                         "bytes_read_per_launch": read_bytes, "avg_launch_ms": bulk_avg_ms, "launches": bulk_launches, "timed_every_nth_launch": time_every,
-                         "per_sweep_period": {"ms": period_s * 1e3, "GBps": read_bytes / period_s / 1e9, "frac": read_bytes / period_s / 1e9 / HBM_PEAK_GBPS,
-                                              "note": "the same bytes ÷ ms_per_step (launches of consecutive sweeps overlap on two streams, so a launch lasts longer than a period)"},
-                         "traffic": traffic_rec["k_bulk_hbm_bytes_per_launch"] if traffic_rec else None, "traffic_source": traffic_source,
-                         "traffic_note": "bytes at the L2's memory side per launch (rocprofv3 --pmc FETCH_SIZE x 2 + WRITE_SIZE, separate passes, collected offline with this command); Infinity-Cache hits are counted there",
-                         "compute": compute,
-                         "measured_streaming_read_GBps": ceiling, "frac_of_measured_streaming_read": (achieved / ceiling) if achieved and ceiling else None,
-                         # SURVEY.md §8(d)'s algorithmic pricing of the same launches (n²·sizeof per sweep with logD derived, 2·n²·sizeof stored):
-                         # what a kernel that read every entry of the matrices would have to stream to keep up — NOT a bandwidth
-                         "equivalent_dataflow_GBps": (survey_bytes / (bulk_avg_ms * 1e-3) / 1e9) if bulk_launches else None,
-                         "equivalent_dataflow_bytes_per_sweep": survey_bytes,
-                         "equivalent_dataflow_GBps_per_sweep_period": survey_bytes / period_s / 1e9,
-                         "reference_dataflow_bytes_per_sweep": full_bytes,
-                         "event_pair_overhead_ms_subtracted": ctx.event_overhead_ms()},
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(D, P, truth, r, p)
+        if args.full:
+            bulk_ms, bulk_launches = results[0]["bulk_ms"], results[0]["bulk_launches"]
+            period_s = dt / args.steps
+            # a sweep is priced at 2·n²·sizeof (D and logD read once each), or n²·sizeof "if the build recomputes log on
+            # the fly instead of staging logD".  This design reads less than either (symmetry, 48-bit packing), so that pricing is an
+            # EQUIVALENT-DATAFLOW rate, reported under that name and never as a fraction of a bandwidth peak.
+            survey_bytes = (1.0 if derived else 2.0) * n * n * esz
+            full_bytes = 2.0 * n * n * esz
+            bulk_avg_ms = bulk_ms / max(bulk_launches, 1)
+            achieved = read_bytes / (bulk_avg_ms * 1e-3) / 1e9 if bulk_launches else None        # bytes the kernel reads ÷ its mean launch duration
+            tag = kernel_name.replace("<", "_").replace(">", "").replace(", ", "_").replace(" ", "")
+            # rocprofv3 --pmc results of this same command, collected OFFLINE (tools/prof_r04.sh) and committed: bytes at the L2's memory
+            # side per launch (FETCH_SIZE x 2 on gfx950 + WRITE_SIZE, separate passes) and the instruction counters of the kernel
+            traffic_rec, traffic_source = profile_json(f"pmc_traffic_n{n}_{tag}.json", f"pmc_traffic_n{n}_{kernel_family}.json") if BITS == 64 else (None, None)
+            counters, counters_source = profile_json(f"counters_n{n}_{tag}.json") if BITS == 64 else (None, None)
+            working_set_fits_mall = read_bytes <= 256 * 2 ** 20
+            if kernel_name.startswith("k_bulk_syml2") and working_set_fits_mall:
+                bound = "valu_issue+memory_side_atomics"
+                served = ("Infinity Cache: the %.0f MB the kernel reads per launch stay resident in the 256 MiB last-level cache from one sweep to the next "
+                          "(FETCH_SIZE counts those hits at the L2's memory side); HBM itself is close to idle" % (read_bytes / 1e6))
+            else:
+                bound = "hbm"
+                served = "HBM" if not working_set_fits_mall else "Infinity Cache / HBM"
+            compute = None
+            if counters and bulk_launches:
+                # VALU issue time of one launch: wave instructions x measured cycles per instruction and SIMD ÷ (SIMDs x clock)
+                # (tools/valu_rate.hip: 1.9 cycles for 32-bit ALU ops with >= 3 waves per SIMD, 3.0-3.9 for 64-bit integer, FP64, DPP
+                # and conversion instructions; the kernel's mix is priced at the figure the counters file states)
+                simds = 4 * 256
+                issue_s = counters["SQ_INSTS_VALU"] * counters["cycles_per_valu_inst"] / (simds * counters["clock_ghz"] * 1e9)
+                compute = {"valu_wave_insts_per_launch": counters["SQ_INSTS_VALU"], "salu_wave_insts_per_launch": counters.get("SQ_INSTS_SALU"),
+                           "lds_bank_conflict_rate": (counters["SQ_LDS_BANK_CONFLICT"] / counters["SQ_LDS_IDX_ACTIVE"]) if counters.get("SQ_LDS_IDX_ACTIVE") else None,
+                           "atomic_bytes_per_launch": counters.get("WRITE_SIZE_bytes"), "cycles_per_valu_inst": counters["cycles_per_valu_inst"],
+                           "simds": simds, "clock_ghz": counters["clock_ghz"], "valu_issue_us_per_launch": issue_s * 1e6,
+                           "frac_of_launch": issue_s / (bulk_avg_ms * 1e-3), "source": counters_source}
+            ceiling = None
+            try:   # also against a streaming-read ceiling measured on this box, now (2 GiB: HBM, not the cache)
+                ceiling = rc.measure_read_ceiling(dev0, 2048, 5)
+            except Exception:   # noqa: BLE001
+                pass
+            out["config"].update({
+                "rccl_ranks": nranks,
+                "windows_sweeps_per_s": [world * args.steps / x for x in win],
+                "windows_min_max_sweeps_per_s": [world * args.steps / max(win), world * args.steps / min(win)],
+                "windows_note": f"{windows} more windows of exactly {args.steps} steps after the headline one, HIP events in the dispatch (roofline)",
+                "sweeps_per_s_before_settle": (world * args.steps / unsettled_t) if unsettled_t else None})
+            out.update({
+                "kcap512_sweeps_per_s": kcap512,
+                "moving_regime": moving,
+                "reference_default_options": defaults,
+                "other_configs": other,
+                "incremental_mode_sweeps_per_s_rank0": inc_sweeps_per_s,
+                "coclustering_allreduce_ms": allreduce_ms, "coclustering_merge_path": merge_path, "coclustering_diag_ok": diag_ok,
+                # Roofline of the dominant kernel — physical figures only.  achieved = the bytes this kernel reads per launch ÷ its mean
+                # launch duration; frac = achieved ÷ the 8 TB/s HBM peak (<= 1 by construction, reproducible from the rocprofv3 kernel
+                # stats under profiles/); `bound` names what limits the kernel; `served_from` the memory level its bytes come from.
+                "roofline": {"kernel": kernel_name, "bound": bound, "served_from": served,
+                             "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": (achieved / HBM_PEAK_GBPS) if achieved else None,
+                             "bytes_read_per_launch": read_bytes, "avg_launch_ms": bulk_avg_ms, "launches": bulk_launches, "timed_every_nth_launch": time_every,
+                             "per_sweep_period": {"ms": period_s * 1e3, "GBps": read_bytes / period_s / 1e9, "frac": read_bytes / period_s / 1e9 / HBM_PEAK_GBPS,
+                                                  "note": "the same bytes ÷ ms_per_step (launches of consecutive sweeps overlap on two streams, so a launch lasts longer than a period)"},
+                             "traffic": traffic_rec["k_bulk_hbm_bytes_per_launch"] if traffic_rec else None, "traffic_source": traffic_source,
+                             "traffic_note": "bytes at the L2's memory side per launch (rocprofv3 --pmc FETCH_SIZE x 2 + WRITE_SIZE, separate passes, collected offline with this command); Infinity-Cache hits are counted there",
+                             "compute": compute,
+                             "measured_streaming_read_GBps": ceiling, "frac_of_measured_streaming_read": (achieved / ceiling) if achieved and ceiling else None,
+                             # SURVEY.md §8(d)'s algorithmic pricing of the same launches (n²·sizeof per sweep with logD derived, 2·n²·sizeof stored):
+                             # what a kernel that read every entry of the matrices would have to stream to keep up — NOT a bandwidth
+                             "equivalent_dataflow_GBps": (survey_bytes / (bulk_avg_ms * 1e-3) / 1e9) if bulk_launches else None,
+                             "equivalent_dataflow_bytes_per_sweep": survey_bytes,
+                             "equivalent_dataflow_GBps_per_sweep_period": survey_bytes / period_s / 1e9,
+                             "reference_dataflow_bytes_per_sweep": full_bytes,
+                             "event_pair_overhead_ms_subtracted": ctx.event_overhead_ms()},
+            })
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(D, P, truth, r, p)
         print(json.dumps(out))
     ctx.close()
     if distributed:

@@ -1,6 +1,7 @@
 #!/bin/bash
 # PMC counters of the row-reduction kernel and the resolver (separate passes; kernel-trace only).  usage: tools/pmc_r3.sh <tag> [VAR=value ...]
 # (program directly after `--`: no env / bash hop under rocprofv3; the variables are exported here)
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 TAG=$1; shift
 for kv in "$@"; do export "$kv"; done
@@ -9,7 +10,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 for grp in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_INSTS_VMEM_WR SQ_INSTS_SMEM" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" "SQ_INST_CYCLES_SALU SQ_WAVES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS" "FETCH_SIZE" "WRITE_SIZE"; do
   name=$(echo $grp | tr ' ' '_' | cut -c1-40)
-  rocprofv3 --kernel-trace --output-format csv --pmc $grp -d $OUT/$name -o r -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --steps 30 --warmup 5 > $OUT/$name.log 2>&1
+  rocprofv3 --kernel-trace --output-format csv --pmc $grp -d $OUT/$name -o r -- python3 $R/bench.py --full --no-cpu-baseline --steps 30 --warmup 5 > $OUT/$name.log 2>&1
 done
 python3 - <<PY
 import glob, csv, collections

@@ -5,13 +5,13 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r03; mkdir -p $O
 export RC_BENCH_NO_INCREMENTAL=1 RC_BENCH_NO_DEFAULTS=1 RC_BENCH_NO_KCAP512=1
 # 1. kernel-trace stats: headline leg alone, then headline + moving regime
-RC_BENCH_NO_MOVING=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o b -- python3 $R/bench.py --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_headline_under_rocprof.json 2> $O/stats.err
+RC_BENCH_NO_MOVING=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o b -- python3 $R/bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_headline_under_rocprof.json 2> $O/stats.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_moving -o b -- python3 $R/tools/moving_rate.py > $O/moving_under_rocprof.json 2> $O/stats_moving.err
 # 2. PMC, one group per pass: the headline leg (k_bulk_syml2 + the stationary k_resolve)
 export RC_BENCH_NO_TIMING=1 RC_BENCH_WINDOWS=2
 for grp in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_INSTS_SMEM" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" "SQ_WAVES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_SALU"; do
   name=$(echo $grp | tr ' ' '_' | cut -c1-40)
-  RC_BENCH_NO_MOVING=1 rocprofv3 --kernel-trace --output-format csv --pmc $grp -d $O/pmc_headline_$name -o p -- python3 $R/bench.py --no-cpu-baseline --steps 30 --warmup 5 > $O/pmc_headline_$name.log 2>&1
+  RC_BENCH_NO_MOVING=1 rocprofv3 --kernel-trace --output-format csv --pmc $grp -d $O/pmc_headline_$name -o p -- python3 $R/bench.py --full --no-cpu-baseline --steps 30 --warmup 5 > $O/pmc_headline_$name.log 2>&1
   rocprofv3 --kernel-trace --output-format csv --pmc $grp -d $O/pmc_moving_$name -o p -- python3 $R/tools/moving_rate.py > $O/pmc_moving_$name.log 2>&1
 done
 # 3. FETCH_SIZE / WRITE_SIZE calibration on known byte counts

@@ -232,6 +232,21 @@ typedef struct rc_wb_stats {
 } rc_wb_stats;
 int32_t rc_within_between(rc_ctx *ctx, rc_wb_stats *out);
 
+/* kmedoids(D, k; maxiter, tol) of Clustering.jl with k-medoids++ seeding by costs, as fitprior (src/prior.jl:22-128) and
+ * runsampler's default start (src/mcmc.jl:516-527) call it, on the context's fixed-point D in the caller's point order
+ * (the algorithm as restated, its tie rules and the integer weighted draw).  Sums and comparisons are exact
+ * integers, so the result is a pure function of (D, k, seed).  Uniforms: Philox keyed (seed_lo, seed_hi ^ 0x4B4D4544),
+ * counter (step, k, 0, 0).  Converged when |totalcost - previous| < tol (units of D).  Works on any context (64- or 32-bit
+ * storage, from D or from points, with or without a state) and leaves the chain state, the layout and the co-clustering
+ * counts untouched.  RC_ERR_DOMAIN when a group becomes empty (a nonzero diagonal entry) or every seeding weight is zero. */
+int32_t rc_kmedoids(rc_ctx *ctx, int64_t k, int64_t maxiter, double tol, uint64_t seed,
+                    int64_t *assignments /* n, 1-based */, int64_t *medoids /* k, 1-based */, double *totalcost,
+                    int64_t *iterations, uint8_t *converged);
+/* rc_kmedoids for every k in kmin..kmax in one batched job (the per-k loop of fitprior, src/prior.jl:63-70): entry k - kmin
+ * of each array (length kmax - kmin + 1) equals rc_kmedoids(k) with the same seed, bit for bit. */
+int32_t rc_kmedoids_scan(rc_ctx *ctx, int64_t kmin, int64_t kmax, int64_t maxiter, double tol, uint64_t seed,
+                         double *totalcost, int64_t *iterations, uint8_t *converged);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * The iteration loop of runsampler (src/mcmc.jl:533-556) as native host code: per iteration sample_r!, sample_p!
  * (src/mcmc.jl:80-155, on the build's counter-based scalar stream — DESIGN.md), sample_labels! (numMH split–merge

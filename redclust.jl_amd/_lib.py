@@ -8,6 +8,8 @@ import subprocess
 
 import numpy as np
 
+from .types import KmedoidsResult
+
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
@@ -76,6 +78,7 @@ class RcSweepStats(C.Structure):
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, "redclust_hip.hip"), os.path.join(CSRC, "pointestimate.inc.hip"),
+            os.path.join(CSRC, "kmedoids.inc.hip"),
             os.path.join(CSRC, "chain.inc.hip"), os.path.join(CSRC, "chains.inc.hip"), HEADER]
     if not force and os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(s) for s in srcs):
         return SO
@@ -156,6 +159,10 @@ SIGNATURES = {
     "rc_loss_matrix": (C.c_int32, [C.c_int32, _ip, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                    C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "rc_pair_measures": (C.c_int32, [C.c_int32, _ip, _ip, C.c_int64, C.POINTER(RcPairMeasures)]),
+    "rc_kmedoids": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_uint64, _ip, _ip, C.POINTER(C.c_double),
+                                C.POINTER(C.c_int64), C.POINTER(C.c_uint8)]),
+    "rc_kmedoids_scan": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_uint64, _dp, _ip,
+                                     np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")]),
     "rc_layout_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rc_event_overhead_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "rc_kernel_timing": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -427,6 +434,23 @@ class Context:
         o = RcWbStats()
         self._chk(self.L.rc_within_between(self.h, C.byref(o)))
         return {k: getattr(o, k) for k, _ in RcWbStats._fields_}
+
+    def kmedoids(self, k, maxiter=200, tol=1e-8, seed=0) -> KmedoidsResult:
+        """rc_kmedoids: Clustering.jl's kmedoids(D, k; maxiter, tol) (k-medoids++ seeding) on the device's D; the state is untouched."""
+        a = np.zeros(self.n, np.int64)
+        m = np.zeros(max(int(k), 0), np.int64)
+        tc, it, cv = C.c_double(), C.c_int64(), C.c_uint8()
+        self._chk(self.L.rc_kmedoids(self.h, int(k), int(maxiter), float(tol), int(seed) & 0xFFFFFFFFFFFFFFFF, a,
+                                     m if m.size else np.zeros(1, np.int64), C.byref(tc), C.byref(it), C.byref(cv)))
+        return KmedoidsResult(medoids=m, assignments=a, totalcost=tc.value, iterations=int(it.value), converged=bool(cv.value))
+
+    def kmedoids_scan(self, kmin, kmax, maxiter=200, tol=1e-8, seed=0) -> dict:
+        """rc_kmedoids_scan: totalcost, iterations and converged of kmedoids(k) for k = kmin..kmax (arrays indexed by k - kmin)."""
+        m = max(int(kmax) - int(kmin) + 1, 1)
+        tc, it, cv = np.zeros(m), np.zeros(m, np.int64), np.zeros(m, np.uint8)
+        self._chk(self.L.rc_kmedoids_scan(self.h, int(kmin), int(kmax), int(maxiter), float(tol), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                          tc, it, cv))
+        return dict(totalcost=tc, iterations=it, converged=cv.astype(bool))
 
     def layout_info(self):
         """(layouts built so far, label runs in the internal point order)"""

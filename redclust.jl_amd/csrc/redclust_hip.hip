@@ -7538,5 +7538,6 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 }
 
 #include "pointestimate.inc.hip"
+#include "kmedoids.inc.hip"
 #include "chain.inc.hip"
 #include "chains.inc.hip"

@@ -9,8 +9,10 @@ in the reference, both log-likelihoods on the device.  `splitmerge="as_written"`
 literally, including its rebinding quirk (after an accepted proposal the iteration leaves
 the caller's labels untouched); `splitmerge="intended"` keeps accepted proposals and sweeps them.
 
-Not in this build: fitprior (params must be given) and the k-medoids initialisation (init must be
-given)."""
+Without params, runsampler fits them with fitprior(data.D, "k-medoids", diss=True) (src/mcmc.jl:516-518; prior.py);
+without init, it starts from the k-medoids labels of min(maxK, K_initial) clusters (K_initial when maxK = 0) and draws
+r ~ Gamma(η, 1/σ), p ~ Beta(u, v) (src/mcmc.jl:519-527).  Both run on the context the sampler stages, so the matrix is
+staged once."""
 from __future__ import annotations
 
 import math
@@ -94,10 +96,6 @@ def runsampler(data: MCMCData, options: MCMCOptionsList | None = None, params: P
     if engine not in ("native", "python"):
         raise ValueError("engine must be 'native' or 'python'")
     options = options or MCMCOptionsList()
-    if params is None:
-        raise NotImplementedError("fitprior is outside this build's scope (SURVEY.md §8): pass params explicitly")
-    if init is None:
-        raise NotImplementedError("k-medoids initialisation is outside this build's scope (SURVEY.md §8): pass init")
     if splitmerge not in ("as_written", "intended"):
         raise ValueError("splitmerge must be 'as_written' or 'intended'")
     out = print if verbose else (lambda *a, **k: None)
@@ -109,6 +107,14 @@ def runsampler(data: MCMCData, options: MCMCOptionsList | None = None, params: P
         ctx = (Context.from_points(data.points, device=device, kcap=kcap) if data.points is not None
                else Context(data.D, device=device, kcap=kcap))
     try:
+        if params is None or init is None:
+            from .prior import KMED_STREAM_INIT, fitprior, kmedoids_stream_seed
+            if params is None:                                                     # mcmc.jl:516-518
+                params = fitprior(data, "k-medoids", True, verbose=verbose, seed=seed, device=device, ctx=ctx)
+            if init is None:                                                       # mcmc.jl:519-527
+                k0 = min(params.maxK, params.K_initial) if params.maxK > 0 else params.K_initial
+                clusts = ctx.kmedoids(k0, maxiter=1000, seed=kmedoids_stream_seed(seed, KMED_STREAM_INIT)).assignments
+                init = MCMCState(clusts, rng.gamma(params.eta, 1.0 / params.sigma), rng.beta(params.u, params.v))
         ctx.set_params(**params.as_dict())
         ctx.set_state(init.clusts)
         ctx.set_mode(mode)

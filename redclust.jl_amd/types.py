@@ -186,3 +186,14 @@ class MCMCResult:
 
     def __repr__(self):
         return f"MCMC result with {self.options.numsamples} samples"
+
+
+@dataclass
+class KmedoidsResult:
+    """Clustering.jl's KmedoidsResult: medoids (k point indices, 1-based), assignments (n, 1-based into medoids),
+    totalcost, iterations, converged."""
+    medoids: np.ndarray
+    assignments: np.ndarray
+    totalcost: float
+    iterations: int
+    converged: bool

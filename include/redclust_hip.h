@@ -246,6 +246,21 @@ int32_t rc_kmedoids(rc_ctx *ctx, int64_t k, int64_t maxiter, double tol, uint64_
  * of each array (length kmax - kmin + 1) equals rc_kmedoids(k) with the same seed, bit for bit. */
 int32_t rc_kmedoids_scan(rc_ctx *ctx, int64_t kmin, int64_t kmax, int64_t maxiter, double tol, uint64_t seed,
                          double *totalcost, int64_t *iterations, uint8_t *converged);
+/* The scan above plus, for every k, the within / between split of its final assignment (fitprior2's A_k and B_k,
+ * src/prior.jl:211-217): split[k - kmin] equals what rc_within_between returns after rc_set_state with that assignment, bit
+ * for bit, and totalcost / iterations / converged equal the plain scan's.  Exact integer sums over the pairs of every group
+ * on the device; the chain state, the layout and the co-clustering counts stay untouched. */
+int32_t rc_kmedoids_scan_split(rc_ctx *ctx, int64_t kmin, int64_t kmax, int64_t maxiter, double tol, uint64_t seed,
+                               double *totalcost, int64_t *iterations, uint8_t *converged,
+                               rc_wb_stats *split /* kmax - kmin + 1 */);
+
+/* sampleK (src/prior.jl:316-338) for m samples whose r[i] ~ Gamma(eta, 1/sigma) and p[i] ~ Beta(u, v) the caller has
+ * drawn: the Gumbel-max draw over the n log-probabilities of every sample on the device.  Uniforms: Philox keyed
+ * (seed_lo, seed_hi ^ 0x534D504B), counter (K, i_lo, i_hi, 0); sample i is a pure function of (n, r[i], p[i], seed, i).
+ * A sample with no score above -inf (p = 1) returns K = 1.  n in 1..2^30.  K_out: m values in 1..n.  kernel_ms (may be
+ * NULL): device time of the launches.  No context: errors are read with a NULL context. */
+int32_t rc_sample_k(int32_t device, int64_t n, int64_t m, const double *r, const double *p, uint64_t seed,
+                    int64_t *K_out /* m, 1-based */, double *kernel_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * The iteration loop of runsampler (src/mcmc.jl:533-556) as native host code: per iteration sample_r!, sample_p!

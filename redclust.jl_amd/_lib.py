@@ -79,7 +79,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, "redclust_hip.hip"), os.path.join(CSRC, "pointestimate.inc.hip"),
             os.path.join(CSRC, "kmedoids.inc.hip"),
-            os.path.join(CSRC, "chain.inc.hip"), os.path.join(CSRC, "chains.inc.hip"), HEADER]
+            os.path.join(CSRC, "chain.inc.hip"), os.path.join(CSRC, "chains.inc.hip"), os.path.join(CSRC, "samplek.inc.hip"), HEADER]
     if not force and os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(s) for s in srcs):
         return SO
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-o", SO, srcs[0]]
@@ -163,6 +163,9 @@ SIGNATURES = {
                                 C.POINTER(C.c_int64), C.POINTER(C.c_uint8)]),
     "rc_kmedoids_scan": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_uint64, _dp, _ip,
                                      np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")]),
+    "rc_kmedoids_scan_split": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_uint64, _dp, _ip,
+                                           np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS"), C.POINTER(RcWbStats)]),
+    "rc_sample_k": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, _dp, _dp, C.c_uint64, _ip, C.POINTER(C.c_double)]),
     "rc_layout_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rc_event_overhead_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "rc_kernel_timing": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -444,13 +447,22 @@ class Context:
                                      m if m.size else np.zeros(1, np.int64), C.byref(tc), C.byref(it), C.byref(cv)))
         return KmedoidsResult(medoids=m, assignments=a, totalcost=tc.value, iterations=int(it.value), converged=bool(cv.value))
 
-    def kmedoids_scan(self, kmin, kmax, maxiter=200, tol=1e-8, seed=0) -> dict:
-        """rc_kmedoids_scan: totalcost, iterations and converged of kmedoids(k) for k = kmin..kmax (arrays indexed by k - kmin)."""
+    def kmedoids_scan(self, kmin, kmax, maxiter=200, tol=1e-8, seed=0, split=False) -> dict:
+        """rc_kmedoids_scan: totalcost, iterations and converged of kmedoids(k) for k = kmin..kmax (arrays indexed by k - kmin).
+        split=True (rc_kmedoids_scan_split): also every k's within / between split of its final assignment, as within_between
+        would return it — count_within, sum_within, sumlog_within and the same three _between, one array each."""
         m = max(int(kmax) - int(kmin) + 1, 1)
         tc, it, cv = np.zeros(m), np.zeros(m, np.int64), np.zeros(m, np.uint8)
-        self._chk(self.L.rc_kmedoids_scan(self.h, int(kmin), int(kmax), int(maxiter), float(tol), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                          tc, it, cv))
-        return dict(totalcost=tc, iterations=it, converged=cv.astype(bool))
+        args = (self.h, int(kmin), int(kmax), int(maxiter), float(tol), int(seed) & 0xFFFFFFFFFFFFFFFF, tc, it, cv)
+        if not split:
+            self._chk(self.L.rc_kmedoids_scan(*args))
+            return dict(totalcost=tc, iterations=it, converged=cv.astype(bool))
+        wb = (RcWbStats * m)()
+        self._chk(self.L.rc_kmedoids_scan_split(*args, wb))
+        out = dict(totalcost=tc, iterations=it, converged=cv.astype(bool))
+        for k, ty in RcWbStats._fields_:
+            out[k] = np.array([getattr(x, k) for x in wb], dtype=np.int64 if ty is C.c_int64 else np.float64)
+        return out
 
     def layout_info(self):
         """(layouts built so far, label runs in the internal point order)"""
@@ -599,6 +611,22 @@ def loss_matrix(samples, loss: int, device: int = 0, want_matrix: bool = True):
     if rc != RC_OK:
         raise RedClustHIPError(rc, L.rc_last_error(None).decode())
     return M, cs, int(am.value), float(ms.value)
+
+
+def sample_k(n: int, r, p, seed: int = 0, device: int = 0):
+    """rc_sample_k: (K of every sample as int64 in 1..n, kernel ms) for the caller's draws r[i], p[i] — the device part of
+    sampleK (prior.py)."""
+    L = lib()
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    if r.ndim != 1 or r.shape != p.shape:
+        raise ValueError("r and p must be vectors of the same length")
+    K = np.zeros(len(r), np.int64)
+    ms = C.c_double()
+    rc = L.rc_sample_k(int(device), int(n), len(r), r, p, int(seed) & 0xFFFFFFFFFFFFFFFF, K, C.byref(ms))
+    if rc != RC_OK:
+        raise _error(rc, L.rc_last_error(None).decode())
+    return K, float(ms.value)
 
 
 def pair_measures(a, b, device: int = 0) -> dict:

@@ -41,6 +41,10 @@ struct Ws {
     int *iter, *flags;     // [C]
     unsigned *active;      // [maxiter + 1] runs still active after round r
     unsigned *err;         // OR of the RC_KMED_ERR_* bits of every slot
+    // per-k split (rc_kmedoids_scan_split only; null otherwise)
+    unsigned long long *acc;  // [C + 2][4]: within sums of slot s (D hi, D lo, logD hi, logD lo: RC_LO_BITS halves as
+                              // k_blocksums); row C the upper triangle's totals, row C + 1 (logD's diagonal hi, lo, 0, 0)
+    long long *pairs;         // [C] within pairs: Σ_g n_g (n_g - 1) / 2
 };
 
 // Philox4x32-10, key (seed_lo, seed_hi ^ "KMED"), counter (step, k, 0, 0): 53 random bits
@@ -114,6 +118,41 @@ __device__ long long assign_all(const T *__restrict__ D, int n, int ld, const in
         sum += best;
     }
     return block_sum(sum, red);
+}
+
+// The groups of assignment a (k medoids): sizes cnt, offsets off (exclusive scan over the k sizes, each thread owning a
+// contiguous run of groups; off[k] = n), scatter cursors cur and the members grouped by medoid (their order inside a group
+// depends on timing: every use of it is order-free).  Returns whether some group is empty (the same answer in every thread).
+// Called by every thread of the block; wtot: [RC_KMED_NW] and flag: one int, both in LDS.
+__device__ bool group_points(const int *a, int n, int k, int *cnt, int *off, int *cur, int *mem, int *wtot, int *flag)
+{
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (threadIdx.x == 0) *flag = 0;
+    for (int g = threadIdx.x; g < k; g += RC_KMED_T) cnt[g] = 0;
+    __syncthreads();
+    for (int j = threadIdx.x; j < n; j += RC_KMED_T) atomicAdd(&cnt[a[j]], 1);
+    __syncthreads();
+    const int per = (k + RC_KMED_T - 1) / RC_KMED_T, g0 = min(k, (int)threadIdx.x * per), g1 = min(k, g0 + per);
+    int local = 0, my_empty = 0;
+    for (int g = g0; g < g1; ++g) { local += cnt[g]; my_empty |= cnt[g] == 0; }
+    if (my_empty) *flag = 1;
+    int incl = local;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int x = __shfl_up(incl, d);
+        if (lane >= d) incl += x;
+    }
+    if (lane == 63) wtot[wid] = incl;
+    __syncthreads();
+    const bool empty = *flag != 0;
+    int run = incl - local;
+    for (int q = 0; q < wid; ++q) run += wtot[q];
+    for (int g = g0; g < g1; ++g) { off[g] = run; cur[g] = run; run += cnt[g]; }
+    if (threadIdx.x == 0) off[k] = n;
+    __syncthreads();
+    for (int j = threadIdx.x; j < n; j += RC_KMED_T) mem[atomicAdd(&cur[a[j]], 1)] = j;
+    __syncthreads();
+    return empty;
 }
 
 // k-medoids++ by costs (Clustering.jl initseeds_by_costs!, :kmpp) and the initial assignment.
@@ -200,35 +239,12 @@ __global__ __launch_bounds__(RC_KMED_T) void k_kmed_round(const T *__restrict__ 
     int *cnt = w.cnt + ko, *off = w.off + ko, *cur = w.cur + ko, *med = w.med + ko, *bestj = w.bestj + ko;
     long long *bestc = w.bestc + ko;
     const int t = w.iter[slot] + 1;
-    if (threadIdx.x == 0) empty = 0;
-    for (int g = threadIdx.x; g < k; g += RC_KMED_T) { cnt[g] = 0; bestc[g] = 0x7fffffffffffffffll; bestj[g] = 0x7fffffff; }
-    __syncthreads();
-    // groups: sizes, offsets (exclusive scan over the k sizes; each thread owns a contiguous run of groups), members
-    for (int j = threadIdx.x; j < n; j += RC_KMED_T) atomicAdd(&cnt[a[j]], 1);
-    __syncthreads();
-    const int per = (k + RC_KMED_T - 1) / RC_KMED_T, g0 = min(k, (int)threadIdx.x * per), g1 = min(k, g0 + per);
-    int local = 0, my_empty = 0;
-    for (int g = g0; g < g1; ++g) { local += cnt[g]; my_empty |= cnt[g] == 0; }
-    if (my_empty) empty = 1;
-    int incl = local;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int x = __shfl_up(incl, d);
-        if (lane >= d) incl += x;
-    }
-    if (lane == 63) wtot[wid] = incl;
-    __syncthreads();
-    if (empty) {   // Clustering.jl asserts here; only a nonzero diagonal entry can get a medoid out of its own group
+    for (int g = threadIdx.x; g < k; g += RC_KMED_T) { bestc[g] = 0x7fffffffffffffffll; bestj[g] = 0x7fffffff; }
+    if (group_points(a, n, k, cnt, off, cur, mem, wtot, &empty)) {
+        // Clustering.jl asserts here; only a nonzero diagonal entry can get a medoid out of its own group
         if (threadIdx.x == 0) { w.flags[slot] = RC_KMED_DONE | RC_KMED_ERR_EMPTY; atomicOr(w.err, (unsigned)RC_KMED_ERR_EMPTY); }
         return;
     }
-    int run = incl - local;
-    for (int q = 0; q < wid; ++q) run += wtot[q];
-    for (int g = g0; g < g1; ++g) { off[g] = run; cur[g] = run; run += cnt[g]; }
-    if (threadIdx.x == 0) off[k] = n;
-    __syncthreads();
-    for (int j = threadIdx.x; j < n; j += RC_KMED_T) mem[atomicAdd(&cur[a[j]], 1)] = j;
-    __syncthreads();
     // medoid update: candidate j of group g costs sum_{h in g} D[j, h] (row j: D is symmetric).  One wave per candidate;
     // a large group streams row j masked by the labels, a small one gathers its members' columns
     for (int q = wid; q < n; q += RC_KMED_NW) {
@@ -267,12 +283,124 @@ __global__ __launch_bounds__(RC_KMED_T) void k_kmed_round(const T *__restrict__ 
     }
 }
 
+// ---- The per-k split of rc_kmedoids_scan_split: Σ D and Σ logD over the pairs i < j of one group under each slot's final
+// assignment, in exact integers.  logD entries as the block sums take them: rc_qlog of Dq when the context derives logD
+// (L == null), otherwise the stored fixed-point logD in the caller's order (Lq_src).  Row sums fit int64 (quant_exponent);
+// sums over rows go through (hi, lo) halves as in k_blocksums.
+
+__device__ __forceinline__ void acc_add(long long v, long long &hi, long long &lo)
+{
+    hi += v >> RC_LO_BITS;
+    lo += v & (((long long)1 << RC_LO_BITS) - 1);
+}
+
+template <typename T>
+__device__ __forceinline__ void pair_add(const T *__restrict__ D, const T *__restrict__ L, size_t e, int eD, double sL,
+                                         const double2 *__restrict__ tab, long long &sd, long long &sl)
+{
+    const long long d = (long long)D[e];
+    sd += d;
+    sl += L ? (long long)L[e] : rc_qlog(d, eD, sL, tab);
+}
+
+// the groups of every slot's final assignment (members / cnt of the last round predate its reassignment) and the count of
+// within pairs
+__global__ __launch_bounds__(RC_KMED_T) void k_kmed_split_group(Ws w)
+{
+    __shared__ long long red[RC_KMED_NW];
+    __shared__ int wtot[RC_KMED_NW];
+    __shared__ int flag;
+    const int slot = blockIdx.x, k = w.khi - slot, n = w.n;
+    const size_t ko = (size_t)slot * w.kstride;
+    int *cnt = w.cnt + ko;
+    (void)group_points(w.assign + (size_t)slot * n, n, k, cnt, w.off + ko, w.cur + ko, w.members + (size_t)slot * n, wtot, &flag);
+    long long v = 0;   // (an empty group — a run that ended on a degenerate reassignment — contributes nothing)
+    for (int g = threadIdx.x; g < k; g += RC_KMED_T) v += (long long)cnt[g] * (cnt[g] - 1) / 2;
+    v = block_sum(v, red);
+    if (threadIdx.x == 0) w.pairs[slot] = v;
+}
+
+// blockIdx.y = slot; each wave owns 64 consecutive member positions.  A lane whose group has at most 64 members sums its row
+// against the group's later positions on its own; the rows of larger groups go through the whole wave one at a time — as the
+// medoid update does, a group above n/16 streams the row's tail masked by the labels (pairs i < j by point index), a smaller
+// one gathers its later members' columns (pairs by member position).  Within a group every row takes the same path, so each
+// unordered pair is summed exactly once.
+template <typename T>
+__global__ __launch_bounds__(RC_KMED_T) void k_kmed_split_pairs(const T *__restrict__ D, const T *__restrict__ L, Ws w, int eD,
+                                                                double sL, const double2 *__restrict__ tab)
+{
+    const int slot = blockIdx.y, n = w.n, ld = w.ld;
+    const int lane = threadIdx.x & 63, q0 = ((int)blockIdx.x * RC_KMED_NW + (threadIdx.x >> 6)) * 64;
+    if (q0 >= n) return;   // (whole waves; no block-level synchronisation follows)
+    const int *a = w.assign + (size_t)slot * n, *mem = w.members + (size_t)slot * n;
+    const size_t ko = (size_t)slot * w.kstride;
+    const int *cnt = w.cnt + ko, *off = w.off + ko;
+    const int q = q0 + lane;
+    int i = 0, g = 0, s = 0, o = 0;
+    if (q < n) { i = mem[q]; g = a[i]; s = cnt[g]; o = off[g]; }
+    long long dh = 0, dl = 0, lh = 0, ll = 0;
+    if (q < n && s <= 64) {
+        long long sd = 0, sl = 0;
+        for (int x = q + 1; x < o + s; ++x) pair_add(D, L, (size_t)i * ld + mem[x], eD, sL, tab, sd, sl);
+        acc_add(sd, dh, dl);
+        acc_add(sl, lh, ll);
+    }
+    for (u64 big = __ballot(q < n && s > 64); big; big &= big - 1) {
+        const int b = __ffsll((unsigned long long)big) - 1;
+        const int bi = __shfl(i, b), bg = __shfl(g, b), bs = __shfl(s, b), bo = __shfl(o, b), bq = q0 + b;
+        const size_t row = (size_t)bi * ld;
+        long long sd = 0, sl = 0;
+        if ((long long)bs * 16 > n) {
+            for (int j = bi + 1 + lane; j < n; j += 64)
+                if (a[j] == bg) pair_add(D, L, row + j, eD, sL, tab, sd, sl);
+        } else {
+            for (int x = bq + 1 + lane; x < bo + bs; x += 64) pair_add(D, L, row + mem[x], eD, sL, tab, sd, sl);
+        }
+        sd = wave_sum(sd);
+        sl = wave_sum(sl);
+        if (lane == 0) { acc_add(sd, dh, dl); acc_add(sl, lh, ll); }
+    }
+    dh = wave_sum(dh); dl = wave_sum(dl); lh = wave_sum(lh); ll = wave_sum(ll);
+    if (lane == 0) {
+        unsigned long long *acc = w.acc + (size_t)slot * 4;
+        atomicAdd(&acc[0], (unsigned long long)dh);
+        atomicAdd(&acc[1], (unsigned long long)dl);
+        atomicAdd(&acc[2], (unsigned long long)lh);
+        atomicAdd(&acc[3], (unsigned long long)ll);
+    }
+}
+
+// Σ_{i<j} D and Σ_{i<j} logD over the whole upper triangle and Σ_i logD[i][i] (zero unless the caller's logD has a diagonal):
+// the between sums follow as total - within.  One wave per row.
+template <typename T>
+__global__ __launch_bounds__(RC_KMED_T) void k_kmed_split_total(const T *__restrict__ D, const T *__restrict__ L, int n, int ld,
+                                                                int eD, double sL, const double2 *__restrict__ tab,
+                                                                unsigned long long *tot /* [8] */)
+{
+    const int lane = threadIdx.x & 63, i = (int)blockIdx.x * RC_KMED_NW + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const size_t row = (size_t)i * ld;
+    long long sd = 0, sl = 0;
+    for (int j = i + 1 + lane; j < n; j += 64) pair_add(D, L, row + j, eD, sL, tab, sd, sl);
+    sd = wave_sum(sd);
+    sl = wave_sum(sl);
+    if (lane == 0) {
+        long long h[6] = {0, 0, 0, 0, 0, 0};
+        acc_add(sd, h[0], h[1]);
+        acc_add(sl, h[2], h[3]);
+        acc_add(L ? (long long)L[row + i] : 0ll, h[4], h[5]);
+        for (int t = 0; t < 6; ++t) atomicAdd(&tot[t], (unsigned long long)h[t]);
+    }
+}
+
 }  // namespace kmed
 
 // Runs k = kmax, kmax-1, ..., kmin in chunks; per-k results into totalcost / iterations / converged[k - kmin].  With
-// assignments / medoids non-null (kmin == kmax) the single run's labels and medoids (1-based) as well.
+// assignments / medoids non-null (kmin == kmax) the single run's labels and medoids (1-based) as well; with split non-null
+// the within / between split of every k's final assignment into split[k - kmin].
 static int32_t kmed_run(rc_ctx *c, const char *who, int64_t kmin, int64_t kmax, int64_t maxiter, double tol, uint64_t seed,
-                        double *totalcost, int64_t *iterations, uint8_t *converged, int64_t *assignments, int64_t *medoids)
+                        double *totalcost, int64_t *iterations, uint8_t *converged, int64_t *assignments, int64_t *medoids,
+                        rc_wb_stats *split)
 {
     if (!c) return fail(c, RC_ERR_ARG, "%s: NULL ctx", who);
     if (c->broken) return fail(c, RC_ERR_STATE, "%s: the context is void after a failed capacity growth", who);
@@ -284,11 +412,12 @@ static int32_t kmed_run(rc_ctx *c, const char *who, int64_t kmin, int64_t kmax, 
     if (!(tol >= 0.0)) return fail(c, RC_ERR_ARG, "%s: tol must be >= 0", who);
     HIPCHK(c, hipSetDevice(c->dev));
     const size_t kstride = (size_t)kmax + 1;
-    const size_t per_slot = (size_t)n * 16 + kstride * 28 + 16;
+    const size_t per_slot = (size_t)n * 16 + kstride * 28 + 16 + (split ? 40 : 0);
     const int64_t R = kmax - kmin + 1;
     const int64_t C = std::max<int64_t>(1, std::min<int64_t>(R, (int64_t)(RC_KMED_WS_BYTES / per_slot)));
     char *base = nullptr;
-    const size_t bytes = (size_t)C * per_slot + (size_t)(maxiter + 2) * sizeof(unsigned) + 16 * 16;   // + alignment of the 14 arrays
+    const size_t bytes = (size_t)C * per_slot + (size_t)(maxiter + 2) * sizeof(unsigned) + 16 * 16   // + alignment of the 14 arrays
+                         + (split ? 64 + 2 * 16 : 0);                                                  // + the split's totals, 2 arrays
     HIPCHK(c, hipMalloc(&base, bytes));
     kmed::Ws w{};
     {
@@ -308,6 +437,10 @@ static int32_t kmed_run(rc_ctx *c, const char *who, int64_t kmin, int64_t kmax, 
         w.flags = (int *)take((size_t)C * 4);
         w.err = (unsigned *)take(4);
         w.active = (unsigned *)take((size_t)(maxiter + 1) * 4);
+        if (split) {
+            w.acc = (unsigned long long *)take((size_t)(C + 2) * 32);
+            w.pairs = (long long *)take((size_t)C * 8);
+        }
         if ((size_t)(p - base) > bytes) { (void)hipFree(base); return fail(c, RC_ERR_HIP, "%s: workspace layout", who); }
     }
     w.n = (int)n; w.ld = c->ld; w.kstride = (int)kstride;
@@ -317,6 +450,29 @@ static int32_t kmed_run(rc_ctx *c, const char *who, int64_t kmin, int64_t kmax, 
     std::vector<int> h_it((size_t)C), h_fl((size_t)C);
     hipError_t e = hipSuccess;
     unsigned h_err = 0;
+    // the split: logD entries as the block sums take them (derived: rc_qlog of Dq; stored: Lq_src, the caller's order)
+    const void *Lsrc = c->derived ? nullptr : c->Lq_src;
+    const double sL = std::ldexp(1.0, c->eL);
+    unsigned long long h_tot[8] = {};
+    std::vector<unsigned long long> h_acc;
+    std::vector<long long> h_pairs;
+    if (split) {
+        h_acc.resize((size_t)C * 4);
+        h_pairs.resize((size_t)C);
+        unsigned long long *tot = w.acc + (size_t)C * 4;
+        const unsigned nb = (unsigned)((n + RC_KMED_NW - 1) / RC_KMED_NW);
+        e = hipMemsetAsync(tot, 0, 64, s);
+        if (e == hipSuccess) {
+            if (c->bits == 64) kmed::k_kmed_split_total<long long><<<nb, RC_KMED_T, 0, s>>>((const long long *)c->Dq_src, (const long long *)Lsrc, (int)n, c->ld, c->eD, sL, c->ltab, tot);
+            else kmed::k_kmed_split_total<int><<<nb, RC_KMED_T, 0, s>>>((const int *)c->Dq_src, (const int *)Lsrc, (int)n, c->ld, c->eD, sL, c->ltab, tot);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(h_tot, tot, 64, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    auto join = [](const unsigned long long *h) {   // (hi, lo) halves -> exact integer
+        return (__int128)(long long)h[0] * ((__int128)1 << RC_LO_BITS) + (__int128)(long long)h[1];
+    };
     for (int64_t khi = kmax; khi >= kmin && e == hipSuccess; khi -= C) {
         const int cnt = (int)std::min<int64_t>(C, khi - kmin + 1);
         w.khi = (int)khi;
@@ -353,6 +509,27 @@ static int32_t kmed_run(rc_ctx *c, const char *who, int64_t kmin, int64_t kmax, 
             iterations[i] = h_it[(size_t)q];
             converged[i] = (h_fl[(size_t)q] & RC_KMED_CONV) ? 1 : 0;
         }
+        if (split) {   // (before the next chunk's seeding overwrites the assignments)
+            e = hipMemsetAsync(w.acc, 0, (size_t)cnt * 32, s);
+            if (e != hipSuccess) break;
+            kmed::k_kmed_split_group<<<cnt, RC_KMED_T, 0, s>>>(w);
+            // (slots on y: a chunk has fewer than 65536 of them — more would need per_slot < 8 KB, i.e. n < 512 >= kmax)
+            const dim3 grid((unsigned)((n + 64 * RC_KMED_NW - 1) / (64 * RC_KMED_NW)), (unsigned)cnt);
+            if (c->bits == 64) kmed::k_kmed_split_pairs<long long><<<grid, RC_KMED_T, 0, s>>>((const long long *)c->Dq_src, (const long long *)Lsrc, w, c->eD, sL, c->ltab);
+            else kmed::k_kmed_split_pairs<int><<<grid, RC_KMED_T, 0, s>>>((const int *)c->Dq_src, (const int *)Lsrc, w, c->eD, sL, c->ltab);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(h_acc.data(), w.acc, (size_t)cnt * 32, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(h_pairs.data(), w.pairs, (size_t)cnt * 8, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) break;
+            const __int128 uD = join(h_tot), uL = join(h_tot + 2), dgL = join(h_tot + 4);
+            const long long all_pairs = (long long)n * (n - 1) / 2;
+            for (int q = 0; q < cnt; ++q) {
+                const __int128 wD = join(&h_acc[(size_t)q * 4]), wL = join(&h_acc[(size_t)q * 4 + 2]);
+                const long long pA = h_pairs[(size_t)q];
+                wb_finish(c, pA, all_pairs - pA, 2 * wD, 2 * wL + dgL, uD - wD, uL - wL, &split[khi - q - kmin]);
+            }
+        }
         if (assignments || medoids) {   // single run: slot 0
             std::vector<int> ha((size_t)n), hm((size_t)kmax);
             e = hipMemcpyAsync(ha.data(), w.assign, (size_t)n * 4, hipMemcpyDeviceToHost, s);
@@ -378,11 +555,19 @@ extern "C" int32_t rc_kmedoids(rc_ctx *c, int64_t k, int64_t maxiter, double tol
                                int64_t *medoids, double *totalcost, int64_t *iterations, uint8_t *converged)
 {
     if (!assignments || !medoids) return fail(c, RC_ERR_ARG, "rc_kmedoids: NULL output");
-    return kmed_run(c, "rc_kmedoids", k, k, maxiter, tol, seed, totalcost, iterations, converged, assignments, medoids);
+    return kmed_run(c, "rc_kmedoids", k, k, maxiter, tol, seed, totalcost, iterations, converged, assignments, medoids, nullptr);
 }
 
 extern "C" int32_t rc_kmedoids_scan(rc_ctx *c, int64_t kmin, int64_t kmax, int64_t maxiter, double tol, uint64_t seed,
                                     double *totalcost, int64_t *iterations, uint8_t *converged)
 {
-    return kmed_run(c, "rc_kmedoids_scan", kmin, kmax, maxiter, tol, seed, totalcost, iterations, converged, nullptr, nullptr);
+    return kmed_run(c, "rc_kmedoids_scan", kmin, kmax, maxiter, tol, seed, totalcost, iterations, converged, nullptr, nullptr, nullptr);
+}
+
+extern "C" int32_t rc_kmedoids_scan_split(rc_ctx *c, int64_t kmin, int64_t kmax, int64_t maxiter, double tol, uint64_t seed,
+                                          double *totalcost, int64_t *iterations, uint8_t *converged, rc_wb_stats *split)
+{
+    if (!split) return fail(c, RC_ERR_ARG, "rc_kmedoids_scan_split: NULL output");
+    return kmed_run(c, "rc_kmedoids_scan_split", kmin, kmax, maxiter, tol, seed, totalcost, iterations, converged, nullptr, nullptr,
+                    split);
 }

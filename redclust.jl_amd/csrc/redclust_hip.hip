@@ -6529,6 +6529,20 @@ extern "C" int32_t rc_loglik(rc_ctx *c, double *out)
     return RC_OK;
 }
 
+// rc_wb_stats from the exact fixed-point sums of a split: wD2 / wL2 = TWICE the within sums (every within pair in both
+// orders; wL2 also carries logD's diagonal, zero unless the caller's logD has one), bD / bL = the between sums.  The one
+// conversion to doubles, shared by rc_within_between and the k-medoids scan's per-k split.
+static void wb_finish(const rc_ctx *c, long long cntA, long long cntB, __int128 wD2, __int128 wL2, __int128 bD, __int128 bL,
+                      rc_wb_stats *out)
+{
+    const long double scD = ldexpl(1.0L, -c->eD), scL = ldexpl(1.0L, -c->eL);
+    out->count_within = cntA; out->count_between = cntB;
+    out->sum_within = (double)((long double)wD2 * scD / 2);
+    out->sumlog_within = (double)((long double)wL2 * scL / 2);
+    out->sum_between = (double)((long double)bD * scD);
+    out->sumlog_between = (double)((long double)bL * scL);
+}
+
 // The within- / between-cluster split of the upper triangle that fitprior feeds to its Gamma fits
 // (src/prior.jl:73-75: A = distances of pairs in the same cluster, B = the others; :96-110 use |A|, ΣA, Σlog A and the
 // same for B) for the CURRENT labels, from the block sums: Σ_A = ½ Σ_k B(k,k), Σ_B = Σ_{k<t} B(k,t).  Exact integer
@@ -6570,12 +6584,7 @@ extern "C" int32_t rc_within_between(rc_ctx *c, rc_wb_stats *out)
     HIPCHK(c, hipMemcpy(dg.data(), c->diagq, (size_t)c->n * sizeof(long long), hipMemcpyDeviceToHost));
     __int128 dsum = 0;
     for (long long v : dg) dsum += v;
-    const long double scD = ldexpl(1.0L, -c->eD), scL = ldexpl(1.0L, -c->eL);
-    out->count_within = cntA; out->count_between = cntB;
-    out->sum_within = (double)((long double)(wD - dsum) * scD / 2);
-    out->sumlog_within = (double)((long double)wL * scL / 2);
-    out->sum_between = (double)((long double)bD * scD);
-    out->sumlog_between = (double)((long double)bL * scL);
+    wb_finish(c, cntA, cntB, wD - dsum, wL, bD, bL, out);
     return RC_OK;
 }
 
@@ -7541,3 +7550,4 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "kmedoids.inc.hip"
 #include "chain.inc.hip"
 #include "chains.inc.hip"
+#include "samplek.inc.hip"

@@ -1,10 +1,13 @@
-"""fitprior (src/prior.jl:22-128), its elbow rule detectknee (src/prior.jl:340-360), sample_rp (src/mcmc.jl:592-636) and
-Clustering.jl's kmedoids, which fitprior and runsampler's default start (src/mcmc.jl:516-527) call.
+"""fitprior (src/prior.jl:22-128), fitprior2 (:151-277), sampledist (:284-308), sampleK (:316-338), pmf (:362-367), the
+elbow rule detectknee (:340-360), sample_rp (src/mcmc.jl:592-636) and Clustering.jl's kmedoids, which fitprior, fitprior2
+and runsampler's default start (src/mcmc.jl:516-527) call.
 
 The k-medoids runs — one per k of the elbow scan, then the notional clustering — are batched on the device
 (rc_kmedoids_scan / rc_kmedoids, csrc/kmedoids.inc.hip); the within / between split of the distances under the notional
-clustering comes from the device's block sums (rc_within_between).  On the host, as in the reference: the elbow, the
-scalar chain of sample_rp and the maximum-likelihood fits.  The k-means path of fitprior is not in this build."""
+clustering comes from the device's block sums (rc_within_between), fitprior2's split under every k of the scan from the
+scan itself (rc_kmedoids_scan_split).  sampleK's Gumbel-max draws run on the device (rc_sample_k, csrc/samplek.inc.hip).
+On the host, as in the reference: the elbow, the scalar chain of sample_rp, the draws of r / p and the maximum-likelihood
+fits.  The k-means path of fitprior / fitprior2 is not in this build."""
 from __future__ import annotations
 
 import math
@@ -13,7 +16,7 @@ import warnings
 import numpy as np
 from scipy.special import digamma, polygamma
 
-from ._lib import Context
+from ._lib import Context, sample_k
 from .datagen import _gamma_shape_mle
 from .sampler import sample_p, sample_r
 from .types import KmedoidsResult, MCMCData, MCMCOptionsList, PriorHyperparamsList
@@ -21,6 +24,8 @@ from .types import KmedoidsResult, MCMCData, MCMCOptionsList, PriorHyperparamsLi
 # Seeds of the k-medoids streams the reference draws from its one global RNG: the elbow scan uses `seed` itself, the
 # notional clustering and runsampler's starting labels fresh streams derived from it (kmedoids_stream_seed).
 KMED_STREAM_SCAN, KMED_STREAM_NOTIONAL, KMED_STREAM_INIT = 0, 1, 2
+# fitprior2's sampleK call (host r / p draws and the device's Gumbel noise) draws from a stream of its own as well
+SAMPLEK_STREAM = 3
 
 
 def kmedoids_stream_seed(seed: int, stream: int) -> int:
@@ -131,15 +136,8 @@ def _staging(data, diss):
     return x.shape[0], "points", x
 
 
-def fitprior(data, algo: str, diss: bool = False, *, Kmin: int = 1, Kmax: int | None = None, verbose: bool = True,
-             seed: int = 0, device: int = 0, ctx: Context | None = None) -> PriorHyperparamsList:
-    """fitprior(data, algo, diss; Kmin, Kmax, verbose) — src/prior.jl:22-128, algo = "k-medoids".
-
-    data: points (one observation per row, this package's convention: the reference's columns), a dissimilarity matrix
-    with diss=True, or an MCMCData.  ctx reuses a Context that holds the same matrix (its label state is overwritten
-    with the notional clustering); otherwise one is staged for the call — from points the device computes the distances.
-    seed keys the k-medoids streams (kmedoids_stream_seed) and the sample_rp chain."""
-    out = print if verbose else (lambda *a, **k: None)
+def _prepare(name, data, algo, diss, Kmin, Kmax, ctx, out):
+    """The input handling and checks fitprior and fitprior2 share (src/prior.jl:30-56, :160-188): (N, kind, payload, Kmax)."""
     out("Fitting prior hyperparameters")
     is_data = isinstance(data, MCMCData)
     N, kind, x = _staging(data, diss)
@@ -156,12 +154,39 @@ def fitprior(data, algo: str, diss: bool = False, *, Kmin: int = 1, Kmax: int | 
     if not (1 <= Kmin <= Kmax <= N):
         raise ValueError("Kmin and Kmax must satisfy 1 ≤ Kmin ≤ Kmax ≤ N")
     if algo == "k-means":
-        raise NotImplementedError("fitprior(algo='k-means') is not in this build: use algo='k-medoids'")
+        raise NotImplementedError(f"{name}(algo='k-means') is not in this build: use algo='k-medoids'")
     if ctx is not None and ctx.n != N:
         raise ValueError(f"ctx holds {ctx.n} observations, data {N}")
+    return N, kind, x, Kmax
+
+
+def _stage(kind, x, device):
+    return Context.from_points(x, device=device) if kind == "points" else Context(x, device=device)
+
+
+def _partition_prior(notional, verbose, seed):
+    """src/prior.jl:88-94 (and :229-235): sample_rp on the notional clustering's sizes, then the Gamma fit of r and the Beta
+    fit of p.  Returns (proposalsd_r, eta, sigma, u, v)."""
+    temp = sample_rp(np.bincount(notional)[1:], verbose=verbose, seed=seed)
+    proposalsd_r = float(np.std(temp["r"], ddof=1))
+    eta, sigma = _gamma_mle(temp["r"])
+    u, v = _beta_mle(temp["p"])
+    return proposalsd_r, eta, sigma, u, v
+
+
+def fitprior(data, algo: str, diss: bool = False, *, Kmin: int = 1, Kmax: int | None = None, verbose: bool = True,
+             seed: int = 0, device: int = 0, ctx: Context | None = None) -> PriorHyperparamsList:
+    """fitprior(data, algo, diss; Kmin, Kmax, verbose) — src/prior.jl:22-128, algo = "k-medoids".
+
+    data: points (one observation per row, this package's convention: the reference's columns), a dissimilarity matrix
+    with diss=True, or an MCMCData.  ctx reuses a Context that holds the same matrix (its label state is overwritten
+    with the notional clustering); otherwise one is staged for the call — from points the device computes the distances.
+    seed keys the k-medoids streams (kmedoids_stream_seed) and the sample_rp chain."""
+    out = print if verbose else (lambda *a, **k: None)
+    N, kind, x, Kmax = _prepare("fitprior", data, algo, diss, Kmin, Kmax, ctx, out)
     own = ctx is None
     if own:
-        ctx = Context.from_points(x, device=device) if kind == "points" else Context(x, device=device)
+        ctx = _stage(kind, x, device)
     try:
         out("Computing notional clustering.")
         # as written (prior.jl:63-70): the runs are for k = 1:(Kmax-Kmin+1), their costs are labelled Kmin:Kmax
@@ -174,11 +199,7 @@ def fitprior(data, algo: str, diss: bool = False, *, Kmin: int = 1, Kmax: int | 
         wb = ctx.within_between()
 
         out("Computing partition prior hyperparameters.")
-        clustsizes = np.bincount(notional)[1:]
-        temp = sample_rp(clustsizes, verbose=verbose, seed=seed)
-        proposalsd_r = float(np.std(temp["r"], ddof=1))
-        eta, sigma = _gamma_mle(temp["r"])
-        u, v = _beta_mle(temp["p"])
+        proposalsd_r, eta, sigma, u, v = _partition_prior(notional, verbose, seed)
 
         out("Computing likelihood hyperparameters.")
         if K == N:   # A is empty
@@ -195,6 +216,121 @@ def fitprior(data, algo: str, diss: bool = False, *, Kmin: int = 1, Kmax: int | 
             cB = wb["count_between"]
             delta2 = _gamma_shape_mle(wb["sum_between"] / cB, wb["sumlog_between"] / cB)
             zeta, gamma = cB * delta2, wb["sum_between"]
+        return PriorHyperparamsList(delta1=delta1, delta2=delta2, alpha=alpha, beta=beta, zeta=zeta, gamma=gamma, eta=eta,
+                                    sigma=sigma, proposalsd_r=proposalsd_r, u=u, v=v, K_initial=K)
+    finally:
+        if own:
+            ctx.close()
+
+
+def pmf(X, N: int | None = None):
+    """src/prior.jl:362-367: p[k-1] = #{X == k} / length(X) for k = 1..max X; with N, padded with zeros to length N as
+    fitprior2 does."""
+    X = np.asarray(X, dtype=np.int64)
+    if X.size == 0 or X.min() < 1:
+        raise ValueError("pmf needs a non-empty vector of positive integers")
+    p = np.bincount(X)[1:] / len(X)
+    if N is not None and len(p) < N:
+        p = np.concatenate([p, np.zeros(N - len(p))])
+    return p
+
+
+def sampleK(*args, seed: int = 0, device: int = 0):
+    """sampleK(params, numsamples, n) or sampleK(η, σ, u, v, numsamples, n) — src/prior.jl:316-338: numsamples draws of K
+    from its prior predictive for n observations, as int64 in 1..n.  r ~ Gamma(η, 1/σ) then p ~ Beta(u, v) come from
+    np.random.default_rng(seed); the Gumbel-max draw over K = 1..n runs on the device (rc_sample_k, uniforms keyed by seed)."""
+    if len(args) == 3:
+        params, numsamples, n = args
+        eta, sigma, u, v = params.eta, params.sigma, params.u, params.v
+    elif len(args) == 6:
+        eta, sigma, u, v, numsamples, n = args
+    else:
+        raise TypeError("sampleK(params, numsamples, n) or sampleK(eta, sigma, u, v, numsamples, n)")
+    if n < 1:
+        raise ValueError("n must be a positive integer.")
+    if numsamples < 1:
+        raise ValueError("numsamples must be a positive integer.")
+    rng = np.random.default_rng(seed)
+    r = rng.gamma(eta, 1.0 / sigma, int(numsamples))
+    p = rng.beta(u, v, int(numsamples))
+    return sample_k(int(n), r, p, seed=seed, device=device)[0]
+
+
+def sampledist(params: PriorHyperparamsList, type: str, numsamples: int = 1, *, seed: int = 0):
+    """src/prior.jl:284-308: numsamples draws from the prior predictive of the within-cluster ("intracluster": α, β, δ1) or
+    between-cluster ("intercluster": ζ, γ, δ2) distances: λ ~ Gamma(a, 1/b), then x ~ Gamma(δ, 1/λ).  Host NumPy."""
+    if type not in ("intercluster", "intracluster"):
+        raise ValueError('type must be either "intercluster" or "intracluster".')
+    if numsamples < 1:
+        raise ValueError("numsamples must be a positive integer.")
+    a, b, d = (params.alpha, params.beta, params.delta1) if type == "intracluster" else (params.zeta, params.gamma, params.delta2)
+    rng = np.random.default_rng(seed)
+    lam = rng.gamma(a, 1.0 / b, int(numsamples))
+    return rng.gamma(d, 1.0 / lam)
+
+
+def _fit_weighted(stats, Kprior, Kmin: int, Kmax: int):
+    """fitprior2's likelihood fits (src/prior.jl:238-266) from the per-k sufficient statistics: stats holds count_, sum_ and
+    sumlog_ within / between arrays indexed by k - Kmin for k = Kmin..Kmax, Kprior[k - 1] the weight of k.  fit_mle(Gamma, x,
+    w) is the unweighted fit of the weighted statistics; the sums run over k in ascending order.  Returns (δ1, α, β, δ2, ζ, γ)."""
+    w = np.asarray(Kprior, dtype=np.float64)[Kmin - 1:Kmax]
+    res = []
+    for side, what in (("within", "cohesion"), ("between", "repulsion")):
+        c = np.asarray(stats["count_" + side], dtype=np.int64)[:Kmax - Kmin + 1]
+        S = np.asarray(stats["sum_" + side], dtype=np.float64)[:Kmax - Kmin + 1]
+        L = np.asarray(stats["sumlog_" + side], dtype=np.float64)[:Kmax - Kmin + 1]
+        if not c.any():
+            if side == "within":
+                warnings.warn("The ensemble of clusterings has only one clustering, consisting of all singletons. This might be "
+                              "because you have set Kmin = Kmax = number of points. Falling back to defaults for cohesion parameters.")
+            else:
+                warnings.warn("The ensemble of clusterings has only one clustering, consisting of a single cluster. This might be "
+                              "because you have set Kmin = Kmax = 1. Falling back to defaults for repulsion parameters.")
+            res += [1.0, 1.0, 1.0]
+            continue
+        tw = sx = slx = 0.0
+        for k in range(len(c)):
+            tw += w[k] * c[k]
+            sx += w[k] * S[k]
+            slx += w[k] * L[k]
+        if not tw > 0:
+            raise ValueError(f"fitprior2: the sampled prior on K puts no weight on Kmin..Kmax = {Kmin}..{Kmax}, so the weighted "
+                             f"{what} fit has total weight zero (the reference fails in fit_mle here)")
+        shape = _gamma_shape_mle(sx / tw, slx / tw)
+        res += [shape, tw * shape, sx]
+    return tuple(res)
+
+
+def fitprior2(data, algo: str, diss: bool = False, *, Kmin: int = 1, Kmax: int | None = None, verbose: bool = True,
+              seed: int = 0, device: int = 0, ctx: Context | None = None) -> PriorHyperparamsList:
+    """fitprior2(data, algo, diss; Kmin, Kmax, verbose) — src/prior.jl:151-277, algo = "k-medoids".
+
+    As fitprior (same inputs, checks and partition-prior fit), but the likelihood hyperparameters are fitted to the
+    within / between distances of the clusterings of EVERY k in Kmin..Kmax, each weighted by the prior probability of k
+    (pmf of sampleK with max(10^4, 100 N) samples).  The per-k splits come from the device scan (rc_kmedoids_scan_split)
+    as exact sufficient statistics; no distance vector is formed.  Streams: the scan and the notional run as in fitprior,
+    sample_rp keyed by seed, sampleK by kmedoids_stream_seed(seed, SAMPLEK_STREAM).  ctx: a Context holding the same matrix
+    (its state is left as it is)."""
+    out = print if verbose else (lambda *a, **k: None)
+    N, kind, x, Kmax = _prepare("fitprior2", data, algo, diss, Kmin, Kmax, ctx, out)
+    own = ctx is None
+    if own:
+        ctx = _stage(kind, x, device)
+    try:
+        out("Computing notional clustering.")
+        scan = ctx.kmedoids_scan(Kmin, Kmax, maxiter=1000, seed=kmedoids_stream_seed(seed, KMED_STREAM_SCAN), split=True)
+        for k in np.flatnonzero(~scan["converged"]) + Kmin:
+            warnings.warn(f"Clustering did not converge at K = {k}")
+        K = int(detectknee(np.arange(Kmin, Kmax + 1), scan["totalcost"])[0])
+        notional = ctx.kmedoids(K, maxiter=1000, seed=kmedoids_stream_seed(seed, KMED_STREAM_NOTIONAL)).assignments
+
+        out("Computing partition prior hyperparameters.")
+        proposalsd_r, eta, sigma, u, v = _partition_prior(notional, verbose, seed)
+        Ks = sampleK(eta, sigma, u, v, max(10000, 100 * N), N, seed=kmedoids_stream_seed(seed, SAMPLEK_STREAM), device=device)
+        Kprior = pmf(Ks, N)
+
+        out("Computing likelihood hyperparameters.")
+        delta1, alpha, beta, delta2, zeta, gamma = _fit_weighted(scan, Kprior, Kmin, Kmax)
         return PriorHyperparamsList(delta1=delta1, delta2=delta2, alpha=alpha, beta=beta, zeta=zeta, gamma=gamma, eta=eta,
                                     sigma=sigma, proposalsd_r=proposalsd_r, u=u, v=v, K_initial=K)
     finally:

@@ -1,5 +1,6 @@
-"""Wall time of the batched k-medoids scan and of fitprior (prior.py) on the device, and of the NumPy restatement
-(tests/kmedoids_ref.py) doing the scan's work on one CPU core.
+"""Wall time of the batched k-medoids scan, of fitprior and fitprior2 (prior.py) and of sampleK on the device, and of the
+NumPy restatement (tests/kmedoids_ref.py) doing the scan's work on one CPU core.  fitprior2 - fitprior is the cost of the
+per-k split plus sampleK; the sampleK line has its default count for n, max(10^4, 100 n), with rc_sample_k's kernel time.
 
     python tools/time_fitprior.py                 # device: n = 2000 (Kmax 1000) and n = 8192 (Kmax 4096)
     python tools/time_fitprior.py --ref           # + the restatement's scan at n = 2000 (no GPU needed; minutes)
@@ -18,6 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import redclust_amd as rc  # noqa: E402
+from redclust_amd._lib import sample_k  # noqa: E402
 
 
 def device(n):
@@ -35,6 +37,25 @@ def device(n):
     print(json.dumps(dict(what="device", n=n, Kmax=n // 2, scan_s=round(t_scan, 3), fitprior_s=round(t_fit, 3),
                           K=P.K_initial, iterations_max=int(it.max()), iterations_mean=round(float(it.mean()), 2),
                           not_converged=int((~scan["converged"]).sum()))), flush=True)
+    ctx = rc.Context(D)
+    t0 = time.perf_counter()
+    ctx.kmedoids_scan(1, n // 2, maxiter=1000, split=True)
+    t_split = time.perf_counter() - t0
+    ctx.close()
+    t0 = time.perf_counter()
+    P2 = rc.fitprior2(D, "k-medoids", True, verbose=False)
+    t_fit2 = time.perf_counter() - t0
+    print(json.dumps(dict(what="device_fitprior2", n=n, Kmax=n // 2, scan_split_s=round(t_split, 3),
+                          split_minus_scan_s=round(t_split - t_scan, 3), fitprior2_s=round(t_fit2, 3),
+                          fitprior2_minus_fitprior_s=round(t_fit2 - t_fit, 3), K=P2.K_initial)), flush=True)
+    m = max(10000, 100 * n)
+    rng = np.random.default_rng(0)
+    r, p = rng.gamma(P.eta, 1 / P.sigma, m), rng.beta(P.u, P.v, m)
+    t0 = time.perf_counter()
+    _, kms = sample_k(n, r, p, seed=1)
+    t_sk = time.perf_counter() - t0
+    print(json.dumps(dict(what="device_sampleK", n=n, numsamples=m, scores=m * n, wall_s=round(t_sk, 3),
+                          kernel_ms=round(kms, 2), scores_per_s=float(f"{m * n / (kms * 1e-3):.3g}"))), flush=True)
 
 
 def restatement(n):

@@ -262,6 +262,20 @@ int32_t rc_kmedoids_scan_split(rc_ctx *ctx, int64_t kmin, int64_t kmax, int64_t 
 int32_t rc_sample_k(int32_t device, int64_t n, int64_t m, const double *r, const double *p, uint64_t seed,
                     int64_t *K_out /* m, 1-based */, double *kernel_ms);
 
+/* generatemixture's oracle co-clustering matrix (src/utils.jl:130-143) for the caller's weight draws:
+ * out = (1/T)·Σ_t P_t P_tᵀ with P_t[i][j] = softmax_j(log w_tj + radius·x_ij/σ²), j < K (the centres are radius·e_j;
+ * every other factor of the pdfs cancels).  f64 MFMA product on the device; every entry is summed in one fixed order
+ * (ascending t, then j), so the result does not depend on iters_per_chunk, is the same run to run and is exactly
+ * symmetric.  n in 1..2^16 (the device holds the n² sum), K in 1..dim, radius > 0, sigma > 0,
+ * numiters >= 1: RC_ERR_ARG otherwise.  RC_ERR_DOMAIN for a non-finite point or radius·x/σ², or a weight row that is
+ * not finite, has a negative entry or no positive one (rows need not sum to 1).  iters_per_chunk: iterations per
+ * device pass, 0 = automatic (a workspace of about 1 GiB).  kernel_ms (may be NULL): device time.  No context: errors
+ * are read with a NULL context. */
+int32_t rc_oracle_coclustering(int32_t device, int64_t n, int64_t dim, const double *points /* n×dim row-major */,
+                               int64_t K, double radius, double sigma, int64_t numiters,
+                               const double *weights /* numiters×K */, int64_t iters_per_chunk /* 0 = automatic */,
+                               double *out /* n×n */, double *kernel_ms /* may be NULL */);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * The iteration loop of runsampler (src/mcmc.jl:533-556) as native host code: per iteration sample_r!, sample_p!
  * (src/mcmc.jl:80-155, on the build's counter-based scalar stream — DESIGN.md), sample_labels! (numMH split–merge

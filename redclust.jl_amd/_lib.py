@@ -79,7 +79,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, "redclust_hip.hip"), os.path.join(CSRC, "pointestimate.inc.hip"),
             os.path.join(CSRC, "kmedoids.inc.hip"),
-            os.path.join(CSRC, "chain.inc.hip"), os.path.join(CSRC, "chains.inc.hip"), os.path.join(CSRC, "samplek.inc.hip"), HEADER]
+            os.path.join(CSRC, "chain.inc.hip"), os.path.join(CSRC, "chains.inc.hip"), os.path.join(CSRC, "samplek.inc.hip"),
+            os.path.join(CSRC, "mixture.inc.hip"), HEADER]
     if not force and os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(s) for s in srcs):
         return SO
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-o", SO, srcs[0]]
@@ -166,6 +167,8 @@ SIGNATURES = {
     "rc_kmedoids_scan_split": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_uint64, _dp, _ip,
                                            np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS"), C.POINTER(RcWbStats)]),
     "rc_sample_k": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, _dp, _dp, C.c_uint64, _ip, C.POINTER(C.c_double)]),
+    "rc_oracle_coclustering": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, _dp, C.c_int64, C.c_double, C.c_double, C.c_int64,
+                                           _dp, C.c_int64, _dp, C.POINTER(C.c_double)]),
     "rc_layout_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rc_event_overhead_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "rc_kernel_timing": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -627,6 +630,22 @@ def sample_k(n: int, r, p, seed: int = 0, device: int = 0):
     if rc != RC_OK:
         raise _error(rc, L.rc_last_error(None).decode())
     return K, float(ms.value)
+
+
+def oracle_coclustering(points, K: int, radius: float, sigma: float, weights, iters_per_chunk: int = 0, device: int = 0):
+    """rc_oracle_coclustering: (n×n oracle co-clustering matrix, kernel ms) for n×dim points and numiters×K weights —
+    the device part of datagen.oracle_coclustering, which checks the arguments."""
+    L = lib()
+    X = np.ascontiguousarray(points, dtype=np.float64)
+    W = np.ascontiguousarray(weights, dtype=np.float64)
+    n, dim = X.shape
+    out = np.empty((n, n))
+    ms = C.c_double()
+    rc = L.rc_oracle_coclustering(int(device), n, dim, X.reshape(-1), int(K), float(radius), float(sigma), W.shape[0],
+                                  W.reshape(-1), int(iters_per_chunk), out.reshape(-1), C.byref(ms))
+    if rc != RC_OK:
+        raise _error(rc, L.rc_last_error(None).decode())
+    return out, float(ms.value)
 
 
 def pair_measures(a, b, device: int = 0) -> dict:

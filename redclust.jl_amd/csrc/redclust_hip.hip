@@ -7551,3 +7551,4 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "chain.inc.hip"
 #include "chains.inc.hip"
 #include "samplek.inc.hip"
+#include "mixture.inc.hip"

@@ -1,15 +1,96 @@
 """Synthetic benchmark inputs with the distribution of the reference's generatemixture
-(/root/reference/src/utils.jl:101-147) — the build's own generator (Julia's RNG stream cannot be reproduced;
-the O(5000·N²·K) oracle-coclustering loop of utils.jl:130-143 is skipped) — and the likelihood
-hyperparameters fitted from a labelling with fitprior's formulas (/root/reference/src/prior.jl:73-75,96-110)."""
+(/root/reference/src/utils.jl:101-147) — the build's own generator (Julia's RNG stream cannot be reproduced) — its
+oracle co-clustering matrix (utils.jl:130-143, O(5000·N²·K): built on the device by rc_oracle_coclustering)
+and the likelihood hyperparameters fitted from a labelling with fitprior's formulas
+(/root/reference/src/prior.jl:73-75,96-110)."""
 from __future__ import annotations
 
 import numpy as np
 from scipy.special import digamma, polygamma
 
+ORACLE_TAG = 0x4F524143   # "ORAC": the oracle's Dirichlet draws come from default_rng([ORACLE_TAG, seed])
+ORACLE_MAX_N = 1 << 16    # rc_oracle_coclustering holds the n² sum on the device
+
+
+def _int(name, v, lo):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < lo:
+        raise ValueError(f"{name} must be an integer >= {lo} (got {v!r}).")
+    return int(v)
+
+
+def _positive(name, v):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not (
+            np.isfinite(v) and v > 0):
+        raise ValueError(f"{name} must be positive and finite (got {v!r}).")
+    return float(v)
+
+
+def _oracle_inputs(points, K, alpha, radius, sigma, numiters, seed, weights):
+    """Checks the arguments of oracle_coclustering on the host; returns (points, K, radius, sigma, weights) as the
+    library takes them."""
+    X = np.asarray(points)
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1 or not np.issubdtype(X.dtype, np.number) \
+            or np.iscomplexobj(X):
+        raise ValueError("points must be a real N×dim matrix, one observation per row.")
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    n, dim = X.shape
+    if n > ORACLE_MAX_N:
+        raise ValueError(f"N must be at most {ORACLE_MAX_N} (the device holds the N² sum).")
+    K = _int("K", K, 1)
+    if K > dim:
+        raise ValueError("K must satisfy 1 ≤ K ≤ dim.")
+    radius, sigma = _positive("radius", radius), _positive("σ", sigma)
+    if not np.all(np.isfinite(X)):
+        raise ValueError("points must be finite.")
+    with np.errstate(over="ignore"):
+        if not np.all(np.isfinite(radius * X[:, :K] / sigma ** 2)):
+            raise ValueError("radius·x/σ² must be finite.")
+    if weights is None:
+        alpha = float(K) if alpha is None else _positive("α", alpha)
+        numiters = 5000 if numiters is None else _int("numiters", numiters, 1)
+        W = np.random.default_rng([ORACLE_TAG, _int("seed", seed, 0)]).dirichlet(np.full(K, alpha), size=numiters)
+    else:
+        if alpha is not None:
+            _positive("α", alpha)
+        W = np.asarray(weights)
+        if W.ndim != 2 or W.shape[1] != K or W.shape[0] < 1 or not np.issubdtype(W.dtype, np.number) \
+                or np.iscomplexobj(W):
+            raise ValueError("weights must be a real numiters×K matrix.")
+        if numiters is not None and _int("numiters", numiters, 1) != W.shape[0]:
+            raise ValueError(f"numiters ({numiters}) differs from the rows of weights ({W.shape[0]}).")
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if not np.all(np.isfinite(W)) or np.any(W < 0) or not np.all(W.max(axis=1) > 0):
+            raise ValueError("every weight row must be finite and non-negative with a positive entry.")
+    return X, K, radius, sigma, W
+
+
+def oracle_coclustering(points, K: int, *, alpha: float | None = None, radius: float = 1.0, sigma: float = 0.1,
+                        numiters: int | None = None, seed: int = 0, weights=None, iters_per_chunk: int = 0,
+                        device: int = 0) -> np.ndarray:
+    """generatemixture's oracle co-clustering matrix (utils.jl:130-143) for N×dim points (one observation per row):
+    (1/T)·Σ_t P_t P_tᵀ with P_t the posterior of the K components, centres radius·e_j and covariance σ²I, under
+    weights w_t ~ Dirichlet(K, α), α = K by default.  The weights come from a stream of their own,
+    default_rng([ORACLE_TAG, seed]), or are the caller's `weights` (numiters × K, non-negative, rows need not sum to 1;
+    numiters then defaults to its rows).  numiters defaults to 5000, as in the reference.
+
+    Computed on the device as softmax_j(log w_tj + radius·x_ij/σ²): finite where the reference's literal
+    pdf ratio is Inf/Inf or 0/0.  The result is exactly symmetric and the same bits for any
+    iters_per_chunk (iterations per device pass, 0 = automatic).  Returns an N×N float64 array."""
+    X, K, radius, sigma, W = _oracle_inputs(points, K, alpha, radius, sigma, numiters, seed, weights)
+    iters_per_chunk, device = _int("iters_per_chunk", iters_per_chunk, 0), _int("device", device, 0)
+    from ._lib import oracle_coclustering as _device_oracle
+    return _device_oracle(X, K, radius, sigma, W, iters_per_chunk, device)[0]
+
+
+_oracle_coclustering = oracle_coclustering   # generatemixture's flag of the same name shadows it there
+
 
 def generatemixture(N: int, K: int, *, alpha: float | None = None, dim: int | None = None, radius: float = 1.0,
-                    sigma: float = 0.1, seed: int = 0, dtype=np.float64, points_only: bool = False):
+                    sigma: float = 0.1, seed: int = 0, dtype=np.float64, points_only: bool = False,
+                    oracle_coclustering: bool = False, device: int = 0):
+    """Points, generating labels, mixture weights and (unless points_only) the distance matrix.  With
+    oracle_coclustering=True the dict also holds "oracle_coclustering", the reference's fifth output (T = 5000) for
+    the returned points, computed on `device`; it equals the standalone function with the same α, radius, σ and seed."""
     if N < 1:
         raise ValueError("N must be greater than 1.")
     if K < 1 or K > N:
@@ -27,8 +108,12 @@ def generatemixture(N: int, K: int, *, alpha: float | None = None, dim: int | No
     clusts = np.sort(rng.choice(K, size=N, p=probs)) + 1          # utils.jl:114 (sorted labels)
     pts = rng.normal(0.0, sigma, size=(N, dim))                   # utils.jl:123-128
     pts[np.arange(N), clusts - 1] += radius                       # centre k = radius·e_k, utils.jl:117-120
+    out = dict(points=pts, distancematrix=None, clusts=clusts.astype(np.int64), probs=probs)
+    if oracle_coclustering:
+        out["oracle_coclustering"] = _oracle_coclustering(pts, K, alpha=alpha, radius=radius, sigma=sigma, seed=seed,
+                                                          device=device)
     if points_only:   # the n×n matrix is left to the device (MCMCData(points), rc_create_from_points)
-        return dict(points=pts, distancematrix=None, clusts=clusts.astype(np.int64), probs=probs)
+        return out
     # pairwise Euclidean distances (utils.jl:144-145), built block-row-wise so that N = 32768 needs one N×N array
     sq = np.einsum("ij,ij->i", pts, pts)
     D = np.empty((N, N), dtype=np.float64)
@@ -53,7 +138,8 @@ def generatemixture(N: int, K: int, *, alpha: float | None = None, dim: int | No
             else:
                 D[j0:j1, i0:i1] = D[i0:i1, j0:j1].T
     np.fill_diagonal(D, 0.0)
-    return dict(points=pts, distancematrix=D if dtype == np.float64 else D.astype(dtype), clusts=clusts.astype(np.int64), probs=probs)
+    out["distancematrix"] = D if dtype == np.float64 else D.astype(dtype)
+    return out
 
 
 def _gamma_shape_mle(mean_x, mean_logx):

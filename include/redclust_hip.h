@@ -199,6 +199,10 @@ int32_t rc_bulk_kernel_info(rc_ctx *ctx, int32_t *which, double *algorithmic_byt
 /* The kernel's name as a profiler shows it (k_bulk_syml2<true, true>: logD derived, packed copy; k_bulk<long long, false>,
  * k_bulk_sym<false>, k_bulk_sym32 ...). */
 const char *rc_bulk_kernel_name(rc_ctx *ctx);
+/* k_bulk_syml2 with logD derived exists in two forms under that one name: 1 = this context's launches read the log table with
+ * the exponent folded in (its entries span at most four binades and option "fold_log_table" is 1); 0 = they derive the exponent
+ * per entry — a profiler shows those as k_bulk_syml2w — or the context does not derive logD.  Same integers either way. */
+int32_t rc_log_table_folded(rc_ctx *ctx);
 /* Force the kernel family: -1 automatic, 0 k_bulk (full read), 1 the symmetric kernel of this context (tests / measurements;
  * results are identical bit for bit). */
 int32_t rc_set_bulk_kernel(rc_ctx *ctx, int32_t which);
@@ -211,6 +215,9 @@ int32_t rc_set_bulk_kernel(rc_ctx *ctx, int32_t which);
  *   "chain_workers"  worker threads of rc_run_chain (0 = automatic: the host's cores shared by the chains of this process)
  *   "chain_depth"    iterations rc_run_chain keeps in flight (0 = automatic: 24)
  *   "chain_pipeline" 1 (default): the pipelined loop; 0: its synchronous form (the same chain bit for bit)
+ *   "fold_log_table" 1 (default): a context that derives logD and whose entries span at most four binades runs the row reduction
+ *                    that reads the exponent from its log table (k_bulk_syml2); 0: always the one that derives it per entry
+ *                    (k_bulk_syml2w; same integers)
  * No reference counterpart (the reference has no tuning knobs on this path). */
 int32_t rc_set_option(rc_ctx *ctx, const char *name, int64_t value);
 /* Internal point layout.  rc_set_state stores D and logD with the points of a cluster contiguous (a stable sort of

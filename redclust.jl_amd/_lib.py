@@ -144,6 +144,7 @@ SIGNATURES = {
     "rc_set_bulk_kernel": (C.c_int32, [C.c_void_p, C.c_int32]),
     "rc_set_option": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_int64]),
     "rc_bulk_kernel_name": (C.c_char_p, [C.c_void_p]),
+    "rc_log_table_folded": (C.c_int32, [C.c_void_p]),
     "rc_within_between": (C.c_int32, [C.c_void_p, C.POINTER(RcWbStats)]),
     "rc_run_chain": (C.c_int32, [C.c_void_p, C.POINTER(RcChainOptions), C.POINTER(RcChainOutputs)]),
     "rc_comm_unique_id": (C.c_int32, [C.c_void_p]),
@@ -385,11 +386,16 @@ class Context:
     def bulk_kernel_name(self) -> str:
         return self.L.rc_bulk_kernel_name(self.h).decode()
 
+    def log_table_folded(self) -> bool:
+        """rc_log_table_folded: k_bulk_syml2 reads the log table with the exponent folded in (False: k_bulk_syml2w derives it per entry)."""
+        return bool(self.L.rc_log_table_folded(self.h))
+
     def set_bulk_kernel(self, which):
         self._chk(self.L.rc_set_bulk_kernel(self.h, {"auto": -1, "perm": 0, "sym": 1}[which]))
 
     def set_option(self, name, value):
-        """rc_set_option: "prune" (-1 automatic / 0 / 1), "lds_point_cache" (0 / 1), "chain_workers", "chain_depth" (0 = automatic), "chain_pipeline" (0 / 1)."""
+        """rc_set_option: "prune" (-1 automatic / 0 / 1), "lds_point_cache" (0 / 1), "chain_workers", "chain_depth" (0 = automatic), "chain_pipeline" (0 / 1),
+        "fold_log_table" (1 / 0: 0 keeps a derived context on k_bulk_syml2w, the row reduction that derives the exponent per entry)."""
         self._chk(self.L.rc_set_option(self.h, name.encode(), int(value)))
 
     def run_chain(self, numiters, burnin, thin, numGibbs, numMH, seed, r0, p0, proposalsd_r, splitmerge="as_written",

@@ -190,6 +190,7 @@ struct View {
     int derived;               // 1: logD is not stored; Lq(i,j) = rc_qlog(Dq(i,j)) for i != j, 0 on the diagonal
     double qsD, qsL;           // 2^-eD, 2^eL
     const double2 *ltab;       // [128] table of rc_qlog (see there)
+    const double *vtab;        // [128 + 512] the same table with the exponent folded in (rc_qlog_prep_f): 2/c_j, then V[E & 3][j]; used by k_bulk_syml2 when the context's entries span at most four binades
     const double2 *flt;        // [128] table of rc_flog: (1/c_i rounded, -log of that double) — the logarithms of the scores
     int qeD;                   // eD
     long long *SD[3], *SL[3];  // three generations of the [kcap][ld] row-sum table (software pipelining)
@@ -364,6 +365,8 @@ __global__ __launch_bounds__(256) void k_pairwise(const double *__restrict__ pts
 // 16 VALU instructions per entry — six of them double-precision FMAs / multiplies — and one 16-byte table read (round 2's form of
 // the same idea took 23: a degree-6 polynomial, the scaling and the rounding as separate steps); the libm log is ~100.
 // ltab[j] = (2/c_j, T_j): 128 entries, rebuilt per context once eL is known (create_impl).
+// (k_bulk_syml2's streaming loop takes 13: contexts whose entries span at most four binades read v from a table indexed by
+// (exponent & 3, j) — rc_qlog_prep_f below; wider contexts run this form, in k_bulk_syml2w)
 // ---------------------------------------------------------------------------------------------------
 // Front end: the fixed-point entry is an integer below 2^52 (create_impl caps eD accordingly in the derived mode), so
 // OR-ing it into the mantissa of 2^52 and subtracting 2^52 converts it to a double exactly in two instructions; exponent,
@@ -414,6 +417,49 @@ __device__ __forceinline__ double rc_third_vgpr()
     unsigned lo, hi;
     asm volatile("v_mov_b32 %0, 0x55555555\n\tv_mov_b32 %1, 0x3fd55555" : "=v"(lo), "=v"(hi));
     return __hiloint2double((int)hi, (int)lo);
+}
+// The same function with the exponent folded into the table (k_bulk_syml2's streaming loop).  v = fma(kd, LN2S, T_j) depends only
+// on the binade k and the table index j, so a context whose positive entries span at most four consecutive binades (create_impl:
+// fold_ok) stores it: vtab = [2/c_j : 128 doubles][V[E & 3][j] = fma((double)(E - 1023 - eD), LN2S, T_j) : 512 doubles], E the
+// biased exponent of the entry as a double — four consecutive exponents differ in their low two bits, so (E & 3, j) are the nine
+// bits 13..21 of the high dword, one shift and one mask (a second mask gives j alone).  k_fold_table computes V on the device with
+// the very fma rc_qlog_raw uses, so w and Lq are the same bits; the shift, the bias subtraction, the int -> double conversion and
+// that fma leave the loop (6 instructions become 3; the 16-byte table read becomes two 8-byte reads).  The bias of the magic
+// number stays on the value as well: rc_qlog_raw_f returns bits(w), the callers take count x bits(1.5·2^52) off their sums
+// (64-bit sums are modular; the bias has a zero low dword, so that is one 32-bit subtraction per flushed sum).
+// dq = 0 (padding, masked entries) indexes slot 0 and gives a finite value the callers discard, as in rc_qlog_prep.
+#define RC_VTAB_N 640
+#define RC_QLOG_BIAS 0x4338000000000000ll     // bits(1.5·2^52)
+#define RC_QLOG_BIAS_HI 0x43380000u
+struct QlogPrepF { unsigned joff, voff; double m; };
+__device__ __forceinline__ QlogPrepF rc_qlog_prep_f(long long dq)
+{
+    const double x = __longlong_as_double(dq | 0x4330000000000000ll) - 0x1p52;
+    const unsigned t = (unsigned)__double2hiint(x) >> 10;
+    QlogPrepF P;
+    P.voff = t & 0xff8u;                                                    // 8 (128 (E & 3) + j): byte offset into V
+    P.joff = t & 0x3f8u;                                                    // 8 j: byte offset into the 2/c_j column
+    P.m = __builtin_amdgcn_frexp_mant(x);                                   // m / 2
+    return P;
+}
+__device__ __forceinline__ long long rc_qlog_raw_f(double m, double inv, double v, double sL, double third, double mquarter)
+{
+    const double r = fma(m, inv, -1.0);
+    double p = fma(r, mquarter, third);
+    p = fma(r, p, -1.0 / 2);
+    const double q = fma(r * r, p, r);                                      // log1p(r)
+    return __double_as_longlong(fma(q, sL, v));                             // Lq + RC_QLOG_BIAS
+}
+// V of one context: Emin = biased exponent (as a double) of the smallest positive entry; slot s holds the binade E in
+// [Emin, Emin + 3] with E & 3 == s
+__global__ void k_fold_table(const double2 *__restrict__ ltab, double *__restrict__ vtab, int Emin, int eD, double sL)
+{
+    const int t = (int)threadIdx.x;                                        // 512 threads
+    const int s_ = t >> 7, j = t & 127;
+    const int E = Emin + ((s_ - Emin) & 3);
+    const double kd = (double)(E - (eD + 0x3ff));
+    vtab[128 + t] = fma(kd, 0.69314718055994530942 * sL, ltab[j].y);
+    if (t < 128) vtab[t] = ltab[t].x;
 }
 __device__ __forceinline__ long long rc_qlog_finish(long long dq, const QlogPrep &P, double2 t, double sL)
 {
@@ -481,9 +527,9 @@ __device__ __forceinline__ long long rc_load_L(const View &V, int row, int col, 
 }
 
 // one-off scan for the derived mode: smallest off-diagonal Dq (must be > 0) and largest |log| (fixes eL)
-__global__ void k_derived_scan(const long long *__restrict__ Dq, int n, int ld, int eD, long long *min_dq, u64 *maxabs_bits)
+__global__ void k_derived_scan(const long long *__restrict__ Dq, int n, int ld, int eD, long long *min_dq, u64 *maxabs_bits, long long *max_dq)
 {
-    long long mn = 0x7fffffffffffffffll;
+    long long mn = 0x7fffffffffffffffll, mxq = 0;
     double mx = 0.0;
     const size_t total = (size_t)n * n;
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
@@ -491,9 +537,11 @@ __global__ void k_derived_scan(const long long *__restrict__ Dq, int n, int ld, 
         if (i == j) continue;
         const long long dq = Dq[i * ld + j];
         mn = min(mn, dq);
+        mxq = max(mxq, dq);
         if (dq > 0) mx = fmax(mx, fabs(log(ldexp((double)dq, -eD))));   // (one-off; the table of rc_qlog needs eL, which this fixes)
     }
     atomicMin((long long *)min_dq, mn);
+    atomicMax((long long *)max_dq, mxq);
     atomicMax((unsigned long long *)maxabs_bits, (unsigned long long)__double_as_longlong(mx));
 }
 
@@ -1677,13 +1725,22 @@ __device__ __forceinline__ long long wave_from_prev64(long long v)
     return (long long)(((u64)hi << 32) | lo);
 }
 
-template <bool DERIVED, bool PACK>
+// FOLD (derived logs only): the log table with the exponent folded in (rc_qlog_prep_f; tab = [128 + 512] doubles), the rounding bias
+// taken off the sums where they are flushed instead of off every entry, and the rare-lane work (atomic addresses, zeroing the values
+// of lanes that are not whole) behind uniform branches.  `bounce` may then be the wave's p-buffer itself: it is used only by the
+// direction-2 write-out, after the last transposed read of a 64-row half (flush1, which can run between a group's writes and its
+// read, exchanges through ds_bpermute instead: no LDS storage).
+template <bool DERIVED, bool PACK, bool FOLD>
 __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8][RC_S2_PITCH], wave-private */, long long *bounce /* [128], wave-private */,
                                            const double2 *tab /* [128], block-shared */,
                                            int wgen, int sgen, int first_unit, int end_unit /* this wave's units: [first_unit, end_unit) of V.ufast */,
                                            long long *pf_out = nullptr)
 {
     typedef typename S2Raw<PACK>::T raw_t;
+#ifndef RC_S2_STEPS
+#define RC_S2_STEPS 14   // what rides on the folded table, for per-step measurements (tools/build_variants.sh): 2 bias per flush, 4 atomic addresses behind the branch, 8 no selects in units of whole lanes
+#endif
+    constexpr bool LATE = FOLD && (RC_S2_STEPS & 2), BR3 = FOLD && (RC_S2_STEPS & 4), BR4 = FOLD && (RC_S2_STEPS & 8);
     RC_PF(long long pf_wait = 0; long long pf_tiles = 0; long long pf_setup = 0; long long pf_log = 0; long long pf_d2 = 0; long long pf_issue = 0; long long pf_ldsw = 0; long long pf_d1 = 0;)
     RC_PF(const long long pf_t0 = __builtin_amdgcn_s_memtime(); const long long pf_r0 = __builtin_amdgcn_s_memrealtime();)
     (void)pf_out;
@@ -1721,7 +1778,13 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
 #ifndef RC_S2_LOGS
 #define RC_S2_LOGS 2     // logs evaluated together (table reads first, then the arithmetic): 4 or 2 (4 spills, as above)
 #endif
-    constexpr int NP = RC_S2_NP;
+#ifndef RC_S2_NP_FOLD
+#define RC_S2_NP_FOLD 2  // the same two for the folded kernel, which has ~20 registers to spare
+#endif
+#ifndef RC_S2_LOGS_FOLD
+#define RC_S2_LOGS_FOLD 2
+#endif
+    constexpr int NP = FOLD ? RC_S2_NP_FOLD : RC_S2_NP;
     raw_t d[NP][2];
     ll2 l[NP][2];
     // the rows are requested strictly in order — down a unit, then on into the wave's next unit — so the (uniform) address of the
@@ -1814,25 +1877,53 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
         // bytes, but one instruction adds only one of them: 16 half-used requests each), its direction-2 totals the rows
         // 8 (l & 7) + (l >> 3) (64 different requests per instruction): both go through a 1 KiB bounce in the wave's LDS first,
         // after which lane l holds column c0 + l and c0 + 64 + l, or row h0 + l — 8 full requests per instruction.
+        int nacc = 0;                                                   // FOLD: rows added into aL0 / aL1 since the last flush (uniform): each carries the bias
         auto flush1 = [&]() {
             if (cur >= 0) {
                 long long *const rowD = SD + (size_t)cur * ld + c0, *const rowL = SL + (size_t)cur * ld + c0;
+                long long d0, d1, l0, l1;
+                if constexpr (FOLD) {
+                    // lane l takes column l from lane l >> 1 and column 64 + l from lane 32 + (l >> 1) (all 64 lanes are active here)
+                    const int i0 = (lane >> 1) << 2, i1 = i0 + 128;
+                    auto from = [](int idx, long long v) {
+                        const unsigned lo = (unsigned)__builtin_amdgcn_ds_bpermute(idx, (int)(unsigned)(u64)v), hi = (unsigned)__builtin_amdgcn_ds_bpermute(idx, (int)(unsigned)((u64)v >> 32));
+                        return (long long)(((u64)hi << 32) | lo);
+                    };
+                    const bool odd = lane & 1;
+                    const long long fix = LATE ? (long long)((u64)((unsigned)nacc * RC_QLOG_BIAS_HI) << 32) : 0ll;
+                    const long long bL0 = aL0 - fix, bL1 = aL1 - fix;
+                    const long long p0 = from(i0, aD0), p1 = from(i0, aD1), p2 = from(i1, aD0), p3 = from(i1, aD1);
+                    d0 = odd ? p1 : p0; d1 = odd ? p3 : p2;
+                    const long long q0 = from(i0, bL0), q1 = from(i0, bL1), q2 = from(i1, bL0), q3 = from(i1, bL1);
+                    l0 = odd ? q1 : q0; l1 = odd ? q3 : q2;
+                } else {
                 __builtin_amdgcn_wave_barrier();
                 *(ll2 *)&bounce[2 * lane] = ll2{aD0, aD1};
                 __builtin_amdgcn_wave_barrier();
-                const long long d0 = bounce[lane], d1 = bounce[64 + lane];
+                d0 = bounce[lane]; d1 = bounce[64 + lane];
                 __builtin_amdgcn_wave_barrier();
                 *(ll2 *)&bounce[2 * lane] = ll2{aL0, aL1};
                 __builtin_amdgcn_wave_barrier();
-                const long long l0 = bounce[lane], l1 = bounce[64 + lane];
+                l0 = bounce[lane]; l1 = bounce[64 + lane];
                 __builtin_amdgcn_wave_barrier();
+                }
                 if (d0) add64(rowD + lane, d0);
                 if (d1) add64(rowD + 64 + lane, d1);
                 if (l0) add64(rowL + lane, l0);
                 if (l1) add64(rowL + 64 + lane, l1);
             }
             aD0 = aD1 = aL0 = aL1 = 0;
+            nacc = 0;
         };
+        // FOLD: pre-added values of cluster A / B in one row (each carries the bias): two per whole lane, one for a donor, one more for
+        // the lane a donor hands its second column to (always whole)
+        int cntA = 0, cntB = 0;
+        if constexpr (LATE) {
+            const u64 bW = __ballot(whole), bDn = __ballot(donor);
+            const u64 mA = bW & ~bB;
+            cntA = 2 * __popcll(mA) - __popcll(bDn & mA) + __popcll((bDn << 1) & mA);
+            cntB = 2 * __popcll(bB) - __popcll(bDn & bB) + __popcll((bDn << 1) & bB);
+        }
         for (int h0 = a0; h0 < a1; h0 += 64) {                            // 64-row halves (direction-2 totals live one row per lane)
             const int h1 = min(h0 + 64, a1);
             const int rowslots = (h0 + lane < h1) ? slot[h0 + lane] : -1; // slot of row h0 + lane (read back with readlane)
@@ -1859,6 +1950,22 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
                     RC_PF(const long long pl0 = __builtin_amdgcn_s_memtime();)
                     if (RC_S2_EXP & 2) {
                         y[0] = x[0]; y[1] = x[1];
+                    } else if (FOLD) {                                    // (as below, through the table with the exponent folded in)
+                        const char *const ftab = (const char *)tab;
+#pragma unroll
+                        for (int g_ = 0; g_ < 4; g_ += RC_S2_LOGS_FOLD) {
+                            QlogPrepF pp[RC_S2_LOGS_FOLD];
+                            double ti[RC_S2_LOGS_FOLD], tv[RC_S2_LOGS_FOLD];
+#pragma unroll
+                            for (int u = 0; u < RC_S2_LOGS_FOLD; ++u) pp[u] = rc_qlog_prep_f(((g_ + u) & 1) ? x[(g_ + u) >> 1].y : x[(g_ + u) >> 1].x);
+#pragma unroll
+                            for (int u = 0; u < RC_S2_LOGS_FOLD; ++u) { ti[u] = *(const double *)(ftab + pp[u].joff); tv[u] = *(const double *)(ftab + 1024 + pp[u].voff); }
+#pragma unroll
+                            for (int u = 0; u < RC_S2_LOGS_FOLD; ++u) {
+                                const long long v = rc_qlog_raw_f(pp[u].m, ti[u], tv[u], qsL, qthird, qmq) - (LATE ? 0ll : RC_QLOG_BIAS);
+                                if ((g_ + u) & 1) y[(g_ + u) >> 1].y = v; else y[(g_ + u) >> 1].x = v;
+                            }
+                        }
                     } else if (DERIVED) {                                 // RC_S2_LOGS logs together: table reads first, then the arithmetic
 #pragma unroll
                         for (int g_ = 0; g_ < 4; g_ += RC_S2_LOGS) {
@@ -1882,12 +1989,45 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
                     if (diag) {   // strictly upper triangle: element (row, col) lives iff col > row (the logs of dead entries are garbage: masked too)
 #pragma unroll
                         for (int u = 0; u < 2; ++u) {
-                            if (!(colx > ar + u && colx < V.n)) { x[u].x = 0; y[u].x = 0; }
-                            if (!(coly > ar + u && coly < V.n)) { x[u].y = 0; y[u].y = 0; }
+                            if (!(colx > ar + u && colx < V.n)) { x[u].x = 0; y[u].x = LATE ? RC_QLOG_BIAS : 0; }   // (LATE: every value carries the bias)
+                            if (!(coly > ar + u && coly < V.n)) { x[u].y = 0; y[u].y = LATE ? RC_QLOG_BIAS : 0; }
                         }
                     }
                     RC_PF(asm volatile("" ::: "memory"); const long long pw0 = __builtin_amdgcn_s_memtime(); pf_log += pw0 - pl0;)
                     // direction 2: one pre-added value per lane, row and matrix into the wave's buffer
+                    if constexpr (BR4) {
+                        long long vd[2], vl[2];
+#pragma unroll
+                        for (int u = 0; u < 2; ++u) {
+                            vd[u] = x[u].x + x[u].y; vl[u] = y[u].x + y[u].y;
+                            if (any_donor) {
+                                const long long gd = wave_from_prev64(donor ? x[u].y : 0), gl = wave_from_prev64(donor ? y[u].y : 0);
+                                vd[u] = (donor ? x[u].x : vd[u]) + gd; vl[u] = (donor ? y[u].x : vl[u]) + gl;
+                            }
+                        }
+                        if (any_odd) {   // uniform, rare (a real branch: the asm statements keep the selects and the address arithmetic from being hoisted in front of it)
+                            asm volatile("; lanes that are not whole");
+                            if (!whole) {
+                                vd[0] = vd[1] = vl[0] = vl[1] = 0;
+                                int s0 = cs0, s1 = cs1;
+                                if (BR3) asm volatile("" : "+v"(s0), "+v"(s1));
+                                unsigned nbias = 0;                     // -bias, high dword: one scalar constant for the four subtractions
+                                if (LATE) asm volatile("s_mov_b32 %0, 0xbcc80000" : "=s"(nbias));
+                                auto unbias = [nbias](long long v) { return (long long)((u64)(unsigned)(u64)v | ((u64)((unsigned)((u64)v >> 32) + nbias) << 32)); };
+#pragma unroll
+                                for (int u = 0; u < 2; ++u) {
+                                    const int row = ar + u;
+                                    add64(SD + (size_t)s0 * ld + row, x[u].x); add64(SL + (size_t)s0 * ld + row, unbias(y[u].x));
+                                    add64(SD + (size_t)s1 * ld + row, x[u].y); add64(SL + (size_t)s1 * ld + row, unbias(y[u].y));
+                                }
+                            }
+                        }
+#pragma unroll
+                        for (int u = 0; u < 2; ++u) {
+                            pD[(2 * q + u) * RC_S2_PITCH + lane] = vd[u];
+                            pL[(2 * q + u) * RC_S2_PITCH + lane] = vl[u];
+                        }
+                    } else {
                     if (!(RC_S2_EXP & 4)) {
 #pragma unroll
                         for (int u = 0; u < 2; ++u) {
@@ -1903,24 +2043,30 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
                     }
                     if (any_odd) {   // uniform, rare: the elements of the lanes that are not whole
                         if (!whole) {
+                            int s0 = cs0, s1 = cs1;
+                            if (BR3) asm volatile("" : "+v"(s0), "+v"(s1));
+                            const long long ub = LATE ? RC_QLOG_BIAS : 0ll;
 #pragma unroll
                             for (int u = 0; u < 2; ++u) {
                                 const int row = ar + u;
-                                add64(SD + (size_t)cs0 * ld + row, x[u].x); add64(SL + (size_t)cs0 * ld + row, y[u].x);
-                                add64(SD + (size_t)cs1 * ld + row, x[u].y); add64(SL + (size_t)cs1 * ld + row, y[u].y);
+                                add64(SD + (size_t)s0 * ld + row, x[u].x); add64(SL + (size_t)s0 * ld + row, y[u].x - ub);
+                                add64(SD + (size_t)s1 * ld + row, x[u].y); add64(SL + (size_t)s1 * ld + row, y[u].y - ub);
                             }
                         }
+                    }
                     }
                     RC_PF(const long long pd0 = __builtin_amdgcn_s_memtime(); pf_ldsw += pd0 - pw0;)
                     // direction 1
                     if (RC_S2_EXP & 8) { aD0 += x[0].x ^ x[1].y; aL0 += y[0].x ^ y[1].y; } else if (((chg >> (ar - h0)) & 3ull) == 0) {
                         aD0 += x[0].x + x[1].x; aD1 += x[0].y + x[1].y; aL0 += y[0].x + y[1].x; aL1 += y[0].y + y[1].y;
+                        nacc += 2;
                     } else {
 #pragma unroll
                         for (int u = 0; u < 2; ++u) {
                             const int sr = __builtin_amdgcn_readlane(rowslots, ar + u - h0);
                             if (sr != cur) { flush1(); cur = sr; }
                             aD0 += x[u].x; aD1 += x[u].y; aL0 += y[u].x; aL1 += y[u].y;
+                            nacc += 1;
                         }
                     }
                     RC_PF(asm volatile("" ::: "memory"); pf_d1 += __builtin_amdgcn_s_memtime() - pd0;)
@@ -1972,8 +2118,9 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
                 __builtin_amdgcn_wave_barrier();
                 bounce[mine_] = rDA; bounce[64 + mine_] = rLA;
                 __builtin_amdgcn_wave_barrier();
-                const long long tD = bounce[lane], tL = bounce[64 + lane];
+                long long tD = bounce[lane], tL = bounce[64 + lane];
                 __builtin_amdgcn_wave_barrier();
+                if (LATE) tL -= (long long)((u64)((unsigned)cntA * RC_QLOG_BIAS_HI) << 32);
                 if (row < h1) {
                     if (tD) add64(SD + (size_t)dsA * ld + row, tD);
                     if (tL) add64(SL + (size_t)dsA * ld + row, tL);
@@ -1981,8 +2128,9 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
                 if (hasB) {
                     bounce[mine_] = rDB; bounce[64 + mine_] = rLB;
                     __builtin_amdgcn_wave_barrier();
-                    const long long uD = bounce[lane], uL = bounce[64 + lane];
+                    long long uD = bounce[lane], uL = bounce[64 + lane];
                     __builtin_amdgcn_wave_barrier();
+                    if (LATE) uL -= (long long)((u64)((unsigned)cntB * RC_QLOG_BIAS_HI) << 32);
                     if (row < h1) {
                         if (uD) add64(SD + (size_t)dsB * ld + row, uD);
                         if (uL) add64(SL + (size_t)dsB * ld + row, uL);
@@ -2015,21 +2163,47 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
 // every row in flight (one spilled class mask made each 8-row group of a two-cluster unit wait for all its loads: 5,400 cycles
 // instead of 730) — which is why the ragged units have their own launch (k_bulk_syml_list) instead of sharing this kernel's
 // register allocation.
-template <bool DERIVED, bool PACK>
-__global__ __launch_bounds__(256, RC_SYML_MINWAVES) RC_S2_VGPR_CAP void k_bulk_syml2(View V, int wgen, int sgen, int cgen)
+// With the exponent folded into the log table (FOLD) the block holds [2/c_j 1 KiB][V 4 KiB][4 waves x 8.5 KiB of p-buffers] = 39 KiB:
+// the bounces are the first KiB of each wave's p-buffer (see syml2_fast).
+template <bool DERIVED, bool PACK, bool FOLD>
+__device__ __forceinline__ void syml2_block(const View &V, int wgen, int sgen, int cgen)
 {
-    constexpr int TABLL = 256 * RC_S2_TABREP;        // long longs of the log table (128 entries x 16 B x copies)
-    __shared__ __attribute__((aligned(16))) long long lds[TABLL + 4 * (2 * 8 * RC_S2_PITCH + 128)];
+    constexpr int TABLL = FOLD ? RC_VTAB_N : 256 * RC_S2_TABREP;   // long longs of the log table (128 entries x 16 B x copies; FOLD: 128 + 512 doubles)
+    constexpr int WAVELL = 2 * 8 * RC_S2_PITCH;
+    __shared__ __attribute__((aligned(16))) long long lds[TABLL + 4 * (WAVELL + (FOLD ? 0 : 128))];
+    // The folded kernel needs 105 registers, and must still ALLOCATE the resolver's 128 (granules of 8; naming v125 does it).  Measured,
+    // same code, sweeps/s of the headline pipeline by allocation: 112 -> 16.3-16.5 k, 120 -> 16.2 k, 128 -> 17.9 k (the kernel before
+    // the fold, 128: 17.6 k), while the launch alone is as fast or faster with fewer: beside a smaller allocation the resolver's
+    // launches last 41.6 us instead of 33.0 and start 10.7 us instead of 6.5 after the reduction they follow.  A wave's registers are
+    // one contiguous range: the hole a retired wave of 112 leaves takes the next reduction wave, never a resolver wave.
+#ifndef RC_S2_FOLD_SMALL_ALLOC
+    if (FOLD) asm volatile("" ::: "v125");
+#endif
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int w = (int)blockIdx.x * 4 + wv;
     double2 *tab = (double2 *)lds;
-    if (DERIVED)
+    if (FOLD)
+        for (int q = threadIdx.x; q < RC_VTAB_N; q += 256) ((double *)lds)[q] = V.vtab[q];
+    else if (DERIVED)
         for (int q = threadIdx.x; q < 128 * RC_S2_TABREP; q += 256) tab[q] = V.ltab[q / RC_S2_TABREP];
     __syncthreads();
     long long *pf = nullptr;
     RC_PF(if (w < 8192 - 256) pf = (long long *)((char *)V.work[cgen] + 64) + (size_t)w * 16;)
-    syml2_fast<DERIVED, PACK>(V, lds + TABLL + (size_t)wv * (2 * 8 * RC_S2_PITCH), lds + TABLL + 4 * (2 * 8 * RC_S2_PITCH) + (size_t)wv * 128, tab, wgen, sgen, V.wfast[w], V.wfast[w + 1], pf);
+    long long *const pb = lds + TABLL + (size_t)wv * WAVELL;
+    syml2_fast<DERIVED, PACK, FOLD>(V, pb, FOLD ? pb : lds + TABLL + 4 * WAVELL + (size_t)wv * 128, tab, wgen, sgen, V.wfast[w], V.wfast[w + 1], pf);
     (void)cgen;
+}
+// k_bulk_syml2: derived logs through the table with the exponent folded in (contexts whose entries span at most four binades);
+// k_bulk_syml2w: the exponent derived per entry — any range
+template <bool DERIVED, bool PACK>
+__global__ __launch_bounds__(256, RC_SYML_MINWAVES) RC_S2_VGPR_CAP void k_bulk_syml2(View V, int wgen, int sgen, int cgen)
+{
+    syml2_block<DERIVED, PACK, DERIVED>(V, wgen, sgen, cgen);
+}
+template <bool DERIVED, bool PACK>
+__global__ __launch_bounds__(256, RC_SYML_MINWAVES) RC_S2_VGPR_CAP void k_bulk_syml2w(View V, int wgen, int sgen, int cgen)
+{
+    syml2_block<DERIVED, PACK, false>(V, wgen, sgen, cgen);
 }
 
 // the units k_bulk_syml2's fast path does not take (a ragged last column block: n not a multiple of 128), by the round-2 unit code,
@@ -4649,6 +4823,9 @@ struct rc_ctx {
     struct S2Alt { int4 *ufast = nullptr, *uslow = nullptr; int *wfast = nullptr, *wslow = nullptr; int nfast = 0, nslow = 0, blocks = 0; } s2alt;
     bool derived = false;               // logD derived from Dq on the fly (rc_qlog), not stored
     double2 *ltab = nullptr;            // device table of rc_qlog
+    double *vtab = nullptr;             // device table of rc_qlog with the exponent folded in (k_fold_table; View.vtab)
+    bool fold_ok = false;               // derived mode: the off-diagonal entries span at most four binades, so k_bulk_syml2 may index vtab by (E & 3, j)
+    int opt_fold = 1;                   // rc_set_option "fold_log_table": 0 = always the unfolded kernel (k_bulk_syml2w)
     double2 *flt = nullptr;             // device table of rc_flog
     int n_relayouts = 0;                // re-layouts done so far (rc_set_state + automatic ones)
     int bits = 64;
@@ -4795,7 +4972,7 @@ static View make_view(const rc_ctx *c)
     V.n = c->n; V.ld = c->ld; V.kcap = c->kcap; V.maxb = c->maxb; V.used_scratch = c->used_scratch; V.wide_scratch = c->wide_scratch;
     V.cu_cache = c->opt_cu_cache; V.wc = c->wc; V.wc_always = c->wc_always; V.ldw = (c->n + RC_PTS - 1) / RC_PTS * RC_PTS;
     V.Dq = c->Dq; V.Lq = c->Lq; V.Dq48 = c->Dq48; V.bits = c->bits; V.diagq = c->diagq; V.pi = c->pi;
-    V.derived = c->derived ? 1 : 0; V.qsD = std::ldexp(1.0, -c->eD); V.qsL = std::ldexp(1.0, c->eL); V.ltab = c->ltab; V.flt = c->flt; V.qeD = c->eD;
+    V.derived = c->derived ? 1 : 0; V.qsD = std::ldexp(1.0, -c->eD); V.qsL = std::ldexp(1.0, c->eL); V.ltab = c->ltab; V.vtab = c->vtab; V.flt = c->flt; V.qeD = c->eD;
     for (int g = 0; g < 3; ++g) { V.SD[g] = c->SD[g]; V.SL[g] = c->SL[g]; }
     for (int g = 0; g < 2; ++g) { V.perm[g] = c->perm[g]; V.pslot[g] = c->pslot[g]; V.keys[g] = c->keys[g]; V.arrive[g] = c->arrive[g]; V.snap[g] = c->lsnap[g]; V.work[g] = c->work[g]; V.cword[g] = c->cword[g]; }
     V.rec = c->rec;
@@ -4834,7 +5011,7 @@ static void free_all(rc_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->dev);
-    void *ptrs[] = {c->Dq48, c->ltab, c->flt, c->Dq, c->Lq, c->Dq_src, c->Lq_src, c->diag_src, c->pi, c->ipi, c->diagq, c->SD[0], c->SD[1], c->SD[2], c->SL[0], c->SL[1], c->SL[2], c->slot_of,
+    void *ptrs[] = {c->Dq48, c->ltab, c->vtab, c->flt, c->Dq, c->Lq, c->Dq_src, c->Lq_src, c->diag_src, c->pi, c->ipi, c->diagq, c->SD[0], c->SD[1], c->SD[2], c->SL[0], c->SL[1], c->SL[2], c->slot_of,
                     c->slot_size, c->slot_label, c->slot_pos, c->slot_act, c->perm[0], c->perm[1], c->pslot[0],
                     c->pslot[1], c->lsnap[0], c->lsnap[1], c->work[0], c->work[1], c->cword[0], c->cword[1], c->rec, c->A, c->keys[0], c->keys[1], c->arrive[0], c->arrive[1], c->sc, c->blocks,
                     c->counts, c->cc_out, c->snap, c->d_moves, c->used_scratch, c->wide_scratch, c->wc, c->ufast, c->uslow, c->wfast, c->wslow, c->s2alt.ufast, c->s2alt.uslow, c->s2alt.wfast, c->s2alt.wslow};
@@ -5026,6 +5203,7 @@ static int32_t create_impl(rc_ctx *c, int64_t n, const double *D, const double *
     HIPCHK2(hipMalloc(&c->pi, (size_t)n * sizeof(int)));
     HIPCHK2(hipMalloc(&c->ipi, (size_t)n * sizeof(int)));
     HIPCHK2(hipMalloc(&c->ltab, 128 * sizeof(double2)));
+    HIPCHK2(hipMalloc(&c->vtab, RC_VTAB_N * sizeof(double)));
     {   // table of rc_flog (see there): interval i of z's offset from 0.6875 in units of 2^-7 of the mantissa; long double on the host
         double2 ft[128];
         for (int i = 0; i < 128; ++i) {
@@ -5104,6 +5282,7 @@ static int32_t create_impl(rc_ctx *c, int64_t n, const double *D, const double *
         return fail(c, RC_ERR_DOMAIN, "off-diagonal entries of D must be positive: log D = -Inf / NaN otherwise (duplicate observations? remove them or add a small jitter).");
     }
     double maxD, maxL = 0;
+    long long dq_min = 0, dq_max = 0;                                     // derived mode: range of the off-diagonal entries (k_derived_scan)
     std::memcpy(&maxD, &hmx[0], 8);
     c->eD = quant_exponent(n, maxD, c->bits);
     if (derived && maxD > 0.0) {
@@ -5117,17 +5296,19 @@ static int32_t create_impl(rc_ctx *c, int64_t n, const double *D, const double *
     if (c->bits == 64) k_quantize<long long><<<gb, 256, 0, s>>>(tmpD, (int)n, c->ld, c->eD, (long long *)c->Dq_src, c->diag_src);
     else k_quantize<int><<<gb, 256, 0, s>>>(tmpD, (int)n, c->ld, c->eD, (int *)c->Dq_src, c->diag_src);
     if (derived) {
-        long long *mn = nullptr;
-        HIPCHK2(hipMalloc(&mn, sizeof(long long)));
-        const long long big = 0x7fffffffffffffffll;
-        HIPCHK2(hipMemcpyAsync(mn, &big, sizeof(big), hipMemcpyHostToDevice, s));
-        k_derived_scan<<<gb, 256, 0, s>>>((const long long *)c->Dq_src, (int)n, c->ld, c->eD, mn, mx + 1);
-        long long hmn = 0;
-        hipError_t e1 = hipMemcpyAsync(&hmn, mn, sizeof(hmn), hipMemcpyDeviceToHost, s);
+        long long *mn = nullptr;                                         // [0] smallest, [1] largest off-diagonal entry
+        HIPCHK2(hipMalloc(&mn, 2 * sizeof(long long)));
+        const long long big[2] = {0x7fffffffffffffffll, 0};
+        HIPCHK2(hipMemcpyAsync(mn, big, sizeof(big), hipMemcpyHostToDevice, s));
+        k_derived_scan<<<gb, 256, 0, s>>>((const long long *)c->Dq_src, (int)n, c->ld, c->eD, mn, mx + 1, mn + 1);
+        long long hmn2[2] = {0, 0};
+        hipError_t e1 = hipMemcpyAsync(hmn2, mn, sizeof(hmn2), hipMemcpyDeviceToHost, s);
         hipError_t e2 = hipMemcpyAsync(&hmx[1], mx + 1, sizeof(u64), hipMemcpyDeviceToHost, s);
         hipError_t e3 = hipStreamSynchronize(s);
         (void)hipFree(mn);
         HIPCHK2(e1); HIPCHK2(e2); HIPCHK2(e3);
+        const long long hmn = hmn2[0];
+        dq_min = hmn2[0]; dq_max = hmn2[1];
         // log(Dq·2^-eD) differs from log(D) by the relative rounding of the entry, 1/(2·Dq): derive only when every
         // off-diagonal entry is at least 2^32 quanta (error ≤ 1.2e-10 per entry, ≤ 1e-12 for entries within 2^-10 of the
         // largest); a matrix with (near-)zero distances keeps logD of the exact doubles
@@ -5172,6 +5353,14 @@ static int32_t create_impl(rc_ctx *c, int64_t n, const double *D, const double *
             tab[2 * j + 1] = (double)(rintl(logl(cj) * ldexpl(1.0L, c->eL)) + 0x1.8p52L);
         }
         HIPCHK2(hipMemcpy(c->ltab, tab, sizeof(tab), hipMemcpyHostToDevice));
+    }
+    c->fold_ok = false;
+    if (derived && dq_min > 0) {
+        // rc_qlog_prep_f: every entry is an integer below 2^52, exact as a double — its biased exponent is 1023 + floor(log2 dq).
+        // At most four consecutive binades: the table with the exponent folded in serves k_bulk_syml2; more: k_bulk_syml2w derives it
+        const int Emin = 1023 + (63 - __builtin_clzll((unsigned long long)dq_min)), Emax = 1023 + (63 - __builtin_clzll((unsigned long long)dq_max));
+        c->fold_ok = Emax - Emin <= 3;
+        if (c->fold_ok) k_fold_table<<<1, 512, 0, s>>>(c->ltab, c->vtab, Emin, c->eD, std::ldexp(1.0, c->eL));
     }
     if (derived && !(rc_env_diag("RC_NO_LQ_COPY") && atoi(rc_env_diag("RC_NO_LQ_COPY")))) {
         // random-access copy of the derived values for the resolver (see k_derived_fill); the row reduction ignores it
@@ -5263,6 +5452,8 @@ static int sym_variant_of(const rc_ctx *c) { return c->sym_variant >= 0 ? c->sym
 // the wave-autonomous kernels (three 40-42 KiB blocks per CU) are the symmetric kernel of this context: 3 = k_bulk_syml2 (round 3),
 // 2 = k_bulk_syml (round 2)
 static bool uses_syml(const rc_ctx *c) { return sym_variant_of(c) >= 2; }
+// k_bulk_syml2 reads the log table with the exponent folded in (rc_qlog_prep_f); otherwise a derived context runs k_bulk_syml2w
+static bool syml2_folds(const rc_ctx *c) { return c->derived && c->fold_ok && c->opt_fold != 0; }
 
 // Unit lists of k_bulk_syml2 for `cap_blocks` resident 4-wave blocks.  Column block J (128 columns) holds the rows 0 .. 128 J + 127
 // of the upper triangle.  Rows [0, 128 J) lie entirely above the diagonal block: FAST units of g rows (a multiple of 8; the rest of a
@@ -6001,7 +6192,11 @@ static int32_t enqueue_bulk(rc_ctx *c, const View &V, long long t)
                 V2.nfast = c->s2alt.nfast; V2.nslow = c->s2alt.nslow;
                 s2_blocks = c->s2alt.blocks; s2_nslow = c->s2alt.nslow;
             }
-            if (c->derived && c->Dq48) { auto kf_ = k_bulk_syml2<true, true>; RC_BULK_LAUNCH(kf_, s2_blocks, 256, c->syml_pad, V2, (int)(t % 3), (int)(t & 1), (int)(t & 1)); }
+            if (c->derived && !syml2_folds(c)) {   // entries over more than four binades (or rc_set_option "fold_log_table" 0): the exponent is derived per entry
+                if (c->Dq48) { auto kf_ = k_bulk_syml2w<true, true>; RC_BULK_LAUNCH(kf_, s2_blocks, 256, c->syml_pad, V2, (int)(t % 3), (int)(t & 1), (int)(t & 1)); }
+                else { auto kf_ = k_bulk_syml2w<true, false>; RC_BULK_LAUNCH(kf_, s2_blocks, 256, c->syml_pad, V2, (int)(t % 3), (int)(t & 1), (int)(t & 1)); }
+            }
+            else if (c->derived && c->Dq48) { auto kf_ = k_bulk_syml2<true, true>; RC_BULK_LAUNCH(kf_, s2_blocks, 256, c->syml_pad, V2, (int)(t % 3), (int)(t & 1), (int)(t & 1)); }
             else if (c->derived) { auto kf_ = k_bulk_syml2<true, false>; RC_BULK_LAUNCH(kf_, s2_blocks, 256, c->syml_pad, V2, (int)(t % 3), (int)(t & 1), (int)(t & 1)); }
             else { auto kf_ = k_bulk_syml2<false, false>; RC_BULK_LAUNCH(kf_, s2_blocks, 256, c->syml_pad, V2, (int)(t % 3), (int)(t & 1), (int)(t & 1)); }
             if (s2_nslow > 0) {   // ragged last column block: its units by the round-2 code, behind the main launch
@@ -7422,12 +7617,15 @@ extern "C" int32_t rc_set_option(rc_ctx *c, const char *name, int64_t value)
     } else if (!strcmp(name, "chain_pipeline")) {
         if (value != 0 && value != 1) return fail(c, RC_ERR_ARG, "rc_set_option: chain_pipeline must be 0 or 1");
         c->opt_chain_pipeline = (int)value;
+    } else if (!strcmp(name, "fold_log_table")) {
+        if (value != 0 && value != 1) return fail(c, RC_ERR_ARG, "rc_set_option: fold_log_table must be 0 or 1");
+        c->opt_fold = (int)value;
 #ifdef RC_DIAG
     } else if (!strcmp(name, "debug_flags")) {   // timing ablations (SweepArgs.dbg): results are wrong on purpose
         c->dbg = (int)value;
 #endif
     } else {
-        return fail(c, RC_ERR_ARG, "rc_set_option: unknown option '%s' (prune, lds_point_cache, chain_workers, chain_depth, chain_pipeline)", name);
+        return fail(c, RC_ERR_ARG, "rc_set_option: unknown option '%s' (prune, lds_point_cache, chain_workers, chain_depth, chain_pipeline, fold_log_table)", name);
     }
     return RC_OK;
 }
@@ -7447,7 +7645,9 @@ extern "C" int32_t rc_bulk_kernel_info(rc_ctx *c, int32_t *which, double *algori
 }
 
 
-// name of the row-reduction kernel the last enqueued sweep used, as a profiler shows it
+// name of the row-reduction kernel the last enqueued sweep used, as a profiler shows it — except that both forms of the derived
+// k_bulk_syml2 go by that name: a context whose entries span more than four binades launches k_bulk_syml2w, the same template
+// arguments (rc_log_table_folded tells the two apart)
 extern "C" const char *rc_bulk_kernel_name(rc_ctx *c)
 {
     if (!c) return "";
@@ -7458,6 +7658,13 @@ extern "C" const char *rc_bulk_kernel_name(rc_ctx *c)
     if (v == 2) return c->derived ? "k_bulk_syml<true>" : "k_bulk_syml<false>";
     if (v == 1) return c->derived ? "k_bulk_symw<true>" : "k_bulk_symw<false>";
     return c->derived ? "k_bulk_sym<true>" : "k_bulk_sym<false>";
+}
+
+// 1: this context's k_bulk_syml2 launches read the log table with the exponent folded in; 0: they derive the exponent per entry
+// (k_bulk_syml2w), or the context does not derive logD
+extern "C" int32_t rc_log_table_folded(rc_ctx *c)
+{
+    return (c && syml2_folds(c)) ? 1 : 0;
 }
 
 extern "C" int32_t rc_layout_info(rc_ctx *c, int32_t *n_relayouts, int32_t *label_runs)

@@ -15,6 +15,7 @@ __global__ __launch_bounds__(256) void k(long long *out, int iters, double seed)
     double d[8]; long long q[8]; unsigned u[8]; int c[8];
     for (int i = 0; i < 8; ++i) { d[i] = seed + i + threadIdx.x; q[i] = (long long)(seed * 1000) + i * 77 + threadIdx.x; u[i] = (unsigned)q[i]; c[i] = i; }
     const double m = 1.0000001, a = 1e-9;
+    const unsigned long long smask = __ballot(((threadIdx.x * 2654435761u) >> 7) & 1);   // a lane mask in an SGPR pair (OP 24 / 25)
     const long long t0 = __builtin_amdgcn_s_memtime();
     for (int it = 0; it < iters; ++it) {
 #pragma unroll
@@ -115,6 +116,14 @@ __global__ __launch_bounds__(256) void k(long long *out, int iters, double seed)
 #define X(i) asm volatile("v_cvt_i32_f64 %0, %1" : "=v"(c[i]) : "v"(d[i]));
                 REP8(X)
 #undef X
+            } else if (OP == 24) {   // the select as the compiler emits it in the row reduction: mask in an SGPR pair, no vcc traffic
+#define X(i) asm volatile("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(u[i]) : "v"(u[(i + 1) & 7]), "s"(smask));
+                REP8(X)
+#undef X
+            } else if (OP == 25) {   // ... with a constant 0 as the first source (v_cndmask_b32 v, 0, x, s[n:n+1])
+#define X(i) asm volatile("v_cndmask_b32_e64 %0, 0, %0, %1" : "+v"(u[i]) : "s"(smask));
+                REP8(X)
+#undef X
             }
         }
     }
@@ -153,7 +162,9 @@ int main()
     printf("%s, %d CUs; cycles per wave-instruction per SIMD (shader clock, s_memtime)\n", p.name, ncu);
     run<2>("v_add_u32", d, ncu);
     run<10>("v_fma_f32", d, ncu);
-    run<13>("v_cndmask_b32", d, ncu);
+    run<13>("v_cndmask_b32 (vcc)", d, ncu);
+    run<24>("v_cndmask_b32 (sgpr pair)", d, ncu);
+    run<25>("v_cndmask_b32 0,x (sgpr pair)", d, ncu);
     run<16>("v_mad_u32_u24", d, ncu);
     run<14>("v_mul_lo_u32", d, ncu);
     run<15>("v_mul_hi_u32", d, ncu);

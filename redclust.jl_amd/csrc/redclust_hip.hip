@@ -629,7 +629,8 @@ __global__ __launch_bounds__(256) void k_pack48(const long long *__restrict__ Dq
         const ll2 v = *(const ll2 *)(Dq + 2 * t);
         const u64 a = (u64)v.x, b = (u64)v.y;
         out[3 * t] = (unsigned)a;                                               // the low words as they are, the two 16-bit tops share the middle word
-        out[3 * t + 1] = (unsigned)(a >> 32) | ((unsigned)(b >> 32) << 16);
+        // (a negative entry — only a diagonal one can be, and the reductions mask it — must not spill its sign bits into its neighbour's top)
+        out[3 * t + 1] = ((unsigned)(a >> 32) & 0xffffu) | ((unsigned)(b >> 32) << 16);
         out[3 * t + 2] = (unsigned)b;
     }
 }
@@ -5355,6 +5356,7 @@ static int32_t create_impl(rc_ctx *c, int64_t n, const double *D, const double *
         HIPCHK2(hipMemcpy(c->ltab, tab, sizeof(tab), hipMemcpyHostToDevice));
     }
     c->fold_ok = false;
+    if (derived && dq_max < dq_min) dq_min = dq_max = 1;   // n = 1: no off-diagonal entry (k_derived_scan left its start values; clz(0) below is undefined)
     if (derived && dq_min > 0) {
         // rc_qlog_prep_f: every entry is an integer below 2^52, exact as a double — its biased exponent is 1023 + floor(log2 dq).
         // At most four consecutive binades: the table with the exponent folded in serves k_bulk_syml2; more: k_bulk_syml2w derives it
@@ -5432,7 +5434,10 @@ static int32_t alloc_ctx(int64_t n, int32_t storage_bits, int32_t device_id, int
     c->prefetch = !(rc_env_diag("RC_NO_PREFETCH") && atoi(rc_env_diag("RC_NO_PREFETCH")));
     c->relayout = !(rc_env("RC_NO_RELAYOUT") && atoi(rc_env("RC_NO_RELAYOUT")));
     c->res_one_stream = rc_env("RC_RES_ONE_STREAM") ? atoi(rc_env("RC_RES_ONE_STREAM")) != 0 : (n <= RC_RES_ONE_STREAM_MAX_N);
-    if (rc_env("RC_SYM_VARIANT")) c->sym_variant = atoi(rc_env("RC_SYM_VARIANT"));
+    if (rc_env("RC_SYM_VARIANT")) {   // 0..3 select a kernel; anything else is "automatic", like the variable not being set
+        const int v_ = atoi(rc_env("RC_SYM_VARIANT"));
+        c->sym_variant = (v_ >= 0 && v_ <= 3) ? v_ : -1;
+    }
     if (rc_env_diag("RC_SYMW_PER_CU")) c->symw_per_cu = std::max(1, atoi(rc_env_diag("RC_SYMW_PER_CU")));
     if (rc_env_diag("RC_SYML_PAD")) c->syml_pad = (size_t)std::max(0, atoi(rc_env_diag("RC_SYML_PAD")));
     if (rc_env_diag("RC_SW_COARSE")) c->sw_coarse = std::min(128, std::max(8, atoi(rc_env_diag("RC_SW_COARSE")) & ~3));

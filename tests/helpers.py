@@ -45,3 +45,25 @@ def assert_derived_log_close(L, D, eD, eL, block=1024):
         worst = max(worst, float(err.max())); worst_ratio = max(worst_ratio, float(ratio.max()))
     assert worst_ratio <= 1.0, (worst, worst_ratio, eD, eL)
     return worst, worst_ratio
+
+
+def diagonal(kind, n):
+    """Three nonzero diagonals for D (tests/test_diagonal_cpu.py, tests/test_gpu_diagonal.py): positive, mixed sign, larger than
+    every off-diagonal entry of the data sets used there."""
+    rng = np.random.default_rng({"positive": 21, "mixed": 22, "large": 23}[kind])
+    if kind == "positive":
+        return rng.uniform(0.1, 3.0, n)
+    if kind == "mixed":
+        return rng.normal(0.0, 2.0, n)
+    return np.full(n, 50.0)
+
+
+def with_diagonal(D, kind):
+    D = D.copy()
+    D[np.diag_indices_from(D)] = diagonal(kind, D.shape[0])
+    return D
+
+
+def cluster_terms_positive(D, clusts, beta):
+    """every β + matsum(D, C_k, C_k)/2 of loglik (mcmc.jl:32), diagonal included"""
+    return all(beta + D[np.ix_(clusts == k, clusts == k)].sum() / 2 > 0 for k in np.unique(clusts))

@@ -261,6 +261,32 @@ int32_t rc_kmedoids_scan_split(rc_ctx *ctx, int64_t kmin, int64_t kmax, int64_t 
                                double *totalcost, int64_t *iterations, uint8_t *converged,
                                rc_wb_stats *split /* kmax - kmin + 1 */);
 
+/* kmeans(X, k; maxiter, tol) of Clustering.jl with k-means++ seeding, as fitprior / fitprior2 call it with algo = "k-means"
+ * (src/prior.jl:64, :197), on the f64 points a context created by rc_create_from_points keeps (a context created from a
+ * matrix: RC_ERR_STATE).  DESIGN.md §8 "k-means (built)" restates the algorithm and its fixed orders: squared distances summed
+ * over ascending coordinates without fma, centres as ordered member sums and one division, the objective in one fixed tree,
+ * integer weighted draws — so a run is a pure function of (points, k, seed | init), reproducible bit for bit on the host.
+ * Uniforms: Philox keyed (seed_lo, seed_hi ^ 0x4B4D4E53), counter (draw, k, 0, 0); draw 0 is the uniform first seed, the
+ * repicks of empty groups continue the count (from 0 when init is given).  init_or_null: k distinct 1-based point indices
+ * whose points are the starting centres (RC_ERR_ARG for an index outside 1..n or a repeated one).  Converged as Clustering.jl:
+ * objective change <= tol and (k == 1 or |change| < tol).  maxiter = 0 returns the initial assignment.  Leaves the chain
+ * state, the layout and the co-clustering counts untouched.  RC_ERR_DOMAIN: k outside 1..n (kmax < kmin), maxiter outside
+ * 0..2^24, tol negative or NaN, or every weight of a draw zero (fewer distinct points than k; Clustering.jl's wsample fails
+ * there).  Non-finite points never get this far: rc_create_from_points refuses them. */
+int32_t rc_kmeans(rc_ctx *ctx, int64_t k, int64_t maxiter, double tol, uint64_t seed, const int64_t *init_or_null,
+                  int64_t *assignments /* n, 1-based */, double *centers /* k×dim row-major */, double *costs /* n */,
+                  int64_t *counts /* k */, double *totalcost, int64_t *iterations, uint8_t *converged);
+/* rc_kmeans for every k in kmin..kmax in one batched job: entry k - kmin of each array equals rc_kmeans(k) with the same
+ * seed, bit for bit.  slots_per_chunk: runs per device pass, 0 = automatic (a workspace of at most 512 MiB; RC_ERR_OOM when
+ * one run alone exceeds it); the results do not depend on it. */
+int32_t rc_kmeans_scan(rc_ctx *ctx, int64_t kmin, int64_t kmax, int64_t maxiter, double tol, uint64_t seed,
+                       int64_t slots_per_chunk /* 0 = automatic */, double *totalcost, int64_t *iterations, uint8_t *converged);
+/* The scan above plus, for every k, the within / between split of the context's D under that k's final assignment:
+ * split[k - kmin] equals rc_set_state(assignments_k) + rc_within_between, bit for bit (as rc_kmedoids_scan_split). */
+int32_t rc_kmeans_scan_split(rc_ctx *ctx, int64_t kmin, int64_t kmax, int64_t maxiter, double tol, uint64_t seed,
+                             int64_t slots_per_chunk /* 0 = automatic */, double *totalcost, int64_t *iterations,
+                             uint8_t *converged, rc_wb_stats *split /* kmax - kmin + 1 */);
+
 /* sampleK (src/prior.jl:316-338) for m samples whose r[i] ~ Gamma(eta, 1/sigma) and p[i] ~ Beta(u, v) the caller has
  * drawn: the Gumbel-max draw over the n log-probabilities of every sample on the device.  Uniforms: Philox keyed
  * (seed_lo, seed_hi ^ 0x534D504B), counter (K, i_lo, i_hi, 0); sample i is a pure function of (n, r[i], p[i], seed, i).

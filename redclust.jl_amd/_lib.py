@@ -8,7 +8,7 @@ import subprocess
 
 import numpy as np
 
-from .types import KmedoidsResult
+from .types import KmeansResult, KmedoidsResult
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
@@ -80,7 +80,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     srcs = [os.path.join(CSRC, "redclust_hip.hip"), os.path.join(CSRC, "pointestimate.inc.hip"),
             os.path.join(CSRC, "kmedoids.inc.hip"),
             os.path.join(CSRC, "chain.inc.hip"), os.path.join(CSRC, "chains.inc.hip"), os.path.join(CSRC, "samplek.inc.hip"),
-            os.path.join(CSRC, "mixture.inc.hip"), HEADER]
+            os.path.join(CSRC, "mixture.inc.hip"), os.path.join(CSRC, "kmeans.inc.hip"), HEADER]
     if not force and os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(s) for s in srcs):
         return SO
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-o", SO, srcs[0]]
@@ -167,6 +167,12 @@ SIGNATURES = {
                                      np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")]),
     "rc_kmedoids_scan_split": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_uint64, _dp, _ip,
                                            np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS"), C.POINTER(RcWbStats)]),
+    "rc_kmeans": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_uint64, C.c_void_p, _ip, _dp, _dp, _ip,
+                              C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)]),
+    "rc_kmeans_scan": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_uint64, C.c_int64, _dp, _ip,
+                                   np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")]),
+    "rc_kmeans_scan_split": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_uint64, C.c_int64, _dp, _ip,
+                                         np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS"), C.POINTER(RcWbStats)]),
     "rc_sample_k": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, _dp, _dp, C.c_uint64, _ip, C.POINTER(C.c_double)]),
     "rc_oracle_coclustering": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, _dp, C.c_int64, C.c_double, C.c_double, C.c_int64,
                                            _dp, C.c_int64, _dp, C.POINTER(C.c_double)]),
@@ -228,6 +234,7 @@ class Context:
         if pts.ndim != 2:
             raise ValueError("points must be an n×dim array (one observation per row)")
         self.n = int(pts.shape[0])
+        self.dim = int(pts.shape[1])
         h = C.c_void_p()
         rc = self.L.rc_create_from_points(self.n, int(pts.shape[1]), pts.ctypes.data_as(C.c_void_p), storage_bits, device,
                                           kcap, C.byref(h))
@@ -468,6 +475,43 @@ class Context:
             return dict(totalcost=tc, iterations=it, converged=cv.astype(bool))
         wb = (RcWbStats * m)()
         self._chk(self.L.rc_kmedoids_scan_split(*args, wb))
+        out = dict(totalcost=tc, iterations=it, converged=cv.astype(bool))
+        for k, ty in RcWbStats._fields_:
+            out[k] = np.array([getattr(x, k) for x in wb], dtype=np.int64 if ty is C.c_int64 else np.float64)
+        return out
+
+    def kmeans(self, k, maxiter=100, tol=1e-6, seed=0, init=None) -> KmeansResult:
+        """rc_kmeans: Clustering.jl's kmeans(X, k; maxiter, tol) (k-means++ seeding, or init: k distinct 1-based point indices)
+        on the points of a context made by from_points; the state is untouched."""
+        k = int(k)
+        dim = getattr(self, "dim", 0)
+        a, costs = np.zeros(self.n, np.int64), np.zeros(self.n)
+        cen, cnt = np.zeros((max(k, 1), max(dim, 1))), np.zeros(max(k, 1), np.int64)
+        ip = None
+        if init is not None:
+            init = np.ascontiguousarray(init, dtype=np.int64)
+            if init.shape != (k,):
+                raise ValueError("init must hold k point indices")
+            ip = init.ctypes.data_as(C.c_void_p)
+        tc, it, cv = C.c_double(), C.c_int64(), C.c_uint8()
+        self._chk(self.L.rc_kmeans(self.h, k, int(maxiter), float(tol), int(seed) & 0xFFFFFFFFFFFFFFFF, ip, a, cen.reshape(-1),
+                                   costs, cnt, C.byref(tc), C.byref(it), C.byref(cv)))
+        return KmeansResult(centers=cen[:k, :dim], assignments=a, costs=costs, counts=cnt[:k], totalcost=tc.value,
+                            iterations=int(it.value), converged=bool(cv.value))
+
+    def kmeans_scan(self, kmin, kmax, maxiter=100, tol=1e-6, seed=0, split=False, slots_per_chunk=0) -> dict:
+        """rc_kmeans_scan: totalcost, iterations and converged of kmeans(k) for k = kmin..kmax (arrays indexed by k - kmin);
+        split=True (rc_kmeans_scan_split): also every k's within / between split of the context's D under its final
+        assignment, as kmedoids_scan returns it.  slots_per_chunk: runs per device pass (0 = automatic; same results)."""
+        m = max(int(kmax) - int(kmin) + 1, 1)
+        tc, it, cv = np.zeros(m), np.zeros(m, np.int64), np.zeros(m, np.uint8)
+        args = (self.h, int(kmin), int(kmax), int(maxiter), float(tol), int(seed) & 0xFFFFFFFFFFFFFFFF, int(slots_per_chunk),
+                tc, it, cv)
+        if not split:
+            self._chk(self.L.rc_kmeans_scan(*args))
+            return dict(totalcost=tc, iterations=it, converged=cv.astype(bool))
+        wb = (RcWbStats * m)()
+        self._chk(self.L.rc_kmeans_scan_split(*args, wb))
         out = dict(totalcost=tc, iterations=it, converged=cv.astype(bool))
         for k, ty in RcWbStats._fields_:
             out[k] = np.array([getattr(x, k) for x in wb], dtype=np.int64 if ty is C.c_int64 else np.float64)

@@ -4808,6 +4808,9 @@ struct rc_ctx {
     void *Dq = nullptr, *Lq = nullptr;  // int64 or int32 fixed point, INTERNAL point order (what the kernels read)
     void *Dq48 = nullptr;               // derived mode: Dq packed to 48 bits per entry (k_pack48), what k_bulk_syml2's fast path streams
     void *Dq_src = nullptr, *Lq_src = nullptr;  // the same matrices in the caller's point order (source of every re-layout)
+    double *pts = nullptr, *ptsT = nullptr;     // rc_create_from_points only: the n×dim points and their dim×n transpose (k-means)
+    int dim = 0;                                // their dimension (0: the context was created from a matrix)
+    int km_shift = 0;                           // k-means: weights of the integer draws are floor(w · 2^km_shift) (kmeans.inc.hip)
     long long *diagq = nullptr, *diag_src = nullptr;
     int *pi = nullptr, *ipi = nullptr;  // device: original -> internal, internal -> original
     std::vector<int> h_pi, h_ipi;       // host copies
@@ -5012,7 +5015,7 @@ static void free_all(rc_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->dev);
-    void *ptrs[] = {c->Dq48, c->ltab, c->vtab, c->flt, c->Dq, c->Lq, c->Dq_src, c->Lq_src, c->diag_src, c->pi, c->ipi, c->diagq, c->SD[0], c->SD[1], c->SD[2], c->SL[0], c->SL[1], c->SL[2], c->slot_of,
+    void *ptrs[] = {c->pts, c->ptsT, c->Dq48, c->ltab, c->vtab, c->flt, c->Dq, c->Lq, c->Dq_src, c->Lq_src, c->diag_src, c->pi, c->ipi, c->diagq, c->SD[0], c->SD[1], c->SD[2], c->SL[0], c->SL[1], c->SL[2], c->slot_of,
                     c->slot_size, c->slot_label, c->slot_pos, c->slot_act, c->perm[0], c->perm[1], c->pslot[0],
                     c->pslot[1], c->lsnap[0], c->lsnap[1], c->work[0], c->work[1], c->cword[0], c->cword[1], c->rec, c->A, c->keys[0], c->keys[1], c->arrive[0], c->arrive[1], c->sc, c->blocks,
                     c->counts, c->cc_out, c->snap, c->d_moves, c->used_scratch, c->wide_scratch, c->wc, c->ufast, c->uslow, c->wfast, c->wslow, c->s2alt.ufast, c->s2alt.uslow, c->s2alt.wfast, c->s2alt.wslow};
@@ -5143,6 +5146,39 @@ static int32_t alloc_slot_buffers(rc_ctx *c)
     return RC_OK;
 }
 
+// dim×n transpose of the n×dim points (the k-means kernels read a coordinate of consecutive points coalesced)
+__global__ __launch_bounds__(256) void k_transpose_points(const double *__restrict__ pts, int n, int dim, double *__restrict__ T)
+{
+    const size_t total = (size_t)n * (size_t)dim;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        const size_t i = e / (size_t)dim, c = e - i * (size_t)dim;
+        T[c * (size_t)n + i] = pts[e];
+    }
+}
+
+// The power-of-two scale of k-means' integer weighted draws: weights are floor(w · 2^s) with
+// s = 61 - ceil(log2 n) - ex, B < 2^ex the squared diagonal of the points' bounding box (every squared distance is at most
+// B up to rounding), so that n · max weight < 2^63.  Clamped to ±2000 (ldexp scales exactly); 0 when B is zero or not finite.
+static int kmeans_shift(const double *points, int64_t n, int64_t dim)
+{
+#pragma clang fp contract(off)
+    double B = 0.0;
+    for (int64_t c = 0; c < dim; ++c) {
+        double lo = points[c], hi = points[c];
+        for (int64_t i = 1; i < n; ++i) {
+            const double x = points[(size_t)i * (size_t)dim + c];
+            if (x < lo) lo = x;
+            if (x > hi) hi = x;
+        }
+        const double d = hi - lo;
+        B = B + d * d;
+    }
+    if (!(B > 0.0) || !std::isfinite(B)) return 0;
+    int ex;
+    std::frexp(B, &ex);
+    return std::max(-2000, std::min(2000, 61 - ceil_log2_ll((long long)n) - ex));
+}
+
 static int32_t create_impl(rc_ctx *c, int64_t n, const double *D, const double *logD, const double *points = nullptr,
                            int64_t dim = 0)
 {
@@ -5254,6 +5290,13 @@ static int32_t create_impl(rc_ctx *c, int64_t n, const double *D, const double *
         HIPCHK2(hipMemcpyAsync(tmpL, points, (size_t)n * (size_t)dim * sizeof(double), hipMemcpyHostToDevice, s));  // tmpL as staging
         const unsigned nt = (unsigned)((n + 63) / 64);
         k_pairwise<<<dim3(nt, nt), 256, 0, s>>>(tmpL, (int)n, (int)dim, tmpD);
+        // the k-means entry points (kmeans.inc.hip) work on the points themselves: keep them, row-major and transposed
+        HIPCHK2(hipMalloc(&c->pts, (size_t)n * (size_t)dim * sizeof(double)));
+        HIPCHK2(hipMalloc(&c->ptsT, (size_t)n * (size_t)dim * sizeof(double)));
+        HIPCHK2(hipMemcpyAsync(c->pts, tmpL, (size_t)n * (size_t)dim * sizeof(double), hipMemcpyDeviceToDevice, s));
+        k_transpose_points<<<(unsigned)std::min<size_t>(((size_t)n * (size_t)dim + 255) / 256, 65535), 256, 0, s>>>(c->pts, (int)n, (int)dim, c->ptsT);
+        c->dim = (int)dim;
+        c->km_shift = kmeans_shift(points, n, dim);
     } else {
         HIPCHK2(hipMemcpyAsync(tmpD, D, nn * sizeof(double), hipMemcpyHostToDevice, s));
     }
@@ -7764,3 +7807,4 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "chains.inc.hip"
 #include "samplek.inc.hip"
 #include "mixture.inc.hip"
+#include "kmeans.inc.hip"

@@ -7,7 +7,11 @@ The k-medoids runs — one per k of the elbow scan, then the notional clustering
 clustering comes from the device's block sums (rc_within_between), fitprior2's split under every k of the scan from the
 scan itself (rc_kmedoids_scan_split).  sampleK's Gumbel-max draws run on the device (rc_sample_k, csrc/samplek.inc.hip).
 On the host, as in the reference: the elbow, the scalar chain of sample_rp, the draws of r / p and the maximum-likelihood
-fits.  The k-means path of fitprior / fitprior2 is not in this build."""
+fits.
+
+The k-means path (Clustering.jl's kmeans on the observations, csrc/kmeans.inc.hip: rc_kmeans / rc_kmeans_scan[_split]) is
+reached through fitprior_kmeans / fitprior2_kmeans, which share one body with the k-medoids fits; the string "k-means"
+given to fitprior / fitprior2 still raises NotImplementedError."""
 from __future__ import annotations
 
 import math
@@ -19,7 +23,7 @@ from scipy.special import digamma, polygamma
 from ._lib import Context, sample_k
 from .datagen import _gamma_shape_mle
 from .sampler import sample_p, sample_r
-from .types import KmedoidsResult, MCMCData, MCMCOptionsList, PriorHyperparamsList
+from .types import KmeansResult, KmedoidsResult, MCMCData, MCMCOptionsList, PriorHyperparamsList
 
 # Seeds of the k-medoids streams the reference draws from its one global RNG: the elbow scan uses `seed` itself, the
 # notional clustering and runsampler's starting labels fresh streams derived from it (kmedoids_stream_seed).
@@ -40,6 +44,20 @@ def kmedoids(D_or_ctx, k: int, *, maxiter: int = 200, tol: float = 1e-8, seed: i
     ctx = Context(D_or_ctx, device=device)
     try:
         return ctx.kmedoids(k, maxiter=maxiter, tol=tol, seed=seed)
+    finally:
+        ctx.close()
+
+
+def kmeans(points_or_ctx, k: int, *, maxiter: int = 100, tol: float = 1e-6, seed: int = 0, init=None,
+           device: int = 0) -> KmeansResult:
+    """kmeans(X, k; maxiter, tol, init) of Clustering.jl (k-means++ seeding, or init: k distinct 1-based point indices) on
+    the device.  points_or_ctx: n×dim observations (one per row) or a Context made by Context.from_points (its chain state
+    is left as it is)."""
+    if isinstance(points_or_ctx, Context):
+        return points_or_ctx.kmeans(k, maxiter=maxiter, tol=tol, seed=seed, init=init)
+    ctx = Context.from_points(points_or_ctx, device=device)
+    try:
+        return ctx.kmeans(k, maxiter=maxiter, tol=tol, seed=seed, init=init)
     finally:
         ctx.close()
 
@@ -136,7 +154,7 @@ def _staging(data, diss):
     return x.shape[0], "points", x
 
 
-def _prepare(name, data, algo, diss, Kmin, Kmax, ctx, out):
+def _prepare(name, data, algo, diss, Kmin, Kmax, ctx, out, kmeans_built=False):
     """The input handling and checks fitprior and fitprior2 share (src/prior.jl:30-56, :160-188): (N, kind, payload, Kmax)."""
     out("Fitting prior hyperparameters")
     is_data = isinstance(data, MCMCData)
@@ -153,11 +171,18 @@ def _prepare(name, data, algo, diss, Kmin, Kmax, ctx, out):
         raise ValueError("Algo must be 'k-means' or 'k-medoids'.")
     if not (1 <= Kmin <= Kmax <= N):
         raise ValueError("Kmin and Kmax must satisfy 1 ≤ Kmin ≤ Kmax ≤ N")
-    if algo == "k-means":
+    if algo == "k-means" and not kmeans_built:
         raise NotImplementedError(f"{name}(algo='k-means') is not in this build: use algo='k-medoids'")
     if ctx is not None and ctx.n != N:
         raise ValueError(f"ctx holds {ctx.n} observations, data {N}")
+    if algo == "k-means" and ctx is not None and not getattr(ctx, "dim", 0):
+        raise ValueError("Cannot use algorithm `k-means` with a dissimilarity matrix.")   # a Context made from a matrix
     return N, kind, x, Kmax
+
+
+def _clusterer(ctx, algo):
+    """(scan, single run) of the backend: both take (…, maxiter=, seed=), the scan also split=."""
+    return (ctx.kmeans_scan, ctx.kmeans) if algo == "k-means" else (ctx.kmedoids_scan, ctx.kmedoids)
 
 
 def _stage(kind, x, device):
@@ -181,20 +206,41 @@ def fitprior(data, algo: str, diss: bool = False, *, Kmin: int = 1, Kmax: int | 
     data: points (one observation per row, this package's convention: the reference's columns), a dissimilarity matrix
     with diss=True, or an MCMCData.  ctx reuses a Context that holds the same matrix (its label state is overwritten
     with the notional clustering); otherwise one is staged for the call — from points the device computes the distances.
-    seed keys the k-medoids streams (kmedoids_stream_seed) and the sample_rp chain."""
+    seed keys the k-medoids streams (kmedoids_stream_seed) and the sample_rp chain.
+    algo = "k-means" raises NotImplementedError: that path is fitprior_kmeans."""
+    return _fitprior(data, algo, diss, Kmin, Kmax, verbose, seed, device, ctx, False)
+
+
+def fitprior_kmeans(data, *, Kmin: int = 1, Kmax: int | None = None, verbose: bool = True, seed: int = 0, device: int = 0,
+                    ctx: Context | None = None) -> PriorHyperparamsList:
+    """What the reference's fitprior(data, "k-means"; Kmin, Kmax, verbose) computes (src/prior.jl:22-128 with
+    kmeans(x, k; maxiter = 1000) at :64 and :72): the elbow scan and the notional clustering by k-means on the observations
+    (rc_kmeans_scan / rc_kmeans), the distance split and every fit as in fitprior.
+
+    data: points (one observation per row) or an MCMCData built from points; dissimilarities alone are the reference's
+    ValueError.  ctx: a Context made by Context.from_points from the same points (its label state is overwritten with the
+    notional clustering).  Seeds and streams as in fitprior.  fitprior(data, "k-means") itself still raises
+    NotImplementedError because the suite pins that; routing the string here is a one-line follow-up (kmeans_built=True in
+    fitprior's call of the shared body) once those two assertions may change."""
+    return _fitprior(data, "k-means", False, Kmin, Kmax, verbose, seed, device, ctx, True)
+
+
+def _fitprior(data, algo, diss, Kmin, Kmax, verbose, seed, device, ctx, kmeans_built):
+    """The body fitprior (k-medoids) and fitprior_kmeans share."""
     out = print if verbose else (lambda *a, **k: None)
-    N, kind, x, Kmax = _prepare("fitprior", data, algo, diss, Kmin, Kmax, ctx, out)
+    N, kind, x, Kmax = _prepare("fitprior", data, algo, diss, Kmin, Kmax, ctx, out, kmeans_built)
     own = ctx is None
     if own:
         ctx = _stage(kind, x, device)
     try:
         out("Computing notional clustering.")
+        scan_fn, run_fn = _clusterer(ctx, algo)
         # as written (prior.jl:63-70): the runs are for k = 1:(Kmax-Kmin+1), their costs are labelled Kmin:Kmax
-        scan = ctx.kmedoids_scan(1, Kmax - Kmin + 1, maxiter=1000, seed=kmedoids_stream_seed(seed, KMED_STREAM_SCAN))
+        scan = scan_fn(1, Kmax - Kmin + 1, maxiter=1000, seed=kmedoids_stream_seed(seed, KMED_STREAM_SCAN))
         for k in np.flatnonzero(~scan["converged"]) + 1:
             warnings.warn(f"Clustering did not converge at K = {k}")
         K = int(detectknee(np.arange(Kmin, Kmax + 1), scan["totalcost"])[0])
-        notional = ctx.kmedoids(K, maxiter=1000, seed=kmedoids_stream_seed(seed, KMED_STREAM_NOTIONAL)).assignments
+        notional = run_fn(K, maxiter=1000, seed=kmedoids_stream_seed(seed, KMED_STREAM_NOTIONAL)).assignments
         ctx.set_state(notional)
         wb = ctx.within_between()
 
@@ -310,19 +356,35 @@ def fitprior2(data, algo: str, diss: bool = False, *, Kmin: int = 1, Kmax: int |
     (pmf of sampleK with max(10^4, 100 N) samples).  The per-k splits come from the device scan (rc_kmedoids_scan_split)
     as exact sufficient statistics; no distance vector is formed.  Streams: the scan and the notional run as in fitprior,
     sample_rp keyed by seed, sampleK by kmedoids_stream_seed(seed, SAMPLEK_STREAM).  ctx: a Context holding the same matrix
-    (its state is left as it is)."""
+    (its state is left as it is).  algo = "k-means" raises NotImplementedError: that path is fitprior2_kmeans."""
+    return _fitprior2(data, algo, diss, Kmin, Kmax, verbose, seed, device, ctx, False)
+
+
+def fitprior2_kmeans(data, *, Kmin: int = 1, Kmax: int | None = None, verbose: bool = True, seed: int = 0, device: int = 0,
+                     ctx: Context | None = None) -> PriorHyperparamsList:
+    """What the reference's fitprior2(data, "k-means"; Kmin, Kmax, verbose) computes (src/prior.jl:151-277 with
+    kmeans(x, k; maxiter = 1000)): as fitprior2, with the scan, its per-k splits (rc_kmeans_scan_split) and the notional
+    clustering by k-means on the observations.  data, ctx, seeds and streams as in fitprior_kmeans (the context's state is
+    left as it is).  fitprior2(data, "k-means") itself still raises NotImplementedError because the suite pins that; routing
+    the string here is a one-line follow-up once that assertion may change."""
+    return _fitprior2(data, "k-means", False, Kmin, Kmax, verbose, seed, device, ctx, True)
+
+
+def _fitprior2(data, algo, diss, Kmin, Kmax, verbose, seed, device, ctx, kmeans_built):
+    """The body fitprior2 (k-medoids) and fitprior2_kmeans share."""
     out = print if verbose else (lambda *a, **k: None)
-    N, kind, x, Kmax = _prepare("fitprior2", data, algo, diss, Kmin, Kmax, ctx, out)
+    N, kind, x, Kmax = _prepare("fitprior2", data, algo, diss, Kmin, Kmax, ctx, out, kmeans_built)
     own = ctx is None
     if own:
         ctx = _stage(kind, x, device)
     try:
         out("Computing notional clustering.")
-        scan = ctx.kmedoids_scan(Kmin, Kmax, maxiter=1000, seed=kmedoids_stream_seed(seed, KMED_STREAM_SCAN), split=True)
+        scan_fn, run_fn = _clusterer(ctx, algo)
+        scan = scan_fn(Kmin, Kmax, maxiter=1000, seed=kmedoids_stream_seed(seed, KMED_STREAM_SCAN), split=True)
         for k in np.flatnonzero(~scan["converged"]) + Kmin:
             warnings.warn(f"Clustering did not converge at K = {k}")
         K = int(detectknee(np.arange(Kmin, Kmax + 1), scan["totalcost"])[0])
-        notional = ctx.kmedoids(K, maxiter=1000, seed=kmedoids_stream_seed(seed, KMED_STREAM_NOTIONAL)).assignments
+        notional = run_fn(K, maxiter=1000, seed=kmedoids_stream_seed(seed, KMED_STREAM_NOTIONAL)).assignments
 
         out("Computing partition prior hyperparameters.")
         proposalsd_r, eta, sigma, u, v = _partition_prior(notional, verbose, seed)

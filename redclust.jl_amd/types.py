@@ -197,3 +197,16 @@ class KmedoidsResult:
     totalcost: float
     iterations: int
     converged: bool
+
+
+@dataclass
+class KmeansResult:
+    """Clustering.jl's KmeansResult: centers (k×dim, one centre per row), assignments (n, 1-based into centers), costs (n:
+    squared distance of every point to its centre), counts (k group sizes), totalcost, iterations, converged."""
+    centers: np.ndarray
+    assignments: np.ndarray
+    costs: np.ndarray
+    counts: np.ndarray
+    totalcost: float
+    iterations: int
+    converged: bool

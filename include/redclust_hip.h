@@ -438,6 +438,54 @@ typedef struct rc_pair_measures_t {
 } rc_pair_measures_t;
 int32_t rc_pair_measures(int32_t device, const int64_t *a, const int64_t *b, int64_t n, rc_pair_measures_t *out);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Point-estimate search: a greedy search over ALL partitions for the clustering of minimum expected loss under the
+ * posterior co-clustering counts — what the reference's docs/src/index.md "Point estimation" sends its users to R's SALSO
+ * for; the MPEL search above only looks at the clusterings the chain visited.  DESIGN.md §8 "Point-estimate search".
+ *
+ * counts: n×n uint32, symmetric, diagonal = m (the number of samples), no entry above m.  Criterion of a labelling c:
+ *   RC_PSM_BINDER  num = Σ_{i<j} C_ij + Σ_{i<j, c_i=c_j} (m − 2·C_ij), loss = num / (m·n(n−1)/2) (0 for n = 1): the posterior
+ *                  mean of binderloss(c, sample; normalised = true), src/pointestimate.jl:68-76.  Exact integers.
+ *   RC_PSM_VILB    Wade & Ghahramani's lower bound of the expected VI without its partition-independent constant:
+ *                  f = Σ_i [log n_{c_i} − 2·log T_i], T_i = Σ_{j: c_j=c_i} C_ij (C_ii included), loss = f/n + 2·log m.
+ * A run: starting labels (0 = not yet allocated, else 1..n: the slots), a point order (a permutation of 1..n), maxK (0 = no
+ * cap) and maxsweeps.  A sweep visits the points in that order: the point is taken out of its cluster, every non-empty
+ * cluster and — while the cluster count is below maxK — a new one are scored by the change of the criterion, and the
+ * point goes to the minimum.  Equal scores: the point's own slot first (it does not move), then the lowest slot; a new
+ * cluster takes the slot the point just emptied, else the lowest free one.  A point counts as moved when the partition
+ * changed (an unallocated point always).  The run ends after a sweep without a move (converged) or after maxsweeps.
+ * From all-zero labels the first sweep is a sequential allocation, the later ones improve it.
+ * One launch, one 1024-thread workgroup per run with its state in LDS: n <= 8192 and m·n < 2^31, RC_ERR_CAPACITY beyond.
+ * Binder runs are exact integers; VI sums its log terms in fixed point (2^-40 per term, integer atomics): both are
+ * pure functions of their arguments, bit for bit.  labels_out: sortlabels'd (src/utils.jl:69-74).  best: the first run
+ * of minimal loss (0-based).  kernel_ms (may be NULL): device time of the search kernel.
+ * RC_ERR_ARG: a NULL pointer, m, n or nruns < 1, maxsweeps < 1, maxK < 0, an unknown loss, a label outside 0..n, an
+ * order that is not a permutation, counts that are asymmetric, exceed m or whose diagonal is not m, a run that starts
+ * with more than a non-zero maxK clusters.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define RC_PSM_BINDER 0
+#define RC_PSM_VILB 1
+typedef struct rc_psm_run_t {
+    double loss;
+    int64_t loss_num; /* Binder numerator, 0 for VI */
+    int32_t sweeps, converged;
+    int64_t moves;
+    int32_t K;
+} rc_psm_run_t;
+
+/* counts: host n×n uint32; runs_out: nruns rc_psm_run_t.  Both are untyped so that hosts binding through a plain FFI
+ * (julia/RedClustHIP.jl) pass their buffers as they are.  No context: errors are read with a NULL context. */
+int32_t rc_psm_search(int32_t device, const void *counts /* uint32_t n×n */, int64_t m, int64_t n, int32_t loss,
+                      int32_t nruns, const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */,
+                      int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */, void *runs_out /* rc_psm_run_t[nruns] */,
+                      int32_t *best, double *kernel_ms);
+/* The same search on the context's own device count matrix (what rc_record_sample and rc_run_chain accumulate), read in
+ * place: no copy.  Equal to the stand-alone entry on rc_cocluster_counts, bit for bit.  Leaves the chain state, the
+ * layout and the counts untouched.  RC_ERR_STATE when no sample has been recorded. */
+int32_t rc_psm_search_ctx(rc_ctx *ctx, int64_t numsamples, int32_t loss, int32_t nruns, const int64_t *init,
+                          const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out,
+                          rc_psm_run_t *runs_out, int32_t *best, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ using RedClust: MCMCData, MCMCOptionsList, PriorHyperparamsList, MCMCState, MCMC
 using Clustering: kmedoids
 using Distributions: Beta, Gamma
 using StatsBase: mean, mean_and_var
+import Random
 
 const LIB = get(ENV, "REDCLUST_HIP_LIB", "libredclust_hip.so")
 
@@ -295,5 +296,56 @@ function getpointestimate_hip(result; loss::String = "VI", device::Integer = 0)
     check(Ptr{Cvoid}(C_NULL), rc)
     return (result.clusts[best[] + 1], Int(best[]) + 1)
 end
+
+"""
+    searchpointestimate(HIPBackend(), result; loss = "VI", nruns = 16, maxK = 0, maxsweeps = 100, seed = 0) -> (clust, info)
+
+A greedy search over all partitions for the clustering of minimum expected loss under `result`'s co-clustering counts
+(rc_psm_search: the SALSO-style search the reference's documentation sends its users to R for).  `nruns` runs from empty
+labels in random point orders plus one run started at `getpointestimate_hip(result; loss)`, so the answer is never worse
+under the searched criterion than the best sample.  `loss`: "binder" or "VI" (Wade & Ghahramani's lower bound).
+`info`: named tuple of the per-run `loss`, `sweeps`, `converged`, `moves`, `K`, all `labels` (n × runs) and `best`.
+"""
+struct RcPsmRun
+    loss::Cdouble
+    loss_num::Int64
+    sweeps::Int32; converged::Int32
+    moves::Int64
+    K::Int32; pad_::Int32
+end
+
+function searchpointestimate(b::HIPBackend, result; loss::String = "VI", nruns::Integer = 16, maxK::Integer = 0,
+                             maxsweeps::Integer = 100, seed::Integer = 0)
+    code = Dict("binder" => 0, "VI" => 1)
+    haskey(code, loss) || throw(ArgumentError("Invalid loss function specifier."))
+    m = length(result.clusts); n = length(result.clusts[1])
+    counts = zeros(UInt32, n, n)                                  # Σ adjacencymatrix(clusts[s]) (src/utils.jl:59-63), exact
+    for c in result.clusts, j in 1:n, i in 1:n
+        counts[i, j] += UInt32(c[i] == c[j])
+    end
+    R = Int(nruns) + 1
+    init = zeros(Int64, n, R)                                     # column r = run r: row-major R×n for the library
+    order = Matrix{Int32}(undef, n, R)
+    rng = Random.MersenneTwister(seed)
+    for r in 1:nruns
+        order[:, r] .= Random.randperm(rng, n)
+    end
+    start, _ = getpointestimate_hip(result; loss = loss, device = b.device)
+    init[:, R] .= start
+    order[:, R] .= 1:n
+    labels = Matrix{Int64}(undef, n, R)
+    runs = Vector{RcPsmRun}(undef, R)
+    best = Int32[0]
+    rc = ccall((:rc_psm_search, LIB), Int32,
+               (Int32, Ptr{Cvoid}, Int64, Int64, Int32, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
+                Ptr{Int32}, Ptr{Cdouble}),
+               b.device, counts, m, n, code[loss], R, init, order, maxK, maxsweeps, labels, runs, best, C_NULL)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    info = (loss = [x.loss for x in runs], sweeps = [Int(x.sweeps) for x in runs], converged = [x.converged != 0 for x in runs],
+            moves = [Int(x.moves) for x in runs], K = [Int(x.K) for x in runs], labels = labels, best = Int(best[1]) + 1)
+    return (labels[:, best[1] + 1], info)
+end
+
+export searchpointestimate
 
 end # module

@@ -71,6 +71,11 @@ class RcChainsInput(C.Structure):
                 ("init_clusts", C.c_void_p)]
 
 
+class RcPsmRun(C.Structure):
+    _fields_ = [("loss", C.c_double), ("loss_num", C.c_int64), ("sweeps", C.c_int32), ("converged", C.c_int32),
+                ("moves", C.c_int64), ("K", C.c_int32)]
+
+
 class RcSweepStats(C.Structure):
     _fields_ = [("n_changes", C.c_int64), ("n_rounds", C.c_int64), ("K", C.c_int64)]
 
@@ -80,7 +85,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     srcs = [os.path.join(CSRC, "redclust_hip.hip"), os.path.join(CSRC, "pointestimate.inc.hip"),
             os.path.join(CSRC, "kmedoids.inc.hip"),
             os.path.join(CSRC, "chain.inc.hip"), os.path.join(CSRC, "chains.inc.hip"), os.path.join(CSRC, "samplek.inc.hip"),
-            os.path.join(CSRC, "mixture.inc.hip"), os.path.join(CSRC, "kmeans.inc.hip"), HEADER]
+            os.path.join(CSRC, "mixture.inc.hip"), os.path.join(CSRC, "kmeans.inc.hip"),
+            os.path.join(CSRC, "pointsearch.inc.hip"), HEADER]
     if not force and os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(s) for s in srcs):
         return SO
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-o", SO, srcs[0]]
@@ -176,6 +182,10 @@ SIGNATURES = {
     "rc_sample_k": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, _dp, _dp, C.c_uint64, _ip, C.POINTER(C.c_double)]),
     "rc_oracle_coclustering": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, _dp, C.c_int64, C.c_double, C.c_double, C.c_int64,
                                            _dp, C.c_int64, _dp, C.POINTER(C.c_double)]),
+    "rc_psm_search": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                  C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_psm_search_ctx": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                      C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rc_layout_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rc_event_overhead_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "rc_kernel_timing": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -664,6 +674,41 @@ def loss_matrix(samples, loss: int, device: int = 0, want_matrix: bool = True):
     if rc != RC_OK:
         raise RedClustHIPError(rc, L.rc_last_error(None).decode())
     return M, cs, int(am.value), float(ms.value)
+
+
+def psm_search(counts, numsamples: int, loss: int, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0, ctx=None):
+    """rc_psm_search (counts: n×n uint32) or, with ctx, rc_psm_search_ctx on that context's device counts (counts is ignored).
+    init: nruns×n labels (0 = unallocated), order: nruns×n 1-based permutations.  Returns a dict: labels (nruns×n, sortlabels'd),
+    the per-run arrays loss, loss_num, sweeps, converged, moves, K, and best, kernel_ms."""
+    L = lib()
+    init = np.ascontiguousarray(init, dtype=np.int64)
+    order = np.ascontiguousarray(order, dtype=np.int32)
+    if init.ndim != 2 or init.shape != order.shape:
+        raise ValueError("init and order must be nruns×n arrays of the same shape")
+    nruns, n = init.shape
+    labels = np.zeros((max(nruns, 1), max(n, 1)), np.int64)
+    runs = (RcPsmRun * max(nruns, 1))()
+    best, ms = C.c_int32(-1), C.c_double()
+    if ctx is not None:
+        if n != ctx.n:
+            raise ValueError("init must have the context's n columns")
+        rc = L.rc_psm_search_ctx(ctx.h, int(numsamples), int(loss), nruns, init.ctypes.data, order.ctypes.data, int(maxK),
+                                 int(maxsweeps), labels.ctypes.data, runs, C.byref(best), C.byref(ms))
+        if rc != RC_OK:
+            raise _error(rc, L.rc_last_error(ctx.h).decode())
+    else:
+        cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+        if cnt.shape != (n, n):
+            raise ValueError("counts must be an n×n matrix matching init")
+        rc = L.rc_psm_search(int(device), cnt.ctypes.data, int(numsamples), n, int(loss), nruns, init.ctypes.data,
+                             order.ctypes.data, int(maxK), int(maxsweeps), labels.ctypes.data, runs, C.byref(best), C.byref(ms))
+        if rc != RC_OK:
+            raise _error(rc, L.rc_last_error(None).decode())
+    out = dict(labels=labels[:nruns, :n], best=int(best.value), kernel_ms=float(ms.value))
+    for k, ty in RcPsmRun._fields_:
+        out[k] = np.array([getattr(r, k) for r in runs[:nruns]], dtype=np.float64 if ty is C.c_double else np.int64)
+    out["converged"] = out["converged"].astype(bool)
+    return out
 
 
 def sample_k(n: int, r, p, seed: int = 0, device: int = 0):

@@ -58,6 +58,112 @@ def getpointestimate(samples, method: str = "MAP", loss="VI", device: int = 0):
     return clusts[i], i + 1
 
 
+_PSM_LOSSES = {"binder": 0, "VI": 1}   # RC_PSM_BINDER, RC_PSM_VILB
+
+
+def cocluster_counts(clusts) -> np.ndarray:
+    """Σ_s adjacencymatrix(clusts[s]) (utils.jl:59-63) as exact uint32 counts, on the host."""
+    S = np.stack([_labels(c) for c in clusts])
+    m, n = S.shape
+    counts = np.zeros((n, n), np.uint32)
+    for s in range(m):
+        onehot = np.zeros((n, int(S[s].max()) + 1), np.float32)
+        onehot[np.arange(n), S[s]] = 1.0
+        counts += (onehot @ onehot.T).astype(np.uint32)
+    return counts
+
+
+def expectedloss(clust, counts, numsamples: int, loss="VI") -> float:
+    """The criterion searchpointestimate minimises, evaluated on the host in NumPy for any labelling `clust`, from the n×n
+    co-clustering counts C (C_ii = numsamples = m):
+      "binder": [Σ_{i<j} C_ij + Σ_{i<j, c_i=c_j} (m − 2·C_ij)] / (m·n(n−1)/2) — the mean over the samples of
+                binderloss(clust, sample; normalised = true) (pointestimate.jl:68-76), exact in integers (0 for n = 1);
+      "VI":     (1/n)·Σ_i [log n_{c_i} − 2·log T_i] + 2·log m with T_i = Σ_{j: c_j=c_i} C_ij — Wade & Ghahramani's
+                lower bound of the expected VI without its partition-independent constant (natural logs)."""
+    if loss not in _PSM_LOSSES:
+        raise ValueError("Invalid loss function specifier.")
+    c = _labels(clust)
+    C = np.asarray(counts)
+    n, m = len(c), int(numsamples)
+    if C.shape != (n, n):
+        raise ValueError("counts must be an n×n matrix matching clust")
+    same = c[:, None] == c[None, :]
+    Ci = C.astype(np.int64)
+    if loss == "binder":
+        if n < 2:
+            return 0.0
+        iu = np.triu_indices(n, 1)
+        num = int(Ci[iu].sum()) + int((m - 2 * Ci[iu][same[iu]]).sum())
+        return num / (m * (n * (n - 1) // 2))
+    T = (Ci * same).sum(axis=1)
+    return float(np.sum(np.log(same.sum(axis=1)) - 2.0 * np.log(T))) / n + 2.0 * float(np.log(m))
+
+
+def searchpointestimate(samples_or_counts=None, loss="VI", *, nruns: int = 16, maxK: int = 0, maxsweeps: int = 100,
+                        seed: int = 0, init=None, numsamples=None, ctx=None, device: int = 0):
+    """Search ALL partitions for the clustering of minimum expected loss under the posterior co-clustering counts (the
+    reference's docs send its users to R's SALSO for this; getpointestimate(method="MPEL") only looks at the sampled
+    clusterings).  Runs on the GPU (csrc/pointsearch.inc.hip), every run one workgroup; there is no CPU fallback.
+
+    samples_or_counts: an MCMCResult (its counts are rebuilt exactly from `clusts`), or an n×n uint32 count matrix together
+    with numsamples; or pass a live Context as ctx= (with numsamples): its device counts are searched in place.
+    loss: "binder" or "VI" — see expectedloss; "VI" is the lower bound, not the exact posterior expected VI.  When the
+    samples are given, the partition-independent constant (1/n)·Σ_i mean_s log n^(s)_{c_i} that turns the bound's value into
+    Wade & Ghahramani's is returned as info["vi_constant"]; the losses themselves leave it out.
+    Runs: nruns runs from empty labels (sequential allocation, then improving sweeps) in the orders
+    np.random.Generator(np.random.Philox(key=seed)).permutation(n), drawn in run order; one more run per labelling in init
+    (identity order); and, for an MCMCResult, one run started at getpointestimate(samples, "MPEL", loss), so that the result is
+    never worse under the searched criterion than that sample.  maxK: cap on the number of clusters (0 = none).
+    Returns (clust, info): the best labelling (sortlabels'd) and a dict with the per-run loss, sweeps, converged, moves, K,
+    all labellings (labels), best (index of the first minimal run), kernel_ms."""
+    if loss not in _PSM_LOSSES:
+        raise ValueError("Invalid loss function specifier.")
+    samples = None
+    if ctx is not None:
+        if numsamples is None:
+            raise ValueError("numsamples is required with ctx=")
+        counts, n = None, ctx.n
+    elif hasattr(samples_or_counts, "clusts"):
+        samples = samples_or_counts
+        counts = cocluster_counts(samples.clusts)
+        numsamples, n = len(samples.clusts), counts.shape[0]
+    else:
+        if samples_or_counts is None:
+            raise ValueError("need an MCMCResult, a count matrix or ctx=")
+        if numsamples is None:
+            raise ValueError("numsamples is required with a count matrix")
+        counts = np.asarray(samples_or_counts)
+        if counts.ndim != 2 or counts.shape[0] != counts.shape[1] or not np.issubdtype(counts.dtype, np.integer):
+            raise ValueError("counts must be a square matrix of integer counts")
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        n = counts.shape[0]
+    inits, orders = [], []
+    rng = np.random.Generator(np.random.Philox(key=int(seed)))
+    ident = np.arange(1, n + 1, dtype=np.int32)
+    for _ in range(int(nruns)):
+        inits.append(np.zeros(n, np.int64))
+        orders.append(rng.permutation(n).astype(np.int32) + 1)
+    for lab in ([] if init is None else (np.atleast_2d(np.asarray(init)))):
+        if len(lab) != n:
+            raise ValueError("every labelling in init must have n entries")
+        inits.append(np.asarray(lab, np.int64))
+        orders.append(ident)
+    if samples is not None:
+        start, _ = getpointestimate(samples, "MPEL", "binder" if loss == "binder" else "VI", device=device)
+        inits.append(_labels(start))
+        orders.append(ident)
+    if not inits:
+        raise ValueError("no run: nruns = 0 and no init")
+    res = _lib.psm_search(counts, int(numsamples), _PSM_LOSSES[loss], np.stack(inits), np.stack(orders), maxK=maxK,
+                          maxsweeps=maxsweeps, device=device, ctx=ctx)
+    info = {k: res[k] for k in ("loss", "sweeps", "converged", "moves", "K", "labels", "best", "kernel_ms", "loss_num")}
+    if samples is not None and loss == "VI":
+        S = np.stack([_labels(c) for c in samples.clusts])
+        sizes = np.stack([np.bincount(s, minlength=n + 1)[s] for s in S])
+        info["vi_constant"] = float(np.mean(np.log(sizes)))
+    return res["labels"][res["best"]].copy(), info
+
+
 def lossmatrix(samples, loss: str = "VI", device: int = 0):
     """The symmetrised matrix of pairwise losses that getpointestimate(method="MPEL") searches (pointestimate.jl:49-56)
     and its column sums."""

@@ -486,6 +486,34 @@ int32_t rc_psm_search_ctx(rc_ctx *ctx, int64_t numsamples, int32_t loss, int32_t
                           const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out,
                           rc_psm_run_t *runs_out, int32_t *best, double *kernel_ms);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Exact expected-VI search: the same greedy search (one run = starting labels, a point order, maxsweeps; the same scoring
+ * of every non-empty cluster and a new one, the same tie rules) for the posterior expected Variation of Information itself
+ * — the mean over the m samples of VI(c, sample), SALSO's "VI" — instead of RC_PSM_VILB's lower bound.  It needs the
+ * samples, not only their pairwise counts.  DESIGN.md §8 "Exact expected VI search".
+ *
+ * Fixed point.  phi(x) = x·log x, g(x) = phi(x+1) − phi(x).  rc_vi_gtable writes Gq[x] = llrint(g(x)·2^32), x = 0..n−1
+ * (Gq[0] = 0; g(x) = log(x+1) + x·log1p(1/x) for x >= 1); Phiq(x) = Σ_{y<x} Gq[y].  The search minimises the integer
+ *   Q(c) = m·Σ_k Phiq(n_k) − 2·Σ_s Σ_{k,l} Phiq(N^s_kl),   N^s_kl = #{j : c_j = k, sample_s[j] = l},
+ * and a move of point i into cluster k changes Q by exactly m·Gq[n_k] − 2·Σ_s Gq[N^s[l_s(i)][k]] (0 for a new cluster), so
+ * a run is a pure integer function of its arguments.  Per run: loss_num = Q, loss = (Q + Σ_s Σ_l Phiq(n^s_l)) / (2^32·n·m),
+ * the expected VI in nats (within 2·2^-32 of the f64 value); sweeps, converged, moves, K as rc_psm_search.
+ *
+ * Differences from rc_psm_search: the slot cap is always positive — Kcap = maxK, or with maxK = 0 the largest cluster
+ * count among the samples — and starting labels are compacted to slots 1..K0 by first appearance before the run.
+ * samples: host m×n int64, labels 1..n.  Capacity (RC_ERR_CAPACITY beyond, checked before the samples are read where
+ * possible): n <= 8192, m·n <= 2^26, min(Kcap, n) <= 1024, nruns·m·Lmax·Kcap4·2 bytes of contingency tables <= 4 GiB
+ * (Lmax = largest cluster count among the samples, Kcap4 = Kcap rounded up to a multiple of 4).
+ * RC_ERR_ARG: a NULL pointer, m, n or nruns < 1, maxsweeps < 1, maxK < 0, a sample label outside 1..n, a starting label
+ * outside 0..n, an order that is not a permutation, a run that starts with more than Kcap clusters.
+ * best: the first run of minimal loss_num (0-based).  runs_out is untyped for the same reason as rc_psm_search's.
+ * ------------------------------------------------------------------------------------------------------------- */
+int32_t rc_vi_gtable(int64_t n, int64_t *out /* n */);
+int32_t rc_vi_search(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n, int32_t nruns,
+                     const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */,
+                     int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */, void *runs_out /* rc_psm_run_t[nruns] */,
+                     int32_t *best, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

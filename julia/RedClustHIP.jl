@@ -305,6 +305,12 @@ A greedy search over all partitions for the clustering of minimum expected loss 
 labels in random point orders plus one run started at `getpointestimate_hip(result; loss)`, so the answer is never worse
 under the searched criterion than the best sample.  `loss`: "binder" or "VI" (Wade & Ghahramani's lower bound).
 `info`: named tuple of the per-run `loss`, `sweeps`, `converged`, `moves`, `K`, all `labels` (n × runs) and `best`.
+
+`exact = true` (`loss = "VI"` only) minimises the posterior expected VI itself — the mean over `result.clusts` of VI(c, sample),
+SALSO's "VI" — instead of its lower bound (rc_vi_search: fixed point, every run an exact integer function of its inputs).
+Its runs are the same `nruns` orders from empty labels, one from the MPEL VI sample and one from the result of the
+lower-bound search with the same arguments, so the answer is never worse in expected VI than either; `info.loss` is then the
+expected VI and `info.loss_num` the integer criterion.
 """
 struct RcPsmRun
     loss::Cdouble
@@ -315,9 +321,13 @@ struct RcPsmRun
 end
 
 function searchpointestimate(b::HIPBackend, result; loss::String = "VI", nruns::Integer = 16, maxK::Integer = 0,
-                             maxsweeps::Integer = 100, seed::Integer = 0)
+                             maxsweeps::Integer = 100, seed::Integer = 0, exact::Bool = false)
     code = Dict("binder" => 0, "VI" => 1)
     haskey(code, loss) || throw(ArgumentError("Invalid loss function specifier."))
+    if exact
+        loss == "VI" || throw(ArgumentError("exact = true needs loss = \"VI\""))
+        return searchexactvi(b, result, nruns, maxK, maxsweeps, seed)
+    end
     m = length(result.clusts); n = length(result.clusts[1])
     counts = zeros(UInt32, n, n)                                  # Σ adjacencymatrix(clusts[s]) (src/utils.jl:59-63), exact
     for c in result.clusts, j in 1:n, i in 1:n
@@ -343,6 +353,43 @@ function searchpointestimate(b::HIPBackend, result; loss::String = "VI", nruns::
     check(Ptr{Cvoid}(C_NULL), rc)
     info = (loss = [x.loss for x in runs], sweeps = [Int(x.sweeps) for x in runs], converged = [x.converged != 0 for x in runs],
             moves = [Int(x.moves) for x in runs], K = [Int(x.K) for x in runs], labels = labels, best = Int(best[1]) + 1)
+    return (labels[:, best[1] + 1], info)
+end
+
+function searchexactvi(b::HIPBackend, result, nruns::Integer, maxK::Integer, maxsweeps::Integer, seed::Integer)
+    m = length(result.clusts); n = length(result.clusts[1])
+    samples = Matrix{Int64}(undef, n, m)                          # column s = sample s: row-major m×n for the library
+    for s in 1:m
+        samples[:, s] .= result.clusts[s]
+    end
+    lower, _ = searchpointestimate(b, result; loss = "VI", nruns = nruns, maxK = maxK, maxsweeps = maxsweeps, seed = seed)
+    R = Int(nruns) + 2
+    init = zeros(Int64, n, R)                                     # column r = run r: row-major R×n for the library
+    order = Matrix{Int32}(undef, n, R)
+    rng = Random.MersenneTwister(seed)
+    for r in 1:nruns
+        order[:, r] .= Random.randperm(rng, n)
+    end
+    start, _ = getpointestimate_hip(result; loss = "VI", device = b.device)
+    init[:, R - 1] .= start; order[:, R - 1] .= 1:n
+    init[:, R] .= lower; order[:, R] .= 1:n
+    cap = Int(maxK)
+    if cap == 0                                                   # the library's default cap, widened to the starts' cluster counts
+        lmax = maximum(length(unique(c)) for c in result.clusts)
+        need = max(length(unique(start)), length(unique(lower)))
+        cap = need > lmax ? need : 0
+    end
+    labels = Matrix{Int64}(undef, n, R)
+    runs = Vector{RcPsmRun}(undef, R)
+    best = Int32[0]
+    rc = ccall((:rc_vi_search, LIB), Int32,
+               (Int32, Ptr{Int64}, Int64, Int64, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
+                Ptr{Int32}, Ptr{Cdouble}),
+               b.device, samples, m, n, R, init, order, cap, maxsweeps, labels, runs, best, C_NULL)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    info = (loss = [x.loss for x in runs], loss_num = [x.loss_num for x in runs], sweeps = [Int(x.sweeps) for x in runs],
+            converged = [x.converged != 0 for x in runs], moves = [Int(x.moves) for x in runs], K = [Int(x.K) for x in runs],
+            labels = labels, best = Int(best[1]) + 1)
     return (labels[:, best[1] + 1], info)
 end
 

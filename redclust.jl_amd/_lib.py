@@ -86,7 +86,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
             os.path.join(CSRC, "kmedoids.inc.hip"),
             os.path.join(CSRC, "chain.inc.hip"), os.path.join(CSRC, "chains.inc.hip"), os.path.join(CSRC, "samplek.inc.hip"),
             os.path.join(CSRC, "mixture.inc.hip"), os.path.join(CSRC, "kmeans.inc.hip"),
-            os.path.join(CSRC, "pointsearch.inc.hip"), HEADER]
+            os.path.join(CSRC, "pointsearch.inc.hip"), os.path.join(CSRC, "visearch.inc.hip"), HEADER]
     if not force and os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(s) for s in srcs):
         return SO
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-o", SO, srcs[0]]
@@ -186,6 +186,9 @@ SIGNATURES = {
                                   C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rc_psm_search_ctx": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_vi_gtable": (C.c_int32, [C.c_int64, C.c_void_p]),
+    "rc_vi_search": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rc_layout_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rc_event_overhead_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "rc_kernel_timing": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -704,6 +707,44 @@ def psm_search(counts, numsamples: int, loss: int, init, order, maxK: int = 0, m
                              order.ctypes.data, int(maxK), int(maxsweeps), labels.ctypes.data, runs, C.byref(best), C.byref(ms))
         if rc != RC_OK:
             raise _error(rc, L.rc_last_error(None).decode())
+    out = dict(labels=labels[:nruns, :n], best=int(best.value), kernel_ms=float(ms.value))
+    for k, ty in RcPsmRun._fields_:
+        out[k] = np.array([getattr(r, k) for r in runs[:nruns]], dtype=np.float64 if ty is C.c_double else np.int64)
+    out["converged"] = out["converged"].astype(bool)
+    return out
+
+
+def vi_gtable(n: int) -> np.ndarray:
+    """rc_vi_gtable: Gq[x] = llrint((phi(x+1) − phi(x))·2^32), x = 0..n−1, phi(x) = x·log x — the table rc_vi_search decides on."""
+    L = lib()
+    out = np.zeros(max(int(n), 1), np.int64)
+    rc = L.rc_vi_gtable(int(n), out.ctypes.data)
+    if rc != RC_OK:
+        raise _error(rc, L.rc_last_error(None).decode())
+    return out
+
+
+def vi_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
+    """rc_vi_search: the exact expected-VI search.  samples: m×n labels in 1..n; init: nruns×n labels (0 = unallocated), order:
+    nruns×n 1-based permutations.  Returns psm_search's dict: labels (nruns×n, sortlabels'd), the per-run arrays loss (the
+    expected VI), loss_num (the integer Q), sweeps, converged, moves, K, and best, kernel_ms."""
+    L = lib()
+    S = np.ascontiguousarray(samples, dtype=np.int64)
+    init = np.ascontiguousarray(init, dtype=np.int64)
+    order = np.ascontiguousarray(order, dtype=np.int32)
+    if S.ndim != 2:
+        raise ValueError("samples must be an m×n matrix of labels")
+    if init.ndim != 2 or init.shape != order.shape or init.shape[1] != S.shape[1]:
+        raise ValueError("init and order must be nruns×n arrays of the same shape, n the samples' length")
+    m, n = S.shape
+    nruns = init.shape[0]
+    labels = np.zeros((max(nruns, 1), max(n, 1)), np.int64)
+    runs = (RcPsmRun * max(nruns, 1))()
+    best, ms = C.c_int32(-1), C.c_double()
+    rc = L.rc_vi_search(int(device), S.ctypes.data, m, n, nruns, init.ctypes.data, order.ctypes.data, int(maxK), int(maxsweeps),
+                        labels.ctypes.data, runs, C.byref(best), C.byref(ms))
+    if rc != RC_OK:
+        raise _error(rc, L.rc_last_error(None).decode())
     out = dict(labels=labels[:nruns, :n], best=int(best.value), kernel_ms=float(ms.value))
     for k, ty in RcPsmRun._fields_:
         out[k] = np.array([getattr(r, k) for r in runs[:nruns]], dtype=np.float64 if ty is C.c_double else np.int64)

@@ -7809,3 +7809,4 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "mixture.inc.hip"
 #include "kmeans.inc.hip"
 #include "pointsearch.inc.hip"
+#include "visearch.inc.hip"

@@ -1,0 +1,477 @@
+// Exact posterior expected VI search on the device: the greedy search of pointsearch.inc.hip (same mechanism, same tie
+// rules) for the criterion SALSO calls "VI" proper — the mean over the m samples of VI(c, sample) — instead of Wade &
+// Ghahramani's lower bound.  Included at the end of redclust_hip.hip (same translation unit: shares fail(), PECHK, the
+// error buffer and psm's sortable-key reduction).
+//
+// Criterion (DESIGN.md §8 "Exact expected VI search"), φ(x) = x·log x:
+//   n·m·E[VI](c) = m·Σ_k φ(n_k) + Σ_s Σ_l φ(n^s_l) − 2·Σ_s Σ_{k,l} φ(N^s_kl),   N^s_kl = #{j : c_j = k, c^s_j = l}
+// in fixed point: Gq[x] = llrint((φ(x+1) − φ(x))·2^32), Φq(x) = Σ_{y<x} Gq[y], and the search minimises the integer
+//   Q(c) = m·Σ_k Φq(n_k) − 2·Σ_s Σ_kl Φq(N^s_kl).
+// With point i out of its cluster, putting it into k changes Q by exactly  Δ_k = m·Gq[n_k] − 2·Σ_s Gq[N^s[l_s(i)][k]]
+// (Δ_new = 0), so a run is a pure integer function of its inputs and every accepted move lowers Q strictly.
+//
+// One run = one workgroup of 1024 threads, persistent over its sweeps; nruns workgroups per launch.
+// Global memory, per run: the contingency tables u16 N[s][l][kpad] (kpad = Kcap rounded up to 4; a point's m rows
+// N[s][l_s(i)][·] are each contiguous over k).  Shared by the runs: the samples, re-labelled per sample to 0..L_s−1 and
+// transposed to SL[i][s], so the m labels of the visited point are contiguous.
+// A table row is covered by G = kpad/4 threads of 8 bytes (4 slots) each; thread (r, c) = (tid / G, tid % G) takes the
+// samples r, r + R, … (R = 1024 / G rows per pass) and the slots 4c..4c+3 of each.  Every table element is only ever
+// read (phase A) and written (phase C) by that one thread, so the tables need no barrier of their own.
+// A step: (A) each thread adds Gq[N] of its slots over its samples into four registers, then into the per-slot LDS
+// accumulators with 64-bit integer atomics (order-free); barrier; (B) thread k − 1 scores slot k, argmin by psm's
+// sortable keys; barrier; (C) every thread reads the 16 partials, adds the new-cluster candidate; lab / sz are written
+// by thread 0, N[s][l][a] −= 1 and N[s][l][w] += 1 by the owners of those slots (nothing when a = w).  Two barriers per
+// step.  The next point's m sample labels are loaded into registers at the top of a step and parked in the other half
+// of an LDS double buffer behind the first barrier (m ≤ 4096; beyond that they are read from global memory in place).
+//
+// LDS (dynamic, carved at 16-byte offsets): Gq i64[n+1] (64 KiB at n = 8192; Φq at the end), acc u64[kpad], the
+// reduction partials, sz u16[Kcap+2], lab u16[n], the label double buffer u16[2][1024·PQ]: 109 024 B at the largest sizes.
+
+namespace visearch {
+
+constexpr int TPB = 1024;
+constexpr int NWAVE = TPB / 64;
+constexpr int NMAX = 8192;
+constexpr int KCAP_MAX = 1024;                        // one slot per thread in phase B
+constexpr int VEC = 4;                                // slots per thread in a table row (8 bytes)
+constexpr long long MN_MAX = 1ll << 26;               // |Q| <= 2·m·n·log(n)·2^32 < 2^63
+constexpr size_t TABLE_BUDGET = (size_t)4 << 30;      // bytes of contingency tables, all runs together
+constexpr int STAGE_Q = 4;                            // labels of the next point staged in LDS while m <= 1024·STAGE_Q
+
+struct RunOut {
+    long long Q, moves;
+    int sweeps, converged, K, pad_;
+};
+
+struct Args {
+    const long long *Gq;          // n entries
+    const long long *Phi;         // n + 1 entries
+    const unsigned short *SL;     // n × m per-sample labels, 0-based
+    unsigned short *N;            // nruns × m × Lmax × kpad, zeroed
+    const unsigned short *init;   // nruns × n slots, 0 = unallocated
+    const unsigned short *sz0;    // nruns × (Kcap + 2) slot sizes of init
+    const int *K0;                // clusters of init
+    const int *order;             // nruns × n, 0-based
+    unsigned short *labels;       // nruns × n out (slots)
+    RunOut *out;
+    int n, m, Lmax, kpad, Kcap, maxsweeps;
+};
+
+__host__ __device__ inline size_t up16(size_t x) { return (x + 15) / 16 * 16; }
+
+struct Carve {
+    size_t gq, acc, red, sz, lab, stage, total;
+    __host__ __device__ Carve(int n, int kpad, int Kcap, int PQ)
+    {
+        gq = 0;
+        acc = gq + up16(8 * (size_t)(n + 1));
+        red = acc + up16(8 * (size_t)kpad);
+        sz = red + up16((size_t)NWAVE * (8 + 8 + 4 + 4 + 4));
+        lab = sz + up16(2 * (size_t)(Kcap + 2));
+        stage = lab + up16(2 * (size_t)n);
+        total = stage + up16(2 * 2 * (size_t)TPB * PQ);
+    }
+};
+
+__device__ inline void add_row(const uint2 v, int ka, const long long *Gq, long long (&acc)[VEC])
+{
+    // ka: where the visited point's own slot sits in this thread's four, if it does — the point itself is out
+    const unsigned x0 = (v.x & 0xFFFFu) - (ka == 0 ? 1u : 0u), x1 = (v.x >> 16) - (ka == 1 ? 1u : 0u);
+    const unsigned x2 = (v.y & 0xFFFFu) - (ka == 2 ? 1u : 0u), x3 = (v.y >> 16) - (ka == 3 ? 1u : 0u);
+    acc[0] += Gq[x0]; acc[1] += Gq[x1]; acc[2] += Gq[x2]; acc[3] += Gq[x3];
+}
+
+template <int PQ>
+__global__ __launch_bounds__(TPB) void k_visearch(Args A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char vis_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = A.n, m = A.m, Lmax = A.Lmax, kpad = A.kpad, Kcap = A.Kcap, run = blockIdx.x;
+
+    const Carve cv(n, kpad, Kcap, PQ);
+    long long *Gq = reinterpret_cast<long long *>(vis_lds + cv.gq);
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(vis_lds + cv.acc);
+    unsigned long long *r_sc = reinterpret_cast<unsigned long long *>(vis_lds + cv.red);
+    unsigned long long *r_q = r_sc + NWAVE;
+    unsigned *r_pr = reinterpret_cast<unsigned *>(r_q + NWAVE), *r_slot = r_pr + NWAVE, *r_free = r_slot + NWAVE;
+    unsigned short *sz = reinterpret_cast<unsigned short *>(vis_lds + cv.sz);
+    unsigned short *lab = reinterpret_cast<unsigned short *>(vis_lds + cv.lab);
+    unsigned short *stage = reinterpret_cast<unsigned short *>(vis_lds + cv.stage);   // [2][TPB·PQ]
+
+    const unsigned short *__restrict__ SL = A.SL;
+    unsigned short *Nrun = A.N + (size_t)run * m * Lmax * kpad;
+    const size_t lstride = (size_t)Lmax * kpad;                       // elements per sample
+
+    for (int x = tid; x < n; x += TPB) Gq[x] = A.Gq[x];
+    for (int k = tid; k < kpad; k += TPB) acc[k] = 0;
+    for (int k = tid; k < Kcap + 2; k += TPB) sz[k] = A.sz0[(size_t)run * (Kcap + 2) + k];
+    for (int j = tid; j < n; j += TPB) lab[j] = A.init[(size_t)run * n + j];
+    __syncthreads();
+    int K = A.K0[run];
+    if (K) {
+        // the tables of the starting labels: one thread per sample (the only pass in which a thread writes elements
+        // it does not own; the barrier below orders it before everything else)
+        for (int s = tid; s < m; s += TPB) {
+            unsigned short *Ns = Nrun + (size_t)s * lstride;
+            for (int j = 0; j < n; ++j) {
+                const unsigned l = lab[j];
+                if (l) Ns[(size_t)SL[(size_t)j * m + s] * kpad + (l - 1)] += 1;
+            }
+        }
+    }
+
+    const int G = kpad / VEC, R = TPB / G;
+    const int r = tid / G, c = tid - r * G;
+    const bool active = r < R;
+    const int *__restrict__ ord = A.order + (size_t)run * n;
+    int i = ord[0], i1 = ord[n > 1 ? 1 : 0];
+    int iprev = -1, buf = 0;
+    unsigned wprev = 0;
+    if (PQ) {
+#pragma unroll
+        for (int q = 0; q < PQ; ++q) {
+            const int s = tid + q * TPB;
+            if (s < m) stage[s] = SL[(size_t)i * m + s];
+        }
+    }
+    __syncthreads();
+
+    long long moves = 0;
+    int sweeps = 0, converged = 0;
+    const unsigned long long key_new = psm::key_i64(0);
+
+    for (;;) {
+        int moved = 0;
+        for (int t = 0; t < n; ++t) {
+            // the next point's sample labels: issued now, parked in LDS behind the first barrier
+            const int inext = i1;
+            {
+                int t2 = t + 2;
+                if (t2 >= n) t2 -= n;
+                if (t2 >= n) t2 -= n;
+                i1 = ord[t2];
+            }
+            unsigned short nxt[PQ ? PQ : 1];
+            if (PQ) {
+#pragma unroll
+                for (int q = 0; q < PQ; ++q) {
+                    const int s = tid + q * TPB;
+                    nxt[q] = (s < m) ? SL[(size_t)inext * m + s] : (unsigned short)0;
+                }
+            }
+            const unsigned short *cur = PQ ? stage + (size_t)buf * TPB * PQ : SL + (size_t)i * m;
+
+            // lab[i] was written by another thread without a barrier in between only if i is the previous point (n = 1)
+            const unsigned a = (i == iprev) ? wprev : (unsigned)lab[i];
+
+            // phase A: Σ_s Gq[N^s[l_s(i)][k]] for this thread's four slots over its samples
+            if (active) {
+                const int ka = (int)a - 1 - c * VEC;
+                const unsigned short *Nc = Nrun + (size_t)c * VEC;
+                long long part[VEC] = {0, 0, 0, 0};
+                int s = r;
+                for (; s + 3 * R < m; s += 4 * R) {
+                    const unsigned l0 = cur[s], l1 = cur[s + R], l2 = cur[s + 2 * R], l3 = cur[s + 3 * R];
+                    const uint2 v0 = *reinterpret_cast<const uint2 *>(Nc + (size_t)s * lstride + (size_t)l0 * kpad);
+                    const uint2 v1 = *reinterpret_cast<const uint2 *>(Nc + (size_t)(s + R) * lstride + (size_t)l1 * kpad);
+                    const uint2 v2 = *reinterpret_cast<const uint2 *>(Nc + (size_t)(s + 2 * R) * lstride + (size_t)l2 * kpad);
+                    const uint2 v3 = *reinterpret_cast<const uint2 *>(Nc + (size_t)(s + 3 * R) * lstride + (size_t)l3 * kpad);
+                    add_row(v0, ka, Gq, part); add_row(v1, ka, Gq, part); add_row(v2, ka, Gq, part); add_row(v3, ka, Gq, part);
+                }
+                for (; s < m; s += R) {
+                    const unsigned l0 = cur[s];
+                    add_row(*reinterpret_cast<const uint2 *>(Nc + (size_t)s * lstride + (size_t)l0 * kpad), ka, Gq, part);
+                }
+#pragma unroll
+                for (int e = 0; e < VEC; ++e)
+                    if (part[e]) atomicAdd(&acc[c * VEC + e], (unsigned long long)part[e]);
+            }
+            __syncthreads();
+
+            // phase B: score the slots (and clear their accumulators); thread k − 1 owns slot k
+            if (PQ) {
+#pragma unroll
+                for (int q = 0; q < PQ; ++q) {
+                    const int s = tid + q * TPB;
+                    if (s < m) stage[(size_t)(buf ^ 1) * TPB * PQ + s] = nxt[q];
+                }
+            }
+            const unsigned emptied = (a && sz[a] == 1) ? 1u : 0u;
+            psm::Cand best{~0ull, ~0u, 0u, 0u};
+            unsigned minfree = ~0u;
+            if (tid < kpad) {
+                const unsigned k = (unsigned)tid + 1u;
+                const long long sum = (long long)acc[tid];
+                acc[tid] = 0;
+                if (k <= (unsigned)Kcap) {
+                    const int nk = (int)sz[k] - (k == a ? 1 : 0);
+                    if (nk <= 0) minfree = k;
+                    else best = psm::Cand{psm::key_i64((long long)m * Gq[nk] - 2 * sum), (k == a) ? 0u : k, k, 0u};
+                }
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const unsigned long long osc = psm::shfl_xor_u64(best.sc, off);
+                const unsigned opr = (unsigned)__shfl_xor((int)best.pr, off), oslot = (unsigned)__shfl_xor((int)best.slot, off);
+                if (psm::better(osc, opr, best)) best = psm::Cand{osc, opr, oslot, 0u};
+                minfree = min(minfree, (unsigned)__shfl_xor((int)minfree, off));
+            }
+            if (lane == 0) { r_sc[wave] = best.sc; r_pr[wave] = best.pr; r_slot[wave] = best.slot; r_free[wave] = minfree; }
+            __syncthreads();
+            best = psm::Cand{r_sc[0], r_pr[0], r_slot[0], 0u};
+            minfree = r_free[0];
+#pragma unroll
+            for (int w = 1; w < NWAVE; ++w) {
+                if (psm::better(r_sc[w], r_pr[w], best)) best = psm::Cand{r_sc[w], r_pr[w], r_slot[w], 0u};
+                minfree = min(minfree, r_free[w]);
+            }
+            // the new-cluster candidate: while the cluster count is below the cap there is a free slot in 1..Kcap
+            const int Know = K - (int)emptied;
+            unsigned isnew = 0;
+            if (Know < Kcap) {
+                const unsigned slot = emptied ? a : minfree;
+                const unsigned pr = emptied ? 0u : minfree;
+                if (psm::better(key_new, pr, best)) { best = psm::Cand{key_new, pr, slot, 0u}; isnew = 1; }
+            }
+            const unsigned w = best.slot;
+
+            // phase C: put i into w.  A table element is touched only by the thread that reads it in phase A; lab and sz
+            // are read by the other threads only behind the next step's first barrier
+            if (a != w && active) {
+                const bool da = a && (int)(a - 1u) / VEC == c, dw = (int)(w - 1u) / VEC == c;
+                if (da || dw) {
+                    for (int s = r; s < m; s += R) {
+                        unsigned short *row = Nrun + (size_t)s * lstride + (size_t)cur[s] * kpad;
+                        if (da) row[a - 1u] = (unsigned short)(row[a - 1u] - 1u);
+                        if (dw) row[w - 1u] = (unsigned short)(row[w - 1u] + 1u);
+                    }
+                }
+            }
+            if (tid == 0) {
+                lab[i] = (unsigned short)w;
+                if (a) sz[a] = (unsigned short)(sz[a] - 1);
+                sz[w] = (unsigned short)(sz[w] + 1);
+            }
+            moved += (a == 0 || w != a) ? 1 : 0;
+            K = Know + (int)isnew;
+            iprev = i; wprev = w;
+            i = inext;
+            buf ^= 1;
+        }
+        ++sweeps;
+        moves += moved;
+        if (!moved) { converged = 1; break; }
+        if (sweeps >= A.maxsweeps) break;
+    }
+    __syncthreads();
+
+    // Q of the final labelling from the tables, with Φq in place of Gq
+    for (int j = tid; j < n; j += TPB) A.labels[(size_t)run * n + j] = lab[j];
+    for (int x = tid; x <= n; x += TPB) Gq[x] = A.Phi[x];
+    __syncthreads();
+    unsigned long long q = 0;
+    if (tid < Kcap) q = (unsigned long long)((long long)m * Gq[sz[tid + 1]]);
+    {
+        unsigned long long t2 = 0;
+        const uint2 *N2 = reinterpret_cast<const uint2 *>(Nrun);
+        const size_t cnt = (size_t)m * lstride / VEC;
+        for (size_t x = tid; x < cnt; x += TPB) {
+            const uint2 v = N2[x];
+            t2 += (unsigned long long)Gq[v.x & 0xFFFFu] + (unsigned long long)Gq[v.x >> 16] +
+                  (unsigned long long)Gq[v.y & 0xFFFFu] + (unsigned long long)Gq[v.y >> 16];
+        }
+        q -= 2 * t2;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) q += psm::shfl_xor_u64(q, off);
+    if (lane == 0) r_q[wave] = q;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long s = 0;
+        for (int w = 0; w < NWAVE; ++w) s += r_q[w];
+        RunOut o{};
+        o.Q = (long long)s; o.moves = moves; o.sweeps = sweeps; o.converged = converged; o.K = K;
+        A.out[run] = o;
+    }
+}
+
+static hipError_t launch(int PQ, int nruns, size_t lds, const Args &A)
+{
+#define VIS_LAUNCH(QQ)                                                                                                    \
+    do {                                                                                                                  \
+        hipError_t e = hipFuncSetAttribute((const void *)k_visearch<QQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        if (e != hipSuccess) return e;                                                                                    \
+        k_visearch<QQ><<<nruns, TPB, lds, 0>>>(A);                                                                        \
+    } while (0)
+    if (PQ == 0) VIS_LAUNCH(0);
+    else if (PQ == 1) VIS_LAUNCH(1);
+    else VIS_LAUNCH(STAGE_Q);
+#undef VIS_LAUNCH
+    return hipGetLastError();
+}
+
+static void gtable(int64_t n, int64_t *out)
+{
+    out[0] = 0;
+    for (int64_t x = 1; x < n; ++x) {
+        const double d = (double)x;
+        out[x] = (int64_t)std::llrint(std::ldexp(std::log(d + 1.0) + d * std::log1p(1.0 / d), 32));
+    }
+}
+
+}  // namespace visearch
+
+extern "C" int32_t rc_vi_gtable(int64_t n, int64_t *out)
+{
+    if (!out) return fail(nullptr, RC_ERR_ARG, "rc_vi_gtable: NULL argument");
+    if (n < 1) return fail(nullptr, RC_ERR_ARG, "rc_vi_gtable: need n >= 1 (got %lld)", (long long)n);
+    visearch::gtable(n, out);
+    return RC_OK;
+}
+
+extern "C" int32_t rc_vi_search(int32_t device, const int64_t *samples, int64_t m, int64_t n, int32_t nruns, const int64_t *init,
+                                const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out_,
+                                int32_t *best, double *kernel_ms)
+{
+    using namespace visearch;
+    const char *who = "rc_vi_search";
+    rc_psm_run_t *runs_out = (rc_psm_run_t *)runs_out_;
+    if (!samples || !init || !order || !labels_out || !runs_out || !best) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
+    if (m < 1 || n < 1 || nruns < 1)
+        return fail(nullptr, RC_ERR_ARG, "%s: need m >= 1, n >= 1 and nruns >= 1 (got m=%lld n=%lld nruns=%d)", who, (long long)m, (long long)n, nruns);
+    if (maxsweeps < 1 || maxK < 0) return fail(nullptr, RC_ERR_ARG, "%s: need maxsweeps >= 1 and maxK >= 0 (got %d, %d)", who, maxsweeps, maxK);
+    // the capacity in n and m·n before anything is read
+    if (n > NMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %d points whose state fits the workgroup's LDS", who, (long long)n, NMAX);
+    if (m > MN_MAX / n) return fail(nullptr, RC_ERR_CAPACITY, "%s: m*n exceeds 2^26 = %lld (m=%lld n=%lld)", who, MN_MAX, (long long)m, (long long)n);
+
+    // ---- the samples: labels 1..n, re-labelled per sample to 0..L_s-1 by first appearance, transposed to [i][s]
+    std::vector<unsigned short> h_SL((size_t)n * m);
+    std::vector<int> map((size_t)n + 1), cnt((size_t)n + 1);
+    std::vector<int64_t> Gq((size_t)n), Phi((size_t)n + 1);
+    gtable(n, Gq.data());
+    Phi[0] = 0;
+    for (int64_t x = 0; x < n; ++x) Phi[(size_t)x + 1] = Phi[(size_t)x] + Gq[(size_t)x];
+    int Lmax = 0;
+    __int128 constant = 0;                                              // Σ_s Σ_l Φq(n^s_l)
+    for (int64_t s = 0; s < m; ++s) {
+        std::fill(map.begin(), map.end(), 0);
+        std::fill(cnt.begin(), cnt.end(), 0);
+        int L = 0;
+        for (int64_t j = 0; j < n; ++j) {
+            const int64_t l = samples[(size_t)s * n + j];
+            if (l < 1 || l > n) return fail(nullptr, RC_ERR_ARG, "%s: label %lld of sample %lld outside 1..n", who, (long long)l, (long long)s + 1);
+            if (!map[(size_t)l]) map[(size_t)l] = ++L;
+            h_SL[(size_t)j * m + s] = (unsigned short)(map[(size_t)l] - 1);
+            cnt[(size_t)map[(size_t)l]]++;
+        }
+        for (int l = 1; l <= L; ++l) constant += Phi[(size_t)cnt[(size_t)l]];
+        Lmax = std::max(Lmax, L);
+    }
+    // ---- the slot cap: always positive
+    const int64_t Kcap64 = std::min<int64_t>(maxK > 0 ? maxK : Lmax, n);
+    if (Kcap64 > KCAP_MAX)
+        return fail(nullptr, RC_ERR_CAPACITY, "%s: the slot cap %lld (maxK, or the largest cluster count among the samples) exceeds %d", who,
+                    (long long)Kcap64, KCAP_MAX);
+    const int Kcap = (int)Kcap64, kpad = (Kcap + VEC - 1) / VEC * VEC;
+    const size_t table_elems = (size_t)m * Lmax * kpad;
+    if ((double)table_elems * 2.0 * nruns > (double)TABLE_BUDGET)
+        return fail(nullptr, RC_ERR_CAPACITY, "%s: the contingency tables (runs x m x Lmax x Kcap4 x 2 B = %d x %lld x %d x %d x 2, Kcap4 = the slot cap rounded up to 4) exceed the budget of %llu MiB",
+                    who, nruns, (long long)m, Lmax, kpad, (unsigned long long)(TABLE_BUDGET >> 20));
+
+    // ---- the runs: labels in 0..n compacted to slots 1..K0 by first appearance, orders permutations of 1..n
+    std::vector<unsigned short> h_init((size_t)nruns * n), h_sz((size_t)nruns * (Kcap + 2), 0);
+    std::vector<int> h_K((size_t)nruns), h_ord((size_t)nruns * n);
+    std::vector<char> seen((size_t)n);
+    for (int r = 0; r < nruns; ++r) {
+        std::fill(map.begin(), map.end(), 0);
+        int K = 0;
+        for (int64_t j = 0; j < n; ++j) {
+            const int64_t l = init[(size_t)r * n + j];
+            if (l < 0 || l > n) return fail(nullptr, RC_ERR_ARG, "%s: label %lld of run %d outside 0..n", who, (long long)l, r + 1);
+            if (l && !map[(size_t)l]) map[(size_t)l] = ++K;
+        }
+        if (K > Kcap) return fail(nullptr, RC_ERR_ARG, "%s: run %d starts with %d clusters, more than the slot cap %d", who, r + 1, K, Kcap);
+        for (int64_t j = 0; j < n; ++j) {
+            const int slot = map[(size_t)init[(size_t)r * n + j]];      // map[0] = 0
+            h_init[(size_t)r * n + j] = (unsigned short)slot;
+            if (slot) h_sz[(size_t)r * (Kcap + 2) + slot]++;
+        }
+        h_K[(size_t)r] = K;
+        std::fill(seen.begin(), seen.end(), 0);
+        for (int64_t t = 0; t < n; ++t) {
+            const int32_t o = order[(size_t)r * n + t];
+            if (o < 1 || o > n || seen[(size_t)o - 1]) return fail(nullptr, RC_ERR_ARG, "%s: the order of run %d is not a permutation of 1..n", who, r + 1);
+            seen[(size_t)o - 1] = 1;
+            h_ord[(size_t)r * n + t] = o - 1;
+        }
+    }
+
+    int ndev = 0;
+    PECHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(nullptr, RC_ERR_ARG, "%s: device %d not available (%d visible)", who, device, ndev);
+    PECHK(hipSetDevice(device));
+
+    psm::DevBufs B;
+    long long *d_G, *d_Phi; unsigned short *d_SL, *d_N, *d_init, *d_sz, *d_lab; int *d_K, *d_ord; RunOut *d_out;
+    PECHK(hipMalloc(&B.p[0], Gq.size() * 8)); d_G = (long long *)B.p[0];
+    PECHK(hipMalloc(&B.p[1], Phi.size() * 8)); d_Phi = (long long *)B.p[1];
+    PECHK(hipMalloc(&B.p[2], h_SL.size() * 2)); d_SL = (unsigned short *)B.p[2];
+    PECHK(hipMalloc(&B.p[3], table_elems * 2 * (size_t)nruns)); d_N = (unsigned short *)B.p[3];
+    PECHK(hipMalloc(&B.p[4], h_init.size() * 2)); d_init = (unsigned short *)B.p[4];
+    PECHK(hipMalloc(&B.p[5], h_sz.size() * 2)); d_sz = (unsigned short *)B.p[5];
+    PECHK(hipMalloc(&B.p[6], h_K.size() * 4)); d_K = (int *)B.p[6];
+    PECHK(hipMalloc(&B.p[7], h_ord.size() * 4)); d_ord = (int *)B.p[7];
+    PECHK(hipMalloc(&B.p[8], h_init.size() * 2)); d_lab = (unsigned short *)B.p[8];
+    PECHK(hipMalloc(&B.p[9], (size_t)nruns * sizeof(RunOut))); d_out = (RunOut *)B.p[9];
+    PECHK(hipMemcpy(d_G, Gq.data(), Gq.size() * 8, hipMemcpyHostToDevice));
+    PECHK(hipMemcpy(d_Phi, Phi.data(), Phi.size() * 8, hipMemcpyHostToDevice));
+    PECHK(hipMemcpy(d_SL, h_SL.data(), h_SL.size() * 2, hipMemcpyHostToDevice));
+    PECHK(hipMemset(d_N, 0, table_elems * 2 * (size_t)nruns));
+    PECHK(hipMemcpy(d_init, h_init.data(), h_init.size() * 2, hipMemcpyHostToDevice));
+    PECHK(hipMemcpy(d_sz, h_sz.data(), h_sz.size() * 2, hipMemcpyHostToDevice));
+    PECHK(hipMemcpy(d_K, h_K.data(), h_K.size() * 4, hipMemcpyHostToDevice));
+    PECHK(hipMemcpy(d_ord, h_ord.data(), h_ord.size() * 4, hipMemcpyHostToDevice));
+
+    Args A{};
+    A.Gq = d_G; A.Phi = d_Phi; A.SL = d_SL; A.N = d_N; A.init = d_init; A.sz0 = d_sz; A.K0 = d_K; A.order = d_ord; A.labels = d_lab;
+    A.out = d_out; A.n = (int)n; A.m = (int)m; A.Lmax = Lmax; A.kpad = kpad; A.Kcap = Kcap; A.maxsweeps = maxsweeps;
+    const int PQ = m <= TPB ? 1 : (m <= (int64_t)TPB * STAGE_Q ? STAGE_Q : 0);
+    const size_t lds = Carve((int)n, kpad, Kcap, PQ).total;
+    hipEvent_t e0, e1;
+    PECHK(hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail(nullptr, RC_ERR_HIP, "%s: hipEventCreate failed", who); }
+    hipError_t le = hipEventRecord(e0, 0);
+    if (le == hipSuccess) le = launch(PQ, nruns, lds, A);
+    if (le == hipSuccess) le = hipEventRecord(e1, 0);
+    if (le == hipSuccess) le = hipDeviceSynchronize();
+    float ms = 0;
+    if (le == hipSuccess) le = hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if (le != hipSuccess) return fail(nullptr, RC_ERR_HIP, "%s: the search kernel failed: %s", who, hipGetErrorString(le));
+    if (kernel_ms) *kernel_ms = ms;
+    std::vector<unsigned short> h_lab(h_init.size());
+    std::vector<RunOut> h_out((size_t)nruns);
+    PECHK(hipMemcpy(h_lab.data(), d_lab, h_lab.size() * 2, hipMemcpyDeviceToHost));
+    PECHK(hipMemcpy(h_out.data(), d_out, h_out.size() * sizeof(RunOut), hipMemcpyDeviceToHost));
+
+    // ---- results: sortlabels (utils.jl:69-74), the losses, the first minimum
+    const double scale = std::ldexp((double)n * (double)m, 32);
+    int b = 0;
+    for (int r = 0; r < nruns; ++r) {
+        std::fill(map.begin(), map.end(), 0);
+        int next = 0;
+        for (int64_t j = 0; j < n; ++j) {
+            const unsigned short l = h_lab[(size_t)r * n + j];
+            if (!map[l]) map[l] = ++next;
+            labels_out[(size_t)r * n + j] = map[l];
+        }
+        const RunOut &o = h_out[(size_t)r];
+        rc_psm_run_t &R = runs_out[r];
+        R.sweeps = o.sweeps; R.converged = o.converged; R.moves = o.moves; R.K = o.K;
+        R.loss_num = o.Q;
+        R.loss = (double)((__int128)o.Q + constant) / scale;
+        if (R.loss_num < runs_out[b].loss_num) b = r;
+    }
+    *best = b;
+    return RC_OK;
+}

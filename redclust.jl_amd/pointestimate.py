@@ -99,8 +99,59 @@ def expectedloss(clust, counts, numsamples: int, loss="VI") -> float:
     return float(np.sum(np.log(same.sum(axis=1)) - 2.0 * np.log(T))) / n + 2.0 * float(np.log(m))
 
 
+def expectedvi(clust, samples) -> float:
+    """The posterior expected Variation of Information of `clust`: the mean over the samples (an MCMCResult, anything with
+    `.clusts`, or an m×n label matrix) of VI(clust, sample) = [φ(n_k) and φ(n_l) summed − 2·Σ_kl φ(N_kl)] / n with
+    φ(x) = x·log x, natural logs — what searchpointestimate(exact=True) minimises, in plain NumPy on the host."""
+    c = np.unique(_labels(clust), return_inverse=True)[1].astype(np.int64)      # 0..K−1: K·L bins per sample below
+    clusts = samples.clusts if hasattr(samples, "clusts") else samples
+    n = len(c)
+    if len(clusts) == 0:
+        raise ValueError("no samples")
+
+    def phi(x):
+        x = x[x > 0].astype(np.float64)
+        return float(np.sum(x * np.log(x)))
+
+    base = phi(np.bincount(c))
+    total = 0.0
+    for s in clusts:
+        s = np.asarray(s)
+        if len(s) != n:
+            raise ValueError("every sample must have as many labels as clust")
+        s = np.unique(_labels(s), return_inverse=True)[1].astype(np.int64)
+        total += base + phi(np.bincount(s)) - 2.0 * phi(np.bincount(c * (int(s.max()) + 1) + s))
+    return total / (n * len(clusts))
+
+
+def _vi_search_exact(samples, nruns, maxK, maxsweeps, seed, init, device):
+    """searchpointestimate(loss="VI", exact=True): see there."""
+    S = np.stack([_labels(c) for c in samples.clusts])
+    n = S.shape[1]
+    _, lower = searchpointestimate(samples, "VI", nruns=nruns, maxK=maxK, maxsweeps=maxsweeps, seed=seed, init=init, device=device)
+    inits = [np.zeros(n, np.int64)] * int(nruns)
+    rng = np.random.Generator(np.random.Philox(key=int(seed)))
+    ident = np.arange(1, n + 1, dtype=np.int32)
+    orders = [rng.permutation(n).astype(np.int32) + 1 for _ in range(int(nruns))]
+    for lab in ([] if init is None else (np.atleast_2d(np.asarray(init)))):
+        inits.append(np.asarray(lab, np.int64))                      # (lengths were checked by the lower-bound call)
+        orders.append(ident)
+    start, _ = getpointestimate(samples, "MPEL", "VI", device=device)
+    inits += [_labels(start), lower["labels"][lower["best"]]]
+    orders += [ident, ident]
+    if not maxK:
+        # the library's default cap is the samples' largest cluster count; a start with more clusters widens it
+        lmax = max(len(np.unique(s)) for s in S)
+        need = max(len(np.unique(x[x > 0])) for x in inits)
+        maxK = need if need > lmax else 0
+    res = _lib.vi_search(S, np.stack(inits), np.stack(orders), maxK=maxK, maxsweeps=maxsweeps, device=device)
+    info = {k: res[k] for k in ("loss", "sweeps", "converged", "moves", "K", "labels", "best", "kernel_ms", "loss_num")}
+    info["lower_bound"] = lower
+    return res["labels"][res["best"]].copy(), info
+
+
 def searchpointestimate(samples_or_counts=None, loss="VI", *, nruns: int = 16, maxK: int = 0, maxsweeps: int = 100,
-                        seed: int = 0, init=None, numsamples=None, ctx=None, device: int = 0):
+                        seed: int = 0, init=None, numsamples=None, ctx=None, device: int = 0, exact: bool = False):
     """Search ALL partitions for the clustering of minimum expected loss under the posterior co-clustering counts (the
     reference's docs send its users to R's SALSO for this; getpointestimate(method="MPEL") only looks at the sampled
     clusterings).  Runs on the GPU (csrc/pointsearch.inc.hip), every run one workgroup; there is no CPU fallback.
@@ -115,9 +166,26 @@ def searchpointestimate(samples_or_counts=None, loss="VI", *, nruns: int = 16, m
     (identity order); and, for an MCMCResult, one run started at getpointestimate(samples, "MPEL", loss), so that the result is
     never worse under the searched criterion than that sample.  maxK: cap on the number of clusters (0 = none).
     Returns (clust, info): the best labelling (sortlabels'd) and a dict with the per-run loss, sweeps, converged, moves, K,
-    all labellings (labels), best (index of the first minimal run), kernel_ms."""
+    all labellings (labels), best (index of the first minimal run), kernel_ms.
+
+    exact=True (loss="VI" and an MCMCResult, or anything with `.clusts`, only): minimise the posterior expected VI itself
+    (expectedvi; SALSO's "VI") instead of its lower bound — csrc/visearch.inc.hip, in fixed point, so a run is an exact
+    integer function of its inputs.  Runs: the same nruns Philox orders from empty labels, one per init labelling, one from the
+    MPEL VI sample and one from the result of the same call with exact=False (info["lower_bound"] is that call's info), so the
+    result is never worse than either in the searched integer criterion info["loss_num"] (runs, and the choice of best, are
+    exact in it).  info["loss"] is the expected VI as the library returns it, (Q + constant)/(2^32·n·m): within
+    2·2^-32 ≈ 4.7e-10 of expectedvi's f64 value, so allow that much when comparing it with expectedvi of another labelling.
+    Besides the search the call costs the exact=False search and the MPEL loss matrix.  maxK = 0 caps the clusters at the largest cluster count among the samples (or a start's, if larger)."""
     if loss not in _PSM_LOSSES:
         raise ValueError("Invalid loss function specifier.")
+    if exact:
+        if loss != "VI":
+            raise ValueError('exact=True needs loss="VI"')
+        if ctx is not None:
+            raise ValueError("exact=True needs the samples; a Context keeps only their counts")
+        if not hasattr(samples_or_counts, "clusts"):
+            raise ValueError("exact=True needs the samples (an MCMCResult), not a count matrix")
+        return _vi_search_exact(samples_or_counts, nruns, maxK, maxsweeps, seed, init, device)
     samples = None
     if ctx is not None:
         if numsamples is None:

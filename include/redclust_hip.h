@@ -486,6 +486,24 @@ int32_t rc_psm_search_ctx(rc_ctx *ctx, int64_t numsamples, int32_t loss, int32_t
                           const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out,
                           rc_psm_run_t *runs_out, int32_t *best, double *kernel_ms);
 
+/* Counts from samples that are already there (a stored result, several merged chains, another sampler's draws), built on
+ * the device: counts[i][j] = #{s : samples[s][i] == samples[s][j]} — exact, symmetric, diagonal m; what rc_record_sample
+ * accumulates for a live chain.  samples: host m×n int64 row-major, labels 1..n.  One kernel computes every count once from
+ * zero in registers and stores it once (DESIGN.md §8 "Counts from samples"); kernel_ms (may be NULL) is its device time.
+ * rc_samples_counts copies the result into the caller's dense n×n buffer.  Capacity: n <= 32767 (labels are narrowed to 16
+ * bits beside two pad values) and m < 2^31, RC_ERR_CAPACITY beyond.  RC_ERR_ARG: a NULL pointer, m < 1, n < 1, a device that
+ * is not there, a label outside 1..n (the message names the sample and the position). */
+int32_t rc_samples_counts(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n,
+                          void *counts_out /* uint32_t n×n */, double *kernel_ms);
+/* rc_psm_search on those counts without a host copy of them: they are built in device memory as rc_psm_search stages its
+ * copy and searched there; equal to rc_psm_search on rc_samples_counts' matrix, bit for bit.  Arguments, errors and capacity
+ * (n <= 8192, m·n < 2^31, checked before any device work) as rc_psm_search; counts_ms (may be NULL): device time of the
+ * counts kernel, kernel_ms: of the search kernel. */
+int32_t rc_psm_search_samples(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n, int32_t loss,
+                              int32_t nruns, const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */,
+                              int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */, void *runs_out /* rc_psm_run_t[nruns] */,
+                              int32_t *best, double *kernel_ms, double *counts_ms);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Exact expected-VI search: the same greedy search (one run = starting labels, a point order, maxsweeps; the same scoring
  * of every non-empty cluster and a new one, the same tie rules) for the posterior expected Variation of Information itself

@@ -301,7 +301,8 @@ end
     searchpointestimate(HIPBackend(), result; loss = "VI", nruns = 16, maxK = 0, maxsweeps = 100, seed = 0) -> (clust, info)
 
 A greedy search over all partitions for the clustering of minimum expected loss under `result`'s co-clustering counts
-(rc_psm_search: the SALSO-style search the reference's documentation sends its users to R for).  `nruns` runs from empty
+(rc_psm_search_samples: the SALSO-style search the reference's documentation sends its users to R for; the counts are built
+from `result.clusts` on the GPU and never reach the host).  `nruns` runs from empty
 labels in random point orders plus one run started at `getpointestimate_hip(result; loss)`, so the answer is never worse
 under the searched criterion than the best sample.  `loss`: "binder" or "VI" (Wade & Ghahramani's lower bound).
 `info`: named tuple of the per-run `loss`, `sweeps`, `converged`, `moves`, `K`, all `labels` (n × runs) and `best`.
@@ -320,6 +321,20 @@ struct RcPsmRun
     K::Int32; pad_::Int32
 end
 
+# column s = sample s: row-major m×n for the library
+function samplematrix(result)
+    m = length(result.clusts); n = length(result.clusts[1])
+    samples = Matrix{Int64}(undef, n, m)
+    for s in 1:m
+        samples[:, s] .= result.clusts[s]
+    end
+    return samples
+end
+
+psminfo(runs, labels, best) =
+    (loss = [x.loss for x in runs], sweeps = [Int(x.sweeps) for x in runs], converged = [x.converged != 0 for x in runs],
+     moves = [Int(x.moves) for x in runs], K = [Int(x.K) for x in runs], labels = labels, best = Int(best[1]) + 1)
+
 function searchpointestimate(b::HIPBackend, result; loss::String = "VI", nruns::Integer = 16, maxK::Integer = 0,
                              maxsweeps::Integer = 100, seed::Integer = 0, exact::Bool = false)
     code = Dict("binder" => 0, "VI" => 1)
@@ -328,11 +343,8 @@ function searchpointestimate(b::HIPBackend, result; loss::String = "VI", nruns::
         loss == "VI" || throw(ArgumentError("exact = true needs loss = \"VI\""))
         return searchexactvi(b, result, nruns, maxK, maxsweeps, seed)
     end
-    m = length(result.clusts); n = length(result.clusts[1])
-    counts = zeros(UInt32, n, n)                                  # Σ adjacencymatrix(clusts[s]) (src/utils.jl:59-63), exact
-    for c in result.clusts, j in 1:n, i in 1:n
-        counts[i, j] += UInt32(c[i] == c[j])
-    end
+    samples = samplematrix(result)                                # the counts are built from these on the device and stay there
+    n, m = size(samples)
     R = Int(nruns) + 1
     init = zeros(Int64, n, R)                                     # column r = run r: row-major R×n for the library
     order = Matrix{Int32}(undef, n, R)
@@ -346,22 +358,72 @@ function searchpointestimate(b::HIPBackend, result; loss::String = "VI", nruns::
     labels = Matrix{Int64}(undef, n, R)
     runs = Vector{RcPsmRun}(undef, R)
     best = Int32[0]
+    rc = ccall((:rc_psm_search_samples, LIB), Int32,
+               (Int32, Ptr{Int64}, Int64, Int64, Int32, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
+                Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}),
+               b.device, samples, m, n, code[loss], R, init, order, maxK, maxsweeps, labels, runs, best, C_NULL, C_NULL)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return (labels[:, best[1] + 1], psminfo(runs, labels, best))
+end
+
+"""
+    searchpointestimate(HIPBackend(), counts, numsamples; loss = "VI", nruns = 16, maxK = 0, maxsweeps = 100, seed = 0, init = nothing)
+
+The same search for callers that hold the co-clustering counts and not the samples (rc_psm_search): `counts` is the n × n
+`Matrix{UInt32}` with `numsamples` on its diagonal, e.g. from `posteriorcounts` or summed over several results.  Runs: `nruns`
+from empty labels in random point orders and one per column of `init` (an n × k matrix of labels, identity order).
+"""
+function searchpointestimate(b::HIPBackend, counts::Matrix{UInt32}, numsamples::Integer; loss::String = "VI",
+                             nruns::Integer = 16, maxK::Integer = 0, maxsweeps::Integer = 100, seed::Integer = 0,
+                             init::Union{Matrix{Int64},Nothing} = nothing)
+    code = Dict("binder" => 0, "VI" => 1)
+    haskey(code, loss) || throw(ArgumentError("Invalid loss function specifier."))
+    n = size(counts, 1)
+    size(counts, 2) == n || throw(ArgumentError("counts must be a square matrix"))
+    extra = init === nothing ? 0 : size(init, 2)
+    R = Int(nruns) + extra
+    R >= 1 || throw(ArgumentError("no run: nruns = 0 and no init"))
+    inits = zeros(Int64, n, R)                                    # column r = run r: row-major R×n for the library
+    order = Matrix{Int32}(undef, n, R)
+    rng = Random.MersenneTwister(seed)
+    for r in 1:nruns
+        order[:, r] .= Random.randperm(rng, n)
+    end
+    for k in 1:extra
+        inits[:, nruns + k] .= view(init, :, k)
+        order[:, nruns + k] .= 1:n
+    end
+    labels = Matrix{Int64}(undef, n, R)
+    runs = Vector{RcPsmRun}(undef, R)
+    best = Int32[0]
     rc = ccall((:rc_psm_search, LIB), Int32,
                (Int32, Ptr{Cvoid}, Int64, Int64, Int32, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
                 Ptr{Int32}, Ptr{Cdouble}),
-               b.device, counts, m, n, code[loss], R, init, order, maxK, maxsweeps, labels, runs, best, C_NULL)
+               b.device, counts, numsamples, n, code[loss], R, inits, order, maxK, maxsweeps, labels, runs, best, C_NULL)
     check(Ptr{Cvoid}(C_NULL), rc)
-    info = (loss = [x.loss for x in runs], sweeps = [Int(x.sweeps) for x in runs], converged = [x.converged != 0 for x in runs],
-            moves = [Int(x.moves) for x in runs], K = [Int(x.K) for x in runs], labels = labels, best = Int(best[1]) + 1)
-    return (labels[:, best[1] + 1], info)
+    return (labels[:, best[1] + 1], psminfo(runs, labels, best))
+end
+
+"""
+    posteriorcounts(HIPBackend(), result) -> Matrix{UInt32}
+
+The exact co-clustering counts of `result.clusts` — entry (i, j) is the number of samples in which i and j share a cluster,
+`result.posterior_coclustering` times the number of samples — built on the GPU (rc_samples_counts).
+"""
+function posteriorcounts(b::HIPBackend, result)
+    samples = samplematrix(result)
+    n, m = size(samples)
+    counts = Matrix{UInt32}(undef, n, n)                          # symmetric: row- and column-major agree
+    rc = ccall((:rc_samples_counts, LIB), Int32,
+               (Int32, Ptr{Int64}, Int64, Int64, Ptr{Cvoid}, Ptr{Cdouble}),
+               b.device, samples, m, n, counts, C_NULL)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return counts
 end
 
 function searchexactvi(b::HIPBackend, result, nruns::Integer, maxK::Integer, maxsweeps::Integer, seed::Integer)
-    m = length(result.clusts); n = length(result.clusts[1])
-    samples = Matrix{Int64}(undef, n, m)                          # column s = sample s: row-major m×n for the library
-    for s in 1:m
-        samples[:, s] .= result.clusts[s]
-    end
+    samples = samplematrix(result)
+    n, m = size(samples)
     lower, _ = searchpointestimate(b, result; loss = "VI", nruns = nruns, maxK = maxK, maxsweeps = maxsweeps, seed = seed)
     R = Int(nruns) + 2
     init = zeros(Int64, n, R)                                     # column r = run r: row-major R×n for the library
@@ -393,6 +455,6 @@ function searchexactvi(b::HIPBackend, result, nruns::Integer, maxK::Integer, max
     return (labels[:, best[1] + 1], info)
 end
 
-export searchpointestimate
+export searchpointestimate, posteriorcounts
 
 end # module

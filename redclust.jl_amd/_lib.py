@@ -86,7 +86,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
             os.path.join(CSRC, "kmedoids.inc.hip"),
             os.path.join(CSRC, "chain.inc.hip"), os.path.join(CSRC, "chains.inc.hip"), os.path.join(CSRC, "samplek.inc.hip"),
             os.path.join(CSRC, "mixture.inc.hip"), os.path.join(CSRC, "kmeans.inc.hip"),
-            os.path.join(CSRC, "pointsearch.inc.hip"), os.path.join(CSRC, "visearch.inc.hip"), HEADER]
+            os.path.join(CSRC, "pointsearch.inc.hip"), os.path.join(CSRC, "visearch.inc.hip"),
+            os.path.join(CSRC, "samplecounts.inc.hip"), HEADER]
     if not force and os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(s) for s in srcs):
         return SO
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-o", SO, srcs[0]]
@@ -189,6 +190,10 @@ SIGNATURES = {
     "rc_vi_gtable": (C.c_int32, [C.c_int64, C.c_void_p]),
     "rc_vi_search": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_samples_counts": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_double)]),
+    "rc_psm_search_samples": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_double)]),
     "rc_layout_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rc_event_overhead_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "rc_kernel_timing": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -708,6 +713,49 @@ def psm_search(counts, numsamples: int, loss: int, init, order, maxK: int = 0, m
         if rc != RC_OK:
             raise _error(rc, L.rc_last_error(None).decode())
     out = dict(labels=labels[:nruns, :n], best=int(best.value), kernel_ms=float(ms.value))
+    for k, ty in RcPsmRun._fields_:
+        out[k] = np.array([getattr(r, k) for r in runs[:nruns]], dtype=np.float64 if ty is C.c_double else np.int64)
+    out["converged"] = out["converged"].astype(bool)
+    return out
+
+
+def samples_counts(samples, device: int = 0):
+    """rc_samples_counts: (n×n uint32 co-clustering counts, kernel ms) of an m×n int64 label matrix (labels 1..n), built on
+    the device: counts[i, j] = number of samples in which i and j share a label."""
+    L = lib()
+    S = np.ascontiguousarray(samples, dtype=np.int64)
+    if S.ndim != 2:
+        raise ValueError("samples must be an m×n matrix of labels")
+    m, n = S.shape
+    out = np.empty((max(n, 1), max(n, 1)), np.uint32)
+    ms = C.c_double()
+    rc = L.rc_samples_counts(int(device), S.ctypes.data, m, n, out.ctypes.data, C.byref(ms))
+    if rc != RC_OK:
+        raise _error(rc, L.rc_last_error(None).decode())
+    return out, float(ms.value)
+
+
+def psm_search_samples(samples, loss: int, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
+    """rc_psm_search_samples: psm_search on the counts of an m×n int64 label matrix (labels 1..n), which are built on the
+    device and stay there.  Returns psm_search's dict and counts_ms, the device time of the counts kernel."""
+    L = lib()
+    S = np.ascontiguousarray(samples, dtype=np.int64)
+    init = np.ascontiguousarray(init, dtype=np.int64)
+    order = np.ascontiguousarray(order, dtype=np.int32)
+    if S.ndim != 2:
+        raise ValueError("samples must be an m×n matrix of labels")
+    if init.ndim != 2 or init.shape != order.shape or init.shape[1] != S.shape[1]:
+        raise ValueError("init and order must be nruns×n arrays of the same shape, n the samples' length")
+    m, n = S.shape
+    nruns = init.shape[0]
+    labels = np.zeros((max(nruns, 1), max(n, 1)), np.int64)
+    runs = (RcPsmRun * max(nruns, 1))()
+    best, ms, cms = C.c_int32(-1), C.c_double(), C.c_double()
+    rc = L.rc_psm_search_samples(int(device), S.ctypes.data, m, n, int(loss), nruns, init.ctypes.data, order.ctypes.data, int(maxK),
+                                 int(maxsweeps), labels.ctypes.data, runs, C.byref(best), C.byref(ms), C.byref(cms))
+    if rc != RC_OK:
+        raise _error(rc, L.rc_last_error(None).decode())
+    out = dict(labels=labels[:nruns, :n], best=int(best.value), kernel_ms=float(ms.value), counts_ms=float(cms.value))
     for k, ty in RcPsmRun._fields_:
         out[k] = np.array([getattr(r, k) for r in runs[:nruns]], dtype=np.float64 if ty is C.c_double else np.int64)
     out["converged"] = out["converged"].astype(bool)

@@ -1,0 +1,224 @@
+// Co-clustering counts from samples on the device: counts[i][j] = #{s : samples[s][i] == samples[s][j]} for an m×n label
+// matrix that is already there — a stored MCMCResult, several merged chains, another sampler's draws — and the point-estimate
+// search on those counts without the matrix ever reaching the host.  A live chain builds the same counts as it goes
+// (k_snapshot / k_cocluster_batch, 32 samples per read-modify-write pass over the matrix); here all m samples are present, so
+// every count is computed once from zero in registers and stored once.  DESIGN.md §8 "Counts from samples".
+// Included at the end of redclust_hip.hip (same translation unit: shares fail(), PECHK, psm::run, psm::check_args, psm::DevBufs).
+//
+// Geometry.  The matrix is cut into TI × TJ = 128 × 128 tiles; a 256-thread workgroup computes one tile on or above the
+// diagonal and stores it to both triangles.  A thread owns 8 × 8 counts (64 u32 registers): rows h·64 + ty·4 + 0..3 and columns
+// g·64 + tx·4 + 0..3 (h, g = 0, 1).  A wave is an 8 (ty) × 8 (tx) patch of threads, so a store instruction of the tile as
+// computed writes, for each of 8 rows, 8 lanes × 16 B = one whole 128-byte line, and so does a store instruction of the
+// mirrored tile (there the 8 lanes of a line differ in ty): neither triangle is a strided scatter and nothing is transposed
+// through LDS.
+// Labels are u16, sample-major with leading dimension ldn (n rounded up to a multiple of TJ), padded with 0xFFFE.  Per
+// sample a thread reads its 8 column labels from that array (two 8-byte loads, 64 contiguous bytes per row of the patch) and its
+// 8 row labels from LDS, where the tile's row labels are staged SC = 32 samples at a time (8 KiB) with rows beyond n set to
+// 0xFFFF: a pad never equals a label (<= 32767) and a row pad never equals a column pad, so pad entries count zero — which is
+// what the columns n..ld-1 of the matrix must hold for the search.
+
+namespace sc {
+
+constexpr int TI = 128, TJ = 128;     // tile
+constexpr int SC = 32;                // samples per staged chunk of row labels
+constexpr int TPB = 256;
+constexpr int64_t NMAX = 32767;       // the chain's limit: u16 values above it are free for the two pads
+constexpr unsigned PAD_COL = 0xFFFEu;
+
+// a staged row pad is the column pad with its lowest bit set (0xFFFF), in both halves of a packed pair
+__device__ inline unsigned row_pads(unsigned x)
+{
+    return x | ((x & 0xFFFFu) == PAD_COL ? 1u : 0u) | ((x >> 16) == PAD_COL ? 0x10000u : 0u);
+}
+
+// One row of the thread's 8 × 8 patch for one sample: acc[R][c] += (row label == column label c).  The labels stay packed two
+// per register and are compared as 16-bit halves (SDWA); a comparison's mask goes to its own SGPR pair and is added as a carry.
+// gfx950 needs two wait states between a vector instruction that writes an SGPR and one that reads it: eight comparisons,
+// then the eight additions, keeps seven instructions between each pair, where the compiler left alone alternates them and
+// pads every pair with s_nop.
+#define SC_ROW(R, ROWREG, SEL)                                                                                          \
+    asm("v_cmp_eq_u32_sdwa %[m0], %[r], %[ca] src0_sel:" SEL " src1_sel:WORD_0\n\t"                                    \
+        "v_cmp_eq_u32_sdwa %[m1], %[r], %[ca] src0_sel:" SEL " src1_sel:WORD_1\n\t"                                    \
+        "v_cmp_eq_u32_sdwa %[m2], %[r], %[cb] src0_sel:" SEL " src1_sel:WORD_0\n\t"                                    \
+        "v_cmp_eq_u32_sdwa %[m3], %[r], %[cb] src0_sel:" SEL " src1_sel:WORD_1\n\t"                                    \
+        "v_cmp_eq_u32_sdwa %[m4], %[r], %[cc] src0_sel:" SEL " src1_sel:WORD_0\n\t"                                    \
+        "v_cmp_eq_u32_sdwa %[m5], %[r], %[cc] src0_sel:" SEL " src1_sel:WORD_1\n\t"                                    \
+        "v_cmp_eq_u32_sdwa %[m6], %[r], %[cd] src0_sel:" SEL " src1_sel:WORD_0\n\t"                                    \
+        "v_cmp_eq_u32_sdwa %[m7], %[r], %[cd] src0_sel:" SEL " src1_sel:WORD_1\n\t"                                    \
+        "v_addc_co_u32_e64 %[a0], %[m0], 0, %[a0], %[m0]\n\t"                                                          \
+        "v_addc_co_u32_e64 %[a1], %[m1], 0, %[a1], %[m1]\n\t"                                                          \
+        "v_addc_co_u32_e64 %[a2], %[m2], 0, %[a2], %[m2]\n\t"                                                          \
+        "v_addc_co_u32_e64 %[a3], %[m3], 0, %[a3], %[m3]\n\t"                                                          \
+        "v_addc_co_u32_e64 %[a4], %[m4], 0, %[a4], %[m4]\n\t"                                                          \
+        "v_addc_co_u32_e64 %[a5], %[m5], 0, %[a5], %[m5]\n\t"                                                          \
+        "v_addc_co_u32_e64 %[a6], %[m6], 0, %[a6], %[m6]\n\t"                                                          \
+        "v_addc_co_u32_e64 %[a7], %[m7], 0, %[a7], %[m7]"                                                                \
+        : [a0] "+v"(acc[R][0]), [a1] "+v"(acc[R][1]), [a2] "+v"(acc[R][2]), [a3] "+v"(acc[R][3]), [a4] "+v"(acc[R][4]),   \
+          [a5] "+v"(acc[R][5]), [a6] "+v"(acc[R][6]), [a7] "+v"(acc[R][7]), [m0] "=&s"(msk[0]), [m1] "=&s"(msk[1]),       \
+          [m2] "=&s"(msk[2]), [m3] "=&s"(msk[3]), [m4] "=&s"(msk[4]), [m5] "=&s"(msk[5]), [m6] "=&s"(msk[6]),             \
+          [m7] "=&s"(msk[7])                                                                                            \
+        : [r] "v"(ROWREG), [ca] "v"(c0.x), [cb] "v"(c0.y), [cc] "v"(c1.x), [cd] "v"(c1.y))
+
+__global__ __launch_bounds__(TPB) void k_sample_counts(const unsigned short *__restrict__ S, int m, int n, size_t ldn,
+                                                      unsigned *__restrict__ C, size_t ld)
+{
+    const int bi = blockIdx.y, bj = blockIdx.x;
+    if (bj < bi) return;                                   // tiles below the diagonal are written by their mirror images
+    __shared__ __align__(16) unsigned short rows[SC][TI];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int ty = (wave >> 1) * 8 + (lane >> 3), tx = (wave & 1) * 8 + (lane & 7);
+    const int i0 = bi * TI, j0 = bj * TJ;
+
+    unsigned acc[8][8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) acc[r][c] = 0u;
+
+    const unsigned short *__restrict__ colp = S + j0 + tx * 4;
+    uint2 n0 = *reinterpret_cast<const uint2 *>(colp), n1 = *reinterpret_cast<const uint2 *>(colp + 64);   // sample 0
+    unsigned long long msk[8];
+    for (int s0 = 0; s0 < m; s0 += SC) {
+        const int cnt = min(SC, m - s0);
+        __syncthreads();                                   // the previous chunk has been read
+        // 16 threads per sample, 8 row labels (16 bytes) each; ldn covers the whole tile, so every read is in bounds
+        for (int q = tid; q < cnt * (TI / 8); q += TPB) {
+            const int t = q >> 4, r = (q & 15) * 8;
+            uint4 v = *reinterpret_cast<const uint4 *>(S + (size_t)(s0 + t) * ldn + i0 + r);
+            v.x = row_pads(v.x); v.y = row_pads(v.y); v.z = row_pads(v.z); v.w = row_pads(v.w);
+            *reinterpret_cast<uint4 *>(&rows[t][r]) = v;
+        }
+        __syncthreads();
+        for (int t = 0; t < cnt; ++t) {
+            const uint2 c0 = n0, c1 = n1;
+            {   // the next sample's column labels (the last sample again at the very end: always in bounds)
+                const unsigned short *cp = colp + (size_t)min(s0 + t + 1, m - 1) * ldn;
+                n0 = *reinterpret_cast<const uint2 *>(cp); n1 = *reinterpret_cast<const uint2 *>(cp + 64);
+            }
+            __builtin_amdgcn_sched_barrier(0);             // keep those loads in front of the sample's 128 instructions
+            const uint2 r0 = *reinterpret_cast<const uint2 *>(&rows[t][ty * 4]), r1 = *reinterpret_cast<const uint2 *>(&rows[t][64 + ty * 4]);
+            SC_ROW(0, r0.x, "WORD_0"); SC_ROW(1, r0.x, "WORD_1"); SC_ROW(2, r0.y, "WORD_0"); SC_ROW(3, r0.y, "WORD_1");
+            SC_ROW(4, r1.x, "WORD_0"); SC_ROW(5, r1.x, "WORD_1"); SC_ROW(6, r1.y, "WORD_0"); SC_ROW(7, r1.y, "WORD_1");
+        }
+    }
+#undef SC_ROW
+
+    // the tile as computed: rows below n, 16-byte column groups below ld (ld is a multiple of 4; pad columns hold zero)
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const int row = i0 + (r >> 2) * 64 + ty * 4 + (r & 3);
+        if (row >= n) continue;
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            const size_t col = (size_t)j0 + g * 64 + tx * 4;
+            if (col < ld) *reinterpret_cast<uint4 *>(C + (size_t)row * ld + col) = make_uint4(acc[r][g * 4], acc[r][g * 4 + 1], acc[r][g * 4 + 2], acc[r][g * 4 + 3]);
+        }
+    }
+    if (bj == bi) return;
+    // its mirror image: row = the thread's column, 16-byte groups along the thread's rows
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const int row = j0 + (c >> 2) * 64 + tx * 4 + (c & 3);
+        if (row >= n) continue;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const size_t col = (size_t)i0 + h * 64 + ty * 4;
+            if (col < ld) *reinterpret_cast<uint4 *>(C + (size_t)row * ld + col) = make_uint4(acc[h * 4][c], acc[h * 4 + 1][c], acc[h * 4 + 2][c], acc[h * 4 + 3][c]);
+        }
+    }
+}
+
+// Labels 1..n narrowed to u16, sample-major with leading dimension ldn, pads 0xFFFE.  Host only.
+static int32_t narrow(const char *who, const int64_t *samples, int64_t m, int64_t n, size_t ldn, std::vector<unsigned short> &out)
+{
+    try { out.assign((size_t)m * ldn, (unsigned short)PAD_COL); }
+    catch (const std::bad_alloc &) { return fail(nullptr, RC_ERR_OOM, "%s: no host memory for the %lld x %zu 16-bit labels", who, (long long)m, ldn); }
+    for (int64_t s = 0; s < m; ++s) {
+        const int64_t *src = samples + (size_t)s * n;
+        unsigned short *dst = out.data() + (size_t)s * ldn;
+        for (int64_t j = 0; j < n; ++j) {
+            const int64_t l = src[j];
+            if (l < 1 || l > n)
+                return fail(nullptr, RC_ERR_ARG, "%s: label %lld of sample %lld at position %lld outside 1..n", who, (long long)l, (long long)s + 1, (long long)j + 1);
+            dst[j] = (unsigned short)l;
+        }
+    }
+    return RC_OK;
+}
+
+// The counts of the samples in device memory: n × ld uint32 in B.p[0] (every entry written, pad columns zero); B.p[1] holds
+// the labels.  The device is selected; work goes to the null stream.  ms (may be NULL): device time of the kernel.
+static int32_t build(const char *who, const int64_t *samples, int64_t m, int64_t n, int64_t ld, psm::DevBufs &B, double *ms)
+{
+    const size_t ldn = (size_t)(n + TJ - 1) / TJ * TJ;
+    std::vector<unsigned short> h_S;
+    int32_t rc = narrow(who, samples, m, n, ldn, h_S);
+    if (rc != RC_OK) return rc;
+    PECHK(hipMalloc(&B.p[0], (size_t)n * (size_t)ld * sizeof(unsigned)));
+    PECHK(hipMalloc(&B.p[1], h_S.size() * 2));
+    PECHK(hipMemcpy(B.p[1], h_S.data(), h_S.size() * 2, hipMemcpyHostToDevice));
+    const unsigned nt = (unsigned)(ldn / TJ);
+    hipEvent_t e0, e1;
+    PECHK(hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail(nullptr, RC_ERR_HIP, "%s: hipEventCreate failed", who); }
+    hipError_t le = hipEventRecord(e0, 0);
+    if (le == hipSuccess) {
+        k_sample_counts<<<dim3(nt, nt), TPB, 0, 0>>>((const unsigned short *)B.p[1], (int)m, (int)n, ldn, (unsigned *)B.p[0], (size_t)ld);
+        le = hipGetLastError();
+    }
+    if (le == hipSuccess) le = hipEventRecord(e1, 0);
+    if (le == hipSuccess) le = hipEventSynchronize(e1);
+    float t = 0;
+    if (le == hipSuccess) le = hipEventElapsedTime(&t, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if (le != hipSuccess) return fail(nullptr, RC_ERR_HIP, "%s: the counts kernel failed: %s", who, hipGetErrorString(le));
+    if (ms) *ms = t;
+    return RC_OK;
+}
+
+static int32_t select_device(const char *who, int32_t device)
+{
+    int ndev = 0;
+    PECHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(nullptr, RC_ERR_ARG, "%s: device %d not available (%d visible)", who, device, ndev);
+    PECHK(hipSetDevice(device));
+    return RC_OK;
+}
+
+}  // namespace sc
+
+extern "C" int32_t rc_samples_counts(int32_t device, const int64_t *samples, int64_t m, int64_t n, void *counts_out, double *kernel_ms)
+{
+    const char *who = "rc_samples_counts";
+    if (!samples || !counts_out) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
+    if (m < 1 || n < 1) return fail(nullptr, RC_ERR_ARG, "%s: need m >= 1 and n >= 1 (got m=%lld n=%lld)", who, (long long)m, (long long)n);
+    if (n > sc::NMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %lld points whose labels fit 16 bits beside the pads", who, (long long)n, (long long)sc::NMAX);
+    if (m > 0x7FFFFFFFll) return fail(nullptr, RC_ERR_CAPACITY, "%s: m = %lld exceeds the 2^31 - 1 samples a 32-bit count holds", who, (long long)m);
+    int32_t rc = sc::select_device(who, device);
+    if (rc != RC_OK) return rc;
+    const int64_t ld = (n + 3) / 4 * 4;
+    psm::DevBufs B;
+    rc = sc::build(who, samples, m, n, ld, B, kernel_ms);
+    if (rc != RC_OK) return rc;
+    PECHK(hipMemcpy2D(counts_out, (size_t)n * sizeof(unsigned), B.p[0], (size_t)ld * sizeof(unsigned), (size_t)n * sizeof(unsigned), (size_t)n,
+                      hipMemcpyDeviceToHost));
+    return RC_OK;
+}
+
+extern "C" int32_t rc_psm_search_samples(int32_t device, const int64_t *samples, int64_t m, int64_t n, int32_t loss, int32_t nruns,
+                                         const int64_t *init, const int32_t *order, int32_t maxK, int32_t maxsweeps,
+                                         int64_t *labels_out, void *runs_out, int32_t *best, double *kernel_ms, double *counts_ms)
+{
+    const char *who = "rc_psm_search_samples";
+    if (!samples) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
+    int32_t rc = psm::check_args(nullptr, who, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best);
+    if (rc != RC_OK) return rc;
+    rc = sc::select_device(who, device);
+    if (rc != RC_OK) return rc;
+    const int64_t ld = (n + 3) / 4 * 4;
+    psm::DevBufs B;                                        // the counts stay on the device
+    rc = sc::build(who, samples, m, n, ld, B, counts_ms);
+    if (rc != RC_OK) return rc;
+    return psm::run(nullptr, nullptr, (const unsigned *)B.p[0], ld, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out,
+                    (rc_psm_run_t *)runs_out, best, kernel_ms);
+}

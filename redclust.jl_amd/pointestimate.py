@@ -73,6 +73,29 @@ def cocluster_counts(clusts) -> np.ndarray:
     return counts
 
 
+def _sample_matrix(samples) -> np.ndarray:
+    """The m×n int64 label matrix of an MCMCResult, anything with `.clusts`, or an m×n label matrix (every sample through
+    _labels)."""
+    clusts = samples.clusts if hasattr(samples, "clusts") else samples
+    if len(clusts) == 0:
+        raise ValueError("no samples")
+    return np.stack([_labels(c) for c in clusts])
+
+
+def posterior_counts(samples, device: int = 0) -> np.ndarray:
+    """cocluster_counts built on the GPU (csrc/samplecounts.inc.hip): the exact n×n uint32 matrix whose entry (i, j) is the
+    number of samples in which i and j share a cluster.  samples: an MCMCResult, anything with `.clusts`, or an m×n label
+    matrix — a stored result, several chains' samples stacked, another sampler's draws.  There is no CPU fallback."""
+    return _lib.samples_counts(_sample_matrix(samples), device=device)[0]
+
+
+def posterior_coclustering(samples, device: int = 0) -> np.ndarray:
+    """The posterior co-clustering matrix of the samples, posterior_counts / m in f64 (./ numsamples, mcmc.jl:560) — equal
+    bit for bit to the `posterior_coclustering` runsampler returns for the same samples."""
+    S = _sample_matrix(samples)
+    return _lib.samples_counts(S, device=device)[0].astype(np.float64) / float(S.shape[0])
+
+
 def expectedloss(clust, counts, numsamples: int, loss="VI") -> float:
     """The criterion searchpointestimate minimises, evaluated on the host in NumPy for any labelling `clust`, from the n×n
     co-clustering counts C (C_ii = numsamples = m):
@@ -156,7 +179,8 @@ def searchpointestimate(samples_or_counts=None, loss="VI", *, nruns: int = 16, m
     reference's docs send its users to R's SALSO for this; getpointestimate(method="MPEL") only looks at the sampled
     clusterings).  Runs on the GPU (csrc/pointsearch.inc.hip), every run one workgroup; there is no CPU fallback.
 
-    samples_or_counts: an MCMCResult (its counts are rebuilt exactly from `clusts`), or an n×n uint32 count matrix together
+    samples_or_counts: an MCMCResult (its counts are rebuilt exactly from `clusts` on the device and stay there:
+    rc_psm_search_samples; info["counts_ms"] is that kernel's time), or an n×n uint32 count matrix together
     with numsamples; or pass a live Context as ctx= (with numsamples): its device counts are searched in place.
     loss: "binder" or "VI" — see expectedloss; "VI" is the lower bound, not the exact posterior expected VI.  When the
     samples are given, the partition-independent constant (1/n)·Σ_i mean_s log n^(s)_{c_i} that turns the bound's value into
@@ -175,7 +199,7 @@ def searchpointestimate(samples_or_counts=None, loss="VI", *, nruns: int = 16, m
     result is never worse than either in the searched integer criterion info["loss_num"] (runs, and the choice of best, are
     exact in it).  info["loss"] is the expected VI as the library returns it, (Q + constant)/(2^32·n·m): within
     2·2^-32 ≈ 4.7e-10 of expectedvi's f64 value, so allow that much when comparing it with expectedvi of another labelling.
-    Besides the search the call costs the exact=False search and the MPEL loss matrix.  maxK = 0 caps the clusters at the largest cluster count among the samples (or a start's, if larger)."""
+    Besides the search the call costs the exact=False search (with its counts kernel) and the MPEL loss matrix.  maxK = 0 caps the clusters at the largest cluster count among the samples (or a start's, if larger)."""
     if loss not in _PSM_LOSSES:
         raise ValueError("Invalid loss function specifier.")
     if exact:
@@ -193,8 +217,8 @@ def searchpointestimate(samples_or_counts=None, loss="VI", *, nruns: int = 16, m
         counts, n = None, ctx.n
     elif hasattr(samples_or_counts, "clusts"):
         samples = samples_or_counts
-        counts = cocluster_counts(samples.clusts)
-        numsamples, n = len(samples.clusts), counts.shape[0]
+        S = np.stack([_labels(c) for c in samples.clusts])             # the counts are built from these on the device
+        counts, (numsamples, n) = None, S.shape
     else:
         if samples_or_counts is None:
             raise ValueError("need an MCMCResult, a count matrix or ctx=")
@@ -222,11 +246,16 @@ def searchpointestimate(samples_or_counts=None, loss="VI", *, nruns: int = 16, m
         orders.append(ident)
     if not inits:
         raise ValueError("no run: nruns = 0 and no init")
-    res = _lib.psm_search(counts, int(numsamples), _PSM_LOSSES[loss], np.stack(inits), np.stack(orders), maxK=maxK,
-                          maxsweeps=maxsweeps, device=device, ctx=ctx)
+    if samples is not None:
+        res = _lib.psm_search_samples(S, _PSM_LOSSES[loss], np.stack(inits), np.stack(orders), maxK=maxK, maxsweeps=maxsweeps,
+                                      device=device)
+    else:
+        res = _lib.psm_search(counts, int(numsamples), _PSM_LOSSES[loss], np.stack(inits), np.stack(orders), maxK=maxK,
+                              maxsweeps=maxsweeps, device=device, ctx=ctx)
     info = {k: res[k] for k in ("loss", "sweeps", "converged", "moves", "K", "labels", "best", "kernel_ms", "loss_num")}
+    if samples is not None:
+        info["counts_ms"] = res["counts_ms"]
     if samples is not None and loss == "VI":
-        S = np.stack([_labels(c) for c in samples.clusts])
         sizes = np.stack([np.bincount(s, minlength=n + 1)[s] for s in S])
         info["vi_constant"] = float(np.mean(np.log(sizes)))
     return res["labels"][res["best"]].copy(), info

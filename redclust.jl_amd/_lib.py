@@ -82,8 +82,8 @@ class RcSweepStats(C.Structure):
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, "redclust_hip.hip"), os.path.join(CSRC, "pointestimate.inc.hip"),
-            os.path.join(CSRC, "kmedoids.inc.hip"),
+    srcs = [os.path.join(CSRC, "redclust_hip.hip"), os.path.join(CSRC, "hostutil.inc.hip"),
+            os.path.join(CSRC, "pointestimate.inc.hip"), os.path.join(CSRC, "cluster.inc.hip"), os.path.join(CSRC, "kmedoids.inc.hip"),
             os.path.join(CSRC, "chain.inc.hip"), os.path.join(CSRC, "chains.inc.hip"), os.path.join(CSRC, "samplek.inc.hip"),
             os.path.join(CSRC, "mixture.inc.hip"), os.path.join(CSRC, "kmeans.inc.hip"),
             os.path.join(CSRC, "pointsearch.inc.hip"), os.path.join(CSRC, "visearch.inc.hip"),
@@ -481,22 +481,26 @@ class Context:
                                      m if m.size else np.zeros(1, np.int64), C.byref(tc), C.byref(it), C.byref(cv)))
         return KmedoidsResult(medoids=m, assignments=a, totalcost=tc.value, iterations=int(it.value), converged=bool(cv.value))
 
-    def kmedoids_scan(self, kmin, kmax, maxiter=200, tol=1e-8, seed=0, split=False) -> dict:
-        """rc_kmedoids_scan: totalcost, iterations and converged of kmedoids(k) for k = kmin..kmax (arrays indexed by k - kmin).
-        split=True (rc_kmedoids_scan_split): also every k's within / between split of its final assignment, as within_between
-        would return it — count_within, sum_within, sumlog_within and the same three _between, one array each."""
+    def _scan(self, name, kmin, kmax, maxiter, tol, seed, split, *extra) -> dict:
+        """rc_<name>_scan(ctx, kmin, kmax, maxiter, tol, seed, *extra, outputs) or, with split, rc_<name>_scan_split."""
         m = max(int(kmax) - int(kmin) + 1, 1)
         tc, it, cv = np.zeros(m), np.zeros(m, np.int64), np.zeros(m, np.uint8)
-        args = (self.h, int(kmin), int(kmax), int(maxiter), float(tol), int(seed) & 0xFFFFFFFFFFFFFFFF, tc, it, cv)
+        args = (self.h, int(kmin), int(kmax), int(maxiter), float(tol), int(seed) & 0xFFFFFFFFFFFFFFFF, *extra, tc, it, cv)
         if not split:
-            self._chk(self.L.rc_kmedoids_scan(*args))
+            self._chk(getattr(self.L, f"rc_{name}_scan")(*args))
             return dict(totalcost=tc, iterations=it, converged=cv.astype(bool))
         wb = (RcWbStats * m)()
-        self._chk(self.L.rc_kmedoids_scan_split(*args, wb))
+        self._chk(getattr(self.L, f"rc_{name}_scan_split")(*args, wb))
         out = dict(totalcost=tc, iterations=it, converged=cv.astype(bool))
         for k, ty in RcWbStats._fields_:
             out[k] = np.array([getattr(x, k) for x in wb], dtype=np.int64 if ty is C.c_int64 else np.float64)
         return out
+
+    def kmedoids_scan(self, kmin, kmax, maxiter=200, tol=1e-8, seed=0, split=False) -> dict:
+        """rc_kmedoids_scan: totalcost, iterations and converged of kmedoids(k) for k = kmin..kmax (arrays indexed by k - kmin).
+        split=True (rc_kmedoids_scan_split): also every k's within / between split of its final assignment, as within_between
+        would return it — count_within, sum_within, sumlog_within and the same three _between, one array each."""
+        return self._scan("kmedoids", kmin, kmax, maxiter, tol, seed, split)
 
     def kmeans(self, k, maxiter=100, tol=1e-6, seed=0, init=None) -> KmeansResult:
         """rc_kmeans: Clustering.jl's kmeans(X, k; maxiter, tol) (k-means++ seeding, or init: k distinct 1-based point indices)
@@ -521,19 +525,7 @@ class Context:
         """rc_kmeans_scan: totalcost, iterations and converged of kmeans(k) for k = kmin..kmax (arrays indexed by k - kmin);
         split=True (rc_kmeans_scan_split): also every k's within / between split of the context's D under its final
         assignment, as kmedoids_scan returns it.  slots_per_chunk: runs per device pass (0 = automatic; same results)."""
-        m = max(int(kmax) - int(kmin) + 1, 1)
-        tc, it, cv = np.zeros(m), np.zeros(m, np.int64), np.zeros(m, np.uint8)
-        args = (self.h, int(kmin), int(kmax), int(maxiter), float(tol), int(seed) & 0xFFFFFFFFFFFFFFFF, int(slots_per_chunk),
-                tc, it, cv)
-        if not split:
-            self._chk(self.L.rc_kmeans_scan(*args))
-            return dict(totalcost=tc, iterations=it, converged=cv.astype(bool))
-        wb = (RcWbStats * m)()
-        self._chk(self.L.rc_kmeans_scan_split(*args, wb))
-        out = dict(totalcost=tc, iterations=it, converged=cv.astype(bool))
-        for k, ty in RcWbStats._fields_:
-            out[k] = np.array([getattr(x, k) for x in wb], dtype=np.int64 if ty is C.c_int64 else np.float64)
-        return out
+        return self._scan("kmeans", kmin, kmax, maxiter, tol, seed, split, int(slots_per_chunk))
 
     def layout_info(self):
         """(layouts built so far, label runs in the internal point order)"""

@@ -7,7 +7,7 @@
 // host-mapped memory), two scalar draws, launch sweep t+1 — while the row reduction of sweep t+1 has been running on
 // the other stream since sweep t was launched.
 //
-// Scalar stream: Philox4x32-10 keyed (seed_lo, seed_hi ^ 0x52505F5F), counter (draw, kind, iter_lo,
+// Scalar stream: Philox4x32-10 keyed (seed_lo, seed_hi ^ RC_RP_TAG), counter (draw, kind, iter_lo,
 // iter_hi); kind 0 = r update, 1 = p update.  Normal: Box–Muller; truncated Normal: redraw; Gamma: Marsaglia–Tsang;
 // Beta = Gamma ratio.  (The reference samples through Distributions.jl on Julia's global RNG — same distributions,
 // irreproducible stream.)
@@ -24,17 +24,10 @@ struct Stream {
     uint64_t draw;
     double uniform()
     {
-        uint32_t c[4] = {(uint32_t)draw, kind, (uint32_t)iter, (uint32_t)(iter >> 32)};
+        const Philox4 x = rc_philox((uint32_t)draw, kind, (uint32_t)iter, (uint32_t)(iter >> 32), (uint32_t)seed,
+                                    (uint32_t)(seed >> 32) ^ RC_RP_TAG);
         ++draw;
-        uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ 0x52505F5Fu;
-        for (int r = 0; r < 10; ++r) {
-            const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-            const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-            c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
-            k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-        }
-        const uint64_t bits = (((uint64_t)c[0] << 32) | c[1]) >> 12;
-        return ((double)bits + 0.5) * 0x1p-52;
+        return rc_unit52(x);
     }
     double normal()
     {

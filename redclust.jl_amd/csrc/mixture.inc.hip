@@ -1,5 +1,6 @@
 // generatemixture's oracle co-clustering matrix (src/utils.jl:130-143 of the reference) on the device.  Derivation, order
-// and exactness contract as in DESIGN.md §8.  Included at the end of redclust_hip.hip (same translation unit: shares fail()).
+// and exactness contract as in DESIGN.md §8.  Included at the end of redclust_hip.hip (same translation unit: shares fail(),
+// HIPCHK and the holders of hostutil.inc.hip).
 //
 // The centres are radius·e_j, so every factor of w_j·pdf(MvNormal(c_j, σ²I), x_i) but exp(radius·x_ij/σ²) is common to
 // all j and cancels in the normalisation: with b_ij = radius·x_ij/σ² (j < K only),
@@ -111,16 +112,6 @@ __global__ __launch_bounds__(256) void k_mix_finish(int npad, double T, double *
 
 }  // namespace mixture
 
-#define MXCHK(call)                                                                                   \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) {                                                                       \
-            free_all();                                                                               \
-            return fail(nullptr, (e_ == hipErrorOutOfMemory) ? RC_ERR_OOM : RC_ERR_HIP, "rc_oracle_coclustering: %s failed: %s (%s:%d)", \
-                        #call, hipGetErrorString(e_), __FILE__, __LINE__);                            \
-        }                                                                                             \
-    } while (0)
-
 extern "C" int32_t rc_oracle_coclustering(int32_t device, int64_t n, int64_t dim, const double *points, int64_t K, double radius,
                                           double sigma, int64_t numiters, const double *weights, int64_t iters_per_chunk,
                                           double *out, double *kernel_ms)
@@ -162,49 +153,38 @@ extern "C" int32_t rc_oracle_coclustering(int32_t device, int64_t n, int64_t dim
     std::vector<int> tiles;
     for (int bi = 0; bi < nb; ++bi)
         for (int bj = bi; bj < nb; ++bj) { tiles.push_back(bi); tiles.push_back(bj); }
-    double *d_B = nullptr, *d_lw = nullptr, *d_Q = nullptr, *d_S = nullptr;
-    int *d_tiles = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto free_all = [&]() {
-        for (void *q : {(void *)d_B, (void *)d_lw, (void *)d_Q, (void *)d_S, (void *)d_tiles})
-            if (q) (void)hipFree(q);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
-    int ndev = 0;
-    MXCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(nullptr, RC_ERR_ARG, "rc_oracle_coclustering: device %d not available (%d visible)", device, ndev);
-    MXCHK(hipSetDevice(device));
-    MXCHK(hipMalloc(&d_B, B.size() * 8));
-    MXCHK(hipMalloc(&d_lw, logw.size() * 8));
-    MXCHK(hipMalloc(&d_Q, (size_t)(ipc * per_iter)));
-    MXCHK(hipMalloc(&d_S, (size_t)npad * npad * 8));
-    MXCHK(hipMalloc(&d_tiles, tiles.size() * sizeof(int)));
-    MXCHK(hipMemcpy(d_B, B.data(), B.size() * 8, hipMemcpyHostToDevice));
-    MXCHK(hipMemcpy(d_lw, logw.data(), logw.size() * 8, hipMemcpyHostToDevice));
-    MXCHK(hipMemcpy(d_tiles, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice));
-    MXCHK(hipMemset(d_S, 0, (size_t)npad * npad * 8));
-    MXCHK(hipEventCreate(&e0));
-    MXCHK(hipEventCreate(&e1));
-    MXCHK(hipEventRecord(e0, 0));
+    int32_t rc = select_device("rc_oracle_coclustering", device);
+    if (rc != RC_OK) return rc;
+    DeviceBuffers bufs;
+    TimingEvents ev;
+    double *d_B, *d_lw, *d_Q, *d_S;
+    int *d_tiles;
+    HIPCHK(nullptr, bufs.alloc(d_B, B.size()));
+    HIPCHK(nullptr, bufs.alloc(d_lw, logw.size()));
+    HIPCHK(nullptr, bufs.alloc(d_Q, (size_t)(ipc * per_iter) / 8));
+    HIPCHK(nullptr, bufs.alloc(d_S, (size_t)npad * npad));
+    HIPCHK(nullptr, bufs.alloc(d_tiles, tiles.size()));
+    HIPCHK(nullptr, hipMemcpy(d_B, B.data(), B.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_lw, logw.data(), logw.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_tiles, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemset(d_S, 0, (size_t)npad * npad * 8));
+    HIPCHK(nullptr, ev.create());
+    HIPCHK(nullptr, hipEventRecord(ev.e0, 0));
     for (int64_t t0 = 0; t0 < numiters; t0 += ipc) {
         const int it = (int)std::min<int64_t>(ipc, numiters - t0);
         mixture::k_mix_q<<<dim3((unsigned)((npad + 255) / 256), (unsigned)std::min(it, 65535)), 256, 0, 0>>>(
             npad, (int)n, (int)K, K4, it, d_B, d_lw + (size_t)t0 * K, d_Q);
-        MXCHK(hipGetLastError());
+        HIPCHK(nullptr, hipGetLastError());
         mixture::k_mix_syrk<<<(unsigned)(tiles.size() / 2), 256, 0, 0>>>(npad, it * K4, d_tiles, d_Q, d_S);
-        MXCHK(hipGetLastError());
+        HIPCHK(nullptr, hipGetLastError());
     }
     mixture::k_mix_finish<<<dim3((unsigned)(npad / 32), (unsigned)(npad / 32)), 256, 0, 0>>>(npad, (double)numiters, d_S);
-    MXCHK(hipGetLastError());
-    MXCHK(hipEventRecord(e1, 0));
-    MXCHK(hipEventSynchronize(e1));
+    HIPCHK(nullptr, hipGetLastError());
+    HIPCHK(nullptr, hipEventRecord(ev.e1, 0));
+    HIPCHK(nullptr, hipEventSynchronize(ev.e1));
     float ms = 0;
-    MXCHK(hipEventElapsedTime(&ms, e0, e1));
-    MXCHK(hipMemcpy2D(out, (size_t)n * 8, d_S, (size_t)npad * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToHost));
-    free_all();
+    HIPCHK(nullptr, hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    HIPCHK(nullptr, hipMemcpy2D(out, (size_t)n * 8, d_S, (size_t)npad * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToHost));
     if (kernel_ms) *kernel_ms = ms;
     return RC_OK;
 }
-
-#undef MXCHK

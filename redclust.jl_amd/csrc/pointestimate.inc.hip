@@ -1,7 +1,8 @@
 // Point estimation on the device: the numsamples × numsamples matrix of pairwise clustering losses of
 // getpointestimate(method = "MPEL") (/root/reference/src/pointestimate.jl:49-58) and the pair measures behind
 // binderloss / infodist / evaluateclustering (pointestimate.jl:68-99, src/summaries.jl:12-23).
-// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, the error buffer).
+// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, the error buffer and
+// the holders of hostutil.inc.hip).
 //
 // Every loss the reference offers is a function of the contingency table n_ij of two labelings through just two
 // sums, Σ n_ij² and Σ n_ij log n_ij, plus per-sample marginals (Σ a_i², Σ a_i log a_i) that the host prepares
@@ -212,19 +213,6 @@ static int32_t prepare(const int64_t *samples, int64_t m, int64_t n, Prep &P)
     return RC_OK;
 }
 
-struct DevBufs {
-    void *p[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~DevBufs() { for (void *q : p) if (q) (void)hipFree(q); }
-};
-
-#define PECHK(call)                                                                                   \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess)                                                                         \
-            return fail(nullptr, (e_ == hipErrorOutOfMemory) ? RC_ERR_OOM : RC_ERR_HIP, "%s failed: %s (%s:%d)", #call, \
-                        hipGetErrorString(e_), __FILE__, __LINE__);                                   \
-    } while (0)
-
 // runs the pair kernel for each kind in `kinds`, copying the m×m result of kind t to outs[t] (host, may be null),
 // and the column sums of the LAST kind to colsum (may be null)
 static int32_t run(int32_t device, const int64_t *samples, int64_t m, int64_t n, const int *kinds, int nkinds,
@@ -232,27 +220,25 @@ static int32_t run(int32_t device, const int64_t *samples, int64_t m, int64_t n,
 {
     if (!samples || m < 1 || n < 2) return fail(nullptr, RC_ERR_ARG, "point estimate: need samples, m >= 1 and n >= 2 (got m=%lld n=%lld)", (long long)m, (long long)n);
     if (m > 46340) return fail(nullptr, RC_ERR_ARG, "point estimate: at most 46340 samples (m*m must fit 32 bits), got %lld", (long long)m);
-    int ndev = 0;
-    PECHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(nullptr, RC_ERR_ARG, "point estimate: device %d not available (%d visible)", device, ndev);
-    PECHK(hipSetDevice(device));
-    Prep P;
-    int32_t rc = prepare(samples, m, n, P);
+    int32_t rc = select_device("point estimate", device);
     if (rc != RC_OK) return rc;
-    DevBufs B;
+    Prep P;
+    rc = prepare(samples, m, n, P);
+    if (rc != RC_OK) return rc;
+    DeviceBuffers B;
     unsigned short *d_lab; int *d_K; double *d_nis, *d_ea, *d_x, *d_L, *d_cs; unsigned *d_gt = nullptr;
-    PECHK(hipMalloc(&B.p[0], P.lab.size() * 2)); d_lab = (unsigned short *)B.p[0];
-    PECHK(hipMalloc(&B.p[1], (size_t)m * 4)); d_K = (int *)B.p[1];
-    PECHK(hipMalloc(&B.p[2], (size_t)m * 8)); d_nis = (double *)B.p[2];
-    PECHK(hipMalloc(&B.p[3], (size_t)m * 8)); d_ea = (double *)B.p[3];
-    PECHK(hipMalloc(&B.p[4], P.xlogx.size() * 8)); d_x = (double *)B.p[4];
-    PECHK(hipMalloc(&B.p[5], (size_t)m * m * 8)); d_L = (double *)B.p[5];
-    PECHK(hipMalloc(&B.p[6], (size_t)m * 8)); d_cs = (double *)B.p[6];
-    PECHK(hipMemcpy(d_lab, P.lab.data(), P.lab.size() * 2, hipMemcpyHostToDevice));
-    PECHK(hipMemcpy(d_K, P.K.data(), (size_t)m * 4, hipMemcpyHostToDevice));
-    PECHK(hipMemcpy(d_nis, P.nis.data(), (size_t)m * 8, hipMemcpyHostToDevice));
-    PECHK(hipMemcpy(d_ea, P.ea.data(), (size_t)m * 8, hipMemcpyHostToDevice));
-    PECHK(hipMemcpy(d_x, P.xlogx.data(), P.xlogx.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, B.alloc(d_lab, P.lab.size()));
+    HIPCHK(nullptr, B.alloc(d_K, (size_t)m));
+    HIPCHK(nullptr, B.alloc(d_nis, (size_t)m));
+    HIPCHK(nullptr, B.alloc(d_ea, (size_t)m));
+    HIPCHK(nullptr, B.alloc(d_x, P.xlogx.size()));
+    HIPCHK(nullptr, B.alloc(d_L, (size_t)m * m));
+    HIPCHK(nullptr, B.alloc(d_cs, (size_t)m));
+    HIPCHK(nullptr, hipMemcpy(d_lab, P.lab.data(), P.lab.size() * 2, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_K, P.K.data(), (size_t)m * 4, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_nis, P.nis.data(), (size_t)m * 8, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_ea, P.ea.data(), (size_t)m * 8, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_x, P.xlogx.data(), P.xlogx.size() * 8, hipMemcpyHostToDevice));
 
     if (P.Kmax > 16384) return fail(nullptr, RC_ERR_CAPACITY, "point estimate: %d clusters in one sample (limit 16384)", P.Kmax);
     Args A{};
@@ -263,7 +249,7 @@ static int32_t run(int32_t device, const int64_t *samples, int64_t m, int64_t n,
     A.N = (double)n; A.logN = std::log((double)n); A.t1 = (double)n * ((double)n - 1) / 2;
     // launch shape: W waves per block, each with touched list + table in LDS when that fits
     hipDeviceProp_t prop;
-    PECHK(hipGetDeviceProperties(&prop, device));
+    HIPCHK(nullptr, hipGetDeviceProperties(&prop, device));
     const size_t lds_max = 160 * 1024 - 1024;
     const size_t per_wave = 4 * ((size_t)TOUCH_CAP + (size_t)A.tab_cells);
     int W = 4;
@@ -279,38 +265,37 @@ static int32_t run(int32_t device, const int64_t *samples, int64_t m, int64_t n,
         // keep the scratch under 8 GiB
         while (grid > 1 && (size_t)grid * W * A.tab_cells * 4 > ((size_t)8 << 30)) grid >>= 1;
         A.gtab_stride = (unsigned long long)A.tab_cells;
-        PECHK(hipMalloc(&B.p[7], (size_t)grid * W * A.tab_cells * 4)); d_gt = (unsigned *)B.p[7];
-        PECHK(hipMemset(d_gt, 0, (size_t)grid * W * A.tab_cells * 4));
+        HIPCHK(nullptr, B.alloc(d_gt, (size_t)grid * W * A.tab_cells));
+        HIPCHK(nullptr, hipMemset(d_gt, 0, (size_t)grid * W * A.tab_cells * 4));
         A.gtab = d_gt;
     } else {
         lds = W * per_wave;
         const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, lds_max / lds));
         grid = std::min(A.ntile * A.ntile, prop.multiProcessorCount * per_cu * 2);
-        PECHK(hipFuncSetAttribute((const void *)k_pair_losses<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(nullptr, hipFuncSetAttribute((const void *)k_pair_losses<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
     (void)ntiles_upper;
-    hipEvent_t e0, e1;
-    PECHK(hipEventCreate(&e0)); PECHK(hipEventCreate(&e1));
+    TimingEvents ev;
+    HIPCHK(nullptr, ev.create());
     double ms_total = 0;
     for (int t = 0; t < nkinds; ++t) {
         A.kind = kinds[t];
-        PECHK(hipMemset(d_L, 0, (size_t)m * m * 8));
-        PECHK(hipEventRecord(e0, 0));
+        HIPCHK(nullptr, hipMemset(d_L, 0, (size_t)m * m * 8));
+        HIPCHK(nullptr, hipEventRecord(ev.e0, 0));
         if (global_tab) k_pair_losses<true><<<grid, 64 * W, lds, 0>>>(A);
         else k_pair_losses<false><<<grid, 64 * W, lds, 0>>>(A);
-        PECHK(hipGetLastError());
-        PECHK(hipEventRecord(e1, 0));
-        PECHK(hipEventSynchronize(e1));
+        HIPCHK(nullptr, hipGetLastError());
+        HIPCHK(nullptr, hipEventRecord(ev.e1, 0));
+        HIPCHK(nullptr, hipEventSynchronize(ev.e1));
         float ms = 0;
-        PECHK(hipEventElapsedTime(&ms, e0, e1));
+        HIPCHK(nullptr, hipEventElapsedTime(&ms, ev.e0, ev.e1));
         ms_total += ms;
-        if (outs && outs[t]) PECHK(hipMemcpy(outs[t], d_L, (size_t)m * m * 8, hipMemcpyDeviceToHost));
+        if (outs && outs[t]) HIPCHK(nullptr, hipMemcpy(outs[t], d_L, (size_t)m * m * 8, hipMemcpyDeviceToHost));
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (colsum) {
         k_colsum<<<(unsigned)((m + 127) / 128), 128>>>(d_L, (int)m, d_cs);
-        PECHK(hipGetLastError());
-        PECHK(hipMemcpy(colsum, d_cs, (size_t)m * 8, hipMemcpyDeviceToHost));
+        HIPCHK(nullptr, hipGetLastError());
+        HIPCHK(nullptr, hipMemcpy(colsum, d_cs, (size_t)m * 8, hipMemcpyDeviceToHost));
     }
     if (kernel_ms) *kernel_ms = ms_total;
     if (prep_out) { prep_out->K = P.K; prep_out->nis = P.nis; prep_out->ea = P.ea; }

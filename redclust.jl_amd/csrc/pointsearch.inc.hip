@@ -2,7 +2,8 @@
 // under the posterior co-clustering counts C (n×n uint32, C_ii = m = number of samples) — the step the reference's
 // docs/src/index.md §"Point estimation" sends its users to R's SALSO for; getpointestimate(method = "MPEL")
 // (src/pointestimate.jl:49-58 of the reference) only ever looks at the clusterings the chain visited.
-// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, rc_ctx, the error buffer).
+// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, rc_ctx, the error buffer and the
+// holders of hostutil.inc.hip).
 //
 // Criterion (DESIGN.md §8 "Point-estimate search"):
 //   Binder   num(c) = Σ_{i<j} C_ij + Σ_{i<j, c_i=c_j} (m − 2·C_ij)                 loss = num / (m·n(n−1)/2)   exact integers
@@ -325,11 +326,6 @@ __global__ __launch_bounds__(TPB) void k_search(Args A)
     }
 }
 
-struct DevBufs {
-    void *p[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~DevBufs() { for (void *q : p) if (q) (void)hipFree(q); }
-};
-
 template <int LOSS>
 static hipError_t launch(int Q, int nruns, size_t lds, hipStream_t st, const Args &A)
 {
@@ -377,13 +373,14 @@ static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, in
         }
     }
     // ---- the counts: symmetric, diagonal m, nothing above m
-    DevBufs B;
-    HIPCHK(c, hipMalloc(&B.p[0], sizeof(unsigned)));
-    HIPCHK(c, hipMemsetAsync(B.p[0], 0, sizeof(unsigned), st));
-    k_check<<<dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8), (unsigned)n), 256, 0, st>>>(dC, ld, (int)n, (unsigned)m, (unsigned *)B.p[0]);
+    DeviceBuffers B;
+    unsigned *d_flag;
+    HIPCHK(c, B.alloc(d_flag, 1));
+    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(unsigned), st));
+    k_check<<<dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8), (unsigned)n), 256, 0, st>>>(dC, ld, (int)n, (unsigned)m, d_flag);
     HIPCHK(c, hipGetLastError());
     unsigned flag = 0;
-    HIPCHK(c, hipMemcpyAsync(&flag, B.p[0], sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(&flag, d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     if (flag & 1u) return fail(c, RC_ERR_ARG, "point search: the diagonal of the counts is not m = %lld everywhere", (long long)m);
     if (flag & 2u) return fail(c, RC_ERR_ARG, "point search: the counts are not symmetric");
@@ -401,13 +398,13 @@ static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, in
     const size_t lds = (fixed + per_slot * (size_t)W + 15) / 16 * 16;
 
     unsigned short *d_init, *d_sz, *d_lab; int *d_K, *d_hi, *d_ord; RunOut *d_out;
-    HIPCHK(c, hipMalloc(&B.p[1], h_init.size() * 2)); d_init = (unsigned short *)B.p[1];
-    HIPCHK(c, hipMalloc(&B.p[2], h_sz.size() * 2)); d_sz = (unsigned short *)B.p[2];
-    HIPCHK(c, hipMalloc(&B.p[3], h_K.size() * 4)); d_K = (int *)B.p[3];
-    HIPCHK(c, hipMalloc(&B.p[4], h_hi.size() * 4)); d_hi = (int *)B.p[4];
-    HIPCHK(c, hipMalloc(&B.p[5], h_ord.size() * 4)); d_ord = (int *)B.p[5];
-    HIPCHK(c, hipMalloc(&B.p[6], h_init.size() * 2)); d_lab = (unsigned short *)B.p[6];
-    HIPCHK(c, hipMalloc(&B.p[7], (size_t)nruns * sizeof(RunOut))); d_out = (RunOut *)B.p[7];
+    HIPCHK(c, B.alloc(d_init, h_init.size()));
+    HIPCHK(c, B.alloc(d_sz, h_sz.size()));
+    HIPCHK(c, B.alloc(d_K, h_K.size()));
+    HIPCHK(c, B.alloc(d_hi, h_hi.size()));
+    HIPCHK(c, B.alloc(d_ord, h_ord.size()));
+    HIPCHK(c, B.alloc(d_lab, h_init.size()));
+    HIPCHK(c, B.alloc(d_out, (size_t)nruns));
     HIPCHK(c, hipMemcpyAsync(d_init, h_init.data(), h_init.size() * 2, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_sz, h_sz.data(), h_sz.size() * 2, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_K, h_K.data(), h_K.size() * 4, hipMemcpyHostToDevice, st));
@@ -417,24 +414,20 @@ static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, in
     Args A{};
     A.C = dC; A.ld = ld; A.init = d_init; A.sz0 = d_sz; A.K0 = d_K; A.hi0 = d_hi; A.order = d_ord; A.labels = d_lab; A.out = d_out;
     A.n = (int)n; A.W = (int)W; A.maxK = maxK; A.maxsweeps = maxsweeps; A.m = (unsigned)m;
-    hipEvent_t e0, e1;
-    HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
-    HIPCHK(c, hipEventRecord(e0, st));
+    TimingEvents ev;
+    HIPCHK(c, ev.create());
+    HIPCHK(c, hipEventRecord(ev.e0, st));
     const int Q = (int)((n + TPB - 1) / TPB);
     const hipError_t le = vi ? launch<RC_PSM_VILB>(Q, nruns, lds, st, A) : launch<RC_PSM_BINDER>(Q, nruns, lds, st, A);
-    if (le != hipSuccess) {
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        return fail(c, RC_ERR_HIP, "point search: launch failed: %s", hipGetErrorString(le));
-    }
-    HIPCHK(c, hipEventRecord(e1, st));
+    if (le != hipSuccess) return fail(c, RC_ERR_HIP, "point search: launch failed: %s", hipGetErrorString(le));
+    HIPCHK(c, hipEventRecord(ev.e1, st));
     std::vector<unsigned short> h_lab(h_init.size());
     std::vector<RunOut> h_out((size_t)nruns);
     HIPCHK(c, hipMemcpyAsync(h_lab.data(), d_lab, h_lab.size() * 2, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(h_out.data(), d_out, h_out.size() * sizeof(RunOut), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
     if (kernel_ms) *kernel_ms = ms;
 
     // ---- results: sortlabels (utils.jl:69-74), the losses, the first minimum
@@ -491,17 +484,16 @@ extern "C" int32_t rc_psm_search(int32_t device, const void *counts, int64_t m, 
     if (!counts) return fail(nullptr, RC_ERR_ARG, "rc_psm_search: NULL argument");
     int32_t rc = psm::check_args(nullptr, "rc_psm_search", m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best);
     if (rc != RC_OK) return rc;
-    int ndev = 0;
-    PECHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(nullptr, RC_ERR_ARG, "rc_psm_search: device %d not available (%d visible)", device, ndev);
-    PECHK(hipSetDevice(device));
+    rc = select_device("rc_psm_search", device);
+    if (rc != RC_OK) return rc;
     const int64_t ld = (n + 3) / 4 * 4;
-    psm::DevBufs B;
-    PECHK(hipMalloc(&B.p[0], (size_t)n * ld * sizeof(unsigned)));
-    if (ld != n) PECHK(hipMemset(B.p[0], 0, (size_t)n * ld * sizeof(unsigned)));
-    PECHK(hipMemcpy2D(B.p[0], (size_t)ld * sizeof(unsigned), counts, (size_t)n * sizeof(unsigned), (size_t)n * sizeof(unsigned), (size_t)n,
+    DeviceBuffers B;
+    unsigned *d_C;
+    HIPCHK(nullptr, B.alloc(d_C, (size_t)n * ld));
+    if (ld != n) HIPCHK(nullptr, hipMemset(d_C, 0, (size_t)n * ld * sizeof(unsigned)));
+    HIPCHK(nullptr, hipMemcpy2D(d_C, (size_t)ld * sizeof(unsigned), counts, (size_t)n * sizeof(unsigned), (size_t)n * sizeof(unsigned), (size_t)n,
                       hipMemcpyHostToDevice));
-    return psm::run(nullptr, nullptr, (const unsigned *)B.p[0], ld, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out,
+    return psm::run(nullptr, nullptr, d_C, ld, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out,
                     (rc_psm_run_t *)runs_out, best, kernel_ms);
 }
 

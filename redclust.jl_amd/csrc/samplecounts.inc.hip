@@ -3,7 +3,8 @@
 // search on those counts without the matrix ever reaching the host.  A live chain builds the same counts as it goes
 // (k_snapshot / k_cocluster_batch, 32 samples per read-modify-write pass over the matrix); here all m samples are present, so
 // every count is computed once from zero in registers and stored once.  DESIGN.md §8 "Counts from samples".
-// Included at the end of redclust_hip.hip (same translation unit: shares fail(), PECHK, psm::run, psm::check_args, psm::DevBufs).
+// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, psm::run, psm::check_args and
+// the holders and select_device of hostutil.inc.hip).
 //
 // Geometry.  The matrix is cut into TI × TJ = 128 × 128 tiles; a 256-thread workgroup computes one tile on or above the
 // diagonal and stores it to both triangles.  A thread owns 8 × 8 counts (64 u32 registers): rows h·64 + ty·4 + 0..3 and columns
@@ -146,42 +147,30 @@ static int32_t narrow(const char *who, const int64_t *samples, int64_t m, int64_
     return RC_OK;
 }
 
-// The counts of the samples in device memory: n × ld uint32 in B.p[0] (every entry written, pad columns zero); B.p[1] holds
-// the labels.  The device is selected; work goes to the null stream.  ms (may be NULL): device time of the kernel.
-static int32_t build(const char *who, const int64_t *samples, int64_t m, int64_t n, int64_t ld, psm::DevBufs &B, double *ms)
+// The counts of the samples in device memory: n × ld uint32 in d_counts, owned by B (every entry written, pad columns zero).
+// The device is selected; work goes to the null stream.  ms (may be NULL): device time of the kernel.
+static int32_t build(const char *who, const int64_t *samples, int64_t m, int64_t n, int64_t ld, DeviceBuffers &B,
+                     unsigned *&d_counts, double *ms)
 {
     const size_t ldn = (size_t)(n + TJ - 1) / TJ * TJ;
     std::vector<unsigned short> h_S;
     int32_t rc = narrow(who, samples, m, n, ldn, h_S);
     if (rc != RC_OK) return rc;
-    PECHK(hipMalloc(&B.p[0], (size_t)n * (size_t)ld * sizeof(unsigned)));
-    PECHK(hipMalloc(&B.p[1], h_S.size() * 2));
-    PECHK(hipMemcpy(B.p[1], h_S.data(), h_S.size() * 2, hipMemcpyHostToDevice));
+    unsigned short *d_S;
+    HIPCHK(nullptr, B.alloc(d_counts, (size_t)n * (size_t)ld));
+    HIPCHK(nullptr, B.alloc(d_S, h_S.size()));
+    HIPCHK(nullptr, hipMemcpy(d_S, h_S.data(), h_S.size() * 2, hipMemcpyHostToDevice));
     const unsigned nt = (unsigned)(ldn / TJ);
-    hipEvent_t e0, e1;
-    PECHK(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail(nullptr, RC_ERR_HIP, "%s: hipEventCreate failed", who); }
-    hipError_t le = hipEventRecord(e0, 0);
-    if (le == hipSuccess) {
-        k_sample_counts<<<dim3(nt, nt), TPB, 0, 0>>>((const unsigned short *)B.p[1], (int)m, (int)n, ldn, (unsigned *)B.p[0], (size_t)ld);
-        le = hipGetLastError();
-    }
-    if (le == hipSuccess) le = hipEventRecord(e1, 0);
-    if (le == hipSuccess) le = hipEventSynchronize(e1);
+    TimingEvents ev;
+    HIPCHK(nullptr, ev.create());
+    HIPCHK(nullptr, hipEventRecord(ev.e0, 0));
+    k_sample_counts<<<dim3(nt, nt), TPB, 0, 0>>>(d_S, (int)m, (int)n, ldn, d_counts, (size_t)ld);
+    HIPCHK(nullptr, hipGetLastError());
+    HIPCHK(nullptr, hipEventRecord(ev.e1, 0));
+    HIPCHK(nullptr, hipEventSynchronize(ev.e1));
     float t = 0;
-    if (le == hipSuccess) le = hipEventElapsedTime(&t, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (le != hipSuccess) return fail(nullptr, RC_ERR_HIP, "%s: the counts kernel failed: %s", who, hipGetErrorString(le));
+    HIPCHK(nullptr, hipEventElapsedTime(&t, ev.e0, ev.e1));
     if (ms) *ms = t;
-    return RC_OK;
-}
-
-static int32_t select_device(const char *who, int32_t device)
-{
-    int ndev = 0;
-    PECHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(nullptr, RC_ERR_ARG, "%s: device %d not available (%d visible)", who, device, ndev);
-    PECHK(hipSetDevice(device));
     return RC_OK;
 }
 
@@ -194,13 +183,14 @@ extern "C" int32_t rc_samples_counts(int32_t device, const int64_t *samples, int
     if (m < 1 || n < 1) return fail(nullptr, RC_ERR_ARG, "%s: need m >= 1 and n >= 1 (got m=%lld n=%lld)", who, (long long)m, (long long)n);
     if (n > sc::NMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %lld points whose labels fit 16 bits beside the pads", who, (long long)n, (long long)sc::NMAX);
     if (m > 0x7FFFFFFFll) return fail(nullptr, RC_ERR_CAPACITY, "%s: m = %lld exceeds the 2^31 - 1 samples a 32-bit count holds", who, (long long)m);
-    int32_t rc = sc::select_device(who, device);
+    int32_t rc = select_device(who, device);
     if (rc != RC_OK) return rc;
     const int64_t ld = (n + 3) / 4 * 4;
-    psm::DevBufs B;
-    rc = sc::build(who, samples, m, n, ld, B, kernel_ms);
+    DeviceBuffers B;
+    unsigned *d_counts;
+    rc = sc::build(who, samples, m, n, ld, B, d_counts, kernel_ms);
     if (rc != RC_OK) return rc;
-    PECHK(hipMemcpy2D(counts_out, (size_t)n * sizeof(unsigned), B.p[0], (size_t)ld * sizeof(unsigned), (size_t)n * sizeof(unsigned), (size_t)n,
+    HIPCHK(nullptr, hipMemcpy2D(counts_out, (size_t)n * sizeof(unsigned), d_counts, (size_t)ld * sizeof(unsigned), (size_t)n * sizeof(unsigned), (size_t)n,
                       hipMemcpyDeviceToHost));
     return RC_OK;
 }
@@ -213,12 +203,13 @@ extern "C" int32_t rc_psm_search_samples(int32_t device, const int64_t *samples,
     if (!samples) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
     int32_t rc = psm::check_args(nullptr, who, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best);
     if (rc != RC_OK) return rc;
-    rc = sc::select_device(who, device);
+    rc = select_device(who, device);
     if (rc != RC_OK) return rc;
     const int64_t ld = (n + 3) / 4 * 4;
-    psm::DevBufs B;                                        // the counts stay on the device
-    rc = sc::build(who, samples, m, n, ld, B, counts_ms);
+    DeviceBuffers B;                                       // the counts stay on the device
+    unsigned *d_counts;
+    rc = sc::build(who, samples, m, n, ld, B, d_counts, counts_ms);
     if (rc != RC_OK) return rc;
-    return psm::run(nullptr, nullptr, (const unsigned *)B.p[0], ld, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out,
+    return psm::run(nullptr, nullptr, d_counts, ld, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out,
                     (rc_psm_run_t *)runs_out, best, kernel_ms);
 }

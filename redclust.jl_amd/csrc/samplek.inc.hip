@@ -1,7 +1,8 @@
 // sampleK (src/prior.jl:316-338 of the reference): draws of K from its prior predictive, the Gumbel-max draw over the n
 // log-probabilities of every sample done on the device.  fitprior2 calls it with max(10^4, 100 n) samples, which is
 // 6.7·10^9 scores at n = 8192 (two lgamma each).  Algorithm and streams as restated in DESIGN.md §8.
-// Included at the end of redclust_hip.hip (same translation unit: shares fail()).
+// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, rc_philox and the holders of
+// hostutil.inc.hip).
 //
 // The host draws r_i ~ Gamma(η, 1/σ) and p_i ~ Beta(u, v); the device scores K = 1..n of sample i as the reference does,
 //     lp[K] = (r·K)·log(1-p) + (n-K)·log(p) - log(n-K) - logbeta(r·K, n-K)   (K < n),   lp[n] = r·n·log(1-p),
@@ -14,7 +15,6 @@
 // draw as p -> 1 (and what the reference's argmax returns on that row).  K and the loop index are int32: n <= 2^30.
 
 #define RC_SK_T 256                      // threads per workgroup: one wave per sample
-#define RC_SK_TAG 0x534D504Bu            // "SMPK": domain tag of the sampleK stream, XORed into the high key word
 #define RC_SK_MAX_N (1 << 30)
 #define RC_SK_SCORES_PER_LAUNCH ((int64_t)1 << 30)   // ~10 ms of scores per launch by the op count (<< 100 ms)
 
@@ -22,16 +22,7 @@ namespace samplek {
 
 __device__ __forceinline__ double uniform(u64 seed, unsigned K, u64 i)
 {
-    unsigned c0 = K, c1 = (unsigned)i, c2 = (unsigned)(i >> 32), c3 = 0, k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32) ^ RC_SK_TAG;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const u64 p0 = (u64)0xD2511F53u * (u64)c0, p1 = (u64)0xCD9E8D57u * (u64)c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    const u64 bits = (((u64)c0 << 32) | c1) >> 12;
-    return ((double)bits + 0.5) * 0x1p-52;
+    return rc_unit52(rc_philox(K, (unsigned)i, (unsigned)(i >> 32), 0, (unsigned)seed, (unsigned)(seed >> 32) ^ RC_SK_TAG));
 }
 
 // sample s of the launch is sample i0 + s of the call; lg[K] = lgamma(n-K), lnk[K] = log(n-K) for K = 1..n-1
@@ -71,35 +62,14 @@ __global__ __launch_bounds__(RC_SK_T) void k_samplek(int n, int m, const double 
 
 }  // namespace samplek
 
-#define SKCHK(call)                                                                                   \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) {                                                                       \
-            free_all();                                                                               \
-            return fail(nullptr, (e_ == hipErrorOutOfMemory) ? RC_ERR_OOM : RC_ERR_HIP, "rc_sample_k: %s failed: %s (%s:%d)", \
-                        #call, hipGetErrorString(e_), __FILE__, __LINE__);                            \
-        }                                                                                             \
-    } while (0)
-
 extern "C" int32_t rc_sample_k(int32_t device, int64_t n, int64_t m, const double *r, const double *p, uint64_t seed,
                                int64_t *K_out, double *kernel_ms)
 {
     if (!r || !p || !K_out) return fail(nullptr, RC_ERR_ARG, "rc_sample_k: NULL argument");
     if (n < 1 || n > RC_SK_MAX_N) return fail(nullptr, RC_ERR_ARG, "rc_sample_k: n must be in 1..2^30 (got %lld)", (long long)n);
     if (m < 1) return fail(nullptr, RC_ERR_ARG, "rc_sample_k: need m >= 1 samples (got %lld)", (long long)m);
-    double *d_r = nullptr, *d_p = nullptr, *d_lg = nullptr, *d_lnk = nullptr;
-    long long *d_K = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto free_all = [&]() {
-        for (void *q : {(void *)d_r, (void *)d_p, (void *)d_lg, (void *)d_lnk, (void *)d_K})
-            if (q) (void)hipFree(q);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
-    int ndev = 0;
-    SKCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(nullptr, RC_ERR_ARG, "rc_sample_k: device %d not available (%d visible)", device, ndev);
-    SKCHK(hipSetDevice(device));
+    int32_t rc = select_device("rc_sample_k", device);
+    if (rc != RC_OK) return rc;
     std::vector<double> lg((size_t)n), lnk((size_t)n);
     for (int64_t K = 1; K < n; ++K) {
         lg[(size_t)K] = std::lgamma((double)(n - K));
@@ -108,33 +78,33 @@ extern "C" int32_t rc_sample_k(int32_t device, int64_t n, int64_t m, const doubl
     // samples per launch: ~RC_SK_SCORES_PER_LAUNCH scores, a whole number of workgroups
     const int64_t per = RC_SK_T / 64;
     const int64_t mb = std::min<int64_t>(m, std::max<int64_t>(per, std::min<int64_t>((int64_t)1 << 20, RC_SK_SCORES_PER_LAUNCH / n) / per * per));
-    SKCHK(hipMalloc(&d_r, (size_t)mb * 8));
-    SKCHK(hipMalloc(&d_p, (size_t)mb * 8));
-    SKCHK(hipMalloc(&d_K, (size_t)mb * 8));
-    SKCHK(hipMalloc(&d_lg, (size_t)n * 8));
-    SKCHK(hipMalloc(&d_lnk, (size_t)n * 8));
-    SKCHK(hipMemcpy(d_lg, lg.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-    SKCHK(hipMemcpy(d_lnk, lnk.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-    SKCHK(hipEventCreate(&e0));
-    SKCHK(hipEventCreate(&e1));
+    DeviceBuffers B;
+    TimingEvents ev;
+    double *d_r, *d_p, *d_lg, *d_lnk;
+    long long *d_K;
+    HIPCHK(nullptr, B.alloc(d_r, (size_t)mb));
+    HIPCHK(nullptr, B.alloc(d_p, (size_t)mb));
+    HIPCHK(nullptr, B.alloc(d_K, (size_t)mb));
+    HIPCHK(nullptr, B.alloc(d_lg, (size_t)n));
+    HIPCHK(nullptr, B.alloc(d_lnk, (size_t)n));
+    HIPCHK(nullptr, hipMemcpy(d_lg, lg.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_lnk, lnk.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, ev.create());
     double ms_total = 0;
     for (int64_t i0 = 0; i0 < m; i0 += mb) {
         const int cnt = (int)std::min<int64_t>(mb, m - i0);
-        SKCHK(hipMemcpy(d_r, r + i0, (size_t)cnt * 8, hipMemcpyHostToDevice));
-        SKCHK(hipMemcpy(d_p, p + i0, (size_t)cnt * 8, hipMemcpyHostToDevice));
-        SKCHK(hipEventRecord(e0, 0));
+        HIPCHK(nullptr, hipMemcpy(d_r, r + i0, (size_t)cnt * 8, hipMemcpyHostToDevice));
+        HIPCHK(nullptr, hipMemcpy(d_p, p + i0, (size_t)cnt * 8, hipMemcpyHostToDevice));
+        HIPCHK(nullptr, hipEventRecord(ev.e0, 0));
         samplek::k_samplek<<<(unsigned)((cnt + per - 1) / per), RC_SK_T, 0, 0>>>((int)n, cnt, d_r, d_p, d_lg, d_lnk, seed, (u64)i0, d_K);
-        SKCHK(hipGetLastError());
-        SKCHK(hipEventRecord(e1, 0));
-        SKCHK(hipEventSynchronize(e1));
+        HIPCHK(nullptr, hipGetLastError());
+        HIPCHK(nullptr, hipEventRecord(ev.e1, 0));
+        HIPCHK(nullptr, hipEventSynchronize(ev.e1));
         float ms = 0;
-        SKCHK(hipEventElapsedTime(&ms, e0, e1));
+        HIPCHK(nullptr, hipEventElapsedTime(&ms, ev.e0, ev.e1));
         ms_total += ms;
-        SKCHK(hipMemcpy(K_out + i0, d_K, (size_t)cnt * 8, hipMemcpyDeviceToHost));
+        HIPCHK(nullptr, hipMemcpy(K_out + i0, d_K, (size_t)cnt * 8, hipMemcpyDeviceToHost));
     }
-    free_all();
     if (kernel_ms) *kernel_ms = ms_total;
     return RC_OK;
 }
-
-#undef SKCHK

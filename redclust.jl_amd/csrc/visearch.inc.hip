@@ -1,7 +1,7 @@
 // Exact posterior expected VI search on the device: the greedy search of pointsearch.inc.hip (same mechanism, same tie
 // rules) for the criterion SALSO calls "VI" proper — the mean over the m samples of VI(c, sample) — instead of Wade &
-// Ghahramani's lower bound.  Included at the end of redclust_hip.hip (same translation unit: shares fail(), PECHK, the
-// error buffer and psm's sortable-key reduction).
+// Ghahramani's lower bound.  Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, the
+// error buffer, the holders and select_device of hostutil.inc.hip and psm's sortable-key reduction).
 //
 // Criterion (DESIGN.md §8 "Exact expected VI search"), φ(x) = x·log x:
 //   n·m·E[VI](c) = m·Σ_k φ(n_k) + Σ_s Σ_l φ(n^s_l) − 2·Σ_s Σ_{k,l} φ(N^s_kl),   N^s_kl = #{j : c_j = k, c^s_j = l}
@@ -406,53 +406,48 @@ extern "C" int32_t rc_vi_search(int32_t device, const int64_t *samples, int64_t 
         }
     }
 
-    int ndev = 0;
-    PECHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(nullptr, RC_ERR_ARG, "%s: device %d not available (%d visible)", who, device, ndev);
-    PECHK(hipSetDevice(device));
+    int32_t rc = select_device(who, device);
+    if (rc != RC_OK) return rc;
 
-    psm::DevBufs B;
+    DeviceBuffers B;
     long long *d_G, *d_Phi; unsigned short *d_SL, *d_N, *d_init, *d_sz, *d_lab; int *d_K, *d_ord; RunOut *d_out;
-    PECHK(hipMalloc(&B.p[0], Gq.size() * 8)); d_G = (long long *)B.p[0];
-    PECHK(hipMalloc(&B.p[1], Phi.size() * 8)); d_Phi = (long long *)B.p[1];
-    PECHK(hipMalloc(&B.p[2], h_SL.size() * 2)); d_SL = (unsigned short *)B.p[2];
-    PECHK(hipMalloc(&B.p[3], table_elems * 2 * (size_t)nruns)); d_N = (unsigned short *)B.p[3];
-    PECHK(hipMalloc(&B.p[4], h_init.size() * 2)); d_init = (unsigned short *)B.p[4];
-    PECHK(hipMalloc(&B.p[5], h_sz.size() * 2)); d_sz = (unsigned short *)B.p[5];
-    PECHK(hipMalloc(&B.p[6], h_K.size() * 4)); d_K = (int *)B.p[6];
-    PECHK(hipMalloc(&B.p[7], h_ord.size() * 4)); d_ord = (int *)B.p[7];
-    PECHK(hipMalloc(&B.p[8], h_init.size() * 2)); d_lab = (unsigned short *)B.p[8];
-    PECHK(hipMalloc(&B.p[9], (size_t)nruns * sizeof(RunOut))); d_out = (RunOut *)B.p[9];
-    PECHK(hipMemcpy(d_G, Gq.data(), Gq.size() * 8, hipMemcpyHostToDevice));
-    PECHK(hipMemcpy(d_Phi, Phi.data(), Phi.size() * 8, hipMemcpyHostToDevice));
-    PECHK(hipMemcpy(d_SL, h_SL.data(), h_SL.size() * 2, hipMemcpyHostToDevice));
-    PECHK(hipMemset(d_N, 0, table_elems * 2 * (size_t)nruns));
-    PECHK(hipMemcpy(d_init, h_init.data(), h_init.size() * 2, hipMemcpyHostToDevice));
-    PECHK(hipMemcpy(d_sz, h_sz.data(), h_sz.size() * 2, hipMemcpyHostToDevice));
-    PECHK(hipMemcpy(d_K, h_K.data(), h_K.size() * 4, hipMemcpyHostToDevice));
-    PECHK(hipMemcpy(d_ord, h_ord.data(), h_ord.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, B.alloc(d_G, Gq.size()));
+    HIPCHK(nullptr, B.alloc(d_Phi, Phi.size()));
+    HIPCHK(nullptr, B.alloc(d_SL, h_SL.size()));
+    HIPCHK(nullptr, B.alloc(d_N, table_elems * (size_t)nruns));
+    HIPCHK(nullptr, B.alloc(d_init, h_init.size()));
+    HIPCHK(nullptr, B.alloc(d_sz, h_sz.size()));
+    HIPCHK(nullptr, B.alloc(d_K, h_K.size()));
+    HIPCHK(nullptr, B.alloc(d_ord, h_ord.size()));
+    HIPCHK(nullptr, B.alloc(d_lab, h_init.size()));
+    HIPCHK(nullptr, B.alloc(d_out, (size_t)nruns));
+    HIPCHK(nullptr, hipMemcpy(d_G, Gq.data(), Gq.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_Phi, Phi.data(), Phi.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_SL, h_SL.data(), h_SL.size() * 2, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemset(d_N, 0, table_elems * 2 * (size_t)nruns));
+    HIPCHK(nullptr, hipMemcpy(d_init, h_init.data(), h_init.size() * 2, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_sz, h_sz.data(), h_sz.size() * 2, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_K, h_K.data(), h_K.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_ord, h_ord.data(), h_ord.size() * 4, hipMemcpyHostToDevice));
 
     Args A{};
     A.Gq = d_G; A.Phi = d_Phi; A.SL = d_SL; A.N = d_N; A.init = d_init; A.sz0 = d_sz; A.K0 = d_K; A.order = d_ord; A.labels = d_lab;
     A.out = d_out; A.n = (int)n; A.m = (int)m; A.Lmax = Lmax; A.kpad = kpad; A.Kcap = Kcap; A.maxsweeps = maxsweeps;
     const int PQ = m <= TPB ? 1 : (m <= (int64_t)TPB * STAGE_Q ? STAGE_Q : 0);
     const size_t lds = Carve((int)n, kpad, Kcap, PQ).total;
-    hipEvent_t e0, e1;
-    PECHK(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail(nullptr, RC_ERR_HIP, "%s: hipEventCreate failed", who); }
-    hipError_t le = hipEventRecord(e0, 0);
-    if (le == hipSuccess) le = launch(PQ, nruns, lds, A);
-    if (le == hipSuccess) le = hipEventRecord(e1, 0);
-    if (le == hipSuccess) le = hipDeviceSynchronize();
+    TimingEvents ev;
+    HIPCHK(nullptr, ev.create());
+    HIPCHK(nullptr, hipEventRecord(ev.e0, 0));
+    HIPCHK(nullptr, launch(PQ, nruns, lds, A));
+    HIPCHK(nullptr, hipEventRecord(ev.e1, 0));
+    HIPCHK(nullptr, hipDeviceSynchronize());
     float ms = 0;
-    if (le == hipSuccess) le = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (le != hipSuccess) return fail(nullptr, RC_ERR_HIP, "%s: the search kernel failed: %s", who, hipGetErrorString(le));
+    HIPCHK(nullptr, hipEventElapsedTime(&ms, ev.e0, ev.e1));
     if (kernel_ms) *kernel_ms = ms;
     std::vector<unsigned short> h_lab(h_init.size());
     std::vector<RunOut> h_out((size_t)nruns);
-    PECHK(hipMemcpy(h_lab.data(), d_lab, h_lab.size() * 2, hipMemcpyDeviceToHost));
-    PECHK(hipMemcpy(h_out.data(), d_out, h_out.size() * sizeof(RunOut), hipMemcpyDeviceToHost));
+    HIPCHK(nullptr, hipMemcpy(h_lab.data(), d_lab, h_lab.size() * 2, hipMemcpyDeviceToHost));
+    HIPCHK(nullptr, hipMemcpy(h_out.data(), d_out, h_out.size() * sizeof(RunOut), hipMemcpyDeviceToHost));
 
     // ---- results: sortlabels (utils.jl:69-74), the losses, the first minimum
     const double scale = std::ldexp((double)n * (double)m, 32);

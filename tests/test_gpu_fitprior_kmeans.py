@@ -43,6 +43,25 @@ def test_scan_split_equals_within_between(pts):
     ctx.close()
 
 
+def test_scan_split_on_32_bit_storage():
+    """The split of rc_kmeans_scan_split on a context that stores D in 32 bits.  n = 130: two full waves plus two lanes, a
+    partial 256-thread tile, and at k = 1 a group that takes both the "> 64 members" and the "> n/16" branches.  (dim = 3: the
+    smallest generatemixture accepts for three components.)"""
+    p = rc.generatemixture(130, 3, dim=3, seed=4, points_only=True)["points"]
+    ctx = rc.Context.from_points(p, storage_bits=32)
+    scan = ctx.kmeans_scan(1, 130, maxiter=1000, seed=3, split=True)
+    chunked = ctx.kmeans_scan(1, 130, maxiter=1000, seed=3, split=True, slots_per_chunk=7)
+    assert set(scan) == set(chunked) and set(WB) <= set(scan)
+    for f in scan:
+        assert np.array_equal(scan[f], chunked[f]), f
+    for k in (1, 2, 3, 17, 129, 130):
+        ctx.set_state(ctx.kmeans(k, maxiter=1000, seed=3).assignments)
+        wb = ctx.within_between()
+        for f in WB:
+            assert scan[f][k - 1] == wb[f], (k, f, scan[f][k - 1], wb[f])
+    ctx.close()
+
+
 def compose_fitprior(ctx, n, seed, Kmin=1, Kmax=None):
     """fitprior_kmeans from the public pieces: scan -> elbow -> notional run -> set_state / within_between -> host fits."""
     Kmax = n // 2 if Kmax is None else Kmax

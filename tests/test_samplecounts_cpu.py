@@ -32,6 +32,17 @@ def test_the_source_is_part_of_the_build():
     assert '"samplecounts.inc.hip"' in open(os.path.join(ROOT, "redclust.jl_amd", "_lib.py")).read()
 
 
+def test_every_include_is_built_and_listed():
+    """The *.inc.hip files of csrc/, the ones redclust_hip.hip includes and the ones build() watches are the same set."""
+    csrc = os.path.join(ROOT, "redclust.jl_amd", "csrc")
+    on_disk = {f for f in os.listdir(csrc) if f.endswith(".inc.hip")}
+    included = set(re.findall(r'^#include "([^"]+\.inc\.hip)"', open(os.path.join(csrc, "redclust_hip.hip")).read(), flags=re.M))
+    lib = open(os.path.join(ROOT, "redclust.jl_amd", "_lib.py")).read()
+    body = lib[lib.index("def build("):lib.index("def build_diag(")]
+    listed = set(re.findall(r'"([^"]+\.inc\.hip)"', body))
+    assert on_disk and on_disk == included == listed, (sorted(on_disk), sorted(included), sorted(listed))
+
+
 def test_julia_glue_calls_the_new_entries():
     jl = open(os.path.join(ROOT, "julia", "RedClustHIP.jl")).read()
     assert "ccall((:rc_psm_search_samples, LIB)" in jl and "ccall((:rc_samples_counts, LIB)" in jl

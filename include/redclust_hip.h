@@ -532,6 +532,27 @@ int32_t rc_vi_search(int32_t device, const int64_t *samples /* m×n, labels 1..n
                      int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */, void *runs_out /* rc_psm_run_t[nruns] */,
                      int32_t *best, double *kernel_ms);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Exact expected-ID search: rc_vi_search's search — the same runs, slot cap, compaction of the start, tie rules, tables and
+ * capacity — for the posterior expected information distance, the mean over the m samples of
+ * infodist(c, sample; normalised = false) = max(H(c), H(sample)) − I(c, sample) (src/pointestimate.jl:89-99; the `id` of
+ * evaluateclustering, whose `nid` is id / log n, so the same partition minimises both).  DESIGN.md §8 "Exact expected ID search".
+ *
+ * With rc_vi_gtable's Gq and Phiq:  Aq(c) = Σ_k Phiq(n_k),  Bq_s = Σ_l Phiq(n^s_l), and the search minimises the integer
+ *   Q_ID(c) = Σ_s max(Aq(c), Bq_s) − Σ_s Σ_{k,l} Phiq(N^s_kl).
+ * With point i out (Aq becomes A0), putting it into a cluster of n_k members changes Q_ID by exactly
+ *   F(A0 + Gq[n_k]) − F(A0) − Σ_s Gq[N^s[l_s(i)][k]],   F(x) = Σ_s max(x, Bq_s)   (0 for a new cluster),
+ * so a run is a pure integer function of its arguments.  Per run: loss_num = Q_ID, loss = Q_ID / (2^32·n·m), the expected
+ * ID in nats (within 2^-32 of the f64 value).  The sorted Bq_s and their prefix sums (16·(m+1) bytes) sit in the workgroup's LDS
+ * where they fit beside rc_vi_search's state, else in global memory — the same integers either way; RC_ID_TABLE_GLOBAL=1 in the
+ * environment (read at every call) forces the latter, for tests.
+ * Arguments, RC_ERR_ARG and RC_ERR_CAPACITY (n <= 8192, m·n <= 2^26, slot cap <= 1024, the table budget) as rc_vi_search.
+ * ------------------------------------------------------------------------------------------------------------- */
+int32_t rc_id_search(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n, int32_t nruns,
+                     const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */,
+                     int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */, void *runs_out /* rc_psm_run_t[nruns] */,
+                     int32_t *best, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -312,6 +312,11 @@ SALSO's "VI" — instead of its lower bound (rc_vi_search: fixed point, every ru
 Its runs are the same `nruns` orders from empty labels, one from the MPEL VI sample and one from the result of the
 lower-bound search with the same arguments, so the answer is never worse in expected VI than either; `info.loss` is then the
 expected VI and `info.loss_num` the integer criterion.
+
+`loss = "ID"` minimises the posterior expected information distance — the mean over `result.clusts` of
+`infodist(c, sample; normalised = false)`, the `id` of `evaluateclustering` — with the same kernel and fixed point
+(rc_id_search); `exact` may be either value.  Its runs are the `nruns` orders from empty labels, one from the MPEL ID sample
+and one from the result of `exact = true, loss = "VI"` with the same arguments; `info.loss` is the expected ID.
 """
 struct RcPsmRun
     loss::Cdouble
@@ -338,6 +343,7 @@ psminfo(runs, labels, best) =
 function searchpointestimate(b::HIPBackend, result; loss::String = "VI", nruns::Integer = 16, maxK::Integer = 0,
                              maxsweeps::Integer = 100, seed::Integer = 0, exact::Bool = false)
     code = Dict("binder" => 0, "VI" => 1)
+    loss == "ID" && return searchexactid(b, result, nruns, maxK, maxsweeps, seed)
     haskey(code, loss) || throw(ArgumentError("Invalid loss function specifier."))
     if exact
         loss == "VI" || throw(ArgumentError("exact = true needs loss = \"VI\""))
@@ -445,6 +451,40 @@ function searchexactvi(b::HIPBackend, result, nruns::Integer, maxK::Integer, max
     runs = Vector{RcPsmRun}(undef, R)
     best = Int32[0]
     rc = ccall((:rc_vi_search, LIB), Int32,
+               (Int32, Ptr{Int64}, Int64, Int64, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
+                Ptr{Int32}, Ptr{Cdouble}),
+               b.device, samples, m, n, R, init, order, cap, maxsweeps, labels, runs, best, C_NULL)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    info = (loss = [x.loss for x in runs], loss_num = [x.loss_num for x in runs], sweeps = [Int(x.sweeps) for x in runs],
+            converged = [x.converged != 0 for x in runs], moves = [Int(x.moves) for x in runs], K = [Int(x.K) for x in runs],
+            labels = labels, best = Int(best[1]) + 1)
+    return (labels[:, best[1] + 1], info)
+end
+
+function searchexactid(b::HIPBackend, result, nruns::Integer, maxK::Integer, maxsweeps::Integer, seed::Integer)
+    samples = samplematrix(result)
+    n, m = size(samples)
+    vi, _ = searchexactvi(b, result, nruns, maxK, maxsweeps, seed)
+    R = Int(nruns) + 2
+    init = zeros(Int64, n, R)                                     # column r = run r: row-major R×n for the library
+    order = Matrix{Int32}(undef, n, R)
+    rng = Random.MersenneTwister(seed)
+    for r in 1:nruns
+        order[:, r] .= Random.randperm(rng, n)
+    end
+    start, _ = getpointestimate_hip(result; loss = "ID", device = b.device)
+    init[:, R - 1] .= start; order[:, R - 1] .= 1:n
+    init[:, R] .= vi; order[:, R] .= 1:n
+    cap = Int(maxK)
+    if cap == 0                                                   # the library's default cap, widened to the starts' cluster counts
+        lmax = maximum(length(unique(c)) for c in result.clusts)
+        need = max(length(unique(start)), length(unique(vi)))
+        cap = need > lmax ? need : 0
+    end
+    labels = Matrix{Int64}(undef, n, R)
+    runs = Vector{RcPsmRun}(undef, R)
+    best = Int32[0]
+    rc = ccall((:rc_id_search, LIB), Int32,
                (Int32, Ptr{Int64}, Int64, Int64, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
                 Ptr{Int32}, Ptr{Cdouble}),
                b.device, samples, m, n, R, init, order, cap, maxsweeps, labels, runs, best, C_NULL)

@@ -12,5 +12,5 @@ from .prior import fitprior, fitprior2, fitprior_kmeans, fitprior2_kmeans, kmean
 from .datagen import generatemixture, oracle_coclustering, likelihood_hyperparams, likelihood_hyperparams_device  # noqa: F401
 from .chains import chain_seed, merge_chains, run_chains, run_chains_single_process, library_merge, agreed_merge, device_counts_tensor  # noqa: F401
 from .pointestimate import (getpointestimate, lossmatrix, binderloss, infodist, varinfo, evaluateclustering,  # noqa: F401
-                            summarise, searchpointestimate, expectedloss, expectedvi, cocluster_counts,
+                            summarise, searchpointestimate, expectedloss, expectedvi, expectedid, cocluster_counts,
                             posterior_counts, posterior_coclustering)

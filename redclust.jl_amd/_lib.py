@@ -190,6 +190,8 @@ SIGNATURES = {
     "rc_vi_gtable": (C.c_int32, [C.c_int64, C.c_void_p]),
     "rc_vi_search": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_id_search": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rc_samples_counts": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_double)]),
     "rc_psm_search_samples": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double),
@@ -764,10 +766,11 @@ def vi_gtable(n: int) -> np.ndarray:
     return out
 
 
-def vi_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
+def vi_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0, entry: str = "rc_vi_search"):
     """rc_vi_search: the exact expected-VI search.  samples: m×n labels in 1..n; init: nruns×n labels (0 = unallocated), order:
     nruns×n 1-based permutations.  Returns psm_search's dict: labels (nruns×n, sortlabels'd), the per-run arrays loss (the
-    expected VI), loss_num (the integer Q), sweeps, converged, moves, K, and best, kernel_ms."""
+    expected VI), loss_num (the integer Q), sweeps, converged, moves, K, and best, kernel_ms.  entry: the symbol called —
+    rc_id_search has the same parameter list (id_search)."""
     L = lib()
     S = np.ascontiguousarray(samples, dtype=np.int64)
     init = np.ascontiguousarray(init, dtype=np.int64)
@@ -781,8 +784,8 @@ def vi_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device:
     labels = np.zeros((max(nruns, 1), max(n, 1)), np.int64)
     runs = (RcPsmRun * max(nruns, 1))()
     best, ms = C.c_int32(-1), C.c_double()
-    rc = L.rc_vi_search(int(device), S.ctypes.data, m, n, nruns, init.ctypes.data, order.ctypes.data, int(maxK), int(maxsweeps),
-                        labels.ctypes.data, runs, C.byref(best), C.byref(ms))
+    rc = getattr(L, entry)(int(device), S.ctypes.data, m, n, nruns, init.ctypes.data, order.ctypes.data, int(maxK), int(maxsweeps),
+                           labels.ctypes.data, runs, C.byref(best), C.byref(ms))
     if rc != RC_OK:
         raise _error(rc, L.rc_last_error(None).decode())
     out = dict(labels=labels[:nruns, :n], best=int(best.value), kernel_ms=float(ms.value))
@@ -790,6 +793,12 @@ def vi_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device:
         out[k] = np.array([getattr(r, k) for r in runs[:nruns]], dtype=np.float64 if ty is C.c_double else np.int64)
     out["converged"] = out["converged"].astype(bool)
     return out
+
+
+def id_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
+    """rc_id_search: the exact expected-ID search.  Arguments and the returned dict as vi_search; loss is the expected
+    information distance (nats), loss_num the integer Q_ID."""
+    return vi_search(samples, init, order, maxK=maxK, maxsweeps=maxsweeps, device=device, entry="rc_id_search")
 
 
 def sample_k(n: int, r, p, seed: int = 0, device: int = 0):

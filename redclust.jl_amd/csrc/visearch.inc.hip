@@ -26,6 +26,14 @@
 //
 // LDS (dynamic, carved at 16-byte offsets): Gq i64[n+1] (64 KiB at n = 8192; Φq at the end), acc u64[kpad], the
 // reduction partials, sz u16[Kcap+2], lab u16[n], the label double buffer u16[2][1024·PQ]: 109 024 B at the largest sizes.
+//
+// The same kernel searches the posterior expected information distance (LOSS = LOSS_ID, rc_id_search; DESIGN.md §8 "Exact
+// expected ID search"):  n·m·E[ID](c) = F(A(c)) − Σ_s Σ_kl φ(N^s_kl),  A(c) = Σ_k φ(n_k),  F(x) = Σ_s max(x, B_s),
+// B_s = Σ_l φ(n^s_l).  In fixed point Q_ID(c) = Σ_s max(Aq(c), Bq_s) − Σ_s Σ_kl Φq(N^s_kl), and with Bs the Bq_s sorted
+// ascending, Pre their prefix sums and p(x) = #{t : Bs[t] <= x}:  F(x) = x·p(x) + Pre[m] − Pre[p(x)].  Phase A is the VI
+// search's; phase B scores slot k as F(A₀ + Gq[n_k]) − F(A₀) − acc_k, A₀ = Aq without the visited point; thread 0 keeps Aq
+// (LDS) up to date in phase C under sz's discipline.  Behind the carve above: Aq, then Bs i64[m] and Pre i64[m+1] — 16·(m+1)
+// bytes with Aq — when that fits the 160 KiB, else 16 bytes for Aq and the two tables are read from global memory.
 
 namespace visearch {
 
@@ -37,6 +45,8 @@ constexpr int VEC = 4;                                // slots per thread in a t
 constexpr long long MN_MAX = 1ll << 26;               // |Q| <= 2·m·n·log(n)·2^32 < 2^63
 constexpr size_t TABLE_BUDGET = (size_t)4 << 30;      // bytes of contingency tables, all runs together
 constexpr int STAGE_Q = 4;                            // labels of the next point staged in LDS while m <= 1024·STAGE_Q
+constexpr size_t LDS_MAX = 160 * 1024;                // of a gfx950 CU, all of which one workgroup may take
+constexpr int LOSS_VI = 0, LOSS_ID = 1;
 
 struct RunOut {
     long long Q, moves;
@@ -55,6 +65,12 @@ struct Args {
     unsigned short *labels;       // nruns × n out (slots)
     RunOut *out;
     int n, m, Lmax, kpad, Kcap, maxsweeps;
+    // LOSS_ID only
+    const long long *Bs;          // m: the samples' Σ_l Φq(n^s_l), ascending
+    const long long *Pre;         // m + 1: Pre[p] = Σ_{t<p} Bs[t]
+    const long long *Aq0;         // nruns: Σ_k Φq(n_k) of init
+    int nbits;                    // trip count of the search for p(x): ceil(log2(m + 1))
+    int tab_lds;                  // Bs and Pre are copied to LDS behind Aq
 };
 
 __host__ __device__ inline size_t up16(size_t x) { return (x + 15) / 16 * 16; }
@@ -73,6 +89,22 @@ struct Carve {
     }
 };
 
+// ID: (F(x0), F(x1)) from the sorted table, both searches in one loop of nbits trips (the same for every thread)
+template <typename P>
+__device__ inline void id_F2(P Bs, P Pre, int m, int nbits, long long x0, long long x1, long long &F0, long long &F1)
+{
+    int p0 = 0, p1 = 0;
+    for (int b = nbits - 1; b >= 0; --b) {
+        const int q0 = p0 + (1 << b), q1 = p1 + (1 << b);
+        const long long b0 = Bs[min(q0, m) - 1], b1 = Bs[min(q1, m) - 1];
+        if (q0 <= m && b0 <= x0) p0 = q0;
+        if (q1 <= m && b1 <= x1) p1 = q1;
+    }
+    const long long tot = Pre[m];
+    F0 = x0 * p0 + tot - Pre[p0];
+    F1 = x1 * p1 + tot - Pre[p1];
+}
+
 __device__ inline void add_row(const uint2 v, int ka, const long long *Gq, long long (&acc)[VEC])
 {
     // ka: where the visited point's own slot sits in this thread's four, if it does — the point itself is out
@@ -81,7 +113,7 @@ __device__ inline void add_row(const uint2 v, int ka, const long long *Gq, long 
     acc[0] += Gq[x0]; acc[1] += Gq[x1]; acc[2] += Gq[x2]; acc[3] += Gq[x3];
 }
 
-template <int PQ>
+template <int PQ, int LOSS>
 __global__ __launch_bounds__(TPB) void k_visearch(Args A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char vis_lds[];
@@ -97,6 +129,8 @@ __global__ __launch_bounds__(TPB) void k_visearch(Args A)
     unsigned short *sz = reinterpret_cast<unsigned short *>(vis_lds + cv.sz);
     unsigned short *lab = reinterpret_cast<unsigned short *>(vis_lds + cv.lab);
     unsigned short *stage = reinterpret_cast<unsigned short *>(vis_lds + cv.stage);   // [2][TPB·PQ]
+    long long *Aq = reinterpret_cast<long long *>(vis_lds + cv.total);                // ID: Aq, Bs[m], Pre[m + 1]
+    long long *Bs_l = Aq + 1, *Pre_l = Bs_l + m;
 
     const unsigned short *__restrict__ SL = A.SL;
     unsigned short *Nrun = A.N + (size_t)run * m * Lmax * kpad;
@@ -106,6 +140,13 @@ __global__ __launch_bounds__(TPB) void k_visearch(Args A)
     for (int k = tid; k < kpad; k += TPB) acc[k] = 0;
     for (int k = tid; k < Kcap + 2; k += TPB) sz[k] = A.sz0[(size_t)run * (Kcap + 2) + k];
     for (int j = tid; j < n; j += TPB) lab[j] = A.init[(size_t)run * n + j];
+    if (LOSS == LOSS_ID) {
+        if (tid == 0) Aq[0] = A.Aq0[run];
+        if (A.tab_lds) {
+            for (int s = tid; s < m; s += TPB) Bs_l[s] = A.Bs[s];
+            for (int s = tid; s <= m; s += TPB) Pre_l[s] = A.Pre[s];
+        }
+    }
     __syncthreads();
     int K = A.K0[run];
     if (K) {
@@ -205,8 +246,17 @@ __global__ __launch_bounds__(TPB) void k_visearch(Args A)
                 acc[tid] = 0;
                 if (k <= (unsigned)Kcap) {
                     const int nk = (int)sz[k] - (k == a ? 1 : 0);
+                    long long idsc = 0;
+                    if (LOSS == LOSS_ID) {
+                        // F(A0 + Gq[n_k]) − F(A0) − acc_k; an empty slot runs the search too (nk = 0) and drops the result
+                        const long long A0 = Aq[0] - (a ? Gq[sz[a] - 1] : 0ll);
+                        long long F0, F1;
+                        if (A.tab_lds) id_F2(Bs_l, Pre_l, m, A.nbits, A0, A0 + Gq[nk], F0, F1);
+                        else id_F2(A.Bs, A.Pre, m, A.nbits, A0, A0 + Gq[nk], F0, F1);
+                        idsc = F1 - F0 - sum;
+                    }
                     if (nk <= 0) minfree = k;
-                    else best = psm::Cand{psm::key_i64((long long)m * Gq[nk] - 2 * sum), (k == a) ? 0u : k, k, 0u};
+                    else best = psm::Cand{psm::key_i64(LOSS == LOSS_ID ? idsc : (long long)m * Gq[nk] - 2 * sum), (k == a) ? 0u : k, k, 0u};
                 }
             }
 #pragma unroll
@@ -249,6 +299,7 @@ __global__ __launch_bounds__(TPB) void k_visearch(Args A)
             }
             if (tid == 0) {
                 lab[i] = (unsigned short)w;
+                if (LOSS == LOSS_ID && a != w) Aq[0] += Gq[sz[w]] - (a ? Gq[sz[a] - 1] : 0ll);
                 if (a) sz[a] = (unsigned short)(sz[a] - 1);
                 sz[w] = (unsigned short)(sz[w] + 1);
             }
@@ -270,7 +321,14 @@ __global__ __launch_bounds__(TPB) void k_visearch(Args A)
     for (int x = tid; x <= n; x += TPB) Gq[x] = A.Phi[x];
     __syncthreads();
     unsigned long long q = 0;
-    if (tid < Kcap) q = (unsigned long long)((long long)m * Gq[sz[tid + 1]]);
+    if (LOSS == LOSS_ID) {
+        if (tid == 0) {
+            long long F0, F1;
+            if (A.tab_lds) id_F2(Bs_l, Pre_l, m, A.nbits, Aq[0], Aq[0], F0, F1);
+            else id_F2(A.Bs, A.Pre, m, A.nbits, Aq[0], Aq[0], F0, F1);
+            q = (unsigned long long)F0;
+        }
+    } else if (tid < Kcap) q = (unsigned long long)((long long)m * Gq[sz[tid + 1]]);
     {
         unsigned long long t2 = 0;
         const uint2 *N2 = reinterpret_cast<const uint2 *>(Nrun);
@@ -280,7 +338,7 @@ __global__ __launch_bounds__(TPB) void k_visearch(Args A)
             t2 += (unsigned long long)Gq[v.x & 0xFFFFu] + (unsigned long long)Gq[v.x >> 16] +
                   (unsigned long long)Gq[v.y & 0xFFFFu] + (unsigned long long)Gq[v.y >> 16];
         }
-        q -= 2 * t2;
+        q -= (LOSS == LOSS_ID ? 1 : 2) * t2;
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) q += psm::shfl_xor_u64(q, off);
@@ -295,13 +353,14 @@ __global__ __launch_bounds__(TPB) void k_visearch(Args A)
     }
 }
 
+template <int LOSS>
 static hipError_t launch(int PQ, int nruns, size_t lds, const Args &A)
 {
 #define VIS_LAUNCH(QQ)                                                                                                    \
     do {                                                                                                                  \
-        hipError_t e = hipFuncSetAttribute((const void *)k_visearch<QQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipError_t e = hipFuncSetAttribute((const void *)k_visearch<QQ, LOSS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         if (e != hipSuccess) return e;                                                                                    \
-        k_visearch<QQ><<<nruns, TPB, lds, 0>>>(A);                                                                        \
+        k_visearch<QQ, LOSS><<<nruns, TPB, lds, 0>>>(A);                                                                  \
     } while (0)
     if (PQ == 0) VIS_LAUNCH(0);
     else if (PQ == 1) VIS_LAUNCH(1);
@@ -319,22 +378,11 @@ static void gtable(int64_t n, int64_t *out)
     }
 }
 
-}  // namespace visearch
-
-extern "C" int32_t rc_vi_gtable(int64_t n, int64_t *out)
+// The host side of rc_vi_search (loss = LOSS_VI) and rc_id_search (LOSS_ID): the same arguments, checks, staging and results
+static int32_t run(int loss, const char *who, int32_t device, const int64_t *samples, int64_t m, int64_t n, int32_t nruns,
+                   const int64_t *init, const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out_,
+                   int32_t *best, double *kernel_ms)
 {
-    if (!out) return fail(nullptr, RC_ERR_ARG, "rc_vi_gtable: NULL argument");
-    if (n < 1) return fail(nullptr, RC_ERR_ARG, "rc_vi_gtable: need n >= 1 (got %lld)", (long long)n);
-    visearch::gtable(n, out);
-    return RC_OK;
-}
-
-extern "C" int32_t rc_vi_search(int32_t device, const int64_t *samples, int64_t m, int64_t n, int32_t nruns, const int64_t *init,
-                                const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out_,
-                                int32_t *best, double *kernel_ms)
-{
-    using namespace visearch;
-    const char *who = "rc_vi_search";
     rc_psm_run_t *runs_out = (rc_psm_run_t *)runs_out_;
     if (!samples || !init || !order || !labels_out || !runs_out || !best) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
     if (m < 1 || n < 1 || nruns < 1)
@@ -353,6 +401,7 @@ extern "C" int32_t rc_vi_search(int32_t device, const int64_t *samples, int64_t 
     for (int64_t x = 0; x < n; ++x) Phi[(size_t)x + 1] = Phi[(size_t)x] + Gq[(size_t)x];
     int Lmax = 0;
     __int128 constant = 0;                                              // Σ_s Σ_l Φq(n^s_l)
+    std::vector<long long> Bs(loss == LOSS_ID ? (size_t)m : 0);         // ID: the same sum per sample (Bq_s)
     for (int64_t s = 0; s < m; ++s) {
         std::fill(map.begin(), map.end(), 0);
         std::fill(cnt.begin(), cnt.end(), 0);
@@ -364,7 +413,10 @@ extern "C" int32_t rc_vi_search(int32_t device, const int64_t *samples, int64_t 
             h_SL[(size_t)j * m + s] = (unsigned short)(map[(size_t)l] - 1);
             cnt[(size_t)map[(size_t)l]]++;
         }
-        for (int l = 1; l <= L; ++l) constant += Phi[(size_t)cnt[(size_t)l]];
+        long long bq = 0;
+        for (int l = 1; l <= L; ++l) bq += Phi[(size_t)cnt[(size_t)l]];
+        constant += bq;
+        if (loss == LOSS_ID) Bs[(size_t)s] = bq;
         Lmax = std::max(Lmax, L);
     }
     // ---- the slot cap: always positive
@@ -381,6 +433,7 @@ extern "C" int32_t rc_vi_search(int32_t device, const int64_t *samples, int64_t 
     // ---- the runs: labels in 0..n compacted to slots 1..K0 by first appearance, orders permutations of 1..n
     std::vector<unsigned short> h_init((size_t)nruns * n), h_sz((size_t)nruns * (Kcap + 2), 0);
     std::vector<int> h_K((size_t)nruns), h_ord((size_t)nruns * n);
+    std::vector<long long> h_Aq((size_t)nruns, 0);                      // ID: Σ_k Φq(n_k) of the start
     std::vector<char> seen((size_t)n);
     for (int r = 0; r < nruns; ++r) {
         std::fill(map.begin(), map.end(), 0);
@@ -397,6 +450,7 @@ extern "C" int32_t rc_vi_search(int32_t device, const int64_t *samples, int64_t 
             if (slot) h_sz[(size_t)r * (Kcap + 2) + slot]++;
         }
         h_K[(size_t)r] = K;
+        for (int k = 1; k <= K; ++k) h_Aq[(size_t)r] += Phi[(size_t)h_sz[(size_t)r * (Kcap + 2) + k]];
         std::fill(seen.begin(), seen.end(), 0);
         for (int64_t t = 0; t < n; ++t) {
             const int32_t o = order[(size_t)r * n + t];
@@ -434,11 +488,30 @@ extern "C" int32_t rc_vi_search(int32_t device, const int64_t *samples, int64_t 
     A.Gq = d_G; A.Phi = d_Phi; A.SL = d_SL; A.N = d_N; A.init = d_init; A.sz0 = d_sz; A.K0 = d_K; A.order = d_ord; A.labels = d_lab;
     A.out = d_out; A.n = (int)n; A.m = (int)m; A.Lmax = Lmax; A.kpad = kpad; A.Kcap = Kcap; A.maxsweeps = maxsweeps;
     const int PQ = m <= TPB ? 1 : (m <= (int64_t)TPB * STAGE_Q ? STAGE_Q : 0);
-    const size_t lds = Carve((int)n, kpad, Kcap, PQ).total;
+    size_t lds = Carve((int)n, kpad, Kcap, PQ).total;
+    if (loss == LOSS_ID) {
+        // F's table: the Bq_s ascending and their prefix sums; in LDS behind Aq where that fits, else read from global memory
+        std::sort(Bs.begin(), Bs.end());
+        std::vector<long long> Pre((size_t)m + 1, 0);
+        for (int64_t s = 0; s < m; ++s) Pre[(size_t)s + 1] = Pre[(size_t)s] + Bs[(size_t)s];
+        long long *d_Bs, *d_Pre, *d_Aq;
+        HIPCHK(nullptr, B.alloc(d_Bs, Bs.size()));
+        HIPCHK(nullptr, B.alloc(d_Pre, Pre.size()));
+        HIPCHK(nullptr, B.alloc(d_Aq, h_Aq.size()));
+        HIPCHK(nullptr, hipMemcpy(d_Bs, Bs.data(), Bs.size() * 8, hipMemcpyHostToDevice));
+        HIPCHK(nullptr, hipMemcpy(d_Pre, Pre.data(), Pre.size() * 8, hipMemcpyHostToDevice));
+        HIPCHK(nullptr, hipMemcpy(d_Aq, h_Aq.data(), h_Aq.size() * 8, hipMemcpyHostToDevice));
+        A.Bs = d_Bs; A.Pre = d_Pre; A.Aq0 = d_Aq;
+        while ((1ll << A.nbits) < m + 1) ++A.nbits;                     // p(x) is in 0..m
+        const char *e = std::getenv("RC_ID_TABLE_GLOBAL");              // tests: force the global-memory table at small m
+        const bool force_global = e && std::atoi(e) != 0;
+        A.tab_lds = (!force_global && lds + 16 * ((size_t)m + 1) <= LDS_MAX) ? 1 : 0;
+        lds += A.tab_lds ? 16 * ((size_t)m + 1) : 16;
+    }
     TimingEvents ev;
     HIPCHK(nullptr, ev.create());
     HIPCHK(nullptr, hipEventRecord(ev.e0, 0));
-    HIPCHK(nullptr, launch(PQ, nruns, lds, A));
+    HIPCHK(nullptr, loss == LOSS_ID ? launch<LOSS_ID>(PQ, nruns, lds, A) : launch<LOSS_VI>(PQ, nruns, lds, A));
     HIPCHK(nullptr, hipEventRecord(ev.e1, 0));
     HIPCHK(nullptr, hipDeviceSynchronize());
     float ms = 0;
@@ -464,9 +537,35 @@ extern "C" int32_t rc_vi_search(int32_t device, const int64_t *samples, int64_t 
         rc_psm_run_t &R = runs_out[r];
         R.sweeps = o.sweeps; R.converged = o.converged; R.moves = o.moves; R.K = o.K;
         R.loss_num = o.Q;
-        R.loss = (double)((__int128)o.Q + constant) / scale;
+        R.loss = (double)((__int128)o.Q + (loss == LOSS_ID ? (__int128)0 : constant)) / scale;
         if (R.loss_num < runs_out[b].loss_num) b = r;
     }
     *best = b;
     return RC_OK;
+}
+
+}  // namespace visearch
+
+extern "C" int32_t rc_vi_gtable(int64_t n, int64_t *out)
+{
+    if (!out) return fail(nullptr, RC_ERR_ARG, "rc_vi_gtable: NULL argument");
+    if (n < 1) return fail(nullptr, RC_ERR_ARG, "rc_vi_gtable: need n >= 1 (got %lld)", (long long)n);
+    visearch::gtable(n, out);
+    return RC_OK;
+}
+
+extern "C" int32_t rc_vi_search(int32_t device, const int64_t *samples, int64_t m, int64_t n, int32_t nruns, const int64_t *init,
+                                const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out,
+                                int32_t *best, double *kernel_ms)
+{
+    return visearch::run(visearch::LOSS_VI, "rc_vi_search", device, samples, m, n, nruns, init, order, maxK, maxsweeps, labels_out,
+                         runs_out, best, kernel_ms);
+}
+
+extern "C" int32_t rc_id_search(int32_t device, const int64_t *samples, int64_t m, int64_t n, int32_t nruns, const int64_t *init,
+                                const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out,
+                                int32_t *best, double *kernel_ms)
+{
+    return visearch::run(visearch::LOSS_ID, "rc_id_search", device, samples, m, n, nruns, init, order, maxK, maxsweeps, labels_out,
+                         runs_out, best, kernel_ms);
 }

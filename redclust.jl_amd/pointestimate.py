@@ -147,28 +147,76 @@ def expectedvi(clust, samples) -> float:
     return total / (n * len(clusts))
 
 
-def _vi_search_exact(samples, nruns, maxK, maxsweeps, seed, init, device):
-    """searchpointestimate(loss="VI", exact=True): see there."""
-    S = np.stack([_labels(c) for c in samples.clusts])
+def expectedid(clust, samples) -> float:
+    """The posterior expected information distance of `clust`: the mean over the samples (an MCMCResult, anything with
+    `.clusts`, or an m×n label matrix) of infodist(clust, sample; normalised = false) = max(H(c), H(s)) − I(c, s) =
+    [max(Σ_k φ(n_k), Σ_l φ(n_l)) − Σ_kl φ(N_kl)] / n with φ(x) = x·log x, natural logs — what searchpointestimate(loss="ID")
+    minimises, in plain NumPy on the host.  evaluateclustering's `nid` is this divided by log n."""
+    c = np.unique(_labels(clust), return_inverse=True)[1].astype(np.int64)      # 0..K−1: K·L bins per sample below
+    clusts = samples.clusts if hasattr(samples, "clusts") else samples
+    n = len(c)
+    if len(clusts) == 0:
+        raise ValueError("no samples")
+
+    def phi(x):
+        x = x[x > 0].astype(np.float64)
+        return float(np.sum(x * np.log(x)))
+
+    base = phi(np.bincount(c))
+    total = 0.0
+    for s in clusts:
+        s = np.asarray(s)
+        if len(s) != n:
+            raise ValueError("every sample must have as many labels as clust")
+        s = np.unique(_labels(s), return_inverse=True)[1].astype(np.int64)
+        total += max(base, phi(np.bincount(s))) - phi(np.bincount(c * (int(s.max()) + 1) + s))
+    return total / (n * len(clusts))
+
+
+def _search_starts(samples, S, nruns, maxK, seed, init, device, mpel_loss, extra):
+    """The runs of the exact searches: nruns Philox orders from empty labels, one run per init labelling, one from the MPEL
+    sample of mpel_loss and one from `extra`, the last three kinds in the identity order; and the slot cap to hand to the
+    library — with maxK = 0 its default is the samples' largest cluster count, which a start with more clusters widens."""
     n = S.shape[1]
-    _, lower = searchpointestimate(samples, "VI", nruns=nruns, maxK=maxK, maxsweeps=maxsweeps, seed=seed, init=init, device=device)
     inits = [np.zeros(n, np.int64)] * int(nruns)
     rng = np.random.Generator(np.random.Philox(key=int(seed)))
     ident = np.arange(1, n + 1, dtype=np.int32)
     orders = [rng.permutation(n).astype(np.int32) + 1 for _ in range(int(nruns))]
     for lab in ([] if init is None else (np.atleast_2d(np.asarray(init)))):
-        inits.append(np.asarray(lab, np.int64))                      # (lengths were checked by the lower-bound call)
+        inits.append(np.asarray(lab, np.int64))                      # (lengths were checked by the call that gave `extra`)
         orders.append(ident)
-    start, _ = getpointestimate(samples, "MPEL", "VI", device=device)
-    inits += [_labels(start), lower["labels"][lower["best"]]]
+    start, _ = getpointestimate(samples, "MPEL", mpel_loss, device=device)
+    inits += [_labels(start), extra]
     orders += [ident, ident]
     if not maxK:
-        # the library's default cap is the samples' largest cluster count; a start with more clusters widens it
         lmax = max(len(np.unique(s)) for s in S)
         need = max(len(np.unique(x[x > 0])) for x in inits)
         maxK = need if need > lmax else 0
-    res = _lib.vi_search(S, np.stack(inits), np.stack(orders), maxK=maxK, maxsweeps=maxsweeps, device=device)
-    info = {k: res[k] for k in ("loss", "sweeps", "converged", "moves", "K", "labels", "best", "kernel_ms", "loss_num")}
+    return np.stack(inits), np.stack(orders), maxK
+
+
+_INFO_KEYS = ("loss", "sweeps", "converged", "moves", "K", "labels", "best", "kernel_ms", "loss_num")
+
+
+def _id_search(samples, nruns, maxK, maxsweeps, seed, init, device):
+    """searchpointestimate(loss="ID"): see there."""
+    S = np.stack([_labels(c) for c in samples.clusts])
+    vi_clust, vi = searchpointestimate(samples, "VI", nruns=nruns, maxK=maxK, maxsweeps=maxsweeps, seed=seed, init=init, device=device,
+                                       exact=True)
+    inits, orders, maxK = _search_starts(samples, S, nruns, maxK, seed, init, device, "ID", vi_clust)
+    res = _lib.id_search(S, inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device)
+    info = {k: res[k] for k in _INFO_KEYS}
+    info["vi"] = vi
+    return res["labels"][res["best"]].copy(), info
+
+
+def _vi_search_exact(samples, nruns, maxK, maxsweeps, seed, init, device):
+    """searchpointestimate(loss="VI", exact=True): see there."""
+    S = np.stack([_labels(c) for c in samples.clusts])
+    _, lower = searchpointestimate(samples, "VI", nruns=nruns, maxK=maxK, maxsweeps=maxsweeps, seed=seed, init=init, device=device)
+    inits, orders, maxK = _search_starts(samples, S, nruns, maxK, seed, init, device, "VI", lower["labels"][lower["best"]])
+    res = _lib.vi_search(S, inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device)
+    info = {k: res[k] for k in _INFO_KEYS}
     info["lower_bound"] = lower
     return res["labels"][res["best"]].copy(), info
 
@@ -182,7 +230,7 @@ def searchpointestimate(samples_or_counts=None, loss="VI", *, nruns: int = 16, m
     samples_or_counts: an MCMCResult (its counts are rebuilt exactly from `clusts` on the device and stay there:
     rc_psm_search_samples; info["counts_ms"] is that kernel's time), or an n×n uint32 count matrix together
     with numsamples; or pass a live Context as ctx= (with numsamples): its device counts are searched in place.
-    loss: "binder" or "VI" — see expectedloss; "VI" is the lower bound, not the exact posterior expected VI.  When the
+    loss: "binder", "VI" — see expectedloss; "VI" is the lower bound, not the exact posterior expected VI — or "ID", below.  When the
     samples are given, the partition-independent constant (1/n)·Σ_i mean_s log n^(s)_{c_i} that turns the bound's value into
     Wade & Ghahramani's is returned as info["vi_constant"]; the losses themselves leave it out.
     Runs: nruns runs from empty labels (sequential allocation, then improving sweeps) in the orders
@@ -199,7 +247,21 @@ def searchpointestimate(samples_or_counts=None, loss="VI", *, nruns: int = 16, m
     result is never worse than either in the searched integer criterion info["loss_num"] (runs, and the choice of best, are
     exact in it).  info["loss"] is the expected VI as the library returns it, (Q + constant)/(2^32·n·m): within
     2·2^-32 ≈ 4.7e-10 of expectedvi's f64 value, so allow that much when comparing it with expectedvi of another labelling.
-    Besides the search the call costs the exact=False search (with its counts kernel) and the MPEL loss matrix.  maxK = 0 caps the clusters at the largest cluster count among the samples (or a start's, if larger)."""
+    Besides the search the call costs the exact=False search (with its counts kernel) and the MPEL loss matrix.  maxK = 0 caps the clusters at the largest cluster count among the samples (or a start's, if larger).
+
+    loss="ID" (an MCMCResult, or anything with `.clusts`, only; `exact` may be either value, there is no bound variant):
+    minimise the posterior expected information distance (expectedid; the `id` of evaluateclustering, SALSO's "ID") — the
+    same kernel and fixed point as exact=True (rc_id_search), so a run is again an exact integer function of its inputs.
+    Runs: the nruns Philox orders from empty labels, one per init labelling, one from the MPEL ID sample and one from the
+    result of searchpointestimate(samples, "VI", exact=True) with the same arguments (info["vi"] is that call's info), so the
+    result is never worse in the integer criterion info["loss_num"] than either.  info["loss"] = Q_ID/(2^32·n·m) is within
+    2^-32 ≈ 2.3e-10 of expectedid's f64 value.  maxK = 0 is widened as for exact=True."""
+    if loss == "ID":
+        if ctx is not None:
+            raise ValueError('loss="ID" needs the samples; a Context keeps only their counts')
+        if not hasattr(samples_or_counts, "clusts"):
+            raise ValueError('loss="ID" needs the samples (an MCMCResult), not a count matrix')
+        return _id_search(samples_or_counts, nruns, maxK, maxsweeps, seed, init, device)
     if loss not in _PSM_LOSSES:
         raise ValueError("Invalid loss function specifier.")
     if exact:

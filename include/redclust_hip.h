@@ -553,6 +553,64 @@ int32_t rc_id_search(int32_t device, const int64_t *samples /* m×n, labels 1..n
                      int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */, void *runs_out /* rc_psm_run_t[nruns] */,
                      int32_t *best, double *kernel_ms);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Hierarchical point estimates: agglomerative clustering of the co-clustering counts (Medvedovic's method; mcclust's
+ * minbinder and mcclust.ext's minVI with method = "avg" / "comp"), the whole dendrogram in one launch, and the expected
+ * loss of given labellings on the device.  DESIGN.md §8 "Hierarchical point estimates".
+ *
+ * counts, m, n, capacity (n <= 8192, m·n < 2^31: RC_ERR_CAPACITY beyond, before any device work) and the checks of the
+ * counts (RC_ERR_ARG) as in the point-estimate search above.  Clusters are named by their smallest member (1-based).  Per
+ * pair of active clusters a < b: S_ab = Σ_{i∈a, j∈b} C_ij and M_ab = the minimum (complete) or maximum (single) of C_ij over
+ * the pair.  Similarity, larger is closer:  average S_ab / (|a|·|b|), compared exactly by cross-multiplication in 128 bits;
+ * complete and single M_ab.  A step merges the pair of largest similarity — ties: the smallest a, then the smallest b — b
+ * into a: S_ac += S_bc and M_ac = min / max(M_ac, M_bc) for every other active c, |a| += |b|.  n − 1 steps; pairs of
+ * similarity 0 merge too, at the end.  No floating point: a run is a pure integer function of (counts, m, linkage).
+ * merges_out[t − 1], t = 1..n−1: a, b, the new size of a, S_ab and M_ab (0 for average) of step t.
+ * binder_num[t], t = 0..n−1: RC_PSM_BINDER's num of the partition after t merges (K = n − t clusters):
+ *   binder_num[0] = Σ_{i<j} C_ij,  binder_num[t] = binder_num[t−1] + |a|·|b|·m − 2·S_ab.
+ * vilb (may be NULL with maxcut = 0): vilb[K − 1], K = 1..maxcut <= n, is RC_PSM_VILB's loss of the cut with K clusters,
+ * evaluated like the expected-loss entry points below on labellings the host derives from the merges.
+ * kernel_ms (may be NULL): device time of the call's kernels.  RC_ERR_ARG also: a NULL pointer, an unknown linkage, maxcut
+ * outside 0..n.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define RC_HCLUST_AVERAGE 0
+#define RC_HCLUST_COMPLETE 1
+#define RC_HCLUST_SINGLE 2
+typedef struct rc_hclust_merge_t {
+    int32_t a, b;  /* a < b; b goes into a */
+    int32_t size;  /* members of a after the merge */
+    uint32_t m_ab; /* 0 for average */
+    int64_t s_ab;
+} rc_hclust_merge_t;
+
+/* counts: host n×n uint32; merges_out: rc_hclust_merge_t[n − 1] (untyped for plain FFIs, like runs_out above). */
+int32_t rc_hclust(int32_t device, const void *counts /* uint32_t n×n */, int64_t m, int64_t n, int32_t linkage,
+                  void *merges_out /* rc_hclust_merge_t[n-1] */, int64_t *binder_num /* n */, int32_t maxcut, double *vilb /* maxcut */,
+                  double *kernel_ms);
+/* On the counts of an m×n label matrix, built on the device where they stay (as rc_psm_search_samples; counts_ms likewise). */
+int32_t rc_hclust_samples(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n, int32_t linkage,
+                          void *merges_out /* rc_hclust_merge_t[n-1] */, int64_t *binder_num /* n */, int32_t maxcut,
+                          double *vilb /* maxcut */, double *kernel_ms, double *counts_ms);
+/* On the context's own device counts, read in place: chain state, layout and counts stay untouched.  RC_ERR_STATE when no
+ * sample has been recorded. */
+int32_t rc_hclust_ctx(rc_ctx *ctx, int64_t numsamples, int32_t linkage, void *merges_out /* rc_hclust_merge_t[n-1] */,
+                      int64_t *binder_num /* n */, int32_t maxcut, double *vilb /* maxcut */, double *kernel_ms);
+/* Host only: the labelling with K clusters (after the first n − K merges), labels 1..K in sortlabels order — names are
+ * smallest members, so ranking the names gives that order.  RC_ERR_ARG: K outside 1..n, n outside 1..8192, merges that are
+ * not merges of active clusters a < b. */
+int32_t rc_hclust_cut(const void *merges /* rc_hclust_merge_t[n-1] */, int64_t n, int64_t K, int64_t *labels_out /* n */);
+
+/* The expected loss of L given labellings (labels 1..n, L×n row-major, L <= 65536) under the counts: one kernel returns
+ * T_i = Σ_{j: c_j=c_i} C_ij (uint32) for every labelling and point, reading each row of the counts once per group of 8
+ * labellings; the host finishes from T and the cluster sizes:
+ *   RC_PSM_BINDER  num_out = Σ_{i<j} C_ij + m·#{i<j: c_i=c_j} − Σ_i (T_i − m), exact; loss_out = num / (m·n(n−1)/2);
+ *   RC_PSM_VILB    loss_out = f/n + 2·log m, f = Σ_i [log n_{c_i} − 2·log T_i] summed in index order in f64; num_out = 0.
+ * Errors as rc_hclust; RC_ERR_ARG also for a label outside 1..n and an unknown loss. */
+int32_t rc_psm_expected_loss(int32_t device, const void *counts /* uint32_t n×n */, int64_t m, int64_t n, int32_t loss, int64_t L,
+                             const int64_t *labels /* L×n */, double *loss_out /* L */, int64_t *num_out /* L */, double *kernel_ms);
+int32_t rc_psm_expected_loss_ctx(rc_ctx *ctx, int64_t numsamples, int32_t loss, int64_t L, const int64_t *labels /* L×n */,
+                                 double *loss_out /* L */, int64_t *num_out /* L */, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -497,4 +497,78 @@ end
 
 export searchpointestimate, posteriorcounts
 
+# rc_hclust_merge_t
+struct RcHclustMerge
+    a::Int32; b::Int32
+    size::Int32
+    m_ab::UInt32
+    s_ab::Int64
+end
+
+const HCLUST_LINKAGES = Dict("average" => 0, "complete" => 1, "single" => 2)
+
+# the cut of minimum loss among K = 1..maxK (ties: the smaller K), its labels from the library's own rc_hclust_cut
+function hclustchoose(merges, binder_num, vilb, n::Integer, m::Integer, loss::String, maxK::Integer, kernel_ms)
+    pairs = n * (n - 1) ÷ 2
+    losses = loss == "binder" ? [pairs == 0 ? 0.0 : binder_num[n - K + 1] / (m * pairs) for K in 1:maxK] : vilb
+    K = loss == "binder" ? argmin([binder_num[n - K + 1] for K in 1:maxK]) : argmin(vilb)
+    labels = Vector{Int64}(undef, n)
+    rc = ccall((:rc_hclust_cut, LIB), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}), merges, n, K, labels)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return (labels, (loss = losses, K = K, merges = merges[1:n-1], binder_num = binder_num, kernel_ms = kernel_ms[1]))
+end
+
+"""
+    hclustpointestimate(HIPBackend(), counts, numsamples; loss = "VI", linkage = "average", maxK = 0) -> (clust, info)
+    hclustpointestimate(HIPBackend(), result; loss = "VI", linkage = "average", maxK = 0) -> (clust, info)
+
+The hierarchical point estimate (Medvedovic's method; mcclust's `minbinder` / mcclust.ext's `minVI` with `method = "avg"` /
+`"comp"`): agglomerative clustering of the co-clustering counts on the GPU (rc_hclust, rc_hclust_samples), cut at the number
+of clusters `K` in `1:maxK` of minimum expected loss, ties going to the smaller `K`.  `linkage`: "average", "complete" or
+"single", on similarities; ties between pairs go to the smallest cluster name (its smallest member), then the smallest partner,
+and every decision is exact integer arithmetic.  `loss`: "binder" (from the exact curve `info.binder_num`, index t + 1 = after t
+merges) or "VI" (the lower bound, evaluated for every cut on the device).  `maxK = 0` means ⌈n/8⌉.  `info.merges` holds one
+`RcHclustMerge` per step.
+"""
+function hclustpointestimate(b::HIPBackend, counts::Matrix{UInt32}, numsamples::Integer; loss::String = "VI",
+                             linkage::String = "average", maxK::Integer = 0)
+    loss in ("binder", "VI") || throw(ArgumentError("Invalid loss function specifier."))
+    haskey(HCLUST_LINKAGES, linkage) || throw(ArgumentError("Invalid linkage specifier."))
+    n = size(counts, 1)
+    size(counts, 2) == n || throw(ArgumentError("counts must be a square matrix"))
+    maxK = maxK == 0 ? cld(n, 8) : Int(maxK)
+    1 <= maxK <= n || throw(ArgumentError("maxK must lie in 1:n"))
+    merges = Vector{RcHclustMerge}(undef, max(n - 1, 1))
+    binder_num = Vector{Int64}(undef, n)
+    maxcut = loss == "VI" ? maxK : 0
+    vilb = Vector{Cdouble}(undef, max(maxcut, 1))
+    ms = Cdouble[0]
+    rc = ccall((:rc_hclust, LIB), Int32,
+               (Int32, Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Int64}, Int32, Ptr{Cdouble}, Ptr{Cdouble}),
+               b.device, counts, numsamples, n, HCLUST_LINKAGES[linkage], merges, binder_num, maxcut, vilb, ms)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return hclustchoose(merges, binder_num, vilb[1:maxcut], n, numsamples, loss, maxK, ms)
+end
+
+function hclustpointestimate(b::HIPBackend, result; loss::String = "VI", linkage::String = "average", maxK::Integer = 0)
+    loss in ("binder", "VI") || throw(ArgumentError("Invalid loss function specifier."))
+    haskey(HCLUST_LINKAGES, linkage) || throw(ArgumentError("Invalid linkage specifier."))
+    samples = samplematrix(result)                                # the counts are built from these on the device and stay there
+    n, m = size(samples)
+    maxK = maxK == 0 ? cld(n, 8) : Int(maxK)
+    1 <= maxK <= n || throw(ArgumentError("maxK must lie in 1:n"))
+    merges = Vector{RcHclustMerge}(undef, max(n - 1, 1))
+    binder_num = Vector{Int64}(undef, n)
+    maxcut = loss == "VI" ? maxK : 0
+    vilb = Vector{Cdouble}(undef, max(maxcut, 1))
+    ms = Cdouble[0]
+    rc = ccall((:rc_hclust_samples, LIB), Int32,
+               (Int32, Ptr{Int64}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Int64}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+               b.device, samples, m, n, HCLUST_LINKAGES[linkage], merges, binder_num, maxcut, vilb, ms, C_NULL)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return hclustchoose(merges, binder_num, vilb[1:maxcut], n, m, loss, maxK, ms)
+end
+
+export hclustpointestimate
+
 end # module

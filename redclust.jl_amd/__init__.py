@@ -13,4 +13,5 @@ from .datagen import generatemixture, oracle_coclustering, likelihood_hyperparam
 from .chains import chain_seed, merge_chains, run_chains, run_chains_single_process, library_merge, agreed_merge, device_counts_tensor  # noqa: F401
 from .pointestimate import (getpointestimate, lossmatrix, binderloss, infodist, varinfo, evaluateclustering,  # noqa: F401
                             summarise, searchpointestimate, expectedloss, expectedvi, expectedid, cocluster_counts,
-                            posterior_counts, posterior_coclustering)
+                            posterior_counts, posterior_coclustering, hclust, hclustpointestimate, expectedlosses,
+                            linkage_matrix, leaf_order)

@@ -87,7 +87,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
             os.path.join(CSRC, "chain.inc.hip"), os.path.join(CSRC, "chains.inc.hip"), os.path.join(CSRC, "samplek.inc.hip"),
             os.path.join(CSRC, "mixture.inc.hip"), os.path.join(CSRC, "kmeans.inc.hip"),
             os.path.join(CSRC, "pointsearch.inc.hip"), os.path.join(CSRC, "visearch.inc.hip"),
-            os.path.join(CSRC, "samplecounts.inc.hip"), HEADER]
+            os.path.join(CSRC, "samplecounts.inc.hip"), os.path.join(CSRC, "hclust.inc.hip"), HEADER]
     if not force and os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(s) for s in srcs):
         return SO
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-o", SO, srcs[0]]
@@ -196,6 +196,17 @@ SIGNATURES = {
     "rc_psm_search_samples": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                           C.POINTER(C.c_double)]),
+    "rc_hclust": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                              C.POINTER(C.c_double)]),
+    "rc_hclust_samples": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                      C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rc_hclust_ctx": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                  C.POINTER(C.c_double)]),
+    "rc_hclust_cut": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "rc_psm_expected_loss": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.POINTER(C.c_double)]),
+    "rc_psm_expected_loss_ctx": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(C.c_double)]),
     "rc_layout_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rc_event_overhead_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "rc_kernel_timing": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -799,6 +810,85 @@ def id_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device:
     """rc_id_search: the exact expected-ID search.  Arguments and the returned dict as vi_search; loss is the expected
     information distance (nats), loss_num the integer Q_ID."""
     return vi_search(samples, init, order, maxK=maxK, maxsweeps=maxsweeps, device=device, entry="rc_id_search")
+
+
+# rc_hclust_merge_t
+HCLUST_MERGE = np.dtype([("a", np.int32), ("b", np.int32), ("size", np.int32), ("m_ab", np.uint32), ("s_ab", np.int64)], align=True)
+
+
+def hclust(counts, numsamples, linkage: int, maxcut: int = 0, device: int = 0, ctx=None, samples=None):
+    """rc_hclust (counts: n×n uint32), rc_hclust_samples (samples: m×n int64 labels; counts and numsamples are ignored) or,
+    with ctx, rc_hclust_ctx on that context's device counts.  Returns a dict: merges (n − 1 records of HCLUST_MERGE),
+    binder_num (n int64; index t = after t merges), vilb (maxcut f64: the VI-bound loss of the cuts K = 1..maxcut), kernel_ms,
+    and counts_ms for the samples form."""
+    L = lib()
+    if samples is not None:
+        S = np.ascontiguousarray(samples, dtype=np.int64)
+        if S.ndim != 2:
+            raise ValueError("samples must be an m×n matrix of labels")
+        numsamples, n = S.shape
+    elif ctx is not None:
+        n = ctx.n
+    else:
+        cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+        if cnt.ndim != 2 or cnt.shape[0] != cnt.shape[1]:
+            raise ValueError("counts must be an n×n matrix")
+        n = cnt.shape[0]
+    merges = np.zeros(max(n - 1, 1), HCLUST_MERGE)
+    bnum = np.zeros(max(n, 1), np.int64)
+    vilb = np.zeros(max(int(maxcut), 1))
+    ms, cms = C.c_double(), C.c_double()
+    out = {}
+    if samples is not None:
+        rc = L.rc_hclust_samples(int(device), S.ctypes.data, int(numsamples), n, int(linkage), merges.ctypes.data, bnum.ctypes.data,
+                                 int(maxcut), vilb.ctypes.data, C.byref(ms), C.byref(cms))
+        out["counts_ms"] = float(cms.value)
+    elif ctx is not None:
+        rc = L.rc_hclust_ctx(ctx.h, int(numsamples), int(linkage), merges.ctypes.data, bnum.ctypes.data, int(maxcut), vilb.ctypes.data,
+                             C.byref(ms))
+    else:
+        rc = L.rc_hclust(int(device), cnt.ctypes.data, int(numsamples), n, int(linkage), merges.ctypes.data, bnum.ctypes.data,
+                         int(maxcut), vilb.ctypes.data, C.byref(ms))
+    if rc != RC_OK:
+        raise _error(rc, L.rc_last_error(ctx.h if ctx is not None and samples is None else None).decode())
+    out.update(merges=merges[:max(n - 1, 0)], binder_num=bnum[:n], vilb=vilb[:int(maxcut)], kernel_ms=float(ms.value))
+    return out
+
+
+def hclust_cut(merges, n: int, K: int) -> np.ndarray:
+    """rc_hclust_cut (host only): the labelling with K clusters, labels 1..K in sortlabels order."""
+    L = lib()
+    mg = np.ascontiguousarray(merges, dtype=HCLUST_MERGE)
+    labels = np.zeros(max(int(n), 1), np.int64)
+    rc = L.rc_hclust_cut(mg.ctypes.data, int(n), int(K), labels.ctypes.data)
+    if rc != RC_OK:
+        raise _error(rc, L.rc_last_error(None).decode())
+    return labels[:int(n)]
+
+
+def psm_expected_loss(labels, counts, numsamples: int, loss: int, device: int = 0, ctx=None):
+    """rc_psm_expected_loss (counts: n×n uint32) or, with ctx, rc_psm_expected_loss_ctx: (loss f64[L], num int64[L], kernel ms)
+    of the L×n labellings `labels` (1..n)."""
+    L = lib()
+    lab = np.ascontiguousarray(labels, dtype=np.int64)
+    if lab.ndim != 2:
+        raise ValueError("labels must be an L×n matrix")
+    nl, n = lab.shape
+    loss_out, num_out, ms = np.zeros(max(nl, 1)), np.zeros(max(nl, 1), np.int64), C.c_double()
+    if ctx is not None:
+        if n != ctx.n:
+            raise ValueError("labels must have the context's n columns")
+        rc = L.rc_psm_expected_loss_ctx(ctx.h, int(numsamples), int(loss), nl, lab.ctypes.data, loss_out.ctypes.data,
+                                        num_out.ctypes.data, C.byref(ms))
+    else:
+        cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+        if cnt.shape != (n, n):
+            raise ValueError("counts must be an n×n matrix matching labels")
+        rc = L.rc_psm_expected_loss(int(device), cnt.ctypes.data, int(numsamples), n, int(loss), nl, lab.ctypes.data,
+                                    loss_out.ctypes.data, num_out.ctypes.data, C.byref(ms))
+    if rc != RC_OK:
+        raise _error(rc, L.rc_last_error(ctx.h if ctx is not None else None).decode())
+    return loss_out[:nl], num_out[:nl], float(ms.value)
 
 
 def sample_k(n: int, r, p, seed: int = 0, device: int = 0):

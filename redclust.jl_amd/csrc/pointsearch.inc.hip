@@ -100,6 +100,24 @@ __global__ __launch_bounds__(256) void k_check(const unsigned *__restrict__ C, l
     if (bad) atomicOr(flag, bad);
 }
 
+// k_check on the device counts (n × ld), with its flags turned into RC_ERR_ARG messages that start with `who`
+static int32_t check_counts(rc_ctx *c, hipStream_t st, const char *who, const unsigned *dC, int64_t ld, int64_t m, int64_t n)
+{
+    DeviceBuffers B;
+    unsigned *d_flag;
+    HIPCHK(c, B.alloc(d_flag, 1));
+    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(unsigned), st));
+    k_check<<<dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8), (unsigned)n), 256, 0, st>>>(dC, ld, (int)n, (unsigned)m, d_flag);
+    HIPCHK(c, hipGetLastError());
+    unsigned flag = 0;
+    HIPCHK(c, hipMemcpyAsync(&flag, d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (flag & 1u) return fail(c, RC_ERR_ARG, "%s: the diagonal of the counts is not m = %lld everywhere", who, (long long)m);
+    if (flag & 2u) return fail(c, RC_ERR_ARG, "%s: the counts are not symmetric", who);
+    if (flag & 4u) return fail(c, RC_ERR_ARG, "%s: a count exceeds m = %lld", who, (long long)m);
+    return RC_OK;
+}
+
 template <int LOSS, int Q>
 __global__ __launch_bounds__(TPB) void k_search(Args A)
 {
@@ -373,18 +391,9 @@ static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, in
         }
     }
     // ---- the counts: symmetric, diagonal m, nothing above m
+    const int32_t crc = check_counts(c, st, "point search", dC, ld, m, n);
+    if (crc != RC_OK) return crc;
     DeviceBuffers B;
-    unsigned *d_flag;
-    HIPCHK(c, B.alloc(d_flag, 1));
-    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(unsigned), st));
-    k_check<<<dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8), (unsigned)n), 256, 0, st>>>(dC, ld, (int)n, (unsigned)m, d_flag);
-    HIPCHK(c, hipGetLastError());
-    unsigned flag = 0;
-    HIPCHK(c, hipMemcpyAsync(&flag, d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (flag & 1u) return fail(c, RC_ERR_ARG, "point search: the diagonal of the counts is not m = %lld everywhere", (long long)m);
-    if (flag & 2u) return fail(c, RC_ERR_ARG, "point search: the counts are not symmetric");
-    if (flag & 4u) return fail(c, RC_ERR_ARG, "point search: a count exceeds m = %lld", (long long)m);
 
     // ---- geometry
     const bool vi = loss == RC_PSM_VILB;

@@ -7827,3 +7827,4 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "pointsearch.inc.hip"
 #include "visearch.inc.hip"
 #include "samplecounts.inc.hip"
+#include "hclust.inc.hip"

@@ -323,6 +323,127 @@ def searchpointestimate(samples_or_counts=None, loss="VI", *, nruns: int = 16, m
     return res["labels"][res["best"]].copy(), info
 
 
+_LINKAGES = {"average": 0, "complete": 1, "single": 2}   # RC_HCLUST_AVERAGE, _COMPLETE, _SINGLE
+
+
+def _counts_input(samples_or_counts, numsamples, ctx):
+    """The three input forms of searchpointestimate as (samples matrix or None, counts or None, numsamples, n)."""
+    if ctx is not None:
+        if numsamples is None:
+            raise ValueError("numsamples is required with ctx=")
+        return None, None, int(numsamples), ctx.n
+    if hasattr(samples_or_counts, "clusts"):
+        S = _sample_matrix(samples_or_counts)
+        return S, None, S.shape[0], S.shape[1]
+    if samples_or_counts is None:
+        raise ValueError("need an MCMCResult, a count matrix or ctx=")
+    if numsamples is None:
+        raise ValueError("numsamples is required with a count matrix")
+    counts = np.asarray(samples_or_counts)
+    if counts.ndim != 2 or counts.shape[0] != counts.shape[1] or not np.issubdtype(counts.dtype, np.integer):
+        raise ValueError("counts must be a square matrix of integer counts")
+    return None, np.ascontiguousarray(counts, dtype=np.uint32), int(numsamples), counts.shape[0]
+
+
+def linkage_matrix(merges, numsamples: int, linkage: str = "average") -> np.ndarray:
+    """SciPy's (n−1)×4 linkage matrix of a merge sequence of hclust: SciPy's node numbering (leaves 0..n−1, step t makes
+    node n + t; the smaller id first), height = 1 − similarity/m (similarity: S_ab/(|a|·|b|) for average, M_ab otherwise),
+    size of the new cluster.  Host only."""
+    if linkage not in _LINKAGES:
+        raise ValueError("Invalid linkage specifier.")
+    n = len(merges) + 1
+    Z = np.zeros((n - 1, 4))
+    node, size = np.arange(n + 1), np.ones(n + 1, np.int64)           # by cluster name (1-based)
+    for t, g in enumerate(merges):
+        a, b = int(g["a"]), int(g["b"])
+        sim = int(g["s_ab"]) / (int(size[a]) * int(size[b])) if linkage == "average" else int(g["m_ab"])
+        Z[t] = (min(node[a], node[b]) - 1, max(node[a], node[b]) - 1, 1.0 - sim / int(numsamples), int(g["size"]))
+        node[a], size[a] = n + t + 1, int(g["size"])
+    return Z
+
+
+def leaf_order(Z) -> np.ndarray:
+    """The leaves of a linkage matrix from left to right (first child first) — scipy.cluster.hierarchy.leaves_list's order,
+    the one co-clustering heatmaps are drawn in.  0-based."""
+    n = len(Z) + 1
+    out, stack = [], [2 * n - 2] if n > 1 else [0]
+    while stack:
+        v = stack.pop()
+        if v < n:
+            out.append(v)
+        else:
+            stack += [int(Z[v - n, 1]), int(Z[v - n, 0])]
+    return np.array(out, np.int64)
+
+
+def hclust(samples_or_counts=None, linkage="average", *, numsamples=None, ctx=None, device: int = 0):
+    """Agglomerative clustering of the posterior co-clustering counts on the GPU (csrc/hclust.inc.hip): the classical
+    hierarchical point estimate's dendrogram (Medvedovic; mcclust's minbinder / mcclust.ext's minVI with method "avg" /
+    "comp").  Input forms as searchpointestimate: an MCMCResult (the counts are built on the device and stay there), an n×n
+    count matrix with numsamples, or ctx= with numsamples.  linkage: "average", "complete" or "single", on similarities —
+    the pair of largest average / minimum / maximum count merges first; ties go to the smallest cluster name (smallest
+    member), then the smallest partner; everything is exact integer arithmetic, so a run is reproducible bit for bit.
+    Returns a dict: merges (records a, b, size, m_ab, s_ab per step, names 1-based), binder_num (the exact Binder numerator
+    of the partition after t merges, t = 0..n−1), Z (linkage_matrix: usable with scipy.cluster.hierarchy.dendrogram),
+    order (leaf_order(Z)), kernel_ms.  There is no CPU fallback."""
+    if linkage not in _LINKAGES:
+        raise ValueError("Invalid linkage specifier.")
+    S, counts, m, _ = _counts_input(samples_or_counts, numsamples, ctx)
+    res = _lib.hclust(counts, m, _LINKAGES[linkage], device=device, ctx=ctx, samples=S)
+    Z = linkage_matrix(res["merges"], m, linkage)
+    out = dict(merges=res["merges"], binder_num=res["binder_num"], Z=Z, order=leaf_order(Z), kernel_ms=res["kernel_ms"])
+    if "counts_ms" in res:
+        out["counts_ms"] = res["counts_ms"]
+    return out
+
+
+def hclustpointestimate(samples_or_counts=None, loss="VI", linkage="average", *, maxK: int = 0, numsamples=None, ctx=None,
+                        device: int = 0):
+    """The hierarchical point estimate: hclust's dendrogram cut at the number of clusters K in 1..maxK of minimum expected
+    loss (ties: the smaller K).  loss: "binder" — from the exact curve binder_num — or "VI", the lower bound expectedloss(…,
+    "VI") evaluates, computed for every cut on the device.  maxK = 0 means ⌈n/8⌉.  Returns (clust, info): the cut
+    (sortlabels'd) and a dict with loss (per K = 1..maxK), K, merges, binder_num, kernel_ms, and loss_num (per K) for
+    "binder".  A deterministic start for searchpointestimate(init=[clust])."""
+    if loss not in _PSM_LOSSES:
+        raise ValueError("Invalid loss function specifier.")
+    if linkage not in _LINKAGES:
+        raise ValueError("Invalid linkage specifier.")
+    S, counts, m, n = _counts_input(samples_or_counts, numsamples, ctx)
+    maxK = int(maxK) if maxK else -(-n // 8)
+    if not 1 <= maxK <= n:
+        raise ValueError("maxK must lie in 1..n")
+    res = _lib.hclust(counts, m, _LINKAGES[linkage], maxcut=maxK if loss == "VI" else 0, device=device, ctx=ctx, samples=S)
+    info = dict(merges=res["merges"], binder_num=res["binder_num"], kernel_ms=res["kernel_ms"])
+    if loss == "binder":
+        pairs = n * (n - 1) // 2
+        info["loss_num"] = res["binder_num"][::-1][:maxK].copy()       # K clusters = n − K merges
+        info["loss"] = np.array([int(x) / (m * pairs) if pairs else 0.0 for x in info["loss_num"]])
+        K = int(np.argmin(info["loss_num"])) + 1
+    else:
+        info["loss"] = res["vilb"]
+        K = int(np.argmin(info["loss"])) + 1
+    info["K"] = K
+    return _lib.hclust_cut(res["merges"], n, K), info
+
+
+def expectedlosses(labellings, counts_or_samples=None, numsamples=None, loss="VI", *, ctx=None, device: int = 0):
+    """expectedloss for a batch of labellings (L×n, or one labelling) on the GPU: against an n×n count matrix with numsamples
+    (copied to the device once for the batch), against ctx= with numsamples (its device counts, in place, no copy), or against an
+    MCMCResult — its counts are built on the device, but come back to the host and go in again as a count matrix: there is no
+    samples entry point for this call, so hold the counts (posterior_counts) when evaluating several batches.
+    Returns (loss[L], num[L]): num is the exact Binder numerator (0 for "VI")."""
+    if loss not in _PSM_LOSSES:
+        raise ValueError("Invalid loss function specifier.")
+    labs = np.stack([_labels(c) for c in np.atleast_2d(np.asarray(labellings))])
+    S, counts, m, n = _counts_input(counts_or_samples, numsamples, ctx)
+    if labs.shape[1] != n:
+        raise ValueError("every labelling must have n entries")
+    if S is not None:
+        counts = _lib.samples_counts(S, device=device)[0]
+    out_loss, num, _ = _lib.psm_expected_loss(labs, counts, m, _PSM_LOSSES[loss], device=device, ctx=ctx)
+    return out_loss, num
+
+
 def lossmatrix(samples, loss: str = "VI", device: int = 0):
     """The symmetrised matrix of pairwise losses that getpointestimate(method="MPEL") searches (pointestimate.jl:49-56)
     and its column sums."""

@@ -611,6 +611,51 @@ int32_t rc_psm_expected_loss(int32_t device, const void *counts /* uint32_t n×n
 int32_t rc_psm_expected_loss_ctx(rc_ctx *ctx, int64_t numsamples, int32_t loss, int64_t L, const int64_t *labels /* L×n */,
                                  double *loss_out /* L */, int64_t *num_out /* L */, double *kernel_ms);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Predict: where do observations go that were not in the fit?  For every posterior sample s and every new point i, the
+ * Gibbs full conditional (src/mcmc.jl:192-252) of an (n+1)-th point whose own cluster is empty, and a draw from it.  New
+ * points are allocated independently of each other given a sample.  No context: errors through rc_last_error(NULL).
+ * DESIGN.md §8 "Predict".
+ *
+ * Quantisation, per new point: row i of Dnew is q_ij = llrint(ldexp(x_ij, eD_i)), eD_i = 62 − ex_i − ceil(log2 n) where
+ * max_j |x_ij| < 2^ex_i (frexp) — the rule of the context's matrices, applied to the row; the log row likewise with eL_i
+ * (logDnew_or_null = NULL: the host's libm log of Dnew).  A new point's result is therefore a pure function of its own
+ * row, the samples and the offsets, whichever other points share the call.
+ * Sums: for sample s with labels z, S_D[k] = Σ_j q_ij·[z_j = k] and S_L[k] likewise — exact int64.
+ * Scores: an existing cluster k of size s_k (nothing is removed: the new point is in no cluster)
+ *   A[s_k] + (log p_s + log(s_k − 1 + r_s)) + cL·S_L − (α + δ1 s_k)·log1p(S_D/β) + rep·(ζ + δ2 s_k)·log1p(S_D/γ),
+ * A and cL as for the sweep, the two log1p by the sweep's own routines; a new cluster
+ *   log(K_s + 1) + r_s·log(1 − p_s),  offered iff params->maxK == 0 || K_s < params->maxK.
+ * Draw: Gumbel-max.  The uniform of candidate label c (0 = the new cluster) is Philox4x32-10 with key
+ * (seed_lo, seed_hi ^ 0x50524544), counter (c, point_offset + i, s_lo, s_hi), s = sample_offset + sample index,
+ * u = (top 52 bits + ½)·2^-52.  Ties go to the smaller label, the new cluster last.
+ *
+ * labels_out[s][i]: the drawn label in sample s's own label names, 0 = a cluster of its own.  map_out (may be NULL): the
+ * argmax of the noise-free scores, same tie rule.  scores_out (may be NULL) [s][i][t]: t < K_s the noise-free score of the
+ * t-th smallest label of sample s, column Kmax the new cluster (−inf when not offered), NaN between.  sums_out (may be
+ * NULL) [s][i][t][0..1]: (S_D, S_L) of the same candidates (0 beyond K_s).  Kmax is read only when one of the two is given
+ * and must then be >= every K_s.  eD_out, eL_out (may be NULL): the exponents of every new point.  kernel_ms (may be NULL):
+ * device time of the call's kernels.
+ *
+ * Errors, all before any device work.  RC_ERR_ARG: a NULL required pointer; n, q or m < 1; a label outside 1..n; r <= 0 or
+ * not finite; p outside (0, 1); params that rc_set_params would reject; Kmax below a K_s; a device that is not there.
+ * RC_ERR_DOMAIN: an entry of Dnew that is not finite or not > 0, a given log that is not finite.  RC_ERR_CAPACITY (checked
+ * first, before any array is read): n > 32767 or m·n >= 2^31.  q is unbounded: the host walks the new points, and the
+ * samples if need be, in chunks of a device workspace of about 1 GiB.  RC_PREDICT_ROWS_GLOBAL=1 in the environment (read at
+ * every call) makes the sums gather from the rows in global memory instead of LDS, as n > 10240 does, and
+ * RC_PREDICT_WORKSPACE_KIB=<k> shrinks the workspace so that small calls are chunked — the same results either way; for tests.
+ * ------------------------------------------------------------------------------------------------------------- */
+int32_t rc_predict(int32_t device, int64_t n, int64_t q,
+                   const double *Dnew /* q×n row-major: new point i to training point j */,
+                   const double *logDnew_or_null /* q×n; NULL: host libm log() of Dnew */,
+                   int64_t m, const int64_t *samples /* m×n, labels 1..n */,
+                   const double *r /* m */, const double *p /* m */, const rc_params *params,
+                   uint64_t seed, uint64_t sample_offset, uint64_t point_offset,
+                   int64_t *labels_out /* m×q */, int64_t *map_out /* m×q or NULL */,
+                   int64_t Kmax, double *scores_out /* m×q×(Kmax+1) or NULL */,
+                   int64_t *sums_out /* m×q×Kmax×2 or NULL */,
+                   int32_t *eD_out /* q or NULL */, int32_t *eL_out /* q or NULL */, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -571,4 +571,34 @@ end
 
 export hclustpointestimate
 
+"""
+    predict(HIPBackend(), result, Dnew; seed = 0) -> (labels, map_labels)
+
+Allocate observations that were not in the fit to the clusters of every sample of `result` on the GPU (rc_predict): under
+one sample, the Gibbs full conditional of an (n+1)-th point whose own cluster is empty, and a draw from it.  `Dnew` is q×n,
+the distances of every new observation to every training observation (finite and positive).  `labels[i, s]` is the label new
+point `i` drew under sample `s`, in that sample's own label names, `0` for a cluster of its own; `map_labels` holds the most
+probable label instead.  New observations are allocated independently of each other given a sample.
+"""
+function predict(b::HIPBackend, result, Dnew::Matrix{Float64}; seed = 0)
+    samples = samplematrix(result)
+    n, m = size(samples)
+    q = size(Dnew, 1)
+    size(Dnew, 2) == n || throw(ArgumentError("Dnew must have one column per training observation."))
+    rows = permutedims(Dnew)                                      # n×q column-major = q×n row-major
+    r = Vector{Float64}(result.r); p = Vector{Float64}(result.p)
+    labels = Matrix{Int64}(undef, q, m)                           # column s = sample s: row-major m×q for the library
+    maplabels = Matrix{Int64}(undef, q, m)
+    rc = ccall((:rc_predict, LIB), Int32,
+               (Int32, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{RcParams},
+                UInt64, UInt64, UInt64, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Cdouble}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32},
+                Ptr{Cdouble}),
+               b.device, n, q, rows, C_NULL, m, samples, r, p, Ref(RcParams(result.params)), seed % UInt64, UInt64(0),
+               UInt64(0), labels, maplabels, 0, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return (labels, maplabels)
+end
+
+export predict
+
 end # module

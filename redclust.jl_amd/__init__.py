@@ -15,3 +15,4 @@ from .pointestimate import (getpointestimate, lossmatrix, binderloss, infodist, 
                             summarise, searchpointestimate, expectedloss, expectedvi, expectedid, cocluster_counts,
                             posterior_counts, posterior_coclustering, hclust, hclustpointestimate, expectedlosses,
                             linkage_matrix, leaf_order)
+from .predict import predict, Prediction  # noqa: F401

@@ -87,7 +87,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
             os.path.join(CSRC, "chain.inc.hip"), os.path.join(CSRC, "chains.inc.hip"), os.path.join(CSRC, "samplek.inc.hip"),
             os.path.join(CSRC, "mixture.inc.hip"), os.path.join(CSRC, "kmeans.inc.hip"),
             os.path.join(CSRC, "pointsearch.inc.hip"), os.path.join(CSRC, "visearch.inc.hip"),
-            os.path.join(CSRC, "samplecounts.inc.hip"), os.path.join(CSRC, "hclust.inc.hip"), HEADER]
+            os.path.join(CSRC, "samplecounts.inc.hip"), os.path.join(CSRC, "hclust.inc.hip"), os.path.join(CSRC, "predict.inc.hip"), HEADER]
     if not force and os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(s) for s in srcs):
         return SO
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-o", SO, srcs[0]]
@@ -207,6 +207,9 @@ SIGNATURES = {
                                          C.c_void_p, C.POINTER(C.c_double)]),
     "rc_psm_expected_loss_ctx": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.POINTER(C.c_double)]),
+    "rc_predict": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.POINTER(RcParams), C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "rc_layout_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rc_event_overhead_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "rc_kernel_timing": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -889,6 +892,52 @@ def psm_expected_loss(labels, counts, numsamples: int, loss: int, device: int = 
     if rc != RC_OK:
         raise _error(rc, L.rc_last_error(ctx.h if ctx is not None else None).decode())
     return loss_out[:nl], num_out[:nl], float(ms.value)
+
+
+def predict(Dnew, samples, r, p, params: dict, seed: int = 0, sample_offset: int = 0, point_offset: int = 0, logDnew=None,
+            want_map: bool = True, Kmax: int = 0, want_scores: bool = False, want_sums: bool = False, device: int = 0) -> dict:
+    """rc_predict: labels (m×q, 0 = a cluster of its own), map (or None), eD / eL (q), kernel_ms and, when asked for with Kmax,
+    scores (m×q×(Kmax+1)) and sums (m×q×Kmax×2) for the q×n distances Dnew of new points to the training points and an m×n
+    label matrix with one r and p per sample."""
+    L = lib()
+    D = np.ascontiguousarray(Dnew, dtype=np.float64)
+    S = np.ascontiguousarray(samples, dtype=np.int64)
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    if D.ndim != 2 or S.ndim != 2 or D.shape[1] != S.shape[1]:
+        raise ValueError("Dnew must be q×n and samples m×n")
+    q, n = D.shape
+    m = S.shape[0]
+    if r.shape != (m,) or p.shape != (m,):
+        raise ValueError("r and p must hold one value per sample")
+    lp = None
+    if logDnew is not None:
+        logDnew = np.ascontiguousarray(logDnew, dtype=np.float64)
+        if logDnew.shape != D.shape:
+            raise ValueError("logDnew must have Dnew's shape")
+        lp = logDnew.ctypes.data
+    g = params.get
+    prm = RcParams(g("delta1"), g("delta2"), g("alpha"), g("beta"), g("zeta"), g("gamma"), g("eta", 1.0), g("sigma", 1.0),
+                   g("u", 1.0), g("v", 1.0), int(g("maxK", 0)), int(bool(g("repulsion", True))))
+    labels = np.zeros((max(m, 1), max(q, 1)), np.int64)
+    mp = np.zeros_like(labels) if want_map else None
+    sc = np.zeros((max(m, 1), max(q, 1), int(Kmax) + 1)) if want_scores else None
+    sm = np.zeros((max(m, 1), max(q, 1), max(int(Kmax), 1), 2), np.int64) if want_sums else None
+    eD, eL = np.zeros(max(q, 1), np.int32), np.zeros(max(q, 1), np.int32)
+    ms = C.c_double()
+    M64 = 0xFFFFFFFFFFFFFFFF
+    rc = L.rc_predict(int(device), n, q, D.ctypes.data, lp, m, S.ctypes.data, r.ctypes.data, p.ctypes.data, C.byref(prm),
+                      int(seed) & M64, int(sample_offset) & M64, int(point_offset) & M64, labels.ctypes.data,
+                      None if mp is None else mp.ctypes.data, int(Kmax), None if sc is None else sc.ctypes.data,
+                      None if sm is None else sm.ctypes.data, eD.ctypes.data, eL.ctypes.data, C.byref(ms))
+    if rc != RC_OK:
+        raise _error(rc, L.rc_last_error(None).decode())
+    out = dict(labels=labels[:m, :q], map=None if mp is None else mp[:m, :q], eD=eD[:q], eL=eL[:q], kernel_ms=float(ms.value))
+    if want_scores:
+        out["scores"] = sc[:m, :q]
+    if want_sums:
+        out["sums"] = sm[:m, :q, :int(Kmax)]
+    return out
 
 
 def sample_k(n: int, r, p, seed: int = 0, device: int = 0):

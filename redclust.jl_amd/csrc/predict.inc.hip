@@ -1,0 +1,457 @@
+// Predict: allocate observations that were not in the fit to the clusters of every posterior sample, on the device.  Under
+// one sample the allocation of a new observation is the Gibbs full conditional (src/mcmc.jl:192-252) of an (n+1)-th point
+// whose own cluster is empty: the stable score of DESIGN.md §4 on the sums of the new point's distances to the n training
+// points, grouped by the sample's labels, and a Gumbel-max draw.  New points are conditionally independent given a sample, so
+// every (sample, new point) pair is its own problem.  DESIGN.md §8 "Predict"; the contract is in include/redclust_hip.h.
+// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, check_params, size_table, flog_table,
+// quant_exponent, rc_philox, rc_flog / rc_flog1p / rc_gumbel and the holders and select_device of hostutil.inc.hip).
+//
+// Fixed point, per new point: its row of D and its row of logD are quantised with exponents of their own (quant_exponent on
+// the row), so a point's result does not depend on which other points share the call.  Every sum is an exact int64.
+//
+// Host, per sample: the labels are compacted to slots 0..K-1 in ascending label order and the training points are sorted by
+// slot (counting sort).  The sorted order is stored transposed, perm[j][s] (u16: point index, bit 15 set on the last point
+// of its slot), so 64 lanes that own 64 consecutive samples read 128 contiguous bytes per step.  Everything of a score that
+// depends only on (sample, slot) — A[size] + (log p + log(size - 1 + r)) — and the new cluster's score are computed there
+// too, once, instead of once per new point.
+//
+// k_predict_sums (phase 1, the q·m·n integer adds): one workgroup per new point.  Its row is staged in LDS as interleaved
+// (Dq, Lq) pairs, 16 bytes per training point, so one 128-bit LDS gather fetches both addends; rows beyond the LDS (n > 10240)
+// or RC_PREDICT_ROWS_GLOBAL=1 gather from global memory instead — the same integers.  A lane owns (sample, part of the sorted
+// order), adds into two int64 registers and at every slot boundary flushes them to the (point, sample, slot) sums: a plain
+// store when a sample is one part, 64-bit integer atomic adds when the workgroup has more lanes than samples and cuts every
+// sample into parts (exact in any order).  No scoring here: at a boundary it would run one lane at a time.
+// k_predict_draw (phase 2): one wave per (sample, new point), one lane per candidate: score, Philox, noise; then a wave
+// argmax whose key (value, then smaller label, the new cluster last) gives the tie rule whatever the reduction order.
+
+namespace prd {
+
+constexpr int64_t NMAX = 32767;                 // u16 point indices with bit 15 free for the boundary mark
+constexpr int TPB1 = 1024, TPB2 = 256;
+constexpr int64_t LDS_ROW_MAX_N = 160 * 1024 / 16;
+constexpr size_t WORKSPACE = (size_t)1 << 30;   // device bytes per chunk that scale with the number of new points
+constexpr size_t PERM_BYTES = (size_t)1 << 29;  // ... and the most the sorted orders of one chunk of samples take
+constexpr unsigned TAG = 0x50524544u;           // "PRED": key (seed_lo, seed_hi ^ TAG), counter (label, point, sample_lo, sample_hi)
+constexpr unsigned KEY_NEW = 0x7FFFFFFFu, KEY_NONE = 0xFFFFFFFFu;
+
+template <bool ATOMIC> __device__ __forceinline__ void flush(ll2 *o, long long sd, long long sl)
+{
+    if (ATOMIC) {
+        atomicAdd((u64 *)o, (u64)sd);
+        atomicAdd((u64 *)o + 1, (u64)sl);
+    } else {
+        ll2 v; v.x = sd; v.y = sl;
+        *o = v;
+    }
+}
+
+// rows: [points][n] (Dq, Lq); perm: [n][ms_pad]; koff: [ms] first slot of every sample; startslot: [parts][ms_pad] slot of a
+// part's first position (ATOMIC only); sums: [points][ktot].  Grid: one block per point.
+template <bool LDSROW, bool ATOMIC>
+__global__ __launch_bounds__(TPB1) void k_predict_sums(const ll2 *__restrict__ rows, int n, const unsigned short *__restrict__ perm, int ms, int ms_pad,
+                                                       int parts, const int *__restrict__ startslot, const long long *__restrict__ koff, long long ktot,
+                                                       ll2 *__restrict__ sums)
+{
+    extern __shared__ __align__(16) unsigned char prd_lds[];
+    const ll2 *grow = rows + (size_t)blockIdx.x * (size_t)n;
+    const ll2 *row = grow;
+    if (LDSROW) {
+        ll2 *l = reinterpret_cast<ll2 *>(prd_lds);
+        for (int j = threadIdx.x; j < n; j += blockDim.x) l[j] = grow[j];
+        __syncthreads();
+        row = l;
+    }
+    ll2 *out = sums + (size_t)blockIdx.x * (size_t)ktot;
+    for (int w = threadIdx.x; w < ms_pad * parts; w += blockDim.x) {
+        const int part = w / ms_pad, s = w - part * ms_pad;
+        if (s >= ms) continue;
+        const int j0 = (int)((long long)part * n / parts), j1 = (int)((long long)(part + 1) * n / parts);
+        ll2 *o = out + koff[s] + (ATOMIC ? startslot[w] : 0);
+        const unsigned short *pp = perm + (size_t)j0 * (size_t)ms_pad + s;
+        long long sd = 0, sl = 0;
+        unsigned e = 0x8000u;
+        // Batches of NB steps: the NB entries of the sorted order are requested one batch ahead and the NB row gathers are
+        // issued together, so a lane waits once per batch for either memory, not once per step — a flush is a branch, and
+        // across a branch the compiler keeps no load in flight.  (The prefetch past the part's end re-reads its last entry.)
+        constexpr int NB = 8;
+        unsigned en[NB];
+        int j = j0;
+        if (j + NB <= j1) {
+#pragma unroll
+            for (int u = 0; u < NB; ++u) en[u] = pp[(size_t)u * ms_pad];
+        }
+        for (; j + NB <= j1; j += NB) {
+            unsigned ec[NB];
+            ll2 v[NB];
+#pragma unroll
+            for (int u = 0; u < NB; ++u) ec[u] = en[u];
+#pragma unroll
+            for (int u = 0; u < NB; ++u) en[u] = pp[(size_t)(min(j + NB + u, j1 - 1) - j) * ms_pad];
+#pragma unroll
+            for (int u = 0; u < NB; ++u) v[u] = row[ec[u] & 0x7FFFu];
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                sd += v[u].x; sl += v[u].y;
+                if (ec[u] & 0x8000u) { flush<ATOMIC>(o, sd, sl); ++o; sd = 0; sl = 0; }
+            }
+            e = ec[NB - 1];
+            pp += (size_t)NB * ms_pad;
+        }
+        for (; j < j1; ++j, pp += ms_pad) {
+            e = *pp;
+            const ll2 v = row[e & 0x7FFFu];
+            sd += v.x; sl += v.y;
+            if (e & 0x8000u) { flush<ATOMIC>(o, sd, sl); ++o; sd = 0; sl = 0; }
+        }
+        if (ATOMIC && !(e & 0x8000u)) flush<ATOMIC>(o, sd, sl);   // the part ends inside a slot
+    }
+}
+
+struct DrawArgs {
+    int ms, npts, Kmax;                     // Kmax: columns of the optional outputs (0 when neither is asked for)
+    long long ktot;
+    const ll2 *sums;                        // [npts][ktot]
+    const long long *koff;                  // [ms]
+    const int *K;                           // [ms]
+    const int2 *szlab;                      // [ktot] (size, label)
+    const double *base;                     // [ktot] A[size] + (log p + log(size - 1 + r))
+    const double *newscore;                 // [ms] log(K + 1) + r·log(1 - p), or -inf when no new cluster is offered
+    const double *scD, *scL;                // [npts] 2^-eD, 2^-eL
+    const double2 *flt;
+    double alpha, beta, zeta, gamma, delta1, delta2, cL;
+    int repulsion;
+    unsigned k0, k1;
+    u64 sample0, point0;                    // counters of sample 0 and point 0 of this launch
+    long long *labels, *map;                // [ms][npts]
+    double *scores;                         // [ms][npts][Kmax + 1] or null
+    long long *sums_out;                    // [ms][npts][Kmax][2] or null
+};
+
+__device__ __forceinline__ bool better(double v, unsigned key, double bv, unsigned bkey)
+{
+    return key != KEY_NONE && (bkey == KEY_NONE || v > bv || (v == bv && key < bkey));
+}
+
+__global__ __launch_bounds__(TPB2) void k_predict_draw(const DrawArgs a)
+{
+    const long long pair = (long long)blockIdx.x * (TPB2 / 64) + (threadIdx.x >> 6);
+    if (pair >= (long long)a.ms * a.npts) return;
+    const int lane = threadIdx.x & 63;
+    const int i = (int)(pair / a.ms), s = (int)(pair - (long long)i * a.ms);
+    const int K = a.K[s];
+    const long long k0 = a.koff[s];
+    const ll2 *S = a.sums + (size_t)i * (size_t)a.ktot + k0;
+    const double scD = a.scD[i], scL = a.scL[i], vnew = a.newscore[s];
+    const u64 sc = a.sample0 + (u64)s;
+    const unsigned pc = (unsigned)(a.point0 + (u64)i), s_lo = (unsigned)sc, s_hi = (unsigned)(sc >> 32);
+    const size_t o = (size_t)s * a.npts + i;
+    double bv = 0.0, bm = 0.0;
+    unsigned bvk = KEY_NONE, bmk = KEY_NONE;
+    const int T = a.Kmax > K ? a.Kmax : K;          // columns K..Kmax-1 of the optional outputs are filled by the same loop
+    for (int t = lane; t <= T; t += 64) {
+        double v;
+        unsigned key;
+        if (t < K) {
+            const ll2 x = S[t];
+            const int2 zl = a.szlab[k0 + t];
+            const double sz = (double)zl.x;
+            const double SDr = (double)x.x * scD, SLr = (double)x.y * scL;
+            double lik = a.cL * SLr - (a.alpha + a.delta1 * sz) * rc_flog1p(SDr / a.beta, a.flt);
+            if (a.repulsion) lik += (a.zeta + a.delta2 * sz) * rc_flog1p(SDr / a.gamma, a.flt);
+            v = a.base[k0 + t] + lik;
+            key = (unsigned)zl.y;
+            if (a.scores) a.scores[o * (size_t)(a.Kmax + 1) + t] = v;
+            if (a.sums_out) { a.sums_out[(o * (size_t)a.Kmax + t) * 2] = x.x; a.sums_out[(o * (size_t)a.Kmax + t) * 2 + 1] = x.y; }
+        } else if (t < T) {
+            if (a.scores) a.scores[o * (size_t)(a.Kmax + 1) + t] = __longlong_as_double(0x7FF8000000000000ll);
+            if (a.sums_out) { a.sums_out[(o * (size_t)a.Kmax + t) * 2] = 0; a.sums_out[(o * (size_t)a.Kmax + t) * 2 + 1] = 0; }
+            continue;
+        } else {
+            if (a.scores) a.scores[o * (size_t)(a.Kmax + 1) + a.Kmax] = vnew;
+            if (!(vnew > -1.79769313486231570e308)) continue;       // not offered
+            v = vnew;
+            key = KEY_NEW;
+        }
+        if (better(v, key, bm, bmk)) { bm = v; bmk = key; }
+        const double g = v + rc_gumbel(rc_unit52(rc_philox(key == KEY_NEW ? 0u : key, pc, s_lo, s_hi, a.k0, a.k1)), a.flt);
+        if (better(g, key, bv, bvk)) { bv = g; bvk = key; }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double ov = __shfl_xor(bv, off), om = __shfl_xor(bm, off);
+        const unsigned ovk = __shfl_xor(bvk, off), omk = __shfl_xor(bmk, off);
+        if (better(ov, ovk, bv, bvk)) { bv = ov; bvk = ovk; }
+        if (better(om, omk, bm, bmk)) { bm = om; bmk = omk; }
+    }
+    if (lane == 0) {
+        a.labels[o] = bvk == KEY_NEW ? 0 : (long long)bvk;
+        a.map[o] = bmk == KEY_NEW ? 0 : (long long)bmk;
+    }
+}
+
+// what the caller passed, after the checks
+struct Call {
+    int64_t n, q, m, Kmax;
+    const double *Dnew, *logDnew;
+    const int64_t *samples;
+    const double *r, *p;
+    const rc_params *P;
+    uint64_t seed, sample_offset, point_offset;
+    int64_t *labels_out, *map_out, *sums_out;
+    double *scores_out;
+    const int *eD, *eL;              // [q]
+    const int *K;                    // [m]
+    const double *A;                 // [n + 1]
+    const double2 *d_flt;
+    bool rows_global;
+};
+
+// samples s0 .. s0 + ms - 1 against every new point, the points in chunks of at most qc.  ms_acc: device milliseconds, added to.
+static int32_t run_samples(const char *who, const Call &c, int64_t s0, int64_t ms, int64_t qc, double &ms_acc)
+{
+    const int64_t n = c.n;
+    const int ms_pad = (int)((ms + 63) / 64 * 64);
+    const int parts = ms_pad >= TPB1 ? 1 : (int)std::min<int64_t>(TPB1 / ms_pad, n);
+    const bool want_tab = c.scores_out || c.sums_out;
+    const int Kcols = want_tab ? (int)c.Kmax : 0;
+    std::vector<unsigned short> perm;
+    std::vector<int> startslot, partat, cnt, slot_of_label, pos, Ks;
+    std::vector<long long> koff;
+    std::vector<int2> szlab;
+    std::vector<double> base, newscore;
+    long long ktot = 0;
+    try {
+        perm.assign((size_t)n * ms_pad, 0);
+        startslot.assign((size_t)parts * ms_pad, 0);
+        partat.assign((size_t)n, -1);
+        cnt.assign((size_t)n + 1, 0); slot_of_label.assign((size_t)n + 1, 0); pos.assign((size_t)n, 0);
+        koff.resize((size_t)ms); newscore.resize((size_t)ms); Ks.resize((size_t)ms);
+        for (int64_t s = 0; s < ms; ++s) ktot += c.K[s0 + s];
+        szlab.resize((size_t)ktot); base.resize((size_t)ktot);
+    } catch (const std::bad_alloc &) { return fail(nullptr, RC_ERR_OOM, "%s: no host memory for the sorted orders of %lld samples", who, (long long)ms); }
+    for (int p = 0; p < parts; ++p) partat[(size_t)((long long)p * n / parts)] = p;
+    long long k0 = 0;
+    for (int64_t s = 0; s < ms; ++s) {
+        const int64_t *z = c.samples + (size_t)(s0 + s) * n;
+        const double r = c.r[s0 + s], p = c.p[s0 + s], logp = std::log(p);
+        for (int64_t j = 0; j < n; ++j) cnt[(size_t)z[j]]++;
+        int K = 0, at = 0;
+        for (int64_t l = 1; l <= n; ++l) {
+            const int sz = cnt[(size_t)l];
+            if (!sz) continue;
+            slot_of_label[(size_t)l] = K;
+            pos[(size_t)K] = at; at += sz;
+            szlab[(size_t)(k0 + K)] = make_int2(sz, (int)l);
+            base[(size_t)(k0 + K)] = c.A[sz] + (logp + std::log((double)sz - 1.0 + r));
+            cnt[(size_t)l] = 0;
+            ++K;
+        }
+        koff[(size_t)s] = k0; Ks[(size_t)s] = K;
+        newscore[(size_t)s] = (c.P->maxK == 0 || K < c.P->maxK) ? std::log((double)(K + 1)) + r * std::log(1 - p) : -INFINITY;
+        for (int64_t j = 0; j < n; ++j) {
+            const int t = slot_of_label[(size_t)z[j]];
+            const int at_ = pos[(size_t)t]++;
+            perm[(size_t)at_ * ms_pad + s] = (unsigned short)j;
+            if (partat[(size_t)at_] >= 0) startslot[(size_t)partat[(size_t)at_] * ms_pad + s] = t;
+        }
+        // after the fill pos[t] is one past slot t's last position: mark those
+        for (int t = 0; t < K; ++t) perm[(size_t)(pos[(size_t)t] - 1) * ms_pad + s] |= 0x8000u;
+        k0 += K;
+    }
+
+    DeviceBuffers B;
+    unsigned short *d_perm; int *d_startslot, *d_K; long long *d_koff; int2 *d_szlab; double *d_base, *d_newscore, *d_scD, *d_scL;
+    ll2 *d_rows, *d_sums; long long *d_labels, *d_map, *d_sums_out = nullptr; double *d_scores = nullptr;
+    HIPCHK(nullptr, B.alloc(d_perm, perm.size()));
+    HIPCHK(nullptr, B.alloc(d_startslot, startslot.size()));
+    HIPCHK(nullptr, B.alloc(d_K, (size_t)ms));
+    HIPCHK(nullptr, B.alloc(d_koff, (size_t)ms));
+    HIPCHK(nullptr, B.alloc(d_szlab, (size_t)ktot));
+    HIPCHK(nullptr, B.alloc(d_base, (size_t)ktot));
+    HIPCHK(nullptr, B.alloc(d_newscore, (size_t)ms));
+    HIPCHK(nullptr, B.alloc(d_scD, (size_t)qc));
+    HIPCHK(nullptr, B.alloc(d_scL, (size_t)qc));
+    HIPCHK(nullptr, B.alloc(d_rows, (size_t)qc * n));
+    HIPCHK(nullptr, B.alloc(d_sums, (size_t)qc * ktot));
+    HIPCHK(nullptr, B.alloc(d_labels, (size_t)qc * ms));
+    HIPCHK(nullptr, B.alloc(d_map, (size_t)qc * ms));
+    if (c.scores_out) HIPCHK(nullptr, B.alloc(d_scores, (size_t)qc * ms * (Kcols + 1)));
+    if (c.sums_out) HIPCHK(nullptr, B.alloc(d_sums_out, (size_t)qc * ms * std::max(Kcols, 1) * 2));
+    HIPCHK(nullptr, hipMemcpy(d_perm, perm.data(), perm.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_startslot, startslot.data(), startslot.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_K, Ks.data(), (size_t)ms * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_koff, koff.data(), (size_t)ms * sizeof(long long), hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_szlab, szlab.data(), (size_t)ktot * sizeof(int2), hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_base, base.data(), (size_t)ktot * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(nullptr, hipMemcpy(d_newscore, newscore.data(), (size_t)ms * sizeof(double), hipMemcpyHostToDevice));
+
+    const bool ldsrow = !c.rows_global && n <= LDS_ROW_MAX_N;
+    const size_t lds = ldsrow ? (size_t)n * sizeof(ll2) : 0;
+    auto kern = ldsrow ? (parts > 1 ? k_predict_sums<true, true> : k_predict_sums<true, false>)
+                       : (parts > 1 ? k_predict_sums<false, true> : k_predict_sums<false, false>);
+    if (lds > 64 * 1024) HIPCHK(nullptr, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+
+    std::vector<ll2> rows;
+    std::vector<long long> h_lab, h_tab;
+    std::vector<double> h_sc, scD, scL;
+    try {
+        rows.resize((size_t)qc * n); h_lab.resize((size_t)qc * ms); scD.resize((size_t)qc); scL.resize((size_t)qc);
+        if (c.scores_out) h_sc.resize((size_t)qc * ms * (Kcols + 1));
+        if (c.sums_out) h_tab.resize((size_t)qc * ms * std::max(Kcols, 1) * 2);
+    } catch (const std::bad_alloc &) { return fail(nullptr, RC_ERR_OOM, "%s: no host memory for a chunk of %lld new points", who, (long long)qc); }
+    TimingEvents ev;
+    HIPCHK(nullptr, ev.create());
+    const rc_params &P = *c.P;
+    for (int64_t i0 = 0; i0 < c.q; i0 += qc) {
+        const int64_t np = std::min(qc, c.q - i0);
+        for (int64_t i = 0; i < np; ++i) {
+            const double *x = c.Dnew + (size_t)(i0 + i) * n, *lx = c.logDnew ? c.logDnew + (size_t)(i0 + i) * n : nullptr;
+            const int eD = c.eD[i0 + i], eL = c.eL[i0 + i];
+            ll2 *dst = rows.data() + (size_t)i * n;
+            for (int64_t j = 0; j < n; ++j) {
+                dst[j].x = std::llrint(std::ldexp(x[j], eD));
+                dst[j].y = std::llrint(std::ldexp(lx ? lx[j] : std::log(x[j]), eL));
+            }
+            scD[(size_t)i] = std::ldexp(1.0, -eD); scL[(size_t)i] = std::ldexp(1.0, -eL);
+        }
+        HIPCHK(nullptr, hipMemcpy(d_rows, rows.data(), (size_t)np * n * sizeof(ll2), hipMemcpyHostToDevice));
+        HIPCHK(nullptr, hipMemcpy(d_scD, scD.data(), (size_t)np * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(nullptr, hipMemcpy(d_scL, scL.data(), (size_t)np * sizeof(double), hipMemcpyHostToDevice));
+        DrawArgs a{};
+        a.ms = (int)ms; a.npts = (int)np; a.Kmax = Kcols; a.ktot = ktot; a.sums = d_sums; a.koff = d_koff; a.K = d_K; a.szlab = d_szlab;
+        a.base = d_base; a.newscore = d_newscore; a.scD = d_scD; a.scL = d_scL; a.flt = c.d_flt;
+        a.alpha = P.alpha; a.beta = P.beta; a.zeta = P.zeta; a.gamma = P.gamma; a.delta1 = P.delta1; a.delta2 = P.delta2;
+        a.cL = (P.delta1 - 1.0) - (P.repulsion ? (P.delta2 - 1.0) : 0.0);
+        a.repulsion = P.repulsion ? 1 : 0;
+        a.k0 = (unsigned)c.seed; a.k1 = (unsigned)(c.seed >> 32) ^ TAG;
+        a.sample0 = c.sample_offset + (uint64_t)s0; a.point0 = c.point_offset + (uint64_t)i0;
+        a.labels = d_labels; a.map = d_map; a.scores = d_scores; a.sums_out = d_sums_out;
+        HIPCHK(nullptr, hipEventRecord(ev.e0, 0));
+        if (parts > 1) HIPCHK(nullptr, hipMemsetAsync(d_sums, 0, (size_t)np * ktot * sizeof(ll2), 0));   // the parts add into zeros
+        kern<<<(unsigned)np, TPB1, lds, 0>>>(d_rows, (int)n, d_perm, (int)ms, ms_pad, parts, d_startslot, d_koff, ktot, d_sums);
+        HIPCHK(nullptr, hipGetLastError());
+        k_predict_draw<<<(unsigned)(((size_t)np * ms + TPB2 / 64 - 1) / (TPB2 / 64)), TPB2, 0, 0>>>(a);
+        HIPCHK(nullptr, hipGetLastError());
+        HIPCHK(nullptr, hipEventRecord(ev.e1, 0));
+        HIPCHK(nullptr, hipEventSynchronize(ev.e1));
+        float t = 0;
+        HIPCHK(nullptr, hipEventElapsedTime(&t, ev.e0, ev.e1));
+        ms_acc += t;
+        // device [ms][np][..] into the caller's [m][q][..]
+        for (int pass = 0; pass < 2; ++pass) {
+            int64_t *dst = pass ? c.map_out : c.labels_out;
+            if (!dst) continue;
+            HIPCHK(nullptr, hipMemcpy(h_lab.data(), pass ? d_map : d_labels, (size_t)np * ms * sizeof(long long), hipMemcpyDeviceToHost));
+            for (int64_t s = 0; s < ms; ++s) memcpy(dst + (size_t)(s0 + s) * c.q + i0, h_lab.data() + (size_t)s * np, (size_t)np * sizeof(int64_t));
+        }
+        if (c.scores_out) {
+            const size_t w = (size_t)Kcols + 1;
+            HIPCHK(nullptr, hipMemcpy(h_sc.data(), d_scores, (size_t)np * ms * w * sizeof(double), hipMemcpyDeviceToHost));
+            for (int64_t s = 0; s < ms; ++s) memcpy(c.scores_out + ((size_t)(s0 + s) * c.q + i0) * w, h_sc.data() + (size_t)s * np * w, (size_t)np * w * sizeof(double));
+        }
+        if (c.sums_out && Kcols > 0) {
+            const size_t w = (size_t)Kcols * 2;
+            HIPCHK(nullptr, hipMemcpy(h_tab.data(), d_sums_out, (size_t)np * ms * w * sizeof(long long), hipMemcpyDeviceToHost));
+            for (int64_t s = 0; s < ms; ++s) memcpy(c.sums_out + ((size_t)(s0 + s) * c.q + i0) * w, h_tab.data() + (size_t)s * np * w, (size_t)np * w * sizeof(int64_t));
+        }
+    }
+    return RC_OK;
+}
+
+}  // namespace prd
+
+extern "C" int32_t rc_predict(int32_t device, int64_t n, int64_t q, const double *Dnew, const double *logDnew_or_null, int64_t m,
+                              const int64_t *samples, const double *r, const double *p, const rc_params *params, uint64_t seed,
+                              uint64_t sample_offset, uint64_t point_offset, int64_t *labels_out, int64_t *map_out, int64_t Kmax,
+                              double *scores_out, int64_t *sums_out, int32_t *eD_out, int32_t *eL_out, double *kernel_ms)
+{
+    const char *who = "rc_predict";
+    if (!Dnew || !samples || !r || !p || !params || !labels_out) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
+    if (n < 1 || q < 1 || m < 1) return fail(nullptr, RC_ERR_ARG, "%s: need n >= 1, q >= 1 and m >= 1 (got n=%lld q=%lld m=%lld)", who, (long long)n, (long long)q, (long long)m);
+    if (n > prd::NMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %lld training points whose indices fit 15 bits", who, (long long)n, (long long)prd::NMAX);
+    if (m >= ((int64_t)1 << 31) / n + (((int64_t)1 << 31) % n != 0)) return fail(nullptr, RC_ERR_CAPACITY, "%s: m·n = %lld·%lld is not below 2^31", who, (long long)m, (long long)n);
+    int32_t rc = check_params(nullptr, who, params);
+    if (rc != RC_OK) return rc;
+    for (int64_t s = 0; s < m; ++s) {
+        if (!(r[s] > 0 && r[s] <= 1.79769313486231570e308)) return fail(nullptr, RC_ERR_ARG, "%s: r of sample %lld must be positive and finite", who, (long long)s + 1);
+        if (!(p[s] > 0 && p[s] < 1)) return fail(nullptr, RC_ERR_ARG, "%s: p of sample %lld must lie in (0, 1)", who, (long long)s + 1);
+    }
+    const bool want_tab = scores_out || sums_out;
+    std::vector<int> K, eD, eL, seen;
+    std::vector<double> A;
+    try { K.assign((size_t)m, 0); eD.resize((size_t)q); eL.resize((size_t)q); seen.assign((size_t)n + 1, -1); A.resize((size_t)n + 1); }
+    catch (const std::bad_alloc &) { return fail(nullptr, RC_ERR_OOM, "%s: no host memory", who); }
+    for (int64_t s = 0; s < m; ++s) {
+        const int64_t *z = samples + (size_t)s * n;
+        int k = 0;
+        for (int64_t j = 0; j < n; ++j) {
+            const int64_t l = z[j];
+            if (l < 1 || l > n) return fail(nullptr, RC_ERR_ARG, "%s: label %lld of sample %lld at position %lld outside 1..n", who, (long long)l, (long long)s + 1, (long long)j + 1);
+            if (seen[(size_t)l] != (int)s) { seen[(size_t)l] = (int)s; ++k; }
+        }
+        K[(size_t)s] = k;
+        if (want_tab && k > Kmax) return fail(nullptr, RC_ERR_ARG, "%s: sample %lld has %d clusters, Kmax = %lld", who, (long long)s + 1, k, (long long)Kmax);
+    }
+    for (int64_t i = 0; i < q; ++i) {
+        const double *x = Dnew + (size_t)i * n, *lx = logDnew_or_null ? logDnew_or_null + (size_t)i * n : nullptr;
+        double lo = INFINITY, hi = 0.0, lmax = 0.0;
+        for (int64_t j = 0; j < n; ++j) {
+            if (!(x[j] > 0.0 && x[j] <= 1.79769313486231570e308))
+                return fail(nullptr, RC_ERR_DOMAIN, "%s: Dnew[%lld][%lld] = %g is not a positive finite distance", who, (long long)i + 1, (long long)j + 1, x[j]);
+            lo = std::min(lo, x[j]); hi = std::max(hi, x[j]);
+            if (lx) {
+                if (!(std::fabs(lx[j]) <= 1.79769313486231570e308)) return fail(nullptr, RC_ERR_DOMAIN, "%s: logDnew[%lld][%lld] is not finite", who, (long long)i + 1, (long long)j + 1);
+                lmax = std::max(lmax, std::fabs(lx[j]));
+            }
+        }
+        if (!lx) lmax = std::max(std::fabs(std::log(lo)), std::fabs(std::log(hi)));   // log is monotone: the row's largest |log|
+        eD[(size_t)i] = quant_exponent(n, hi, 64);
+        eL[(size_t)i] = quant_exponent(n, lmax, 64);
+        if (eD_out) eD_out[i] = eD[(size_t)i];
+        if (eL_out) eL_out[i] = eL[(size_t)i];
+    }
+    rc = select_device(who, device);
+    if (rc != RC_OK) return rc;
+    size_table(params, n, A.data());
+    DeviceBuffers B;
+    double2 *d_flt;
+    {
+        double2 ft[128];
+        flog_table(ft);
+        HIPCHK(nullptr, B.alloc(d_flt, 128));
+        HIPCHK(nullptr, hipMemcpy(d_flt, ft, sizeof(ft), hipMemcpyHostToDevice));
+    }
+    prd::Call c{n, q, m, want_tab ? Kmax : 0, Dnew, logDnew_or_null, samples, r, p, params, seed, sample_offset, point_offset,
+                labels_out, map_out, sums_out, scores_out, eD.data(), eL.data(), K.data(), A.data(), d_flt, false};
+    {
+        const char *e = std::getenv("RC_PREDICT_ROWS_GLOBAL");             // tests: gather from the rows in global memory at small n
+        c.rows_global = e && atoi(e) != 0;
+    }
+    // Chunks.  Device bytes per new point for a run of samples: its row, and per sample its slots' sums, two labels and the
+    // optional columns.  Samples are taken while 512 points (or all q) of them fit the workspace and their sorted orders fit
+    // theirs; the points then go in chunks of what fits.
+    size_t workspace = prd::WORKSPACE;
+    if (const char *e = std::getenv("RC_PREDICT_WORKSPACE_KIB")) {        // tests: chunks at small shapes (the same results)
+        const long long v = atoll(e);
+        if (v > 0) workspace = (size_t)v << 10;
+    }
+    const size_t per_sample = 16 + (scores_out ? 8 * ((size_t)c.Kmax + 1) : 0) + (sums_out ? 16 * (size_t)c.Kmax : 0);
+    const int64_t qt = std::min<int64_t>(q, 512);
+    const int64_t ms_cap = std::max<int64_t>(64, (int64_t)(prd::PERM_BYTES / 2 / (size_t)n) / 64 * 64);
+    double ms_acc = 0.0;
+    for (int64_t s0 = 0; s0 < m;) {
+        size_t bytes = 16 * (size_t)n;
+        int64_t ms = 0;
+        while (s0 + ms < m && ms < ms_cap) {
+            const size_t add = 16 * (size_t)K[(size_t)(s0 + ms)] + per_sample;
+            if (ms > 0 && (bytes + add) * (size_t)qt > workspace) break;
+            bytes += add; ++ms;
+        }
+        const int64_t qc = std::max<int64_t>(1, std::min<int64_t>(q, (int64_t)(workspace / bytes)));
+        rc = prd::run_samples(who, c, s0, ms, qc, ms_acc);
+        if (rc != RC_OK) return rc;
+        s0 += ms;
+    }
+    if (kernel_ms) *kernel_ms = ms_acc;
+    return RC_OK;
+}

@@ -5033,6 +5033,44 @@ static int quant_exponent(long long n, double maxabs, int bits)
 
 extern "C" const char *rc_last_error(const rc_ctx *ctx) { return ctx ? ctx->err : g_err; }
 
+// The checks of rc_set_params, for every entry point that takes an rc_params.
+static int32_t check_params(rc_ctx *c, const char *who, const rc_params *P)
+{
+    if (!(P->delta1 > 0 && P->delta2 > 0 && P->alpha > 0 && P->beta > 0 && P->zeta > 0 && P->gamma > 0))
+        return fail(c, RC_ERR_ARG, "%s: likelihood hyperparameters must be positive", who);
+    if (P->maxK < 0) return fail(c, RC_ERR_ARG, "%s: maxK must be >= 0", who);
+    return RC_OK;
+}
+
+// size table A[0..n] (see DESIGN.md "Score arithmetic"): long double on the host
+static void size_table(const rc_params *P, long long n, double *A)
+{
+    const long double d1 = P->delta1, d2 = P->delta2, al = P->alpha, be = P->beta, ze = P->zeta, ga = P->gamma;
+    const long double lga = lgammal(al), lgz = lgammal(ze), lgd1 = lgammal(d1), lgd2 = lgammal(d2);
+    const long double lb = logl(be), lg = logl(ga);
+    A[0] = 0.0;
+    for (long long s = 1; s <= n; ++s) {
+        const long double S = (long double)s;
+        const long double t1 = lgammal(al + d1 * S) - lga - d1 * S * lb - S * lgd1;
+        const long double t2 = lgammal(ze + d2 * S) - lgz - d2 * S * lg - S * lgd2;
+        A[(size_t)s] = (double)(t1 - (P->repulsion ? t2 : 0.0L) + logl((S + 1) / S));
+    }
+}
+
+// table of rc_flog (see there): interval i of z's offset from 0.6875 in units of 2^-7 of the mantissa; long double on the host
+static void flog_table(double2 ft[128])
+{
+    for (int i = 0; i < 128; ++i) {
+        const uint64_t b0 = ((uint64_t)(0x3fe60000u + ((uint32_t)i << 13))) << 32, b1 = ((uint64_t)(0x3fe60000u + ((uint32_t)(i + 1) << 13))) << 32;
+        double z0, z1;
+        memcpy(&z0, &b0, 8); memcpy(&z1, &b1, 8);
+        if (i == 79 || i == 80) { ft[i].x = 1.0; ft[i].y = 0.0; continue; }   // the intervals that touch 1.0: r = z - 1, exactly
+        const long double cc = 0.5L * ((long double)z0 + (long double)z1);
+        const double invc = (double)(1.0L / cc);
+        ft[i].x = invc; ft[i].y = (double)(-logl((long double)invc));
+    }
+}
+
 static void free_all(rc_ctx *c)
 {
     if (!c) return;
@@ -5263,17 +5301,9 @@ static int32_t create_impl(rc_ctx *c, int64_t n, const double *D, const double *
     HIPCHK2(hipMalloc(&c->ipi, (size_t)n * sizeof(int)));
     HIPCHK2(hipMalloc(&c->ltab, 128 * sizeof(double2)));
     HIPCHK2(hipMalloc(&c->vtab, RC_VTAB_N * sizeof(double)));
-    {   // table of rc_flog (see there): interval i of z's offset from 0.6875 in units of 2^-7 of the mantissa; long double on the host
+    {
         double2 ft[128];
-        for (int i = 0; i < 128; ++i) {
-            const uint64_t b0 = ((uint64_t)(0x3fe60000u + ((uint32_t)i << 13))) << 32, b1 = ((uint64_t)(0x3fe60000u + ((uint32_t)(i + 1) << 13))) << 32;
-            double z0, z1;
-            memcpy(&z0, &b0, 8); memcpy(&z1, &b1, 8);
-            if (i == 79 || i == 80) { ft[i].x = 1.0; ft[i].y = 0.0; continue; }   // the intervals that touch 1.0: r = z - 1, exactly
-            const long double cc = 0.5L * ((long double)z0 + (long double)z1);
-            const double invc = (double)(1.0L / cc);
-            ft[i].x = invc; ft[i].y = (double)(-logl((long double)invc));
-        }
+        flog_table(ft);
         HIPCHK2(hipMalloc(&c->flt, sizeof(ft)));
         HIPCHK2(hipMemcpy(c->flt, ft, sizeof(ft), hipMemcpyHostToDevice));
     }
@@ -5889,9 +5919,8 @@ extern "C" int32_t rc_debug_rowtotals(rc_ctx *c, int64_t *totD_q, int64_t *totL_
 extern "C" int32_t rc_set_params(rc_ctx *c, const rc_params *P)
 {
     if (!c || !P) return fail(c, RC_ERR_ARG, "rc_set_params: NULL argument");
-    if (!(P->delta1 > 0 && P->delta2 > 0 && P->alpha > 0 && P->beta > 0 && P->zeta > 0 && P->gamma > 0))
-        return fail(c, RC_ERR_ARG, "rc_set_params: likelihood hyperparameters must be positive");
-    if (P->maxK < 0) return fail(c, RC_ERR_ARG, "rc_set_params: maxK must be >= 0");
+    const int32_t bad = check_params(c, "rc_set_params", P);
+    if (bad != RC_OK) return bad;
     HIPCHK(c, hipSetDevice(c->dev));
     HIPCHK(c, hipStreamSynchronize(c->sA));
     HIPCHK(c, hipStreamSynchronize(c->sB));
@@ -5903,16 +5932,7 @@ extern "C" int32_t rc_set_params(rc_ctx *c, const rc_params *P)
     c->B_version = -2;
     // size table (see DESIGN.md "Score arithmetic"): long double on the host, once per parameter set
     std::vector<double> A((size_t)c->n + 1);
-    const long double d1 = P->delta1, d2 = P->delta2, al = P->alpha, be = P->beta, ze = P->zeta, ga = P->gamma;
-    const long double lga = lgammal(al), lgz = lgammal(ze), lgd1 = lgammal(d1), lgd2 = lgammal(d2);
-    const long double lb = logl(be), lg = logl(ga);
-    A[0] = 0.0;
-    for (int s = 1; s <= c->n; ++s) {
-        const long double S = (long double)s;
-        const long double t1 = lgammal(al + d1 * S) - lga - d1 * S * lb - S * lgd1;
-        const long double t2 = lgammal(ze + d2 * S) - lgz - d2 * S * lg - S * lgd2;
-        A[(size_t)s] = (double)(t1 - (P->repulsion ? t2 : 0.0L) + logl((S + 1) / S));
-    }
+    size_table(P, c->n, A.data());
     HIPCHK(c, hipMemcpyAsync(c->A, A.data(), A.size() * sizeof(double), hipMemcpyHostToDevice, c->sA));
     HIPCHK(c, hipStreamSynchronize(c->sA));
     c->have_params = true;
@@ -7828,3 +7848,4 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "visearch.inc.hip"
 #include "samplecounts.inc.hip"
 #include "hclust.inc.hip"
+#include "predict.inc.hip"

@@ -1,0 +1,138 @@
+"""Predict: allocate observations that were not in the fit to the clusters of every posterior sample, on the GPU
+(csrc/predict.inc.hip through rc_predict; include/redclust_hip.h has the contract, DESIGN.md §8 "Predict" the design).
+Under one sample the allocation of a new observation is the Gibbs full conditional of an (n+1)-th point whose own cluster is
+empty; new observations are allocated independently of each other given a sample.  There is no CPU fallback."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+
+_DIST_CHUNK_BYTES = 64 << 20   # the difference tensor of one chunk of new points (rows × n × dim f64)
+
+
+@dataclass
+class Prediction:
+    """labels[s, i]: the label new point i drew under sample s, in that sample's own label names; 0 = a cluster of its own.
+    map_labels: the most probable label instead of a draw.  scores (optional, m×q×(Kmax+1)): the noise-free log weights —
+    column t < K_s belongs to the t-th smallest label of sample s, the last column to a new cluster (-inf when maxK forbids
+    it), NaN between.  kernel_ms: device time of the kernels."""
+    labels: np.ndarray
+    map_labels: np.ndarray
+    scores: np.ndarray | None = None
+    kernel_ms: float = 0.0
+
+    def new_cluster_frequency(self) -> np.ndarray:
+        """Per new point: the share of samples in which it opened a cluster of its own."""
+        return (self.labels == 0).mean(axis=0)
+
+    def extended_samples(self, samples) -> np.ndarray:
+        """The m×(n+q) label matrix of training and new points together.  Within a sample the a-th new point that drew 0
+        gets the a-th smallest positive label the sample does not use, so independent singletons stay distinct; every
+        label lies in 1..n+q, and posterior_counts, searchpointestimate, hclustpointestimate take the matrix as it is."""
+        S = _label_matrix(samples)
+        m, q = self.labels.shape
+        if S.shape[0] != m:
+            raise ValueError(f"samples must be the {m} samples of the prediction")
+        n = S.shape[1]
+        out = np.empty((m, n + q), np.int64)
+        out[:, :n] = S
+        out[:, n:] = self.labels
+        every = np.arange(1, n + q + 1)
+        for s in range(m):
+            own = np.flatnonzero(self.labels[s] == 0)
+            if len(own):
+                out[s, n + own] = np.setdiff1d(every, S[s], assume_unique=False)[:len(own)]
+        return out
+
+
+def _label_matrix(samples) -> np.ndarray:
+    clusts = samples.clusts if hasattr(samples, "clusts") else samples
+    if len(clusts) == 0:
+        raise ValueError("no samples")
+    S = np.asarray(clusts if isinstance(clusts, np.ndarray) else np.stack([np.asarray(c) for c in clusts]))
+    if S.ndim != 2 or not np.issubdtype(S.dtype, np.integer):
+        raise ValueError("samples must be an m×n matrix of integer labels")
+    S = np.ascontiguousarray(S, dtype=np.int64)
+    if S.shape[1] < 1 or S.min() < 1 or S.max() > S.shape[1]:
+        raise ValueError("sample labels must lie in 1..n")
+    return S
+
+
+def _params_dict(params) -> dict:
+    P = params.as_dict() if hasattr(params, "as_dict") else dict(params)
+    for k in ("delta1", "delta2", "alpha", "beta", "zeta", "gamma"):
+        if k not in P or not float(P[k]) > 0:
+            raise ValueError(f"params: {k} must be given and positive")
+    if int(P.get("maxK", 0)) < 0:
+        raise ValueError("params: maxK must be >= 0")
+    return P
+
+
+def predict(result_or_samples, Dnew=None, *, new_points=None, points=None, r=None, p=None, params=None, seed: int = 0,
+            scores: bool = False, device: int = 0) -> Prediction:
+    """Allocate new observations to the clusters of every posterior sample.
+
+    result_or_samples: an MCMCResult (its clusts, r, p and params are used) or an m×n label matrix with r, p (one per
+    sample) and params (a PriorHyperparamsList or a dict of the likelihood hyperparameters) given.  The new data: Dnew
+    (q×n, distances of every new observation to every training observation) or new_points with the training points, one
+    observation per row — the distances are then computed on the host in row chunks, so q×n never exists at once; every new
+    point is quantised by itself and keyed by its own index, so the chunked result equals the unchunked one."""
+    S = _label_matrix(result_or_samples)
+    m, n = S.shape
+    res = result_or_samples
+    r = getattr(res, "r", None) if r is None else r
+    p = getattr(res, "p", None) if p is None else p
+    params = getattr(res, "params", None) if params is None else params
+    if r is None or p is None or params is None:
+        raise ValueError("r, p and params are needed with a plain label matrix")
+    r = np.ascontiguousarray(r, dtype=np.float64).reshape(-1)
+    p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1)
+    if r.shape != (m,) or p.shape != (m,):
+        raise ValueError(f"r and p must hold one value per sample ({m})")
+    if not (np.all(np.isfinite(r)) and np.all(r > 0)):
+        raise ValueError("r must be positive and finite")
+    if not (np.all(p > 0) and np.all(p < 1)):
+        raise ValueError("p must lie in (0, 1)")
+    P = _params_dict(params)
+    if (Dnew is None) == (new_points is None):
+        raise ValueError("give either Dnew or new_points (with points)")
+    Kmax = int(max(len(np.unique(row)) for row in S)) if scores else 0
+    if Dnew is not None:
+        if points is not None:
+            raise ValueError("points goes with new_points, not with Dnew")
+        Dnew = np.ascontiguousarray(Dnew, dtype=np.float64)
+        if Dnew.ndim != 2 or Dnew.shape[1] != n or Dnew.shape[0] < 1:
+            raise ValueError(f"Dnew must be a q×n matrix with n = {n} columns and q >= 1")
+        if not (np.all(np.isfinite(Dnew)) and np.all(Dnew > 0)):
+            raise ValueError("Dnew must be finite and positive")
+        out = _lib.predict(Dnew, S, r, p, P, seed=seed, Kmax=Kmax, want_scores=scores, device=device)
+        return Prediction(out["labels"], out["map"], out.get("scores"), out["kernel_ms"])
+    if points is None:
+        raise ValueError("new_points needs the training points")
+    X = np.ascontiguousarray(points, dtype=np.float64)
+    Y = np.ascontiguousarray(new_points, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] != n:
+        raise ValueError(f"points must hold the n = {n} training observations, one per row")
+    if Y.ndim != 2 or Y.shape[1] != X.shape[1] or Y.shape[0] < 1:
+        raise ValueError("new_points must hold q >= 1 observations of the training points' dimension, one per row")
+    if not (np.all(np.isfinite(X)) and np.all(np.isfinite(Y))):
+        raise ValueError("points must be finite")
+    q = Y.shape[0]
+    step = max(1, _DIST_CHUNK_BYTES // (8 * n * max(X.shape[1], 1)))
+    labels, maps = np.empty((m, q), np.int64), np.empty((m, q), np.int64)
+    sc = np.empty((m, q, Kmax + 1)) if scores else None
+    ms = 0.0
+    for i0 in range(0, q, step):
+        Yc = Y[i0:i0 + step]
+        Dc = np.sqrt(((Yc[:, None, :] - X[None, :, :]) ** 2).sum(axis=2))
+        if not np.all(Dc > 0):
+            raise ValueError("a new point coincides with a training point: the distances must be positive")
+        out = _lib.predict(Dc, S, r, p, P, seed=seed, point_offset=i0, Kmax=Kmax, want_scores=scores, device=device)
+        labels[:, i0:i0 + step], maps[:, i0:i0 + step] = out["labels"], out["map"]
+        if scores:
+            sc[:, i0:i0 + step] = out["scores"]
+        ms += out["kernel_ms"]
+    return Prediction(labels, maps, sc, ms)

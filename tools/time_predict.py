@@ -1,0 +1,100 @@
+"""Kernel and wall time of predict (rc_predict; csrc/predict.inc.hip) and, for scale, of its NumPy restatement on the CPU.
+
+    python tools/time_predict.py                       # n = 8192, K = 50, m = 1000 samples, q = 1024 new points
+    python tools/time_predict.py --n 2048 --q 256 --reps 3
+
+Inputs (seed 0): n + q observations from K Gaussian groups in 8 dimensions, the last q held out; the m samples are the true
+training labels with 2 % of the points relabelled at random in each; r and p drawn once per sample; the likelihood
+hyperparameters are likelihood_hyperparams of the first 1024 training points under the truth.  Timed, after a small call
+that loads the module and a first full call: `reps` calls of rc_predict on the q×n distances (logarithms taken by the
+library).  kernel_ms is the device time of the call's kernels (events around them), wall the whole call: the host's checks,
+quantisation and sorted orders, the copies, the kernels.  The NumPy reference (tests/predict_ref.py: np.add.at for the sums,
+math.log1p per candidate, the oracle's uniforms) is timed on a few (sample, point) cases and extrapolated to q·m; the device's
+labels of those cases are compared with it.  One JSON line per measurement."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import redclust_amd as rc  # noqa: E402
+from redclust_amd import _lib  # noqa: E402
+
+
+def planted(n, q, K, m, noise, dim=8, seed=0):
+    rng = np.random.default_rng(seed)
+    truth = rng.integers(0, K, size=n + q)
+    X = 4.0 * rng.standard_normal((K, dim))[truth] + rng.standard_normal((n + q, dim))
+    samples = np.tile(truth[:n], (m, 1))
+    flip = rng.random((m, n)) < noise
+    samples[flip] = rng.integers(0, K, size=int(flip.sum()))
+    return X[:n], X[n:], truth, samples.astype(np.int64) + 1, rng.uniform(0.5, 3.0, m), rng.uniform(0.2, 0.8, m)
+
+
+def distances(A, B, rows=64):
+    out = np.empty((len(A), len(B)))
+    for i in range(0, len(A), rows):
+        out[i:i + rows] = np.sqrt(((A[i:i + rows, None, :] - B[None, :, :]) ** 2).sum(axis=2))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=8192)
+    ap.add_argument("--q", type=int, default=1024)
+    ap.add_argument("--m", type=int, default=1000)
+    ap.add_argument("--K", type=int, default=50)
+    ap.add_argument("--noise", type=float, default=0.02)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--ref-cases", type=int, default=6)
+    ap.add_argument("--no-host", action="store_true")
+    a = ap.parse_args()
+    tr, new, truth, S, r, p = planted(a.n, a.q, a.K, a.m, a.noise)
+    sub = min(a.n, 1024)
+    P = rc.likelihood_hyperparams(distances(tr[:sub], tr[:sub]), truth[:sub] + 1)
+    Dnew = distances(new, tr)
+    _lib.predict(Dnew[:2, :64], S[:3, :64] % 64 + 1, r[:3], p[:3], P)           # module load, first launches
+    out = _lib.predict(Dnew, S, r, p, P)                                        # first call at the timed shape
+    walls, kms = [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        o = _lib.predict(Dnew, S, r, p, P)
+        walls.append(time.perf_counter() - t0)
+        kms.append(o["kernel_ms"])
+        assert np.array_equal(o["labels"], out["labels"])
+    adds = float(a.q) * a.m * a.n
+    hit = float((out["map"] == (truth[a.n:] + 1)[None, :]).mean())
+    print(json.dumps(dict(what="rc_predict", n=a.n, q=a.q, m=a.m, K=a.K, reps=a.reps, kernel_ms_median=round(statistics.median(kms), 3),
+                          kernel_ms_min=round(min(kms), 3), kernel_ms_max=round(max(kms), 3),
+                          gathers_per_s=round(adds / (statistics.median(kms) * 1e-3), 0), wall_s_median=round(statistics.median(walls), 4),
+                          wall_s_min=round(min(walls), 4), wall_s_max=round(max(walls), 4), map_equals_truth=round(hit, 4),
+                          new_cluster_share=round(float((out["labels"] == 0).mean()), 6))), flush=True)
+    if a.no_host:
+        return
+    import oracle_lib as O
+    import predict_ref as R
+    logD = np.log(Dnew)
+    given = _lib.predict(Dnew, S, r, p, P, logDnew=logD)                        # the reference's own logarithms
+    rng = np.random.default_rng(1)
+    cases = [(int(rng.integers(a.m)), int(rng.integers(a.q))) for _ in range(a.ref_cases)]
+    A = O.size_table(P, a.n)
+    t0 = time.perf_counter()
+    agree = 0
+    for s, i in cases:
+        Dq, Lq, eD, eL = R.quantise_rows(Dnew[i:i + 1], logD[i:i + 1], a.n)
+        cands, _, sc, _ = R.score_point(Dq[0], Lq[0], eD[0], eL[0], S[s], float(r[s]), float(p[s]), P, A)
+        lab, mp, _, _ = R.draw(cands, sc, 0, s, i)
+        agree += int(lab == given["labels"][s, i] and mp == given["map"][s, i])
+    per_case = (time.perf_counter() - t0) / len(cases)
+    print(json.dumps(dict(what="numpy reference", cases=len(cases), s_per_case=round(per_case, 6),
+                          extrapolated_s=round(per_case * a.q * a.m, 1), device_labels_equal=f"{agree}/{len(cases)}")), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -656,6 +656,39 @@ int32_t rc_predict(int32_t device, int64_t n, int64_t q,
                    int64_t *sums_out /* m×q×Kmax×2 or NULL */,
                    int32_t *eD_out /* q or NULL */, int32_t *eL_out /* q or NULL */, double *kernel_ms);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Partition distances: what the Binder loss, the VI and the information distance between each of L labellings and each
+ * of m samples are made of, as exact integers — the L×m rectangle behind credible balls and exact expected losses.  No
+ * context: errors through rc_last_error(NULL).  DESIGN.md §8 "Partition distances".
+ *
+ * With N_kl = #{j : labels[l][j] = k, samples[s][j] = l'} the contingency table of labelling l and sample s, and Gq / Phiq
+ * the fixed-point table of rc_vi_gtable (Phiq(x) = Σ_{y<x} Gq[y]; the same table, not a second one):
+ *   sq_out[l][s]  = P = Σ_kl N_kl²            phi_out[l][s] = T = Σ_kl Phiq(N_kl)
+ *   lab_marg[l]   = (A₂, A_q, K) = (Σ_k n_k², Σ_k Phiq(n_k), number of clusters) of labelling l;  smp_marg[s] = (B₂, B_q, K)
+ *                   likewise of sample s.
+ * The three distances follow in integers:
+ *   Binder numerator = (A₂ + B₂ − 2P)/2, the number of pairs of points on which the two partitions disagree — what
+ *                      binderloss(normalised = false) returns; divide by n(n−1)/2 for the normalised loss;
+ *   VI_q = A_q + B_q − 2T   and   ID_q = max(A_q, B_q) − T,   both in units of 2^-32/n nats: VI = VI_q/(2^32·n).
+ *   Σ_s VI_q of a labelling is rc_vi_search's loss_num for it plus that search's constant Σ_s B_q.
+ * Every output is a pure function of (labelling, sample) — bit for bit the same whatever L is, however the call is
+ * chunked and whichever other labellings share it.  Any of sq_out, phi_out, lab_marg, smp_marg may be NULL (with both
+ * sq_out and phi_out NULL no device is touched).  kernel_ms (may be NULL): device time of the call's kernels.
+ *
+ * Errors, all before any device work.  RC_ERR_ARG: samples or labels NULL; m, n or L < 1; a label outside 1..n (the
+ * message names the sample or labelling and the position); a device that is not there.  RC_ERR_CAPACITY (checked before
+ * any array is read): n > 32767, m·n >= 2^31 or L > 65536.  L and m are otherwise unbounded in memory terms: the host
+ * walks the labellings, and the samples if need be, in chunks of a device workspace of about 1 GiB.  Labellings of more
+ * than 1024 clusters keep their histograms in global memory instead of LDS; RC_PARTDIST_HIST_GLOBAL=1 in the environment
+ * (read at every call) does that for every labelling, RC_PARTDIST_GQ_GLOBAL=1 reads Gq from global memory where its
+ * reachable part would be copied to LDS, and RC_PARTDIST_WORKSPACE_KIB=<k> shrinks the workspace so that small calls are
+ * chunked — the same integers either way; for tests.
+ * ------------------------------------------------------------------------------------------------------------- */
+int32_t rc_partition_distances(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n,
+                               int64_t L, const int64_t *labels /* L×n, labels 1..n */,
+                               int64_t *sq_out /* L×m or NULL */, int64_t *phi_out /* L×m or NULL */,
+                               int64_t *lab_marg /* L×3 or NULL */, int64_t *smp_marg /* m×3 or NULL */, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -601,4 +601,76 @@ end
 
 export predict
 
+const DISTANCE_LOSSES = ("binder", "VI", "ID")
+
+"""
+    partitiondistances(HIPBackend(), labellings, result; loss = "VI") -> (dist, info)
+
+The distance from each of `L` labellings (a vector of label vectors) to each of the `m` samples of `result`, on the GPU in
+exact integers (rc_partition_distances).  `loss`: "binder" (normalised, as `binderloss`), "VI" or "ID" (nats, as
+`infodist(...; normalised = false)`).  `dist` is L×m; `info.num` holds the integer numerators it was divided from once —
+Binder: disagreeing pairs; VI, ID: units of 2^-32/n nats, VI_q = A_q + B_q − 2T and ID_q = max(A_q, B_q) − T with the
+library's fixed-point table — and `info.K_labellings`, `info.K_samples` the cluster counts.
+"""
+function partitiondistances(b::HIPBackend, labellings::Vector{<:AbstractVector{<:Integer}}, result; loss::String = "VI")
+    loss in DISTANCE_LOSSES || throw(ArgumentError("Invalid loss function specifier."))
+    samples = samplematrix(result)
+    n, m = size(samples)
+    L = length(labellings)
+    labels = Matrix{Int64}(undef, n, L)                           # column l = labelling l: row-major L×n for the library
+    for l in 1:L
+        length(labellings[l]) == n || throw(ArgumentError("Length of the input vectors must be equal."))
+        labels[:, l] .= labellings[l]
+    end
+    part = Matrix{Int64}(undef, m, L)                             # P for "binder", T otherwise: row-major L×m
+    labmarg = Matrix{Int64}(undef, 3, L); smpmarg = Matrix{Int64}(undef, 3, m)
+    ms = Cdouble[0]
+    rc = ccall((:rc_partition_distances, LIB), Int32,
+               (Int32, Ptr{Int64}, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}),
+               b.device, samples, m, n, L, labels, loss == "binder" ? part : C_NULL, loss == "binder" ? C_NULL : part,
+               labmarg, smpmarg, ms)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    row = loss == "binder" ? 1 : 2
+    num = Matrix{Int64}(undef, L, m)
+    for l in 1:L, s in 1:m
+        a, c, t = labmarg[row, l], smpmarg[row, s], part[s, l]
+        num[l, s] = loss == "binder" ? (a + c - 2t) ÷ 2 : loss == "VI" ? a + c - 2t : max(a, c) - t
+    end
+    den = loss == "binder" ? n * (n - 1) ÷ 2 : 2.0^32 * n
+    dist = den == 0 ? zeros(L, m) : num ./ den
+    return (dist, (num = num, K_labellings = labmarg[3, :], K_samples = smpmarg[3, :], kernel_ms = ms[1]))
+end
+
+"""
+    credibleball(HIPBackend(), clust, result; loss = "VI", alpha = 0.05)
+
+The (1 − alpha) credible ball around the point estimate `clust` (Wade & Ghahramani 2018; mcclust.ext's `credibleball`), from
+the exact integer distances of `partitiondistances`: with k = m − ⌊alpha·m + 1e-9⌋, `epsilon` is the k-th smallest distance
+and the ball is every sample within it (ties at the radius are in).  `horizontal`: the ball's samples at distance epsilon;
+`upper` / `lower`: among the ball's samples with the fewest / most clusters, those of greatest distance.  Returns a named
+tuple: epsilon, epsilon_num, level, ball, distances, distances_num, K, and per bound `<name>_index` (ascending sample indices)
+and `<name>` (the distinct partitions among them, sortlabels'd, in order of first occurrence).
+"""
+function credibleball(b::HIPBackend, clust::AbstractVector{<:Integer}, result; loss::String = "VI", alpha::Real = 0.05)
+    0 <= alpha < 1 || throw(ArgumentError("alpha must lie in [0, 1)"))
+    dist, info = partitiondistances(b, [clust], result; loss = loss)
+    num = info.num[1, :]; K = info.K_samples
+    m = length(num)
+    k = m - floor(Int, alpha * m + 1e-9)
+    eps_num = sort(num)[k]
+    ball = num .<= eps_num
+    farthest(mask) = (far = maximum(num[mask]); findall(mask .& (num .== far)))
+    index = (horizontal = findall(ball .& (num .== eps_num)), upper = farthest(ball .& (K .== minimum(K[ball]))),
+             lower = farthest(ball .& (K .== maximum(K[ball]))))
+    parts(idx) = unique([RedClust.sortlabels(result.clusts[s]) for s in idx])
+    n = length(clust)
+    den = loss == "binder" ? n * (n - 1) ÷ 2 : 2.0^32 * n
+    return (epsilon = den == 0 ? 0.0 : eps_num / den, epsilon_num = eps_num, level = count(ball) / m, ball = ball,
+            distances = dist[1, :], distances_num = num, K = K,
+            horizontal_index = index.horizontal, upper_index = index.upper, lower_index = index.lower,
+            horizontal = parts(index.horizontal), upper = parts(index.upper), lower = parts(index.lower))
+end
+
+export partitiondistances, credibleball
+
 end # module

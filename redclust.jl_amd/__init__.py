@@ -14,5 +14,6 @@ from .chains import chain_seed, merge_chains, run_chains, run_chains_single_proc
 from .pointestimate import (getpointestimate, lossmatrix, binderloss, infodist, varinfo, evaluateclustering,  # noqa: F401
                             summarise, searchpointestimate, expectedloss, expectedvi, expectedid, cocluster_counts,
                             posterior_counts, posterior_coclustering, hclust, hclustpointestimate, expectedlosses,
-                            linkage_matrix, leaf_order)
+                            linkage_matrix, leaf_order, partitiondistances, expecteddistances, credibleball,
+                            credibleball_from_distances)
 from .predict import predict, Prediction  # noqa: F401

@@ -87,7 +87,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
             os.path.join(CSRC, "chain.inc.hip"), os.path.join(CSRC, "chains.inc.hip"), os.path.join(CSRC, "samplek.inc.hip"),
             os.path.join(CSRC, "mixture.inc.hip"), os.path.join(CSRC, "kmeans.inc.hip"),
             os.path.join(CSRC, "pointsearch.inc.hip"), os.path.join(CSRC, "visearch.inc.hip"),
-            os.path.join(CSRC, "samplecounts.inc.hip"), os.path.join(CSRC, "hclust.inc.hip"), os.path.join(CSRC, "predict.inc.hip"), HEADER]
+            os.path.join(CSRC, "samplecounts.inc.hip"), os.path.join(CSRC, "hclust.inc.hip"), os.path.join(CSRC, "predict.inc.hip"),
+            os.path.join(CSRC, "partdist.inc.hip"), HEADER]
     if not force and os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(s) for s in srcs):
         return SO
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-o", SO, srcs[0]]
@@ -210,6 +211,8 @@ SIGNATURES = {
     "rc_predict": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.POINTER(RcParams), C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "rc_partition_distances": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "rc_layout_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rc_event_overhead_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "rc_kernel_timing": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -938,6 +941,27 @@ def predict(Dnew, samples, r, p, params: dict, seed: int = 0, sample_offset: int
     if want_sums:
         out["sums"] = sm[:m, :q, :int(Kmax)]
     return out
+
+
+def partition_distances(labels, samples, want_sq: bool = True, want_phi: bool = True, device: int = 0) -> dict:
+    """rc_partition_distances for L×n labellings and m×n samples (int64 labels in 1..n): a dict with sq and phi (L×m int64, or
+    None when not asked for), lab_marg (L×3) and smp_marg (m×3) — Σ n_k², Σ Phiq(n_k), K of every row — and kernel_ms."""
+    L = lib()
+    lab = np.ascontiguousarray(labels, dtype=np.int64)
+    S = np.ascontiguousarray(samples, dtype=np.int64)
+    if lab.ndim != 2 or S.ndim != 2 or lab.shape[1] != S.shape[1]:
+        raise ValueError("labels must be L×n and samples m×n")
+    (nl, n), m = lab.shape, S.shape[0]
+    sq = np.zeros((max(nl, 1), max(m, 1)), np.int64) if want_sq else None
+    phi = np.zeros((max(nl, 1), max(m, 1)), np.int64) if want_phi else None
+    lm, sm = np.zeros((max(nl, 1), 3), np.int64), np.zeros((max(m, 1), 3), np.int64)
+    ms = C.c_double()
+    rc = L.rc_partition_distances(int(device), S.ctypes.data, m, n, nl, lab.ctypes.data, None if sq is None else sq.ctypes.data,
+                                  None if phi is None else phi.ctypes.data, lm.ctypes.data, sm.ctypes.data, C.byref(ms))
+    if rc != RC_OK:
+        raise _error(rc, L.rc_last_error(None).decode())
+    return dict(sq=None if sq is None else sq[:nl, :m], phi=None if phi is None else phi[:nl, :m], lab_marg=lm[:nl], smp_marg=sm[:m],
+                kernel_ms=float(ms.value))
 
 
 def sample_k(n: int, r, p, seed: int = 0, device: int = 0):

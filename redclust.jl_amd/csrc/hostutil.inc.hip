@@ -35,6 +35,33 @@ struct TimingEvents {
     }
 };
 
+// The cluster-contiguous order of one labelling z (n labels in 1..n, checked by the caller), shared by predict and the partition
+// distances.  The labels are compacted to slots 0..K-1 in ascending label order: slot(t, label, size) is called once per slot,
+// in that order.  The points are then counting-sorted by slot: put(at, j, t) is called for every point j, in index order, with
+// its position in the sorted order and its slot.  Returns K; afterwards pos[t] is one past slot t's last position.  Scratch of
+// the caller's: cnt (n + 1 zeros, left zeroed), slot_of_label (n + 1), pos (n).
+template <typename Slot, typename Put>
+static int cluster_order(const int64_t *z, int64_t n, std::vector<int> &cnt, std::vector<int> &slot_of_label, std::vector<int> &pos,
+                         Slot slot, Put put)
+{
+    for (int64_t j = 0; j < n; ++j) cnt[(size_t)z[j]]++;
+    int K = 0, at = 0;
+    for (int64_t l = 1; l <= n; ++l) {
+        const int sz = cnt[(size_t)l];
+        if (!sz) continue;
+        slot_of_label[(size_t)l] = K;
+        pos[(size_t)K] = at; at += sz;
+        slot(K, l, sz);
+        cnt[(size_t)l] = 0;
+        ++K;
+    }
+    for (int64_t j = 0; j < n; ++j) {
+        const int t = slot_of_label[(size_t)z[j]];
+        put(pos[(size_t)t]++, j, t);
+    }
+    return K;
+}
+
 static int32_t select_device(const char *who, int32_t device)
 {
     int ndev = 0;

@@ -234,26 +234,17 @@ static int32_t run_samples(const char *who, const Call &c, int64_t s0, int64_t m
     for (int64_t s = 0; s < ms; ++s) {
         const int64_t *z = c.samples + (size_t)(s0 + s) * n;
         const double r = c.r[s0 + s], p = c.p[s0 + s], logp = std::log(p);
-        for (int64_t j = 0; j < n; ++j) cnt[(size_t)z[j]]++;
-        int K = 0, at = 0;
-        for (int64_t l = 1; l <= n; ++l) {
-            const int sz = cnt[(size_t)l];
-            if (!sz) continue;
-            slot_of_label[(size_t)l] = K;
-            pos[(size_t)K] = at; at += sz;
-            szlab[(size_t)(k0 + K)] = make_int2(sz, (int)l);
-            base[(size_t)(k0 + K)] = c.A[sz] + (logp + std::log((double)sz - 1.0 + r));
-            cnt[(size_t)l] = 0;
-            ++K;
-        }
+        const int K = cluster_order(z, n, cnt, slot_of_label, pos,
+            [&](int t, int64_t l, int sz) {
+                szlab[(size_t)(k0 + t)] = make_int2(sz, (int)l);
+                base[(size_t)(k0 + t)] = c.A[sz] + (logp + std::log((double)sz - 1.0 + r));
+            },
+            [&](int at_, int64_t j, int t) {
+                perm[(size_t)at_ * ms_pad + s] = (unsigned short)j;
+                if (partat[(size_t)at_] >= 0) startslot[(size_t)partat[(size_t)at_] * ms_pad + s] = t;
+            });
         koff[(size_t)s] = k0; Ks[(size_t)s] = K;
         newscore[(size_t)s] = (c.P->maxK == 0 || K < c.P->maxK) ? std::log((double)(K + 1)) + r * std::log(1 - p) : -INFINITY;
-        for (int64_t j = 0; j < n; ++j) {
-            const int t = slot_of_label[(size_t)z[j]];
-            const int at_ = pos[(size_t)t]++;
-            perm[(size_t)at_ * ms_pad + s] = (unsigned short)j;
-            if (partat[(size_t)at_] >= 0) startslot[(size_t)partat[(size_t)at_] * ms_pad + s] = t;
-        }
         // after the fill pos[t] is one past slot t's last position: mark those
         for (int t = 0; t < K; ++t) perm[(size_t)(pos[(size_t)t] - 1) * ms_pad + s] |= 0x8000u;
         k0 += K;

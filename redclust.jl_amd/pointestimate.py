@@ -398,12 +398,39 @@ def hclust(samples_or_counts=None, linkage="average", *, numsamples=None, ctx=No
 
 
 def hclustpointestimate(samples_or_counts=None, loss="VI", linkage="average", *, maxK: int = 0, numsamples=None, ctx=None,
-                        device: int = 0):
+                        device: int = 0, exact: bool = False):
     """The hierarchical point estimate: hclust's dendrogram cut at the number of clusters K in 1..maxK of minimum expected
     loss (ties: the smaller K).  loss: "binder" — from the exact curve binder_num — or "VI", the lower bound expectedloss(…,
     "VI") evaluates, computed for every cut on the device.  maxK = 0 means ⌈n/8⌉.  Returns (clust, info): the cut
     (sortlabels'd) and a dict with loss (per K = 1..maxK), K, merges, binder_num, kernel_ms, and loss_num (per K) for
-    "binder".  A deterministic start for searchpointestimate(init=[clust])."""
+    "binder".  A deterministic start for searchpointestimate(init=[clust]).
+
+    exact=True (samples only: an MCMCResult or anything with `.clusts`): the cut is chosen by the exact posterior expected
+    loss of every cut — expecteddistances on the maxK cuts, one call of rc_partition_distances — instead of the VI's lower
+    bound; loss may then also be "ID".  info["loss"] and info["loss_num"] (per K; Python integers) are the exact expected
+    loss and its integer numerator, and the choice is exact in loss_num."""
+    if exact:
+        if loss not in _DIST_LOSSES:
+            raise ValueError("Invalid loss function specifier.")
+        if linkage not in _LINKAGES:
+            raise ValueError("Invalid linkage specifier.")
+        if ctx is not None:
+            raise ValueError("exact=True needs the samples; a Context keeps only their counts")
+        if not hasattr(samples_or_counts, "clusts"):
+            raise ValueError("exact=True needs the samples (an MCMCResult), not a count matrix")
+        S = _sample_matrix(samples_or_counts)
+        m, n = S.shape
+        maxK = int(maxK) if maxK else -(-n // 8)
+        if not 1 <= maxK <= n:
+            raise ValueError("maxK must lie in 1..n")
+        res = _lib.hclust(None, m, _LINKAGES[linkage], device=device, samples=S)
+        cuts = np.stack([_lib.hclust_cut(res["merges"], n, K) for K in range(1, maxK + 1)])
+        dist = _lib.partition_distances(cuts, S, want_sq=loss == "binder", want_phi=loss != "binder", device=device)
+        losses, num = _expected_from_parts(dist, loss, n)
+        K = min(range(maxK), key=lambda k: (num[k], k)) + 1
+        info = dict(merges=res["merges"], binder_num=res["binder_num"], kernel_ms=res["kernel_ms"], counts_ms=res["counts_ms"],
+                    distances_ms=dist["kernel_ms"], loss=losses, loss_num=num, K=K)
+        return cuts[K - 1].copy(), info
     if loss not in _PSM_LOSSES:
         raise ValueError("Invalid loss function specifier.")
     if linkage not in _LINKAGES:
@@ -442,6 +469,146 @@ def expectedlosses(labellings, counts_or_samples=None, numsamples=None, loss="VI
         counts = _lib.samples_counts(S, device=device)[0]
     out_loss, num, _ = _lib.psm_expected_loss(labs, counts, m, _PSM_LOSSES[loss], device=device, ctx=ctx)
     return out_loss, num
+
+
+_DIST_LOSSES = ("binder", "VI", "ID")
+
+
+def _numerators(dist, loss):
+    """The L×m int64 numerators of a loss from rc_partition_distances' outputs (include/redclust_hip.h): Binder
+    (A₂ + B₂ − 2P)/2, VI_q = A_q + B_q − 2T, ID_q = max(A_q, B_q) − T.  Each is below 2^52 (A_q, B_q <= Phiq(n) < n·log n·2^32
+    + n with n <= 32767), so int64 holds them with room."""
+    A, B = dist["lab_marg"], dist["smp_marg"]
+    if loss == "binder":
+        return (A[:, 0][:, None] + B[:, 0][None, :] - 2 * dist["sq"]) // 2
+    if loss == "VI":
+        return A[:, 1][:, None] + B[:, 1][None, :] - 2 * dist["phi"]
+    return np.maximum(A[:, 1][:, None], B[:, 1][None, :]) - dist["phi"]
+
+
+def _denominator(loss, n):
+    """What a numerator is divided by: n(n−1)/2 pairs for Binder (normalised as binderloss does it), 2^32·n for VI and ID (nats)."""
+    return float(n * (n - 1) // 2) if loss == "binder" else 2.0 ** 32 * n
+
+
+def _divide(num, den):
+    return num / den if den else np.zeros(np.shape(num))                 # Binder at n = 1: no pairs, loss 0
+
+
+def _expected_from_parts(dist, loss, n):
+    """(loss[L] f64, num[L]) from rc_partition_distances' outputs: num = Σ_s numerator, exact.
+    Range: a VI numerator is below 2·Phiq(n) <= 2·(n·log n·2^32 + n), so Σ_s stays below 2^63 while m·n·log n < 2^30 — always
+    within the exact searches' capacity m·n <= 2^26 (log n < 16), but not for every call this entry accepts (m·n < 2^31).  The
+    rows are therefore summed in two 32-bit halves, each of which fits int64 (m < 2^31 terms below 2^32, and terms below
+    2^20), and joined as Python integers; num is an int64 array when every sum fits and an object array of Python integers
+    otherwise."""
+    numer = _numerators(dist, loss)
+    m = numer.shape[1]
+    lo, hi = (numer & 0xFFFFFFFF).sum(axis=1), (numer >> 32).sum(axis=1)
+    sums = [(int(h) << 32) + int(l) for h, l in zip(hi, lo)]
+    den = _denominator(loss, n) * m
+    losses = np.array([x / den if den else 0.0 for x in sums])
+    fits = all(x < 2 ** 63 for x in sums)
+    return losses, np.array(sums, dtype=np.int64 if fits else object)
+
+
+def _distance_inputs(labellings, samples):
+    labs = np.stack([_labels(c) for c in np.atleast_2d(np.asarray(labellings))])
+    S = _sample_matrix(samples)
+    if labs.shape[1] != S.shape[1]:
+        raise ValueError("every labelling must have as many labels as the samples")
+    return labs, S
+
+
+def partitiondistances(labellings, samples, loss="VI", device: int = 0):
+    """The distance from each of L labellings (L×n, or one labelling) to each of the m samples (an MCMCResult, anything with
+    `.clusts`, or an m×n label matrix), on the GPU in exact integers (rc_partition_distances, csrc/partdist.inc.hip); there is
+    no CPU fallback.  loss: "binder" — normalised as binderloss does it — or "VI" / "ID" in nats, as varinfo and
+    infodist(normalised=False) give them.  Returns (dist, info): dist is L×m f64; info["num"] the L×m int64 numerators dist was
+    divided from once (Binder: disagreeing pairs; VI, ID: units of 2^-32/n nats, in the fixed point of the exact searches, so
+    equal distances compare equal), info["K_labellings"], info["K_samples"] the cluster counts, info["kernel_ms"]."""
+    if loss not in _DIST_LOSSES:
+        raise ValueError("Invalid loss function specifier.")
+    labs, S = _distance_inputs(labellings, samples)
+    dist = _lib.partition_distances(labs, S, want_sq=loss == "binder", want_phi=loss != "binder", device=device)
+    num = _numerators(dist, loss)
+    info = dict(num=num, K_labellings=dist["lab_marg"][:, 2].copy(), K_samples=dist["smp_marg"][:, 2].copy(), kernel_ms=dist["kernel_ms"])
+    return _divide(num, _denominator(loss, S.shape[1])), info
+
+
+def expecteddistances(labellings, samples, loss="VI", device: int = 0):
+    """The posterior expected Binder loss, VI or ID of each of L labellings: the mean over the samples of partitiondistances'
+    rows, summed in integers on the host and divided once.  Returns (loss[L], num[L]): num = Σ_s numerator, exact (int64, or
+    Python integers in an object array where a sum passes 2^63 — possible only beyond the exact searches' capacity).  For "VI",
+    num is rc_vi_search's loss_num plus its constant; expectedvi / expectedid / expectedloss(…, "binder") give the same
+    values in f64 on the host, one labelling at a time."""
+    if loss not in _DIST_LOSSES:
+        raise ValueError("Invalid loss function specifier.")
+    labs, S = _distance_inputs(labellings, samples)
+    dist = _lib.partition_distances(labs, S, want_sq=loss == "binder", want_phi=loss != "binder", device=device)
+    return _expected_from_parts(dist, loss, S.shape[1])
+
+
+def _sortlabels(x):
+    """utils.jl:69-74: relabel by order of first appearance"""
+    _, first, inv = np.unique(x, return_index=True, return_inverse=True)
+    return (np.argsort(np.argsort(first))[inv] + 1).astype(np.int64)
+
+
+def credibleball_from_distances(num, K, alpha: float = 0.05) -> dict:
+    """The selection behind credibleball, on the host, for callers that hold the distances already (rc_partition_distances
+    through the C ABI): num[s] is the integer distance of sample s from the point estimate, K[s] its number of clusters.
+      k = m − ⌊α·m + 1e-9⌋;  ε = the k-th smallest distance;  the ball is every sample with distance <= ε — ties at ε are in,
+      so it may hold more than k samples (a ball is defined by its radius);
+      horizontal: the ball's samples at distance ε;  upper: among the ball's samples with the fewest clusters, those of greatest
+      distance;  lower: among the ball's samples with the most clusters, those of greatest distance
+    (Wade & Ghahramani's vertical upper / lower and horizontal bounds; mcclust.ext's credibleball).  Returns a dict: epsilon_num,
+    level = |ball|/m, ball (bool[m]) and horizontal_index, upper_index, lower_index (ascending 0-based sample indices)."""
+    if not 0.0 <= alpha < 1.0:
+        raise ValueError("alpha must lie in [0, 1)")
+    num, K = np.asarray(num), np.asarray(K)
+    if num.ndim != 1 or num.shape != K.shape or len(num) == 0:
+        raise ValueError("num and K must be vectors of the same positive length")
+    m = len(num)
+    k = m - int(np.floor(alpha * m + 1e-9))
+    eps = np.sort(num)[k - 1]
+    ball = num <= eps
+
+    def farthest(mask):
+        return np.flatnonzero(mask & (num == num[mask].max()))
+
+    return dict(epsilon_num=int(eps), level=int(ball.sum()) / m, ball=ball, horizontal_index=np.flatnonzero(ball & (num == eps)),
+                upper_index=farthest(ball & (K == K[ball].min())), lower_index=farthest(ball & (K == K[ball].max())))
+
+
+def credibleball(clust, samples, loss="VI", alpha: float = 0.05, device: int = 0) -> dict:
+    """The (1 − alpha) credible ball around the point estimate `clust` (Wade & Ghahramani 2018; mcclust.ext's credibleball):
+    the smallest ball in the metric `loss` ("binder", "VI" or "ID") that holds at least 1 − alpha of the samples (an
+    MCMCResult, anything with `.clusts`, or an m×n label matrix), and its three bounds — see credibleball_from_distances for
+    the definition.  The distances come from the GPU in exact integers (partitiondistances), so ties are ties.
+    Returns that function's dict and: epsilon (the radius in the units of partitiondistances), distances and distances_num (m),
+    K (m, the samples' cluster counts), and horizontal, upper, lower: the distinct partitions among the samples of each bound,
+    sortlabels'd, in order of first occurrence."""
+    if loss not in _DIST_LOSSES:
+        raise ValueError("Invalid loss function specifier.")
+    if not 0.0 <= alpha < 1.0:
+        raise ValueError("alpha must lie in [0, 1)")
+    labs, S = _distance_inputs(clust, samples)
+    if labs.shape[0] != 1:
+        raise ValueError("clust must be one labelling")
+    dist, info = partitiondistances(labs, S, loss, device=device)
+    out = credibleball_from_distances(info["num"][0], info["K_samples"], alpha)
+    out.update(epsilon=float(_divide(out["epsilon_num"], _denominator(loss, S.shape[1]))), distances=dist[0], distances_num=info["num"][0],
+               K=info["K_samples"], kernel_ms=info["kernel_ms"])
+    for name in ("horizontal", "upper", "lower"):
+        parts, seen = [], set()
+        for i in out[name + "_index"]:
+            c = _sortlabels(S[i])
+            if c.tobytes() not in seen:
+                seen.add(c.tobytes())
+                parts.append(c)
+        out[name] = np.stack(parts)
+    return out
 
 
 def lossmatrix(samples, loss: str = "VI", device: int = 0):

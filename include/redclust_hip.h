@@ -689,6 +689,41 @@ int32_t rc_partition_distances(int32_t device, const int64_t *samples /* m×n, l
                                int64_t *sq_out /* L×m or NULL */, int64_t *phi_out /* L×m or NULL */,
                                int64_t *lab_marg /* L×3 or NULL */, int64_t *smp_marg /* m×3 or NULL */, double *kernel_ms);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Relabelling: each of m samples renamed onto a pivot labelling (a point estimate), and per point how often it lands in
+ * each of the pivot's clusters — pivot relabelling in exact integers.  No context: errors through rc_last_error(NULL).
+ * DESIGN.md §8 "Relabelling".
+ *
+ * Dense ids are given in ascending label order to the pivot's K_p clusters and to the K_s clusters of sample s;
+ * N[k][l] = #{j : pivot[j] has dense id k, samples[s][j] has dense id l}.  The sample's clusters are matched to the
+ * pivot's by the injective partial matching of size min(K_p, K_s) that maximises the matched overlap Σ N[σ(l)][l], found
+ * by shortest augmenting paths with potentials on cost = −N: rows are the side with fewer clusters (the pivot on a tie),
+ * inserted in ascending dense id from zero potentials; every step goes to the unused column of minimum reduced cost, the
+ * smallest column id among equals.  The matching, not only its value, is therefore a function of the inputs.
+ *   labels_out[s][j]  the label of point j in sample s in the pivot's names; 0 where its cluster is unmatched (K_s > K_p only)
+ *   maps_out[s][t]    the pivot label that the t-th smallest label of sample s is sent to; 0 unmatched; −1 for t >= K_s.
+ *                     maps_width columns, at least the largest K_s
+ *   overlap_out[s]    the matched overlap: n − overlap points disagree with the pivot after renaming
+ *   counts_out[j][k]  k = 0..K_p: the samples whose renamed label of point j is the pivot's k-th smallest label; column 0
+ *                     counts unmatched.  Every row sums to m.  K_p is passed in so that the caller can size the array; it
+ *                     must be the pivot's cluster count.
+ * labels_out, maps_out and kernel_ms (device time of the call's kernels) may be NULL.  Every sample's outputs are a pure
+ * function of (pivot, sample): the same whatever m is and however the call is chunked.
+ *
+ * Errors, all before any device work.  RC_ERR_ARG: samples, pivot, overlap_out or counts_out NULL; m or n < 1; a label
+ * outside 1..n (the message names the sample and the position); K_p that is not the pivot's cluster count; maps_width
+ * below the largest K_s; a device that is not there.  RC_ERR_CAPACITY: n > 32767 (checked before any array is read), a
+ * pivot or a sample of more than 1024 clusters.  m is otherwise unbounded in memory terms: the samples go through a device
+ * workspace of about 1 GiB in chunks, counts accumulating on the device.  The contingency table of a sample is kept in LDS
+ * when it fits 128 KiB beside the assignment's vectors, else in global memory; RC_RELABEL_TABLE_GLOBAL=1 in the
+ * environment (read at every call) does the latter for every sample and RC_RELABEL_WORKSPACE_KIB=<k> shrinks the
+ * workspace so that small calls are chunked — the same integers either way; for tests.
+ * ------------------------------------------------------------------------------------------------------------- */
+int32_t rc_relabel(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n,
+                   const int64_t *pivot /* n, labels 1..n */, int64_t Kp,
+                   int64_t *labels_out /* m×n or NULL */, int64_t *maps_out /* m×maps_width or NULL */, int64_t maps_width,
+                   int64_t *overlap_out /* m */, void *counts_out /* uint32_t n×(Kp+1) */, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

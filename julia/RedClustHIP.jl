@@ -673,4 +673,38 @@ end
 
 export partitiondistances, credibleball
 
+"""
+    relabel(HIPBackend(), result, pivot) -> (labels, maps, overlap, counts, pivot_labels, kernel_ms)
+
+Rename every sample of `result` onto the labelling `pivot` (a point estimate, say) on the GPU in exact integers (rc_relabel):
+each sample's clusters are matched to the pivot's so that the number of points on which the two agree is largest, by shortest
+augmenting paths with the library's fixed tie rule (the smallest column id among equal reduced costs), so the matching is a
+function of the inputs.  `labels` is m×n in the pivot's names (0: the sample's cluster has no counterpart), `maps[s, t]` the
+pivot label that the t-th smallest label of sample s is sent to (0 unmatched, −1 past its clusters), `overlap[s]` the number of
+points on which the renamed sample agrees with the pivot, and `counts[j, k]`, k = 1..K_p+1, the number of samples in which
+point j lands in the pivot's cluster `pivot_labels[k-1]` (column 1: unmatched); `counts ./ m` are allocation probabilities.
+"""
+function relabel(b::HIPBackend, result, pivot::AbstractVector{<:Integer})
+    samples = samplematrix(result)
+    n, m = size(samples)
+    length(pivot) == n || throw(ArgumentError("Length of the input vectors must be equal."))
+    piv = Vector{Int64}(pivot)
+    names = sort(unique(piv))
+    Kp = length(names)
+    W = maximum(length(unique(view(samples, :, s))) for s in 1:m)
+    labels = Matrix{Int64}(undef, n, m)                           # column s = sample s: row-major m×n for the library
+    maps = Matrix{Int64}(undef, W, m)
+    overlap = Vector{Int64}(undef, m)
+    counts = Matrix{UInt32}(undef, Kp + 1, n)                     # row-major n×(K_p+1)
+    ms = Cdouble[0]
+    rc = ccall((:rc_relabel, LIB), Int32,
+               (Int32, Ptr{Int64}, Int64, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Cvoid}, Ptr{Cdouble}),
+               b.device, samples, m, n, piv, Kp, labels, maps, W, overlap, counts, ms)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return (labels = permutedims(labels), maps = permutedims(maps), overlap = overlap, counts = permutedims(counts),
+            pivot_labels = names, kernel_ms = ms[1])
+end
+
+export relabel
+
 end # module

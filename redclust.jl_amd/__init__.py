@@ -15,5 +15,5 @@ from .pointestimate import (getpointestimate, lossmatrix, binderloss, infodist, 
                             summarise, searchpointestimate, expectedloss, expectedvi, expectedid, cocluster_counts,
                             posterior_counts, posterior_coclustering, hclust, hclustpointestimate, expectedlosses,
                             linkage_matrix, leaf_order, partitiondistances, expecteddistances, credibleball,
-                            credibleball_from_distances)
+                            credibleball_from_distances, relabel, Relabelling)
 from .predict import predict, Prediction  # noqa: F401

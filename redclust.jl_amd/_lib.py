@@ -88,7 +88,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
             os.path.join(CSRC, "mixture.inc.hip"), os.path.join(CSRC, "kmeans.inc.hip"),
             os.path.join(CSRC, "pointsearch.inc.hip"), os.path.join(CSRC, "visearch.inc.hip"),
             os.path.join(CSRC, "samplecounts.inc.hip"), os.path.join(CSRC, "hclust.inc.hip"), os.path.join(CSRC, "predict.inc.hip"),
-            os.path.join(CSRC, "partdist.inc.hip"), HEADER]
+            os.path.join(CSRC, "partdist.inc.hip"), os.path.join(CSRC, "relabel.inc.hip"), HEADER]
     if not force and os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(s) for s in srcs):
         return SO
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-o", SO, srcs[0]]
@@ -213,6 +213,8 @@ SIGNATURES = {
                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "rc_partition_distances": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "rc_relabel": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                               C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "rc_layout_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rc_event_overhead_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "rc_kernel_timing": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -962,6 +964,31 @@ def partition_distances(labels, samples, want_sq: bool = True, want_phi: bool = 
         raise _error(rc, L.rc_last_error(None).decode())
     return dict(sq=None if sq is None else sq[:nl, :m], phi=None if phi is None else phi[:nl, :m], lab_marg=lm[:nl], smp_marg=sm[:m],
                 kernel_ms=float(ms.value))
+
+
+def relabel(samples, pivot, want_labels: bool = True, want_maps: bool = True, device: int = 0) -> dict:
+    """rc_relabel for m×n samples and a pivot of n labels (int64 in 1..n): a dict with labels (m×n int64, or None), maps (m × the
+    largest K_s, or None), overlap (m), counts (n×(K_p+1) uint32), pivot_labels (the K_p names, ascending) and kernel_ms."""
+    L = lib()
+    S = np.ascontiguousarray(samples, dtype=np.int64)
+    c = np.ascontiguousarray(pivot, dtype=np.int64)
+    if S.ndim != 2 or c.ndim != 1 or S.shape[1] != c.shape[0]:
+        raise ValueError("samples must be m×n and the pivot n labels")
+    m, n = S.shape
+    names = np.unique(c).astype(np.int64)
+    Kp = len(names)
+    valid = S.size > 0 and S.min() >= 1 and S.max() <= n            # otherwise the library names the label
+    W = max(np.count_nonzero(np.bincount(row)) for row in S) if valid else 1       # the largest K_s, without a sort
+    labels = np.zeros((max(m, 1), max(n, 1)), np.int64) if want_labels else None
+    maps = np.zeros((max(m, 1), max(W, 1)), np.int64) if want_maps else None
+    overlap = np.zeros(max(m, 1), np.int64)
+    counts = np.zeros((max(n, 1), Kp + 1), np.uint32)
+    ms = C.c_double()
+    rc = L.rc_relabel(int(device), S.ctypes.data, m, n, c.ctypes.data, Kp, None if labels is None else labels.ctypes.data,
+                      None if maps is None else maps.ctypes.data, W, overlap.ctypes.data, counts.ctypes.data, C.byref(ms))
+    if rc != RC_OK:
+        raise _error(rc, L.rc_last_error(None).decode())
+    return dict(labels=labels, maps=maps, overlap=overlap, counts=counts, pivot_labels=names, kernel_ms=float(ms.value))
 
 
 def sample_k(n: int, r, p, seed: int = 0, device: int = 0):

@@ -7850,3 +7850,4 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "hclust.inc.hip"
 #include "predict.inc.hip"
 #include "partdist.inc.hip"
+#include "relabel.inc.hip"

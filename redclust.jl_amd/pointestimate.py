@@ -4,6 +4,7 @@ src/summaries.jl.  The pairwise loss matrix of the MPEL search and every pair me
 from __future__ import annotations
 
 import sys
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -547,6 +548,53 @@ def expecteddistances(labellings, samples, loss="VI", device: int = 0):
     labs, S = _distance_inputs(labellings, samples)
     dist = _lib.partition_distances(labs, S, want_sq=loss == "binder", want_phi=loss != "binder", device=device)
     return _expected_from_parts(dist, loss, S.shape[1])
+
+
+@dataclass
+class Relabelling:
+    """Posterior samples renamed onto a pivot labelling.  labels[s, j]: the label of point j in sample s in the pivot's names, 0
+    where the sample's cluster has no counterpart (only when the sample has more clusters than the pivot).  maps[s, t]: the pivot
+    label that the t-th smallest label of sample s is sent to, 0 unmatched, -1 for t >= K_s.  overlap[s]: the points on which
+    the renamed sample and the pivot agree.  counts[j, k], k = 0..K_p: the samples in which point j lands in the pivot's cluster
+    pivot_labels[k - 1]; column 0 counts unmatched.  kernel_ms: device time of the kernels."""
+    labels: np.ndarray
+    maps: np.ndarray
+    overlap: np.ndarray
+    counts: np.ndarray
+    pivot_labels: np.ndarray
+    kernel_ms: float = 0.0
+
+    def probabilities(self) -> np.ndarray:
+        """counts / m, n×(K_p + 1): the share of samples in which each point belongs to each of the pivot's clusters."""
+        return self.counts / float(len(self.overlap))
+
+    def allocation(self) -> np.ndarray:
+        """Per point the pivot label of largest count, the smaller column on a tie; 0 (unmatched) is possible."""
+        return np.concatenate([[0], self.pivot_labels]).astype(np.int64)[np.argmax(self.counts, axis=1)]
+
+    def uncertainty(self) -> np.ndarray:
+        """Per point 1 − its largest allocation probability."""
+        return 1.0 - self.counts.max(axis=1) / float(len(self.overlap))
+
+
+def relabel(result_or_samples, pivot, *, device: int = 0) -> Relabelling:
+    """Rename every sample (an MCMCResult, anything with `.clusts`, or an m×n label matrix) onto the labelling `pivot` — a point
+    estimate, say — on the GPU in exact integers (rc_relabel, csrc/relabel.inc.hip); there is no CPU fallback.  Each sample's
+    clusters are matched to the pivot's so that the number of points on which the two agree is largest (a linear assignment on
+    their contingency table; among optimal matchings the one the fixed tie rule of DESIGN.md §8 "Relabelling" finds), and
+    counts says per point how often it then lands in each of the pivot's clusters."""
+    S = _sample_matrix(result_or_samples)
+    c = _labels(pivot)
+    if c.shape[0] != S.shape[1]:
+        raise ValueError("the pivot must have as many labels as the samples")
+    out = _lib.relabel(S, c, device=device)
+    names = np.unique(np.asarray(pivot).astype(np.int64))
+    if not np.array_equal(names, out["pivot_labels"]):              # _labels compacted a pivot with names above n: give them back
+        back = np.concatenate([[0], names])
+        for key in ("labels", "maps"):
+            a = out[key]
+            out[key] = np.where(a > 0, back[np.maximum(a, 0)], a)
+    return Relabelling(out["labels"], out["maps"], out["overlap"], out["counts"], names, out["kernel_ms"])
 
 
 def _sortlabels(x):

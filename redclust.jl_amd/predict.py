@@ -47,6 +47,31 @@ class Prediction:
                 out[s, n + own] = np.setdiff1d(every, S[s], assume_unique=False)[:len(own)]
         return out
 
+    def allocation(self, relabelling, samples) -> np.ndarray:
+        """q×(K_p + 1): the share of samples in which each new observation goes to each of the pivot's clusters, through a
+        Relabelling of the same samples (pointestimate.relabel): the label a new point drew under sample s is one of that
+        sample's names, its rank among them the column of relabelling.maps[s] that says which pivot cluster it became.
+        Columns as relabelling.counts: column k >= 1 is the pivot's cluster pivot_labels[k - 1]; column 0 is a cluster of
+        its own (label 0) or a cluster of the sample that the pivot has no counterpart for.  Every row sums to 1."""
+        S = _label_matrix(samples)
+        m, q = self.labels.shape
+        if S.shape[0] != m or relabelling.maps.shape[0] != m:
+            raise ValueError(f"samples and the relabelling must be of the {m} samples of the prediction")
+        names = np.asarray(relabelling.pivot_labels, dtype=np.int64)
+        counts = np.zeros((q, len(names) + 1), np.int64)
+        for s in range(m):
+            own = np.unique(S[s])
+            lab = self.labels[s]
+            t = np.searchsorted(own, lab)
+            known = (lab > 0) & (t < len(own))
+            known &= own[np.minimum(t, len(own) - 1)] == lab
+            if not np.all(known | (lab == 0)):
+                raise ValueError(f"a label of the prediction is not a label of sample {s + 1}")
+            to = np.where(known, relabelling.maps[s][np.where(known, t, 0)], 0)
+            col = np.where(to > 0, np.searchsorted(names, np.maximum(to, 1)) + 1, 0)
+            counts[np.arange(q), col] += 1
+        return counts / float(m)
+
 
 def _label_matrix(samples) -> np.ndarray:
     clusts = samples.clusts if hasattr(samples, "clusts") else samples

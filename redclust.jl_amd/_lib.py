@@ -3,6 +3,7 @@ missing or no GPU is present, every compute entry point raises."""
 from __future__ import annotations
 
 import ctypes as C
+import glob
 import os
 import subprocess
 
@@ -32,14 +33,23 @@ class RedClustDomainError(RedClustHIPError, ValueError):
     ArgumentError there, so this one is a ValueError as well."""
 
 
-def _error(code, msg):
-    return (RedClustDomainError if code == -4 else RedClustHIPError)(code, msg)
+def _check(rc, handle=None):
+    """Raise the library's error for a return code other than RC_OK.  handle: the context whose error buffer holds the text
+    (None: the calling thread's)."""
+    if rc != RC_OK:
+        raise (RedClustDomainError if rc == -4 else RedClustHIPError)(rc, lib().rc_last_error(handle).decode())
 
 
 class RcParams(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("delta1", "delta2", "alpha", "beta", "zeta", "gamma", "eta", "sigma",
                                           "u", "v")] + [("maxK", C.c_int64), ("repulsion", C.c_uint8),
                                                         ("pad_", C.c_uint8 * 7)]
+
+
+def _params_struct(params: dict) -> RcParams:
+    g = params.get
+    return RcParams(g("delta1"), g("delta2"), g("alpha"), g("beta"), g("zeta"), g("gamma"), g("eta", 1.0), g("sigma", 1.0),
+                    g("u", 1.0), g("v", 1.0), int(g("maxK", 0)), int(bool(g("repulsion", True))))
 
 
 class RcPairMeasures(C.Structure):
@@ -80,22 +90,26 @@ class RcSweepStats(C.Structure):
     _fields_ = [("n_changes", C.c_int64), ("n_rounds", C.c_int64), ("K", C.c_int64)]
 
 
-def build(force: bool = False, verbose: bool = False) -> str:
-    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, "redclust_hip.hip"), os.path.join(CSRC, "hostutil.inc.hip"),
-            os.path.join(CSRC, "pointestimate.inc.hip"), os.path.join(CSRC, "cluster.inc.hip"), os.path.join(CSRC, "kmedoids.inc.hip"),
-            os.path.join(CSRC, "chain.inc.hip"), os.path.join(CSRC, "chains.inc.hip"), os.path.join(CSRC, "samplek.inc.hip"),
-            os.path.join(CSRC, "mixture.inc.hip"), os.path.join(CSRC, "kmeans.inc.hip"),
-            os.path.join(CSRC, "pointsearch.inc.hip"), os.path.join(CSRC, "visearch.inc.hip"),
-            os.path.join(CSRC, "samplecounts.inc.hip"), os.path.join(CSRC, "hclust.inc.hip"), os.path.join(CSRC, "predict.inc.hip"),
-            os.path.join(CSRC, "partdist.inc.hip"), os.path.join(CSRC, "relabel.inc.hip"), HEADER]
-    if not force and os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(s) for s in srcs):
-        return SO
-    cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-o", SO, srcs[0]]
+def _compile(so, defines=(), verbose=False) -> str:
+    cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared"] + [f"-D{d}" for d in defines] + \
+          ["-o", so, os.path.join(CSRC, "redclust_hip.hip")]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd, cwd=CSRC)
-    return SO
+    return so
+
+
+def _sources() -> list:
+    """what the library is built from: the translation unit, every include beside it, the header"""
+    return [os.path.join(CSRC, "redclust_hip.hip")] + sorted(glob.glob(os.path.join(CSRC, "*.inc.hip"))) + \
+           sorted(glob.glob(os.path.join(CSRC, "*.inc.hpp"))) + [HEADER]
+
+
+def build(force: bool = False, verbose: bool = False) -> str:
+    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU) unless it is newer than its sources."""
+    if not force and os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(s) for s in _sources()):
+        return SO
+    return _compile(SO, verbose=verbose)
 
 
 def build_diag(extra_defines=(), name="libredclust_hip_diag.so", verbose: bool = False) -> str:
@@ -104,13 +118,7 @@ def build_diag(extra_defines=(), name="libredclust_hip_diag.so", verbose: bool =
     the box that uses it, select it with RC_LIB_PATH)."""
     out_dir = os.path.join(ROOT, "build_exp")
     os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, name)
-    cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DRC_DIAG"] + [f"-D{d}" for d in extra_defines] + \
-          ["-o", so, os.path.join(CSRC, "redclust_hip.hip")]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd, cwd=CSRC)
-    return so
+    return _compile(os.path.join(out_dir, name), ("RC_DIAG", *extra_defines), verbose)
 
 
 _dp = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
@@ -259,9 +267,7 @@ class Context:
             assert logD.shape == D.shape
             lp = logD.ctypes.data_as(C.c_void_p)
         h = C.c_void_p()
-        rc = self.L.rc_create(self.n, D.ctypes.data_as(C.c_void_p), lp, storage_bits, device, kcap, C.byref(h))
-        if rc != RC_OK:
-            raise _error(rc, self.L.rc_last_error(None).decode())
+        _check(self.L.rc_create(self.n, D.ctypes.data_as(C.c_void_p), lp, storage_bits, device, kcap, C.byref(h)))
         self.h = h
 
     @classmethod
@@ -275,10 +281,8 @@ class Context:
         self.n = int(pts.shape[0])
         self.dim = int(pts.shape[1])
         h = C.c_void_p()
-        rc = self.L.rc_create_from_points(self.n, int(pts.shape[1]), pts.ctypes.data_as(C.c_void_p), storage_bits, device,
-                                          kcap, C.byref(h))
-        if rc != RC_OK:
-            raise _error(rc, self.L.rc_last_error(None).decode())
+        _check(self.L.rc_create_from_points(self.n, int(pts.shape[1]), pts.ctypes.data_as(C.c_void_p), storage_bits, device,
+                                            kcap, C.byref(h)))
         self.h = h
         return self
 
@@ -296,8 +300,7 @@ class Context:
         return out
 
     def _chk(self, rc):
-        if rc != RC_OK:
-            raise _error(rc, self.L.rc_last_error(self.h).decode())
+        _check(rc, self.h)
 
     def close(self):
         if getattr(self, "h", None):
@@ -312,7 +315,8 @@ class Context:
 
     def set_params(self, delta1, delta2, alpha, beta, zeta, gamma, eta=1.0, sigma=1.0, u=1.0, v=1.0,
                    repulsion=True, maxK=0, **_ignored):
-        P = RcParams(delta1, delta2, alpha, beta, zeta, gamma, eta, sigma, u, v, int(maxK), int(bool(repulsion)))
+        P = _params_struct(dict(delta1=delta1, delta2=delta2, alpha=alpha, beta=beta, zeta=zeta, gamma=gamma, eta=eta, sigma=sigma,
+                                u=u, v=v, repulsion=repulsion, maxK=maxK))
         self._chk(self.L.rc_set_params(self.h, C.byref(P)))
 
     def set_state(self, clusts):
@@ -585,9 +589,7 @@ class Comm:
     @staticmethod
     def unique_id() -> bytes:
         buf = (C.c_uint8 * 128)()
-        rc = lib().rc_comm_unique_id(buf)
-        if rc != RC_OK:
-            raise _error(rc, lib().rc_last_error(None).decode())
+        _check(lib().rc_comm_unique_id(buf))
         return bytes(buf)
 
     def __init__(self, device_ids, rank_offset: int = 0, world_size: int | None = None, unique_id: bytes | None = None):
@@ -597,9 +599,7 @@ class Comm:
         devs = (C.c_int32 * len(self.devices))(*self.devices)
         idb = (C.c_uint8 * 128)(*unique_id) if unique_id is not None else None
         h = C.c_void_p()
-        rc = self.L.rc_comm_create(len(self.devices), devs, int(rank_offset), world, idb, C.byref(h))
-        if rc != RC_OK:
-            raise _error(rc, self.L.rc_last_error(None).decode())
+        _check(self.L.rc_comm_create(len(self.devices), devs, int(rank_offset), world, idb, C.byref(h)))
         self.h = h
 
     def allreduce_counts(self, ctxs, num_samples):
@@ -607,9 +607,7 @@ class Comm:
         hs = (C.c_void_p * len(ctxs))(*[c.h for c in ctxs])
         ns = (C.c_int64 * len(ctxs))(*[int(x) for x in num_samples])
         tot, ms = C.c_int64(0), C.c_double(0)
-        rc = self.L.rc_comm_allreduce_counts(self.h, hs, ns, C.byref(tot), C.byref(ms))
-        if rc != RC_OK:
-            raise _error(rc, self.L.rc_last_error(None).decode())
+        _check(self.L.rc_comm_allreduce_counts(self.h, hs, ns, C.byref(tot), C.byref(ms)))
         return int(tot.value), float(ms.value)
 
     def close(self):
@@ -643,9 +641,7 @@ def run_chains(device_ids, params: dict, init_clusts, numiters, burnin, thin, nu
     else:
         points = np.ascontiguousarray(points, dtype=np.float64); keep.append(points)
         n = int(points.shape[0]); inp.points = points.ctypes.data; inp.dim = int(points.shape[1])
-    g = params.get
-    prm = RcParams(g("delta1"), g("delta2"), g("alpha"), g("beta"), g("zeta"), g("gamma"), g("eta", 1.0), g("sigma", 1.0),
-                   g("u", 1.0), g("v", 1.0), int(g("maxK", 0)), int(bool(g("repulsion", True))))
+    prm = _params_struct(params)
     init = np.ascontiguousarray(init_clusts, dtype=np.int64); keep.append(init)
     inp.n, inp.storage_bits, inp.kcap, inp.params, inp.init_clusts = n, int(storage_bits), int(kcap), C.pointer(prm), init.ctypes.data
     ns = 0
@@ -657,10 +653,8 @@ def run_chains(device_ids, params: dict, init_clusts, numiters, burnin, thin, nu
                        int(seed), 0, float(r0), float(p0), float(proposalsd_r), None, None, ns)
     post = np.zeros((n, n)) if want_posterior else None
     tot, ms = C.c_int64(0), C.c_double(0)
-    rc = L.rc_run_chains(nch, (C.c_int32 * nch)(*devs), C.byref(inp), C.byref(o), outs,
-                         post.ctypes.data if post is not None else None, C.byref(tot), C.byref(ms))
-    if rc != RC_OK:
-        raise _error(rc, L.rc_last_error(None).decode())
+    _check(L.rc_run_chains(nch, (C.c_int32 * nch)(*devs), C.byref(inp), C.byref(o), outs,
+                           post.ctypes.data if post is not None else None, C.byref(tot), C.byref(ms)))
     for c, res in enumerate(ress):
         res["num_samples"], res["runtime_s"] = int(outs[c].num_samples), float(outs[c].runtime_s)
         res["r_final"], res["p_final"] = float(outs[c].r_final), float(outs[c].p_final)
@@ -674,26 +668,37 @@ def measure_read_ceiling(device: int = 0, mib: int = 2048, reps: int = 5) -> flo
     """rc_measure_read_ceiling: the device's streaming-read rate in GB/s as measured now (buffer >> Infinity Cache)."""
     L = lib()
     out = C.c_double(0)
-    rc = L.rc_measure_read_ceiling(int(device), int(mib), int(reps), C.byref(out))
-    if rc != RC_OK:
-        raise _error(rc, L.rc_last_error(None).decode())
+    _check(L.rc_measure_read_ceiling(int(device), int(mib), int(reps), C.byref(out)))
     return float(out.value)
+
+
+def _label_matrix(x, what="samples"):
+    """x as a C-contiguous int64 matrix of labels, one labelling per row"""
+    x = np.ascontiguousarray(x, dtype=np.int64)
+    if x.ndim != 2:
+        raise ValueError(f"{what} must be an m×n matrix of labels")
+    return x
+
+
+def _psm_result(labels, runs, nruns, n, best, ms, **extra) -> dict:
+    """The dict of the searches: labels (nruns×n), one array per field of RcPsmRun, best, kernel_ms and what extra names."""
+    out = dict(labels=labels[:nruns, :n], best=int(best.value), kernel_ms=float(ms.value), **extra)
+    for k, ty in RcPsmRun._fields_:
+        out[k] = np.array([getattr(r, k) for r in runs[:nruns]], dtype=np.float64 if ty is C.c_double else np.int64)
+    out["converged"] = out["converged"].astype(bool)
+    return out
 
 
 def loss_matrix(samples, loss: int, device: int = 0, want_matrix: bool = True):
     """rc_loss_matrix: (lossmatrix or None, column sums, 0-based argmin, kernel ms) for an m×n int64 label matrix."""
     L = lib()
-    S = np.ascontiguousarray(samples, dtype=np.int64)
-    if S.ndim != 2:
-        raise ValueError("samples must be an m×n matrix of labels")
+    S = _label_matrix(samples)
     m, n = S.shape
     M = np.zeros((m, m)) if want_matrix else None
     cs = np.zeros(m)
     am, ms = C.c_int64(), C.c_double()
-    rc = L.rc_loss_matrix(device, S.reshape(-1), m, n, int(loss), None if M is None else M.ctypes.data_as(C.c_void_p),
-                          cs.ctypes.data_as(C.c_void_p), C.byref(am), C.byref(ms))
-    if rc != RC_OK:
-        raise RedClustHIPError(rc, L.rc_last_error(None).decode())
+    _check(L.rc_loss_matrix(device, S.reshape(-1), m, n, int(loss), None if M is None else M.ctypes.data_as(C.c_void_p),
+                            cs.ctypes.data_as(C.c_void_p), C.byref(am), C.byref(ms)))
     return M, cs, int(am.value), float(ms.value)
 
 
@@ -713,38 +718,26 @@ def psm_search(counts, numsamples: int, loss: int, init, order, maxK: int = 0, m
     if ctx is not None:
         if n != ctx.n:
             raise ValueError("init must have the context's n columns")
-        rc = L.rc_psm_search_ctx(ctx.h, int(numsamples), int(loss), nruns, init.ctypes.data, order.ctypes.data, int(maxK),
-                                 int(maxsweeps), labels.ctypes.data, runs, C.byref(best), C.byref(ms))
-        if rc != RC_OK:
-            raise _error(rc, L.rc_last_error(ctx.h).decode())
+        _check(L.rc_psm_search_ctx(ctx.h, int(numsamples), int(loss), nruns, init.ctypes.data, order.ctypes.data, int(maxK),
+                                   int(maxsweeps), labels.ctypes.data, runs, C.byref(best), C.byref(ms)), ctx.h)
     else:
         cnt = np.ascontiguousarray(counts, dtype=np.uint32)
         if cnt.shape != (n, n):
             raise ValueError("counts must be an n×n matrix matching init")
-        rc = L.rc_psm_search(int(device), cnt.ctypes.data, int(numsamples), n, int(loss), nruns, init.ctypes.data,
-                             order.ctypes.data, int(maxK), int(maxsweeps), labels.ctypes.data, runs, C.byref(best), C.byref(ms))
-        if rc != RC_OK:
-            raise _error(rc, L.rc_last_error(None).decode())
-    out = dict(labels=labels[:nruns, :n], best=int(best.value), kernel_ms=float(ms.value))
-    for k, ty in RcPsmRun._fields_:
-        out[k] = np.array([getattr(r, k) for r in runs[:nruns]], dtype=np.float64 if ty is C.c_double else np.int64)
-    out["converged"] = out["converged"].astype(bool)
-    return out
+        _check(L.rc_psm_search(int(device), cnt.ctypes.data, int(numsamples), n, int(loss), nruns, init.ctypes.data,
+                               order.ctypes.data, int(maxK), int(maxsweeps), labels.ctypes.data, runs, C.byref(best), C.byref(ms)))
+    return _psm_result(labels, runs, nruns, n, best, ms)
 
 
 def samples_counts(samples, device: int = 0):
     """rc_samples_counts: (n×n uint32 co-clustering counts, kernel ms) of an m×n int64 label matrix (labels 1..n), built on
     the device: counts[i, j] = number of samples in which i and j share a label."""
     L = lib()
-    S = np.ascontiguousarray(samples, dtype=np.int64)
-    if S.ndim != 2:
-        raise ValueError("samples must be an m×n matrix of labels")
+    S = _label_matrix(samples)
     m, n = S.shape
     out = np.empty((max(n, 1), max(n, 1)), np.uint32)
     ms = C.c_double()
-    rc = L.rc_samples_counts(int(device), S.ctypes.data, m, n, out.ctypes.data, C.byref(ms))
-    if rc != RC_OK:
-        raise _error(rc, L.rc_last_error(None).decode())
+    _check(L.rc_samples_counts(int(device), S.ctypes.data, m, n, out.ctypes.data, C.byref(ms)))
     return out, float(ms.value)
 
 
@@ -752,11 +745,9 @@ def psm_search_samples(samples, loss: int, init, order, maxK: int = 0, maxsweeps
     """rc_psm_search_samples: psm_search on the counts of an m×n int64 label matrix (labels 1..n), which are built on the
     device and stay there.  Returns psm_search's dict and counts_ms, the device time of the counts kernel."""
     L = lib()
-    S = np.ascontiguousarray(samples, dtype=np.int64)
+    S = _label_matrix(samples)
     init = np.ascontiguousarray(init, dtype=np.int64)
     order = np.ascontiguousarray(order, dtype=np.int32)
-    if S.ndim != 2:
-        raise ValueError("samples must be an m×n matrix of labels")
     if init.ndim != 2 or init.shape != order.shape or init.shape[1] != S.shape[1]:
         raise ValueError("init and order must be nruns×n arrays of the same shape, n the samples' length")
     m, n = S.shape
@@ -764,24 +755,16 @@ def psm_search_samples(samples, loss: int, init, order, maxK: int = 0, maxsweeps
     labels = np.zeros((max(nruns, 1), max(n, 1)), np.int64)
     runs = (RcPsmRun * max(nruns, 1))()
     best, ms, cms = C.c_int32(-1), C.c_double(), C.c_double()
-    rc = L.rc_psm_search_samples(int(device), S.ctypes.data, m, n, int(loss), nruns, init.ctypes.data, order.ctypes.data, int(maxK),
-                                 int(maxsweeps), labels.ctypes.data, runs, C.byref(best), C.byref(ms), C.byref(cms))
-    if rc != RC_OK:
-        raise _error(rc, L.rc_last_error(None).decode())
-    out = dict(labels=labels[:nruns, :n], best=int(best.value), kernel_ms=float(ms.value), counts_ms=float(cms.value))
-    for k, ty in RcPsmRun._fields_:
-        out[k] = np.array([getattr(r, k) for r in runs[:nruns]], dtype=np.float64 if ty is C.c_double else np.int64)
-    out["converged"] = out["converged"].astype(bool)
-    return out
+    _check(L.rc_psm_search_samples(int(device), S.ctypes.data, m, n, int(loss), nruns, init.ctypes.data, order.ctypes.data, int(maxK),
+                                   int(maxsweeps), labels.ctypes.data, runs, C.byref(best), C.byref(ms), C.byref(cms)))
+    return _psm_result(labels, runs, nruns, n, best, ms, counts_ms=float(cms.value))
 
 
 def vi_gtable(n: int) -> np.ndarray:
     """rc_vi_gtable: Gq[x] = llrint((phi(x+1) − phi(x))·2^32), x = 0..n−1, phi(x) = x·log x — the table rc_vi_search decides on."""
     L = lib()
     out = np.zeros(max(int(n), 1), np.int64)
-    rc = L.rc_vi_gtable(int(n), out.ctypes.data)
-    if rc != RC_OK:
-        raise _error(rc, L.rc_last_error(None).decode())
+    _check(L.rc_vi_gtable(int(n), out.ctypes.data))
     return out
 
 
@@ -791,11 +774,9 @@ def vi_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device:
     expected VI), loss_num (the integer Q), sweeps, converged, moves, K, and best, kernel_ms.  entry: the symbol called —
     rc_id_search has the same parameter list (id_search)."""
     L = lib()
-    S = np.ascontiguousarray(samples, dtype=np.int64)
+    S = _label_matrix(samples)
     init = np.ascontiguousarray(init, dtype=np.int64)
     order = np.ascontiguousarray(order, dtype=np.int32)
-    if S.ndim != 2:
-        raise ValueError("samples must be an m×n matrix of labels")
     if init.ndim != 2 or init.shape != order.shape or init.shape[1] != S.shape[1]:
         raise ValueError("init and order must be nruns×n arrays of the same shape, n the samples' length")
     m, n = S.shape
@@ -803,15 +784,9 @@ def vi_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device:
     labels = np.zeros((max(nruns, 1), max(n, 1)), np.int64)
     runs = (RcPsmRun * max(nruns, 1))()
     best, ms = C.c_int32(-1), C.c_double()
-    rc = getattr(L, entry)(int(device), S.ctypes.data, m, n, nruns, init.ctypes.data, order.ctypes.data, int(maxK), int(maxsweeps),
-                           labels.ctypes.data, runs, C.byref(best), C.byref(ms))
-    if rc != RC_OK:
-        raise _error(rc, L.rc_last_error(None).decode())
-    out = dict(labels=labels[:nruns, :n], best=int(best.value), kernel_ms=float(ms.value))
-    for k, ty in RcPsmRun._fields_:
-        out[k] = np.array([getattr(r, k) for r in runs[:nruns]], dtype=np.float64 if ty is C.c_double else np.int64)
-    out["converged"] = out["converged"].astype(bool)
-    return out
+    _check(getattr(L, entry)(int(device), S.ctypes.data, m, n, nruns, init.ctypes.data, order.ctypes.data, int(maxK), int(maxsweeps),
+                             labels.ctypes.data, runs, C.byref(best), C.byref(ms)))
+    return _psm_result(labels, runs, nruns, n, best, ms)
 
 
 def id_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
@@ -831,9 +806,7 @@ def hclust(counts, numsamples, linkage: int, maxcut: int = 0, device: int = 0, c
     and counts_ms for the samples form."""
     L = lib()
     if samples is not None:
-        S = np.ascontiguousarray(samples, dtype=np.int64)
-        if S.ndim != 2:
-            raise ValueError("samples must be an m×n matrix of labels")
+        S = _label_matrix(samples)
         numsamples, n = S.shape
     elif ctx is not None:
         n = ctx.n
@@ -857,8 +830,7 @@ def hclust(counts, numsamples, linkage: int, maxcut: int = 0, device: int = 0, c
     else:
         rc = L.rc_hclust(int(device), cnt.ctypes.data, int(numsamples), n, int(linkage), merges.ctypes.data, bnum.ctypes.data,
                          int(maxcut), vilb.ctypes.data, C.byref(ms))
-    if rc != RC_OK:
-        raise _error(rc, L.rc_last_error(ctx.h if ctx is not None and samples is None else None).decode())
+    _check(rc, ctx.h if ctx is not None and samples is None else None)
     out.update(merges=merges[:max(n - 1, 0)], binder_num=bnum[:n], vilb=vilb[:int(maxcut)], kernel_ms=float(ms.value))
     return out
 
@@ -868,9 +840,7 @@ def hclust_cut(merges, n: int, K: int) -> np.ndarray:
     L = lib()
     mg = np.ascontiguousarray(merges, dtype=HCLUST_MERGE)
     labels = np.zeros(max(int(n), 1), np.int64)
-    rc = L.rc_hclust_cut(mg.ctypes.data, int(n), int(K), labels.ctypes.data)
-    if rc != RC_OK:
-        raise _error(rc, L.rc_last_error(None).decode())
+    _check(L.rc_hclust_cut(mg.ctypes.data, int(n), int(K), labels.ctypes.data))
     return labels[:int(n)]
 
 
@@ -894,8 +864,7 @@ def psm_expected_loss(labels, counts, numsamples: int, loss: int, device: int = 
             raise ValueError("counts must be an n×n matrix matching labels")
         rc = L.rc_psm_expected_loss(int(device), cnt.ctypes.data, int(numsamples), n, int(loss), nl, lab.ctypes.data,
                                     loss_out.ctypes.data, num_out.ctypes.data, C.byref(ms))
-    if rc != RC_OK:
-        raise _error(rc, L.rc_last_error(ctx.h if ctx is not None else None).decode())
+    _check(rc, ctx.h if ctx is not None else None)
     return loss_out[:nl], num_out[:nl], float(ms.value)
 
 
@@ -921,9 +890,7 @@ def predict(Dnew, samples, r, p, params: dict, seed: int = 0, sample_offset: int
         if logDnew.shape != D.shape:
             raise ValueError("logDnew must have Dnew's shape")
         lp = logDnew.ctypes.data
-    g = params.get
-    prm = RcParams(g("delta1"), g("delta2"), g("alpha"), g("beta"), g("zeta"), g("gamma"), g("eta", 1.0), g("sigma", 1.0),
-                   g("u", 1.0), g("v", 1.0), int(g("maxK", 0)), int(bool(g("repulsion", True))))
+    prm = _params_struct(params)
     labels = np.zeros((max(m, 1), max(q, 1)), np.int64)
     mp = np.zeros_like(labels) if want_map else None
     sc = np.zeros((max(m, 1), max(q, 1), int(Kmax) + 1)) if want_scores else None
@@ -935,8 +902,7 @@ def predict(Dnew, samples, r, p, params: dict, seed: int = 0, sample_offset: int
                       int(seed) & M64, int(sample_offset) & M64, int(point_offset) & M64, labels.ctypes.data,
                       None if mp is None else mp.ctypes.data, int(Kmax), None if sc is None else sc.ctypes.data,
                       None if sm is None else sm.ctypes.data, eD.ctypes.data, eL.ctypes.data, C.byref(ms))
-    if rc != RC_OK:
-        raise _error(rc, L.rc_last_error(None).decode())
+    _check(rc)
     out = dict(labels=labels[:m, :q], map=None if mp is None else mp[:m, :q], eD=eD[:q], eL=eL[:q], kernel_ms=float(ms.value))
     if want_scores:
         out["scores"] = sc[:m, :q]
@@ -960,8 +926,7 @@ def partition_distances(labels, samples, want_sq: bool = True, want_phi: bool = 
     ms = C.c_double()
     rc = L.rc_partition_distances(int(device), S.ctypes.data, m, n, nl, lab.ctypes.data, None if sq is None else sq.ctypes.data,
                                   None if phi is None else phi.ctypes.data, lm.ctypes.data, sm.ctypes.data, C.byref(ms))
-    if rc != RC_OK:
-        raise _error(rc, L.rc_last_error(None).decode())
+    _check(rc)
     return dict(sq=None if sq is None else sq[:nl, :m], phi=None if phi is None else phi[:nl, :m], lab_marg=lm[:nl], smp_marg=sm[:m],
                 kernel_ms=float(ms.value))
 
@@ -986,8 +951,7 @@ def relabel(samples, pivot, want_labels: bool = True, want_maps: bool = True, de
     ms = C.c_double()
     rc = L.rc_relabel(int(device), S.ctypes.data, m, n, c.ctypes.data, Kp, None if labels is None else labels.ctypes.data,
                       None if maps is None else maps.ctypes.data, W, overlap.ctypes.data, counts.ctypes.data, C.byref(ms))
-    if rc != RC_OK:
-        raise _error(rc, L.rc_last_error(None).decode())
+    _check(rc)
     return dict(labels=labels, maps=maps, overlap=overlap, counts=counts, pivot_labels=names, kernel_ms=float(ms.value))
 
 
@@ -1001,9 +965,7 @@ def sample_k(n: int, r, p, seed: int = 0, device: int = 0):
         raise ValueError("r and p must be vectors of the same length")
     K = np.zeros(len(r), np.int64)
     ms = C.c_double()
-    rc = L.rc_sample_k(int(device), int(n), len(r), r, p, int(seed) & 0xFFFFFFFFFFFFFFFF, K, C.byref(ms))
-    if rc != RC_OK:
-        raise _error(rc, L.rc_last_error(None).decode())
+    _check(L.rc_sample_k(int(device), int(n), len(r), r, p, int(seed) & 0xFFFFFFFFFFFFFFFF, K, C.byref(ms)))
     return K, float(ms.value)
 
 
@@ -1018,8 +980,7 @@ def oracle_coclustering(points, K: int, radius: float, sigma: float, weights, it
     ms = C.c_double()
     rc = L.rc_oracle_coclustering(int(device), n, dim, X.reshape(-1), int(K), float(radius), float(sigma), W.shape[0],
                                   W.reshape(-1), int(iters_per_chunk), out.reshape(-1), C.byref(ms))
-    if rc != RC_OK:
-        raise _error(rc, L.rc_last_error(None).decode())
+    _check(rc)
     return out, float(ms.value)
 
 
@@ -1029,7 +990,5 @@ def pair_measures(a, b, device: int = 0) -> dict:
     a = np.ascontiguousarray(a, dtype=np.int64)
     b = np.ascontiguousarray(b, dtype=np.int64)
     out = RcPairMeasures()
-    rc = L.rc_pair_measures(device, a, b, len(a), C.byref(out))
-    if rc != RC_OK:
-        raise RedClustHIPError(rc, L.rc_last_error(None).decode())
+    _check(L.rc_pair_measures(device, a, b, len(a), C.byref(out)))
     return {k: getattr(out, k) for k, _ in RcPairMeasures._fields_}

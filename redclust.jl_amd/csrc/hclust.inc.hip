@@ -338,7 +338,7 @@ static bool cut_labels(const Merge *mg, int64_t n, int64_t K, std::vector<int> &
 
 // T of L labellings (slots 1..n as u16, L × n) under the device counts; ms: device time of the kernel, added to *ms
 static int32_t eloss_T(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ldc, int64_t n, const std::vector<unsigned short> &labs,
-                       int64_t L, std::vector<unsigned> &T, double *ms)
+                       int64_t L, std::vector<unsigned> &T, double &ms)
 {
     DeviceBuffers B;
     unsigned short *d_lab;
@@ -350,17 +350,14 @@ static int32_t eloss_T(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld
     HIPCHK(c, hipFuncSetAttribute((const void *)k_eloss, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     TimingEvents ev;
     HIPCHK(c, ev.create());
-    HIPCHK(c, hipEventRecord(ev.e0, st));
+    HIPCHK(c, ev.begin(st));
     k_eloss<<<dim3((unsigned)std::min<int64_t>((n + NWAVE - 1) / NWAVE, 256), (unsigned)((L + EG - 1) / EG)), TPB, lds, st>>>(
         dC, (size_t)ldc, (int)n, d_lab, (int)L, d_T);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(ev.e1, st));
+    HIPCHK(c, ev.end(st));
     T.resize(labs.size());
     HIPCHK(c, hipMemcpyAsync(T.data(), d_T, T.size() * sizeof(unsigned), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    float t = 0;
-    HIPCHK(c, hipEventElapsedTime(&t, ev.e0, ev.e1));
-    if (ms) *ms += t;
+    HIPCHK(c, ev.elapsed_ms(ms));
     return RC_OK;
 }
 
@@ -439,23 +436,22 @@ static int32_t run(rc_ctx *c, hipStream_t st, const char *who, const unsigned *d
     const size_t lds = ((size_t)n * 14 + 15) / 16 * 16;
     TimingEvents ev;
     HIPCHK(c, ev.create());
-    HIPCHK(c, hipEventRecord(ev.e0, st));
+    HIPCHK(c, ev.begin(st));
     rc = triu_sum(c, st, dC, ldc, n, d_tot);
     if (rc != RC_OK) return rc;
     const hipError_t le = linkage == RC_HCLUST_AVERAGE    ? launch<RC_HCLUST_AVERAGE>(dC, ldc, lds, st, d_val0, d_part0, A)
                           : linkage == RC_HCLUST_COMPLETE ? launch<RC_HCLUST_COMPLETE>(dC, ldc, lds, st, d_val0, d_part0, A)
                                                           : launch<RC_HCLUST_SINGLE>(dC, ldc, lds, st, d_val0, d_part0, A);
     if (le != hipSuccess) return fail(c, RC_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(le));
-    HIPCHK(c, hipEventRecord(ev.e1, st));
+    HIPCHK(c, ev.end(st));
     std::vector<Merge> h_mg((size_t)n);
     long long tot = 0;
     if (n > 1) HIPCHK(c, hipMemcpyAsync(h_mg.data(), A.merges, (size_t)(n - 1) * sizeof(Merge), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(binder_num, A.bnum, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(&tot, d_tot, sizeof(long long), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    float t = 0;
-    HIPCHK(c, hipEventElapsedTime(&t, ev.e0, ev.e1));
-    double ms = t;
+    double ms = 0.0;
+    HIPCHK(c, ev.elapsed_ms(ms));
     for (int64_t t = 0; t + 1 < n; ++t)                                 // (the buffer was zeroed: a step the kernel did not take)
         if (h_mg[(size_t)t].a == 0) return fail(c, RC_ERR_STATE, "%s: the kernel stopped before merge %lld of %lld", who, (long long)t + 1, (long long)n - 1);
     std::memcpy(merges_out, h_mg.data(), (size_t)(n - 1) * sizeof(Merge));
@@ -468,7 +464,7 @@ static int32_t run(rc_ctx *c, hipStream_t st, const char *who, const unsigned *d
             if (!cut_labels(h_mg.data(), n, K, work, nullptr, labs.data() + (size_t)(K - 1) * n))
                 return fail(c, RC_ERR_STATE, "%s: the kernel returned an invalid merge sequence", who);
         std::vector<unsigned> T;
-        rc = eloss_T(c, st, dC, ldc, n, labs, maxcut, T, &ms);
+        rc = eloss_T(c, st, dC, ldc, n, labs, maxcut, T, ms);
         if (rc != RC_OK) return rc;
         std::vector<long long> cnt((size_t)n + 1);
         for (int64_t K = 1; K <= maxcut; ++K)
@@ -482,14 +478,10 @@ static int32_t run(rc_ctx *c, hipStream_t st, const char *who, const unsigned *d
 static int32_t run_eloss(rc_ctx *c, hipStream_t st, const char *who, const unsigned *dC, int64_t ldc, int64_t m, int64_t n, int32_t loss,
                          int64_t L, const int64_t *labels, double *loss_out, int64_t *num_out, double *kernel_ms)
 {
-    std::vector<unsigned short> labs((size_t)L * n);
-    for (int64_t l = 0; l < L; ++l)
-        for (int64_t j = 0; j < n; ++j) {
-            const int64_t v = labels[(size_t)l * n + j];
-            if (v < 1 || v > n) return fail(c, RC_ERR_ARG, "%s: label %lld of labelling %lld outside 1..n", who, (long long)v, (long long)l + 1);
-            labs[(size_t)l * n + j] = (unsigned short)v;
-        }
-    int32_t rc = psm::check_counts(c, st, who, dC, ldc, m, n);
+    int32_t rc = check_label_rows(c, who, "labelling", labels, L, n);
+    if (rc != RC_OK) return rc;
+    std::vector<unsigned short> labs(labels, labels + (size_t)L * n);  // narrowed: 1..n fits 16 bits (check_capacity)
+    rc = psm::check_counts(c, st, who, dC, ldc, m, n);
     if (rc != RC_OK) return rc;
     DeviceBuffers B;
     unsigned long long *d_tot;
@@ -498,7 +490,7 @@ static int32_t run_eloss(rc_ctx *c, hipStream_t st, const char *who, const unsig
     if (rc != RC_OK) return rc;
     std::vector<unsigned> T;
     double ms = 0.0;
-    rc = eloss_T(c, st, dC, ldc, n, labs, L, T, &ms);
+    rc = eloss_T(c, st, dC, ldc, n, labs, L, T, ms);
     if (rc != RC_OK) return rc;
     long long tot = 0;
     HIPCHK(c, hipMemcpy(&tot, d_tot, sizeof(long long), hipMemcpyDeviceToHost));

@@ -1,7 +1,8 @@
 // Host utilities of the entry points that own their device memory for one call (most of them take a device number and no
-// context): a holder of device buffers, a pair of timing events, the device selection.  Included at the end of
-// redclust_hip.hip before every other include (same translation unit: shares fail() and HIPCHK — HIPCHK(nullptr, call)
-// reports into the thread's error buffer).  Both holders release on scope exit, so a HIPCHK may return from anywhere.
+// context): a holder of device buffers, a pair of timing events, the check of a label matrix, the tests' environment switches,
+// the dynamic-LDS attribute, the device selection.  Included at the end of redclust_hip.hip after labels.inc.hpp and before every
+// other include (same translation unit: shares fail() and HIPCHK — HIPCHK(nullptr, call) reports into the thread's error
+// buffer).  Both holders release on scope exit, so a HIPCHK may return from anywhere.
 
 struct DeviceBuffers {
     std::vector<void *> owned;
@@ -33,33 +34,50 @@ struct TimingEvents {
         const hipError_t e = hipEventCreate(&e0);
         return e == hipSuccess ? hipEventCreate(&e1) : e;
     }
+    // begin(st); the launches; end(st): the launches' error, else e1 behind them; elapsed_ms(acc): wait for e1, add e0 → e1 to acc
+    hipError_t begin(hipStream_t st) { return hipEventRecord(e0, st); }
+    hipError_t end(hipStream_t st)
+    {
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? hipEventRecord(e1, st) : e;
+    }
+    hipError_t elapsed_ms(double &acc)
+    {
+        float t = 0;
+        hipError_t e = hipEventSynchronize(e1);
+        if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
+        if (e == hipSuccess) acc += t;
+        return e;
+    }
 };
 
-// The cluster-contiguous order of one labelling z (n labels in 1..n, checked by the caller), shared by predict and the partition
-// distances.  The labels are compacted to slots 0..K-1 in ascending label order: slot(t, label, size) is called once per slot,
-// in that order.  The points are then counting-sorted by slot: put(at, j, t) is called for every point j, in index order, with
-// its position in the sorted order and its slot.  Returns K; afterwards pos[t] is one past slot t's last position.  Scratch of
-// the caller's: cnt (n + 1 zeros, left zeroed), slot_of_label (n + 1), pos (n).
-template <typename Slot, typename Put>
-static int cluster_order(const int64_t *z, int64_t n, std::vector<int> &cnt, std::vector<int> &slot_of_label, std::vector<int> &pos,
-                         Slot slot, Put put)
+// The library's error for the first label of `count` rows (each `what`, e.g. "sample") outside 1..n (labels.inc.hpp finds it)
+static int32_t check_label_rows(rc_ctx *c, const char *who, const char *what, const int64_t *rows, int64_t count, int64_t n)
 {
-    for (int64_t j = 0; j < n; ++j) cnt[(size_t)z[j]]++;
-    int K = 0, at = 0;
-    for (int64_t l = 1; l <= n; ++l) {
-        const int sz = cnt[(size_t)l];
-        if (!sz) continue;
-        slot_of_label[(size_t)l] = K;
-        pos[(size_t)K] = at; at += sz;
-        slot(K, l, sz);
-        cnt[(size_t)l] = 0;
-        ++K;
-    }
-    for (int64_t j = 0; j < n; ++j) {
-        const int t = slot_of_label[(size_t)z[j]];
-        put(pos[(size_t)t]++, j, t);
-    }
-    return K;
+    int64_t r, j;
+    if (!find_bad_label(rows, count, n, 1, &r, &j)) return RC_OK;
+    return fail(c, RC_ERR_ARG, "%s: label %lld of %s %lld at position %lld outside 1..n", who, (long long)rows[(size_t)r * n + j], what,
+                (long long)r + 1, (long long)j + 1);
+}
+
+// The switches the tests set in the environment, read per call: an integer (0 when unset), a flag, and a workspace in KiB that
+// shrinks the default (chunks at small shapes, the same results) and never exceeds it.
+static long long env_int(const char *name)
+{
+    const char *e = std::getenv(name);
+    return e ? atoll(e) : 0;
+}
+static bool env_flag(const char *name) { return env_int(name) != 0; }
+static size_t env_workspace_kib(const char *name, size_t default_bytes)
+{
+    const long long v = env_int(name);
+    return v > 0 ? std::min(default_bytes, (size_t)v << 10) : default_bytes;
+}
+
+// kernels that use more dynamic LDS than the 64 KiB every kernel may have must ask for it before the launch
+template <typename Kernel> static hipError_t set_dynamic_lds(Kernel kernel, size_t bytes)
+{
+    return bytes > 64 * 1024 ? hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess;
 }
 
 static int32_t select_device(const char *who, int32_t device)

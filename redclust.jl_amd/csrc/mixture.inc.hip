@@ -169,7 +169,7 @@ extern "C" int32_t rc_oracle_coclustering(int32_t device, int64_t n, int64_t dim
     HIPCHK(nullptr, hipMemcpy(d_tiles, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(nullptr, hipMemset(d_S, 0, (size_t)npad * npad * 8));
     HIPCHK(nullptr, ev.create());
-    HIPCHK(nullptr, hipEventRecord(ev.e0, 0));
+    HIPCHK(nullptr, ev.begin(0));
     for (int64_t t0 = 0; t0 < numiters; t0 += ipc) {
         const int it = (int)std::min<int64_t>(ipc, numiters - t0);
         mixture::k_mix_q<<<dim3((unsigned)((npad + 255) / 256), (unsigned)std::min(it, 65535)), 256, 0, 0>>>(
@@ -179,11 +179,9 @@ extern "C" int32_t rc_oracle_coclustering(int32_t device, int64_t n, int64_t dim
         HIPCHK(nullptr, hipGetLastError());
     }
     mixture::k_mix_finish<<<dim3((unsigned)(npad / 32), (unsigned)(npad / 32)), 256, 0, 0>>>(npad, (double)numiters, d_S);
-    HIPCHK(nullptr, hipGetLastError());
-    HIPCHK(nullptr, hipEventRecord(ev.e1, 0));
-    HIPCHK(nullptr, hipEventSynchronize(ev.e1));
-    float ms = 0;
-    HIPCHK(nullptr, hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    HIPCHK(nullptr, ev.end(0));
+    double ms = 0.0;
+    HIPCHK(nullptr, ev.elapsed_ms(ms));
     HIPCHK(nullptr, hipMemcpy2D(out, (size_t)n * 8, d_S, (size_t)npad * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToHost));
     if (kernel_ms) *kernel_ms = ms;
     return RC_OK;

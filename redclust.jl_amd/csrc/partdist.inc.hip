@@ -121,34 +121,12 @@ __global__ __launch_bounds__(TPB) void k_partdist(const Args A)
     }
 }
 
-// Dense ids (ascending label order) of one row into out, and its marginals Σ n_k², Σ Phiq(n_k), K.  cnt: n + 1 zeros, left zeroed;
-// id: n + 1 scratch.
-static void compact_row(const int64_t *z, int64_t n, const int64_t *Phi, std::vector<int> &cnt, std::vector<int> &id, unsigned short *out,
-                        int64_t *marg)
+// The marginals of one row: Σ n_k², Σ Phiq(n_k), K.  cnt: n + 1 zeros, left zeroed; id: n + 1 scratch.
+static void marginals(const int64_t *z, int64_t n, const int64_t *Phi, std::vector<int> &cnt, std::vector<int> &id, int64_t *marg)
 {
-    for (int64_t j = 0; j < n; ++j) cnt[(size_t)z[j]]++;
     int64_t sq = 0, ph = 0;
-    int K = 0;
-    for (int64_t l = 1; l <= n; ++l) {
-        const int64_t sz = cnt[(size_t)l];
-        if (!sz) continue;
-        id[(size_t)l] = K++;
-        sq += sz * sz; ph += Phi[(size_t)sz];
-        cnt[(size_t)l] = 0;
-    }
-    if (out) for (int64_t j = 0; j < n; ++j) out[j] = (unsigned short)id[(size_t)z[j]];
-    marg[0] = sq; marg[1] = ph; marg[2] = K;
-}
-
-static int32_t check_rows(const char *who, const char *what, const int64_t *rows, int64_t count, int64_t n)
-{
-    for (int64_t r = 0; r < count; ++r)
-        for (int64_t j = 0; j < n; ++j) {
-            const int64_t l = rows[(size_t)r * n + j];
-            if (l < 1 || l > n)
-                return fail(nullptr, RC_ERR_ARG, "%s: label %lld of %s %lld at position %lld outside 1..n", who, (long long)l, what, (long long)r + 1, (long long)j + 1);
-        }
-    return RC_OK;
+    marg[2] = compact_labels(z, n, cnt, id, [&](int, int64_t, int sz) { sq += (int64_t)sz * sz; ph += Phi[(size_t)sz]; });
+    marg[0] = sq; marg[1] = ph;
 }
 
 // One pass: the labellings idx[0..count) (rows of `labels`) against every sample, with the LDS or the global histograms.
@@ -156,7 +134,6 @@ struct Pass {
     const char *who;
     int64_t n, m, npad;
     const int64_t *samples, *labels;
-    const int64_t *Phi;
     const long long *d_Gq;
     int64_t *sq_out, *phi_out;
     size_t workspace;
@@ -178,7 +155,6 @@ static int32_t run_pass(const Pass &p, const std::vector<int64_t> &idx, bool hgl
     std::vector<unsigned short> h_ord, h_lab;
     std::vector<long long> h_sq, h_phi;
     std::vector<int> cnt, slot_of_label, pos, id;
-    int64_t marg[3];
     try {
         h_ord.assign((size_t)mc * npad, 0); h_lab.resize((size_t)Lc * n);
         if (p.sq_out) h_sq.resize((size_t)Lc * mc);
@@ -215,25 +191,24 @@ static int32_t run_pass(const Pass &p, const std::vector<int64_t> &idx, bool hgl
         const bool gqlds = !p.gq_global && (size_t)gcap * 8 <= GQ_LDS_BYTES;
         const size_t lds = (size_t)npad * 2 + (gqlds ? (size_t)gcap * 8 : 0) + (hglobal ? 0 : (size_t)WPB * KLDS * sizeof(unsigned));
         auto kern = hglobal ? (gqlds ? k_partdist<true, true> : k_partdist<true, false>) : (gqlds ? k_partdist<false, true> : k_partdist<false, false>);
-        if (lds > 64 * 1024) HIPCHK(nullptr, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(nullptr, set_dynamic_lds(kern, lds));
         for (int64_t l0 = 0; l0 < count; l0 += Lc) {
             const int64_t nl = std::min(Lc, count - l0);
-            for (int64_t l = 0; l < nl; ++l)
-                compact_row(p.labels + (size_t)idx[(size_t)(l0 + l)] * n, n, p.Phi, cnt, id, h_lab.data() + (size_t)l * n, marg);
+            for (int64_t l = 0; l < nl; ++l) {
+                const int64_t *z = p.labels + (size_t)idx[(size_t)(l0 + l)] * n;
+                compact_labels(z, n, cnt, id, [](int, int64_t, int) {});
+                dense_ids(z, n, id, h_lab.data() + (size_t)l * n);
+            }
             HIPCHK(nullptr, hipMemcpy(d_lab, h_lab.data(), (size_t)nl * n * sizeof(unsigned short), hipMemcpyHostToDevice));
             Args a{};
             a.ord = d_ord; a.lab = d_lab; a.Gq = p.d_Gq; a.hist = d_hist; a.sq = d_sq; a.phi = d_phi;
             a.n = (int)n; a.npad = (int)npad; a.mc = (int)ms; a.Lc = (int)nl; a.hstride = (int)n; a.gcap = gqlds ? gcap : 0;
             a.items = (long long)ms * ((nl + WPB - 1) / WPB);
             const unsigned grid = (unsigned)(hglobal ? std::min<long long>(grid_global, a.items) : a.items);
-            HIPCHK(nullptr, hipEventRecord(ev.e0, 0));
+            HIPCHK(nullptr, ev.begin(0));
             kern<<<grid, TPB, lds, 0>>>(a);
-            HIPCHK(nullptr, hipGetLastError());
-            HIPCHK(nullptr, hipEventRecord(ev.e1, 0));
-            HIPCHK(nullptr, hipEventSynchronize(ev.e1));
-            float t = 0;
-            HIPCHK(nullptr, hipEventElapsedTime(&t, ev.e0, ev.e1));
-            ms_acc += t;
+            HIPCHK(nullptr, ev.end(0));
+            HIPCHK(nullptr, ev.elapsed_ms(ms_acc));
             // device [nl][ms] into the caller's [L][m]
             for (int pass = 0; pass < 2; ++pass) {
                 int64_t *dst = pass ? p.phi_out : p.sq_out;
@@ -260,9 +235,9 @@ extern "C" int32_t rc_partition_distances(int32_t device, const int64_t *samples
     if (n > NMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %lld points whose indices fit 15 bits", who, (long long)n, (long long)NMAX);
     if (m >= ((int64_t)1 << 31) / n + (((int64_t)1 << 31) % n != 0)) return fail(nullptr, RC_ERR_CAPACITY, "%s: m·n = %lld·%lld is not below 2^31", who, (long long)m, (long long)n);
     if (L > LMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: L = %lld exceeds %lld labellings per call", who, (long long)L, (long long)LMAX);
-    int32_t rc = check_rows(who, "sample", samples, m, n);
+    int32_t rc = check_label_rows(nullptr, who, "sample", samples, m, n);
     if (rc != RC_OK) return rc;
-    rc = check_rows(who, "labelling", labels, L, n);
+    rc = check_label_rows(nullptr, who, "labelling", labels, L, n);
     if (rc != RC_OK) return rc;
 
     std::vector<int64_t> Gq, Phi, lmarg, idx_lds, idx_global;
@@ -274,31 +249,26 @@ extern "C" int32_t rc_partition_distances(int32_t device, const int64_t *samples
     visearch::gtable(n, Gq.data());
     Phi[0] = 0;
     for (int64_t x = 0; x < n; ++x) Phi[(size_t)x + 1] = Phi[(size_t)x] + Gq[(size_t)x];
-    const char *e = std::getenv("RC_PARTDIST_HIST_GLOBAL");                 // tests: the global histograms at every cluster count
-    const bool force_global = e && atoi(e) != 0;
+    const bool force_global = env_flag("RC_PARTDIST_HIST_GLOBAL");          // tests: the global histograms at every cluster count
     for (int64_t l = 0; l < L; ++l) {
-        compact_row(labels + (size_t)l * n, n, Phi.data(), cnt, id, nullptr, lmarg.data() + (size_t)l * 3);
+        marginals(labels + (size_t)l * n, n, Phi.data(), cnt, id, lmarg.data() + (size_t)l * 3);
         (force_global || lmarg[(size_t)l * 3 + 2] > KLDS ? idx_global : idx_lds).push_back(l);
     }
     if (lab_marg) memcpy(lab_marg, lmarg.data(), lmarg.size() * sizeof(int64_t));
     if (smp_marg)
-        for (int64_t s = 0; s < m; ++s) compact_row(samples + (size_t)s * n, n, Phi.data(), cnt, id, nullptr, smp_marg + (size_t)s * 3);
+        for (int64_t s = 0; s < m; ++s) marginals(samples + (size_t)s * n, n, Phi.data(), cnt, id, smp_marg + (size_t)s * 3);
     if (kernel_ms) *kernel_ms = 0.0;
     if (!sq_out && !phi_out) return RC_OK;
 
     rc = select_device(who, device);
     if (rc != RC_OK) return rc;
-    size_t workspace = WORKSPACE;
-    if (const char *w = std::getenv("RC_PARTDIST_WORKSPACE_KIB")) {         // tests: chunks at small shapes (the same results)
-        const long long v = atoll(w);
-        if (v > 0) workspace = std::min(workspace, (size_t)v << 10);
-    }
+    const size_t workspace = env_workspace_kib("RC_PARTDIST_WORKSPACE_KIB", WORKSPACE);
     DeviceBuffers B;
     long long *d_Gq;
     HIPCHK(nullptr, B.alloc(d_Gq, (size_t)n));
     HIPCHK(nullptr, hipMemcpy(d_Gq, Gq.data(), (size_t)n * sizeof(long long), hipMemcpyHostToDevice));
-    const char *g = std::getenv("RC_PARTDIST_GQ_GLOBAL");                  // tests: the table from global memory for every chunk
-    const Pass p{who, n, m, (n + 7) / 8 * 8, samples, labels, Phi.data(), d_Gq, sq_out, phi_out, workspace, g && atoi(g) != 0};
+    const Pass p{who, n, m, (n + 7) / 8 * 8, samples, labels, d_Gq, sq_out, phi_out, workspace,
+                 env_flag("RC_PARTDIST_GQ_GLOBAL")};                        // tests: the table from global memory for every chunk
     double ms_acc = 0.0;
     rc = run_pass(p, idx_lds, false, ms_acc);
     if (rc != RC_OK) return rc;

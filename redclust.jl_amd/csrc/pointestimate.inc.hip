@@ -181,9 +181,8 @@ static int32_t prepare(const int64_t *samples, int64_t m, int64_t n, Prep &P)
     P.xlogx.resize((size_t)n + 1);
     P.xlogx[0] = 0.0;
     for (int64_t c = 1; c <= n; ++c) P.xlogx[(size_t)c] = (double)c * std::log((double)c);
-    for (int64_t t = 0; t < m * n; ++t)
-        if (samples[t] < 1 || samples[t] > n)
-            return fail(nullptr, RC_ERR_ARG, "point estimate: label %lld of sample %lld outside 1..n", (long long)samples[t], (long long)(t / n + 1));
+    const int32_t rc = check_label_rows(nullptr, "point estimate", "sample", samples, m, n);
+    if (rc != RC_OK) return rc;
     // common point order: stable counting sort by the last sample's labels
     std::vector<int> order((size_t)n), cnt((size_t)n + 2, 0), dense((size_t)n + 1, 0);
     const int64_t *last = samples + (m - 1) * n;
@@ -194,16 +193,11 @@ static int32_t prepare(const int64_t *samples, int64_t m, int64_t n, Prep &P)
     P.Kmax = 0;
     for (int64_t s = 0; s < m; ++s) {
         const int64_t *x = samples + s * n;
-        for (int64_t i = 0; i < n; ++i) c2[(size_t)x[i]]++;
-        int K = 0;
-        double nis = 0, ea = 0;
-        for (int64_t l = 1; l <= n; ++l)
-            if (c2[(size_t)l]) {
-                dense[(size_t)l] = K++;
-                nis += (double)c2[(size_t)l] * (double)c2[(size_t)l];
-                ea += P.xlogx[(size_t)c2[(size_t)l]];
-                c2[(size_t)l] = 0;
-            }
+        double nis = 0, ea = 0;                                          // summed in ascending label order
+        const int K = compact_labels(x, n, c2, dense, [&](int, int64_t, int sz) {
+            nis += (double)sz * (double)sz;
+            ea += P.xlogx[(size_t)sz];
+        });
         if (K >= 0xFFFF) return fail(nullptr, RC_ERR_CAPACITY, "point estimate: sample %lld has %d clusters (limit 65534)", (long long)s + 1, K);
         P.K[(size_t)s] = K; P.nis[(size_t)s] = nis; P.ea[(size_t)s] = ea;
         P.Kmax = std::max(P.Kmax, K);
@@ -281,15 +275,11 @@ static int32_t run(int32_t device, const int64_t *samples, int64_t m, int64_t n,
     for (int t = 0; t < nkinds; ++t) {
         A.kind = kinds[t];
         HIPCHK(nullptr, hipMemset(d_L, 0, (size_t)m * m * 8));
-        HIPCHK(nullptr, hipEventRecord(ev.e0, 0));
+        HIPCHK(nullptr, ev.begin(0));
         if (global_tab) k_pair_losses<true><<<grid, 64 * W, lds, 0>>>(A);
         else k_pair_losses<false><<<grid, 64 * W, lds, 0>>>(A);
-        HIPCHK(nullptr, hipGetLastError());
-        HIPCHK(nullptr, hipEventRecord(ev.e1, 0));
-        HIPCHK(nullptr, hipEventSynchronize(ev.e1));
-        float ms = 0;
-        HIPCHK(nullptr, hipEventElapsedTime(&ms, ev.e0, ev.e1));
-        ms_total += ms;
+        HIPCHK(nullptr, ev.end(0));
+        HIPCHK(nullptr, ev.elapsed_ms(ms_total));
         if (outs && outs[t]) HIPCHK(nullptr, hipMemcpy(outs[t], d_L, (size_t)m * m * 8, hipMemcpyDeviceToHost));
     }
     if (colsum) {

@@ -400,10 +400,7 @@ static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, in
     const size_t fixed = (vi ? 4 * (size_t)n : 0) + 2 * (size_t)(n + 2) + 2 * (size_t)n + 16;
     const size_t per_slot = vi ? 12 : 4;
     int64_t W = std::min<int64_t>(n + 1, (int64_t)((LDS_BUDGET - fixed) / per_slot));
-    if (const char *e = std::getenv("RC_PSM_WINDOW")) {                   // tests: force the windowed passes at small n
-        const long v = std::atol(e);
-        if (v >= 1 && v < W) W = v;
-    }
+    if (const long long v = env_int("RC_PSM_WINDOW"); v >= 1 && v < W) W = v;   // tests: force the windowed passes at small n
     const size_t lds = (fixed + per_slot * (size_t)W + 15) / 16 * 16;
 
     unsigned short *d_init, *d_sz, *d_lab; int *d_K, *d_hi, *d_ord; RunOut *d_out;
@@ -425,18 +422,18 @@ static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, in
     A.n = (int)n; A.W = (int)W; A.maxK = maxK; A.maxsweeps = maxsweeps; A.m = (unsigned)m;
     TimingEvents ev;
     HIPCHK(c, ev.create());
-    HIPCHK(c, hipEventRecord(ev.e0, st));
+    HIPCHK(c, ev.begin(st));
     const int Q = (int)((n + TPB - 1) / TPB);
     const hipError_t le = vi ? launch<RC_PSM_VILB>(Q, nruns, lds, st, A) : launch<RC_PSM_BINDER>(Q, nruns, lds, st, A);
     if (le != hipSuccess) return fail(c, RC_ERR_HIP, "point search: launch failed: %s", hipGetErrorString(le));
-    HIPCHK(c, hipEventRecord(ev.e1, st));
+    HIPCHK(c, ev.end(st));
     std::vector<unsigned short> h_lab(h_init.size());
     std::vector<RunOut> h_out((size_t)nruns);
     HIPCHK(c, hipMemcpyAsync(h_lab.data(), d_lab, h_lab.size() * 2, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(h_out.data(), d_out, h_out.size() * sizeof(RunOut), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    double ms = 0.0;
+    HIPCHK(c, ev.elapsed_ms(ms));
     if (kernel_ms) *kernel_ms = ms;
 
     // ---- results: sortlabels (utils.jl:69-74), the losses, the first minimum

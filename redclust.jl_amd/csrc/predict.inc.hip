@@ -280,7 +280,7 @@ static int32_t run_samples(const char *who, const Call &c, int64_t s0, int64_t m
     const size_t lds = ldsrow ? (size_t)n * sizeof(ll2) : 0;
     auto kern = ldsrow ? (parts > 1 ? k_predict_sums<true, true> : k_predict_sums<true, false>)
                        : (parts > 1 ? k_predict_sums<false, true> : k_predict_sums<false, false>);
-    if (lds > 64 * 1024) HIPCHK(nullptr, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(nullptr, set_dynamic_lds(kern, lds));
 
     std::vector<ll2> rows;
     std::vector<long long> h_lab, h_tab;
@@ -317,17 +317,13 @@ static int32_t run_samples(const char *who, const Call &c, int64_t s0, int64_t m
         a.k0 = (unsigned)c.seed; a.k1 = (unsigned)(c.seed >> 32) ^ TAG;
         a.sample0 = c.sample_offset + (uint64_t)s0; a.point0 = c.point_offset + (uint64_t)i0;
         a.labels = d_labels; a.map = d_map; a.scores = d_scores; a.sums_out = d_sums_out;
-        HIPCHK(nullptr, hipEventRecord(ev.e0, 0));
+        HIPCHK(nullptr, ev.begin(0));
         if (parts > 1) HIPCHK(nullptr, hipMemsetAsync(d_sums, 0, (size_t)np * ktot * sizeof(ll2), 0));   // the parts add into zeros
         kern<<<(unsigned)np, TPB1, lds, 0>>>(d_rows, (int)n, d_perm, (int)ms, ms_pad, parts, d_startslot, d_koff, ktot, d_sums);
         HIPCHK(nullptr, hipGetLastError());
         k_predict_draw<<<(unsigned)(((size_t)np * ms + TPB2 / 64 - 1) / (TPB2 / 64)), TPB2, 0, 0>>>(a);
-        HIPCHK(nullptr, hipGetLastError());
-        HIPCHK(nullptr, hipEventRecord(ev.e1, 0));
-        HIPCHK(nullptr, hipEventSynchronize(ev.e1));
-        float t = 0;
-        HIPCHK(nullptr, hipEventElapsedTime(&t, ev.e0, ev.e1));
-        ms_acc += t;
+        HIPCHK(nullptr, ev.end(0));
+        HIPCHK(nullptr, ev.elapsed_ms(ms_acc));
         // device [ms][np][..] into the caller's [m][q][..]
         for (int pass = 0; pass < 2; ++pass) {
             int64_t *dst = pass ? c.map_out : c.labels_out;
@@ -367,6 +363,8 @@ extern "C" int32_t rc_predict(int32_t device, int64_t n, int64_t q, const double
         if (!(r[s] > 0 && r[s] <= 1.79769313486231570e308)) return fail(nullptr, RC_ERR_ARG, "%s: r of sample %lld must be positive and finite", who, (long long)s + 1);
         if (!(p[s] > 0 && p[s] < 1)) return fail(nullptr, RC_ERR_ARG, "%s: p of sample %lld must lie in (0, 1)", who, (long long)s + 1);
     }
+    rc = check_label_rows(nullptr, who, "sample", samples, m, n);
+    if (rc != RC_OK) return rc;
     const bool want_tab = scores_out || sums_out;
     std::vector<int> K, eD, eL, seen;
     std::vector<double> A;
@@ -375,11 +373,8 @@ extern "C" int32_t rc_predict(int32_t device, int64_t n, int64_t q, const double
     for (int64_t s = 0; s < m; ++s) {
         const int64_t *z = samples + (size_t)s * n;
         int k = 0;
-        for (int64_t j = 0; j < n; ++j) {
-            const int64_t l = z[j];
-            if (l < 1 || l > n) return fail(nullptr, RC_ERR_ARG, "%s: label %lld of sample %lld at position %lld outside 1..n", who, (long long)l, (long long)s + 1, (long long)j + 1);
-            if (seen[(size_t)l] != (int)s) { seen[(size_t)l] = (int)s; ++k; }
-        }
+        for (int64_t j = 0; j < n; ++j)
+            if (seen[(size_t)z[j]] != (int)s) { seen[(size_t)z[j]] = (int)s; ++k; }
         K[(size_t)s] = k;
         if (want_tab && k > Kmax) return fail(nullptr, RC_ERR_ARG, "%s: sample %lld has %d clusters, Kmax = %lld", who, (long long)s + 1, k, (long long)Kmax);
     }
@@ -413,19 +408,12 @@ extern "C" int32_t rc_predict(int32_t device, int64_t n, int64_t q, const double
         HIPCHK(nullptr, hipMemcpy(d_flt, ft, sizeof(ft), hipMemcpyHostToDevice));
     }
     prd::Call c{n, q, m, want_tab ? Kmax : 0, Dnew, logDnew_or_null, samples, r, p, params, seed, sample_offset, point_offset,
-                labels_out, map_out, sums_out, scores_out, eD.data(), eL.data(), K.data(), A.data(), d_flt, false};
-    {
-        const char *e = std::getenv("RC_PREDICT_ROWS_GLOBAL");             // tests: gather from the rows in global memory at small n
-        c.rows_global = e && atoi(e) != 0;
-    }
+                labels_out, map_out, sums_out, scores_out, eD.data(), eL.data(), K.data(), A.data(), d_flt,
+                env_flag("RC_PREDICT_ROWS_GLOBAL")};                       // tests: gather from the rows in global memory at small n
     // Chunks.  Device bytes per new point for a run of samples: its row, and per sample its slots' sums, two labels and the
     // optional columns.  Samples are taken while 512 points (or all q) of them fit the workspace and their sorted orders fit
     // theirs; the points then go in chunks of what fits.
-    size_t workspace = prd::WORKSPACE;
-    if (const char *e = std::getenv("RC_PREDICT_WORKSPACE_KIB")) {        // tests: chunks at small shapes (the same results)
-        const long long v = atoll(e);
-        if (v > 0) workspace = (size_t)v << 10;
-    }
+    const size_t workspace = env_workspace_kib("RC_PREDICT_WORKSPACE_KIB", prd::WORKSPACE);
     const size_t per_sample = 16 + (scores_out ? 8 * ((size_t)c.Kmax + 1) : 0) + (sums_out ? 16 * (size_t)c.Kmax : 0);
     const int64_t qt = std::min<int64_t>(q, 512);
     const int64_t ms_cap = std::max<int64_t>(64, (int64_t)(prd::PERM_BYTES / 2 / (size_t)n) / 64 * 64);

@@ -7835,6 +7835,7 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
     return RC_OK;
 }
 
+#include "labels.inc.hpp"
 #include "hostutil.inc.hip"
 #include "pointestimate.inc.hip"
 #include "cluster.inc.hip"

@@ -211,28 +211,23 @@ extern "C" int32_t rc_relabel(int32_t device, const int64_t *samples, int64_t m,
     if (m < 1 || n < 1) return fail(nullptr, RC_ERR_ARG, "%s: need m >= 1 and n >= 1 (got m=%lld n=%lld)", who, (long long)m, (long long)n);
     if (n > NMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %lld points whose counts fit 15 bits", who, (long long)n, (long long)NMAX);
     if (m >= ((int64_t)1 << 31)) return fail(nullptr, RC_ERR_CAPACITY, "%s: m = %lld is not below 2^31", who, (long long)m);
-    int32_t rc = partdist::check_rows(who, "pivot", pivot, 1, n);
+    int32_t rc = check_label_rows(nullptr, who, "pivot", pivot, 1, n);
     if (rc != RC_OK) return rc;
-    rc = partdist::check_rows(who, "sample", samples, m, n);
+    rc = check_label_rows(nullptr, who, "sample", samples, m, n);
     if (rc != RC_OK) return rc;
 
-    std::vector<int64_t> zeros;                                       // compact_row's Phi: the marginals are not wanted here
     std::vector<int> cnt, id, Ks, names;
     std::vector<unsigned short> h_piv;
-    int64_t marg[3];
     try {
-        zeros.assign((size_t)n + 1, 0); cnt.assign((size_t)n + 1, 0); id.assign((size_t)n + 1, 0); Ks.resize((size_t)m); h_piv.resize((size_t)n);
+        cnt.assign((size_t)n + 1, 0); id.assign((size_t)n + 1, 0); Ks.resize((size_t)m); h_piv.resize((size_t)n);
     } catch (const std::bad_alloc &) { return fail(nullptr, RC_ERR_OOM, "%s: no host memory", who); }
-    partdist::compact_row(pivot, n, zeros.data(), cnt, id, h_piv.data(), marg);
-    const int64_t Kp = marg[2];
+    const auto no_slot = [](int, int64_t, int) {};                    // only the ids and the cluster counts are wanted here
+    const int64_t Kp = compact_labels(pivot, n, cnt, id, no_slot);
+    dense_ids(pivot, n, id, h_piv.data());
     if (Kp > KMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: the pivot has %lld clusters, more than %d", who, (long long)Kp, KMAX);
     names.assign((size_t)Kp, 0);
     for (int64_t j = 0; j < n; ++j) names[h_piv[(size_t)j]] = (int)pivot[j];
-    size_t workspace = WORKSPACE;
-    if (const char *w = std::getenv("RC_RELABEL_WORKSPACE_KIB")) {          // tests: chunks at small shapes (the same results)
-        const long long x = atoll(w);
-        if (x > 0) workspace = std::min(workspace, (size_t)x << 10);
-    }
+    const size_t workspace = env_workspace_kib("RC_RELABEL_WORKSPACE_KIB", WORKSPACE);
     // The samples are compacted here for their cluster counts, which the capacity checks need before any device work.  Their
     // dense ids are kept for the chunks when all of them fit a workspace's worth of host memory, else made again per chunk.
     const bool keep_ids = 2 * (size_t)m * (size_t)n <= workspace;
@@ -243,12 +238,13 @@ extern "C" int32_t rc_relabel(int32_t device, const int64_t *samples, int64_t m,
     int64_t W = 0;
     size_t slab_bytes = 0;                                            // the largest table of the call
     for (int64_t s = 0; s < m; ++s) {
-        partdist::compact_row(samples + (size_t)s * n, n, zeros.data(), cnt, id, keep_ids ? h_zid.data() + (size_t)s * n : nullptr, marg);
-        if (marg[2] > KMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: sample %lld has %lld clusters, more than %d", who, (long long)s + 1, (long long)marg[2], KMAX);
-        Ks[(size_t)s] = (int)marg[2];
-        W = std::max(W, marg[2]);
+        const int K = compact_labels(samples + (size_t)s * n, n, cnt, id, no_slot);
+        if (keep_ids) dense_ids(samples + (size_t)s * n, n, id, h_zid.data() + (size_t)s * n);
+        if (K > KMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: sample %lld has %lld clusters, more than %d", who, (long long)s + 1, (long long)K, KMAX);
+        Ks[(size_t)s] = K;
+        W = std::max<int64_t>(W, K);
         int cols;
-        slab_bytes = std::max(slab_bytes, table_bytes((int)Kp, (int)marg[2], cols));
+        slab_bytes = std::max(slab_bytes, table_bytes((int)Kp, K, cols));
     }
     if (Kp_in != Kp) return fail(nullptr, RC_ERR_ARG, "%s: the pivot has %lld clusters, not %lld (counts is n x (K_p + 1))", who, (long long)Kp, (long long)Kp_in);
     if (maps_out && maps_width < W) return fail(nullptr, RC_ERR_ARG, "%s: maps is %lld wide, the largest sample has %lld clusters", who, (long long)maps_width, (long long)W);
@@ -256,8 +252,7 @@ extern "C" int32_t rc_relabel(int32_t device, const int64_t *samples, int64_t m,
 
     rc = select_device(who, device);
     if (rc != RC_OK) return rc;
-    const char *e = std::getenv("RC_RELABEL_TABLE_GLOBAL");                 // tests: the table in the global slab at every size
-    const bool force_global = e && atoi(e) != 0;
+    const bool force_global = env_flag("RC_RELABEL_TABLE_GLOBAL");          // tests: the table in the global slab at every size
     const int64_t Wd = maps_out ? maps_width : 0;
     const size_t per_sample = 2 * (size_t)n + sizeof(int) + sizeof(long long) + (labels_out ? 8 * (size_t)n : 0) + 8 * (size_t)Wd;
     const int64_t mc = std::max<int64_t>(1, std::min<int64_t>(m, (int64_t)(workspace / per_sample)));
@@ -293,7 +288,10 @@ extern "C" int32_t rc_relabel(int32_t device, const int64_t *samples, int64_t m,
         size_t tab = 0;
         int cmax = 0;
         for (int64_t s = 0; s < ms; ++s) {
-            if (!keep_ids) partdist::compact_row(samples + (size_t)(s0 + s) * n, n, zeros.data(), cnt, id, h_zid.data() + (size_t)s * n, marg);
+            if (!keep_ids) {
+                compact_labels(samples + (size_t)(s0 + s) * n, n, cnt, id, no_slot);
+                dense_ids(samples + (size_t)(s0 + s) * n, n, id, h_zid.data() + (size_t)s * n);
+            }
             int cols;
             tab = std::max(tab, table_bytes((int)Kp, Ks[(size_t)(s0 + s)], cols));
             cmax = std::max(cmax, cols);
@@ -306,20 +304,16 @@ extern "C" int32_t rc_relabel(int32_t device, const int64_t *samples, int64_t m,
         HIPCHK(nullptr, hipMemcpy(d_zid, h_zid.data() + (keep_ids ? (size_t)s0 * n : 0), (size_t)ms * n * sizeof(unsigned short), hipMemcpyHostToDevice));
         HIPCHK(nullptr, hipMemcpy(d_Ks, Ks.data() + s0, (size_t)ms * sizeof(int), hipMemcpyHostToDevice));
         auto kern = tglobal ? k_relabel<true> : k_relabel<false>;
-        if (lds > 64 * 1024) HIPCHK(nullptr, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(nullptr, set_dynamic_lds(kern, lds));
         Args a{};
         a.piv = d_piv; a.zid = d_zid; a.Ks = d_Ks; a.names = d_names; a.slab = d_slab; a.labels = d_labels; a.maps = d_maps;
         a.overlap = d_overlap; a.counts = d_counts; a.slab_dwords = slab_dwords;
         a.n = (int)n; a.mc = (int)ms; a.Kp = (int)Kp; a.W = (int)Wd; a.vw = vw;
         const unsigned grid = (unsigned)std::min<int64_t>(tglobal ? grid_global : GRID_MAX, ms);
-        HIPCHK(nullptr, hipEventRecord(ev.e0, 0));
+        HIPCHK(nullptr, ev.begin(0));
         kern<<<grid, TPB, lds, 0>>>(a);
-        HIPCHK(nullptr, hipGetLastError());
-        HIPCHK(nullptr, hipEventRecord(ev.e1, 0));
-        HIPCHK(nullptr, hipEventSynchronize(ev.e1));
-        float t = 0;
-        HIPCHK(nullptr, hipEventElapsedTime(&t, ev.e0, ev.e1));
-        ms_acc += t;
+        HIPCHK(nullptr, ev.end(0));
+        HIPCHK(nullptr, ev.elapsed_ms(ms_acc));
         HIPCHK(nullptr, hipMemcpy(overlap_out + s0, d_overlap, (size_t)ms * sizeof(long long), hipMemcpyDeviceToHost));
         if (labels_out) HIPCHK(nullptr, hipMemcpy(labels_out + (size_t)s0 * n, d_labels, (size_t)ms * n * sizeof(long long), hipMemcpyDeviceToHost));
         if (maps_out) HIPCHK(nullptr, hipMemcpy(maps_out + (size_t)s0 * Wd, d_maps, (size_t)ms * Wd * sizeof(long long), hipMemcpyDeviceToHost));

@@ -132,18 +132,12 @@ __global__ __launch_bounds__(TPB) void k_sample_counts(const unsigned short *__r
 // Labels 1..n narrowed to u16, sample-major with leading dimension ldn, pads 0xFFFE.  Host only.
 static int32_t narrow(const char *who, const int64_t *samples, int64_t m, int64_t n, size_t ldn, std::vector<unsigned short> &out)
 {
+    const int32_t rc = check_label_rows(nullptr, who, "sample", samples, m, n);
+    if (rc != RC_OK) return rc;
     try { out.assign((size_t)m * ldn, (unsigned short)PAD_COL); }
     catch (const std::bad_alloc &) { return fail(nullptr, RC_ERR_OOM, "%s: no host memory for the %lld x %zu 16-bit labels", who, (long long)m, ldn); }
-    for (int64_t s = 0; s < m; ++s) {
-        const int64_t *src = samples + (size_t)s * n;
-        unsigned short *dst = out.data() + (size_t)s * ldn;
-        for (int64_t j = 0; j < n; ++j) {
-            const int64_t l = src[j];
-            if (l < 1 || l > n)
-                return fail(nullptr, RC_ERR_ARG, "%s: label %lld of sample %lld at position %lld outside 1..n", who, (long long)l, (long long)s + 1, (long long)j + 1);
-            dst[j] = (unsigned short)l;
-        }
-    }
+    for (int64_t s = 0; s < m; ++s)
+        for (int64_t j = 0; j < n; ++j) out[(size_t)s * ldn + j] = (unsigned short)samples[(size_t)s * n + j];
     return RC_OK;
 }
 
@@ -163,13 +157,11 @@ static int32_t build(const char *who, const int64_t *samples, int64_t m, int64_t
     const unsigned nt = (unsigned)(ldn / TJ);
     TimingEvents ev;
     HIPCHK(nullptr, ev.create());
-    HIPCHK(nullptr, hipEventRecord(ev.e0, 0));
+    HIPCHK(nullptr, ev.begin(0));
     k_sample_counts<<<dim3(nt, nt), TPB, 0, 0>>>(d_S, (int)m, (int)n, ldn, d_counts, (size_t)ld);
-    HIPCHK(nullptr, hipGetLastError());
-    HIPCHK(nullptr, hipEventRecord(ev.e1, 0));
-    HIPCHK(nullptr, hipEventSynchronize(ev.e1));
-    float t = 0;
-    HIPCHK(nullptr, hipEventElapsedTime(&t, ev.e0, ev.e1));
+    HIPCHK(nullptr, ev.end(0));
+    double t = 0.0;
+    HIPCHK(nullptr, ev.elapsed_ms(t));
     if (ms) *ms = t;
     return RC_OK;
 }

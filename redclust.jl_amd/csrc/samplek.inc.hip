@@ -95,14 +95,10 @@ extern "C" int32_t rc_sample_k(int32_t device, int64_t n, int64_t m, const doubl
         const int cnt = (int)std::min<int64_t>(mb, m - i0);
         HIPCHK(nullptr, hipMemcpy(d_r, r + i0, (size_t)cnt * 8, hipMemcpyHostToDevice));
         HIPCHK(nullptr, hipMemcpy(d_p, p + i0, (size_t)cnt * 8, hipMemcpyHostToDevice));
-        HIPCHK(nullptr, hipEventRecord(ev.e0, 0));
+        HIPCHK(nullptr, ev.begin(0));
         samplek::k_samplek<<<(unsigned)((cnt + per - 1) / per), RC_SK_T, 0, 0>>>((int)n, cnt, d_r, d_p, d_lg, d_lnk, seed, (u64)i0, d_K);
-        HIPCHK(nullptr, hipGetLastError());
-        HIPCHK(nullptr, hipEventRecord(ev.e1, 0));
-        HIPCHK(nullptr, hipEventSynchronize(ev.e1));
-        float ms = 0;
-        HIPCHK(nullptr, hipEventElapsedTime(&ms, ev.e0, ev.e1));
-        ms_total += ms;
+        HIPCHK(nullptr, ev.end(0));
+        HIPCHK(nullptr, ev.elapsed_ms(ms_total));
         HIPCHK(nullptr, hipMemcpy(K_out + i0, d_K, (size_t)cnt * 8, hipMemcpyDeviceToHost));
     }
     if (kernel_ms) *kernel_ms = ms_total;

@@ -393,6 +393,8 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
     if (m > MN_MAX / n) return fail(nullptr, RC_ERR_CAPACITY, "%s: m*n exceeds 2^26 = %lld (m=%lld n=%lld)", who, MN_MAX, (long long)m, (long long)n);
 
     // ---- the samples: labels 1..n, re-labelled per sample to 0..L_s-1 by first appearance, transposed to [i][s]
+    int32_t rc = check_label_rows(nullptr, who, "sample", samples, m, n);
+    if (rc != RC_OK) return rc;
     std::vector<unsigned short> h_SL((size_t)n * m);
     std::vector<int> map((size_t)n + 1), cnt((size_t)n + 1);
     std::vector<int64_t> Gq((size_t)n), Phi((size_t)n + 1);
@@ -408,7 +410,6 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
         int L = 0;
         for (int64_t j = 0; j < n; ++j) {
             const int64_t l = samples[(size_t)s * n + j];
-            if (l < 1 || l > n) return fail(nullptr, RC_ERR_ARG, "%s: label %lld of sample %lld outside 1..n", who, (long long)l, (long long)s + 1);
             if (!map[(size_t)l]) map[(size_t)l] = ++L;
             h_SL[(size_t)j * m + s] = (unsigned short)(map[(size_t)l] - 1);
             cnt[(size_t)map[(size_t)l]]++;
@@ -436,11 +437,13 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
     std::vector<long long> h_Aq((size_t)nruns, 0);                      // ID: Σ_k Φq(n_k) of the start
     std::vector<char> seen((size_t)n);
     for (int r = 0; r < nruns; ++r) {
+        int64_t row, at;                                                // (per run: an earlier run's other errors come first)
+        if (find_bad_label(init + (size_t)r * n, 1, n, 0, &row, &at))
+            return fail(nullptr, RC_ERR_ARG, "%s: label %lld of run %d outside 0..n", who, (long long)init[(size_t)r * n + at], r + 1);
         std::fill(map.begin(), map.end(), 0);
         int K = 0;
         for (int64_t j = 0; j < n; ++j) {
             const int64_t l = init[(size_t)r * n + j];
-            if (l < 0 || l > n) return fail(nullptr, RC_ERR_ARG, "%s: label %lld of run %d outside 0..n", who, (long long)l, r + 1);
             if (l && !map[(size_t)l]) map[(size_t)l] = ++K;
         }
         if (K > Kcap) return fail(nullptr, RC_ERR_ARG, "%s: run %d starts with %d clusters, more than the slot cap %d", who, r + 1, K, Kcap);
@@ -460,7 +463,7 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
         }
     }
 
-    int32_t rc = select_device(who, device);
+    rc = select_device(who, device);
     if (rc != RC_OK) return rc;
 
     DeviceBuffers B;
@@ -503,19 +506,17 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
         HIPCHK(nullptr, hipMemcpy(d_Aq, h_Aq.data(), h_Aq.size() * 8, hipMemcpyHostToDevice));
         A.Bs = d_Bs; A.Pre = d_Pre; A.Aq0 = d_Aq;
         while ((1ll << A.nbits) < m + 1) ++A.nbits;                     // p(x) is in 0..m
-        const char *e = std::getenv("RC_ID_TABLE_GLOBAL");              // tests: force the global-memory table at small m
-        const bool force_global = e && std::atoi(e) != 0;
+        const bool force_global = env_flag("RC_ID_TABLE_GLOBAL");       // tests: force the global-memory table at small m
         A.tab_lds = (!force_global && lds + 16 * ((size_t)m + 1) <= LDS_MAX) ? 1 : 0;
         lds += A.tab_lds ? 16 * ((size_t)m + 1) : 16;
     }
     TimingEvents ev;
     HIPCHK(nullptr, ev.create());
-    HIPCHK(nullptr, hipEventRecord(ev.e0, 0));
+    HIPCHK(nullptr, ev.begin(0));
     HIPCHK(nullptr, loss == LOSS_ID ? launch<LOSS_ID>(PQ, nruns, lds, A) : launch<LOSS_VI>(PQ, nruns, lds, A));
-    HIPCHK(nullptr, hipEventRecord(ev.e1, 0));
-    HIPCHK(nullptr, hipDeviceSynchronize());
-    float ms = 0;
-    HIPCHK(nullptr, hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    HIPCHK(nullptr, ev.end(0));
+    double ms = 0.0;
+    HIPCHK(nullptr, ev.elapsed_ms(ms));
     if (kernel_ms) *kernel_ms = ms;
     std::vector<unsigned short> h_lab(h_init.size());
     std::vector<RunOut> h_out((size_t)nruns);

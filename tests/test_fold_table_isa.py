@@ -6,46 +6,18 @@ cross-compiles without a GPU), as tests/test_kernel_resources.py does:
     of the rounding bias (literal 0xbcc80000 = -bits(1.5·2^52) >> 32) than before the fold: 16 of each then (four entries x four row
     pairs, one copy of the row-pair block).  What remains: no conversion; four bias constants, one per row pair, inside the branch
     taken only by units with lanes that are not whole (their element-wise atomics), none in the streaming path."""
-import os, re, shutil, subprocess
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "redclust.jl_amd", "csrc", "redclust_hip.hip")
+from isa import listing, one, resources
+
 PARENT_CVT_F64_I32 = 16        # k_bulk_syml2<true, true> before the fold
 PARENT_BIAS_ADDS = 16
 
 
 @pytest.fixture(scope="module")
-def isa(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("isa") / "rc.s")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out, SRC],
-                   check=True, cwd=os.path.dirname(SRC), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    bodies, meta, name, cur = {}, {}, None, None
-    for line in open(out):
-        m = re.match(r"(_Z\w+):", line)
-        if m:
-            name, cur = m.group(1), []
-        if cur is not None:
-            cur.append(line)
-            if ".Lfunc_end" in line:
-                bodies[name] = cur; cur = None
-        m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", line)
-        if m:
-            kname = m.group(1); meta[kname] = {}
-        for key in ("next_free_vgpr", "group_segment_fixed_size", "private_segment_fixed_size"):
-            m = re.match(r"\s*\.amdhsa_" + key + r"\s+(\d+)", line)
-            if m:
-                meta[kname][key] = int(m.group(1))
-    return bodies, meta
-
-
-def one(d, fragment):
-    hits = [k for k in d if fragment in k]
-    assert len(hits) == 1, (fragment, hits)
-    return d[hits[0]]
+def isa():
+    """(every kernel's lines, every kernel's numbers)"""
+    return {k: v["text"].splitlines() for k, v in listing().items()}, resources()
 
 
 @pytest.mark.parametrize("fragment", ["k_bulk_syml2wILb1ELb1E", "k_bulk_syml2wILb1ELb0E"])

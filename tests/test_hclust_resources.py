@@ -2,33 +2,15 @@
 metadata of the gfx950 ISA the compiler emits (hipcc cross-compiles without a GPU): k_hclust<LINK> runs as ONE 1024-thread
 workgroup and k_eloss as 1024-thread workgroups — 16 waves, four per SIMD — so a lane may own at most 512 / 4 = 128 VGPRs or
 the kernel cannot be launched, and a scratch access inside k_hclust's step loop would sit between its barriers."""
-import os, re, shutil, subprocess
+import re
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "redclust.jl_amd", "csrc", "redclust_hip.hip")
+from isa import resources
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("isa") / "rc.s")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out, SRC],
-                   check=True, cwd=os.path.dirname(SRC), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    res, name, cur = {}, None, {}
-    for line in open(out):
-        m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", line)
-        if m:
-            name, cur = m.group(1), {}
-        for key in ("next_free_vgpr", "group_segment_fixed_size", "private_segment_fixed_size"):
-            m = re.match(r"\s*\.amdhsa_" + key + r"\s+(\d+)", line)
-            if m and name:
-                cur[key] = int(m.group(1))
-        if ".end_amdhsa_kernel" in line and name:
-            res[name] = cur; name = None
-    return {k: v for k, v in res.items() if re.search(r"3hcl(8k_hclustILi\dEE|7k_eloss)", k)}
+def kernels():
+    return resources(r"3hcl(8k_hclustILi\dEE|7k_eloss)")
 
 
 def test_every_instantiation_is_there(kernels):

@@ -2,39 +2,14 @@
 compiler emits (hipcc cross-compiles without a GPU): the resolver is a 128-register kernel that has to fit on a SIMD beside three waves
 of the row reduction (4 × 128 = 512 registers per lane), the reductions must not spill (a scratch reload inside the streaming loop waits
 for every prefetched row), and their LDS footprints are what `finish_create` sizes the resolver's tables against."""
-import os, re, shutil, subprocess
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "redclust.jl_amd", "csrc", "redclust_hip.hip")
+from isa import one, resources
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("isa") / "rc.s")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out, SRC],
-                   check=True, cwd=os.path.dirname(SRC), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    res, name, cur = {}, None, {}
-    for line in open(out):
-        m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", line)
-        if m:
-            name, cur = m.group(1), {}
-        for key in ("next_free_vgpr", "group_segment_fixed_size", "private_segment_fixed_size"):
-            m = re.match(r"\s*\.amdhsa_" + key + r"\s+(\d+)", line)
-            if m and name:
-                cur[key] = int(m.group(1))
-        if ".end_amdhsa_kernel" in line and name:
-            res[name] = cur; name = None
-    return res
-
-
-def one(kernels, fragment):
-    hits = [k for k in kernels if fragment in k]
-    assert len(hits) == 1, (fragment, hits)
-    return kernels[hits[0]]
+def kernels():
+    return resources()
 
 
 def test_resolver_fits_beside_three_reduction_waves(kernels):

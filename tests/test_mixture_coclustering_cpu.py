@@ -4,17 +4,15 @@ the product kernel in the gfx950 ISA, the host checks of rc.oracle_coclustering,
 paper datasets (tests/golden/paper_oracle.npz)."""
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import isa
 import mixture_ref as MR
 import redclust_amd as rc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "redclust.jl_amd", "csrc", "redclust_hip.hip")
 
 # paper dataset d: σ, and the bounds on max |Δ| / mean |Δ| against the stored matrix (twice the worst of ten seeds of
 # the restatement; equal weights miss them)
@@ -32,24 +30,8 @@ def test_header_and_signature_take_twelve_arguments():
     assert len(argtypes) == 12
 
 
-def test_product_kernel_does_not_spill(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path / "rc.s")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out, SRC],
-                   check=True, cwd=os.path.dirname(SRC), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    res, name, cur = {}, None, {}
-    for line in open(out):
-        m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", line)
-        if m:
-            name, cur = m.group(1), {}
-        m = re.match(r"\s*\.amdhsa_private_segment_fixed_size\s+(\d+)", line)
-        if m and name:
-            cur["private_segment_fixed_size"] = int(m.group(1))
-        if ".end_amdhsa_kernel" in line and name:
-            res[name] = cur
-            name = None
+def test_product_kernel_does_not_spill():
+    res = isa.resources()
     hits = [k for k in res if "k_mix_syrk" in k]
     assert len(hits) == 1, sorted(k for k in res if "k_mix" in k)
     assert res[hits[0]]["private_segment_fixed_size"] == 0, res[hits[0]]

@@ -4,38 +4,15 @@ lane may own at most 512 / 2 = 256 VGPRs or the kernel cannot be launched; three
 LDS each), six waves per SIMD, which needs no more than 80.  Its LDS is dynamic (the sample's order, sized per call, and the
 histograms).  The LDS variant counts with returning LDS atomics and touches global memory with plain loads and stores only; the
 global variant counts and clears with global atomics and has no LDS atomic.  Neither may touch scratch."""
-import os, re, shutil, subprocess
+import re
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "redclust.jl_amd", "csrc", "redclust_hip.hip")
+from isa import listing
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("isa") / "rc.s")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out, SRC],
-                   check=True, cwd=os.path.dirname(SRC), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    res, name, cur = {}, None, {}
-    for line in asm.splitlines():
-        m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", line)
-        if m:
-            name, cur = m.group(1), {}
-        for key in ("next_free_vgpr", "group_segment_fixed_size", "private_segment_fixed_size"):
-            m = re.match(r"\s*\.amdhsa_" + key + r"\s+(\d+)", line)
-            if m and name:
-                cur[key] = int(m.group(1))
-        if ".end_amdhsa_kernel" in line and name:
-            res[name] = cur; name = None
-
-    def text(k):                                                          # the kernel's instructions: its label to the end of the function
-        m = re.search(r"^" + re.escape(k) + r":[^\n]*\n(.*?)^\.Lfunc_end", asm, flags=re.S | re.M)
-        return m.group(1) if m else ""
-    return {k: dict(v, text=text(k)) for k, v in res.items() if "8partdist" in k and "k_partdist" in k}
+def kernels():
+    return {k: v for k, v in listing().items() if "8partdist" in k and "k_partdist" in k}
 
 
 def variant(name):

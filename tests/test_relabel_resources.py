@@ -5,38 +5,15 @@ SIMD, which needs no more than 64 (asked of the LDS-table variant; the global-ta
 runs one workgroup per CU at the most).  Its LDS is dynamic (the assignment's vectors and the table, sized per launch).  The
 LDS-table variant counts the table with non-returning LDS atomics and has one global atomic, the count of phase 3; the
 global-table variant counts the table with a global atomic too and has no LDS atomic.  Neither may touch scratch."""
-import os, re, shutil, subprocess
+import re
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "redclust.jl_amd", "csrc", "redclust_hip.hip")
+from isa import listing
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("isa") / "rc.s")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out, SRC],
-                   check=True, cwd=os.path.dirname(SRC), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    res, name, cur = {}, None, {}
-    for line in asm.splitlines():
-        m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", line)
-        if m:
-            name, cur = m.group(1), {}
-        for key in ("next_free_vgpr", "group_segment_fixed_size", "private_segment_fixed_size"):
-            m = re.match(r"\s*\.amdhsa_" + key + r"\s+(\d+)", line)
-            if m and name:
-                cur[key] = int(m.group(1))
-        if ".end_amdhsa_kernel" in line and name:
-            res[name] = cur; name = None
-
-    def text(k):                                                          # the kernel's instructions: its label to the end of the function
-        m = re.search(r"^" + re.escape(k) + r":[^\n]*\n(.*?)^\.Lfunc_end", asm, flags=re.S | re.M)
-        return m.group(1) if m else ""
-    return {k: dict(v, text=text(k)) for k, v in res.items() if "7relabel" in k and "k_relabel" in k}
+def kernels():
+    return {k: v for k, v in listing().items() if "7relabel" in k and "k_relabel" in k}
 
 
 def variant(name):

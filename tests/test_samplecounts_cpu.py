@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import redclust_amd as rc
+from redclust_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -29,17 +30,15 @@ def test_the_source_is_part_of_the_build():
     csrc = os.path.join(ROOT, "redclust.jl_amd", "csrc")
     assert os.path.exists(os.path.join(csrc, "samplecounts.inc.hip"))
     assert '#include "samplecounts.inc.hip"' in open(os.path.join(csrc, "redclust_hip.hip")).read()
-    assert '"samplecounts.inc.hip"' in open(os.path.join(ROOT, "redclust.jl_amd", "_lib.py")).read()
+    assert os.path.join(csrc, "samplecounts.inc.hip") in _lib._sources()  # build() watches it
 
 
 def test_every_include_is_built_and_listed():
-    """The *.inc.hip files of csrc/, the ones redclust_hip.hip includes and the ones build() watches are the same set."""
+    """The *.inc.hip and *.inc.hpp files of csrc/, the ones redclust_hip.hip includes and the ones build() watches are the same set."""
     csrc = os.path.join(ROOT, "redclust.jl_amd", "csrc")
-    on_disk = {f for f in os.listdir(csrc) if f.endswith(".inc.hip")}
-    included = set(re.findall(r'^#include "([^"]+\.inc\.hip)"', open(os.path.join(csrc, "redclust_hip.hip")).read(), flags=re.M))
-    lib = open(os.path.join(ROOT, "redclust.jl_amd", "_lib.py")).read()
-    body = lib[lib.index("def build("):lib.index("def build_diag(")]
-    listed = set(re.findall(r'"([^"]+\.inc\.hip)"', body))
+    on_disk = {f for f in os.listdir(csrc) if f.endswith((".inc.hip", ".inc.hpp"))}
+    included = set(re.findall(r'^#include "([^"]+\.inc\.h(?:ip|pp))"', open(os.path.join(csrc, "redclust_hip.hip")).read(), flags=re.M))
+    listed = {os.path.basename(s) for s in _lib._sources() if os.path.dirname(s) == csrc} - {"redclust_hip.hip"}
     assert on_disk and on_disk == included == listed, (sorted(on_disk), sorted(included), sorted(listed))
 
 

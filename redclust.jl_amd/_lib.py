@@ -702,31 +702,41 @@ def loss_matrix(samples, loss: int, device: int = 0, want_matrix: bool = True):
     return M, cs, int(am.value), float(ms.value)
 
 
+def _search_runs(init, order, maxK, maxsweeps, call, n=None) -> dict:
+    """What the four searches share: init (nruns×n labels, 0 = unallocated) and order (nruns×n 1-based permutations) coerced and
+    checked — n given: the samples' length, which init must have — the output buffers, and the dict of the results.
+    call(n, *tail) makes the library call and checks its return code; tail is what every search entry point ends with: nruns,
+    init, order, maxK, maxsweeps, labels_out, runs_out, best, kernel_ms.  What it returns (a dict or None) is added to the result."""
+    init = np.ascontiguousarray(init, dtype=np.int64)
+    order = np.ascontiguousarray(order, dtype=np.int32)
+    if init.ndim != 2 or init.shape != order.shape or (n is not None and init.shape[1] != n):
+        raise ValueError("init and order must be nruns×n arrays of the same shape" + (", n the samples' length" if n is not None else ""))
+    nruns, n = init.shape
+    labels = np.zeros((max(nruns, 1), max(n, 1)), np.int64)
+    runs = (RcPsmRun * max(nruns, 1))()
+    best, ms = C.c_int32(-1), C.c_double()
+    extra = call(n, nruns, init.ctypes.data, order.ctypes.data, int(maxK), int(maxsweeps), labels.ctypes.data, runs, C.byref(best),
+                 C.byref(ms))
+    return _psm_result(labels, runs, nruns, n, best, ms, **(extra or {}))
+
+
 def psm_search(counts, numsamples: int, loss: int, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0, ctx=None):
     """rc_psm_search (counts: n×n uint32) or, with ctx, rc_psm_search_ctx on that context's device counts (counts is ignored).
     init: nruns×n labels (0 = unallocated), order: nruns×n 1-based permutations.  Returns a dict: labels (nruns×n, sortlabels'd),
     the per-run arrays loss, loss_num, sweeps, converged, moves, K, and best, kernel_ms."""
     L = lib()
-    init = np.ascontiguousarray(init, dtype=np.int64)
-    order = np.ascontiguousarray(order, dtype=np.int32)
-    if init.ndim != 2 or init.shape != order.shape:
-        raise ValueError("init and order must be nruns×n arrays of the same shape")
-    nruns, n = init.shape
-    labels = np.zeros((max(nruns, 1), max(n, 1)), np.int64)
-    runs = (RcPsmRun * max(nruns, 1))()
-    best, ms = C.c_int32(-1), C.c_double()
-    if ctx is not None:
-        if n != ctx.n:
-            raise ValueError("init must have the context's n columns")
-        _check(L.rc_psm_search_ctx(ctx.h, int(numsamples), int(loss), nruns, init.ctypes.data, order.ctypes.data, int(maxK),
-                                   int(maxsweeps), labels.ctypes.data, runs, C.byref(best), C.byref(ms)), ctx.h)
-    else:
-        cnt = np.ascontiguousarray(counts, dtype=np.uint32)
-        if cnt.shape != (n, n):
-            raise ValueError("counts must be an n×n matrix matching init")
-        _check(L.rc_psm_search(int(device), cnt.ctypes.data, int(numsamples), n, int(loss), nruns, init.ctypes.data,
-                               order.ctypes.data, int(maxK), int(maxsweeps), labels.ctypes.data, runs, C.byref(best), C.byref(ms)))
-    return _psm_result(labels, runs, nruns, n, best, ms)
+
+    def call(n, *tail):
+        if ctx is not None:
+            if n != ctx.n:
+                raise ValueError("init must have the context's n columns")
+            _check(L.rc_psm_search_ctx(ctx.h, int(numsamples), int(loss), *tail), ctx.h)
+        else:
+            cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+            if cnt.shape != (n, n):
+                raise ValueError("counts must be an n×n matrix matching init")
+            _check(L.rc_psm_search(int(device), cnt.ctypes.data, int(numsamples), n, int(loss), *tail))
+    return _search_runs(init, order, maxK, maxsweeps, call)
 
 
 def samples_counts(samples, device: int = 0):
@@ -746,18 +756,12 @@ def psm_search_samples(samples, loss: int, init, order, maxK: int = 0, maxsweeps
     device and stay there.  Returns psm_search's dict and counts_ms, the device time of the counts kernel."""
     L = lib()
     S = _label_matrix(samples)
-    init = np.ascontiguousarray(init, dtype=np.int64)
-    order = np.ascontiguousarray(order, dtype=np.int32)
-    if init.ndim != 2 or init.shape != order.shape or init.shape[1] != S.shape[1]:
-        raise ValueError("init and order must be nruns×n arrays of the same shape, n the samples' length")
-    m, n = S.shape
-    nruns = init.shape[0]
-    labels = np.zeros((max(nruns, 1), max(n, 1)), np.int64)
-    runs = (RcPsmRun * max(nruns, 1))()
-    best, ms, cms = C.c_int32(-1), C.c_double(), C.c_double()
-    _check(L.rc_psm_search_samples(int(device), S.ctypes.data, m, n, int(loss), nruns, init.ctypes.data, order.ctypes.data, int(maxK),
-                                   int(maxsweeps), labels.ctypes.data, runs, C.byref(best), C.byref(ms), C.byref(cms)))
-    return _psm_result(labels, runs, nruns, n, best, ms, counts_ms=float(cms.value))
+    cms = C.c_double()
+
+    def call(n, *tail):
+        _check(L.rc_psm_search_samples(int(device), S.ctypes.data, S.shape[0], n, int(loss), *tail, C.byref(cms)))
+        return dict(counts_ms=float(cms.value))
+    return _search_runs(init, order, maxK, maxsweeps, call, n=S.shape[1])
 
 
 def vi_gtable(n: int) -> np.ndarray:
@@ -768,31 +772,24 @@ def vi_gtable(n: int) -> np.ndarray:
     return out
 
 
-def vi_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0, entry: str = "rc_vi_search"):
+def _exact_search(entry, samples, init, order, maxK, maxsweeps, device) -> dict:
+    """rc_vi_search and rc_id_search have one parameter list"""
+    S = _label_matrix(samples)
+    return _search_runs(init, order, maxK, maxsweeps,
+                        lambda n, *tail: _check(entry(int(device), S.ctypes.data, S.shape[0], n, *tail)), n=S.shape[1])
+
+
+def vi_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
     """rc_vi_search: the exact expected-VI search.  samples: m×n labels in 1..n; init: nruns×n labels (0 = unallocated), order:
     nruns×n 1-based permutations.  Returns psm_search's dict: labels (nruns×n, sortlabels'd), the per-run arrays loss (the
-    expected VI), loss_num (the integer Q), sweeps, converged, moves, K, and best, kernel_ms.  entry: the symbol called —
-    rc_id_search has the same parameter list (id_search)."""
-    L = lib()
-    S = _label_matrix(samples)
-    init = np.ascontiguousarray(init, dtype=np.int64)
-    order = np.ascontiguousarray(order, dtype=np.int32)
-    if init.ndim != 2 or init.shape != order.shape or init.shape[1] != S.shape[1]:
-        raise ValueError("init and order must be nruns×n arrays of the same shape, n the samples' length")
-    m, n = S.shape
-    nruns = init.shape[0]
-    labels = np.zeros((max(nruns, 1), max(n, 1)), np.int64)
-    runs = (RcPsmRun * max(nruns, 1))()
-    best, ms = C.c_int32(-1), C.c_double()
-    _check(getattr(L, entry)(int(device), S.ctypes.data, m, n, nruns, init.ctypes.data, order.ctypes.data, int(maxK), int(maxsweeps),
-                             labels.ctypes.data, runs, C.byref(best), C.byref(ms)))
-    return _psm_result(labels, runs, nruns, n, best, ms)
+    expected VI), loss_num (the integer Q), sweeps, converged, moves, K, and best, kernel_ms."""
+    return _exact_search(lib().rc_vi_search, samples, init, order, maxK, maxsweeps, device)
 
 
 def id_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
     """rc_id_search: the exact expected-ID search.  Arguments and the returned dict as vi_search; loss is the expected
     information distance (nats), loss_num the integer Q_ID."""
-    return vi_search(samples, init, order, maxK=maxK, maxsweeps=maxsweeps, device=device, entry="rc_id_search")
+    return _exact_search(lib().rc_id_search, samples, init, order, maxK, maxsweeps, device)
 
 
 # rc_hclust_merge_t

@@ -1,8 +1,8 @@
 // Hierarchical point estimates on the device: agglomerative clustering of the posterior co-clustering counts C (n×n
 // uint32, C_ii = m) — Medvedovic's method, mcclust's minbinder / mcclust.ext's minVI with method = "avg" / "comp" — and the
 // expected loss of a batch of given labellings under the same counts.  DESIGN.md §8 "Hierarchical point estimates".
-// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, rc_ctx, psm::check_counts, sc::build and
-// the holders of hostutil.inc.hip).
+// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, rc_ctx; the holders, check_counts,
+// check_lds_capacity and LDS_NMAX of hostutil.inc.hip; greedy::shfl_xor_u64; sc::build).
 //
 // Linkage.  Clusters are named by their smallest member.  Per pair of active clusters a < b: S_ab = Σ_{i∈a, j∈b} C_ij (u64)
 // and, for the two extreme linkages, M_ab = min (complete) or max (single) of C_ij over the pair (u32).  The similarity of a
@@ -75,7 +75,7 @@ __device__ inline Cand wave_best(Cand v)
 {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
-        const Cand o{psm::shfl_xor_u64(v.num, off), (unsigned)__shfl_xor((int)v.den, off), (unsigned)__shfl_xor((int)v.idx, off)};
+        const Cand o{greedy::shfl_xor_u64(v.num, off), (unsigned)__shfl_xor((int)v.den, off), (unsigned)__shfl_xor((int)v.idx, off)};
         if (better<LINK>(o, v)) v = o;
     }
     return v;
@@ -89,7 +89,7 @@ __device__ inline Cand block_best(const unsigned long long *num, const unsigned 
     Cand v{num[w], den[w], idx[w]};
 #pragma unroll
     for (int off = NWAVE / 2; off > 0; off >>= 1) {
-        const Cand o{psm::shfl_xor_u64(v.num, off), (unsigned)__shfl_xor((int)v.den, off), (unsigned)__shfl_xor((int)v.idx, off)};
+        const Cand o{greedy::shfl_xor_u64(v.num, off), (unsigned)__shfl_xor((int)v.den, off), (unsigned)__shfl_xor((int)v.idx, off)};
         if (better<LINK>(o, v)) v = o;
     }
     return v;
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256) void k_triu_sum(const unsigned *__restrict__ C
     unsigned long long s = 0;
     for (int c = r + 1 + tid; c < n; c += 256) s += C[(size_t)r * ldc + c];
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += psm::shfl_xor_u64(s, off);
+    for (int off = 32; off > 0; off >>= 1) s += greedy::shfl_xor_u64(s, off);
     if ((tid & 63) == 0) part[tid >> 6] = s;
     __syncthreads();
     if (tid == 0) {
@@ -307,9 +307,7 @@ __global__ __launch_bounds__(TPB) void k_eloss(const unsigned *__restrict__ C, s
 static int32_t check_capacity(rc_ctx *c, const char *who, int64_t m, int64_t n)
 {
     if (m < 1 || n < 1) return fail(c, RC_ERR_ARG, "%s: need m >= 1 and n >= 1 (got m=%lld n=%lld)", who, (long long)m, (long long)n);
-    if (n > psm::NMAX) return fail(c, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %d points whose state fits the workgroup's LDS", who, (long long)n, psm::NMAX);
-    if (m > 0x7FFFFFFFll / n) return fail(c, RC_ERR_CAPACITY, "%s: m*n does not fit 31 bits (m=%lld n=%lld)", who, (long long)m, (long long)n);
-    return RC_OK;
+    return check_lds_capacity(c, who, n, m);
 }
 
 // The partition after the first n − K merges as labels 1..K in sortlabels order: names are smallest members, so a cluster's
@@ -418,7 +416,7 @@ static int32_t check_args(rc_ctx *c, const char *who, int64_t m, int64_t n, int3
 static int32_t run(rc_ctx *c, hipStream_t st, const char *who, const unsigned *dC, int64_t ldc, int64_t m, int64_t n, int32_t linkage,
                    rc_hclust_merge_t *merges_out, int64_t *binder_num, int32_t maxcut, double *vilb, double *kernel_ms)
 {
-    int32_t rc = psm::check_counts(c, st, who, dC, ldc, m, n);
+    int32_t rc = check_counts(c, st, who, dC, ldc, m, n);
     if (rc != RC_OK) return rc;
     DeviceBuffers B;
     Args A{};
@@ -481,7 +479,7 @@ static int32_t run_eloss(rc_ctx *c, hipStream_t st, const char *who, const unsig
     int32_t rc = check_label_rows(c, who, "labelling", labels, L, n);
     if (rc != RC_OK) return rc;
     std::vector<unsigned short> labs(labels, labels + (size_t)L * n);  // narrowed: 1..n fits 16 bits (check_capacity)
-    rc = psm::check_counts(c, st, who, dC, ldc, m, n);
+    rc = check_counts(c, st, who, dC, ldc, m, n);
     if (rc != RC_OK) return rc;
     DeviceBuffers B;
     unsigned long long *d_tot;
@@ -592,7 +590,7 @@ extern "C" int32_t rc_hclust_cut(const void *merges, int64_t n, int64_t K, int64
 {
     const char *who = "rc_hclust_cut";
     if (!labels_out || (!merges && n > 1)) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
-    if (n < 1 || n > psm::NMAX || K < 1 || K > n) return fail(nullptr, RC_ERR_ARG, "%s: need 1 <= K <= n <= %d (got K=%lld n=%lld)", who, psm::NMAX, (long long)K, (long long)n);
+    if (n < 1 || n > LDS_NMAX || K < 1 || K > n) return fail(nullptr, RC_ERR_ARG, "%s: need 1 <= K <= n <= %d (got K=%lld n=%lld)", who, LDS_NMAX, (long long)K, (long long)n);
     std::vector<int> work;
     if (!hcl::cut_labels((const hcl::Merge *)merges, n, K, work, labels_out, nullptr))
         return fail(nullptr, RC_ERR_ARG, "%s: the merges are not a sequence of merges of active clusters a < b", who);

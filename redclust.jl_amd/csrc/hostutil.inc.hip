@@ -1,8 +1,10 @@
 // Host utilities of the entry points that own their device memory for one call (most of them take a device number and no
 // context): a holder of device buffers, a pair of timing events, the check of a label matrix, the tests' environment switches,
-// the dynamic-LDS attribute, the device selection.  Included at the end of redclust_hip.hip after labels.inc.hpp and before every
-// other include (same translation unit: shares fail() and HIPCHK — HIPCHK(nullptr, call) reports into the thread's error
-// buffer).  Both holders release on scope exit, so a HIPCHK may return from anywhere.
+// the dynamic-LDS attribute, the device selection; and what the consumers of a co-clustering count matrix share: the n that fits
+// a workgroup's LDS, the capacity check and the device check of the matrix (k_check_counts, check_counts).  Included at the end
+// of redclust_hip.hip after labels.inc.hpp and before every other include (same translation unit: shares fail() and HIPCHK —
+// HIPCHK(nullptr, call) reports into the thread's error buffer).  Both holders release on scope exit, so a HIPCHK may return
+// from anywhere.
 
 struct DeviceBuffers {
     std::vector<void *> owned;
@@ -86,5 +88,49 @@ static int32_t select_device(const char *who, int32_t device)
     HIPCHK(nullptr, hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(nullptr, RC_ERR_ARG, "%s: device %d not available (%d visible)", who, device, ndev);
     HIPCHK(nullptr, hipSetDevice(device));
+    return RC_OK;
+}
+
+// ---- what the consumers of a co-clustering count matrix share (the searches, hclust, the expected loss)
+
+// One workgroup keeps a state per point in LDS (the searches of greedy.inc.hip, hclust), and where that state holds sums of
+// a row of counts (m >= 1 given) they are kept in 32 bits: RC_ERR_CAPACITY beyond (n >= 1)
+constexpr int LDS_NMAX = 8192;
+static int32_t check_lds_capacity(rc_ctx *c, const char *who, int64_t n, int64_t m = 0)
+{
+    if (n > LDS_NMAX) return fail(c, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %d points whose state fits the workgroup's LDS", who, (long long)n, LDS_NMAX);
+    if (m > 0x7FFFFFFFll / n) return fail(c, RC_ERR_CAPACITY, "%s: m*n does not fit 31 bits (m=%lld n=%lld)", who, (long long)m, (long long)n);
+    return RC_OK;
+}
+
+// counts must be symmetric with diagonal m and no entry above m; flag bits: 1 diagonal, 2 symmetry, 4 range
+__global__ __launch_bounds__(256) void k_check_counts(const unsigned *__restrict__ C, long long ld, int n, unsigned m, unsigned *flag)
+{
+    const int i = blockIdx.y;
+    unsigned bad = 0;
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) {
+        const unsigned v = C[(size_t)i * ld + j];
+        if (j == i) { if (v != m) bad |= 1u; }
+        else if (j > i && v != C[(size_t)j * ld + i]) bad |= 2u;
+        if (v > m) bad |= 4u;
+    }
+    if (bad) atomicOr(flag, bad);
+}
+
+// k_check_counts on the device counts (n × ld), with its flags turned into RC_ERR_ARG messages that start with `who`
+static int32_t check_counts(rc_ctx *c, hipStream_t st, const char *who, const unsigned *dC, int64_t ld, int64_t m, int64_t n)
+{
+    DeviceBuffers B;
+    unsigned *d_flag;
+    HIPCHK(c, B.alloc(d_flag, 1));
+    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(unsigned), st));
+    k_check_counts<<<dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8), (unsigned)n), 256, 0, st>>>(dC, ld, (int)n, (unsigned)m, d_flag);
+    HIPCHK(c, hipGetLastError());
+    unsigned flag = 0;
+    HIPCHK(c, hipMemcpyAsync(&flag, d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (flag & 1u) return fail(c, RC_ERR_ARG, "%s: the diagonal of the counts is not m = %lld everywhere", who, (long long)m);
+    if (flag & 2u) return fail(c, RC_ERR_ARG, "%s: the counts are not symmetric", who);
+    if (flag & 4u) return fail(c, RC_ERR_ARG, "%s: a count exceeds m = %lld", who, (long long)m);
     return RC_OK;
 }

@@ -2,8 +2,10 @@
 // under the posterior co-clustering counts C (n×n uint32, C_ii = m = number of samples) — the step the reference's
 // docs/src/index.md §"Point estimation" sends its users to R's SALSO for; getpointestimate(method = "MPEL")
 // (src/pointestimate.jl:49-58 of the reference) only ever looks at the clusterings the chain visited.
-// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, rc_ctx, the error buffer and the
-// holders of hostutil.inc.hip).
+// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, rc_ctx, the error buffer, the
+// holders and the count-matrix checks of hostutil.inc.hip, and from greedy.inc.hip everything of the search that does not
+// depend on the criterion: the order walk, the keys and the group argmin, the new-cluster candidate, and on the host the
+// shared argument checks, the staging of the runs and the result loop).  What is here: the two scores and their state.
 //
 // Criterion (DESIGN.md §8 "Point-estimate search"):
 //   Binder   num(c) = Σ_{i<j} C_ij + Σ_{i<j, c_i=c_j} (m − 2·C_ij)                 loss = num / (m·n(n−1)/2)   exact integers
@@ -24,8 +26,7 @@
 // W = n + 1 slots when that fits the 160 KiB (always for Binder; VI up to n = 8104); otherwise the occupied slot range
 // 1..hi is covered in passes of W slots (VI, n > 8104, and only while a slot above W is or has been in use).
 //
-// Ties: lower score first; among equal scores the point's own slot (it does not move), then the lowest slot.  A new
-// cluster takes the slot the point just emptied if it emptied one, else the lowest free slot.
+// Ties: greedy.inc.hip.
 
 #include <algorithm>
 #include <cmath>
@@ -33,9 +34,7 @@
 
 namespace psm {
 
-constexpr int TPB = 1024;
-constexpr int NWAVE = TPB / 64;
-constexpr int NMAX = 8192;
+using greedy::TPB, greedy::NWAVE, greedy::Cand, greedy::better, greedy::key_i64, greedy::key_f64, greedy::shfl_xor_u64;
 constexpr double QUANT = 1099511627776.0;            // 2^40
 constexpr size_t LDS_BUDGET = 160 * 1024 - 1024;     // dynamic part; the static reduction scratch is below 1 KiB
 
@@ -58,24 +57,6 @@ struct Args {
     unsigned m;
 };
 
-// (score, priority) pairs compare lexicographically; scores are mapped to u64 so that one reduction serves both losses
-__device__ inline unsigned long long key_i64(long long v) { return (unsigned long long)v ^ 0x8000000000000000ull; }
-__device__ inline unsigned long long key_f64(double v)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v + 0.0);   // (−0 + 0 = +0)
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-struct Cand { unsigned long long sc; unsigned pr, slot, S; };
-
-__device__ inline bool better(unsigned long long sc, unsigned pr, const Cand &b) { return sc < b.sc || (sc == b.sc && pr < b.pr); }
-
-__device__ inline unsigned long long shfl_xor_u64(unsigned long long v, int off)
-{
-    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, off), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), off);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
 template <int Q>
 __device__ inline void load_row(const unsigned *__restrict__ row, int n, int tid, unsigned (&r)[Q])
 {
@@ -84,38 +65,6 @@ __device__ inline void load_row(const unsigned *__restrict__ row, int n, int tid
         const int j = tid + q * TPB;
         r[q] = (j < n) ? row[j] : 0u;
     }
-}
-
-// counts must be symmetric with diagonal m and no entry above m; flag bits: 1 diagonal, 2 symmetry, 4 range
-__global__ __launch_bounds__(256) void k_check(const unsigned *__restrict__ C, long long ld, int n, unsigned m, unsigned *flag)
-{
-    const int i = blockIdx.y;
-    unsigned bad = 0;
-    for (int j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) {
-        const unsigned v = C[(size_t)i * ld + j];
-        if (j == i) { if (v != m) bad |= 1u; }
-        else if (j > i && v != C[(size_t)j * ld + i]) bad |= 2u;
-        if (v > m) bad |= 4u;
-    }
-    if (bad) atomicOr(flag, bad);
-}
-
-// k_check on the device counts (n × ld), with its flags turned into RC_ERR_ARG messages that start with `who`
-static int32_t check_counts(rc_ctx *c, hipStream_t st, const char *who, const unsigned *dC, int64_t ld, int64_t m, int64_t n)
-{
-    DeviceBuffers B;
-    unsigned *d_flag;
-    HIPCHK(c, B.alloc(d_flag, 1));
-    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(unsigned), st));
-    k_check<<<dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8), (unsigned)n), 256, 0, st>>>(dC, ld, (int)n, (unsigned)m, d_flag);
-    HIPCHK(c, hipGetLastError());
-    unsigned flag = 0;
-    HIPCHK(c, hipMemcpyAsync(&flag, d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (flag & 1u) return fail(c, RC_ERR_ARG, "%s: the diagonal of the counts is not m = %lld everywhere", who, (long long)m);
-    if (flag & 2u) return fail(c, RC_ERR_ARG, "%s: the counts are not symmetric", who);
-    if (flag & 4u) return fail(c, RC_ERR_ARG, "%s: a count exceeds m = %lld", who, (long long)m);
-    return RC_OK;
 }
 
 template <int LOSS, int Q>
@@ -160,13 +109,11 @@ __global__ __launch_bounds__(TPB) void k_search(Args A)
         __syncthreads();
     }
 
-    const int *__restrict__ ord = A.order + (size_t)run * n;
+    const greedy::Partials red{r_sc, r_pr, r_slot, r_free, r_S};
+    greedy::Visit v(A.order + (size_t)run * n, n);
     int K = A.K0[run], hi = A.hi0[run];
-    int i = ord[0], i1 = ord[n > 1 ? 1 : 0];
-    int iprev = -1;
-    unsigned wprev = 0;
     unsigned cur[Q], nxt[Q];
-    load_row<Q>(C + (size_t)i * ld, n, tid, cur);
+    load_row<Q>(C + (size_t)v.i * ld, n, tid, cur);
     long long moves = 0;
     int sweeps = 0, converged = 0;
     const double dnew = VI ? -2.0 * log((double)m) : 0.0;
@@ -176,17 +123,10 @@ __global__ __launch_bounds__(TPB) void k_search(Args A)
         int moved = 0;
         for (int t = 0; t < n; ++t) {
             // the next row: issued now, consumed in the next step
-            const int inext = i1;
-            {
-                int t2 = t + 2;
-                if (t2 >= n) t2 -= n;
-                if (t2 >= n) t2 -= n;
-                i1 = ord[t2];
-            }
+            const int i = v.i, inext = v.ahead(t);
             load_row<Q>(C + (size_t)inext * ld, n, tid, nxt);
 
-            // lab[i] was written by another thread without a barrier in between only if i is the previous point (n = 1)
-            const unsigned a = (i == iprev) ? wprev : (unsigned)lab[i];
+            const unsigned a = v.slot_of(lab);
             const int scan_hi = min(hi + 1, n);                          // slots above hi are free; hi + 1 is the lowest of them
             Cand best{~0ull, ~0u, 0u, 0u};
             unsigned minfree = ~0u;
@@ -236,32 +176,10 @@ __global__ __launch_bounds__(TPB) void k_search(Args A)
                     if (better(sc, pr, best)) best = Cand{sc, pr, (unsigned)k, s};
                 }
             }
-            // argmin across the group
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const unsigned long long osc = shfl_xor_u64(best.sc, off);
-                const unsigned opr = (unsigned)__shfl_xor((int)best.pr, off), oslot = (unsigned)__shfl_xor((int)best.slot, off);
-                const unsigned oS = (unsigned)__shfl_xor((int)best.S, off);
-                if (better(osc, opr, best)) best = Cand{osc, opr, oslot, oS};
-                minfree = min(minfree, (unsigned)__shfl_xor((int)minfree, off));
-            }
-            if (lane == 0) { r_sc[wave] = best.sc; r_pr[wave] = best.pr; r_slot[wave] = best.slot; r_S[wave] = best.S; r_free[wave] = minfree; }
-            __syncthreads();
-            best = Cand{r_sc[0], r_pr[0], r_slot[0], r_S[0]};
-            minfree = r_free[0];
-#pragma unroll
-            for (int w = 1; w < NWAVE; ++w) {
-                if (better(r_sc[w], r_pr[w], best)) best = Cand{r_sc[w], r_pr[w], r_slot[w], r_S[w]};
-                minfree = min(minfree, r_free[w]);
-            }
-            // the new-cluster candidate
+            // argmin across the group (the second barrier; only VI's phase C needs the winner's S), then the new-cluster candidate
+            greedy::group_argmin<VI>(best, minfree, red, lane, wave);
             const int Know = K - (int)emptied;
-            unsigned isnew = 0;
-            if (A.maxK == 0 || Know < A.maxK) {
-                const unsigned slot = emptied ? a : minfree;
-                const unsigned pr = emptied ? 0u : minfree;
-                if (better(key_new, pr, best)) { best = Cand{key_new, pr, slot, 0u}; isnew = 1; }
-            }
+            const unsigned isnew = (A.maxK == 0 || Know < A.maxK) ? greedy::offer_new(best, key_new, emptied, a, minfree) : 0u;
             const unsigned w = best.slot;
             // phase C: put i into w.  Per-point entries are written by the thread that owns them, sz by the owner of i;
             // the next step reads sz only behind its first barrier
@@ -278,11 +196,9 @@ __global__ __launch_bounds__(TPB) void k_search(Args A)
                 sz[w] = (unsigned short)(sz[w] + 1);
                 if (VI) T[i] = best.S + m;
             }
-            moved += (a == 0 || w != a) ? 1 : 0;
+            moved += v.moved_to(a, w, inext);
             K = Know + (int)isnew;
             hi = max(hi, (int)w);
-            iprev = i; wprev = w;
-            i = inext;
 #pragma unroll
             for (int q = 0; q < Q; ++q) cur[q] = nxt[q];
         }
@@ -368,27 +284,22 @@ static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, in
                    rc_psm_run_t *runs_out, int32_t *best, double *kernel_ms)
 {
     // ---- the caller's runs: labels in 0..n, orders permutations of 1..n, cluster counts within maxK
-    std::vector<unsigned short> h_init((size_t)nruns * n), h_sz((size_t)nruns * (n + 2), 0);
-    std::vector<int> h_K((size_t)nruns), h_hi((size_t)nruns), h_ord((size_t)nruns * n);
-    std::vector<char> seen((size_t)n);
+    // (the slots are the caller's labels; hi: the highest one in use)
+    greedy::Staging S(nruns, n, (size_t)n + 2);
+    std::vector<int> h_hi((size_t)nruns);
     for (int r = 0; r < nruns; ++r) {
-        unsigned short *szr = h_sz.data() + (size_t)r * (n + 2);
+        unsigned short *szr = S.sz_row(r);
         int K = 0, hi = 0;
         for (int64_t j = 0; j < n; ++j) {
             const int64_t l = init[(size_t)r * n + j];
             if (l < 0 || l > n) return fail(c, RC_ERR_ARG, "point search: label %lld of run %d outside 0..n", (long long)l, r + 1);
-            h_init[(size_t)r * n + j] = (unsigned short)l;
+            S.init_row(r)[j] = (unsigned short)l;
             if (l) { if (szr[l]++ == 0) ++K; hi = std::max(hi, (int)l); }
         }
         if (maxK > 0 && K > maxK) return fail(c, RC_ERR_ARG, "point search: run %d starts with %d clusters, more than maxK = %d", r + 1, K, maxK);
-        h_K[(size_t)r] = K; h_hi[(size_t)r] = hi;
-        std::fill(seen.begin(), seen.end(), 0);
-        for (int64_t t = 0; t < n; ++t) {
-            const int32_t o = order[(size_t)r * n + t];
-            if (o < 1 || o > n || seen[(size_t)o - 1]) return fail(c, RC_ERR_ARG, "point search: the order of run %d is not a permutation of 1..n", r + 1);
-            seen[(size_t)o - 1] = 1;
-            h_ord[(size_t)r * n + t] = o - 1;
-        }
+        S.K[(size_t)r] = K; h_hi[(size_t)r] = hi;
+        const int32_t orc = S.take_order(c, "point search", r, order);
+        if (orc != RC_OK) return orc;
     }
     // ---- the counts: symmetric, diagonal m, nothing above m
     const int32_t crc = check_counts(c, st, "point search", dC, ld, m, n);
@@ -403,82 +314,47 @@ static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, in
     if (const long long v = env_int("RC_PSM_WINDOW"); v >= 1 && v < W) W = v;   // tests: force the windowed passes at small n
     const size_t lds = (fixed + per_slot * (size_t)W + 15) / 16 * 16;
 
-    unsigned short *d_init, *d_sz, *d_lab; int *d_K, *d_hi, *d_ord; RunOut *d_out;
-    HIPCHK(c, B.alloc(d_init, h_init.size()));
-    HIPCHK(c, B.alloc(d_sz, h_sz.size()));
-    HIPCHK(c, B.alloc(d_K, h_K.size()));
+    int *d_hi;
+    HIPCHK(c, S.upload(B, st, sizeof(RunOut)));
     HIPCHK(c, B.alloc(d_hi, h_hi.size()));
-    HIPCHK(c, B.alloc(d_ord, h_ord.size()));
-    HIPCHK(c, B.alloc(d_lab, h_init.size()));
-    HIPCHK(c, B.alloc(d_out, (size_t)nruns));
-    HIPCHK(c, hipMemcpyAsync(d_init, h_init.data(), h_init.size() * 2, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d_sz, h_sz.data(), h_sz.size() * 2, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d_K, h_K.data(), h_K.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_hi, h_hi.data(), h_hi.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d_ord, h_ord.data(), h_ord.size() * 4, hipMemcpyHostToDevice, st));
 
     Args A{};
-    A.C = dC; A.ld = ld; A.init = d_init; A.sz0 = d_sz; A.K0 = d_K; A.hi0 = d_hi; A.order = d_ord; A.labels = d_lab; A.out = d_out;
-    A.n = (int)n; A.W = (int)W; A.maxK = maxK; A.maxsweeps = maxsweeps; A.m = (unsigned)m;
-    TimingEvents ev;
-    HIPCHK(c, ev.create());
-    HIPCHK(c, ev.begin(st));
+    A.C = dC; A.ld = ld; A.init = S.d_init; A.sz0 = S.d_sz; A.K0 = S.d_K; A.hi0 = d_hi; A.order = S.d_order; A.labels = S.d_labels;
+    A.out = (RunOut *)S.d_out; A.n = (int)n; A.W = (int)W; A.maxK = maxK; A.maxsweeps = maxsweeps; A.m = (unsigned)m;
+    HIPCHK(c, S.begin(st));
     const int Q = (int)((n + TPB - 1) / TPB);
     const hipError_t le = vi ? launch<RC_PSM_VILB>(Q, nruns, lds, st, A) : launch<RC_PSM_BINDER>(Q, nruns, lds, st, A);
     if (le != hipSuccess) return fail(c, RC_ERR_HIP, "point search: launch failed: %s", hipGetErrorString(le));
-    HIPCHK(c, ev.end(st));
-    std::vector<unsigned short> h_lab(h_init.size());
-    std::vector<RunOut> h_out((size_t)nruns);
-    HIPCHK(c, hipMemcpyAsync(h_lab.data(), d_lab, h_lab.size() * 2, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(h_out.data(), d_out, h_out.size() * sizeof(RunOut), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    double ms = 0.0;
-    HIPCHK(c, ev.elapsed_ms(ms));
-    if (kernel_ms) *kernel_ms = ms;
+    std::vector<RunOut> h_out;
+    HIPCHK(c, S.collect(st, h_out, kernel_ms));
 
-    // ---- results: sortlabels (utils.jl:69-74), the losses, the first minimum
+    // ---- results: the losses; the best run is the first of minimal loss
     const long long pairs = (long long)n * (n - 1) / 2;
-    std::vector<int> map((size_t)n + 1), cnt((size_t)n + 1);
-    int b = 0;
-    for (int r = 0; r < nruns; ++r) {
-        std::fill(map.begin(), map.end(), 0);
-        std::fill(cnt.begin(), cnt.end(), 0);
-        int next = 0;
-        for (int64_t j = 0; j < n; ++j) {
-            const unsigned short l = h_lab[(size_t)r * n + j];
-            if (!map[l]) map[l] = ++next;
-            labels_out[(size_t)r * n + j] = map[l];
-            cnt[(size_t)map[l]]++;
-        }
-        const RunOut &o = h_out[(size_t)r];
-        rc_psm_run_t &R = runs_out[r];
-        R.sweeps = o.sweeps; R.converged = o.converged; R.moves = o.moves; R.K = o.K;
+    greedy::results(S, h_out, labels_out, runs_out, best, [&](const RunOut &o, rc_psm_run_t &R, const int *cnt, int K) {
         if (vi) {
             R.loss_num = 0;
             R.loss = o.f / (double)n + 2.0 * std::log((double)m);
         } else {
             long long within = 0;
-            for (int k = 1; k <= next; ++k) within += (long long)cnt[(size_t)k] * (cnt[(size_t)k] - 1) / 2;
+            for (int k = 1; k <= K; ++k) within += (long long)cnt[k] * (cnt[k] - 1) / 2;
             R.loss_num = o.tot + (long long)m * within - 2 * o.same;
             R.loss = pairs ? (double)R.loss_num / (double)((long long)m * pairs) : 0.0;
         }
-        if (R.loss < runs_out[b].loss) b = r;
-    }
-    *best = b;
+        return R.loss;
+    });
     return RC_OK;
 }
 
+// greedy::check_args, then what the counts' entry points check besides, in this order
 static int32_t check_args(rc_ctx *c, const char *who, int64_t m, int64_t n, int32_t loss, int32_t nruns, const int64_t *init,
                           const int32_t *order, int32_t maxK, int32_t maxsweeps, const int64_t *labels_out, const void *runs_out,
                           const int32_t *best)
 {
-    if (!init || !order || !labels_out || !runs_out || !best) return fail(c, RC_ERR_ARG, "%s: NULL argument", who);
-    if (m < 1 || n < 1 || nruns < 1) return fail(c, RC_ERR_ARG, "%s: need m >= 1, n >= 1 and nruns >= 1 (got m=%lld n=%lld nruns=%d)", who, (long long)m, (long long)n, nruns);
-    if (maxsweeps < 1 || maxK < 0) return fail(c, RC_ERR_ARG, "%s: need maxsweeps >= 1 and maxK >= 0 (got %d, %d)", who, maxsweeps, maxK);
+    const int32_t rc = greedy::check_args(c, who, m, n, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best);
+    if (rc != RC_OK) return rc;
     if (loss != RC_PSM_BINDER && loss != RC_PSM_VILB) return fail(c, RC_ERR_ARG, "%s: invalid loss specifier %d", who, loss);
-    if (n > NMAX) return fail(c, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %d points whose state fits the workgroup's LDS", who, (long long)n, NMAX);
-    if (m > 0x7FFFFFFFll / n) return fail(c, RC_ERR_CAPACITY, "%s: m*n does not fit 31 bits (m=%lld n=%lld)", who, (long long)m, (long long)n);
-    return RC_OK;
+    return check_lds_capacity(c, who, n, m);
 }
 
 }  // namespace psm

@@ -3,8 +3,8 @@
 // search on those counts without the matrix ever reaching the host.  A live chain builds the same counts as it goes
 // (k_snapshot / k_cocluster_batch, 32 samples per read-modify-write pass over the matrix); here all m samples are present, so
 // every count is computed once from zero in registers and stored once.  DESIGN.md §8 "Counts from samples".
-// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, psm::run, psm::check_args and
-// the holders and select_device of hostutil.inc.hip).
+// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK; the point search's psm::run and
+// psm::check_args; the holders, check_label_rows and select_device of hostutil.inc.hip).
 //
 // Geometry.  The matrix is cut into TI × TJ = 128 × 128 tiles; a 256-thread workgroup computes one tile on or above the
 // diagonal and stores it to both triangles.  A thread owns 8 × 8 counts (64 u32 registers): rows h·64 + ty·4 + 0..3 and columns

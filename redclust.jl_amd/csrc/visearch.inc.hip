@@ -1,7 +1,9 @@
-// Exact posterior expected VI search on the device: the greedy search of pointsearch.inc.hip (same mechanism, same tie
-// rules) for the criterion SALSO calls "VI" proper — the mean over the m samples of VI(c, sample) — instead of Wade &
-// Ghahramani's lower bound.  Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, the
-// error buffer, the holders and select_device of hostutil.inc.hip and psm's sortable-key reduction).
+// Exact posterior expected VI search on the device: the greedy search of greedy.inc.hip (the mechanism and tie rules
+// pointsearch.inc.hip has) for the criterion SALSO calls "VI" proper — the mean over the m samples of VI(c, sample) —
+// instead of Wade & Ghahramani's lower bound.  Included at the end of redclust_hip.hip (same translation unit: shares fail(),
+// HIPCHK, the error buffer; the holders, check_label_rows, check_lds_capacity and select_device of hostutil.inc.hip; and from
+// greedy.inc.hip the order walk, the sortable keys and the group argmin, the new-cluster candidate, and on the host the
+// shared argument checks, the staging of the runs and the result loop).  What is here: the two scores and their tables.
 //
 // Criterion (DESIGN.md §8 "Exact expected VI search"), φ(x) = x·log x:
 //   n·m·E[VI](c) = m·Σ_k φ(n_k) + Σ_s Σ_l φ(n^s_l) − 2·Σ_s Σ_{k,l} φ(N^s_kl),   N^s_kl = #{j : c_j = k, c^s_j = l}
@@ -18,7 +20,7 @@
 // samples r, r + R, … (R = 1024 / G rows per pass) and the slots 4c..4c+3 of each.  Every table element is only ever
 // read (phase A) and written (phase C) by that one thread, so the tables need no barrier of their own.
 // A step: (A) each thread adds Gq[N] of its slots over its samples into four registers, then into the per-slot LDS
-// accumulators with 64-bit integer atomics (order-free); barrier; (B) thread k − 1 scores slot k, argmin by psm's
+// accumulators with 64-bit integer atomics (order-free); barrier; (B) thread k − 1 scores slot k, argmin by greedy's
 // sortable keys; barrier; (C) every thread reads the 16 partials, adds the new-cluster candidate; lab / sz are written
 // by thread 0, N[s][l][a] −= 1 and N[s][l][w] += 1 by the owners of those slots (nothing when a = w).  Two barriers per
 // step.  The next point's m sample labels are loaded into registers at the top of a step and parked in the other half
@@ -37,9 +39,7 @@
 
 namespace visearch {
 
-constexpr int TPB = 1024;
-constexpr int NWAVE = TPB / 64;
-constexpr int NMAX = 8192;
+using greedy::TPB, greedy::NWAVE, greedy::Cand, greedy::key_i64;
 constexpr int KCAP_MAX = 1024;                        // one slot per thread in phase B
 constexpr int VEC = 4;                                // slots per thread in a table row (8 bytes)
 constexpr long long MN_MAX = 1ll << 26;               // |Q| <= 2·m·n·log(n)·2^32 < 2^63
@@ -164,34 +164,27 @@ __global__ __launch_bounds__(TPB) void k_visearch(Args A)
     const int G = kpad / VEC, R = TPB / G;
     const int r = tid / G, c = tid - r * G;
     const bool active = r < R;
-    const int *__restrict__ ord = A.order + (size_t)run * n;
-    int i = ord[0], i1 = ord[n > 1 ? 1 : 0];
-    int iprev = -1, buf = 0;
-    unsigned wprev = 0;
+    const greedy::Partials red{r_sc, r_pr, r_slot, r_free, nullptr};
+    greedy::Visit v(A.order + (size_t)run * n, n);
+    int buf = 0;
     if (PQ) {
 #pragma unroll
         for (int q = 0; q < PQ; ++q) {
             const int s = tid + q * TPB;
-            if (s < m) stage[s] = SL[(size_t)i * m + s];
+            if (s < m) stage[s] = SL[(size_t)v.i * m + s];
         }
     }
     __syncthreads();
 
     long long moves = 0;
     int sweeps = 0, converged = 0;
-    const unsigned long long key_new = psm::key_i64(0);
+    const unsigned long long key_new = key_i64(0);
 
     for (;;) {
         int moved = 0;
         for (int t = 0; t < n; ++t) {
             // the next point's sample labels: issued now, parked in LDS behind the first barrier
-            const int inext = i1;
-            {
-                int t2 = t + 2;
-                if (t2 >= n) t2 -= n;
-                if (t2 >= n) t2 -= n;
-                i1 = ord[t2];
-            }
+            const int i = v.i, inext = v.ahead(t);
             unsigned short nxt[PQ ? PQ : 1];
             if (PQ) {
 #pragma unroll
@@ -202,8 +195,7 @@ __global__ __launch_bounds__(TPB) void k_visearch(Args A)
             }
             const unsigned short *cur = PQ ? stage + (size_t)buf * TPB * PQ : SL + (size_t)i * m;
 
-            // lab[i] was written by another thread without a barrier in between only if i is the previous point (n = 1)
-            const unsigned a = (i == iprev) ? wprev : (unsigned)lab[i];
+            const unsigned a = v.slot_of(lab);
 
             // phase A: Σ_s Gq[N^s[l_s(i)][k]] for this thread's four slots over its samples
             if (active) {
@@ -238,7 +230,7 @@ __global__ __launch_bounds__(TPB) void k_visearch(Args A)
                 }
             }
             const unsigned emptied = (a && sz[a] == 1) ? 1u : 0u;
-            psm::Cand best{~0ull, ~0u, 0u, 0u};
+            Cand best{~0ull, ~0u, 0u, 0u};
             unsigned minfree = ~0u;
             if (tid < kpad) {
                 const unsigned k = (unsigned)tid + 1u;
@@ -256,33 +248,14 @@ __global__ __launch_bounds__(TPB) void k_visearch(Args A)
                         idsc = F1 - F0 - sum;
                     }
                     if (nk <= 0) minfree = k;
-                    else best = psm::Cand{psm::key_i64(LOSS == LOSS_ID ? idsc : (long long)m * Gq[nk] - 2 * sum), (k == a) ? 0u : k, k, 0u};
+                    else best = Cand{key_i64(LOSS == LOSS_ID ? idsc : (long long)m * Gq[nk] - 2 * sum), (k == a) ? 0u : k, k, 0u};
                 }
             }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const unsigned long long osc = psm::shfl_xor_u64(best.sc, off);
-                const unsigned opr = (unsigned)__shfl_xor((int)best.pr, off), oslot = (unsigned)__shfl_xor((int)best.slot, off);
-                if (psm::better(osc, opr, best)) best = psm::Cand{osc, opr, oslot, 0u};
-                minfree = min(minfree, (unsigned)__shfl_xor((int)minfree, off));
-            }
-            if (lane == 0) { r_sc[wave] = best.sc; r_pr[wave] = best.pr; r_slot[wave] = best.slot; r_free[wave] = minfree; }
-            __syncthreads();
-            best = psm::Cand{r_sc[0], r_pr[0], r_slot[0], 0u};
-            minfree = r_free[0];
-#pragma unroll
-            for (int w = 1; w < NWAVE; ++w) {
-                if (psm::better(r_sc[w], r_pr[w], best)) best = psm::Cand{r_sc[w], r_pr[w], r_slot[w], 0u};
-                minfree = min(minfree, r_free[w]);
-            }
-            // the new-cluster candidate: while the cluster count is below the cap there is a free slot in 1..Kcap
+            // argmin across the group (the second barrier), then the new-cluster candidate: while the cluster count is below
+            // the cap there is a free slot in 1..Kcap
+            greedy::group_argmin<false>(best, minfree, red, lane, wave);
             const int Know = K - (int)emptied;
-            unsigned isnew = 0;
-            if (Know < Kcap) {
-                const unsigned slot = emptied ? a : minfree;
-                const unsigned pr = emptied ? 0u : minfree;
-                if (psm::better(key_new, pr, best)) { best = psm::Cand{key_new, pr, slot, 0u}; isnew = 1; }
-            }
+            const unsigned isnew = Know < Kcap ? greedy::offer_new(best, key_new, emptied, a, minfree) : 0u;
             const unsigned w = best.slot;
 
             // phase C: put i into w.  A table element is touched only by the thread that reads it in phase A; lab and sz
@@ -303,10 +276,8 @@ __global__ __launch_bounds__(TPB) void k_visearch(Args A)
                 if (a) sz[a] = (unsigned short)(sz[a] - 1);
                 sz[w] = (unsigned short)(sz[w] + 1);
             }
-            moved += (a == 0 || w != a) ? 1 : 0;
+            moved += v.moved_to(a, w, inext);
             K = Know + (int)isnew;
-            iprev = i; wprev = w;
-            i = inext;
             buf ^= 1;
         }
         ++sweeps;
@@ -341,7 +312,7 @@ __global__ __launch_bounds__(TPB) void k_visearch(Args A)
         q -= (LOSS == LOSS_ID ? 1 : 2) * t2;
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) q += psm::shfl_xor_u64(q, off);
+    for (int off = 32; off > 0; off >>= 1) q += greedy::shfl_xor_u64(q, off);
     if (lane == 0) r_q[wave] = q;
     __syncthreads();
     if (tid == 0) {
@@ -384,16 +355,16 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
                    int32_t *best, double *kernel_ms)
 {
     rc_psm_run_t *runs_out = (rc_psm_run_t *)runs_out_;
-    if (!samples || !init || !order || !labels_out || !runs_out || !best) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
-    if (m < 1 || n < 1 || nruns < 1)
-        return fail(nullptr, RC_ERR_ARG, "%s: need m >= 1, n >= 1 and nruns >= 1 (got m=%lld n=%lld nruns=%d)", who, (long long)m, (long long)n, nruns);
-    if (maxsweeps < 1 || maxK < 0) return fail(nullptr, RC_ERR_ARG, "%s: need maxsweeps >= 1 and maxK >= 0 (got %d, %d)", who, maxsweeps, maxK);
+    if (!samples) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
+    int32_t rc = greedy::check_args(nullptr, who, m, n, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best);
+    if (rc != RC_OK) return rc;
     // the capacity in n and m·n before anything is read
-    if (n > NMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %d points whose state fits the workgroup's LDS", who, (long long)n, NMAX);
+    rc = check_lds_capacity(nullptr, who, n);
+    if (rc != RC_OK) return rc;
     if (m > MN_MAX / n) return fail(nullptr, RC_ERR_CAPACITY, "%s: m*n exceeds 2^26 = %lld (m=%lld n=%lld)", who, MN_MAX, (long long)m, (long long)n);
 
     // ---- the samples: labels 1..n, re-labelled per sample to 0..L_s-1 by first appearance, transposed to [i][s]
-    int32_t rc = check_label_rows(nullptr, who, "sample", samples, m, n);
+    rc = check_label_rows(nullptr, who, "sample", samples, m, n);
     if (rc != RC_OK) return rc;
     std::vector<unsigned short> h_SL((size_t)n * m);
     std::vector<int> map((size_t)n + 1), cnt((size_t)n + 1);
@@ -432,10 +403,8 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
                     who, nruns, (long long)m, Lmax, kpad, (unsigned long long)(TABLE_BUDGET >> 20));
 
     // ---- the runs: labels in 0..n compacted to slots 1..K0 by first appearance, orders permutations of 1..n
-    std::vector<unsigned short> h_init((size_t)nruns * n), h_sz((size_t)nruns * (Kcap + 2), 0);
-    std::vector<int> h_K((size_t)nruns), h_ord((size_t)nruns * n);
+    greedy::Staging S(nruns, n, (size_t)Kcap + 2);
     std::vector<long long> h_Aq((size_t)nruns, 0);                      // ID: Σ_k Φq(n_k) of the start
-    std::vector<char> seen((size_t)n);
     for (int r = 0; r < nruns; ++r) {
         int64_t row, at;                                                // (per run: an earlier run's other errors come first)
         if (find_bad_label(init + (size_t)r * n, 1, n, 0, &row, &at))
@@ -447,49 +416,36 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
             if (l && !map[(size_t)l]) map[(size_t)l] = ++K;
         }
         if (K > Kcap) return fail(nullptr, RC_ERR_ARG, "%s: run %d starts with %d clusters, more than the slot cap %d", who, r + 1, K, Kcap);
+        unsigned short *szr = S.sz_row(r);
         for (int64_t j = 0; j < n; ++j) {
             const int slot = map[(size_t)init[(size_t)r * n + j]];      // map[0] = 0
-            h_init[(size_t)r * n + j] = (unsigned short)slot;
-            if (slot) h_sz[(size_t)r * (Kcap + 2) + slot]++;
+            S.init_row(r)[j] = (unsigned short)slot;
+            if (slot) szr[slot]++;
         }
-        h_K[(size_t)r] = K;
-        for (int k = 1; k <= K; ++k) h_Aq[(size_t)r] += Phi[(size_t)h_sz[(size_t)r * (Kcap + 2) + k]];
-        std::fill(seen.begin(), seen.end(), 0);
-        for (int64_t t = 0; t < n; ++t) {
-            const int32_t o = order[(size_t)r * n + t];
-            if (o < 1 || o > n || seen[(size_t)o - 1]) return fail(nullptr, RC_ERR_ARG, "%s: the order of run %d is not a permutation of 1..n", who, r + 1);
-            seen[(size_t)o - 1] = 1;
-            h_ord[(size_t)r * n + t] = o - 1;
-        }
+        S.K[(size_t)r] = K;
+        for (int k = 1; k <= K; ++k) h_Aq[(size_t)r] += Phi[(size_t)szr[k]];
+        rc = S.take_order(nullptr, who, r, order);
+        if (rc != RC_OK) return rc;
     }
 
     rc = select_device(who, device);
     if (rc != RC_OK) return rc;
 
     DeviceBuffers B;
-    long long *d_G, *d_Phi; unsigned short *d_SL, *d_N, *d_init, *d_sz, *d_lab; int *d_K, *d_ord; RunOut *d_out;
+    long long *d_G, *d_Phi; unsigned short *d_SL, *d_N;
     HIPCHK(nullptr, B.alloc(d_G, Gq.size()));
     HIPCHK(nullptr, B.alloc(d_Phi, Phi.size()));
     HIPCHK(nullptr, B.alloc(d_SL, h_SL.size()));
     HIPCHK(nullptr, B.alloc(d_N, table_elems * (size_t)nruns));
-    HIPCHK(nullptr, B.alloc(d_init, h_init.size()));
-    HIPCHK(nullptr, B.alloc(d_sz, h_sz.size()));
-    HIPCHK(nullptr, B.alloc(d_K, h_K.size()));
-    HIPCHK(nullptr, B.alloc(d_ord, h_ord.size()));
-    HIPCHK(nullptr, B.alloc(d_lab, h_init.size()));
-    HIPCHK(nullptr, B.alloc(d_out, (size_t)nruns));
     HIPCHK(nullptr, hipMemcpy(d_G, Gq.data(), Gq.size() * 8, hipMemcpyHostToDevice));
     HIPCHK(nullptr, hipMemcpy(d_Phi, Phi.data(), Phi.size() * 8, hipMemcpyHostToDevice));
     HIPCHK(nullptr, hipMemcpy(d_SL, h_SL.data(), h_SL.size() * 2, hipMemcpyHostToDevice));
     HIPCHK(nullptr, hipMemset(d_N, 0, table_elems * 2 * (size_t)nruns));
-    HIPCHK(nullptr, hipMemcpy(d_init, h_init.data(), h_init.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(nullptr, hipMemcpy(d_sz, h_sz.data(), h_sz.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(nullptr, hipMemcpy(d_K, h_K.data(), h_K.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(nullptr, hipMemcpy(d_ord, h_ord.data(), h_ord.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(nullptr, S.upload(B, 0, sizeof(RunOut)));
 
     Args A{};
-    A.Gq = d_G; A.Phi = d_Phi; A.SL = d_SL; A.N = d_N; A.init = d_init; A.sz0 = d_sz; A.K0 = d_K; A.order = d_ord; A.labels = d_lab;
-    A.out = d_out; A.n = (int)n; A.m = (int)m; A.Lmax = Lmax; A.kpad = kpad; A.Kcap = Kcap; A.maxsweeps = maxsweeps;
+    A.Gq = d_G; A.Phi = d_Phi; A.SL = d_SL; A.N = d_N; A.init = S.d_init; A.sz0 = S.d_sz; A.K0 = S.d_K; A.order = S.d_order; A.labels = S.d_labels;
+    A.out = (RunOut *)S.d_out; A.n = (int)n; A.m = (int)m; A.Lmax = Lmax; A.kpad = kpad; A.Kcap = Kcap; A.maxsweeps = maxsweeps;
     const int PQ = m <= TPB ? 1 : (m <= (int64_t)TPB * STAGE_Q ? STAGE_Q : 0);
     size_t lds = Carve((int)n, kpad, Kcap, PQ).total;
     if (loss == LOSS_ID) {
@@ -510,38 +466,18 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
         A.tab_lds = (!force_global && lds + 16 * ((size_t)m + 1) <= LDS_MAX) ? 1 : 0;
         lds += A.tab_lds ? 16 * ((size_t)m + 1) : 16;
     }
-    TimingEvents ev;
-    HIPCHK(nullptr, ev.create());
-    HIPCHK(nullptr, ev.begin(0));
+    HIPCHK(nullptr, S.begin(0));
     HIPCHK(nullptr, loss == LOSS_ID ? launch<LOSS_ID>(PQ, nruns, lds, A) : launch<LOSS_VI>(PQ, nruns, lds, A));
-    HIPCHK(nullptr, ev.end(0));
-    double ms = 0.0;
-    HIPCHK(nullptr, ev.elapsed_ms(ms));
-    if (kernel_ms) *kernel_ms = ms;
-    std::vector<unsigned short> h_lab(h_init.size());
-    std::vector<RunOut> h_out((size_t)nruns);
-    HIPCHK(nullptr, hipMemcpy(h_lab.data(), d_lab, h_lab.size() * 2, hipMemcpyDeviceToHost));
-    HIPCHK(nullptr, hipMemcpy(h_out.data(), d_out, h_out.size() * sizeof(RunOut), hipMemcpyDeviceToHost));
+    std::vector<RunOut> h_out;
+    HIPCHK(nullptr, S.collect(0, h_out, kernel_ms));
 
-    // ---- results: sortlabels (utils.jl:69-74), the losses, the first minimum
+    // ---- results: the losses; the best run is the first of minimal Q
     const double scale = std::ldexp((double)n * (double)m, 32);
-    int b = 0;
-    for (int r = 0; r < nruns; ++r) {
-        std::fill(map.begin(), map.end(), 0);
-        int next = 0;
-        for (int64_t j = 0; j < n; ++j) {
-            const unsigned short l = h_lab[(size_t)r * n + j];
-            if (!map[l]) map[l] = ++next;
-            labels_out[(size_t)r * n + j] = map[l];
-        }
-        const RunOut &o = h_out[(size_t)r];
-        rc_psm_run_t &R = runs_out[r];
-        R.sweeps = o.sweeps; R.converged = o.converged; R.moves = o.moves; R.K = o.K;
+    greedy::results(S, h_out, labels_out, runs_out, best, [&](const RunOut &o, rc_psm_run_t &R, const int *, int) {
         R.loss_num = o.Q;
         R.loss = (double)((__int128)o.Q + (loss == LOSS_ID ? (__int128)0 : constant)) / scale;
-        if (R.loss_num < runs_out[b].loss_num) b = r;
-    }
-    *best = b;
+        return R.loss_num;
+    });
     return RC_OK;
 }
 

@@ -174,51 +174,66 @@ def expectedid(clust, samples) -> float:
     return total / (n * len(clusts))
 
 
-def _search_starts(samples, S, nruns, maxK, seed, init, device, mpel_loss, extra):
-    """The runs of the exact searches: nruns Philox orders from empty labels, one run per init labelling, one from the MPEL
-    sample of mpel_loss and one from `extra`, the last three kinds in the identity order; and the slot cap to hand to the
-    library — with maxK = 0 its default is the samples' largest cluster count, which a start with more clusters widens."""
-    n = S.shape[1]
+def _counts_input(samples_or_counts, numsamples, ctx):
+    """The three input forms of searchpointestimate as (samples matrix or None, counts or None, numsamples, n)."""
+    if ctx is not None:
+        if numsamples is None:
+            raise ValueError("numsamples is required with ctx=")
+        return None, None, int(numsamples), ctx.n
+    if hasattr(samples_or_counts, "clusts"):
+        S = _sample_matrix(samples_or_counts)
+        return S, None, S.shape[0], S.shape[1]
+    if samples_or_counts is None:
+        raise ValueError("need an MCMCResult, a count matrix or ctx=")
+    if numsamples is None:
+        raise ValueError("numsamples is required with a count matrix")
+    counts = np.asarray(samples_or_counts)
+    if counts.ndim != 2 or counts.shape[0] != counts.shape[1] or not np.issubdtype(counts.dtype, np.integer):
+        raise ValueError("counts must be a square matrix of integer counts")
+    return None, np.ascontiguousarray(counts, dtype=np.uint32), int(numsamples), counts.shape[0]
+
+
+def _search_starts(n, nruns, seed, init, samples=None, mpel_loss=None, extra=None, device=0):
+    """The runs of every search as (inits, orders): nruns Philox orders from empty labels, drawn in run order; one run per init
+    labelling; given the samples, one from their MPEL sample under mpel_loss; and one from `extra` if there is one — the last
+    three kinds in the identity order.  The count-matrix and ctx forms have neither samples nor extra."""
     inits = [np.zeros(n, np.int64)] * int(nruns)
     rng = np.random.Generator(np.random.Philox(key=int(seed)))
     ident = np.arange(1, n + 1, dtype=np.int32)
     orders = [rng.permutation(n).astype(np.int32) + 1 for _ in range(int(nruns))]
     for lab in ([] if init is None else (np.atleast_2d(np.asarray(init)))):
-        inits.append(np.asarray(lab, np.int64))                      # (lengths were checked by the call that gave `extra`)
-        orders.append(ident)
-    start, _ = getpointestimate(samples, "MPEL", mpel_loss, device=device)
-    inits += [_labels(start), extra]
-    orders += [ident, ident]
-    if not maxK:
-        lmax = max(len(np.unique(s)) for s in S)
-        need = max(len(np.unique(x[x > 0])) for x in inits)
-        maxK = need if need > lmax else 0
-    return np.stack(inits), np.stack(orders), maxK
+        if len(lab) != n:
+            raise ValueError("every labelling in init must have n entries")
+        inits.append(np.asarray(lab, np.int64))
+    if samples is not None:
+        inits.append(_labels(getpointestimate(samples, "MPEL", mpel_loss, device=device)[0]))
+    if extra is not None:
+        inits.append(extra)
+    if not inits:
+        raise ValueError("no run: nruns = 0 and no init")
+    return np.stack(inits), np.stack(orders + [ident] * (len(inits) - len(orders)))
 
 
 _INFO_KEYS = ("loss", "sweeps", "converged", "moves", "K", "labels", "best", "kernel_ms", "loss_num")
 
 
-def _id_search(samples, nruns, maxK, maxsweeps, seed, init, device):
-    """searchpointestimate(loss="ID"): see there."""
-    S = np.stack([_labels(c) for c in samples.clusts])
-    vi_clust, vi = searchpointestimate(samples, "VI", nruns=nruns, maxK=maxK, maxsweeps=maxsweeps, seed=seed, init=init, device=device,
-                                       exact=True)
-    inits, orders, maxK = _search_starts(samples, S, nruns, maxK, seed, init, device, "ID", vi_clust)
-    res = _lib.id_search(S, inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device)
+def _exact_search(samples, loss, nruns, maxK, maxsweeps, seed, init, device):
+    """searchpointestimate(loss="VI", exact=True) and searchpointestimate(loss="ID"): see there.  Two things differ: the
+    library's search, and the call whose result is the last start — the bound's search for VI, the exact VI search for ID —
+    with the key its info is kept under."""
+    search, key = (_lib.id_search, "vi") if loss == "ID" else (_lib.vi_search, "lower_bound")
+    S = _sample_matrix(samples)
+    start, prior = searchpointestimate(samples, "VI", nruns=nruns, maxK=maxK, maxsweeps=maxsweeps, seed=seed, init=init, device=device,
+                                       exact=loss == "ID")
+    inits, orders = _search_starts(S.shape[1], nruns, seed, init, samples, loss, start, device)
+    if not maxK:
+        # the library's default cap is the samples' largest cluster count, which a start with more clusters widens
+        lmax = max(len(np.unique(s)) for s in S)
+        need = max(len(np.unique(x[x > 0])) for x in inits)
+        maxK = need if need > lmax else 0
+    res = search(S, inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device)
     info = {k: res[k] for k in _INFO_KEYS}
-    info["vi"] = vi
-    return res["labels"][res["best"]].copy(), info
-
-
-def _vi_search_exact(samples, nruns, maxK, maxsweeps, seed, init, device):
-    """searchpointestimate(loss="VI", exact=True): see there."""
-    S = np.stack([_labels(c) for c in samples.clusts])
-    _, lower = searchpointestimate(samples, "VI", nruns=nruns, maxK=maxK, maxsweeps=maxsweeps, seed=seed, init=init, device=device)
-    inits, orders, maxK = _search_starts(samples, S, nruns, maxK, seed, init, device, "VI", lower["labels"][lower["best"]])
-    res = _lib.vi_search(S, inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device)
-    info = {k: res[k] for k in _INFO_KEYS}
-    info["lower_bound"] = lower
+    info[key] = prior
     return res["labels"][res["best"]].copy(), info
 
 
@@ -262,7 +277,7 @@ def searchpointestimate(samples_or_counts=None, loss="VI", *, nruns: int = 16, m
             raise ValueError('loss="ID" needs the samples; a Context keeps only their counts')
         if not hasattr(samples_or_counts, "clusts"):
             raise ValueError('loss="ID" needs the samples (an MCMCResult), not a count matrix')
-        return _id_search(samples_or_counts, nruns, maxK, maxsweeps, seed, init, device)
+        return _exact_search(samples_or_counts, "ID", nruns, maxK, maxsweeps, seed, init, device)
     if loss not in _PSM_LOSSES:
         raise ValueError("Invalid loss function specifier.")
     if exact:
@@ -272,78 +287,24 @@ def searchpointestimate(samples_or_counts=None, loss="VI", *, nruns: int = 16, m
             raise ValueError("exact=True needs the samples; a Context keeps only their counts")
         if not hasattr(samples_or_counts, "clusts"):
             raise ValueError("exact=True needs the samples (an MCMCResult), not a count matrix")
-        return _vi_search_exact(samples_or_counts, nruns, maxK, maxsweeps, seed, init, device)
-    samples = None
-    if ctx is not None:
-        if numsamples is None:
-            raise ValueError("numsamples is required with ctx=")
-        counts, n = None, ctx.n
-    elif hasattr(samples_or_counts, "clusts"):
-        samples = samples_or_counts
-        S = np.stack([_labels(c) for c in samples.clusts])             # the counts are built from these on the device
-        counts, (numsamples, n) = None, S.shape
-    else:
-        if samples_or_counts is None:
-            raise ValueError("need an MCMCResult, a count matrix or ctx=")
-        if numsamples is None:
-            raise ValueError("numsamples is required with a count matrix")
-        counts = np.asarray(samples_or_counts)
-        if counts.ndim != 2 or counts.shape[0] != counts.shape[1] or not np.issubdtype(counts.dtype, np.integer):
-            raise ValueError("counts must be a square matrix of integer counts")
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        n = counts.shape[0]
-    inits, orders = [], []
-    rng = np.random.Generator(np.random.Philox(key=int(seed)))
-    ident = np.arange(1, n + 1, dtype=np.int32)
-    for _ in range(int(nruns)):
-        inits.append(np.zeros(n, np.int64))
-        orders.append(rng.permutation(n).astype(np.int32) + 1)
-    for lab in ([] if init is None else (np.atleast_2d(np.asarray(init)))):
-        if len(lab) != n:
-            raise ValueError("every labelling in init must have n entries")
-        inits.append(np.asarray(lab, np.int64))
-        orders.append(ident)
+        return _exact_search(samples_or_counts, "VI", nruns, maxK, maxsweeps, seed, init, device)
+    S, counts, numsamples, n = _counts_input(samples_or_counts, numsamples, ctx)
+    samples = None if S is None else samples_or_counts                  # the counts are built from S on the device
+    inits, orders = _search_starts(n, nruns, seed, init, samples, "binder" if loss == "binder" else "VI", device=device)
     if samples is not None:
-        start, _ = getpointestimate(samples, "MPEL", "binder" if loss == "binder" else "VI", device=device)
-        inits.append(_labels(start))
-        orders.append(ident)
-    if not inits:
-        raise ValueError("no run: nruns = 0 and no init")
-    if samples is not None:
-        res = _lib.psm_search_samples(S, _PSM_LOSSES[loss], np.stack(inits), np.stack(orders), maxK=maxK, maxsweeps=maxsweeps,
-                                      device=device)
+        res = _lib.psm_search_samples(S, _PSM_LOSSES[loss], inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device)
     else:
-        res = _lib.psm_search(counts, int(numsamples), _PSM_LOSSES[loss], np.stack(inits), np.stack(orders), maxK=maxK,
-                              maxsweeps=maxsweeps, device=device, ctx=ctx)
-    info = {k: res[k] for k in ("loss", "sweeps", "converged", "moves", "K", "labels", "best", "kernel_ms", "loss_num")}
+        res = _lib.psm_search(counts, numsamples, _PSM_LOSSES[loss], inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device, ctx=ctx)
+    info = {k: res[k] for k in _INFO_KEYS}
     if samples is not None:
         info["counts_ms"] = res["counts_ms"]
-    if samples is not None and loss == "VI":
-        sizes = np.stack([np.bincount(s, minlength=n + 1)[s] for s in S])
-        info["vi_constant"] = float(np.mean(np.log(sizes)))
+        if loss == "VI":
+            sizes = np.stack([np.bincount(s, minlength=n + 1)[s] for s in S])
+            info["vi_constant"] = float(np.mean(np.log(sizes)))
     return res["labels"][res["best"]].copy(), info
 
 
 _LINKAGES = {"average": 0, "complete": 1, "single": 2}   # RC_HCLUST_AVERAGE, _COMPLETE, _SINGLE
-
-
-def _counts_input(samples_or_counts, numsamples, ctx):
-    """The three input forms of searchpointestimate as (samples matrix or None, counts or None, numsamples, n)."""
-    if ctx is not None:
-        if numsamples is None:
-            raise ValueError("numsamples is required with ctx=")
-        return None, None, int(numsamples), ctx.n
-    if hasattr(samples_or_counts, "clusts"):
-        S = _sample_matrix(samples_or_counts)
-        return S, None, S.shape[0], S.shape[1]
-    if samples_or_counts is None:
-        raise ValueError("need an MCMCResult, a count matrix or ctx=")
-    if numsamples is None:
-        raise ValueError("numsamples is required with a count matrix")
-    counts = np.asarray(samples_or_counts)
-    if counts.ndim != 2 or counts.shape[0] != counts.shape[1] or not np.issubdtype(counts.dtype, np.integer):
-        raise ValueError("counts must be a square matrix of integer counts")
-    return None, np.ascontiguousarray(counts, dtype=np.uint32), int(numsamples), counts.shape[0]
 
 
 def linkage_matrix(merges, numsamples: int, linkage: str = "average") -> np.ndarray:

@@ -8,8 +8,10 @@ import bisect
 
 import numpy as np
 
-from psm_search_ref import sortlabels
-from vi_search_ref import compact, phi_table, relabel
+import greedy_search_ref
+import vi_search_ref
+from greedy_search_ref import sortlabels
+from vi_search_ref import compact, phi_table, relabel  # noqa: F401  (the tests take them from here)
 
 
 def sample_sums(samples, Phi):
@@ -48,99 +50,49 @@ def q_direct(c, samples, G):
     return q
 
 
+class _IdTables(vi_search_ref.Tables):
+    """The exact ID score on the same tables: Δ_k = F(A₀ + G[n_k]) − F(A₀) − Σ_s G[N^s[l_s(i)][k]], with A = Σ_k Φ(n_k) kept up to
+    date as a Python int.  below / above / equal: how the scored candidates lay against the B_s."""
+
+    def __init__(self, samples, G, init, maxK):
+        super().__init__(samples, G, init, maxK)
+        self.Gi = [int(g) for g in self.G]
+        self.Phi = phi_table(G)
+        self.B = sample_sums(self.S, self.Phi)
+        self.Bs, self.Pre = sorted_table(self.B)
+        self.Bset = set(self.B)
+        self.A = sum(self.Phi[int(x)] for x in self.sz)
+        self.below = self.above = self.equal = 0
+
+    def take_out(self, i, a):
+        super().take_out(i, a)
+        self.A -= self.Gi[int(self.sz[a])]
+
+    def scores(self, i, occ):
+        FA = F_sorted(self.A, self.Bs, self.Pre)
+        xs = [self.A + self.Gi[int(self.sz[k])] for k in occ]
+        self.below += sum(x < self.Bs[-1] for x in xs)
+        self.above += sum(x > self.Bs[0] for x in xs)
+        self.equal += sum(x in self.Bset for x in xs)
+        return [F_sorted(x, self.Bs, self.Pre) - FA - int(ak) for x, ak in zip(xs, self.table_sums(i, occ))], None
+
+    def put_in(self, i, w, _):
+        super().put_in(i, w, _)
+        self.A += self.Gi[int(self.sz[w])]
+
+
 def id_search_ref(samples, G, init, order, maxK=0, maxsweeps=100):
     """One run; arguments and the returned dict as vi_search_ref, and besides: below / above, the numbers of scored
     candidates A₀ + G[n_k] that lay strictly below some B_s / strictly above some B_s — whether both sides of the max were
     visited — and equal, the number that met a B_s exactly."""
-    S, Lmax = relabel(samples)
-    m, n = S.shape
-    G = np.asarray(G, np.int64)
-    Gi = [int(g) for g in G]
-    Phi = phi_table(G)
-    B = sample_sums(S, Phi)
-    Bmin, Bmax = min(B), max(B)
-    Bs, Pre = sorted_table(B)
-    Bset = set(B)
-    Kcap = min(maxK if maxK > 0 else Lmax, n)
-    lab = compact(np.asarray(init, np.int64))
-    K = int(lab.max())
-    assert K <= Kcap
-    sz = np.zeros(Kcap + 2, np.int64)
-    N = np.zeros((m, Lmax, Kcap), np.int64)
-    rows = np.arange(m)
-    for j in range(n):
-        if lab[j]:
-            sz[lab[j]] += 1
-            N[rows, S[:, j], lab[j] - 1] += 1
-    A = sum(Phi[int(x)] for x in sz)
-    sweeps = moves = below = above = equal = 0
-    converged = False
-    while sweeps < maxsweeps:
-        moved = 0
-        for i in (int(o) - 1 for o in order):
-            a = int(lab[i])
-            li = S[:, i]
-            if a:
-                lab[i] = 0
-                sz[a] -= 1
-                N[rows, li, a - 1] -= 1
-                A -= Gi[int(sz[a])]
-                if sz[a] == 0:
-                    K -= 1
-            emptied = a != 0 and sz[a] == 0
-            occ = np.flatnonzero(sz[1:Kcap + 1]) + 1
-            best = None                                            # (score, priority, slot, is_new)
-            if len(occ):
-                acc = G[N[rows, li][:, occ - 1]].sum(axis=0)       # Σ_s G[N^s[l_s(i)][k]] (int64: m·G < 2^62)
-                FA = F_sorted(A, Bs, Pre)
-                for k, ak in zip(occ, acc):
-                    x = A + Gi[int(sz[k])]
-                    below += int(x < Bmax)
-                    above += int(x > Bmin)
-                    equal += int(x in Bset)
-                    cand = (F_sorted(x, Bs, Pre) - FA - int(ak), 0 if k == a else int(k), int(k), False)
-                    if best is None or cand[:2] < best[:2]:
-                        best = cand
-            if K < Kcap:
-                slot = a if emptied else int(np.flatnonzero(sz[1:Kcap + 1] == 0)[0]) + 1
-                cand = (0, 0 if emptied else slot, slot, True)
-                if best is None or cand[:2] < best[:2]:
-                    best = cand
-            _, _, w, isnew = best
-            lab[i] = w
-            A += Gi[int(sz[w])]
-            sz[w] += 1
-            N[rows, li, w - 1] += 1
-            K += int(isnew)
-            moved += int(a == 0 or w != a)
-        sweeps += 1
-        moves += moved
-        if moved == 0:
-            converged = True
-            break
-    assert A == sum(Phi[int(x)] for x in sz)
-    q = F(A, B) - sum(Phi[x] * int(cnt) for x, cnt in enumerate(np.bincount(N.ravel())))
-    return dict(raw=lab.copy(), labels=sortlabels(lab), loss_num=q, sweeps=sweeps, converged=converged, moves=moves, K=K, N=N,
-                below=below, above=above, equal=equal)
+    t = _IdTables(samples, G, init, maxK)
+    out = greedy_search_ref.greedy_search(t, order, t.Kcap, maxsweeps)
+    assert t.A == sum(t.Phi[int(x)] for x in t.sz)
+    out.update(loss_num=F(t.A, t.B) - t.phi_of_tables(t.Phi), N=t.N, below=t.below, above=t.above, equal=t.equal)
+    return out
 
 
 def best_single_move_gain(c, samples, G, maxK=0):
     """The largest decrease of Q_ID any single-point move achieves, by brute force over every point and every target
     (existing clusters and, below the cap, a new one): <= 0 means c is a local optimum of the integer criterion."""
-    c = np.asarray(c, np.int64)
-    n = len(c)
-    _, Lmax = relabel(samples)
-    Kcap = min(maxK if maxK > 0 else Lmax, n)
-    base, gain = q_direct(c, samples, G), 0
-    labels = list(np.unique(c))
-    fresh = int(c.max()) + 1
-    for i in range(n):
-        alone = int((c == c[i]).sum()) == 1
-        targets = [l for l in labels if l != c[i]]
-        if len(labels) - int(alone) < Kcap and not alone:
-            targets.append(fresh)
-        for l in targets:
-            x = c.copy()
-            x[i] = l
-            gain = max(gain, base - q_direct(x, samples, G))
-    return gain
+    return vi_search_ref.best_single_move_gain(c, samples, G, maxK, q=q_direct)

@@ -3,6 +3,9 @@ rc_psm_search): a plain loop, test infrastructure only.  Binder runs are exact i
 them bit for bit; VI runs decide on host logarithms and pin properties, not trajectories."""
 import numpy as np
 
+import greedy_search_ref
+from greedy_search_ref import sortlabels  # noqa: F401  (the tests take it from here)
+
 BINDER, VILB = 0, 1
 
 
@@ -19,14 +22,6 @@ def planted_counts(n, m, K, noise, seed):
     for s in range(m):
         counts += (samples[s][:, None] == samples[s][None, :]).astype(np.uint32)
     return samples, counts
-
-
-def sortlabels(x):
-    """utils.jl:69-74: relabel by order of first appearance"""
-    out, seen = np.zeros(len(x), np.int64), {}
-    for i, v in enumerate(x):
-        out[i] = seen.setdefault(int(v), len(seen) + 1)
-    return out
 
 
 def binder_num(c, C, m):
@@ -46,78 +41,58 @@ def vi_f(c, C):
     return float(np.sum(np.log(same.sum(axis=1)) - 2.0 * np.log(T)))
 
 
+class _Counts:
+    """The two scores on the counts: S_ik = Σ_{j∈k} C_ij by a bincount; VI also keeps T_j = Σ_{j' in j's slot} C_jj'"""
+
+    def __init__(self, C, m, loss, init):
+        n = len(init)
+        self.C, self.m, self.loss = C, m, loss
+        self.new_score = 0 if loss == BINDER else -2.0 * np.log(m)
+        self.lab = np.asarray(init, np.int64).copy()
+        self.sz = np.bincount(self.lab, minlength=n + 2)
+        self.sz[0] = 0
+        self.T = np.zeros(n, np.int64)
+        for j in range(n):
+            if self.lab[j]:
+                self.T[j] = C[j, self.lab == self.lab[j]].sum()
+
+    def take_out(self, i, a):
+        mem = self.lab == a
+        self.T[mem] -= self.C[i][mem]
+
+    def scores(self, i, occ):
+        lab, T, row, n = self.lab, self.T, self.C[i], len(self.lab)
+        # every occupied slot at once (bincount of integers below 2^53 in float64 is exact; slot 0 collects the unallocated)
+        S = np.bincount(lab, weights=row.astype(np.float64), minlength=n + 2).astype(np.int64)
+        nk = self.sz[occ]
+        if self.loss == BINDER:
+            d = self.m * nk - 2 * S[occ]
+        else:
+            alloc = lab != 0
+            terms = np.zeros(n)
+            terms[alloc] = np.log((T[alloc] + row[alloc]) / T[alloc])
+            Ls = np.bincount(lab, weights=terms, minlength=n + 2)
+            d = (nk + 1) * np.log(nk + 1) - nk * np.log(nk) - 2.0 * Ls[occ] - 2.0 * np.log(S[occ] + self.m)
+        return d.tolist(), S[occ].tolist()
+
+    def put_in(self, i, w, S):
+        mem = self.lab == w
+        self.T[mem] += self.C[i][mem]
+        self.T[i] = S + self.m
+
+
 def psm_search_ref(C, m, loss, init, order, maxK=0, maxsweeps=100):
     """One run.  init: n labels, 0 = unallocated; order: a permutation of 1..n.  Returns a dict with the raw and the
     sortlabels'd labels, loss, loss_num, sweeps, converged, moves, K."""
     C = np.asarray(C).astype(np.int64)
     n, m = len(init), int(m)
-    lab = np.asarray(init, np.int64).copy()
-    sz = np.zeros(n + 2, np.int64)
-    for l in lab:
-        if l:
-            sz[l] += 1
-    K = int(np.count_nonzero(sz))
-    T = np.zeros(n, np.int64)
-    for j in range(n):
-        if lab[j]:
-            T[j] = C[j, lab == lab[j]].sum()
-    sweeps = moves = 0
-    converged = False
-    while sweeps < maxsweeps:
-        moved = 0
-        for i in (int(o) - 1 for o in order):
-            a = int(lab[i])
-            row = C[i]
-            if a:
-                lab[i] = 0
-                sz[a] -= 1
-                mem = lab == a
-                T[mem] -= row[mem]
-                if sz[a] == 0:
-                    K -= 1
-            emptied = a != 0 and sz[a] == 0
-            # every occupied slot at once (bincount of integers below 2^53 in float64 is exact; slot 0 collects the unallocated)
-            S = np.bincount(lab, weights=row.astype(np.float64), minlength=n + 2).astype(np.int64)
-            occ = np.flatnonzero(sz)
-            best = None                                            # (score, priority, slot, S, is_new)
-            if len(occ):
-                nk = sz[occ]
-                if loss == BINDER:
-                    d = m * nk - 2 * S[occ]
-                else:
-                    alloc = lab != 0
-                    terms = np.zeros(n)
-                    terms[alloc] = np.log((T[alloc] + row[alloc]) / T[alloc])
-                    Ls = np.bincount(lab, weights=terms, minlength=n + 2)
-                    d = (nk + 1) * np.log(nk + 1) - nk * np.log(nk) - 2.0 * Ls[occ] - 2.0 * np.log(S[occ] + m)
-                prio = np.where(occ == a, 0, occ)
-                q = int(np.lexsort((prio, d))[0])
-                best = (d[q], int(prio[q]), int(occ[q]), int(S[occ[q]]), False)
-            if maxK == 0 or K < maxK:
-                slot = a if emptied else int(np.flatnonzero(sz[1:] == 0)[0]) + 1
-                cand = (0 if loss == BINDER else -2.0 * np.log(m), 0 if emptied else slot, slot, 0, True)
-                if best is None or cand[:2] < best[:2]:
-                    best = cand
-            _, _, w, S, isnew = best
-            mem = lab == w
-            T[mem] += row[mem]
-            lab[i] = w
-            sz[w] += 1
-            T[i] = S + m
-            K += int(isnew)
-            moved += int(a == 0 or w != a)
-        sweeps += 1
-        moves += moved
-        if moved == 0:
-            converged = True
-            break
-    out = dict(raw=lab.copy(), labels=sortlabels(lab), sweeps=sweeps, converged=converged, moves=moves, K=K)
+    out = greedy_search_ref.greedy_search(_Counts(C, m, loss, init), order, maxK if maxK else n + 1, maxsweeps)
     if loss == BINDER:
-        num = binder_num(lab, C, m)
+        num = binder_num(out["raw"], C, m)
         pairs = n * (n - 1) // 2
         out.update(loss_num=num, loss=(num / (m * pairs)) if pairs else 0.0)
     else:
-        out.update(loss_num=0, loss=vi_f(lab, C) / n + 2.0 * np.log(m))
+        out.update(loss_num=0, loss=vi_f(out["raw"], C) / n + 2.0 * np.log(m))
     return out
 
 
@@ -154,18 +129,5 @@ def vi_best_move_gain(c, C, m):
 def best_single_move_gain(c, C, m, loss, maxK=0):
     """The largest decrease of the criterion (Binder: num, an int; VI: f) any single-point move achieves, by brute force
     over every point and every target (existing clusters and a new one): <= 0 means c is a local optimum."""
-    c = np.asarray(c, np.int64)
-    n = len(c)
-    ev = (lambda x: binder_num(x, C, m)) if loss == BINDER else (lambda x: vi_f(x, C))
-    base, gain = ev(c), 0
-    labels = list(np.unique(c))
-    fresh = int(c.max()) + 1
-    for i in range(n):
-        targets = [l for l in labels if l != c[i]]
-        if maxK == 0 or len(labels) < maxK:
-            targets.append(fresh)
-        for l in targets:
-            x = c.copy()
-            x[i] = l
-            gain = max(gain, base - ev(x))
-    return gain
+    value = (lambda x: binder_num(x, C, m)) if loss == BINDER else (lambda x: vi_f(x, C))
+    return greedy_search_ref.best_single_move_gain(c, value, lambda k, alone: maxK == 0 or k < maxK)

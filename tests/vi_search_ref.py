@@ -4,7 +4,8 @@ arithmetic on a given table G (Gq of the design: G[x] = rint((φ(x+1) − φ(x))
 bit for bit when the reference is handed the library's table."""
 import numpy as np
 
-from psm_search_ref import sortlabels
+import greedy_search_ref
+from greedy_search_ref import sortlabels
 
 
 def numpy_G(n):
@@ -56,84 +57,56 @@ def constant(samples, G):
     return sum(Phi[int(x)] for s in np.asarray(samples) for x in np.bincount(s))
 
 
+class Tables:
+    """The exact VI score on the contingency tables N (m × Lmax × Kcap): Δ_k = m·G[n_k] − 2·Σ_s G[N^s[l_s(i)][k]]"""
+    new_score = 0
+
+    def __init__(self, samples, G, init, maxK):
+        self.S, self.Lmax = relabel(samples)
+        self.m, n = self.S.shape
+        self.G = np.asarray(G, np.int64)
+        self.Kcap = min(maxK if maxK > 0 else self.Lmax, n)
+        self.lab = compact(np.asarray(init, np.int64))
+        assert int(self.lab.max()) <= self.Kcap
+        self.sz = np.bincount(self.lab, minlength=self.Kcap + 2)
+        self.sz[0] = 0
+        self.N = np.zeros((self.m, self.Lmax, self.Kcap), np.int64)
+        self.rows = np.arange(self.m)
+        for j in np.flatnonzero(self.lab):
+            self.N[self.rows, self.S[:, j], self.lab[j] - 1] += 1
+
+    def take_out(self, i, a):
+        self.N[self.rows, self.S[:, i], a - 1] -= 1
+
+    def table_sums(self, i, occ):
+        """Σ_s G[N^s[l_s(i)][k]] of the slots k of occ (int64: m·G < 2^62)"""
+        return self.G[self.N[self.rows, self.S[:, i]][:, occ - 1]].sum(axis=0)
+
+    def scores(self, i, occ):
+        return (self.m * self.G[self.sz[occ]] - 2 * self.table_sums(i, occ)).tolist(), None
+
+    def put_in(self, i, w, _):
+        self.N[self.rows, self.S[:, i], w - 1] += 1
+
+    def phi_of_tables(self, Phi):
+        """Σ_s Σ_kl Φ(N^s_kl), a Python int"""
+        return sum(Phi[x] * int(cnt) for x, cnt in enumerate(np.bincount(self.N.ravel())))
+
+
 def vi_search_ref(samples, G, init, order, maxK=0, maxsweeps=100):
     """One run.  samples: m×n labels; init: n labels, 0 = unallocated; order: a permutation of 1..n.  Returns a dict with
     the raw slots and the sortlabels'd labels, loss_num (Q of the final labelling, summed over the tables it kept), sweeps,
     converged, moves, K, and the final tables N (m × Lmax × Kcap)."""
-    S, Lmax = relabel(samples)
-    m, n = S.shape
-    G = np.asarray(G, np.int64)
-    Kcap = min(maxK if maxK > 0 else Lmax, n)
-    lab = compact(np.asarray(init, np.int64))
-    K = int(lab.max())
-    assert K <= Kcap
-    sz = np.zeros(Kcap + 2, np.int64)
-    N = np.zeros((m, Lmax, Kcap), np.int64)
-    rows = np.arange(m)
-    for j in range(n):
-        if lab[j]:
-            sz[lab[j]] += 1
-            N[rows, S[:, j], lab[j] - 1] += 1
-    sweeps = moves = 0
-    converged = False
-    while sweeps < maxsweeps:
-        moved = 0
-        for i in (int(o) - 1 for o in order):
-            a = int(lab[i])
-            li = S[:, i]
-            if a:
-                lab[i] = 0
-                sz[a] -= 1
-                N[rows, li, a - 1] -= 1
-                if sz[a] == 0:
-                    K -= 1
-            emptied = a != 0 and sz[a] == 0
-            occ = np.flatnonzero(sz[1:Kcap + 1]) + 1
-            best = None                                            # (score, priority, slot, is_new)
-            if len(occ):
-                acc = G[N[rows, li][:, occ - 1]].sum(axis=0)       # Σ_s G[N^s[l_s(i)][k]] (int64: m·G < 2^62)
-                d = m * G[sz[occ]] - 2 * acc
-                prio = np.where(occ == a, 0, occ)
-                q = int(np.lexsort((prio, d))[0])
-                best = (int(d[q]), int(prio[q]), int(occ[q]), False)
-            if K < Kcap:
-                slot = a if emptied else int(np.flatnonzero(sz[1:Kcap + 1] == 0)[0]) + 1
-                cand = (0, 0 if emptied else slot, slot, True)
-                if best is None or cand[:2] < best[:2]:
-                    best = cand
-            _, _, w, isnew = best
-            lab[i] = w
-            sz[w] += 1
-            N[rows, li, w - 1] += 1
-            K += int(isnew)
-            moved += int(a == 0 or w != a)
-        sweeps += 1
-        moves += moved
-        if moved == 0:
-            converged = True
-            break
+    t = Tables(samples, G, init, maxK)
+    out = greedy_search_ref.greedy_search(t, order, t.Kcap, maxsweeps)
     Phi = phi_table(G)
-    q = m * sum(Phi[int(x)] for x in sz) - 2 * sum(Phi[x] * int(cnt) for x, cnt in enumerate(np.bincount(N.ravel())))
-    return dict(raw=lab.copy(), labels=sortlabels(lab), loss_num=q, sweeps=sweeps, converged=converged, moves=moves, K=K, N=N)
+    out.update(loss_num=t.m * sum(Phi[int(x)] for x in t.sz) - 2 * t.phi_of_tables(Phi), N=t.N)
+    return out
 
 
-def best_single_move_gain(c, samples, G, maxK=0):
-    """The largest decrease of Q any single-point move achieves, by brute force over every point and every target
-    (existing clusters and, below the cap, a new one): <= 0 means c is a local optimum of the integer criterion."""
-    c = np.asarray(c, np.int64)
-    n = len(c)
-    _, Lmax = relabel(samples)
-    Kcap = min(maxK if maxK > 0 else Lmax, n)
-    base, gain = q_direct(c, samples, G), 0
-    labels = list(np.unique(c))
-    fresh = int(c.max()) + 1
-    for i in range(n):
-        alone = int((c == c[i]).sum()) == 1
-        targets = [l for l in labels if l != c[i]]
-        if len(labels) - int(alone) < Kcap and not alone:
-            targets.append(fresh)
-        for l in targets:
-            x = c.copy()
-            x[i] = l
-            gain = max(gain, base - q_direct(x, samples, G))
-    return gain
+def best_single_move_gain(c, samples, G, maxK=0, q=None):
+    """The largest decrease of Q (q = q_direct of this module unless given) any single-point move achieves, by brute force
+    over every point and every target (existing clusters and, below the cap, a new one): <= 0 means c is a local optimum of
+    the integer criterion."""
+    Kcap = min(maxK if maxK > 0 else relabel(samples)[1], len(c))
+    return greedy_search_ref.best_single_move_gain(c, lambda x: (q or q_direct)(x, samples, G), lambda k, alone: not alone and k < Kcap)

@@ -724,6 +724,55 @@ int32_t rc_relabel(int32_t device, const int64_t *samples /* m×n, labels 1..n *
                    int64_t *labels_out /* m×n or NULL */, int64_t *maps_out /* m×maps_width or NULL */, int64_t maps_width,
                    int64_t *overlap_out /* m */, void *counts_out /* uint32_t n×(Kp+1) */, double *kernel_ms);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Scoring labellings: the log-likelihood (src/mcmc.jl:1-56) and log-prior (src/mcmc.jl:58-78) of each of L given labellings
+ * under the model, against the context's fixed-point matrices as they are (64- or 32-bit storage, logD stored or derived,
+ * the current internal point order read through its index map).  DESIGN.md §8 "Scoring labellings".
+ *
+ * For labelling l with its K_l clusters in ascending label order k = 0..K_l−1 and k <= t,
+ *   B_D[l][k][t] = Σ_{i in k} Σ_{j in t} Dq[i][j]        B_L[l][k][t] likewise for logD (diagonal 0; D's as stored)
+ * — rows in the smaller label, columns in the larger, matsum(D, clust_k, clust_t) of mcmc.jl:48 and what rc_loglik reads.
+ * D need not be symmetric.  Every block is an exact integer carried as two halves, value = hi·2^24 + lo, each half the sum
+ * of the halves of the per-row sums Σ_{j in t} Dq[i][j] (an int64 each), so n² terms cannot overflow.  Every output is a
+ * pure function of (matrices, labelling): bit for bit the same whatever L is, however the call is chunked and whichever
+ * other labellings share it.  The matrices are read once per chunk of labellings, never once per labelling.
+ *
+ * loglik_out[l] equals, bit for bit, rc_set_state(labels[l]) + rc_loglik on the same context with the same parameters
+ * (params NULL: the context's, which must then be set; otherwise as after rc_set_params(params)).  logprior_out (may be
+ * NULL; needs r and p) is rc_logprior(r[l], p[l]) of that state.  K_out (may be NULL): the K_l.  blocks_out (may be NULL):
+ * per labelling in turn its K_l(K_l+1)/2 blocks in row-major (k, t >= k) order, 4 int64 each (D_hi, D_lo, L_hi, L_lo);
+ * blocks_len is the caller's count of blocks and must equal Σ_l K_l(K_l+1)/2 (0 with a NULL pointer).  eD_out, eL_out (may
+ * be NULL): the context's exponents, Dq = D·2^eD and Lq = logD·2^eL, which rc_loglik_from_blocks takes.  kernel_ms (may be
+ * NULL): device time of the call's kernels.
+ *
+ * The call waits for the context's streams first and leaves the chain state, the layout, the row-sum tables, the
+ * co-clustering counts and the choice of kernels untouched; a context with no state set is fine.
+ *
+ * Errors, all before any device work.  RC_ERR_ARG: ctx, labels or loglik_out NULL; L < 1; a label outside 1..n (the
+ * message names the labelling and the position); an r that is <= 0 or not finite; a p outside (0, 1); logprior_out without
+ * r and p; params that rc_set_params would reject; a blocks_len that does not match.  RC_ERR_STATE: params NULL on a
+ * context without parameters.  RC_ERR_CAPACITY: n > 32767, L·n >= 2^31, a labelling of more than 4096 clusters.  L is
+ * otherwise unbounded in memory terms: the rows and the labellings go through a device workspace of about 1 GiB in chunks.
+ * RC_SCORE_ROWS_GLOBAL=1 in the environment (read at every call) makes the sums gather from the staged rows in global
+ * memory instead of LDS, as n > 10240 does, and RC_SCORE_WORKSPACE_KIB=<k> shrinks the workspace so that small calls are
+ * chunked — the same integers either way; for tests.
+ * ------------------------------------------------------------------------------------------------------------- */
+int32_t rc_score_labellings(rc_ctx *ctx, int64_t L, const int64_t *labels /* L×n, labels 1..n */,
+                            const double *r /* L or NULL */, const double *p /* L or NULL */,
+                            const rc_params *params /* NULL: the context's */,
+                            double *loglik_out /* L */, double *logprior_out /* L or NULL */, int64_t *K_out /* L or NULL */,
+                            int64_t *blocks_out /* blocks_len×4 or NULL */, int64_t blocks_len,
+                            int32_t *eD_out, int32_t *eL_out, double *kernel_ms);
+
+/* The scalar part of loglik for ONE labelling from its block sums, under any hyperparameters: host only, no device is
+ * touched and no context is needed.  sizes: the K cluster sizes in ascending label order (each >= 1, Σ = n); blocks: the
+ * K(K+1)/2 × 4 int64 of rc_score_labellings; eD, eL: the exponents it reported.  Long double arithmetic, terms summed in
+ * ascending label order — the arithmetic of rc_loglik, so with the parameters of the scoring call the result is its
+ * loglik_out bit for bit.  RC_ERR_ARG: a NULL pointer, n or K < 1, K > n, sizes that are not positive or do not sum to n,
+ * params that rc_set_params would reject. */
+int32_t rc_loglik_from_blocks(int64_t n, int64_t K, const int64_t *sizes /* K */, const int64_t *blocks /* K(K+1)/2 × 4 */,
+                              int32_t eD, int32_t eL, const rc_params *params, double *out);
+
 #ifdef __cplusplus
 }
 #endif

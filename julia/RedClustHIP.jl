@@ -707,4 +707,67 @@ end
 
 export relabel
 
+"""
+    scorelabellings(HIPBackend(), data, labellings, params; r = nothing, p = nothing) -> (loglik, logprior, logposterior, K, kernel_ms)
+
+The log-likelihood of each of `L` labellings (a vector of label vectors, or the `clusts` of a result) under the model with
+hyperparameters `params`, on the GPU (rc_score_labellings): one pass over the matrices for the whole batch, the K×K block
+sums of D and log D of every labelling in exact integers, the scalar part in extended precision.  With `r` and `p` (scalars
+or one per labelling) the log-prior and the log-posterior as well; they are `nothing` otherwise.
+"""
+function scorelabellings(b::HIPBackend, data::MCMCData, labellings::Vector{<:AbstractVector{<:Integer}},
+                         params::PriorHyperparamsList; r = nothing, p = nothing)
+    n = size(data.D, 1)
+    L = length(labellings)
+    labels = Matrix{Int64}(undef, n, L)                           # column l = labelling l: row-major L×n for the library
+    for l in 1:L
+        length(labellings[l]) == n || throw(ArgumentError("Length of the input vectors must be equal."))
+        labels[:, l] .= labellings[l]
+    end
+    (r === nothing) == (p === nothing) || throw(ArgumentError("Give both r and p, or neither."))
+    withprior = r !== nothing
+    rv = withprior ? (r isa Real ? fill(Float64(r), L) : Vector{Float64}(r)) : Float64[]
+    pv = withprior ? (p isa Real ? fill(Float64(p), L) : Vector{Float64}(p)) : Float64[]
+    !withprior || (length(rv) == L && length(pv) == L) || throw(ArgumentError("r and p must hold one value per labelling."))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = ccall((:rc_create, LIB), Int32,
+               (Int64, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Int32, Int64, Ref{Ptr{Cvoid}}),
+               n, data.D, Ptr{Cdouble}(C_NULL), 64, b.device, 0, h)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    ctx = h[]
+    loglik = Vector{Float64}(undef, L); logprior = Vector{Float64}(undef, L); K = Vector{Int64}(undef, L)
+    ms = Cdouble[0]
+    try
+        rc = GC.@preserve rv pv logprior ccall((:rc_score_labellings, LIB), Int32,
+                   (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{RcParams}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int64},
+                    Ptr{Int64}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}),
+                   ctx, L, labels, withprior ? pointer(rv) : Ptr{Cdouble}(C_NULL), withprior ? pointer(pv) : Ptr{Cdouble}(C_NULL),
+                   Ref(RcParams(params)), loglik, withprior ? pointer(logprior) : Ptr{Cdouble}(C_NULL), K, C_NULL, 0, C_NULL, C_NULL, ms)
+        check(ctx, rc)
+    finally
+        ccall((:rc_destroy, LIB), Int32, (Ptr{Cvoid},), ctx)
+    end
+    return (loglik = loglik, logprior = withprior ? logprior : nothing, logposterior = withprior ? loglik .+ logprior : nothing,
+            K = K, kernel_ms = ms[1])
+end
+
+scorelabellings(b::HIPBackend, data::MCMCData, result::MCMCResult, params::PriorHyperparamsList = result.params) =
+    scorelabellings(b, data, [Vector{Int64}(c) for c in result.clusts], params; r = result.r, p = result.p)
+
+"""
+    mapestimate(HIPBackend(), data, candidates, params; r, p) -> (clust, info)
+
+The candidate labelling of highest log-posterior under the model (the first of equals), with the scores of all of them:
+`info.index`, `info.loglik`, `info.logprior`, `info.logposterior`, `info.K`.  `r` and `p` are scalars or one per candidate.
+"""
+function mapestimate(b::HIPBackend, data::MCMCData, candidates::Vector{<:AbstractVector{<:Integer}},
+                     params::PriorHyperparamsList; r, p)
+    sc = scorelabellings(b, data, candidates, params; r = r, p = p)
+    best = argmax(sc.logposterior)                                # the first maximum
+    return (Vector{Int64}(candidates[best]), (index = best, loglik = sc.loglik, logprior = sc.logprior,
+                                              logposterior = sc.logposterior, K = sc.K, kernel_ms = sc.kernel_ms))
+end
+
+export scorelabellings, mapestimate
+
 end # module

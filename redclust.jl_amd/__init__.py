@@ -17,3 +17,4 @@ from .pointestimate import (getpointestimate, lossmatrix, binderloss, infodist, 
                             linkage_matrix, leaf_order, partitiondistances, expecteddistances, credibleball,
                             credibleball_from_distances, relabel, Relabelling)
 from .predict import predict, Prediction  # noqa: F401
+from .score import scorelabellings, loglik_from_blocks, mapestimate, reweight  # noqa: F401

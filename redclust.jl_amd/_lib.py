@@ -223,6 +223,11 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "rc_relabel": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "rc_score_labellings": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RcParams), C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_double)]),
+    "rc_loglik_from_blocks": (C.c_int32, [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RcParams),
+                                          C.POINTER(C.c_double)]),
     "rc_layout_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rc_event_overhead_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "rc_kernel_timing": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -551,6 +556,46 @@ class Context:
         split=True (rc_kmeans_scan_split): also every k's within / between split of the context's D under its final
         assignment, as kmedoids_scan returns it.  slots_per_chunk: runs per device pass (0 = automatic; same results)."""
         return self._scan("kmeans", kmin, kmax, maxiter, tol, seed, split, int(slots_per_chunk))
+
+    def score(self, labellings, r=None, p=None, params=None, want_blocks=False) -> dict:
+        """rc_score_labellings: the log-likelihood of each of L labellings (L×n int64 labels in 1..n, or one labelling) under
+        the model, against this context's matrices; its state, layout and counts are untouched.  r, p: one value per labelling
+        (or None: no log-prior); params: a dict of hyperparameters (None: the context's).  Returns a dict: loglik (L), logprior
+        and logposterior = loglik + logprior (L, or None without r and p), K (L), sizes (a list of L int64 arrays: the cluster
+        sizes in ascending label order), blocks (with want_blocks a list of L int64 arrays K(K+1)/2 × 4: the upper-triangle
+        block sums (D_hi, D_lo, L_hi, L_lo) in row-major (k, t >= k) order, value = hi·2^24 + lo; else None), eD, eL (the
+        exponents loglik_from_blocks takes), kernel_ms."""
+        lab = np.ascontiguousarray(labellings, dtype=np.int64)
+        if lab.ndim == 1:
+            lab = lab[None, :]
+        if lab.ndim != 2 or lab.shape[1] != self.n:
+            raise ValueError("labellings must be an L×n matrix of labels with the context's n columns")
+        nl = lab.shape[0]
+        if (r is None) != (p is None):
+            raise ValueError("give both r and p, or neither")
+        if r is not None:
+            r = np.ascontiguousarray(np.broadcast_to(np.asarray(r, dtype=np.float64).reshape(-1), (nl,)))
+            p = np.ascontiguousarray(np.broadcast_to(np.asarray(p, dtype=np.float64).reshape(-1), (nl,)))
+        prm = None if params is None else _params_struct(params)
+        valid = lab.size > 0 and lab.min() >= 1 and lab.max() <= self.n            # otherwise the library names the label
+        sizes = [np.bincount(row, minlength=self.n + 1)[1:] for row in lab] if valid else []
+        sizes = [z[z > 0].astype(np.int64) for z in sizes]
+        nblocks = sum(len(z) * (len(z) + 1) // 2 for z in sizes) if want_blocks else 0
+        ll, K = np.zeros(max(nl, 1)), np.zeros(max(nl, 1), np.int64)
+        lp = np.zeros(max(nl, 1)) if r is not None else None
+        blocks = np.zeros((max(nblocks, 1), 4), np.int64) if want_blocks else None
+        eD, eL, ms = C.c_int32(), C.c_int32(), C.c_double()
+        self._chk(self.L.rc_score_labellings(self.h, nl, lab.ctypes.data, None if r is None else r.ctypes.data,
+                                             None if p is None else p.ctypes.data, None if prm is None else C.byref(prm),
+                                             ll.ctypes.data, None if lp is None else lp.ctypes.data, K.ctypes.data,
+                                             None if blocks is None else blocks.ctypes.data, nblocks, C.byref(eD), C.byref(eL),
+                                             C.byref(ms)))
+        per = None
+        if want_blocks:
+            off = np.concatenate([[0], np.cumsum([len(z) * (len(z) + 1) // 2 for z in sizes])])
+            per = [blocks[off[i]:off[i + 1]] for i in range(nl)]
+        return dict(loglik=ll[:nl], logprior=None if lp is None else lp[:nl], logposterior=None if lp is None else ll[:nl] + lp[:nl],
+                    K=K[:nl], sizes=sizes, blocks=per, eD=int(eD.value), eL=int(eL.value), kernel_ms=float(ms.value))
 
     def layout_info(self):
         """(layouts built so far, label runs in the internal point order)"""
@@ -950,6 +995,23 @@ def relabel(samples, pivot, want_labels: bool = True, want_maps: bool = True, de
                       None if maps is None else maps.ctypes.data, W, overlap.ctypes.data, counts.ctypes.data, C.byref(ms))
     _check(rc)
     return dict(labels=labels, maps=maps, overlap=overlap, counts=counts, pivot_labels=names, kernel_ms=float(ms.value))
+
+
+def loglik_from_blocks(blocks, sizes, n: int, eD: int, eL: int, params: dict) -> float:
+    """rc_loglik_from_blocks (host only): the log-likelihood of one labelling from its upper-triangle block sums (K(K+1)/2 × 4
+    int64 as Context.score returns them), its cluster sizes in ascending label order and the context's exponents, under any
+    hyperparameters."""
+    L = lib()
+    sz = np.ascontiguousarray(sizes, dtype=np.int64).reshape(-1)
+    B = np.ascontiguousarray(blocks, dtype=np.int64)
+    K = len(sz)
+    if B.size != K * (K + 1) // 2 * 4:
+        raise ValueError("blocks must hold K(K+1)/2 × 4 integers for the K sizes")
+    prm = _params_struct(params)
+    out = C.c_double()
+    _check(L.rc_loglik_from_blocks(int(n), K, sz.ctypes.data if K else None, B.ctypes.data if B.size else None, int(eD), int(eL),
+                                   C.byref(prm), C.byref(out)))
+    return float(out.value)
 
 
 def sample_k(n: int, r, p, seed: int = 0, device: int = 0):

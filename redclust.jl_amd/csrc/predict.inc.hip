@@ -45,23 +45,13 @@ template <bool ATOMIC> __device__ __forceinline__ void flush(ll2 *o, long long s
     }
 }
 
-// rows: [points][n] (Dq, Lq); perm: [n][ms_pad]; koff: [ms] first slot of every sample; startslot: [parts][ms_pad] slot of a
-// part's first position (ATOMIC only); sums: [points][ktot].  Grid: one block per point.
-template <bool LDSROW, bool ATOMIC>
-__global__ __launch_bounds__(TPB1) void k_predict_sums(const ll2 *__restrict__ rows, int n, const unsigned short *__restrict__ perm, int ms, int ms_pad,
-                                                       int parts, const int *__restrict__ startslot, const long long *__restrict__ koff, long long ktot,
-                                                       ll2 *__restrict__ sums)
+// The walk of one row (in LDS or global memory) through the sorted orders of ms samples, shared with the scoring of labellings
+// (score.inc.hip): perm: [n][ms_pad]; koff: [ms] first slot of every sample; startslot: [parts][ms_pad] slot of a part's first
+// position (ATOMIC only); out: the row's [ktot] sums.
+template <bool ATOMIC>
+__device__ __forceinline__ void walk_sums(const ll2 *__restrict__ row, int n, const unsigned short *__restrict__ perm, int ms, int ms_pad, int parts,
+                                          const int *__restrict__ startslot, const long long *__restrict__ koff, ll2 *__restrict__ out)
 {
-    extern __shared__ __align__(16) unsigned char prd_lds[];
-    const ll2 *grow = rows + (size_t)blockIdx.x * (size_t)n;
-    const ll2 *row = grow;
-    if (LDSROW) {
-        ll2 *l = reinterpret_cast<ll2 *>(prd_lds);
-        for (int j = threadIdx.x; j < n; j += blockDim.x) l[j] = grow[j];
-        __syncthreads();
-        row = l;
-    }
-    ll2 *out = sums + (size_t)blockIdx.x * (size_t)ktot;
     for (int w = threadIdx.x; w < ms_pad * parts; w += blockDim.x) {
         const int part = w / ms_pad, s = w - part * ms_pad;
         if (s >= ms) continue;
@@ -105,6 +95,24 @@ __global__ __launch_bounds__(TPB1) void k_predict_sums(const ll2 *__restrict__ r
         }
         if (ATOMIC && !(e & 0x8000u)) flush<ATOMIC>(o, sd, sl);   // the part ends inside a slot
     }
+}
+
+// rows: [points][n] (Dq, Lq); sums: [points][ktot]; the rest as walk_sums.  Grid: one block per point.
+template <bool LDSROW, bool ATOMIC>
+__global__ __launch_bounds__(TPB1) void k_predict_sums(const ll2 *__restrict__ rows, int n, const unsigned short *__restrict__ perm, int ms, int ms_pad,
+                                                       int parts, const int *__restrict__ startslot, const long long *__restrict__ koff, long long ktot,
+                                                       ll2 *__restrict__ sums)
+{
+    extern __shared__ __align__(16) unsigned char prd_lds[];
+    const ll2 *grow = rows + (size_t)blockIdx.x * (size_t)n;
+    const ll2 *row = grow;
+    if (LDSROW) {
+        ll2 *l = reinterpret_cast<ll2 *>(prd_lds);
+        for (int j = threadIdx.x; j < n; j += blockDim.x) l[j] = grow[j];
+        __syncthreads();
+        row = l;
+    }
+    walk_sums<ATOMIC>(row, n, perm, ms, ms_pad, parts, startslot, koff, sums + (size_t)blockIdx.x * (size_t)ktot);
 }
 
 struct DrawArgs {

@@ -4702,6 +4702,16 @@ __global__ __launch_bounds__(1024) void k_sweep_wide(View V, SweepArgs sa, int g
 // ---------------------------------------------------------------------------------------------------
 #define RC_LO_BITS 24
 #define RC_BS_TILE 4096   // slots k per block (LDS bins: 32 B each); blockIdx.y = tile of k — more than one only in wide contexts
+// one (D, logD) pair of exact int64 sums added to bin k of [bins][4] LDS words as its (hi, lo) halves: the inner step of
+// k_blocksums, k_split_eval and the scoring of labellings (score.inc.hip)
+__device__ __forceinline__ void rc_bin_add(u64 *bins, int k, long long d, long long l)
+{
+    const long long mask = ((long long)1 << RC_LO_BITS) - 1;
+    atomicAdd(&bins[k * 4 + 0], (u64)(d >> RC_LO_BITS));
+    atomicAdd(&bins[k * 4 + 1], (u64)(d & mask));
+    atomicAdd(&bins[k * 4 + 2], (u64)(l >> RC_LO_BITS));
+    atomicAdd(&bins[k * 4 + 3], (u64)(l & mask));
+}
 __global__ __launch_bounds__(256) void k_blocksums(View V, int gen, int hi, long long *out)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -4710,15 +4720,10 @@ __global__ __launch_bounds__(256) void k_blocksums(View V, int gen, int hi, long
     if (V.slot_size[t] == 0) return;
     for (int q = threadIdx.x; q < kn * 4; q += blockDim.x) bins[q] = 0;
     __syncthreads();
-    const long long mask = ((long long)1 << RC_LO_BITS) - 1;
     for (int i = threadIdx.x; i < V.n; i += blockDim.x) {
         const int k = V.slot_of[i] - k0;
         if (k < 0 || k >= kn) continue;
-        const long long d = V.SD[gen][(size_t)t * V.ld + i], l = V.SL[gen][(size_t)t * V.ld + i];
-        atomicAdd(&bins[k * 4 + 0], (u64)(d >> RC_LO_BITS));
-        atomicAdd(&bins[k * 4 + 1], (u64)(d & mask));
-        atomicAdd(&bins[k * 4 + 2], (u64)(l >> RC_LO_BITS));
-        atomicAdd(&bins[k * 4 + 3], (u64)(l & mask));
+        rc_bin_add(bins, k, V.SD[gen][(size_t)t * V.ld + i], V.SL[gen][(size_t)t * V.ld + i]);
     }
     __syncthreads();
     for (int q = threadIdx.x; q < kn * 4; q += blockDim.x) out[((size_t)t * hi + k0) * 4 + q] = (long long)bins[q];
@@ -4736,16 +4741,11 @@ __global__ __launch_bounds__(256) void k_split_eval(View V, const unsigned short
     for (int q = threadIdx.x; q < nbuckets * 4; q += blockDim.x) bins[q] = 0;
     __syncthreads();
     const int u = rows[blockIdx.x];
-    const long long mask = ((long long)1 << RC_LO_BITS) - 1;
     for (int x = threadIdx.x; x < V.n; x += blockDim.x) {
         const size_t e = (size_t)u * V.ld + x;
         const long long d = (V.bits == 64) ? ((const long long *)V.Dq)[e] : (long long)((const int *)V.Dq)[e];
         const long long l = rc_load_L(V, u, x, d);
-        const int b = bucket[x];
-        atomicAdd(&bins[b * 4 + 0], (u64)(d >> RC_LO_BITS));
-        atomicAdd(&bins[b * 4 + 1], (u64)(d & mask));
-        atomicAdd(&bins[b * 4 + 2], (u64)(l >> RC_LO_BITS));
-        atomicAdd(&bins[b * 4 + 3], (u64)(l & mask));
+        rc_bin_add(bins, bucket[x], d, l);
     }
     __syncthreads();
     for (int q = threadIdx.x; q < nbuckets * 4; q += blockDim.x)
@@ -6660,6 +6660,44 @@ extern "C" int32_t rc_get_state(rc_ctx *c, int64_t *clusts, int64_t *clustsizes,
     return RC_OK;
 }
 
+// The per-term arithmetic of loglik (mcmc.jl:26-54), shared by loglik_host_c below — rc_loglik and the chain loop — and by the
+// scoring entries of score.inc.hip: the constants of one parameter set, a block sum as a long double, and the term of one
+// cluster (within) or one pair of clusters (between) from its pair count, its memoisable lgamma difference and its block.
+struct LLConsts { long double d1, d2, al, be, ze, ga, lga, lgz, lgd1, lgd2, lb, lg, scD, scL; };
+static LLConsts ll_consts(const rc_params &P, int eD, int eL)
+{
+    LLConsts C;
+    C.d1 = P.delta1; C.d2 = P.delta2; C.al = P.alpha; C.be = P.beta; C.ze = P.zeta; C.ga = P.gamma;
+    C.lga = lgammal(C.al); C.lgz = lgammal(C.ze); C.lgd1 = lgammal(C.d1); C.lgd2 = lgammal(C.d2);
+    C.lb = logl(C.be); C.lg = logl(C.ga);
+    C.scD = ldexpl(1.0L, -eD); C.scL = ldexpl(1.0L, -eL);
+    return C;
+}
+static inline long double ll_block(const LLConsts &C, const long long *e, int which)
+{
+    return ((long double)e[which ? 2 : 0] * (long double)(1ll << RC_LO_BITS) + (long double)e[which ? 3 : 1]) * (which ? C.scL : C.scD);
+}
+static inline long double ll_within_pairs(int size)
+{
+    const long double sz = size;
+    return sz * (sz - 1) / 2;  // binomial(sz_k, 2)
+}
+static inline long double ll_within_lg(const LLConsts &C, long double pairs) { return lgammal(C.al + C.d1 * pairs) - C.lga; }
+static inline long double ll_within_term(const LLConsts &C, long double pairs, long double lgdiff, const long long *e)
+{
+    const long double a = C.al + C.d1 * pairs;
+    const long double bd = ll_block(C, e, 0) / 2, bl = ll_block(C, e, 1) / 2;
+    return (C.d1 - 1) * bl - pairs * C.lgd1 + lgdiff - C.d1 * pairs * C.lb - a * log1pl(bd / C.be);
+}
+static inline long double ll_between_pairs(int sk, int st) { return (long double)sk * (long double)st; }
+static inline long double ll_between_lg(const LLConsts &C, long double pairs) { return lgammal(C.ze + C.d2 * pairs) - C.lgz; }
+static inline long double ll_between_term(const LLConsts &C, long double pairs, long double lgdiff, const long long *e)
+{
+    const long double z = C.ze + C.d2 * pairs;
+    const long double bd = ll_block(C, e, 0), bl = ll_block(C, e, 1);
+    return (C.d2 - 1) * bl - pairs * C.lgd2 + lgdiff - C.d2 * pairs * C.lg - z * log1pl(bd / C.ga);
+}
+
 // Scalar part of loglik (mcmc.jl:26-54) in long double, regrouped as in the oracle's "stable" mode, from the exact
 // fixed-point block sums B[t][k] (hi × hi × 4: D hi/lo, logD hi/lo) and the slot sizes.  A term depends only on its
 // two cluster sizes and its block sums, and most of them do not change from one recorded sample to the next, so the
@@ -6672,10 +6710,7 @@ extern "C" int32_t rc_get_state(rc_ctx *c, int64_t *clusts, int64_t *clustsizes,
 static double loglik_host_c(const rc_ctx *c, rc_ctx::LLCache &cache, int hi, const int *ssize, const long long *B, const int *slabel)
 {
     const rc_params &P = c->P;
-    const long double d1 = P.delta1, d2 = P.delta2, al = P.alpha, be = P.beta, ze = P.zeta, ga = P.gamma;
-    const long double lga = lgammal(al), lgz = lgammal(ze), lgd1 = lgammal(d1), lgd2 = lgammal(d2);
-    const long double lb = logl(be), lg = logl(ga);
-    const long double scD = ldexpl(1.0L, -c->eD), scL = ldexpl(1.0L, -c->eL);
+    const LLConsts C = ll_consts(P, c->eD, c->eL);
     // (the per-pair memo is 64 B per slot pair: kept up to the fast path's capacity; a wide context evaluates every term afresh)
     const bool memo = hi <= RC_MAX_KCAP;
     if (memo && hi > cache.ll_dim) {
@@ -6683,9 +6718,6 @@ static double loglik_host_c(const rc_ctx *c, rc_ctx::LLCache &cache, int hi, con
         cache.ll_cache.assign((size_t)cache.ll_dim * cache.ll_dim, rc_ctx::LLTerm{});
     }
     rc_ctx::LLTerm scratch_term;
-    auto blk = [&](const long long *e, int which) -> long double {
-        return ((long double)e[which ? 2 : 0] * (long double)(1ll << RC_LO_BITS) + (long double)e[which ? 3 : 1]) * (which ? scL : scD);
-    };
     std::vector<int> act;
     for (int k = 0; k < hi; ++k)
         if (ssize[k] > 0) act.push_back(k);
@@ -6696,14 +6728,11 @@ static double loglik_host_c(const rc_ctx *c, rc_ctx::LLCache &cache, int hi, con
         if (!memo) scratch_term = rc_ctx::LLTerm{};
         rc_ctx::LLTerm &T = memo ? cache.ll_cache[(size_t)k * cache.ll_dim + k] : scratch_term;
         if (!(T.sk == ssize[k] && T.e[0] == e[0] && T.e[1] == e[1] && T.e[2] == e[2] && T.e[3] == e[3])) {
-            const long double sz = ssize[k];
-            const long double pairs = sz * (sz - 1) / 2;  // binomial(sz_k, 2)
-            const long double a = al + d1 * pairs;
-            const long double bd = blk(e, 0) / 2, bl = blk(e, 1) / 2;
+            const long double pairs = ll_within_pairs(ssize[k]);
             const long long pk = (long long)pairs;
             auto it = cache.lg_memo1.find(pk);
-            if (it == cache.lg_memo1.end()) it = cache.lg_memo1.emplace(pk, lgammal(a) - lga).first;
-            T.term = (d1 - 1) * bl - pairs * lgd1 + it->second - d1 * pairs * lb - a * log1pl(bd / be);
+            if (it == cache.lg_memo1.end()) it = cache.lg_memo1.emplace(pk, ll_within_lg(C, pairs)).first;
+            T.term = ll_within_term(C, pairs, it->second, e);
             T.sk = ssize[k]; T.st = ssize[k];
             std::memcpy(T.e, e, sizeof(T.e));
         }
@@ -6719,13 +6748,11 @@ static double loglik_host_c(const rc_ctx *c, rc_ctx::LLCache &cache, int hi, con
                 if (!memo) scratch_term = rc_ctx::LLTerm{};
                 rc_ctx::LLTerm &T = memo ? cache.ll_cache[(size_t)t * cache.ll_dim + k] : scratch_term;
                 if (!(T.sk == ssize[k] && T.st == ssize[t] && T.e[0] == e[0] && T.e[1] == e[1] && T.e[2] == e[2] && T.e[3] == e[3])) {
-                    const long double pairs = (long double)ssize[k] * (long double)ssize[t];
-                    const long double z = ze + d2 * pairs;
-                    const long double bd = blk(e, 0), bl = blk(e, 1);
+                    const long double pairs = ll_between_pairs(ssize[k], ssize[t]);
                     const long long pk = (long long)pairs;
                     auto it = cache.lg_memo2.find(pk);
-                    if (it == cache.lg_memo2.end()) it = cache.lg_memo2.emplace(pk, lgammal(z) - lgz).first;
-                    T.term = (d2 - 1) * bl - pairs * lgd2 + it->second - d2 * pairs * lg - z * log1pl(bd / ga);
+                    if (it == cache.lg_memo2.end()) it = cache.lg_memo2.emplace(pk, ll_between_lg(C, pairs)).first;
+                    T.term = ll_between_term(C, pairs, it->second, e);
                     T.sk = ssize[k]; T.st = ssize[t];
                     std::memcpy(T.e, e, sizeof(T.e));
                 }
@@ -6873,25 +6900,31 @@ extern "C" int32_t rc_within_between(rc_ctx *c, rc_wb_stats *out)
     return RC_OK;
 }
 
+// The terms of logprior (mcmc.jl:58-78), shared with score.inc.hip: everything but the clusters' own terms, from n, K, r and p;
+// and the term of one cluster of a given size, to be added in ascending label order.
+static double logprior_head(const rc_params &P, double n, double K, double r, double p)
+{
+    // logpdf(Gamma(η, 1/σ), r) + logpdf(Beta(u, v), p)   (mcmc.jl:73)
+    const double lgam = P.eta * std::log(P.sigma) - std::lgamma(P.eta) + (P.eta - 1) * std::log(r) - P.sigma * r;
+    const double lbet = std::lgamma(P.u + P.v) - std::lgamma(P.u) - std::lgamma(P.v) + (P.u - 1) * std::log(p) + (P.v - 1) * std::log(1 - p);
+    return std::lgamma(K + 1) + (n - K) * std::log(p) + (r * K) * std::log(1 - p) - K * std::lgamma(r) + lgam + lbet;
+}
+static inline double logprior_cluster(int size, double r) { return std::log((double)size) + std::lgamma((double)size + r - 1); }
+
 // logprior (mcmc.jl:58-78) from slot sizes / labels
 // (nslots: length of ssize / slabel — the capacity at the time the tables were taken, which the context's may have outgrown since)
 static double logprior_host(const rc_ctx *c, const int *ssize, const int *slabel, double r, double p, int nslots = -1)
 {
-    const rc_params &P = c->P;
-    const double n = c->n;
     if (nslots < 0) nslots = c->kcap;
     double K = 0;
     for (int k = 0; k < nslots; ++k) K += ssize[k] > 0;
-    // logpdf(Gamma(η, 1/σ), r) + logpdf(Beta(u, v), p)   (mcmc.jl:73)
-    const double lgam = P.eta * std::log(P.sigma) - std::lgamma(P.eta) + (P.eta - 1) * std::log(r) - P.sigma * r;
-    const double lbet = std::lgamma(P.u + P.v) - std::lgamma(P.u) - std::lgamma(P.v) + (P.u - 1) * std::log(p) + (P.v - 1) * std::log(1 - p);
-    double L = std::lgamma(K + 1) + (n - K) * std::log(p) + (r * K) * std::log(1 - p) - K * std::lgamma(r) + lgam + lbet;
+    double L = logprior_head(c->P, (double)c->n, K, r, p);
     // Σ_j log n_j + lgΓ(n_j + r − 1) over non-empty clusters in ascending label order (mcmc.jl:74-76)
     std::vector<std::pair<int, int>> bylabel;
     for (int k = 0; k < nslots; ++k)
         if (ssize[k] > 0) bylabel.push_back({slabel[k], ssize[k]});
     std::sort(bylabel.begin(), bylabel.end());
-    for (auto &e : bylabel) L += std::log((double)e.second) + std::lgamma((double)e.second + r - 1);
+    for (auto &e : bylabel) L += logprior_cluster(e.second, r);
     return L;
 }
 
@@ -7853,3 +7886,4 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "predict.inc.hip"
 #include "partdist.inc.hip"
 #include "relabel.inc.hip"
+#include "score.inc.hip"

@@ -360,7 +360,7 @@ def hclust(samples_or_counts=None, linkage="average", *, numsamples=None, ctx=No
 
 
 def hclustpointestimate(samples_or_counts=None, loss="VI", linkage="average", *, maxK: int = 0, numsamples=None, ctx=None,
-                        device: int = 0, exact: bool = False):
+                        device: int = 0, exact: bool = False, criterion: str = "loss", data=None, params=None, r=None, p=None):
     """The hierarchical point estimate: hclust's dendrogram cut at the number of clusters K in 1..maxK of minimum expected
     loss (ties: the smaller K).  loss: "binder" — from the exact curve binder_num — or "VI", the lower bound expectedloss(…,
     "VI") evaluates, computed for every cut on the device.  maxK = 0 means ⌈n/8⌉.  Returns (clust, info): the cut
@@ -370,7 +370,38 @@ def hclustpointestimate(samples_or_counts=None, loss="VI", linkage="average", *,
     exact=True (samples only: an MCMCResult or anything with `.clusts`): the cut is chosen by the exact posterior expected
     loss of every cut — expecteddistances on the maxK cuts, one call of rc_partition_distances — instead of the VI's lower
     bound; loss may then also be "ID".  info["loss"] and info["loss_num"] (per K; Python integers) are the exact expected
-    loss and its integer numerator, and the choice is exact in loss_num."""
+    loss and its integer numerator, and the choice is exact in loss_num.
+
+    criterion="posterior": the cut of highest log-posterior under the model instead of lowest expected loss — mapestimate
+    (score.py) over the maxK cuts, one device pass over the matrices of data (a Context, an MCMCData or a dissimilarity
+    matrix) with params and r, p (scalars or one per cut; None: the posterior means of an MCMCResult's r and p).  info has K,
+    loglik, logprior, logposterior (per K = 1..maxK), merges, binder_num, kernel_ms, score_ms."""
+    if criterion not in ("loss", "posterior"):
+        raise ValueError("criterion must be 'loss' or 'posterior'")
+    if criterion == "posterior":
+        from .score import mapestimate
+        if exact:
+            raise ValueError("exact=True chooses by expected loss; it does not go with criterion='posterior'")
+        if linkage not in _LINKAGES:
+            raise ValueError("Invalid linkage specifier.")
+        if data is None:
+            raise ValueError("criterion='posterior' needs data= (a Context, an MCMCData or a dissimilarity matrix)")
+        if r is None and p is None and hasattr(samples_or_counts, "r"):
+            r, p = float(np.mean(samples_or_counts.r)), float(np.mean(samples_or_counts.p))
+        if params is None and not isinstance(data, _lib.Context):
+            params = getattr(samples_or_counts, "params", None)
+        if r is None or p is None:
+            raise ValueError("criterion='posterior' needs r and p")
+        S, counts, m, n = _counts_input(samples_or_counts, numsamples, ctx)
+        maxK = int(maxK) if maxK else -(-n // 8)
+        if not 1 <= maxK <= n:
+            raise ValueError("maxK must lie in 1..n")
+        res = _lib.hclust(counts, m, _LINKAGES[linkage], device=device, ctx=ctx, samples=S)
+        cuts = np.stack([_lib.hclust_cut(res["merges"], n, K) for K in range(1, maxK + 1)])
+        clust, sc = mapestimate(data, cuts, params, r, p, device=device)
+        info = dict(merges=res["merges"], binder_num=res["binder_num"], kernel_ms=res["kernel_ms"], score_ms=sc["kernel_ms"],
+                    loglik=sc["loglik"], logprior=sc["logprior"], logposterior=sc["logposterior"], K=sc["index"] + 1)
+        return clust, info
     if exact:
         if loss not in _DIST_LOSSES:
             raise ValueError("Invalid loss function specifier.")

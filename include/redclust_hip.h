@@ -190,8 +190,9 @@ int32_t rc_event_overhead_ms(rc_ctx *ctx, double *out);
 /* Which row-reduction kernel the last enqueued sweep used — *which = 0: k_bulk (reads every entry of D and logD, any point
  * order), 1: one of the symmetric kernels (upper triangle only; chosen automatically when the points of a cluster are
  * contiguous in the internal point order, override with rc_set_bulk_kernel or RC_BULK_KERNEL=perm|sym|auto).  Which symmetric
- * kernel that is depends on the storage: k_bulk_syml2 (64-bit storage, the default: wave-autonomous units; with logD derived
- * it streams the 48-bit packed copy of D), k_bulk_sym (64-bit, logD stored: block-tiled), k_bulk_sym32 (32-bit storage) —
+ * kernel that is depends on the storage (and, for measurements, on RC_SYM_VARIANT): k_bulk_syml2 (64-bit storage with logD
+ * derived, the default: wave-autonomous units, streams the 48-bit packed copy of D), k_bulk_sym (64-bit, logD stored:
+ * block-tiled), k_bulk_sym32 (32-bit storage) —
  * rc_bulk_kernel_name says which.  *algorithmic_bytes = the matrix bytes that kernel has to read per launch (what bench.py's
  * roofline prices): every entry of the matrices it reads for k_bulk, the upper triangle incl. diagonal for the symmetric
  * ones, at 6 bytes per entry for the packed copy. */

@@ -4818,6 +4818,10 @@ __global__ void k_nop() {}
 // ===================================================================================================
 // Host side
 // ===================================================================================================
+// One set of k_bulk_syml2's unit lists on the device (build_syml2_lists) and the grid that reads it: every resident wave has its
+// (possibly empty) share, so `blocks` is the number of resident 4-wave blocks the lists were dealt to; g: rows per fast unit.
+struct S2Lists { int4 *ufast = nullptr, *uslow = nullptr; int *wfast = nullptr, *wslow = nullptr; int nfast = 0, nslow = 0, blocks = 0, g = 0; };
+
 struct rc_ctx {
     int dev = 0;
     int n = 0, ld = 0, kcap = 0;
@@ -4837,16 +4841,15 @@ struct rc_ctx {
     int *pi = nullptr, *ipi = nullptr;  // device: original -> internal, internal -> original
     std::vector<int> h_pi, h_ipi;       // host copies
     bool relayout = true;               // RC_NO_RELAYOUT=1 keeps the caller's point order
-    int sym_variant = -1;               // RC_SYM_VARIANT: 2 k_bulk_syml (wave-private LDS transposition), 1 k_bulk_symw (DPP only), 0 block-tiled
-                                        // k_bulk_sym; -1 (default): k_bulk_syml when logD is derived, k_bulk_sym when it is stored (measured best)
+    int sym_variant = -1;               // RC_SYM_VARIANT: 3 k_bulk_syml2 (host-built unit lists), 2 k_bulk_syml (wave-private LDS transposition),
+                                        // 1 k_bulk_symw (DPP only), 0 block-tiled k_bulk_sym; -1 (default): k_bulk_syml2 when logD is derived,
+                                        // k_bulk_sym when it is stored (measured best).  32-bit storage: 2 k_bulk_syml32, else k_bulk_sym32 (bulk_choice)
     int sw_coarse = 0;                   // RC_SW_COARSE: rows per unit of k_bulk_syml (8..128, multiple of 4); 0 = chosen by syml_geometry
     size_t syml_pad = 0;                // RC_SYML_PAD: unused dynamic LDS per k_bulk_syml block (bytes), caps the blocks per CU
     int symw_per_cu = 3;                // RC_SYMW_PER_CU: blocks of k_bulk_syml / k_bulk_symw per CU (LDS: 40 KiB per block; the fourth slot is the resolver's)
-    int4 *ufast = nullptr, *uslow = nullptr;   // unit lists of k_bulk_syml2 (build_syml2_lists)
-    int *wfast = nullptr, *wslow = nullptr;
-    int nfast = 0, nslow = 0, syml2_blocks = 0, syml2_g = 0;
-    // the same lists for two blocks per CU: used while labels move (the 512-thread resolver of the previous sweep then fits beside the reduction)
-    struct S2Alt { int4 *ufast = nullptr, *uslow = nullptr; int *wfast = nullptr, *wslow = nullptr; int nfast = 0, nslow = 0, blocks = 0; } s2alt;
+    // unit lists of k_bulk_syml2 (64-bit contexts): [0] for symw_per_cu blocks per CU; [1] for two blocks per CU, used while labels
+    // move (the 512-thread resolver of the previous sweep then fits beside the reduction; empty: [0] is used throughout)
+    S2Lists s2[2];
     bool derived = false;               // logD derived from Dq on the fly (rc_qlog), not stored
     double2 *ltab = nullptr;            // device table of rc_qlog
     double *vtab = nullptr;             // device table of rc_qlog with the exponent folded in (k_fold_table; View.vtab)
@@ -4862,8 +4865,8 @@ struct rc_ctx {
     int *lsnap[2] = {nullptr, nullptr}, *work[2] = {nullptr, nullptr};  // label snapshots / work counters of k_bulk_sym
     u64 *cword[2] = {nullptr, nullptr};
     unsigned *rec = nullptr;
-    int bulk_kernel = -1;      // RC_BULK_KERNEL: -1 auto, 0 k_bulk (full read, any layout), 1 k_bulk_sym (upper triangle)
-    int last_bulk_kernel = 0;  // what the last enqueue chose
+    int bulk_kernel = -1;      // RC_BULK_KERNEL: -1 auto, 0 k_bulk (full read, any layout), 1 the context's symmetric kernel (upper triangle; bulk_choice)
+    int last_bulk_kernel = 0;  // BulkId of the last enqueue_bulk; 0 (BK_NONE): nothing enqueued yet
     int sym_item_tiles = 8;
     long long relayout_gap = 128;    // sweeps between two automatic re-layouts while K is between n/64 and n/36 (sweep_enqueue)
     int sym32_tr = 16;               // rows per tile of k_bulk_sym32 (16: 34 KiB blocks, 32: 67 KiB blocks)
@@ -4992,6 +4995,14 @@ static int32_t fail(rc_ctx *c, int32_t code, const char *fmt, ...)
                         hipGetErrorString(e_), __FILE__, __LINE__);                                   \
     } while (0)
 
+static void view_lists(View &V, const S2Lists &L) { V.ufast = L.ufast; V.uslow = L.uslow; V.nfast = L.nfast; V.nslow = L.nslow; V.wfast = L.wfast; V.wslow = L.wslow; }
+static void free_lists(S2Lists &L)
+{
+    for (void *p : {(void *)L.ufast, (void *)L.uslow, (void *)L.wfast, (void *)L.wslow})
+        if (p) (void)hipFree(p);
+    L = S2Lists{};
+}
+
 static View make_view(const rc_ctx *c)
 {
     View V{};
@@ -5005,7 +5016,7 @@ static View make_view(const rc_ctx *c)
     V.slot_of = c->slot_of; V.slot_size = c->slot_size; V.slot_label = c->slot_label;
     V.slot_pos = c->slot_pos; V.slot_act = c->slot_act;
     V.A = c->A; V.sc = c->sc; V.hsum = c->hsum_dev;
-    V.ufast = c->ufast; V.uslow = c->uslow; V.nfast = c->nfast; V.nslow = c->nslow; V.wfast = c->wfast; V.wslow = c->wslow;
+    view_lists(V, c->s2[0]);
     V.scD = std::ldexp(1.0, -c->eD); V.scL = std::ldexp(1.0, -c->eL);
     V.alpha = c->P.alpha; V.beta = c->P.beta; V.zeta = c->P.zeta; V.gamma = c->P.gamma;
     V.delta1 = c->P.delta1; V.delta2 = c->P.delta2;
@@ -5078,9 +5089,10 @@ static void free_all(rc_ctx *c)
     void *ptrs[] = {c->pts, c->ptsT, c->Dq48, c->ltab, c->vtab, c->flt, c->Dq, c->Lq, c->Dq_src, c->Lq_src, c->diag_src, c->pi, c->ipi, c->diagq, c->SD[0], c->SD[1], c->SD[2], c->SL[0], c->SL[1], c->SL[2], c->slot_of,
                     c->slot_size, c->slot_label, c->slot_pos, c->slot_act, c->perm[0], c->perm[1], c->pslot[0],
                     c->pslot[1], c->lsnap[0], c->lsnap[1], c->work[0], c->work[1], c->cword[0], c->cword[1], c->rec, c->A, c->keys[0], c->keys[1], c->arrive[0], c->arrive[1], c->sc, c->blocks,
-                    c->counts, c->cc_out, c->snap, c->d_moves, c->used_scratch, c->wide_scratch, c->wc, c->ufast, c->uslow, c->wfast, c->wslow, c->s2alt.ufast, c->s2alt.uslow, c->s2alt.wfast, c->s2alt.wslow};
+                    c->counts, c->cc_out, c->snap, c->d_moves, c->used_scratch, c->wide_scratch, c->wc};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    for (S2Lists &L : c->s2) free_lists(L);
     if (c->hsum) (void)hipHostFree(c->hsum);
     for (int q = 0; q < RC_REC_SLOTS; ++q) {
         if (c->pinB[q]) (void)hipHostFree(c->pinB[q]);
@@ -5546,152 +5558,49 @@ static int32_t alloc_ctx(int64_t n, int32_t storage_bits, int32_t device_id, int
     return RC_OK;
 }
 
-// Symmetric-kernel variant of a context: RC_SYM_VARIANT, else the wave-autonomous kernel when logD is derived and the block-tiled
-// ones when it is stored.
-static int sym_variant_of(const rc_ctx *c) { return c->sym_variant >= 0 ? c->sym_variant : (c->derived ? 3 : 0); }
-// the wave-autonomous kernels (three 40-42 KiB blocks per CU) are the symmetric kernel of this context: 3 = k_bulk_syml2 (round 3),
-// 2 = k_bulk_syml (round 2)
-static bool uses_syml(const rc_ctx *c) { return sym_variant_of(c) >= 2; }
-// k_bulk_syml2 reads the log table with the exponent folded in (rc_qlog_prep_f); otherwise a derived context runs k_bulk_syml2w
-static bool syml2_folds(const rc_ctx *c) { return c->derived && c->fold_ok && c->opt_fold != 0; }
+static bool uses_syml(const rc_ctx *c);   // (with the kernel choice, ahead of enqueue_bulk)
 
-// Unit lists of k_bulk_syml2 for `cap_blocks` resident 4-wave blocks.  Column block J (128 columns) holds the rows 0 .. 128 J + 127
-// of the upper triangle.  Rows [0, 128 J) lie entirely above the diagonal block: FAST units of g rows (a multiple of 8; the rest of a
-// block is a shorter unit) — no mask of any kind in their tiles.  The diagonal block itself (and every unit of a ragged last column
-// block) is SLOW: the round-2 unit code with its triangle masks, ~3x the cost per 4-row tile, so it is cut fine (RC_S2_SLOW_ROWS
-// rows per unit).  The launch lasts as long as its slowest wave, so the units are dealt to the waves by cost — longest first, each
-// to the least loaded wave — and a wave reads its share as a contiguous range of each list.  g is chosen for the shortest makespan.
-#ifndef RC_S2_SLOW_ROWS
-#define RC_S2_SLOW_ROWS 16
-#endif
-static int32_t build_syml2_lists(rc_ctx *c, int per_cu = 0)
+#include "s2plan.inc.hpp"
+static_assert(S2_COLS == RC_SW_COLS && sizeof(S2Unit) == sizeof(int4), "s2plan.inc.hpp plans for the kernels' column blocks and unit type");
+
+// Unit lists of k_bulk_syml2 for per_cu resident 4-wave blocks per CU (s2_plan), on the device.  *out is assigned only once every
+// allocation and copy has succeeded; what it held before is freed then.
+static int32_t build_syml2_lists(rc_ctx *c, int per_cu, S2Lists *out)
 {
-    const int n = c->n, ncb = (n + RC_SW_COLS - 1) / RC_SW_COLS, cap_blocks = (per_cu > 0 ? per_cu : c->symw_per_cu) * c->num_cus, nwaves = 4 * cap_blocks;
-    struct Unit { int4 u; int cost; bool fast; };
+    const int cap_blocks = per_cu * c->num_cus;
     const int slow_factor = rc_env_diag("RC_S2_SLOW_COST") ? std::max(1, atoi(rc_env_diag("RC_S2_SLOW_COST"))) : 3;
-    auto make_units = [&](int g, std::vector<Unit> &out) {
-        out.clear();
-        for (int J = ncb - 1; J >= 0; --J) {
-            const int c0 = J * RC_SW_COLS, rows = std::min(c0 + RC_SW_COLS, n);
-            const int fast_rows = rows & ~7;                             // (diagonal block and padding columns included: the fast path masks them)
-            for (int a0 = 0; a0 < fast_rows; a0 += g) {
-                const int a1 = std::min(a0 + g, fast_rows);
-                out.push_back({make_int4(c0, a0, a1, 0), (a1 - a0) / 4 + 2, true});
-            }
-            for (int a0 = fast_rows; a0 < rows; a0 += RC_S2_SLOW_ROWS) {
-                const int a1 = std::min(a0 + RC_S2_SLOW_ROWS, rows);
-                out.push_back({make_int4(c0, a0, a1, 0), slow_factor * ((a1 - a0 + 3) / 4) + 3, false});
-            }
-        }
+    const S2Plan p = s2_plan(c->n, cap_blocks, c->sw_coarse, slow_factor);
+    S2Lists L;
+    L.nfast = (int)p.fast.size(); L.nslow = (int)p.slow.size(); L.g = p.g; L.blocks = cap_blocks;   // (every resident wave has its possibly empty share)
+    const auto upload = [](void **dst, const void *src, size_t bytes) {
+        hipError_t e = hipMalloc(dst, std::max<size_t>(16, bytes));
+        if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+        return e;
     };
-    auto schedule = [&](std::vector<Unit> &units, std::vector<int> &owner) -> long long {   // longest first, to the least loaded wave
-        std::vector<int> order(units.size());
-        for (size_t q = 0; q < order.size(); ++q) order[q] = (int)q;
-        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return units[(size_t)x].cost > units[(size_t)y].cost; });
-        std::vector<std::pair<long long, int>> heap;                   // (load, wave), min-heap
-        heap.reserve((size_t)nwaves);
-        for (int w = 0; w < nwaves; ++w) heap.push_back({0, w});
-        auto cmp = [](const std::pair<long long, int> &x, const std::pair<long long, int> &y) { return x > y; };
-        std::make_heap(heap.begin(), heap.end(), cmp);
-        owner.assign(units.size(), 0);
-        long long makespan = 0;
-        for (int q : order) {
-            std::pop_heap(heap.begin(), heap.end(), cmp);
-            auto &top = heap.back();
-            owner[(size_t)q] = top.second;
-            top.first += units[(size_t)q].cost;
-            makespan = std::max(makespan, top.first);
-            std::push_heap(heap.begin(), heap.end(), cmp);
-        }
-        return makespan;
-    };
-    std::vector<Unit> units, best_units;
-    std::vector<int> owner, best_owner;
-    long long best = -1;
-    int best_g = 64;
-    const int g_lo = c->sw_coarse > 0 ? (c->sw_coarse + 7) / 8 * 8 : 16, g_hi = c->sw_coarse > 0 ? g_lo : 256;
-    for (int g = g_lo; g <= g_hi; g += 8) {
-        make_units(g, units);
-        const long long mk = schedule(units, owner);
-        if (best < 0 || mk < best || (mk == best && g > best_g)) { best = mk; best_g = g; best_units = units; best_owner = owner; }
+    hipError_t e = upload((void **)&L.ufast, p.fast.data(), p.fast.size() * sizeof(int4));
+    if (e == hipSuccess) e = upload((void **)&L.uslow, p.slow.data(), p.slow.size() * sizeof(int4));
+    if (e == hipSuccess) e = upload((void **)&L.wfast, p.wfast.data(), p.wfast.size() * sizeof(int));
+    if (e == hipSuccess) e = upload((void **)&L.wslow, p.wslow.data(), p.wslow.size() * sizeof(int));
+    if (e != hipSuccess) {
+        free_lists(L);
+        return fail(c, e == hipErrorOutOfMemory ? RC_ERR_OOM : RC_ERR_HIP, "build_syml2_lists: %s", hipGetErrorString(e));
     }
-    // group by wave (stable: heavy column blocks first inside a wave), fast and slow lists apart
-    std::vector<int4> fast, slow;
-    std::vector<int> wfast((size_t)nwaves + 1, 0), wslow((size_t)nwaves + 1, 0);
-    for (size_t q = 0; q < best_units.size(); ++q) (best_units[q].fast ? wfast : wslow)[(size_t)best_owner[q] + 1]++;
-    for (int w = 0; w < nwaves; ++w) { wfast[(size_t)w + 1] += wfast[(size_t)w]; wslow[(size_t)w + 1] += wslow[(size_t)w]; }
-    fast.resize((size_t)wfast[(size_t)nwaves]); slow.resize((size_t)wslow[(size_t)nwaves]);
-    {
-        std::vector<int> pf(wfast.begin(), wfast.end() - 1), ps(wslow.begin(), wslow.end() - 1);
-        for (size_t q = 0; q < best_units.size(); ++q) {
-            const int w = best_owner[q];
-            if (best_units[q].fast) fast[(size_t)pf[(size_t)w]++] = best_units[q].u; else slow[(size_t)ps[(size_t)w]++] = best_units[q].u;
-        }
-    }
-    // RC_S2_STAGGER=1 (experiment, off): each fast unit cut at a row that differs from wave to wave and taken lower part last, so that
-    // the flushes of a launch spread over its duration instead of coming at the same moments in every wave.  Measured: no gain
-    // (74.9 against 73.5 us) — the ~18 us the atomics cost a launch (55 us without them) are not a drain at its end: 18 MB of 64-bit
-    // atomics at the ~1 TB/s the memory side executes them is a per-CU occupancy of the vector memory path, spread or not.
-    if (rc_env_diag("RC_S2_STAGGER") && atoi(rc_env_diag("RC_S2_STAGGER"))) {
-        std::vector<int4> fast2;
-        std::vector<int> wfast2((size_t)nwaves + 1, 0);
-        fast2.reserve(2 * fast.size());
-        for (int w = 0; w < nwaves; ++w) {
-            wfast2[(size_t)w] = (int)fast2.size();
-            for (int q = wfast[(size_t)w]; q < wfast[(size_t)w + 1]; ++q) {
-                const int4 u = fast[(size_t)q];
-                const int groups = (u.z - u.y) / 8;
-                if (groups < 4) { fast2.push_back(u); continue; }
-                const unsigned h = (unsigned)w * 2654435761u + (unsigned)q * 40503u;
-                const int cut = u.y + 8 * (1 + (int)((h >> 8) % (unsigned)(groups - 1)));
-                fast2.push_back(make_int4(u.x, cut, u.z, 0));
-                fast2.push_back(make_int4(u.x, u.y, cut, 0));
-            }
-        }
-        wfast2[(size_t)nwaves] = (int)fast2.size();
-        fast.swap(fast2); wfast.swap(wfast2);
-    }
-    for (void *pfree : {(void *)c->ufast, (void *)c->uslow, (void *)c->wfast, (void *)c->wslow})
-        if (pfree) (void)hipFree(pfree);
-    c->ufast = c->uslow = nullptr; c->wfast = c->wslow = nullptr;
-    HIPCHK(c, hipMalloc(&c->ufast, std::max<size_t>(1, fast.size()) * sizeof(int4)));
-    HIPCHK(c, hipMalloc(&c->uslow, std::max<size_t>(1, slow.size()) * sizeof(int4)));
-    HIPCHK(c, hipMalloc(&c->wfast, wfast.size() * sizeof(int)));
-    HIPCHK(c, hipMalloc(&c->wslow, wslow.size() * sizeof(int)));
-    if (!fast.empty()) HIPCHK(c, hipMemcpy(c->ufast, fast.data(), fast.size() * sizeof(int4), hipMemcpyHostToDevice));
-    if (!slow.empty()) HIPCHK(c, hipMemcpy(c->uslow, slow.data(), slow.size() * sizeof(int4), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->wfast, wfast.data(), wfast.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->wslow, wslow.data(), wslow.size() * sizeof(int), hipMemcpyHostToDevice));
-    c->nfast = (int)fast.size(); c->nslow = (int)slow.size(); c->syml2_g = best_g;
-    c->syml2_blocks = cap_blocks;      // every resident wave has its (possibly empty) share
+    free_lists(*out);
+    *out = L;
     if (rc_env_diag("RC_SM_PROFILE"))
         fprintf(stderr, "[rc_create] k_bulk_syml2: %d fast units of %d rows, %d slow units of %d rows over %d waves, makespan %lld tile costs\n",
-                c->nfast, best_g, c->nslow, RC_S2_SLOW_ROWS, nwaves, best);
+                L.nfast, L.g, L.nslow, RC_S2_SLOW_ROWS, 4 * cap_blocks, p.makespan);
     return RC_OK;
-}
-
-// The lists for two blocks per CU (moving regime, enqueue_bulk): built by the same routine into the context's primary fields,
-// which are put back afterwards.
-static int32_t build_syml2_alt(rc_ctx *c)
-{
-    if (c->symw_per_cu <= 2 || (rc_env_diag("RC_S2_NO_ALT") && atoi(rc_env_diag("RC_S2_NO_ALT")))) return RC_OK;
-    int4 *uf = c->ufast, *us = c->uslow;
-    int *wf = c->wfast, *ws = c->wslow;
-    const int nf = c->nfast, ns = c->nslow, nb = c->syml2_blocks, g = c->syml2_g;
-    c->ufast = c->uslow = nullptr; c->wfast = c->wslow = nullptr;
-    const int32_t rc = build_syml2_lists(c, rc_env_diag("RC_S2_ALT_PER_CU") ? std::max(1, atoi(rc_env_diag("RC_S2_ALT_PER_CU"))) : 2);
-    c->s2alt.ufast = c->ufast; c->s2alt.uslow = c->uslow; c->s2alt.wfast = c->wfast; c->s2alt.wslow = c->wslow;
-    c->s2alt.nfast = c->nfast; c->s2alt.nslow = c->nslow; c->s2alt.blocks = c->syml2_blocks;
-    c->ufast = uf; c->uslow = us; c->wfast = wf; c->wslow = ws; c->nfast = nf; c->nslow = ns; c->syml2_blocks = nb; c->syml2_g = g;
-    return rc;
 }
 
 // launch geometry and LDS attributes that depend on (n, kcap, bits)
 static int32_t finish_create(rc_ctx *c)
 {
-    if (c->bits == 64 && !c->ufast) {
-        int32_t rcl = build_syml2_lists(c);
-        if (rcl == RC_OK) rcl = build_syml2_alt(c);
+    if (c->bits == 64 && !c->s2[0].ufast) {
+        int32_t rcl = build_syml2_lists(c, c->symw_per_cu, &c->s2[0]);
+        // the lists for two blocks per CU (moving regime, enqueue_bulk)
+        if (rcl == RC_OK && c->symw_per_cu > 2 && !(rc_env_diag("RC_S2_NO_ALT") && atoi(rc_env_diag("RC_S2_NO_ALT"))))
+            rcl = build_syml2_lists(c, rc_env_diag("RC_S2_ALT_PER_CU") ? std::max(1, atoi(rc_env_diag("RC_S2_ALT_PER_CU"))) : 2, &c->s2[1]);
         if (rcl != RC_OK) return rcl;
     }
     if (!c->registered) { res_register(c); c->registered = true; }
@@ -5711,6 +5620,7 @@ static int32_t finish_create(rc_ctx *c)
         // reduction — config 5: 1.34 ms per resolver instead of 0.3).  LDS beside the reduction: three 40 KiB blocks of the
         // wave-autonomous kernel (64-bit, logD derived), two 65 KiB blocks of the block-tiled kernels otherwise; the
         // full-read kernel of small problems sizes itself around the resolver.  Largest capacity whose tables fit.
+        // (Not bulk_choice's answer: 32-bit with RC_SYM_VARIANT=3 is sized for 40 KiB blocks although k_bulk_sym32 runs; fixing it changes maxb.)
         const bool syml = uses_syml(c);
         const size_t beside = syml ? (size_t)c->symw_per_cu * 40960 : (c->bits != 64 && c->sym32_tr == 16) ? (size_t)c->sym32_bpc * 36864 : (size_t)2 * 69632;   // (k_bulk_sym32: 67,864 B per block, k_bulk_sym: 67,288 B; measured: beside two of them 24.6 KB of tables become resident, 26.5 KB do not — 4 KiB allocation granules)
         const size_t avail = 160 * 1024 > beside + 1024 ? 160 * 1024 - beside - 1024 : 0;
@@ -6113,28 +6023,6 @@ extern "C" int32_t rc_set_state(rc_ctx *c, const int64_t *clusts)
                 return la != lb ? lb : clusts[a] < clusts[b];
             });
         }
-        // Every cluster's run gets an EVEN length and hence an even start: the last point of each odd-sized cluster goes to the
-        // tail of the order.  The row reduction gives a lane two adjacent columns (2 l, 2 l + 1); a cluster boundary at an odd
-        // position splits a lane between two clusters, and such a lane's elements cannot go through the pre-added direction-2
-        // path (k_bulk_syml2: element-wise atomics for every row of every unit of that column block — a third of all units with
-        // boundaries at arbitrary positions).  The tail — one point per odd-sized cluster, every singleton — is ragged, but it is
-        // a column block or two.  Exactness does not depend on any of this.
-        // (Kept as an experiment, RC_EVEN_RUNS=1: the ragged tail it creates costs more than it saves once the boundary lanes are
-        // handled inside the kernel — k_bulk_syml2's donor lanes.)
-        if (uses_syml(c) && rc_env_diag("RC_EVEN_RUNS") && atoi(rc_env_diag("RC_EVEN_RUNS"))) {
-            std::vector<int> body, tail;
-            body.reserve((size_t)n);
-            for (int w = 0; w < n;) {
-                int e = w;
-                while (e < n && clusts[ipi[(size_t)e]] == clusts[ipi[(size_t)w]]) ++e;
-                const int keep = (e - w) & ~1;
-                for (int q = w; q < w + keep; ++q) body.push_back(ipi[(size_t)q]);
-                if (keep < e - w) tail.push_back(ipi[(size_t)e - 1]);
-                w = e;
-            }
-            body.insert(body.end(), tail.begin(), tail.end());
-            ipi.swap(body);
-        }
     }
     for (int w = 0; w < n; ++w) pi[(size_t)ipi[(size_t)w]] = w;
     if (pi != c->h_pi) {
@@ -6194,7 +6082,37 @@ extern "C" int32_t rc_set_state(rc_ctx *c, const int64_t *clusts)
     return RC_OK;
 }
 
-// Kernel choice.  The symmetric kernels read half the bytes but want the points of a cluster to be contiguous in the
+// The row reduction of a sweep: which kernel (bulk_choice), its launch (enqueue_bulk) and what the library reports about it.
+// Every form enqueue_bulk can launch is one row of BULK_KERNELS; tests/bulk_rows.py lists the ones a product build reaches.
+enum BulkId : int {
+    BK_NONE = 0,                                    // no sweep enqueued yet: reported as the full-read kernel of the storage
+    BK_FULL_DERIVED, BK_FULL_STORED, BK_FULL_32,    // k_bulk: every entry, any point order
+    BK_SYM_DERIVED, BK_SYM_STORED, BK_SYM32,        // block-tiled, upper triangle (RC_SYM_VARIANT=0; 32-bit: every variant but 2)
+    BK_SYMW_DERIVED, BK_SYMW_STORED, BK_SYML_DERIVED, BK_SYML_STORED, BK_SYML32,   // RC_SYM_VARIANT=1 / 2
+    BK_SYML2_PACK, BK_SYML2_DERIVED, BK_SYML2_STORED,   // RC_SYM_VARIANT=3, the default of a derived context: folded log table
+    BK_SYML2W_PACK, BK_SYML2W_DERIVED, BK_COUNT     // ... the exponent derived per entry (k_bulk_syml2w, reported under k_bulk_syml2's names)
+};
+struct BulkKernel { const char *name; int sym, entry_bytes, matrices; };   // name as a profiler shows it; 1: upper triangle only; bytes per entry read; D alone or D and logD
+static const BulkKernel BULK_KERNELS[BK_COUNT] = {
+    {"", 0, 0, 0},
+    {"k_bulk<long long, true>", 0, 8, 1}, {"k_bulk<long long, false>", 0, 8, 2}, {"k_bulk<int, false>", 0, 4, 2},
+    {"k_bulk_sym<true>", 1, 8, 1}, {"k_bulk_sym<false>", 1, 8, 2}, {"k_bulk_sym32", 1, 4, 2},
+    {"k_bulk_symw<true>", 1, 8, 1}, {"k_bulk_symw<false>", 1, 8, 2},
+    {"k_bulk_syml<true>", 1, 8, 1}, {"k_bulk_syml<false>", 1, 8, 2}, {"k_bulk_syml32", 1, 4, 2},
+    {"k_bulk_syml2<true, true>", 1, 6, 1}, {"k_bulk_syml2<true, false>", 1, 8, 1}, {"k_bulk_syml2<false, false>", 1, 8, 2},   // (PACK: the 48-bit packed copy)
+    {"k_bulk_syml2<true, true>", 1, 6, 1}, {"k_bulk_syml2<true, false>", 1, 8, 1},
+};
+
+// Symmetric-kernel variant of a context: RC_SYM_VARIANT, else the wave-autonomous kernel when logD is derived and the block-tiled
+// ones when it is stored.
+static int sym_variant_of(const rc_ctx *c) { return c->sym_variant >= 0 ? c->sym_variant : (c->derived ? 3 : 0); }
+// the wave-autonomous kernels (three 40-42 KiB blocks per CU) are the symmetric kernel of this context: 3 = k_bulk_syml2 (round 3),
+// 2 = k_bulk_syml (round 2)
+static bool uses_syml(const rc_ctx *c) { return sym_variant_of(c) >= 2; }
+// k_bulk_syml2 reads the log table with the exponent folded in (rc_qlog_prep_f); otherwise a derived context runs k_bulk_syml2w
+static bool syml2_folds(const rc_ctx *c) { return c->derived && c->fold_ok && c->opt_fold != 0; }
+
+// Symmetric or full read.  The symmetric kernels read half the bytes but want the points of a cluster to be contiguous in the
 // point order (few label runs); every kernel is exact for any labelling, so a stale run count only costs speed.
 // Small problems are launch- and latency-bound: with separate launches the full-read kernel (one pass, no per-unit
 // prologue) wins up to n = 4096 even though it reads and — in the derived mode — computes twice as much (measured:
@@ -6227,6 +6145,23 @@ static void syml_geometry(const rc_ctx *c, int cap_blocks, int *gc_out, int *nit
     *gc_out = best_g; *nitems_out = best_items;
 }
 
+// The kernel of the next launch: the one place that decides it.  (Dq48 is null only where a diagnostic build asked for no packed copy.)
+static BulkId bulk_full(const rc_ctx *c) { return c->bits != 64 ? BK_FULL_32 : (c->derived ? BK_FULL_DERIVED : BK_FULL_STORED); }
+static BulkId bulk_choice(const rc_ctx *c)
+{
+    if (!choose_sym(c)) return bulk_full(c);
+    const int v = sym_variant_of(c);
+    if (c->bits != 64) return v == 2 ? BK_SYML32 : BK_SYM32;
+    if (v == 3 && !c->derived) return BK_SYML2_STORED;
+    if (v == 3 && !syml2_folds(c)) return c->Dq48 ? BK_SYML2W_PACK : BK_SYML2W_DERIVED;   // entries over more than four binades (or rc_set_option "fold_log_table" 0)
+    if (v == 3) return c->Dq48 ? BK_SYML2_PACK : BK_SYML2_DERIVED;
+    if (v == 2) return c->derived ? BK_SYML_DERIVED : BK_SYML_STORED;
+    if (v == 1) return c->derived ? BK_SYMW_DERIVED : BK_SYMW_STORED;
+    return c->derived ? BK_SYM_DERIVED : BK_SYM_STORED;
+}
+// what the last launch ran, for the reports
+static const BulkKernel &last_bulk(const rc_ctx *c) { return BULK_KERNELS[c->last_bulk_kernel ? c->last_bulk_kernel : bulk_full(c)]; }
+
 // k_bulk of sweep t on stream B: fills S generation t%3 from perm generation t%2 (labels after sweep t-2),
 // clears generation (t+1)%3.  Needs k_resolve(t-2) (perm, and the last reader of the generation being cleared).
 static int32_t enqueue_bulk(rc_ctx *c, const View &V, long long t)
@@ -6236,13 +6171,6 @@ static int32_t enqueue_bulk(rc_ctx *c, const View &V, long long t)
     // parity streams it ran on this very stream: in order already, and every event wait is a barrier packet the command
     // processor works through on the critical path (12-19 µs between two kernels of one stream with five of them, ~4 without)
     if (t >= 2 && (c->res_one_stream || c->incremental)) HIPCHK(c, hipStreamWaitEvent(sb, c->ev_res[(t - 2) & 3], 0));
-    // While labels move, the resolver of the previous sweep — several rounds, the critical path — runs beside this reduction and the
-    // two compete for the CUs: the full-read kernel then takes half as many, longer splits (one block per CU at n = 8192 instead of
-    // two), which leaves the resolver the issue slots it needs and still finishes inside its run (moving regime of bench.py:
-    // 2,530 -> 3,230 sweeps/s; 1,024-row splits 2,890, 2,048-row splits 2,100: then the reduction is the longer of the two)
-    const int rows_split = (c->hsum->n_changes > 32 && !c->bulk_rows_forced) ? std::max(c->rows_per_split, std::min(512, 2 * c->rows_per_split)) : c->rows_per_split;
-    const int splits = (c->n + rows_split - 1) / rows_split;
-    dim3 gb((unsigned)(c->ld / (c->bits == 64 ? 512 : 1024)), (unsigned)splits);
     std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
     const bool timed = c->timing && (c->timing_every <= 1 || (t % c->timing_every) == 0);
     if (timed) {
@@ -6257,60 +6185,52 @@ static int32_t enqueue_bulk(rc_ctx *c, const View &V, long long t)
         if (timed) hipExtLaunchKernelGGL(kf, dim3(grid), dim3(block), (uint32_t)(lds), sb, ev.first, ev.second, 0u, __VA_ARGS__); \
         else kf<<<grid, block, lds, sb>>>(__VA_ARGS__);                                                                        \
     } while (0)
-    const bool use_sym = choose_sym(c);
-    c->last_bulk_kernel = use_sym ? 1 : 0;
-    const int sym_variant = sym_variant_of(c);
-    if (use_sym && c->bits == 32 && sym_variant == 2) {
-        int gc = 0, nitems = 0;
-        syml_geometry(c, c->symw_per_cu * c->num_cus, &gc, &nitems);
-        const int nblocks = std::max(1, std::min((nitems + 3) / 4, c->symw_per_cu * c->num_cus));
-        auto kf_ = k_bulk_syml32;
-        RC_BULK_LAUNCH(kf_, nblocks, 256, c->syml_pad, V, (int)(t % 3), (int)((t + 1) % 3), (int)(t & 1), (int)(t & 1), nitems, 0, 8, gc);
-    } else if (use_sym && c->bits == 64 && sym_variant >= 1) {
-        const int ncb = (c->n + RC_SW_COLS - 1) / RC_SW_COLS;
-        const int cap_blocks = c->symw_per_cu * c->num_cus;          // resident 4-wave blocks
-        auto rows_of = [&](int J) { return std::min(RC_SW_COLS * J + RC_SW_COLS, c->n); };
-        if (sym_variant == 3) {
-            // While labels move the resolver of the previous sweep runs its rounds with 512-thread blocks (two waves per SIMD at 128
-            // registers), which do not fit on a CU beside three of this kernel's blocks: they would wait for the reduction to retire
-            // and the two launches run one after the other.  Two blocks per CU (their own unit lists) leave the room: N = 8192, 40
-            // label changes per sweep: 3.2 k -> 3.9 k sweeps/s.
-            View V2 = V;
-            int s2_blocks = c->syml2_blocks, s2_nslow = c->nslow;
-            if (c->hsum->n_changes > 32 && c->s2alt.ufast) {
-                V2.ufast = c->s2alt.ufast; V2.uslow = c->s2alt.uslow; V2.wfast = c->s2alt.wfast; V2.wslow = c->s2alt.wslow;
-                V2.nfast = c->s2alt.nfast; V2.nslow = c->s2alt.nslow;
-                s2_blocks = c->s2alt.blocks; s2_nslow = c->s2alt.nslow;
-            }
-            if (c->derived && !syml2_folds(c)) {   // entries over more than four binades (or rc_set_option "fold_log_table" 0): the exponent is derived per entry
-                if (c->Dq48) { auto kf_ = k_bulk_syml2w<true, true>; RC_BULK_LAUNCH(kf_, s2_blocks, 256, c->syml_pad, V2, (int)(t % 3), (int)(t & 1), (int)(t & 1)); }
-                else { auto kf_ = k_bulk_syml2w<true, false>; RC_BULK_LAUNCH(kf_, s2_blocks, 256, c->syml_pad, V2, (int)(t % 3), (int)(t & 1), (int)(t & 1)); }
-            }
-            else if (c->derived && c->Dq48) { auto kf_ = k_bulk_syml2<true, true>; RC_BULK_LAUNCH(kf_, s2_blocks, 256, c->syml_pad, V2, (int)(t % 3), (int)(t & 1), (int)(t & 1)); }
-            else if (c->derived) { auto kf_ = k_bulk_syml2<true, false>; RC_BULK_LAUNCH(kf_, s2_blocks, 256, c->syml_pad, V2, (int)(t % 3), (int)(t & 1), (int)(t & 1)); }
-            else { auto kf_ = k_bulk_syml2<false, false>; RC_BULK_LAUNCH(kf_, s2_blocks, 256, c->syml_pad, V2, (int)(t % 3), (int)(t & 1), (int)(t & 1)); }
-            if (s2_nslow > 0) {   // ragged last column block: its units by the round-2 code, behind the main launch
-                const int nb = std::min((s2_nslow + 3) / 4, cap_blocks);
-                if (c->derived) k_bulk_syml_list<true><<<nb, 256, 0, sb>>>(V2, (int)(t % 3), (int)(t & 1));
-                else k_bulk_syml_list<false><<<nb, 256, 0, sb>>>(V2, (int)(t % 3), (int)(t & 1));
-            }
-        } else if (sym_variant == 2) {
-            int gc = 0, nitems = 0;
-            const int jsplit = 0, gfine = 8;   // (every column block in gc-row units)
-            syml_geometry(c, cap_blocks, &gc, &nitems);
-            const int nblocks = std::max(1, std::min((nitems + 3) / 4, cap_blocks));
-            if (c->derived) { auto kf_ = k_bulk_syml<true>; RC_BULK_LAUNCH(kf_, nblocks, 256, c->syml_pad, V, (int)(t % 3), (int)((t + 1) % 3), (int)(t & 1), (int)(t & 1), nitems, jsplit, gfine, gc); }
-            else { auto kf_ = k_bulk_syml<false>; RC_BULK_LAUNCH(kf_, nblocks, 256, c->syml_pad, V, (int)(t % 3), (int)((t + 1) % 3), (int)(t & 1), (int)(t & 1), nitems, jsplit, gfine, gc); }
-        } else {
-            int nitems = 0;
-            for (int J = 0; J < ncb; ++J) nitems += (rows_of(J) + RC_SW_ROWS - 1) / RC_SW_ROWS;
-            const int nblocks = std::max(1, std::min((nitems + 3) / 4, cap_blocks));
-            if (c->derived) { auto kf_ = k_bulk_symw<true>; RC_BULK_LAUNCH(kf_, nblocks, 256, 0, V, (int)(t % 3), (int)((t + 1) % 3), (int)(t & 1), (int)(t & 1), nitems); }
-            else { auto kf_ = k_bulk_symw<false>; RC_BULK_LAUNCH(kf_, nblocks, 256, 0, V, (int)(t % 3), (int)((t + 1) % 3), (int)(t & 1), (int)(t & 1), nitems); }
+    const BulkId id = bulk_choice(c);
+    c->last_bulk_kernel = id;
+    const int wgen = (int)(t % 3), zgen = (int)((t + 1) % 3), pgen = (int)(t & 1);   // S generation filled / cleared, generation of the two-generation arrays (perm, snapshots, counters)
+    const int cap_blocks = c->symw_per_cu * c->num_cus;              // resident 4-wave blocks of the wave-autonomous kernels
+    switch (id) {
+    case BK_SYML2_PACK: case BK_SYML2_DERIVED: case BK_SYML2_STORED: case BK_SYML2W_PACK: case BK_SYML2W_DERIVED: {
+        // While labels move the resolver of the previous sweep runs its rounds with 512-thread blocks (two waves per SIMD at 128
+        // registers), which do not fit on a CU beside three of this kernel's blocks: they would wait for the reduction to retire
+        // and the two launches run one after the other.  Two blocks per CU (their own unit lists) leave the room: N = 8192, 40
+        // label changes per sweep: 3.2 k -> 3.9 k sweeps/s.
+        const S2Lists &L = c->s2[(c->hsum->n_changes > 32 && c->s2[1].ufast) ? 1 : 0];
+        View V2 = V;
+        view_lists(V2, L);
+        // (in this order the five are instantiated as they always were — innermost pair first — and the device listing keeps its labels)
+        const auto kf = id == BK_SYML2_STORED ? k_bulk_syml2<false, false> : id == BK_SYML2_DERIVED ? k_bulk_syml2<true, false> : id == BK_SYML2_PACK ? k_bulk_syml2<true, true>
+                      : id == BK_SYML2W_PACK ? k_bulk_syml2w<true, true> : k_bulk_syml2w<true, false>;
+        RC_BULK_LAUNCH(kf, L.blocks, 256, c->syml_pad, V2, wgen, pgen, pgen);
+        if (L.nslow > 0) {   // ragged last column block: its units by the round-2 code, behind the main launch
+            const int nb = std::min((L.nslow + 3) / 4, cap_blocks);
+            const auto kl = c->derived ? k_bulk_syml_list<true> : k_bulk_syml_list<false>;
+            kl<<<nb, 256, 0, sb>>>(V2, wgen, pgen);
         }
-    } else if (use_sym) {
-        const int TC = (c->bits == 64) ? RC_SYM_TC : RC_SYM32_TC;
-        const int TR = (c->bits == 64) ? RC_SYM_TR : c->sym32_tr;                   // rows per tile
+        break;
+    }
+    case BK_SYML_DERIVED: case BK_SYML_STORED: case BK_SYML32: {
+        int gc = 0, nitems = 0;
+        const int jsplit = 0, gfine = 8;   // (every column block in gc-row units)
+        syml_geometry(c, cap_blocks, &gc, &nitems);
+        const int nblocks = std::max(1, std::min((nitems + 3) / 4, cap_blocks));
+        const auto kf = id == BK_SYML32 ? k_bulk_syml32 : id == BK_SYML_DERIVED ? k_bulk_syml<true> : k_bulk_syml<false>;
+        RC_BULK_LAUNCH(kf, nblocks, 256, c->syml_pad, V, wgen, zgen, pgen, pgen, nitems, jsplit, gfine, gc);
+        break;
+    }
+    case BK_SYMW_DERIVED: case BK_SYMW_STORED: {
+        const int ncb = (c->n + RC_SW_COLS - 1) / RC_SW_COLS;
+        int nitems = 0;
+        for (int J = 0; J < ncb; ++J) nitems += (std::min(RC_SW_COLS * J + RC_SW_COLS, c->n) + RC_SW_ROWS - 1) / RC_SW_ROWS;
+        const int nblocks = std::max(1, std::min((nitems + 3) / 4, cap_blocks));
+        const auto kf = id == BK_SYMW_DERIVED ? k_bulk_symw<true> : k_bulk_symw<false>;
+        RC_BULK_LAUNCH(kf, nblocks, 256, 0, V, wgen, zgen, pgen, pgen, nitems);
+        break;
+    }
+    case BK_SYM_DERIVED: case BK_SYM_STORED: case BK_SYM32: {
+        const bool b32 = id == BK_SYM32;
+        const int TC = b32 ? RC_SYM32_TC : RC_SYM_TC;
+        const int TR = b32 ? c->sym32_tr : RC_SYM_TR;                                // rows per tile
         const int item_tiles = c->sym_item_tiles * (RC_SYM_TR / TR);                 // (a work item is the same number of rows either way)
         const int ncb = (c->n + TC - 1) / TC;
         int nitems = 0;
@@ -6318,31 +6238,62 @@ static int32_t enqueue_bulk(rc_ctx *c, const View &V, long long t)
             const int ntile = (std::min(TC * J + TC, c->n) + TR - 1) / TR;
             nitems += (ntile + item_tiles - 1) / item_tiles;
         }
-        const int nblocks = std::max(1, std::min(nitems, (c->bits == 64 ? 2 : c->sym32_bpc) * c->num_cus));
-        if (c->bits == 64 && c->derived)
-            { auto kf_ = k_bulk_sym<true>; RC_BULK_LAUNCH(kf_, nblocks, 256, 0, V, (int)(t % 3), (int)((t + 1) % 3), (int)(t & 1), (int)(t & 1), c->sym_item_tiles, nitems); }
-        else if (c->bits == 64)
-            { auto kf_ = k_bulk_sym<false>; RC_BULK_LAUNCH(kf_, nblocks, 256, 0, V, (int)(t % 3), (int)((t + 1) % 3), (int)(t & 1), (int)(t & 1), c->sym_item_tiles, nitems); }
-        else
-            {
-                // (the second generation argument is unused by this kernel: diag builds pass their timing-ablation flags through it)
-                if (c->sym32_tr == 16) { auto kf_ = k_bulk_sym32<16>; RC_BULK_LAUNCH(kf_, nblocks, 256, 0, V, (int)(t % 3), c->dbg, (int)(t & 1), (int)(t & 1), item_tiles, nitems); }
-                else { auto kf_ = k_bulk_sym32<32>; RC_BULK_LAUNCH(kf_, nblocks, 256, 0, V, (int)(t % 3), c->dbg, (int)(t & 1), (int)(t & 1), item_tiles, nitems); }
-            }
-    } else {
+        const int nblocks = std::max(1, std::min(nitems, (b32 ? c->sym32_bpc : 2) * c->num_cus));
+        const auto kf = !b32 ? (id == BK_SYM_DERIVED ? k_bulk_sym<true> : k_bulk_sym<false>) : (c->sym32_tr == 16 ? k_bulk_sym32<16> : k_bulk_sym32<32>);
+        // (k_bulk_sym32 does not use the second generation argument: diag builds pass their timing-ablation flags through it)
+        RC_BULK_LAUNCH(kf, nblocks, 256, 0, V, wgen, b32 ? c->dbg : zgen, pgen, pgen, item_tiles, nitems);
+        break;
+    }
+    default: {   // BK_FULL_*
+        // While labels move, the resolver of the previous sweep — several rounds, the critical path — runs beside this reduction and the
+        // two compete for the CUs: the full-read kernel then takes half as many, longer splits (one block per CU at n = 8192 instead of
+        // two), which leaves the resolver the issue slots it needs and still finishes inside its run (moving regime of bench.py:
+        // 2,530 -> 3,230 sweeps/s; 1,024-row splits 2,890, 2,048-row splits 2,100: then the reduction is the longer of the two)
+        const int rows_split = (c->hsum->n_changes > 32 && !c->bulk_rows_forced) ? std::max(c->rows_per_split, std::min(512, 2 * c->rows_per_split)) : c->rows_per_split;
+        const int splits = (c->n + rows_split - 1) / rows_split;
+        dim3 gb((unsigned)(c->ld / (c->bits == 64 ? 512 : 1024)), (unsigned)splits);
         // bulk_lds: unused dynamic LDS that caps k_bulk at bulk_blocks_per_cu workgroups per CU, which (i) spreads the
         // grid evenly over the CUs and (ii) leaves registers/wave slots on every CU for the concurrent k_resolve
-        if (c->bits == 64 && c->derived)
-            { auto kf_ = k_bulk<long long, true>; RC_BULK_LAUNCH(kf_, gb, 256, c->bulk_lds, V, rows_split, (int)(t % 3), (int)((t + 1) % 3), (int)(t & 1)); }
-        else if (c->bits == 64)
-            { auto kf_ = k_bulk<long long>; RC_BULK_LAUNCH(kf_, gb, 256, c->bulk_lds, V, rows_split, (int)(t % 3), (int)((t + 1) % 3), (int)(t & 1)); }
-        else
-            { auto kf_ = k_bulk<int>; RC_BULK_LAUNCH(kf_, gb, 256, c->bulk_lds, V, rows_split, (int)(t % 3), (int)((t + 1) % 3), (int)(t & 1)); }
+        const auto kf = id == BK_FULL_DERIVED ? k_bulk<long long, true> : id == BK_FULL_STORED ? k_bulk<long long, false> : k_bulk<int, false>;
+        RC_BULK_LAUNCH(kf, gb, 256, c->bulk_lds, V, rows_split, wgen, zgen, pgen);
+    }
     }
 #undef RC_BULK_LAUNCH
     if (timed) c->ev_pending.push_back(ev);
     if (t == 0 || c->res_one_stream) HIPCHK(c, hipEventRecord(c->ev_bulk[t & 3], sb));   // (read by ensure_S for sweep 0 and by the one-stream mode)
     c->bulk_enq = t;
+    return RC_OK;
+}
+
+// Which row-reduction kernel the last enqueued sweep used (0: k_bulk, full read; 1: one of the symmetric kernels, upper triangle only)
+// and the bytes of matrix data it has to read per launch — what bench.py prices the roofline against.
+extern "C" int32_t rc_bulk_kernel_info(rc_ctx *c, int32_t *which, double *algorithmic_bytes)
+{
+    if (!c) return fail(c, RC_ERR_ARG, "rc_bulk_kernel_info: NULL ctx");
+    const BulkKernel &k = last_bulk(c);
+    const double n = c->n;
+    if (which) *which = k.sym;
+    if (algorithmic_bytes) *algorithmic_bytes = k.sym ? k.matrices * (n * (n + 1) / 2) * k.entry_bytes : k.matrices * n * n * k.entry_bytes;
+    return RC_OK;
+}
+
+// name of the row-reduction kernel the last enqueued sweep used, as a profiler shows it — except that both forms of the derived
+// k_bulk_syml2 go by that name: a context whose entries span more than four binades launches k_bulk_syml2w, the same template
+// arguments (rc_log_table_folded tells the two apart)
+extern "C" const char *rc_bulk_kernel_name(rc_ctx *c) { return c ? last_bulk(c).name : ""; }
+
+// 1: this context's k_bulk_syml2 launches read the log table with the exponent folded in; 0: they derive the exponent per entry
+// (k_bulk_syml2w), or the context does not derive logD
+extern "C" int32_t rc_log_table_folded(rc_ctx *c) { return (c && syml2_folds(c)) ? 1 : 0; }
+
+// Selects the row-reduction kernel: -1 automatic (by label-run count), 0 k_bulk (full read), 1 the context's symmetric kernel
+// (upper triangle: whichever bulk_choice gives for its storage and RC_SYM_VARIANT).  All are exact for every labelling; this only
+// exists for tests and measurements.
+extern "C" int32_t rc_set_bulk_kernel(rc_ctx *c, int32_t which)
+{
+    if (!c) return fail(c, RC_ERR_ARG, "rc_set_bulk_kernel: NULL ctx");
+    if (which < -1 || which > 1) return fail(c, RC_ERR_ARG, "rc_set_bulk_kernel: which must be -1, 0 or 1");
+    c->bulk_kernel = which;
     return RC_OK;
 }
 
@@ -6494,7 +6445,7 @@ static int32_t sweep_enqueue(rc_ctx *c, double r, double p, uint64_t seed, uint6
     if (res_threads == 0)
         // (wide blocks pay with many candidates per point — 32 streams of K = 200 candidates; with a few dozen clusters the extra waves only wait)
         res_threads = c->incremental ? ((c->hsum->K > RC_RES_WIDE_MIN_K && tab_bytes(c->kcap, c->n, RC_RES_THREADS_INC / 64, c->maxb) <= 160 * 1024) ? RC_RES_THREADS_INC : RC_RES_THREADS)
-                                     : ((c->prefetch && c->last_bulk_kernel == 1 && c->hsum->n_changes <= 32) ? 256 : RC_RES_THREADS);
+                                     : ((c->prefetch && BULK_KERNELS[c->last_bulk_kernel].sym && c->hsum->n_changes <= 32) ? 256 : RC_RES_THREADS);
     // (the tables' layout depends on the waves per block — the reduction scratch of eval_chunk — and k_resolve carves it by its blockDim)
 #ifdef RC_TRACE_RESOLVE
     const size_t lds = std::max(tab_bytes(c->kcap, c->n, res_threads / 64, c->maxb), 2 * sizeof(int) * (size_t)c->kcap) + 4096;
@@ -7745,43 +7696,6 @@ extern "C" int32_t rc_set_option(rc_ctx *c, const char *name, int64_t value)
     return RC_OK;
 }
 
-// Which row-reduction kernel the last enqueued sweep used (0: k_bulk, full read; 1: one of the symmetric kernels, upper triangle only)
-// and the bytes of matrix data it has to read per launch — what bench.py prices the roofline against.
-extern "C" int32_t rc_bulk_kernel_info(rc_ctx *c, int32_t *which, double *algorithmic_bytes)
-{
-    if (!c) return fail(c, RC_ERR_ARG, "rc_bulk_kernel_info: NULL ctx");
-    const double n = c->n, esz = c->bits / 8.0;
-    if (which) *which = c->last_bulk_kernel;
-    // matrices the kernel reads: D and logD, or D alone when logD is derived on the fly
-    const double nmat = c->derived ? 1.0 : 2.0;
-    const double esz_read = (c->last_bulk_kernel && sym_variant_of(c) == 3 && c->Dq48) ? 6.0 : esz;   // k_bulk_syml2 streams the 48-bit packed copy
-    if (algorithmic_bytes) *algorithmic_bytes = c->last_bulk_kernel ? nmat * (n * (n + 1) / 2) * esz_read : nmat * n * n * esz;
-    return RC_OK;
-}
-
-
-// name of the row-reduction kernel the last enqueued sweep used, as a profiler shows it — except that both forms of the derived
-// k_bulk_syml2 go by that name: a context whose entries span more than four binades launches k_bulk_syml2w, the same template
-// arguments (rc_log_table_folded tells the two apart)
-extern "C" const char *rc_bulk_kernel_name(rc_ctx *c)
-{
-    if (!c) return "";
-    if (!c->last_bulk_kernel) return c->derived ? "k_bulk<long long, true>" : (c->bits == 64 ? "k_bulk<long long, false>" : "k_bulk<int, false>");
-    if (c->bits != 64) return sym_variant_of(c) == 2 ? "k_bulk_syml32" : "k_bulk_sym32";
-    const int v = sym_variant_of(c);
-    if (v == 3) return c->derived ? (c->Dq48 ? "k_bulk_syml2<true, true>" : "k_bulk_syml2<true, false>") : "k_bulk_syml2<false, false>";
-    if (v == 2) return c->derived ? "k_bulk_syml<true>" : "k_bulk_syml<false>";
-    if (v == 1) return c->derived ? "k_bulk_symw<true>" : "k_bulk_symw<false>";
-    return c->derived ? "k_bulk_sym<true>" : "k_bulk_sym<false>";
-}
-
-// 1: this context's k_bulk_syml2 launches read the log table with the exponent folded in; 0: they derive the exponent per entry
-// (k_bulk_syml2w), or the context does not derive logD
-extern "C" int32_t rc_log_table_folded(rc_ctx *c)
-{
-    return (c && syml2_folds(c)) ? 1 : 0;
-}
-
 extern "C" int32_t rc_layout_info(rc_ctx *c, int32_t *n_relayouts, int32_t *label_runs)
 {
     if (!c) return fail(c, RC_ERR_ARG, "rc_layout_info: NULL ctx");
@@ -7792,17 +7706,6 @@ extern "C" int32_t rc_layout_info(rc_ctx *c, int32_t *n_relayouts, int32_t *labe
     if (label_runs) *label_runs = c->hsum->runs;
     return RC_OK;
 }
-
-// Selects the row-reduction kernel: -1 automatic (by label-run count), 0 k_bulk (full read), 1 k_bulk_sym (upper
-// triangle).  Both are exact for every labelling; this only exists for tests and measurements.
-extern "C" int32_t rc_set_bulk_kernel(rc_ctx *c, int32_t which)
-{
-    if (!c) return fail(c, RC_ERR_ARG, "rc_set_bulk_kernel: NULL ctx");
-    if (which < -1 || which > 1) return fail(c, RC_ERR_ARG, "rc_set_bulk_kernel: which must be -1, 0 or 1");
-    c->bulk_kernel = which;
-    return RC_OK;
-}
-
 
 // What is subtracted from every timed launch: 0 — the two events of a timed launch ride in its dispatch (enqueue_bulk) and report the
 // kernel's own start and stop; nothing is calibrated any more (round 1 recorded marker pairs and subtracted what a pair reports around

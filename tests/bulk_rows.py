@@ -1,4 +1,4 @@
-"""The row-reduction kernels enqueue_bulk (csrc/redclust_hip.hip) can launch in the product build, as a table, and the
+"""The rows of BULK_KERNELS (csrc/redclust_hip.hip: what bulk_choice can return) that a product build reaches, as a table, and the
 pieces tests/test_gpu_bulk_matrix.py and tests/test_gpu_diagonal.py share: creating a context that must end up in a given
 kernel, the fixed-point reference matrices and their per-cluster row sums.
 

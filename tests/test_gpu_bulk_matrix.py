@@ -1,6 +1,6 @@
 """Every row-reduction kernel the product library can launch, at the shapes where tiled kernels go wrong (-m gpu).
 
-enqueue_bulk chooses among fourteen kernels by storage width, by whether logD is derived, by RC_SYM_VARIANT and by the symmetric /
+bulk_choice chooses among fourteen kernels by storage width, by whether logD is derived, by RC_SYM_VARIANT and by the symmetric /
 full-read choice (tests/bulk_rows.py lists them).  Each is put through
   * test_row_sums: rc_set_state, then the S table the kernel just wrote (rc_debug_rowsums) against plain integer sums of the
     fixed-point matrices, both matrices bit for bit, plus Σ_labels S == rc_debug_rowtotals — for every size of SIZES (tile edges:
@@ -178,6 +178,43 @@ def test_sym_variant_out_of_range_is_automatic(value):
     """RC_SYM_VARIANT outside 0..3 means "automatic", as if it were not set: the kernels of rows 1, 7 and 12, named truthfully."""
     for row in B.DEFAULT_ROWS:
         _run_size(row._replace(variant=value), 257, True)
+
+
+def test_two_per_cu_lists_at_a_ragged_size():
+    """k_bulk_syml2 reads its second set of unit lists (two blocks per CU) only for a launch enqueued while the last sweep changed
+    more than 32 labels.  n = 135 is one full column block plus seven rows — the last block has 128 fast rows and one slow unit —
+    and from uniformly random labels on a matrix without structure nearly every point moves in every sweep (the CPU oracle: 124 to
+    135 changes per sweep of this chain), so every launch after the first sweep takes those lists.  The full-read kernel, which has
+    no lists, runs the same chain: labels and the row sums of every live label must agree exactly after every sweep."""
+    n, nsweeps, seed = 135, 6, 77
+    D = matrix("narrow", n)
+    init = np.random.default_rng(3000).integers(1, 21, n).astype(np.int64)
+    P = rc.likelihood_hyperparams(D, init)
+    row_sym, row_perm = (next(r for r in B.ROWS if r.id == i) for i in ("01", "06"))
+    sym, _ = B.make_context(row_sym, D)
+    perm, _ = B.make_context(row_perm, D)
+    try:
+        for ctx in (sym, perm):
+            ctx.set_params(**P)
+            ctx.set_state(init)
+        changes = []
+        for t in range(nsweeps):
+            r, p = B.rp_schedule(t)
+            for ctx in (sym, perm):
+                ctx.gibbs_sweep(r, p, seed, t)
+            assert sym.bulk_kernel_name() == row_sym.name and perm.bulk_kernel_name() == row_perm.name, t
+            lab = sym.get_state()[0]
+            assert np.array_equal(lab, perm.get_state()[0]), (t, int(np.sum(lab != perm.get_state()[0])))
+            changes.append(sym.sweep_stats()["n_changes"])
+            assert changes[-1] == perm.sweep_stats()["n_changes"], t
+            for k in np.unique(lab):
+                for a, b in zip(sym.debug_rowsums(int(k))[:2], perm.debug_rowsums(int(k))[:2]):
+                    assert np.array_equal(a, b), (t, int(k), np.flatnonzero(a != b)[:8])
+        print("label changes per sweep:", changes)
+        assert max(changes[:-1]) > 32, changes                 # some sweep with that many changes was followed by another
+    finally:
+        sym.close()
+        perm.close()
 
 
 @pytest.fixture(scope="module")

@@ -658,6 +658,58 @@ int32_t rc_predict(int32_t device, int64_t n, int64_t q,
                    int32_t *eD_out /* q or NULL */, int32_t *eL_out /* q or NULL */, double *kernel_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Joint predict: new observations that may form clusters with each other.  One posterior sample (training labels z over n
+ * points, r_s, p_s) defines an independent problem whose state is z, which never changes, and the labels y_1..y_q of the q
+ * new observations, which start unallocated.  No context: errors through rc_last_error(NULL).  DESIGN.md §8 "Joint predict".
+ *
+ * A visit of new point i does what src/mcmc.jl:192-252 does for point n+i of the (n+q)-point problem whose other
+ * unallocated points do not exist:
+ *  1. Remove i.  If it was allocated its cluster shrinks; a cluster made only of new points may die, training clusters cannot.
+ *  2. Score every non-empty cluster with rc_predict's score above; S_D and S_L run over the cluster's members (its training
+ *     points and the other allocated new points in it), s_k is the cluster's size without i.
+ *  3. Offer a new cluster, log(K_i + 1) + r_s·log(1 − p_s), iff params->maxK == 0 || K_i < params->maxK; K_i counts all
+ *     non-empty clusters after the removal, those born earlier in the same call included.
+ *  4. Draw by Gumbel-max; ties go to the smaller label, the new cluster last.  A new cluster takes the lowest label of 1..n+q
+ *     that has no member at that moment (findfirst(clustsizes .== 0), mcmc.jl:199), so a label freed by a death is reused.
+ * Passes: pass 0 visits i = 1..q in the caller's order (sequential allocation: y_i sees z and y_1..y_{i−1}); `sweeps` >= 0
+ * further passes visit 1..q again with everything else allocated — Gibbs on p(y | z, D, r_s, p_s).
+ * Uniforms: Philox4x32-10, key (seed_lo, seed_hi ^ 0x5052444A), counter (candidate label, or 0 for the new cluster; visit
+ * index v = pass·q + i, 0-based; s_lo; s_hi), s = sample_offset + sample index, u = (top 52 bits + ½)·2^-52.
+ * (sweeps + 1)·q < 2^32 is required.
+ * Fixed point: row i is the n entries of Dnew[i] followed by the q entries of Dnn[i]; the diagonal entry is ignored and
+ * counts as 0.  The row is quantised with one exponent, eD_i = 62 − ex_i − ceil(log2(n + q)), rc_predict's rule with n + q
+ * addends; its logarithms likewise (logDnew / logDnn both NULL: the host's libm log).  Every sum is an exact int64, so a
+ * sample's result is a pure function of that sample, the rows, the seed and its own counter: splitting the samples over
+ * several calls with sample_offset changes no bit.  The new points of a call always travel together.
+ * Size-dependent terms: A[s] for sizes up to n + q; log p_s on the host; log(s − 1 + r_s) on the device by the sweep's
+ * logarithm, which takes positive normal arguments: an r below the smallest normal double is RC_ERR_ARG here.
+ *
+ * labels_out[s][i]: the final label in sample s's own names; new clusters carry the free labels they took, there is no 0.
+ * first_out (may be NULL): the labels after pass 0.  K_out[s]: clusters of the extended sample.  moves_out (may be NULL)
+ * [s][pass]: the visits of the pass whose draw differs from the point's previous label (pass 0 gives q).  sums_out (may be
+ * NULL) [s][i][0..1]: the int64 (S_D, S_L) of the cluster the point joined at its last visit, without the point; (0, 0) for
+ * a cluster it opened.  eD_out, eL_out (may be NULL): the exponents of every new point.  kernel_ms (may be NULL): device time.
+ *
+ * Errors, all before any device work.  rc_predict's own apply (NULL pointers, sizes, labels, r, p, params, the device;
+ * RC_ERR_DOMAIN for an entry of Dnew that is not finite or not > 0 or a given log that is not finite; RC_ERR_CAPACITY for
+ * n > 32767 or m·n >= 2^31).  RC_ERR_ARG also: Dnn or K_out NULL, one of logDnew / logDnn without the other, sweeps < 0,
+ * (sweeps + 1)·q >= 2^32.  RC_ERR_DOMAIN also: Dnn not symmetric, or not finite and > 0 off the diagonal.
+ * RC_ERR_CAPACITY also: K_s + q > 4096 for a sample (the message names it) — a sample's slots, its clusters and up to q new
+ * ones, live in the workgroup's LDS.  Larger q: call in blocks, each block's extended samples the next block's training set.
+ * The host walks the samples in chunks whose base sums (q·16·ΣK_s bytes) fit a workspace of 1 GiB;
+ * RC_PREDICT_WORKSPACE_KIB=<k> shrinks it as for rc_predict — the same results either way; for tests.
+ * ------------------------------------------------------------------------------------------------------------- */
+int32_t rc_predict_joint(int32_t device, int64_t n, int64_t q,
+                         const double *Dnew /* q×n row-major */, const double *Dnn /* q×q symmetric, diagonal ignored */,
+                         const double *logDnew_or_null /* q×n */, const double *logDnn_or_null /* q×q; both or neither */,
+                         int64_t m, const int64_t *samples /* m×n, labels 1..n */,
+                         const double *r /* m */, const double *p /* m */, const rc_params *params,
+                         int64_t sweeps, uint64_t seed, uint64_t sample_offset,
+                         int64_t *labels_out /* m×q */, int64_t *first_out /* m×q or NULL */, int64_t *K_out /* m */,
+                         int64_t *moves_out /* m×(sweeps+1) or NULL */, int64_t *sums_out /* m×q×2 or NULL */,
+                         int32_t *eD_out /* q or NULL */, int32_t *eL_out /* q or NULL */, double *kernel_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Partition distances: what the Binder loss, the VI and the information distance between each of L labellings and each
  * of m samples are made of, as exact integers — the L×m rectangle behind credible balls and exact expected losses.  No
  * context: errors through rc_last_error(NULL).  DESIGN.md §8 "Partition distances".

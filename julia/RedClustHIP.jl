@@ -601,6 +601,44 @@ end
 
 export predict
 
+"""
+    predict_joint(HIPBackend(), result, Dnew, Dnn; sweeps = 2, seed = 0) -> (labels, first_labels, K, moves)
+
+Allocate new observations to the clusters of every sample of `result` jointly, on the GPU (rc_predict_joint): under one sample
+the new observations are allocated one after the other in the order given, each seeing the training labels and the new
+observations before it, and then visited again in `sweeps` Gibbs passes, so that new observations may form clusters with each
+other.  `Dnew` is q×n as for `predict`; `Dnn` is q×q, symmetric, the distances among the new observations (the diagonal is
+ignored).  `labels[i, s]` is the final label of new point `i` under sample `s` in that sample's own names — a cluster that new
+points opened carries a label of 1..n+q the sample did not use, so `vcat(sample, labels[:, s])` is a labelling of n+q points;
+`first_labels` holds the labels after the sequential pass, `K[s]` the clusters of the extended sample, `moves[pass, s]` the
+visits of each pass whose draw changed the point's label.  A sample's clusters and `q` must fit 4096 slots together.
+"""
+function predict_joint(b::HIPBackend, result, Dnew::Matrix{Float64}, Dnn::Matrix{Float64}; sweeps = 2, seed = 0)
+    samples = samplematrix(result)
+    n, m = size(samples)
+    q = size(Dnew, 1)
+    size(Dnew, 2) == n || throw(ArgumentError("Dnew must have one column per training observation."))
+    size(Dnn) == (q, q) || throw(ArgumentError("Dnn must be q×q."))
+    sweeps >= 0 || throw(ArgumentError("sweeps must be non-negative."))
+    rows = permutedims(Dnew)                                      # n×q column-major = q×n row-major
+    rowsn = permutedims(Dnn)
+    r = Vector{Float64}(result.r); p = Vector{Float64}(result.p)
+    labels = Matrix{Int64}(undef, q, m)                           # column s = sample s: row-major m×q for the library
+    first = Matrix{Int64}(undef, q, m)
+    K = Vector{Int64}(undef, m)
+    moves = Matrix{Int64}(undef, sweeps + 1, m)
+    rc = ccall((:rc_predict_joint, LIB), Int32,
+               (Int32, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{Cdouble},
+                Ptr{Cdouble}, Ref{RcParams}, Int64, UInt64, UInt64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64},
+                Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}),
+               b.device, n, q, rows, rowsn, C_NULL, C_NULL, m, samples, r, p, Ref(RcParams(result.params)), sweeps,
+               seed % UInt64, UInt64(0), labels, first, K, moves, C_NULL, C_NULL, C_NULL, C_NULL)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return (labels, first, K, moves)
+end
+
+export predict_joint
+
 const DISTANCE_LOSSES = ("binder", "VI", "ID")
 
 """

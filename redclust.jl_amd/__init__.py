@@ -16,5 +16,5 @@ from .pointestimate import (getpointestimate, lossmatrix, binderloss, infodist, 
                             posterior_counts, posterior_coclustering, hclust, hclustpointestimate, expectedlosses,
                             linkage_matrix, leaf_order, partitiondistances, expecteddistances, credibleball,
                             credibleball_from_distances, relabel, Relabelling)
-from .predict import predict, Prediction  # noqa: F401
+from .predict import predict, Prediction, predict_joint, JointPrediction  # noqa: F401
 from .score import scorelabellings, loglik_from_blocks, mapestimate, reweight  # noqa: F401

@@ -219,6 +219,9 @@ SIGNATURES = {
     "rc_predict": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.POINTER(RcParams), C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "rc_predict_joint": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.POINTER(RcParams), C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "rc_partition_distances": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "rc_relabel": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
@@ -950,6 +953,56 @@ def predict(Dnew, samples, r, p, params: dict, seed: int = 0, sample_offset: int
         out["scores"] = sc[:m, :q]
     if want_sums:
         out["sums"] = sm[:m, :q, :int(Kmax)]
+    return out
+
+
+def predict_joint(Dnew, Dnn, samples, r, p, params: dict, sweeps: int = 2, seed: int = 0, sample_offset: int = 0, logDnew=None,
+                  logDnn=None, want_first: bool = True, want_moves: bool = True, want_sums: bool = False, device: int = 0) -> dict:
+    """rc_predict_joint: labels (m×q, names in 1..n+q), first (the labels after pass 0, or None), K (m), moves (m×(sweeps+1), or
+    None), sums (m×q×2, when asked for), eD / eL (q) and kernel_ms for the q×n distances Dnew of new points to the training
+    points, the q×q distances Dnn among the new points and an m×n label matrix with one r and p per sample."""
+    L = lib()
+    D = np.ascontiguousarray(Dnew, dtype=np.float64)
+    Dn = np.ascontiguousarray(Dnn, dtype=np.float64)
+    S = np.ascontiguousarray(samples, dtype=np.int64)
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    if D.ndim != 2 or S.ndim != 2 or D.shape[1] != S.shape[1]:
+        raise ValueError("Dnew must be q×n and samples m×n")
+    q, n = D.shape
+    m = S.shape[0]
+    if Dn.shape != (q, q):
+        raise ValueError("Dnn must be q×q")
+    if r.shape != (m,) or p.shape != (m,):
+        raise ValueError("r and p must hold one value per sample")
+    if (logDnew is None) != (logDnn is None):
+        raise ValueError("give logDnew and logDnn together or neither")
+    lp = ln = None
+    if logDnew is not None:
+        logDnew = np.ascontiguousarray(logDnew, dtype=np.float64)
+        logDnn = np.ascontiguousarray(logDnn, dtype=np.float64)
+        if logDnew.shape != D.shape or logDnn.shape != Dn.shape:
+            raise ValueError("logDnew and logDnn must have the shapes of Dnew and Dnn")
+        lp, ln = logDnew.ctypes.data, logDnn.ctypes.data
+    prm = _params_struct(params)
+    nm = max(int(sweeps), 0) + 1
+    labels = np.zeros((max(m, 1), max(q, 1)), np.int64)
+    first = np.zeros_like(labels) if want_first else None
+    K = np.zeros(max(m, 1), np.int64)
+    moves = np.zeros((max(m, 1), nm), np.int64) if want_moves else None
+    sm = np.zeros((max(m, 1), max(q, 1), 2), np.int64) if want_sums else None
+    eD, eL = np.zeros(max(q, 1), np.int32), np.zeros(max(q, 1), np.int32)
+    ms = C.c_double()
+    M64 = 0xFFFFFFFFFFFFFFFF
+    rc = L.rc_predict_joint(int(device), n, q, D.ctypes.data, Dn.ctypes.data, lp, ln, m, S.ctypes.data, r.ctypes.data, p.ctypes.data,
+                            C.byref(prm), int(sweeps), int(seed) & M64, int(sample_offset) & M64, labels.ctypes.data,
+                            None if first is None else first.ctypes.data, K.ctypes.data, None if moves is None else moves.ctypes.data,
+                            None if sm is None else sm.ctypes.data, eD.ctypes.data, eL.ctypes.data, C.byref(ms))
+    _check(rc)
+    out = dict(labels=labels[:m, :q], first=None if first is None else first[:m, :q], K=K[:m], moves=None if moves is None else moves[:m],
+               eD=eD[:q], eL=eL[:q], kernel_ms=float(ms.value))
+    if want_sums:
+        out["sums"] = sm[:m, :q]
     return out
 
 

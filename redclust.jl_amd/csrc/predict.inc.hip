@@ -214,58 +214,117 @@ struct Call {
     bool rows_global;
 };
 
+// The preparation of a run of samples that predict and the joint predict (predictjoint.inc.hip) share: the sorted orders on the
+// host and the device, and the launch of k_predict_sums over them.
+struct Orders {
+    int64_t n = 0, ms = 0;
+    int ms_pad = 0, parts = 1;
+    long long ktot = 0;
+    std::vector<unsigned short> perm;       // [n][ms_pad]
+    std::vector<int> startslot, Ks;         // [parts][ms_pad]; [ms]
+    std::vector<long long> koff;            // [ms]
+    std::vector<int2> szlab;                // [ktot] (size, label)
+    unsigned short *d_perm = nullptr; int *d_startslot = nullptr, *d_K = nullptr; long long *d_koff = nullptr; int2 *d_szlab = nullptr;
+
+    // samples s0 .. s0 + ms - 1 of the m×n matrix, K: the cluster counts of all m; slot(s, at, label, size) once per slot of
+    // sample s, `at` its index among the ktot slots.  false: no host memory.
+    template <typename Slot>
+    bool build(const int64_t *samples, int64_t n_, const int *K, int64_t s0, int64_t ms_, Slot slot)
+    {
+        n = n_; ms = ms_;
+        ms_pad = (int)((ms + 63) / 64 * 64);
+        parts = ms_pad >= TPB1 ? 1 : (int)std::min<int64_t>(TPB1 / ms_pad, n);
+        std::vector<int> partat, cnt, slot_of_label, pos;
+        ktot = 0;
+        try {
+            perm.assign((size_t)n * ms_pad, 0);
+            startslot.assign((size_t)parts * ms_pad, 0);
+            partat.assign((size_t)n, -1);
+            cnt.assign((size_t)n + 1, 0); slot_of_label.assign((size_t)n + 1, 0); pos.assign((size_t)n, 0);
+            koff.resize((size_t)ms); Ks.resize((size_t)ms);
+            for (int64_t s = 0; s < ms; ++s) ktot += K[s0 + s];
+            szlab.resize((size_t)ktot);
+        } catch (const std::bad_alloc &) { return false; }
+        for (int p = 0; p < parts; ++p) partat[(size_t)((long long)p * n / parts)] = p;
+        long long k0 = 0;
+        for (int64_t s = 0; s < ms; ++s) {
+            const int64_t *z = samples + (size_t)(s0 + s) * n;
+            const int Ks_ = cluster_order(z, n, cnt, slot_of_label, pos,
+                [&](int t, int64_t l, int sz) {
+                    szlab[(size_t)(k0 + t)] = make_int2(sz, (int)l);
+                    slot(s, k0 + t, l, sz);
+                },
+                [&](int at_, int64_t j, int t) {
+                    perm[(size_t)at_ * ms_pad + s] = (unsigned short)j;
+                    if (partat[(size_t)at_] >= 0) startslot[(size_t)partat[(size_t)at_] * ms_pad + s] = t;
+                });
+            koff[(size_t)s] = k0; Ks[(size_t)s] = Ks_;
+            // after the fill pos[t] is one past slot t's last position: mark those
+            for (int t = 0; t < Ks_; ++t) perm[(size_t)(pos[(size_t)t] - 1) * ms_pad + s] |= 0x8000u;
+            k0 += Ks_;
+        }
+        return true;
+    }
+
+    hipError_t upload(DeviceBuffers &B)
+    {
+        hipError_t e;
+        if ((e = B.alloc(d_perm, perm.size())) != hipSuccess) return e;
+        if ((e = B.alloc(d_startslot, startslot.size())) != hipSuccess) return e;
+        if ((e = B.alloc(d_K, (size_t)ms)) != hipSuccess) return e;
+        if ((e = B.alloc(d_koff, (size_t)ms)) != hipSuccess) return e;
+        if ((e = B.alloc(d_szlab, (size_t)ktot)) != hipSuccess) return e;
+        if ((e = hipMemcpy(d_perm, perm.data(), perm.size() * sizeof(unsigned short), hipMemcpyHostToDevice)) != hipSuccess) return e;
+        if ((e = hipMemcpy(d_startslot, startslot.data(), startslot.size() * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess) return e;
+        if ((e = hipMemcpy(d_K, Ks.data(), (size_t)ms * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess) return e;
+        if ((e = hipMemcpy(d_koff, koff.data(), (size_t)ms * sizeof(long long), hipMemcpyHostToDevice)) != hipSuccess) return e;
+        return hipMemcpy(d_szlab, szlab.data(), (size_t)ktot * sizeof(int2), hipMemcpyHostToDevice);
+    }
+
+    // the [np][ktot] sums of np rows ([np][n] (Dq, Lq)) on stream 0; rows_global: gather from global memory at any n
+    hipError_t launch_sums(const ll2 *d_rows, int64_t np, bool rows_global, ll2 *d_sums) const
+    {
+        const bool ldsrow = !rows_global && n <= LDS_ROW_MAX_N;
+        const size_t lds = ldsrow ? (size_t)n * sizeof(ll2) : 0;
+        auto kern = ldsrow ? (parts > 1 ? k_predict_sums<true, true> : k_predict_sums<true, false>)
+                           : (parts > 1 ? k_predict_sums<false, true> : k_predict_sums<false, false>);
+        hipError_t e = set_dynamic_lds(kern, lds);
+        if (e != hipSuccess) return e;
+        if (parts > 1 && (e = hipMemsetAsync(d_sums, 0, (size_t)np * ktot * sizeof(ll2), 0)) != hipSuccess) return e;   // the parts add into zeros
+        kern<<<(unsigned)np, TPB1, lds, 0>>>(d_rows, (int)n, d_perm, (int)ms, ms_pad, parts, d_startslot, d_koff, ktot, d_sums);
+        return hipGetLastError();
+    }
+};
+
 // samples s0 .. s0 + ms - 1 against every new point, the points in chunks of at most qc.  ms_acc: device milliseconds, added to.
 static int32_t run_samples(const char *who, const Call &c, int64_t s0, int64_t ms, int64_t qc, double &ms_acc)
 {
     const int64_t n = c.n;
-    const int ms_pad = (int)((ms + 63) / 64 * 64);
-    const int parts = ms_pad >= TPB1 ? 1 : (int)std::min<int64_t>(TPB1 / ms_pad, n);
     const bool want_tab = c.scores_out || c.sums_out;
     const int Kcols = want_tab ? (int)c.Kmax : 0;
-    std::vector<unsigned short> perm;
-    std::vector<int> startslot, partat, cnt, slot_of_label, pos, Ks;
-    std::vector<long long> koff;
-    std::vector<int2> szlab;
+    Orders O;
     std::vector<double> base, newscore;
-    long long ktot = 0;
+    bool ok = true;
     try {
-        perm.assign((size_t)n * ms_pad, 0);
-        startslot.assign((size_t)parts * ms_pad, 0);
-        partat.assign((size_t)n, -1);
-        cnt.assign((size_t)n + 1, 0); slot_of_label.assign((size_t)n + 1, 0); pos.assign((size_t)n, 0);
-        koff.resize((size_t)ms); newscore.resize((size_t)ms); Ks.resize((size_t)ms);
-        for (int64_t s = 0; s < ms; ++s) ktot += c.K[s0 + s];
-        szlab.resize((size_t)ktot); base.resize((size_t)ktot);
-    } catch (const std::bad_alloc &) { return fail(nullptr, RC_ERR_OOM, "%s: no host memory for the sorted orders of %lld samples", who, (long long)ms); }
-    for (int p = 0; p < parts; ++p) partat[(size_t)((long long)p * n / parts)] = p;
-    long long k0 = 0;
+        long long kt = 0;
+        for (int64_t s = 0; s < ms; ++s) kt += c.K[s0 + s];
+        base.resize((size_t)kt); newscore.resize((size_t)ms);
+    } catch (const std::bad_alloc &) { ok = false; }
+    ok = ok && O.build(c.samples, n, c.K, s0, ms, [&](int64_t s, long long at, int64_t, int sz) {
+        base[(size_t)at] = c.A[sz] + (std::log(c.p[s0 + s]) + std::log((double)sz - 1.0 + c.r[s0 + s]));
+    });
+    if (!ok) return fail(nullptr, RC_ERR_OOM, "%s: no host memory for the sorted orders of %lld samples", who, (long long)ms);
+    const long long ktot = O.ktot;
     for (int64_t s = 0; s < ms; ++s) {
-        const int64_t *z = c.samples + (size_t)(s0 + s) * n;
-        const double r = c.r[s0 + s], p = c.p[s0 + s], logp = std::log(p);
-        const int K = cluster_order(z, n, cnt, slot_of_label, pos,
-            [&](int t, int64_t l, int sz) {
-                szlab[(size_t)(k0 + t)] = make_int2(sz, (int)l);
-                base[(size_t)(k0 + t)] = c.A[sz] + (logp + std::log((double)sz - 1.0 + r));
-            },
-            [&](int at_, int64_t j, int t) {
-                perm[(size_t)at_ * ms_pad + s] = (unsigned short)j;
-                if (partat[(size_t)at_] >= 0) startslot[(size_t)partat[(size_t)at_] * ms_pad + s] = t;
-            });
-        koff[(size_t)s] = k0; Ks[(size_t)s] = K;
+        const double r = c.r[s0 + s], p = c.p[s0 + s];
+        const int K = O.Ks[(size_t)s];
         newscore[(size_t)s] = (c.P->maxK == 0 || K < c.P->maxK) ? std::log((double)(K + 1)) + r * std::log(1 - p) : -INFINITY;
-        // after the fill pos[t] is one past slot t's last position: mark those
-        for (int t = 0; t < K; ++t) perm[(size_t)(pos[(size_t)t] - 1) * ms_pad + s] |= 0x8000u;
-        k0 += K;
     }
 
     DeviceBuffers B;
-    unsigned short *d_perm; int *d_startslot, *d_K; long long *d_koff; int2 *d_szlab; double *d_base, *d_newscore, *d_scD, *d_scL;
+    double *d_base, *d_newscore, *d_scD, *d_scL;
     ll2 *d_rows, *d_sums; long long *d_labels, *d_map, *d_sums_out = nullptr; double *d_scores = nullptr;
-    HIPCHK(nullptr, B.alloc(d_perm, perm.size()));
-    HIPCHK(nullptr, B.alloc(d_startslot, startslot.size()));
-    HIPCHK(nullptr, B.alloc(d_K, (size_t)ms));
-    HIPCHK(nullptr, B.alloc(d_koff, (size_t)ms));
-    HIPCHK(nullptr, B.alloc(d_szlab, (size_t)ktot));
+    HIPCHK(nullptr, O.upload(B));
     HIPCHK(nullptr, B.alloc(d_base, (size_t)ktot));
     HIPCHK(nullptr, B.alloc(d_newscore, (size_t)ms));
     HIPCHK(nullptr, B.alloc(d_scD, (size_t)qc));
@@ -276,19 +335,8 @@ static int32_t run_samples(const char *who, const Call &c, int64_t s0, int64_t m
     HIPCHK(nullptr, B.alloc(d_map, (size_t)qc * ms));
     if (c.scores_out) HIPCHK(nullptr, B.alloc(d_scores, (size_t)qc * ms * (Kcols + 1)));
     if (c.sums_out) HIPCHK(nullptr, B.alloc(d_sums_out, (size_t)qc * ms * std::max(Kcols, 1) * 2));
-    HIPCHK(nullptr, hipMemcpy(d_perm, perm.data(), perm.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-    HIPCHK(nullptr, hipMemcpy(d_startslot, startslot.data(), startslot.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(nullptr, hipMemcpy(d_K, Ks.data(), (size_t)ms * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(nullptr, hipMemcpy(d_koff, koff.data(), (size_t)ms * sizeof(long long), hipMemcpyHostToDevice));
-    HIPCHK(nullptr, hipMemcpy(d_szlab, szlab.data(), (size_t)ktot * sizeof(int2), hipMemcpyHostToDevice));
     HIPCHK(nullptr, hipMemcpy(d_base, base.data(), (size_t)ktot * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(nullptr, hipMemcpy(d_newscore, newscore.data(), (size_t)ms * sizeof(double), hipMemcpyHostToDevice));
-
-    const bool ldsrow = !c.rows_global && n <= LDS_ROW_MAX_N;
-    const size_t lds = ldsrow ? (size_t)n * sizeof(ll2) : 0;
-    auto kern = ldsrow ? (parts > 1 ? k_predict_sums<true, true> : k_predict_sums<true, false>)
-                       : (parts > 1 ? k_predict_sums<false, true> : k_predict_sums<false, false>);
-    HIPCHK(nullptr, set_dynamic_lds(kern, lds));
 
     std::vector<ll2> rows;
     std::vector<long long> h_lab, h_tab;
@@ -317,7 +365,7 @@ static int32_t run_samples(const char *who, const Call &c, int64_t s0, int64_t m
         HIPCHK(nullptr, hipMemcpy(d_scD, scD.data(), (size_t)np * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(nullptr, hipMemcpy(d_scL, scL.data(), (size_t)np * sizeof(double), hipMemcpyHostToDevice));
         DrawArgs a{};
-        a.ms = (int)ms; a.npts = (int)np; a.Kmax = Kcols; a.ktot = ktot; a.sums = d_sums; a.koff = d_koff; a.K = d_K; a.szlab = d_szlab;
+        a.ms = (int)ms; a.npts = (int)np; a.Kmax = Kcols; a.ktot = ktot; a.sums = d_sums; a.koff = O.d_koff; a.K = O.d_K; a.szlab = O.d_szlab;
         a.base = d_base; a.newscore = d_newscore; a.scD = d_scD; a.scL = d_scL; a.flt = c.d_flt;
         a.alpha = P.alpha; a.beta = P.beta; a.zeta = P.zeta; a.gamma = P.gamma; a.delta1 = P.delta1; a.delta2 = P.delta2;
         a.cL = (P.delta1 - 1.0) - (P.repulsion ? (P.delta2 - 1.0) : 0.0);
@@ -326,9 +374,7 @@ static int32_t run_samples(const char *who, const Call &c, int64_t s0, int64_t m
         a.sample0 = c.sample_offset + (uint64_t)s0; a.point0 = c.point_offset + (uint64_t)i0;
         a.labels = d_labels; a.map = d_map; a.scores = d_scores; a.sums_out = d_sums_out;
         HIPCHK(nullptr, ev.begin(0));
-        if (parts > 1) HIPCHK(nullptr, hipMemsetAsync(d_sums, 0, (size_t)np * ktot * sizeof(ll2), 0));   // the parts add into zeros
-        kern<<<(unsigned)np, TPB1, lds, 0>>>(d_rows, (int)n, d_perm, (int)ms, ms_pad, parts, d_startslot, d_koff, ktot, d_sums);
-        HIPCHK(nullptr, hipGetLastError());
+        HIPCHK(nullptr, O.launch_sums(d_rows, np, c.rows_global, d_sums));
         k_predict_draw<<<(unsigned)(((size_t)np * ms + TPB2 / 64 - 1) / (TPB2 / 64)), TPB2, 0, 0>>>(a);
         HIPCHK(nullptr, ev.end(0));
         HIPCHK(nullptr, ev.elapsed_ms(ms_acc));

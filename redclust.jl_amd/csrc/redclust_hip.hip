@@ -7787,6 +7787,7 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "samplecounts.inc.hip"
 #include "hclust.inc.hip"
 #include "predict.inc.hip"
+#include "predictjoint.inc.hip"
 #include "partdist.inc.hip"
 #include "relabel.inc.hip"
 #include "score.inc.hip"

@@ -1,7 +1,9 @@
 """Predict: allocate observations that were not in the fit to the clusters of every posterior sample, on the GPU
 (csrc/predict.inc.hip through rc_predict; include/redclust_hip.h has the contract, DESIGN.md §8 "Predict" the design).
 Under one sample the allocation of a new observation is the Gibbs full conditional of an (n+1)-th point whose own cluster is
-empty; new observations are allocated independently of each other given a sample.  There is no CPU fallback."""
+empty; predict allocates new observations independently of each other given a sample, predict_joint (rc_predict_joint,
+csrc/predictjoint.inc.hip, DESIGN.md §8 "Joint predict") one after the other and then by Gibbs passes, so that new
+observations may form clusters with each other.  There is no CPU fallback."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -53,24 +55,64 @@ class Prediction:
         sample's names, its rank among them the column of relabelling.maps[s] that says which pivot cluster it became.
         Columns as relabelling.counts: column k >= 1 is the pivot's cluster pivot_labels[k - 1]; column 0 is a cluster of
         its own (label 0) or a cluster of the sample that the pivot has no counterpart for.  Every row sums to 1."""
+        return _allocation(self.labels, relabelling, samples, unknown_raises=True)
+
+
+@dataclass
+class JointPrediction:
+    """labels[s, i]: the label of new point i under sample s after the last pass, in that sample's own label names; a cluster
+    that new points opened carries a label of 1..n+q that the sample did not use (there is no 0).  first_labels: the labels
+    after pass 0, the sequential allocation.  K[s]: clusters of the extended sample.  moves[s, pass]: the visits of the pass
+    whose draw differs from the point's previous label (pass 0 gives q).  kernel_ms: device time of the kernels."""
+    labels: np.ndarray
+    first_labels: np.ndarray
+    K: np.ndarray
+    moves: np.ndarray
+    kernel_ms: float = 0.0
+
+    def extended_samples(self, samples) -> np.ndarray:
+        """The m×(n+q) label matrix of training and new points together: a plain concatenation, because the labels are
+        already names in 1..n+q that are distinct where the clusters are.  posterior_counts, searchpointestimate,
+        hclustpointestimate, relabel and credibleball take the matrix as it is."""
         S = _label_matrix(samples)
-        m, q = self.labels.shape
-        if S.shape[0] != m or relabelling.maps.shape[0] != m:
-            raise ValueError(f"samples and the relabelling must be of the {m} samples of the prediction")
-        names = np.asarray(relabelling.pivot_labels, dtype=np.int64)
-        counts = np.zeros((q, len(names) + 1), np.int64)
-        for s in range(m):
-            own = np.unique(S[s])
-            lab = self.labels[s]
-            t = np.searchsorted(own, lab)
-            known = (lab > 0) & (t < len(own))
-            known &= own[np.minimum(t, len(own) - 1)] == lab
-            if not np.all(known | (lab == 0)):
-                raise ValueError(f"a label of the prediction is not a label of sample {s + 1}")
-            to = np.where(known, relabelling.maps[s][np.where(known, t, 0)], 0)
-            col = np.where(to > 0, np.searchsorted(names, np.maximum(to, 1)) + 1, 0)
-            counts[np.arange(q), col] += 1
-        return counts / float(m)
+        if S.shape[0] != self.labels.shape[0]:
+            raise ValueError(f"samples must be the {self.labels.shape[0]} samples of the prediction")
+        return np.concatenate([S, self.labels], axis=1)
+
+    def new_cluster_frequency(self, samples) -> np.ndarray:
+        """Per new point: the share of samples in which its cluster holds no training point."""
+        S = _label_matrix(samples)
+        if S.shape[0] != self.labels.shape[0]:
+            raise ValueError(f"samples must be the {self.labels.shape[0]} samples of the prediction")
+        return np.stack([~np.isin(lab, z) for lab, z in zip(self.labels, S)]).mean(axis=0)
+
+    def allocation(self, relabelling, samples) -> np.ndarray:
+        """As Prediction.allocation, except that a label that is not one of the sample's training names (a cluster that new
+        points opened) counts in column 0."""
+        return _allocation(self.labels, relabelling, samples, unknown_raises=False)
+
+
+def _allocation(labels, relabelling, samples, unknown_raises: bool) -> np.ndarray:
+    """Prediction.allocation and JointPrediction.allocation: label 0 always counts in column 0; a positive label that is not a
+    name of the sample raises or counts there too."""
+    S = _label_matrix(samples)
+    m, q = labels.shape
+    if S.shape[0] != m or relabelling.maps.shape[0] != m:
+        raise ValueError(f"samples and the relabelling must be of the {m} samples of the prediction")
+    names = np.asarray(relabelling.pivot_labels, dtype=np.int64)
+    counts = np.zeros((q, len(names) + 1), np.int64)
+    for s in range(m):
+        own = np.unique(S[s])
+        lab = labels[s]
+        t = np.searchsorted(own, lab)
+        known = (lab > 0) & (t < len(own))
+        known &= own[np.minimum(t, len(own) - 1)] == lab
+        if unknown_raises and not np.all(known | (lab == 0)):
+            raise ValueError(f"a label of the prediction is not a label of sample {s + 1}")
+        to = np.where(known, relabelling.maps[s][np.where(known, t, 0)], 0)
+        col = np.where(to > 0, np.searchsorted(names, np.maximum(to, 1)) + 1, 0)
+        counts[np.arange(q), col] += 1
+    return counts / float(m)
 
 
 def _label_matrix(samples) -> np.ndarray:
@@ -96,17 +138,10 @@ def _params_dict(params) -> dict:
     return P
 
 
-def predict(result_or_samples, Dnew=None, *, new_points=None, points=None, r=None, p=None, params=None, seed: int = 0,
-            scores: bool = False, device: int = 0) -> Prediction:
-    """Allocate new observations to the clusters of every posterior sample.
-
-    result_or_samples: an MCMCResult (its clusts, r, p and params are used) or an m×n label matrix with r, p (one per
-    sample) and params (a PriorHyperparamsList or a dict of the likelihood hyperparameters) given.  The new data: Dnew
-    (q×n, distances of every new observation to every training observation) or new_points with the training points, one
-    observation per row — the distances are then computed on the host in row chunks, so q×n never exists at once; every new
-    point is quantised by itself and keyed by its own index, so the chunked result equals the unchunked one."""
+def _sample_inputs(result_or_samples, r, p, params):
+    """(S, r, p, P) of an MCMCResult or of a label matrix with r, p and params given, checked"""
     S = _label_matrix(result_or_samples)
-    m, n = S.shape
+    m = S.shape[0]
     res = result_or_samples
     r = getattr(res, "r", None) if r is None else r
     p = getattr(res, "p", None) if p is None else p
@@ -121,7 +156,20 @@ def predict(result_or_samples, Dnew=None, *, new_points=None, points=None, r=Non
         raise ValueError("r must be positive and finite")
     if not (np.all(p > 0) and np.all(p < 1)):
         raise ValueError("p must lie in (0, 1)")
-    P = _params_dict(params)
+    return S, r, p, _params_dict(params)
+
+
+def predict(result_or_samples, Dnew=None, *, new_points=None, points=None, r=None, p=None, params=None, seed: int = 0,
+            scores: bool = False, device: int = 0) -> Prediction:
+    """Allocate new observations to the clusters of every posterior sample.
+
+    result_or_samples: an MCMCResult (its clusts, r, p and params are used) or an m×n label matrix with r, p (one per
+    sample) and params (a PriorHyperparamsList or a dict of the likelihood hyperparameters) given.  The new data: Dnew
+    (q×n, distances of every new observation to every training observation) or new_points with the training points, one
+    observation per row — the distances are then computed on the host in row chunks, so q×n never exists at once; every new
+    point is quantised by itself and keyed by its own index, so the chunked result equals the unchunked one."""
+    S, r, p, P = _sample_inputs(result_or_samples, r, p, params)
+    m, n = S.shape
     if (Dnew is None) == (new_points is None):
         raise ValueError("give either Dnew or new_points (with points)")
     Kmax = int(max(len(np.unique(row)) for row in S)) if scores else 0
@@ -161,3 +209,64 @@ def predict(result_or_samples, Dnew=None, *, new_points=None, points=None, r=Non
             sc[:, i0:i0 + step] = out["scores"]
         ms += out["kernel_ms"]
     return Prediction(labels, maps, sc, ms)
+
+
+def predict_joint(result_or_samples, Dnew=None, Dnn=None, *, new_points=None, points=None, sweeps: int = 2, r=None, p=None,
+                  params=None, seed: int = 0, device: int = 0) -> JointPrediction:
+    """Allocate new observations to the clusters of every posterior sample jointly: under every sample the new observations
+    are allocated one after the other in the order given, each seeing the training labels and the new observations before
+    it, and then visited again in `sweeps` Gibbs passes with every other new observation allocated — so a group that the
+    training data missed ends up as one new cluster instead of as many singletons as it has members.
+
+    result_or_samples, r, p, params as for predict.  The new data: Dnew (q×n, new to training observations) with Dnn (q×q,
+    symmetric, distances among the new observations; the diagonal is ignored), or new_points with the training points, one
+    observation per row — both blocks are then computed on the host.  A sample's clusters and the new observations must fit
+    4096 slots together (K_s + q <= 4096); allocate more observations in blocks, each block's extended_samples being the
+    next block's training samples (with its Dnew extended by the earlier blocks)."""
+    S, r, p, P = _sample_inputs(result_or_samples, r, p, params)
+    m, n = S.shape
+    if int(sweeps) != sweeps or sweeps < 0:
+        raise ValueError("sweeps must be an integer >= 0")
+    if (Dnew is None) == (new_points is None):
+        raise ValueError("give either Dnew with Dnn or new_points (with points)")
+    if Dnew is not None:
+        if points is not None:
+            raise ValueError("points goes with new_points, not with Dnew")
+        if Dnn is None:
+            raise ValueError("Dnew needs Dnn, the distances among the new observations")
+        Dnew = np.ascontiguousarray(Dnew, dtype=np.float64)
+        if Dnew.ndim != 2 or Dnew.shape[1] != n or Dnew.shape[0] < 1:
+            raise ValueError(f"Dnew must be a q×n matrix with n = {n} columns and q >= 1")
+        if not (np.all(np.isfinite(Dnew)) and np.all(Dnew > 0)):
+            raise ValueError("Dnew must be finite and positive")
+        Dnn = np.ascontiguousarray(Dnn, dtype=np.float64)
+        q = Dnew.shape[0]
+        if Dnn.shape != (q, q):
+            raise ValueError(f"Dnn must be a q×q matrix with q = {q}")
+        off = ~np.eye(q, dtype=bool)
+        if not (np.all(np.isfinite(Dnn[off])) and np.all(Dnn[off] > 0)):
+            raise ValueError("Dnn must be finite and positive off the diagonal")
+        if not np.array_equal(Dnn[off], Dnn.T[off]):
+            raise ValueError("Dnn must be symmetric")
+    else:
+        if Dnn is not None:
+            raise ValueError("Dnn goes with Dnew, not with new_points")
+        if points is None:
+            raise ValueError("new_points needs the training points")
+        X = np.ascontiguousarray(points, dtype=np.float64)
+        Y = np.ascontiguousarray(new_points, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] != n:
+            raise ValueError(f"points must hold the n = {n} training observations, one per row")
+        if Y.ndim != 2 or Y.shape[1] != X.shape[1] or Y.shape[0] < 1:
+            raise ValueError("new_points must hold q >= 1 observations of the training points' dimension, one per row")
+        if not (np.all(np.isfinite(X)) and np.all(np.isfinite(Y))):
+            raise ValueError("points must be finite")
+        q = Y.shape[0]
+        Dnew = np.sqrt(((Y[:, None, :] - X[None, :, :]) ** 2).sum(axis=2))
+        Dnn = np.sqrt(((Y[:, None, :] - Y[None, :, :]) ** 2).sum(axis=2))
+        if not np.all(Dnew > 0):
+            raise ValueError("a new point coincides with a training point: the distances must be positive")
+        if not np.all(Dnn[~np.eye(q, dtype=bool)] > 0):
+            raise ValueError("two new points coincide: the distances must be positive")
+    out = _lib.predict_joint(Dnew, Dnn, S, r, p, P, sweeps=int(sweeps), seed=seed, device=device)
+    return JointPrediction(out["labels"], out["first"], out["K"], out["moves"], out["kernel_ms"])

@@ -1,7 +1,9 @@
-"""Kernel and wall time of predict (rc_predict; csrc/predict.inc.hip) and, for scale, of its NumPy restatement on the CPU.
+"""Kernel and wall time of predict (rc_predict; csrc/predict.inc.hip) and, for scale, of its NumPy restatement on the CPU;
+with --joint also of the joint predict (rc_predict_joint; csrc/predictjoint.inc.hip) on the same inputs.
 
     python tools/time_predict.py                       # n = 8192, K = 50, m = 1000 samples, q = 1024 new points
     python tools/time_predict.py --n 2048 --q 256 --reps 3
+    python tools/time_predict.py --joint --sweeps 0 2  # rc_predict, then rc_predict_joint with 0 and with 2 Gibbs passes
 
 Inputs (seed 0): n + q observations from K Gaussian groups in 8 dimensions, the last q held out; the m samples are the true
 training labels with 2 % of the points relabelled at random in each; r and p drawn once per sample; the likelihood
@@ -10,7 +12,12 @@ that loads the module and a first full call: `reps` calls of rc_predict on the q
 library).  kernel_ms is the device time of the call's kernels (events around them), wall the whole call: the host's checks,
 quantisation and sorted orders, the copies, the kernels.  The NumPy reference (tests/predict_ref.py: np.add.at for the sums,
 math.log1p per candidate, the oracle's uniforms) is timed on a few (sample, point) cases and extrapolated to q·m; the device's
-labels of those cases are compared with it.  One JSON line per measurement."""
+labels of those cases are compared with it.  --joint: after rc_predict, `reps` calls of rc_predict_joint per value of --sweeps
+on the same distances and the q×q distances among the new points; its kernel_ms covers the base sums (k_predict_sums) and
+k_joint; a sample's workgroup makes (sweeps + 1)·q visits one after the other, all samples at once, so kernel_ms over that
+number is the time of one visit.  Its NumPy reference (tests/predict_joint_ref.py) is timed on the first visits of sample 0
+and extrapolated to a sample and to the call; the device's labels of those visits are compared with it.  One JSON line per
+measurement."""
 import argparse
 import json
 import os
@@ -44,6 +51,48 @@ def distances(A, B, rows=64):
     return out
 
 
+def joint(a, Dnew, Dnn, S, r, p, P):
+    for sweeps in a.sweeps:
+        out = _lib.predict_joint(Dnew, Dnn, S, r, p, P, sweeps=sweeps)          # first call at the timed shape
+        walls, kms = [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            o = _lib.predict_joint(Dnew, Dnn, S, r, p, P, sweeps=sweeps)
+            walls.append(time.perf_counter() - t0)
+            kms.append(o["kernel_ms"])
+            assert np.array_equal(o["labels"], out["labels"])
+        visits = (sweeps + 1) * a.q
+        Ktr = np.array([len(np.unique(z)) for z in S])
+        print(json.dumps(dict(what="rc_predict_joint", n=a.n, q=a.q, m=a.m, K=a.K, sweeps=sweeps, reps=a.reps,
+                              kernel_ms_median=round(statistics.median(kms), 3), kernel_ms_min=round(min(kms), 3),
+                              kernel_ms_max=round(max(kms), 3), us_per_visit=round(statistics.median(kms) * 1e3 / visits, 3),
+                              visits_per_s=round(visits * a.m / (statistics.median(kms) * 1e-3), 0),
+                              wall_s_median=round(statistics.median(walls), 4), wall_s_min=round(min(walls), 4),
+                              wall_s_max=round(max(walls), 4), new_clusters_mean=round(float((out["K"] - Ktr).mean()), 3),
+                              moves_per_pass=[round(float(x), 2) for x in out["moves"].mean(axis=0)])), flush=True)
+    if a.no_host:
+        return
+    import oracle_lib as O
+    import predict_joint_ref as J
+    k = min(a.ref_visits, a.q)
+    logDnew, logDnn = J.log_blocks(Dnew, Dnn)
+    given = _lib.predict_joint(Dnew, Dnn, S[:1], r[:1], p[:1], P, sweeps=0, logDnew=logDnew, logDnn=logDnn)
+    Dq, Lq, eD, eL = J.quantise_rows(Dnew[:k], Dnn[:k], logDnew[:k], logDnn[:k])
+    A = O.size_table(P, a.n + a.q)
+    y = np.zeros(a.q, np.int64)
+    t0 = time.perf_counter()
+    for i in range(k):
+        cands, newlab, _, sc = J.visit_scores(i, S[0], y, Dq[i], Lq[i], eD[i], eL[i], float(r[0]), float(p[0]), P, A)
+        t, _ = J.draw(cands, sc, 0, 0, i)
+        y[i] = cands[t] if cands[t] else newlab
+    per_visit = (time.perf_counter() - t0) / k
+    agree = int((y[:k] == given["first"][0, :k]).sum())
+    print(json.dumps(dict(what="numpy joint reference", visits=k, s_per_visit=round(per_visit, 6),
+                          extrapolated_s_per_sample={str(sw): round(per_visit * (sw + 1) * a.q, 2) for sw in a.sweeps},
+                          extrapolated_s={str(sw): round(per_visit * (sw + 1) * a.q * a.m, 1) for sw in a.sweeps},
+                          device_labels_equal=f"{agree}/{k}")), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=8192)
@@ -54,6 +103,9 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--ref-cases", type=int, default=6)
     ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--joint", action="store_true")
+    ap.add_argument("--sweeps", type=int, nargs="+", default=[2])
+    ap.add_argument("--ref-visits", type=int, default=24)
     a = ap.parse_args()
     tr, new, truth, S, r, p = planted(a.n, a.q, a.K, a.m, a.noise)
     sub = min(a.n, 1024)
@@ -75,6 +127,8 @@ def main():
                           gathers_per_s=round(adds / (statistics.median(kms) * 1e-3), 0), wall_s_median=round(statistics.median(walls), 4),
                           wall_s_min=round(min(walls), 4), wall_s_max=round(max(walls), 4), map_equals_truth=round(hit, 4),
                           new_cluster_share=round(float((out["labels"] == 0).mean()), 6))), flush=True)
+    if a.joint:
+        joint(a, Dnew, distances(new, new), S, r, p, P)
     if a.no_host:
         return
     import oracle_lib as O

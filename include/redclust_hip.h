@@ -826,6 +826,51 @@ int32_t rc_score_labellings(rc_ctx *ctx, int64_t L, const int64_t *labels /* L×
 int32_t rc_loglik_from_blocks(int64_t n, int64_t K, const int64_t *sizes /* K */, const int64_t *blocks /* K(K+1)/2 × 4 */,
                               int32_t eD, int32_t eL, const rc_params *params, double *out);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Cluster profiles: the medoid of every cluster and, for every point, the sum of its distances within its own cluster and
+ * its neighbour cluster — the integers the silhouette width (Rousseeuw 1987) is made of — for each of L given labellings,
+ * against the context's fixed-point D as it is (64- or 32-bit storage, the current internal point order read through its
+ * index map).  logD plays no part: a context that derives it computes no logarithm here.  DESIGN.md §8 "Cluster profiles".
+ *
+ * Dq is the integer matrix with D = Dq·2^-eD, in the caller's point order (what rc_get_matrix returns).  The diagonal entry
+ * Dq[i][i] never counts, whatever the context holds there.  Labelling l has its K_l clusters in ascending label order, slots
+ * k = 0..K_l−1 of sizes n_k; A(i) is the slot of point i.
+ *   within[l][i]    = Σ_{j in A(i), j != i} Dq[i][j]                          (0 for a singleton)
+ *   S_t(i)          = Σ_{j in t} Dq[i][j] for t != A(i).  The neighbour cluster of i is the slot t != A(i) of minimum mean
+ *                     S_t(i)/n_t.  Means are compared exactly, S_t·n_u against S_u·n_t in 128 bits; ties go to the lower
+ *                     slot, that is the smaller label.
+ *   nearest[l][i]   = S_t(i) of the neighbour cluster, neighbour[l][i] = its label, in the caller's names.  With K_l = 1
+ *                     both are 0.
+ *   medoid of cluster k: its member i of minimum within[l][i]; ties go to the smallest point index.  Reported 1-based, as
+ *                     rc_kmedoids reports medoids, with its within.
+ * The silhouette width is host arithmetic on these: ā = within/(n_A − 1), b̄ = nearest/n_neighbour, s = (b̄ − ā)/max(ā, b̄),
+ * and s = 0 for a singleton, for K_l = 1 and when max(ā, b̄) = 0; the scale 2^-eD cancels.
+ * Every output is an exact integer and a pure function of (Dq, labelling): bit for bit the same whatever L is, however the
+ * call is chunked, whichever other labellings share it and whatever the context's storage.  The matrix is read once per
+ * chunk of labellings, never once per labelling.
+ *
+ * K_out (may be NULL): the K_l.  medoids_out, medoid_within_out (each may be NULL): per labelling in turn its K_l clusters
+ * in ascending label order; medoids_len is the caller's count and must equal Σ_l K_l (0 when both are NULL).  within_out,
+ * nearest_out, neighbour_out (each may be NULL): L×n.  eD_out (may be NULL): the context's exponent.  kernel_ms (may be
+ * NULL): device time of the call's kernels.
+ *
+ * The call waits for the context's streams first and leaves the chain state, the layout, the row-sum tables, the
+ * co-clustering counts and the choice of kernels untouched; a context with no state and no parameters set is fine.
+ *
+ * Errors, all before any device work (no output is written).  RC_ERR_ARG: ctx or labels NULL; L < 1; a label outside 1..n
+ * (the message names the labelling and the position); a medoids_len that does not match.  RC_ERR_CAPACITY: n > 32767,
+ * L·n >= 2^31, a labelling of more than 4096 clusters.  The rows and the labellings go through a device workspace of about
+ * 1 GiB in chunks.  RC_PROFILE_ROWS_GLOBAL=1 in the environment (read at every call) makes the sums gather from the staged
+ * rows in global memory instead of LDS, as n > 10240 does, and RC_PROFILE_WORKSPACE_KIB=<k> shrinks the workspace so that
+ * small calls are chunked — the same integers either way; for tests.
+ * ------------------------------------------------------------------------------------------------------------- */
+int32_t rc_cluster_profiles(rc_ctx *ctx, int64_t L, const int64_t *labels /* L×n, labels 1..n */,
+                            int64_t *K_out /* L or NULL */,
+                            int64_t *medoids_out /* medoids_len or NULL, 1-based */,
+                            int64_t *medoid_within_out /* medoids_len or NULL */, int64_t medoids_len,
+                            int64_t *within_out /* L×n or NULL */, int64_t *nearest_out /* L×n or NULL */,
+                            int64_t *neighbour_out /* L×n or NULL */, int32_t *eD_out, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -808,4 +808,74 @@ end
 
 export scorelabellings, mapestimate
 
+"""
+    clusterprofiles(HIPBackend(), data, labellings; points = true) -> (K, medoids, medoid_within, within, nearest, neighbour, silhouette, eD, kernel_ms)
+
+The medoids, silhouette widths and neighbour clusters of each of `L` labellings (a vector of label vectors) against the
+dissimilarities of `data`, on the GPU (rc_cluster_profiles), in exact integers of `Dq = D·2^eD`; the diagonal never counts.
+With the clusters of a labelling in ascending label order: `medoids[l][k]` is the member of cluster `k` with the least
+`within` (the sum of its distances to the other members), the smallest index on ties, and `medoid_within[l][k]` that sum.
+Per point (`L×n`, or `nothing` with `points = false`): `within`; `neighbour`, the label of the other cluster of least mean
+distance — means compared exactly, the smaller label on ties, 0 with one cluster — and `nearest`, the sum of the distances to
+its members; `silhouette = (b̄ − ā)/max(ā, b̄)` with `ā = within/(n_A − 1)` and `b̄ = nearest/n_neighbour`, 0 for a singleton,
+for one cluster and when `max(ā, b̄) = 0`.
+"""
+function clusterprofiles(b::HIPBackend, data::MCMCData, labellings::Vector{<:AbstractVector{<:Integer}}; points::Bool = true)
+    n = size(data.D, 1)
+    L = length(labellings)
+    labels = Matrix{Int64}(undef, n, L)                           # column l = labelling l: row-major L×n for the library
+    for l in 1:L
+        length(labellings[l]) == n || throw(ArgumentError("Length of the input vectors must be equal."))
+        labels[:, l] .= labellings[l]
+    end
+    Ks = [length(unique(labellings[l])) for l in 1:L]
+    ktot = sum(Ks)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = ccall((:rc_create, LIB), Int32,
+               (Int64, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Int32, Int64, Ref{Ptr{Cvoid}}),
+               n, data.D, Ptr{Cdouble}(C_NULL), 64, b.device, 0, h)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    ctx = h[]
+    K = Vector{Int64}(undef, L); med = Vector{Int64}(undef, ktot); medw = Vector{Int64}(undef, ktot)
+    within = Matrix{Int64}(undef, n, points ? L : 0); nearest = similar(within); neighbour = similar(within)
+    eD = Int32[0]; ms = Cdouble[0]
+    try
+        rc = GC.@preserve within nearest neighbour ccall((:rc_cluster_profiles, LIB), Int32,
+                   (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64},
+                    Ptr{Int32}, Ptr{Cdouble}),
+                   ctx, L, labels, K, med, medw, ktot, points ? pointer(within) : Ptr{Int64}(C_NULL),
+                   points ? pointer(nearest) : Ptr{Int64}(C_NULL), points ? pointer(neighbour) : Ptr{Int64}(C_NULL), eD, ms)
+        check(ctx, rc)
+    finally
+        ccall((:rc_destroy, LIB), Int32, (Ptr{Cvoid},), ctx)
+    end
+    off = cumsum([0; Ks])
+    medoids = [med[off[l]+1:off[l+1]] for l in 1:L]
+    medoid_within = [medw[off[l]+1:off[l+1]] for l in 1:L]
+    points || return (K = K, medoids = medoids, medoid_within = medoid_within, within = nothing, nearest = nothing,
+                      neighbour = nothing, silhouette = nothing, eD = eD[1], kernel_ms = ms[1])
+    sil = zeros(Float64, L, n)
+    for l in 1:L
+        z = labellings[l]
+        sizes = Dict{Int64,Int}()
+        for x in z
+            sizes[x] = get(sizes, x, 0) + 1
+        end
+        for i in 1:n
+            na = sizes[z[i]]
+            (na > 1 && neighbour[i, l] > 0) || continue
+            a = within[i, l] / (na - 1); bb = nearest[i, l] / sizes[neighbour[i, l]]
+            hi = max(a, bb)
+            sil[l, i] = hi > 0 ? (bb - a) / hi : 0.0
+        end
+    end
+    return (K = K, medoids = medoids, medoid_within = medoid_within, within = permutedims(within), nearest = permutedims(nearest),
+            neighbour = permutedims(neighbour), silhouette = sil, eD = eD[1], kernel_ms = ms[1])
+end
+
+clusterprofiles(b::HIPBackend, data::MCMCData, result::MCMCResult; points::Bool = true) =
+    clusterprofiles(b, data, [Vector{Int64}(c) for c in result.clusts]; points = points)
+
+export clusterprofiles
+
 end # module

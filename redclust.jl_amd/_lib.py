@@ -231,6 +231,8 @@ SIGNATURES = {
                                         C.POINTER(C.c_double)]),
     "rc_loglik_from_blocks": (C.c_int32, [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RcParams),
                                           C.POINTER(C.c_double)]),
+    "rc_cluster_profiles": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rc_layout_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rc_event_overhead_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "rc_kernel_timing": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -599,6 +601,38 @@ class Context:
             per = [blocks[off[i]:off[i + 1]] for i in range(nl)]
         return dict(loglik=ll[:nl], logprior=None if lp is None else lp[:nl], logposterior=None if lp is None else ll[:nl] + lp[:nl],
                     K=K[:nl], sizes=sizes, blocks=per, eD=int(eD.value), eL=int(eL.value), kernel_ms=float(ms.value))
+
+    def profiles(self, labellings, points=True) -> dict:
+        """rc_cluster_profiles: the medoids and the per-point sums behind the silhouette of each of L labellings (L×n int64
+        labels in 1..n, or one labelling), against this context's D; its state, layout and counts are untouched and it needs
+        neither parameters nor a state.  All in exact integers of Dq = D·2^eD, the diagonal never counted.  Returns a dict:
+        K (L); labels, sizes (lists of L int64 arrays: the cluster names in ascending order and their sizes); medoids (a
+        list of L int64 arrays, 1-based: per cluster its member of least within, the smallest index on ties), medoid_within
+        (likewise, that least within); with points also within, nearest, neighbour (L×n int64: Σ Dq to the other members of
+        the own cluster; Σ Dq to the members of the neighbour cluster — the other cluster of least mean, compared exactly, the
+        smaller label on ties; that cluster's label, 0 with one cluster) — else None; eD, kernel_ms."""
+        lab = np.ascontiguousarray(labellings, dtype=np.int64)
+        if lab.ndim == 1:
+            lab = lab[None, :]
+        if lab.ndim != 2 or lab.shape[1] != self.n:
+            raise ValueError("labellings must be an L×n matrix of labels with the context's n columns")
+        nl = lab.shape[0]
+        valid = lab.size > 0 and lab.min() >= 1 and lab.max() <= self.n            # otherwise the library names the label
+        counts = [np.bincount(row, minlength=self.n + 1) for row in lab] if valid else []
+        names = [np.flatnonzero(z).astype(np.int64) for z in counts]
+        sizes = [z[z > 0].astype(np.int64) for z in counts]
+        ktot = sum(len(z) for z in sizes)
+        K = np.zeros(max(nl, 1), np.int64)
+        med, medw = np.zeros(max(ktot, 1), np.int64), np.zeros(max(ktot, 1), np.int64)
+        per = [np.zeros((max(nl, 1), self.n), np.int64) for _ in range(3)] if points else [None] * 3
+        eD, ms = C.c_int32(), C.c_double()
+        self._chk(self.L.rc_cluster_profiles(self.h, nl, lab.ctypes.data, K.ctypes.data, med.ctypes.data, medw.ctypes.data, ktot,
+                                             *(None if x is None else x.ctypes.data for x in per), C.byref(eD), C.byref(ms)))
+        off = np.concatenate([[0], np.cumsum([len(z) for z in sizes])]).astype(np.int64)
+        return dict(K=K[:nl], labels=names, sizes=sizes, medoids=[med[off[i]:off[i + 1]] for i in range(nl)],
+                    medoid_within=[medw[off[i]:off[i + 1]] for i in range(nl)],
+                    within=None if per[0] is None else per[0][:nl], nearest=None if per[1] is None else per[1][:nl],
+                    neighbour=None if per[2] is None else per[2][:nl], eD=int(eD.value), kernel_ms=float(ms.value))
 
     def layout_info(self):
         """(layouts built so far, label runs in the internal point order)"""

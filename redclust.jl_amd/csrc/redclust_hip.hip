@@ -7791,3 +7791,4 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "partdist.inc.hip"
 #include "relabel.inc.hip"
 #include "score.inc.hip"
+#include "profile.inc.hip"

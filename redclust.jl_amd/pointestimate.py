@@ -375,9 +375,34 @@ def hclustpointestimate(samples_or_counts=None, loss="VI", linkage="average", *,
     criterion="posterior": the cut of highest log-posterior under the model instead of lowest expected loss — mapestimate
     (score.py) over the maxK cuts, one device pass over the matrices of data (a Context, an MCMCData or a dissimilarity
     matrix) with params and r, p (scalars or one per cut; None: the posterior means of an MCMCResult's r and p).  info has K,
-    loglik, logprior, logposterior (per K = 1..maxK), merges, binder_num, kernel_ms, score_ms."""
-    if criterion not in ("loss", "posterior"):
-        raise ValueError("criterion must be 'loss' or 'posterior'")
+    loglik, logprior, logposterior (per K = 1..maxK), merges, binder_num, kernel_ms, score_ms.
+
+    criterion="silhouette": the best separated cut — the one of highest mean silhouette width (profiles.py: exact integer
+    sums of D on the device, the quotients on the host) among the cuts of 2..maxK clusters (one cluster has silhouette 0 by
+    convention and is not a candidate; maxK >= 2), the fewest clusters on a float tie.  One device pass over the matrix of
+    data (as above) for all cuts; it needs no params, r or p.  info has K, mean_silhouette (per K = 2..maxK), merges,
+    binder_num, kernel_ms, profile_ms."""
+    if criterion not in ("loss", "posterior", "silhouette"):
+        raise ValueError("criterion must be 'loss', 'posterior' or 'silhouette'")
+    if criterion == "silhouette":
+        from .profiles import clusterprofiles
+        if exact:
+            raise ValueError("exact=True chooses by expected loss; it does not go with criterion='silhouette'")
+        if linkage not in _LINKAGES:
+            raise ValueError("Invalid linkage specifier.")
+        if data is None:
+            raise ValueError("criterion='silhouette' needs data= (a Context, an MCMCData or a dissimilarity matrix)")
+        S, counts, m, n = _counts_input(samples_or_counts, numsamples, ctx)
+        maxK = int(maxK) if maxK else max(-(-n // 8), min(n, 2))
+        if not 2 <= maxK <= n:
+            raise ValueError("maxK must lie in 2..n with criterion='silhouette'")
+        res = _lib.hclust(counts, m, _LINKAGES[linkage], device=device, ctx=ctx, samples=S)
+        cuts = np.stack([_lib.hclust_cut(res["merges"], n, K) for K in range(2, maxK + 1)])
+        prof = clusterprofiles(data, cuts, device=device)
+        best = int(np.argmax(prof.mean_silhouette))                 # numpy's argmax is the first maximum: the fewest clusters
+        info = dict(merges=res["merges"], binder_num=res["binder_num"], kernel_ms=res["kernel_ms"],
+                    profile_ms=prof.raw["kernel_ms"], mean_silhouette=prof.mean_silhouette, K=best + 2)
+        return cuts[best].copy(), info
     if criterion == "posterior":
         from .score import mapestimate
         if exact:

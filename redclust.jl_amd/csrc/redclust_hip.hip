@@ -383,7 +383,14 @@ __global__ __launch_bounds__(256) void k_pairwise(const double *__restrict__ pts
 //   log x = k·ln2 + log c_j + log1p(r),   log1p(r) = r + r²(−1/2 + r(1/3 − r/4))   (next term r⁵/5 < 1.8e-13)
 //   Lq = k·LN2S + T_j + 2^eL·log1p(r), rounded to the integer by accumulating on the "magic" 1.5·2^52:
 //        v = fma((double)k, LN2S, T_j), T_j = rint(log c_j·2^eL) + 1.5·2^52 (integer-valued, per context);  w = fma(log1p(r), 2^eL, v);
-//        Lq = bits(w) − bits(1.5·2^52)         (|Lq| < 2^51 by the choice of eL, so v and w stay in [2^52, 2^53): unit spacing)
+//        Lq = bits(w) − bits(1.5·2^52)         (|Lq| < 2^51 by the choice of eL, so w stays in [2^52, 2^53): unit spacing)
+//   That bounds w, not v, T_j or LN2S = ln2·2^eL: those are 53-bit doubles as large as log 2·2^eL + 1.5·2^52, integers exactly only
+//   while that is below 2^53 (eL <= 51).  A matrix with max|log D| < 1/4 has eL >= 52 (every entry within [0.78, 1.28]; eL = 54 for
+//   entries within 6 % of one): T_j for c_j >= 1.133 and LN2S are then rounded to a multiple of 2 or 4 — the bias 1.5·2^52 is such
+//   a multiple and survives — and Lq is off rint(log·2^eL) by their roundings, each at most 2^-53 of log 2·2^eL + 1.5·2^52: a few
+//   times 2^(eL-53) quanta (at most 3 quanta at eL = 54), some 2^-52 in units of log D whatever eL, 1/1000 of the polynomial's
+//   1.8e-13.  Lq stays a pure function of dq, the same for every consumer (k_fold_table takes v from the very fma), which is all
+//   exactness asks (tests/test_gpu_units.py: near_one).
 // 16 VALU instructions per entry — six of them double-precision FMAs / multiplies — and one 16-byte table read (round 2's form of
 // the same idea took 23: a degree-6 polynomial, the scaling and the rounding as separate steps); the libm log is ~100.
 // ltab[j] = (2/c_j, T_j): 128 entries, rebuilt per context once eL is known (create_impl).

@@ -2448,7 +2448,7 @@ struct Tab {
     unsigned *used;  // [(n+31)/32] label occupancy bitset, bit (label-1); built when a round has changers (LDS, or V.used_scratch for large n)
     double *red_v;   // [NW][32] reduction scratch (NW = waves per block)
     int *red_pos, *red_slot;
-    int *misc;       // [0]=K [1]=smallest_empty [2]=scratch [3]=nb [4]=hi [5]=fail [6]=barrier ok [7]=slot_hi [8]=#births [9]=#effective [13]=visited [14]=#clean slots (tab_partition) [15]=#dirty [16]=hot slot of the batch (-1: none) [17]=scratch
+    int *misc;       // [0]=K [1]=smallest_empty [2]=scratch [3]=nb [4]=hi [5]=fail [6]=barrier ok [7]=slot_hi [8]=#births [9]=#effective [13]=visited [14]=#clean slots (tab_partition) [15]=#dirty [16]=hot slot of the batch (-1: none) [17]=scratch [22]=this block announced a changer in the current tentative pass (grid_barrier)
     u64 *blk_key;    // block-local minimum (first violation)
     // batch of tentative changers of the current round (identical in every block), ascending in point index
     int *bx, *bu;             // [RC_MAXB] point (original index), its internal index
@@ -2548,6 +2548,12 @@ static size_t tab_bytes(int kcap, int n, int nw, int maxb = RC_MAXB)
     return tab_layout(kcap, n, nw, off, maxb);
 }
 
+// The thread index as the resolver's code reads it: the same value, but opaque to the optimiser.  With the plain threadIdx.x the
+// compiler hoists every per-thread invariant of the round loop (LDS addresses, lane masks, 64-bit offsets: 53 dwords) to the
+// start of k_resolve, where they do not fit into the 128 registers the kernel has beside three reduction waves and go to
+// scratch — stored in the prologue, reloaded inside the rounds.  Recomputed where they are used they cost a few VALU
+// instructions and the kernel has no scratch at all (tests/test_resolver_setup_image.py).
+__device__ __forceinline__ unsigned rc_tid() { unsigned t = threadIdx.x; asm volatile("" : "+v"(t)); return t; }
 __device__ __forceinline__ double tab_base(const View &V, const SweepArgs &a, int s)
 {
     // A[s] + (log p + log(s - 1 + r)): size-only terms of mcmc.jl:223-226,240-241
@@ -2557,7 +2563,7 @@ __device__ __forceinline__ double tab_base(const View &V, const SweepArgs &a, in
 // per-slot score constants of the active slots.  All threads; ends synchronised.
 __device__ __forceinline__ void tab_bases(const View &V, const SweepArgs &a, Tab &T)
 {
-    for (int k = threadIdx.x; k < T.misc[7]; k += blockDim.x) {
+    for (int k = rc_tid(); k < T.misc[7]; k += blockDim.x) {
         const int s = T.size[k];
         if (T.label[k] > 0) {
             T.base_o[k] = tab_base(V, a, s);
@@ -2572,15 +2578,15 @@ __device__ __forceinline__ void tab_bases(const View &V, const SweepArgs &a, Tab
 __device__ __forceinline__ void tab_structural(const View &V, Tab &T)
 {
     const int nw = (V.n + 31) / 32, hi = T.misc[7];
-    for (int w = threadIdx.x; w < nw; w += blockDim.x) T.used[w] = 0u;
-    if (threadIdx.x == 0) T.misc[2] = V.n + 1;
+    for (int w = rc_tid(); w < nw; w += blockDim.x) T.used[w] = 0u;
+    if (rc_tid() == 0) T.misc[2] = V.n + 1;
     __syncthreads();
-    for (int k = threadIdx.x; k < hi; k += blockDim.x) {
+    for (int k = rc_tid(); k < hi; k += blockDim.x) {
         const int lab = T.label[k];
         if (lab > 0) atomicOr(&T.used[(lab - 1) >> 5], 1u << ((lab - 1) & 31));
     }
     __syncthreads();
-    for (int w = threadIdx.x; w < nw; w += blockDim.x) {
+    for (int w = rc_tid(); w < nw; w += blockDim.x) {
         const unsigned inv = ~T.used[w];
         if (inv) {
             const int lab = w * 32 + __ffs((int)inv);  // 1-based label
@@ -2591,10 +2597,10 @@ __device__ __forceinline__ void tab_structural(const View &V, Tab &T)
     // immaterial: the noise is keyed by label and ties between scores go to the smaller label (eval_chunk), so the label-rank
     // order of round 1 — a pass over all slots per slot — is not needed.
     {
-        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, NW = blockDim.x >> 6;
+        const int wave = rc_tid() >> 6, lane = rc_tid() & 63, NW = blockDim.x >> 6;
         int base = 0;
         for (int k0 = 0; k0 < hi; k0 += blockDim.x) {
-            const int k = k0 + threadIdx.x;
+            const int k = k0 + rc_tid();
             const bool f = k < hi && T.label[k] > 0;
             const u64 m = __ballot(f);
             if (lane == 0) T.red_pos[wave] = __popcll(m);
@@ -2606,7 +2612,7 @@ __device__ __forceinline__ void tab_structural(const View &V, Tab &T)
             __syncthreads();
         }
     }
-    if (threadIdx.x == 0) T.misc[1] = T.misc[2];
+    if (rc_tid() == 0) T.misc[1] = T.misc[2];
     __syncthreads();
 }
 
@@ -2616,13 +2622,13 @@ __device__ __forceinline__ void tab_structural(const View &V, Tab &T)
 __device__ __forceinline__ void tab_after_commit(const View &V, const SweepArgs &a, Tab &T, int nc)
 {
     const int nw = (V.n + 31) / 32, hi = T.misc[7];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, NW = blockDim.x >> 6;
-    for (int q = threadIdx.x; q < nc; q += blockDim.x) {
+    const int wave = rc_tid() >> 6, lane = rc_tid() & 63, NW = blockDim.x >> 6;
+    for (int q = rc_tid(); q < nc; q += blockDim.x) {
         const int lab = T.blab[q];                                   // (0 unless the entry is a birth or a rename)
         if (lab > 0) atomicOr(&T.used[(lab - 1) >> 5], 1u << ((lab - 1) & 31));
     }
-    if (threadIdx.x == 0) T.misc[1] = V.n + 1;
-    for (int k = threadIdx.x; k < hi; k += blockDim.x) {            // score constants (tab_bases): sizes and labels are final
+    if (rc_tid() == 0) T.misc[1] = V.n + 1;
+    for (int k = rc_tid(); k < hi; k += blockDim.x) {            // score constants (tab_bases): sizes and labels are final
         const int s = T.size[k];
         if (T.label[k] > 0) {
             T.base_o[k] = tab_base(V, a, s);
@@ -2632,13 +2638,13 @@ __device__ __forceinline__ void tab_after_commit(const View &V, const SweepArgs 
     }
     int base = 0;
     for (int k0 = 0; k0 < hi; k0 += blockDim.x) {
-        const int k = k0 + threadIdx.x;
+        const int k = k0 + rc_tid();
         const bool f = k < hi && T.label[k] > 0;
         const u64 m = __ballot(f);
         if (lane == 0) T.red_pos[wave] = __popcll(m);
         __syncthreads();
         if (k0 == 0)
-            for (int w = threadIdx.x; w < nw; w += blockDim.x) {   // smallest empty label (the bitset is final behind the barrier)
+            for (int w = rc_tid(); w < nw; w += blockDim.x) {   // smallest empty label (the bitset is final behind the barrier)
                 const unsigned inv = ~T.used[w];
                 if (inv) {
                     const int lab = w * 32 + __ffs((int)inv);
@@ -2655,12 +2661,12 @@ __device__ __forceinline__ void tab_after_commit(const View &V, const SweepArgs 
 
 __device__ __forceinline__ void tab_load(const View &V, Tab &T)
 {
-    for (int k = threadIdx.x; k < V.kcap; k += blockDim.x) {
+    for (int k = rc_tid(); k < V.kcap; k += blockDim.x) {
         T.size[k] = V.slot_size[k];
         T.label[k] = V.slot_label[k];
         T.act[k] = V.slot_act[k];
     }
-    if (threadIdx.x == 0) {
+    if (rc_tid() == 0) {
         T.misc[0] = V.sc->K;
         T.misc[1] = V.sc->smallest_empty;
         T.misc[7] = V.sc->slot_hi;
@@ -2671,12 +2677,12 @@ __device__ __forceinline__ void tab_load(const View &V, Tab &T)
 
 __device__ __forceinline__ void tab_store(const View &V, const Tab &T)
 {
-    for (int k = threadIdx.x; k < V.kcap; k += blockDim.x) {
+    for (int k = rc_tid(); k < V.kcap; k += blockDim.x) {
         V.slot_size[k] = T.size[k];
         V.slot_label[k] = T.label[k];
         V.slot_act[k] = T.act[k];
     }
-    if (threadIdx.x == 0) {
+    if (rc_tid() == 0) {
         V.sc->K = T.misc[0];
         V.sc->smallest_empty = T.misc[1];
         V.sc->slot_hi = T.misc[7];
@@ -2687,33 +2693,33 @@ __device__ __forceinline__ void tab_store(const View &V, const Tab &T)
 // the two halves of snapshot_labels for the resolver's epilogue: the copy by all blocks, the run count by one
 __device__ __forceinline__ void snapshot_copy_grid(const View &V, int g, int G)
 {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < V.n; i += G * blockDim.x) V.snap[g][i] = V.slot_of[i];
+    for (int i = blockIdx.x * blockDim.x + rc_tid(); i < V.n; i += G * blockDim.x) V.snap[g][i] = V.slot_of[i];
 }
 __device__ __forceinline__ void snapshot_runs(const View &V, int *lds_cnt)
 {
-    if (threadIdx.x == 0) *lds_cnt = 0;
+    if (rc_tid() == 0) *lds_cnt = 0;
     __syncthreads();
     int mine = 0;
-    for (int i = threadIdx.x; i < V.n; i += blockDim.x) mine += (i == 0) || (V.slot_of[i] != V.slot_of[i - 1]);
+    for (int i = rc_tid(); i < V.n; i += blockDim.x) mine += (i == 0) || (V.slot_of[i] != V.slot_of[i - 1]);
     atomicAdd(lds_cnt, mine);
     __syncthreads();
-    if (threadIdx.x == 0) { V.sc->runs = *lds_cnt; V.hsum->runs = *lds_cnt; }
+    if (rc_tid() == 0) { V.sc->runs = *lds_cnt; V.hsum->runs = *lds_cnt; }
     __syncthreads();
 }
 
 __device__ __forceinline__ void snapshot_labels(const View &V, int g, int *lds_cnt)
 {
-    if (threadIdx.x == 0) *lds_cnt = 0;
+    if (rc_tid() == 0) *lds_cnt = 0;
     __syncthreads();
     int mine = 0;
-    for (int i = threadIdx.x; i < V.n; i += blockDim.x) {
+    for (int i = rc_tid(); i < V.n; i += blockDim.x) {
         const int s = V.slot_of[i];
         V.snap[g][i] = s;
         mine += (i == 0) || (s != V.slot_of[i - 1]);
     }
     atomicAdd(lds_cnt, mine);
     __syncthreads();
-    if (threadIdx.x == 0) { V.sc->runs = *lds_cnt; V.hsum->runs = *lds_cnt; }
+    if (rc_tid() == 0) { V.sc->runs = *lds_cnt; V.hsum->runs = *lds_cnt; }
     __syncthreads();
 }
 
@@ -2722,11 +2728,11 @@ __device__ __forceinline__ void snapshot_labels(const View &V, int g, int *lds_c
 __device__ __forceinline__ void write_summary(const View &V, int n_changes, int n_rounds, bool tables = true)
 {
     if (tables)
-        for (int k = threadIdx.x; k < V.kcap; k += blockDim.x) {
+        for (int k = rc_tid(); k < V.kcap; k += blockDim.x) {
             V.hsum->size_label[2 * k] = V.slot_size[k];
             V.hsum->size_label[2 * k + 1] = V.slot_label[k];
         }
-    if (threadIdx.x == 0) {
+    if (rc_tid() == 0) {
         V.hsum->K = V.sc->K;
         V.hsum->n_changes = n_changes;
         V.hsum->n_rounds = n_rounds;
@@ -2744,7 +2750,7 @@ __device__ __forceinline__ void write_summary(const View &V, int n_changes, int 
 struct MoveList { const int *mv; int count; int gens[2]; int ngens; };
 __global__ __launch_bounds__(256) void k_apply_moves(View V, MoveList ML)
 {
-    const int i = (blockIdx.x * 256 + threadIdx.x) * 2;
+    const int i = (blockIdx.x * 256 + rc_tid()) * 2;
     if (i >= V.ld) return;
     for (int m = 0; m < ML.count; ++m) {
         const int x = ML.mv[3 * m], a = ML.mv[3 * m + 1], b = ML.mv[3 * m + 2];
@@ -2779,21 +2785,21 @@ __global__ __launch_bounds__(1024) void k_derive(View V, int rebuild_perm)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Tab T = tab_carve(smem, V.kcap, V.n, 1);
     if (V.n > RC_USED_LDS_MAX_N) T.used = V.used_scratch;   // one block
-    for (int k = threadIdx.x; k < V.kcap; k += blockDim.x) { T.size[k] = V.slot_size[k]; T.label[k] = V.slot_label[k]; T.act[k] = 0; }
-    if (threadIdx.x == 0) { T.misc[0] = V.sc->K; T.misc[7] = V.sc->slot_hi; }
+    for (int k = rc_tid(); k < V.kcap; k += blockDim.x) { T.size[k] = V.slot_size[k]; T.label[k] = V.slot_label[k]; T.act[k] = 0; }
+    if (rc_tid() == 0) { T.misc[0] = V.sc->K; T.misc[7] = V.sc->slot_hi; }
     __syncthreads();
     tab_structural(V, T);
     tab_store(V, T);
     __syncthreads();
     snapshot_labels(V, 0, &T.misc[2]);
-    for (int i = threadIdx.x; i < V.n; i += blockDim.x) V.snap[1][i] = V.snap[0][i];
+    for (int i = rc_tid(); i < V.n; i += blockDim.x) V.snap[1][i] = V.snap[0][i];
     __syncthreads();
     write_summary(V, 0, 0);
     __syncthreads();
     if (!rebuild_perm) return;
     int *off = (int *)smem, *cur = off + V.kcap;
     build_perm_block(V, 0, off, cur);
-    for (int p = threadIdx.x; p < V.n; p += blockDim.x) { V.perm[1][p] = V.perm[0][p]; V.pslot[1][p] = V.pslot[0][p]; }
+    for (int p = rc_tid(); p < V.n; p += blockDim.x) { V.perm[1][p] = V.perm[0][p]; V.pslot[1][p] = V.pslot[0][p]; }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2931,8 +2937,8 @@ __device__ __forceinline__ void eval_chunk(const View &V, const SweepArgs &a, Ta
                            int chunk, int cidx /* chunk = blockIdx.x + cidx G */, int lo, int hi, int mode, int nb, u64 *cword, unsigned *rec, unsigned stamp, int cmode,
                            u64 *cword_next = nullptr, unsigned *rec_next = nullptr, unsigned stamp_next = 0u)
 {
-    const int pt = threadIdx.x & (RC_PTS - 1), st = threadIdx.x >> RC_PTS_LOG2, NS = blockDim.x >> RC_PTS_LOG2;
-    const int wave = threadIdx.x >> 6, NW = blockDim.x >> 6;
+    const int pt = rc_tid() & (RC_PTS - 1), st = rc_tid() >> RC_PTS_LOG2, NS = blockDim.x >> RC_PTS_LOG2;
+    const int wave = rc_tid() >> 6, NW = blockDim.x >> 6;
     const int i = chunk * RC_PTS + pt;
     const bool valid = (i < V.n) && (i > lo) && (i <= hi);
 #ifdef RC_PROF_EVAL
@@ -2961,7 +2967,7 @@ __device__ __forceinline__ void eval_chunk(const View &V, const SweepArgs &a, Ta
     const int hot = (mode == 1) ? T.misc[16] : -1;
     long long *const hotacc = (long long *)T.red_v + 4 * pt;
     if (hot >= 0) {
-        if (threadIdx.x < 4 * RC_PTS) ((long long *)T.red_v)[threadIdx.x] = 0;
+        if (rc_tid() < 4 * RC_PTS) ((long long *)T.red_v)[rc_tid()] = 0;
         __syncthreads();
         if (valid && j > 0) hot_accumulate(V, T, hot, u, j, st, NS, hotacc);
         __syncthreads();
@@ -3182,7 +3188,7 @@ __device__ __forceinline__ void eval_chunk(const View &V, const SweepArgs &a, Ta
         const int op = __shfl_xor(bestpos, off), os = __shfl_xor(bestslot, off);
         best_merge(bestv, bestpos, bestslot, ov, op, os);
     }
-    if ((threadIdx.x & 63) < RC_PTS) {
+    if ((rc_tid() & 63) < RC_PTS) {
         T.red_v[wave * RC_PTS + pt] = bestv;
         T.red_pos[wave * RC_PTS + pt] = bestpos;
         T.red_slot[wave * RC_PTS + pt] = bestslot;
@@ -3190,7 +3196,7 @@ __device__ __forceinline__ void eval_chunk(const View &V, const SweepArgs &a, Ta
     __syncthreads();
     if (wave == 0) {
         // lane l: point l % RC_PTS, wave group l / RC_PTS (waves g, g + 64 / RC_PTS, ...); then the groups by shuffles
-        const int grp = (int)(threadIdx.x & 63) >> RC_PTS_LOG2, half = grp;   // (half == 0: the lanes that end up holding a point's result)
+        const int grp = (int)(rc_tid() & 63) >> RC_PTS_LOG2, half = grp;   // (half == 0: the lanes that end up holding a point's result)
         double bv = -INFINITY;
         int bp = 0x7fffffff, bs = -2;
         for (int w = grp; w < NW; w += 64 / RC_PTS) best_merge(bv, bp, bs, T.red_v[w * RC_PTS + pt], T.red_pos[w * RC_PTS + pt], T.red_slot[w * RC_PTS + pt]);
@@ -3216,7 +3222,10 @@ __device__ __forceinline__ void eval_chunk(const View &V, const SweepArgs &a, Ta
             const u64 m = __ballot(changed) & ((1ull << RC_PTS) - 1ull);
             if (m) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the records are out before the mask that announces them
-                if (threadIdx.x == 0) __hip_atomic_store(cword + chunk, ((u64)stamp << 32) | m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (rc_tid() == 0) {
+                    __hip_atomic_store(cword + chunk, ((u64)stamp << 32) | m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    T.misc[22] = 1;   // ... and the block says so when it arrives at the pass's barrier (grid_barrier)
+                }
             }
         } else {
             // The guess this draw is checked against is what the batch says the point does: its entry (the slot it joins; "new
@@ -3236,7 +3245,7 @@ __device__ __forceinline__ void eval_chunk(const View &V, const SweepArgs &a, Ta
             // tentative pass, see resolve_body)
             const u64 m = __ballot(changed) & ((1ull << RC_PTS) - 1ull);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (threadIdx.x == 0) __hip_atomic_store(cword_next + chunk, ((u64)stamp_next << 32) | m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (rc_tid() == 0) __hip_atomic_store(cword_next + chunk, ((u64)stamp_next << 32) | m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     __syncthreads();
@@ -3253,15 +3262,25 @@ __device__ __forceinline__ void eval_chunk(const View &V, const SweepArgs &a, Ta
 // group counters (blockIdx & 7), the last of a group on the top counter, the last of all publishes the barrier number in
 // the eight release words the groups poll.  Returning atomics on one address serialise at ≈25 ns each — 256 blocks on one
 // counter were 5-6 µs per barrier, twice per round; now 32 + 8 in sequence, and the polls no longer queue behind the arrivals.
+// The FIRST barrier of a sweep — the one that ends the tentative pass — also carries one bit per block: "I announced a changer in
+// this pass" (T.misc[22], set by eval_chunk where it stores a non-empty chunk word).  The bit rides in the arrival itself, so it
+// is in the counter whenever the arrival is, and every block learns whether ANYBODY announced from the release word it polls
+// anyway: no load and no returning atomic beyond the ones a plain barrier does, for the last arriver either.  The counters stay
+// 32-bit words: arrivals in the low 24 bits (compared modulo 2^24: exact, the count moves by `members` per barrier), the bits
+// above them used at barrier 1 only — a group's announcers, then the groups with one — and bit 31 of that barrier's release
+// word says "somebody".  (A first version carried the bit at every barrier in the high halves of 64-bit counters; the moving
+// regime of bench.py, five or six barriers a sweep, was 2-4 % slower with it.)  Returns 0 (timed out), 1 (barrier 1 passed and
+// nobody announced) or 3.  A wrong "somebody" would cost a pass over the chunk words, a wrong "nobody" a move: the bit is set
+// and sent by the same thread.
 #define RC_BAR_GROUPS 8
 #define RC_BAR_STRIDE 32                      // unsigneds per line
 #define RC_BAR_WORDS ((2 * RC_BAR_GROUPS + 1) * RC_BAR_STRIDE)
-__device__ __forceinline__ bool grid_barrier(const View &V, Tab &T, unsigned *arrive, int G, unsigned nbar, u64 my_key, u64 *key_word)
+__device__ __forceinline__ int grid_barrier(const View &V, Tab &T, unsigned *arrive, int G, unsigned nbar, u64 my_key, u64 *key_word)
 {
     int &sh_ok = T.misc[6];
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (rc_tid() == 0) {
         if (my_key != RC_KEY_NONE) {
             const u64 old = atomicMin(key_word, my_key);
             asm volatile("" ::"v"((unsigned)old));  // data dependence: the min has been performed before we arrive
@@ -3270,19 +3289,30 @@ __device__ __forceinline__ bool grid_barrier(const View &V, Tab &T, unsigned *ar
         const unsigned members = (unsigned)((G - g + RC_BAR_GROUPS - 1) / RC_BAR_GROUPS);   // blocks b < G with b % 8 == g
         unsigned *grp = arrive + g * RC_BAR_STRIDE, *top = arrive + RC_BAR_GROUPS * RC_BAR_STRIDE;
         unsigned *rel = arrive + (RC_BAR_GROUPS + 1) * RC_BAR_STRIDE;
-        if (__hip_atomic_fetch_add(grp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == members * nbar)
-            if (__hip_atomic_fetch_add(top, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == (unsigned)ngroups * nbar)
-                for (int q = 0; q < ngroups; ++q) __hip_atomic_store(rel + q * RC_BAR_STRIDE, nbar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        unsigned spins = 0;
+        constexpr unsigned CNT = 0x00FFFFFFu, ANN = 1u << 24;
+        const bool first = nbar == 1u;
+        const unsigned mine = 1u + ((first && T.misc[22] != 0) ? ANN : 0u);
+        T.misc[22] = 0;
+        const unsigned cg = __hip_atomic_fetch_add(grp, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + mine;
+        if ((cg & CNT) == ((members * nbar) & CNT)) {
+            const unsigned up = 1u + ((first && (cg >> 24) != 0u) ? ANN : 0u);
+            const unsigned ct = __hip_atomic_fetch_add(top, up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + up;
+            if ((ct & CNT) == (((unsigned)ngroups * nbar) & CNT)) {
+                const unsigned w = nbar | ((first && (ct >> 24) != 0u) ? 0x80000000u : 0u);
+                for (int q = 0; q < ngroups; ++q) __hip_atomic_store(rel + q * RC_BAR_STRIDE, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        unsigned spins = 0, w;
         int ok = 1;
-        while (__hip_atomic_load(rel + g * RC_BAR_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < nbar) {
+        while (((w = __hip_atomic_load(rel + g * RC_BAR_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & 0x7FFFFFFFu) < nbar) {
             __builtin_amdgcn_s_sleep(2);
             if (++spins > RC_SPIN_LIMIT) { ok = 0; atomicOr(&V.sc->err, RC_DERR_BARRIER); break; }
         }
+        if (ok) ok = (first && (w >> 31) == 0u) ? 1 : 3;
         sh_ok = ok;
     }
     __syncthreads();
-    return sh_ok != 0;
+    return sh_ok;
 }
 
 // T.act2 = the active slots with those whose cached scores are still valid first (T.misc[14] of them): not touched by a
@@ -3290,10 +3320,10 @@ __device__ __forceinline__ bool grid_barrier(const View &V, Tab &T, unsigned *ar
 // inside the two parts is arbitrary (ties between candidates are broken by label, not by position).  Ends synchronised.
 __device__ __forceinline__ void tab_partition(const View &V, Tab &T, bool with_batch)
 {
-    if (threadIdx.x == 0) { T.misc[14] = 0; T.misc[15] = 0; }
+    if (rc_tid() == 0) { T.misc[14] = 0; T.misc[15] = 0; }
     __syncthreads();
     const int K = T.misc[0];
-    for (int pos = threadIdx.x; pos < K; pos += blockDim.x) {
+    for (int pos = rc_tid(); pos < K; pos += blockDim.x) {
         const int k = T.act[pos];
         const bool d = T.dirty[k] || (with_batch && (k ? T.seg[k - 1] : 0) != T.seg[k]);
         if (d) T.act2[K - 1 - atomicAdd(&T.misc[15], 1)] = (short)k;
@@ -3331,7 +3361,7 @@ __device__ __forceinline__ int next_empty_label(const Tab &T, int n, int lab)
 // [10] index of the first of them.
 __device__ __forceinline__ void batch_sim(const View &V, Tab &T, int total, int cap)
 {
-    const int lane = threadIdx.x & 63;
+    const int lane = rc_tid() & 63;
     const int nb0 = min(total, cap);
     int K = T.misc[0], se = T.misc[1], fcur = 0, nbirth = 0, neff = 0, first_eff = -1;
     int nb = nb0, hi = (total > cap) ? T.misc[2] - 1 : V.n - 1, fail = 0, nvisited = 0;
@@ -3663,7 +3693,7 @@ __device__ __forceinline__ void batch_sim(const View &V, Tab &T, int total, int 
 // caller's restore is skipped).  Same results as batch_sim entry for entry (the randomised comparisons run both).
 __device__ __forceinline__ void batch_sim_fast(const View &V, Tab &T, int total, int cap)
 {
-    const int lane = threadIdx.x & 63;
+    const int lane = rc_tid() & 63;
     const int nb0 = min(total, cap);
     int K = T.misc[0], se = T.misc[1], nbirth = 0, neff = 0, first_eff = -1;
     int nb = nb0, hi = (total > cap) ? T.misc[2] - 1 : V.n - 1, fail = 0, nvisited = 0;
@@ -3881,7 +3911,7 @@ __device__ __forceinline__ int commit_batch(const View &V, const SweepArgs &sa, 
 #ifdef RC_PROF_COMMIT
     const long long pcA_ = __builtin_amdgcn_s_memrealtime();
 #endif
-    if (threadIdx.x == 0) { T.misc[11] = 0; T.misc[12] = 0; if (nc) T.misc[0] = T.bK[nc - 1]; }
+    if (rc_tid() == 0) { T.misc[11] = 0; T.misc[12] = 0; if (nc) T.misc[0] = T.bK[nc - 1]; }
     __syncthreads();
     // one thread per entry: a slot's label is written by at most one entry of a batch (a cluster dies, is born or is
     // relabelled at most once), sizes by LDS atomics
@@ -3889,7 +3919,7 @@ __device__ __forceinline__ int commit_batch(const View &V, const SweepArgs &sa, 
     // which only reads it): the commit then corrects it in place — the labels its entries free here, the labels they take after
     // the barrier (a label freed by one entry can be taken by a later one) — instead of rebuilding it from all the labels.
     const bool inc_used = V.kcap < 2048;
-    for (int q = threadIdx.x; q < nc; q += blockDim.x) {
+    for (int q = rc_tid(); q < nc; q += blockDim.x) {
         const int a = T.ba[q], b = T.bb[q], flag = T.bflag[q];
         if (a != b) { atomicSub(&T.size[a], 1); atomicAdd(&T.size[b], 1); }
         if (inc_used && (flag & (RC_BF_DEATH | RC_BF_RENAME))) { const int ol = T.label[a]; atomicAnd(&T.used[(ol - 1) >> 5], ~(1u << ((ol - 1) & 31))); }
@@ -3910,10 +3940,10 @@ __device__ __forceinline__ int commit_batch(const View &V, const SweepArgs &sa, 
     }
 #ifdef RC_PROF_COMMIT
     const long long pcB_ = __builtin_amdgcn_s_memrealtime();
-    if (threadIdx.x == 0) { T.misc[13] = (int)(pcB_ - pc0_); T.misc[19] = (int)(pc0_ - pcA_); }
+    if (rc_tid() == 0) { T.misc[13] = (int)(pcB_ - pc0_); T.misc[19] = (int)(pc0_ - pcA_); }
 #endif
     const int nchunks = (V.n + RC_PTS - 1) / RC_PTS;
-    const int pt = threadIdx.x & (RC_PTS - 1), st = threadIdx.x >> RC_PTS_LOG2, NS = blockDim.x >> RC_PTS_LOG2;
+    const int pt = rc_tid() & (RC_PTS - 1), st = rc_tid() >> RC_PTS_LOG2, NS = blockDim.x >> RC_PTS_LOG2;
     long long *SDo = V.SD[own_gen], *SLo = V.SL[own_gen];
     long long *SDn = next_gen >= 0 ? V.SD[next_gen] : nullptr, *SLn = next_gen >= 0 ? V.SL[next_gen] : nullptr;
     const int hi_slots = T.misc[7];   // slots in use, births of this batch included
@@ -3924,7 +3954,7 @@ __device__ __forceinline__ int commit_batch(const View &V, const SweepArgs &sa, 
         const bool act = io < V.n;
         const int i = act ? (T.cached ? T.cu[m * RC_PTS + pt] : V.pi[io]) : 0;
         if (hot >= 0) {
-            if (threadIdx.x < 4 * RC_PTS) ((long long *)T.red_v)[threadIdx.x] = 0;
+            if (rc_tid() < 4 * RC_PTS) ((long long *)T.red_v)[rc_tid()] = 0;
             __syncthreads();
             if (act) hot_accumulate(V, T, hot, i, nc, st, NS, hotacc);
             __syncthreads();
@@ -3951,9 +3981,9 @@ __device__ __forceinline__ int commit_batch(const View &V, const SweepArgs &sa, 
     }
 #ifdef RC_PROF_COMMIT
     __syncthreads();
-    if (threadIdx.x == 0) T.misc[20] = (int)(__builtin_amdgcn_s_memrealtime() - pcB_);
+    if (rc_tid() == 0) T.misc[20] = (int)(__builtin_amdgcn_s_memrealtime() - pcB_);
 #endif
-    for (int q = threadIdx.x; q < nc; q += blockDim.x)
+    for (int q = rc_tid(); q < nc; q += blockDim.x)
         if (T.ba[q] != T.bb[q]) {
             V.slot_of[T.bu[q]] = T.bb[q];  // same values from every block
             if (T.cached) {                 // ... and this block's copy of the slots of its own points
@@ -4035,11 +4065,11 @@ __device__ __forceinline__ void resolve_body(const View &V, const SweepArgs &sa,
         T.cached = V.cu_cache != 0 && cpb <= RC_CPB_LDS && V.kcap < 2048;
         const int ncu = T.cached ? cpb * RC_PTS : 0, kend = max(V.kcap, ncu);
         int hK = 0, hse = 0, hhi = 0;
-        if (threadIdx.x == 0) { hK = V.sc->K; hse = V.sc->smallest_empty; hhi = V.sc->slot_hi; }
+        if (rc_tid() == 0) { hK = V.sc->K; hse = V.sc->smallest_empty; hhi = V.sc->slot_hi; }
         double2 fl_ = {0.0, 0.0};
-        if (threadIdx.x < 128) fl_ = V.flt[threadIdx.x];
+        if (rc_tid() < 128) fl_ = V.flt[rc_tid()];
         bool first = true;
-        for (int k = threadIdx.x; first || k < kend; k += blockDim.x) {
+        for (int k = rc_tid(); first || k < kend; k += blockDim.x) {
             const bool isk = k < V.kcap;
             int sz = 0, lb = 0, ac = 0, u_ = 0, o_ = 0, i_ = V.n;
             if (isk) { sz = V.slot_size[k]; lb = V.slot_label[k]; ac = V.slot_act[k]; }
@@ -4065,11 +4095,12 @@ __device__ __forceinline__ void resolve_body(const View &V, const SweepArgs &sa,
             }
             if (k < ncu) { T.cu[k] = u_; T.cown[k] = (short)o_; }
         }
-        if (threadIdx.x < 128) T.flt[threadIdx.x] = fl_;
-        if (V.kcap < 2048 && threadIdx.x == 128 % blockDim.x) T.base_p[V.kcap] = tab_base(V, sa, 1);   // a cluster of one: the births of a batch as candidates
-        if (threadIdx.x == 0) {
+        if (rc_tid() < 128) T.flt[rc_tid()] = fl_;
+        if (V.kcap < 2048 && rc_tid() == 128 % blockDim.x) T.base_p[V.kcap] = tab_base(V, sa, 1);   // a cluster of one: the births of a batch as candidates
+        if (rc_tid() == 0) {
             T.misc[0] = hK; T.misc[1] = hse; T.misc[7] = hhi;
             *T.blk_key = RC_KEY_NONE;
+            T.misc[22] = 0;   // grid_barrier: this block has announced nothing yet
 #ifdef RC_PROF_EVAL
             T.misc[19] = 0; T.misc[20] = 0; T.misc[21] = 0;
 #endif
@@ -4122,23 +4153,28 @@ __device__ __forceinline__ void resolve_body(const View &V, const SweepArgs &sa,
             if (use_wc && !first_pass) tab_partition(V, T, false);
             for (int c = blockIdx.x, m = 0; c < nchunks; c += G, ++m)
                 if (c * RC_PTS + RC_PTS - 1 > after) eval_chunk(V, sa, T, SD, SL, c, m, after, V.n, 0, 0, cword, rec, gstamp, use_wc ? (first_pass ? 1 : 2) : 0);
-            if (use_wc && !first_pass) { for (int k = threadIdx.x; k < V.kcap; k += blockDim.x) T.dirty[k] = 0; }
+            if (use_wc && !first_pass) { for (int k = rc_tid(); k < V.kcap; k += blockDim.x) T.dirty[k] = 0; }
             if (sa.dbg & 2) break;
             RC_PHASE(6)
 #ifndef RC_PROF_COMMIT
             RC_PF(if (first_pass) ps[2] = __builtin_amdgcn_s_memrealtime();)
 #endif
-            ok = grid_barrier(V, T, arrive, G, (unsigned)(++nbar), RC_KEY_NONE, keys + round);
+            const int bar = grid_barrier(V, T, arrive, G, (unsigned)(++nbar), RC_KEY_NONE, keys + round);
+            ok = bar != 0;
             RC_PF(if (first_pass) ps[3] = __builtin_amdgcn_s_memrealtime();)
             RC_PHASE(7)
             if (!ok) break;
             exact = true; redraw = false; first_pass = false;
+            // No block announced a changer in this pass (the barrier says so), and every point drew under the state as it is: the
+            // sweep is complete — the stationary fast path, without the pass over the chunk words that would find them all empty
+            // (2.2 µs of a 29 µs stationary resolver beside the row reduction: every block re-read all of them)
+            if (bar == 1) break;
         }
         RC_CHAOS_AT(1);
         RC_PF(pt_ = __builtin_amdgcn_s_memrealtime();)
         // 1. the ordered batch of guessed changers after `after` (the bits of the points up to `after` in its chunk are history)
         int any = 0;
-        for (int c = threadIdx.x; c <= nchunks; c += blockDim.x) {
+        for (int c = rc_tid(); c <= nchunks; c += blockDim.x) {
             int cnt = 0;
             if (c < nchunks && c * RC_PTS + RC_PTS - 1 > after) {
                 const u64 w = __hip_atomic_load(cword + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -4151,8 +4187,8 @@ __device__ __forceinline__ void resolve_body(const View &V, const SweepArgs &sa,
             T.ccnt[c] = (unsigned short)cnt;
             any |= cnt;
         }
-        for (int k = threadIdx.x; k <= V.kcap; k += blockDim.x) { T.seg[k] = 0; if (k < V.kcap) T.joined[k] = 0; }
-        if (threadIdx.x == 0) T.misc[2] = 0;
+        for (int k = rc_tid(); k <= V.kcap; k += blockDim.x) { T.seg[k] = 0; if (k < V.kcap) T.joined[k] = 0; }
+        if (rc_tid() == 0) T.misc[2] = 0;
         __syncthreads();
         if (any) T.misc[2] = 1;
         __syncthreads();
@@ -4161,15 +4197,15 @@ __device__ __forceinline__ void resolve_body(const View &V, const SweepArgs &sa,
         if (!any_all && exact) break;  // no point wants to move, and every one of them drew under the state as it is: the sweep is complete (the stationary fast path)
         // exclusive offsets by wave 0: every lane scans its run of chunks, the lanes' totals by shuffles (a scan by one
         // thread costs two LDS round trips per chunk: 14 µs at n = 8192, half of a stationary resolver pass)
-        if (threadIdx.x < 64) {
-            const int per = (nchunks + 1 + 63) / 64, c0_ = (int)threadIdx.x * per, c1_ = min(c0_ + per, nchunks + 1);
+        if (rc_tid() < 64) {
+            const int per = (nchunks + 1 + 63) / 64, c0_ = (int)rc_tid() * per, c1_ = min(c0_ + per, nchunks + 1);
             int sum = 0;
             for (int c = c0_; c < c1_; ++c) sum += T.ccnt[c];
             int incl = sum;
 #pragma unroll
             for (int d_ = 1; d_ < 64; d_ <<= 1) {
                 const int up = __shfl_up(incl, d_);
-                if ((int)threadIdx.x >= d_) incl += up;
+                if ((int)rc_tid() >= d_) incl += up;
             }
             int o = incl - sum;
             for (int c = c0_; c < c1_; ++c) { const int x = T.ccnt[c]; T.ccnt[c] = (unsigned short)min(o, 65535); o += x; }
@@ -4180,7 +4216,7 @@ __device__ __forceinline__ void resolve_body(const View &V, const SweepArgs &sa,
         // point from the rank of its bit in the chunk's mask, then ONE record load — all loads of a batch in flight together (a
         // thread per chunk fetched the records of its up to 32 changers one after the other: 4.6 µs per round in the moving
         // regime, 11.5 when every point moves)
-        for (int o = threadIdx.x; o < min(total, cap + 1); o += blockDim.x) {
+        for (int o = rc_tid(); o < min(total, cap + 1); o += blockDim.x) {
             int lo_ = 0, hi_ = nchunks;                      // the largest c with ccnt[c] <= o (then ccnt[c + 1] > o)
             while (hi_ - lo_ > 1) { const int mid = (lo_ + hi_) >> 1; if ((int)T.ccnt[mid] <= o) lo_ = mid; else hi_ = mid; }
             const int c = lo_;
@@ -4210,9 +4246,9 @@ __device__ __forceinline__ void resolve_body(const View &V, const SweepArgs &sa,
         // scratch of batch_sim: rebuilt from the committed labels every time
         if (total > 0 && !used_current) {
             const int nw_ = (V.n + 31) / 32;
-            for (int w = threadIdx.x; w < nw_; w += blockDim.x) T.used[w] = 0u;
+            for (int w = rc_tid(); w < nw_; w += blockDim.x) T.used[w] = 0u;
             __syncthreads();
-            for (int k = threadIdx.x; k < T.misc[7]; k += blockDim.x) {
+            for (int k = rc_tid(); k < T.misc[7]; k += blockDim.x) {
                 const int lab = T.label[k];
                 if (lab > 0) atomicOr(&T.used[(lab - 1) >> 5], 1u << ((lab - 1) & 31));
             }
@@ -4223,14 +4259,14 @@ __device__ __forceinline__ void resolve_body(const View &V, const SweepArgs &sa,
         if (total > 0) used_current = V.kcap < 2048;
         RC_PHASE(8)
         // clusters that could become empty inside the batch (more leavers than would leave one member): only their sizes matter
-        for (int k = threadIdx.x; k < V.kcap; k += blockDim.x) T.candie[k] = (T.size[k] - T.seg[k] < 1);
+        for (int k = rc_tid(); k < V.kcap; k += blockDim.x) T.candie[k] = (T.size[k] - T.seg[k] < 1);
         __syncthreads();
 #ifdef RC_SIM_OLD   // (comparison builds: the one-entry-at-a-time simulation everywhere)
-        if (threadIdx.x < 64) batch_sim(V, T, total, cap);
+        if (rc_tid() < 64) batch_sim(V, T, total, cap);
 #else
-        if (threadIdx.x < 64) { if (V.kcap < 2048) batch_sim_fast(V, T, total, cap); else batch_sim(V, T, total, cap); }
+        if (rc_tid() < 64) { if (V.kcap < 2048) batch_sim_fast(V, T, total, cap); else batch_sim(V, T, total, cap); }
 #endif
-        if (threadIdx.x == 0) *T.blk_key = RC_KEY_NONE;
+        if (rc_tid() == 0) *T.blk_key = RC_KEY_NONE;
         __syncthreads();
         RC_PHASE(14)
 #if !defined(RC_PROF_COMMIT) && !defined(RC_PROF_EVAL)
@@ -4241,9 +4277,9 @@ __device__ __forceinline__ void resolve_body(const View &V, const SweepArgs &sa,
         {
             const int nbk = T.misc[3];
             const bool sizes_restored = T.misc[18] != 0;   // (batch_sim_fast puts the sizes back itself)
-            for (int k = threadIdx.x; k <= V.kcap; k += blockDim.x) T.seg[k] = 0;
+            for (int k = rc_tid(); k <= V.kcap; k += blockDim.x) T.seg[k] = 0;
             __syncthreads();
-            for (int q = threadIdx.x; q < nbk; q += blockDim.x) {
+            for (int q = rc_tid(); q < nbk; q += blockDim.x) {
                 const int a_ = T.ba[q], b_ = T.bb[q], fl = T.bflag[q];
                 if (a_ != b_ && !sizes_restored) {
                     if (T.candie[a_]) atomicAdd(&T.size[a_], 1);
@@ -4252,38 +4288,38 @@ __device__ __forceinline__ void resolve_body(const View &V, const SweepArgs &sa,
                 if (!(fl & RC_BF_NOOP)) { atomicAdd(&T.seg[a_], 1); if (b_ != a_) atomicAdd(&T.seg[b_], 1); }
             }
             __syncthreads();
-            if (threadIdx.x < 64) {   // exclusive offsets over the slots (wave 0: per-lane runs + shuffle scan)
-                const int per = (V.kcap + 1 + 63) / 64, c0_ = (int)threadIdx.x * per, c1_ = min(c0_ + per, V.kcap + 1);
+            if (rc_tid() < 64) {   // exclusive offsets over the slots (wave 0: per-lane runs + shuffle scan)
+                const int per = (V.kcap + 1 + 63) / 64, c0_ = (int)rc_tid() * per, c1_ = min(c0_ + per, V.kcap + 1);
                 int sum = 0;
                 for (int k = c0_; k < c1_; ++k) sum += T.seg[k];
                 int incl = sum;
 #pragma unroll
                 for (int d_ = 1; d_ < 64; d_ <<= 1) {
                     const int up = __shfl_up(incl, d_);
-                    if ((int)threadIdx.x >= d_) incl += up;
+                    if ((int)rc_tid() >= d_) incl += up;
                 }
                 int o = incl - sum;
                 for (int k = c0_; k < c1_; ++k) { const int x = T.seg[k]; T.seg[k] = o; o += x; }
             }
             __syncthreads();
-            for (int q = threadIdx.x; q < nbk; q += blockDim.x) {
+            for (int q = rc_tid(); q < nbk; q += blockDim.x) {
                 const int a_ = T.ba[q], b_ = T.bb[q];
                 if (!(T.bflag[q] & RC_BF_NOOP)) {
                     T.pairs_tmp[atomicAdd(&T.seg[a_], 1)] = (short)q;
                     if (b_ != a_) T.pairs_tmp[atomicAdd(&T.seg[b_], 1)] = (short)q;
                 }
             }
-            if (threadIdx.x == 0) T.misc[17] = 0;
+            if (rc_tid() == 0) T.misc[17] = 0;
             __syncthreads();   // now seg[k] = end of slot k's group, seg[k-1] (0 for k = 0) its begin
-            for (int k = threadIdx.x; k < V.kcap; k += blockDim.x) {   // the largest group, if it is worth sharing (hot_accumulate)
+            for (int k = rc_tid(); k < V.kcap; k += blockDim.x) {   // the largest group, if it is worth sharing (hot_accumulate)
                 const int sz_ = T.seg[k] - (k ? T.seg[k - 1] : 0);
                 if (sz_ >= RC_HOT_MIN) atomicMax(&T.misc[17], (sz_ << 16) | k);
             }
             __syncthreads();
-            if (threadIdx.x == 0) T.misc[16] = T.misc[17] ? (T.misc[17] & 0xFFFF) : -1;
+            if (rc_tid() == 0) T.misc[16] = T.misc[17] ? (T.misc[17] & 0xFFFF) : -1;
             // order every group by entry index: each entry ranks itself inside the groups of its two slots (a group can hold
             // hundreds of entries when the changers of a batch share a cluster: a one-thread-per-slot sort took 335 µs there)
-            for (int q = threadIdx.x; q < nbk; q += blockDim.x) {
+            for (int q = rc_tid(); q < nbk; q += blockDim.x) {
                 if (T.bflag[q] & RC_BF_NOOP) continue;
                 const int a_ = T.ba[q], b_ = T.bb[q];
                 for (int side = 0; side < 2; ++side) {
@@ -4301,7 +4337,7 @@ __device__ __forceinline__ void resolve_body(const View &V, const SweepArgs &sa,
         RC_PHASE(9)
         RC_CHAOS_AT(2);
 #ifdef RC_TRACE_RESOLVE   // diagnostic builds: per-round record of block RC_TRACE_BLOCK (default 0) behind the work counter
-        if ((int)blockIdx.x == (sa.dbg >> 8) && threadIdx.x == 0 && round < 120) {   // kept in LDS until the sweep is over
+        if ((int)blockIdx.x == (sa.dbg >> 8) && rc_tid() == 0 && round < 120) {   // kept in LDS until the sweep is over
             int *tr = (int *)(smem + tab_bytes_dev(V.kcap, V.n, blockDim.x >> 6, V.maxb)) + (size_t)round * 8;
             tr[0] = round; tr[1] = total; tr[2] = nb; tr[3] = hi; tr[4] = nb ? T.bx[0] : -1; tr[5] = after; tr[6] = neff; tr[7] = T.misc[8] | (exact ? 0x10000 : 0);
         }
@@ -4310,7 +4346,7 @@ __device__ __forceinline__ void resolve_body(const View &V, const SweepArgs &sa,
             // Everything up to `after` is final — with exact guesses also the points between it and this changer (they drew their
             // own labels under the committed state) — and the state is consistent: the host grows the slot tables and resumes
             // this sweep behind that point (with a tentative pass).
-            if (threadIdx.x == 0 && blockIdx.x == 0) {
+            if (rc_tid() == 0 && blockIdx.x == 0) {
                 const int ra = exact ? T.bx[0] - 1 : after;
                 V.sc->fail_t = t; V.sc->resume_after = ra; V.sc->fail_changes = changes; V.sc->fail_rounds = sa.rounds0 + round + 1;
                 V.hsum->fail_t = t; V.hsum->resume_after = ra; V.hsum->fail_changes = changes; V.hsum->fail_rounds = sa.rounds0 + round + 1;
@@ -4339,11 +4375,11 @@ __device__ __forceinline__ void resolve_body(const View &V, const SweepArgs &sa,
 #ifdef RC_PROF_EVAL   // (this build: columns 2 / 13 / 15 = longest thread in the cached-slot part / computed part / rest of the validation passes)
         RC_PF(ps[2] += T.misc[19]; ps[13] += T.misc[20]; ps[15] += T.misc[21];)
         __syncthreads();
-        if (threadIdx.x == 0) { T.misc[19] = 0; T.misc[20] = 0; T.misc[21] = 0; }
+        if (rc_tid() == 0) { T.misc[19] = 0; T.misc[20] = 0; T.misc[21] = 0; }
 #endif
         RC_PHASE(10)
         const u64 mine = *T.blk_key;
-        ok = grid_barrier(V, T, arrive, G, (unsigned)(++nbar), mine, keys + round);
+        ok = grid_barrier(V, T, arrive, G, (unsigned)(++nbar), mine, keys + round) != 0;   // (a validation pass announces through every chunk word: its bit is not used)
         RC_PHASE(11)
         if (!ok) break;
         RC_CHAOS_AT(3);
@@ -4385,7 +4421,7 @@ __device__ __forceinline__ void resolve_body(const View &V, const SweepArgs &sa,
     if ((int)blockIdx.x == (sa.dbg >> 8)) {
         const int *tr = (const int *)(smem + tab_bytes_dev(V.kcap, V.n, blockDim.x >> 6, V.maxb));
         long long *out = (long long *)((char *)V.work[kg] + 64);
-        for (int q = threadIdx.x; q < 120 * 8; q += blockDim.x) out[q] = (q / 8 <= round) ? tr[q] : -7;
+        for (int q = rc_tid(); q < 120 * 8; q += blockDim.x) out[q] = (q / 8 <= round) ? tr[q] : -7;
     }
     __syncthreads();
 #endif
@@ -4396,7 +4432,7 @@ __device__ __forceinline__ void resolve_body(const View &V, const SweepArgs &sa,
         // corrections to it (both ordered after this launch).  Rows >= slot_hi are zero by invariant.
         const size_t total2 = (size_t)T.misc[7] * (size_t)V.ld / 2;
         const size_t nthreads = (size_t)(G > 1 ? G - 1 : 1) * blockDim.x;
-        const size_t me = (size_t)(G > 1 ? blockIdx.x - 1 : 0) * blockDim.x + threadIdx.x;
+        const size_t me = (size_t)(G > 1 ? blockIdx.x - 1 : 0) * blockDim.x + rc_tid();
         ll2 *zd = (ll2 *)V.SD[sa.zero_gen], *zl = (ll2 *)V.SL[sa.zero_gen];
         const ll2 z = {0, 0};
         for (size_t q = me; q < total2; q += nthreads) { zd[q] = z; zl[q] = z; }
@@ -4409,15 +4445,15 @@ __device__ __forceinline__ void resolve_body(const View &V, const SweepArgs &sa,
     __syncthreads();
     if ((int)blockIdx.x == b_rearm) {
         // the row reduction of this sweep is complete (stream order): re-arm its work counter for sweep t+2
-        if (threadIdx.x == 0) *V.work[kg] = 0;
+        if (rc_tid() == 0) *V.work[kg] = 0;
         // re-arm the other key / chunk-word / barrier generation for the next sweep (its last user, sweep t-1, is done)
-        for (int q = threadIdx.x; q < min(prev_rounds + 2, 2 * V.n + 8); q += blockDim.x) V.keys[kg ^ 1][q] = RC_KEY_NONE;   // (the words sweep t-1 used)
-        for (int q = threadIdx.x; q < 2 * (nchunks + 1); q += blockDim.x) V.cword[kg ^ 1][q] = 0;
-        for (int q = threadIdx.x; q < RC_BAR_WORDS; q += blockDim.x) V.arrive[kg ^ 1][q] = 0u;
+        for (int q = rc_tid(); q < min(prev_rounds + 2, 2 * V.n + 8); q += blockDim.x) V.keys[kg ^ 1][q] = RC_KEY_NONE;   // (the words sweep t-1 used)
+        for (int q = rc_tid(); q < 2 * (nchunks + 1); q += blockDim.x) V.cword[kg ^ 1][q] = 0;
+        for (int q = rc_tid(); q < RC_BAR_WORDS; q += blockDim.x) V.arrive[kg ^ 1][q] = 0u;
     }
     if (blockIdx.x == 0) {
         if (changes || t < 2) tab_store(V, T);   // (nothing committed: the tables in global memory are the ones that were loaded)
-        if (threadIdx.x == 0) {
+        if (rc_tid() == 0) {
             V.sc->n_changes = changes;
             V.sc->n_rounds = sa.rounds0 + round + 1;
             if (changes) V.sc->last_change_sweep = t;
@@ -4435,9 +4471,9 @@ __device__ __forceinline__ void resolve_body(const View &V, const SweepArgs &sa,
         __syncthreads();
         build_perm_grid(V, kg, T.size, T.misc[7], G, (int *)smem);   // (the tables in LDS are no longer needed: T.size lies behind the 16·kcap bytes this uses)
     } else if (last == t - 1 && t >= 1) {
-        for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < V.n; p += G * blockDim.x) { V.perm[kg][p] = V.perm[kg ^ 1][p]; V.pslot[kg][p] = V.pslot[kg ^ 1][p]; }
+        for (int p = blockIdx.x * blockDim.x + rc_tid(); p < V.n; p += G * blockDim.x) { V.perm[kg][p] = V.perm[kg ^ 1][p]; V.pslot[kg][p] = V.pslot[kg ^ 1][p]; }
     }
-    RC_PF(if (threadIdx.x == 0 && blockIdx.x < 256) { long long *o = (long long *)((char *)V.work[kg] + 64) + (size_t)(8192 - 256 + blockIdx.x) * 16;
+    RC_PF(if (rc_tid() == 0 && blockIdx.x < 256) { long long *o = (long long *)((char *)V.work[kg] + 64) + (size_t)(8192 - 256 + blockIdx.x) * 16;
                                                        ps[5] = __builtin_amdgcn_s_memrealtime(); for (int q = 0; q < 16; ++q) o[q] = ps[q]; })
 }
 

@@ -802,23 +802,43 @@ def _search_runs(init, order, maxK, maxsweeps, call, n=None) -> dict:
     return _psm_result(labels, runs, nruns, n, best, ms, **(extra or {}))
 
 
+def _counts_form(family, counts, numsamples, ctx, samples, device, n=None, what=None):
+    """Which of the three forms of a consumer of the co-clustering counts a call takes — rc_<family>_samples (samples: an m×n
+    label matrix; counts and numsamples are ignored), rc_<family>_ctx (ctx: that context's device counts) or rc_<family>
+    (counts: n×n uint32) — as (the library's function, its leading arguments, the handle whose error buffer holds its
+    errors, n, whether a counts_ms out-parameter ends its list).  n given: the length of `what`, which the source must match."""
+    L = lib()
+    if samples is not None:
+        S = _label_matrix(samples)
+        return getattr(L, f"rc_{family}_samples"), (int(device), S.ctypes.data_as(C.c_void_p), *S.shape), None, S.shape[1], True
+    if ctx is not None:
+        if n is not None and n != ctx.n:
+            raise ValueError(f"{what} must have the context's n columns")
+        return getattr(L, f"rc_{family}_ctx"), (ctx.h, int(numsamples)), ctx.h, ctx.n, False
+    cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+    if n is None and (cnt.ndim != 2 or cnt.shape[0] != cnt.shape[1]):
+        raise ValueError("counts must be an n×n matrix")
+    if n is not None and cnt.shape != (n, n):
+        raise ValueError(f"counts must be an n×n matrix matching {what}")
+    return getattr(L, f"rc_{family}"), (int(device), cnt.ctypes.data_as(C.c_void_p), int(numsamples), cnt.shape[0]), None, cnt.shape[0], False
+
+
+def _psm_search(counts, numsamples, ctx, samples, loss, init, order, maxK, maxsweeps, device) -> dict:
+    """psm_search and psm_search_samples (samples: the label matrix) behind their parameter lists"""
+    cms = C.c_double()
+
+    def call(n, *tail):
+        fn, head, handle, _, timed = _counts_form("psm_search", counts, numsamples, ctx, samples, device, n, "init")
+        _check(fn(*head, int(loss), *tail, *([C.byref(cms)] if timed else [])), handle)
+        return dict(counts_ms=float(cms.value)) if timed else None
+    return _search_runs(init, order, maxK, maxsweeps, call, n=None if samples is None else samples.shape[1])
+
+
 def psm_search(counts, numsamples: int, loss: int, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0, ctx=None):
     """rc_psm_search (counts: n×n uint32) or, with ctx, rc_psm_search_ctx on that context's device counts (counts is ignored).
     init: nruns×n labels (0 = unallocated), order: nruns×n 1-based permutations.  Returns a dict: labels (nruns×n, sortlabels'd),
     the per-run arrays loss, loss_num, sweeps, converged, moves, K, and best, kernel_ms."""
-    L = lib()
-
-    def call(n, *tail):
-        if ctx is not None:
-            if n != ctx.n:
-                raise ValueError("init must have the context's n columns")
-            _check(L.rc_psm_search_ctx(ctx.h, int(numsamples), int(loss), *tail), ctx.h)
-        else:
-            cnt = np.ascontiguousarray(counts, dtype=np.uint32)
-            if cnt.shape != (n, n):
-                raise ValueError("counts must be an n×n matrix matching init")
-            _check(L.rc_psm_search(int(device), cnt.ctypes.data, int(numsamples), n, int(loss), *tail))
-    return _search_runs(init, order, maxK, maxsweeps, call)
+    return _psm_search(counts, numsamples, ctx, None, loss, init, order, maxK, maxsweeps, device)
 
 
 def samples_counts(samples, device: int = 0):
@@ -836,14 +856,7 @@ def samples_counts(samples, device: int = 0):
 def psm_search_samples(samples, loss: int, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
     """rc_psm_search_samples: psm_search on the counts of an m×n int64 label matrix (labels 1..n), which are built on the
     device and stay there.  Returns psm_search's dict and counts_ms, the device time of the counts kernel."""
-    L = lib()
-    S = _label_matrix(samples)
-    cms = C.c_double()
-
-    def call(n, *tail):
-        _check(L.rc_psm_search_samples(int(device), S.ctypes.data, S.shape[0], n, int(loss), *tail, C.byref(cms)))
-        return dict(counts_ms=float(cms.value))
-    return _search_runs(init, order, maxK, maxsweeps, call, n=S.shape[1])
+    return _psm_search(None, None, None, _label_matrix(samples), loss, init, order, maxK, maxsweeps, device)
 
 
 def vi_gtable(n: int) -> np.ndarray:
@@ -883,33 +896,14 @@ def hclust(counts, numsamples, linkage: int, maxcut: int = 0, device: int = 0, c
     with ctx, rc_hclust_ctx on that context's device counts.  Returns a dict: merges (n − 1 records of HCLUST_MERGE),
     binder_num (n int64; index t = after t merges), vilb (maxcut f64: the VI-bound loss of the cuts K = 1..maxcut), kernel_ms,
     and counts_ms for the samples form."""
-    L = lib()
-    if samples is not None:
-        S = _label_matrix(samples)
-        numsamples, n = S.shape
-    elif ctx is not None:
-        n = ctx.n
-    else:
-        cnt = np.ascontiguousarray(counts, dtype=np.uint32)
-        if cnt.ndim != 2 or cnt.shape[0] != cnt.shape[1]:
-            raise ValueError("counts must be an n×n matrix")
-        n = cnt.shape[0]
+    fn, head, handle, n, timed = _counts_form("hclust", counts, numsamples, ctx, samples, device)
     merges = np.zeros(max(n - 1, 1), HCLUST_MERGE)
     bnum = np.zeros(max(n, 1), np.int64)
     vilb = np.zeros(max(int(maxcut), 1))
     ms, cms = C.c_double(), C.c_double()
-    out = {}
-    if samples is not None:
-        rc = L.rc_hclust_samples(int(device), S.ctypes.data, int(numsamples), n, int(linkage), merges.ctypes.data, bnum.ctypes.data,
-                                 int(maxcut), vilb.ctypes.data, C.byref(ms), C.byref(cms))
-        out["counts_ms"] = float(cms.value)
-    elif ctx is not None:
-        rc = L.rc_hclust_ctx(ctx.h, int(numsamples), int(linkage), merges.ctypes.data, bnum.ctypes.data, int(maxcut), vilb.ctypes.data,
-                             C.byref(ms))
-    else:
-        rc = L.rc_hclust(int(device), cnt.ctypes.data, int(numsamples), n, int(linkage), merges.ctypes.data, bnum.ctypes.data,
-                         int(maxcut), vilb.ctypes.data, C.byref(ms))
-    _check(rc, ctx.h if ctx is not None and samples is None else None)
+    _check(fn(*head, int(linkage), merges.ctypes.data, bnum.ctypes.data, int(maxcut), vilb.ctypes.data, C.byref(ms),
+              *([C.byref(cms)] if timed else [])), handle)
+    out = dict(counts_ms=float(cms.value)) if timed else {}
     out.update(merges=merges[:max(n - 1, 0)], binder_num=bnum[:n], vilb=vilb[:int(maxcut)], kernel_ms=float(ms.value))
     return out
 
@@ -926,24 +920,13 @@ def hclust_cut(merges, n: int, K: int) -> np.ndarray:
 def psm_expected_loss(labels, counts, numsamples: int, loss: int, device: int = 0, ctx=None):
     """rc_psm_expected_loss (counts: n×n uint32) or, with ctx, rc_psm_expected_loss_ctx: (loss f64[L], num int64[L], kernel ms)
     of the L×n labellings `labels` (1..n)."""
-    L = lib()
     lab = np.ascontiguousarray(labels, dtype=np.int64)
     if lab.ndim != 2:
         raise ValueError("labels must be an L×n matrix")
     nl, n = lab.shape
     loss_out, num_out, ms = np.zeros(max(nl, 1)), np.zeros(max(nl, 1), np.int64), C.c_double()
-    if ctx is not None:
-        if n != ctx.n:
-            raise ValueError("labels must have the context's n columns")
-        rc = L.rc_psm_expected_loss_ctx(ctx.h, int(numsamples), int(loss), nl, lab.ctypes.data, loss_out.ctypes.data,
-                                        num_out.ctypes.data, C.byref(ms))
-    else:
-        cnt = np.ascontiguousarray(counts, dtype=np.uint32)
-        if cnt.shape != (n, n):
-            raise ValueError("counts must be an n×n matrix matching labels")
-        rc = L.rc_psm_expected_loss(int(device), cnt.ctypes.data, int(numsamples), n, int(loss), nl, lab.ctypes.data,
-                                    loss_out.ctypes.data, num_out.ctypes.data, C.byref(ms))
-    _check(rc, ctx.h if ctx is not None else None)
+    fn, head, handle, _, _ = _counts_form("psm_expected_loss", counts, numsamples, ctx, None, device, n, "labels")
+    _check(fn(*head, int(loss), nl, lab.ctypes.data, loss_out.ctypes.data, num_out.ctypes.data, C.byref(ms)), handle)
     return loss_out[:nl], num_out[:nl], float(ms.value)
 
 

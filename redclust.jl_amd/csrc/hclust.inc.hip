@@ -1,8 +1,10 @@
 // Hierarchical point estimates on the device: agglomerative clustering of the posterior co-clustering counts C (n×n
 // uint32, C_ii = m) — Medvedovic's method, mcclust's minbinder / mcclust.ext's minVI with method = "avg" / "comp" — and the
 // expected loss of a batch of given labellings under the same counts.  DESIGN.md §8 "Hierarchical point estimates".
-// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, rc_ctx; the holders, check_counts,
-// check_lds_capacity and LDS_NMAX of hostutil.inc.hip; greedy::shfl_xor_u64; sc::build).
+// Included at the end of redclust_hip.hip behind samplecounts.inc.hip (same translation unit: shares fail(), HIPCHK, rc_ctx;
+// the holders, check_counts, check_lds_capacity and LDS_NMAX of hostutil.inc.hip; greedy::shfl_xor_u64; cnt:: of
+// samplecounts.inc.hip, which puts the counts of every entry point here on the device: nothing below stages a matrix or
+// touches a context's counts).
 //
 // Linkage.  Clusters are named by their smallest member.  Per pair of active clusters a < b: S_ab = Σ_{i∈a, j∈b} C_ij (u64)
 // and, for the two extreme linkages, M_ab = min (complete) or max (single) of C_ij over the pair (u32).  The similarity of a
@@ -511,29 +513,25 @@ static int32_t check_eloss_args(rc_ctx *c, const char *who, int64_t m, int64_t n
     return RC_OK;
 }
 
-// the host counts staged as rc_psm_search stages them: n × ld, ld a multiple of 4, pad columns zero
-static int32_t stage_counts(const void *counts, int64_t n, int64_t ld, DeviceBuffers &B, unsigned *&d_C)
+// The entry points of both consumers: cnt::with puts the counts of src on the device between the argument checks and the run
+static int32_t dendrogram(const char *who, const cnt::Source &src, int32_t linkage, void *merges_out, int64_t *binder_num, int32_t maxcut,
+                          double *vilb, double *kernel_ms)
 {
-    HIPCHK(nullptr, B.alloc(d_C, (size_t)n * ld));
-    if (ld != n) HIPCHK(nullptr, hipMemset(d_C, 0, (size_t)n * ld * sizeof(unsigned)));
-    HIPCHK(nullptr, hipMemcpy2D(d_C, (size_t)ld * sizeof(unsigned), counts, (size_t)n * sizeof(unsigned), (size_t)n * sizeof(unsigned), (size_t)n,
-                      hipMemcpyHostToDevice));
-    return RC_OK;
+    return cnt::with(
+        who, src, [&](rc_ctx *c, int64_t m, int64_t n) { return check_args(c, who, m, n, linkage, merges_out, binder_num, maxcut, vilb); },
+        [&](rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ldc, int64_t m, int64_t n) {
+            return run(c, st, who, dC, ldc, m, n, linkage, (rc_hclust_merge_t *)merges_out, binder_num, maxcut, vilb, kernel_ms);
+        });
 }
 
-// the context's device counts, flushed and non-empty
-static int32_t ctx_counts(rc_ctx *c, const char *who)
+static int32_t expected_loss(const char *who, const cnt::Source &src, int32_t loss, int64_t L, const int64_t *labels, double *loss_out,
+                             int64_t *num_out, double *kernel_ms)
 {
-    HIPCHK(c, hipSetDevice(c->dev));
-    if (!c->counts) return fail(c, RC_ERR_STATE, "%s: no sample has been recorded", who);
-    int32_t rc = flush_counts(c);
-    if (rc != RC_OK) return rc;
-    rc = sync_and_check(c);
-    if (rc != RC_OK) return rc;
-    unsigned d0 = 0;
-    HIPCHK(c, hipMemcpy(&d0, c->counts, sizeof(unsigned), hipMemcpyDeviceToHost));
-    if (d0 == 0) return fail(c, RC_ERR_STATE, "%s: no sample has been recorded", who);
-    return RC_OK;
+    return cnt::with(
+        who, src, [&](rc_ctx *c, int64_t m, int64_t n) { return check_eloss_args(c, who, m, n, loss, L, labels, loss_out, num_out); },
+        [&](rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ldc, int64_t m, int64_t n) {
+            return run_eloss(c, st, who, dC, ldc, m, n, loss, L, labels, loss_out, num_out, kernel_ms);
+        });
 }
 
 }  // namespace hcl
@@ -541,49 +539,20 @@ static int32_t ctx_counts(rc_ctx *c, const char *who)
 extern "C" int32_t rc_hclust(int32_t device, const void *counts, int64_t m, int64_t n, int32_t linkage, void *merges_out,
                              int64_t *binder_num, int32_t maxcut, double *vilb, double *kernel_ms)
 {
-    const char *who = "rc_hclust";
-    if (!counts) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
-    int32_t rc = hcl::check_args(nullptr, who, m, n, linkage, merges_out, binder_num, maxcut, vilb);
-    if (rc != RC_OK) return rc;
-    rc = select_device(who, device);
-    if (rc != RC_OK) return rc;
-    const int64_t ld = (n + 3) / 4 * 4;
-    DeviceBuffers B;
-    unsigned *d_C;
-    rc = hcl::stage_counts(counts, n, ld, B, d_C);
-    if (rc != RC_OK) return rc;
-    return hcl::run(nullptr, nullptr, who, d_C, ld, m, n, linkage, (rc_hclust_merge_t *)merges_out, binder_num, maxcut, vilb, kernel_ms);
+    return hcl::dendrogram("rc_hclust", cnt::host_counts(device, counts, m, n), linkage, merges_out, binder_num, maxcut, vilb, kernel_ms);
 }
 
 extern "C" int32_t rc_hclust_samples(int32_t device, const int64_t *samples, int64_t m, int64_t n, int32_t linkage, void *merges_out,
                                      int64_t *binder_num, int32_t maxcut, double *vilb, double *kernel_ms, double *counts_ms)
 {
-    const char *who = "rc_hclust_samples";
-    if (!samples) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
-    int32_t rc = hcl::check_args(nullptr, who, m, n, linkage, merges_out, binder_num, maxcut, vilb);
-    if (rc != RC_OK) return rc;
-    rc = select_device(who, device);
-    if (rc != RC_OK) return rc;
-    const int64_t ld = (n + 3) / 4 * 4;
-    DeviceBuffers B;                                       // the counts stay on the device
-    unsigned *d_counts;
-    rc = sc::build(who, samples, m, n, ld, B, d_counts, counts_ms);
-    if (rc != RC_OK) return rc;
-    return hcl::run(nullptr, nullptr, who, d_counts, ld, m, n, linkage, (rc_hclust_merge_t *)merges_out, binder_num, maxcut, vilb, kernel_ms);
+    return hcl::dendrogram("rc_hclust_samples", cnt::samples(device, samples, m, n, counts_ms), linkage, merges_out, binder_num, maxcut, vilb,
+                           kernel_ms);
 }
 
 extern "C" int32_t rc_hclust_ctx(rc_ctx *c, int64_t numsamples, int32_t linkage, void *merges_out, int64_t *binder_num, int32_t maxcut,
                                  double *vilb, double *kernel_ms)
 {
-    const char *who = "rc_hclust_ctx";
-    if (!c) return fail(c, RC_ERR_ARG, "%s: NULL ctx", who);
-    int32_t rc = hcl::check_args(c, who, numsamples, c->n, linkage, merges_out, binder_num, maxcut, vilb);
-    if (rc != RC_OK) return rc;
-    rc = hcl::ctx_counts(c, who);
-    if (rc != RC_OK) return rc;
-    // the count matrix is read in place (caller's point order, leading dimension ldc); nothing of the context is written
-    return hcl::run(c, c->sA, who, c->counts, c->ldc, numsamples, c->n, linkage, (rc_hclust_merge_t *)merges_out, binder_num, maxcut, vilb,
-                    kernel_ms);
+    return hcl::dendrogram("rc_hclust_ctx", cnt::context(c, numsamples), linkage, merges_out, binder_num, maxcut, vilb, kernel_ms);
 }
 
 extern "C" int32_t rc_hclust_cut(const void *merges, int64_t n, int64_t K, int64_t *labels_out)
@@ -600,28 +569,11 @@ extern "C" int32_t rc_hclust_cut(const void *merges, int64_t n, int64_t K, int64
 extern "C" int32_t rc_psm_expected_loss(int32_t device, const void *counts, int64_t m, int64_t n, int32_t loss, int64_t L,
                                         const int64_t *labels, double *loss_out, int64_t *num_out, double *kernel_ms)
 {
-    const char *who = "rc_psm_expected_loss";
-    if (!counts) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
-    int32_t rc = hcl::check_eloss_args(nullptr, who, m, n, loss, L, labels, loss_out, num_out);
-    if (rc != RC_OK) return rc;
-    rc = select_device(who, device);
-    if (rc != RC_OK) return rc;
-    const int64_t ld = (n + 3) / 4 * 4;
-    DeviceBuffers B;
-    unsigned *d_C;
-    rc = hcl::stage_counts(counts, n, ld, B, d_C);
-    if (rc != RC_OK) return rc;
-    return hcl::run_eloss(nullptr, nullptr, who, d_C, ld, m, n, loss, L, labels, loss_out, num_out, kernel_ms);
+    return hcl::expected_loss("rc_psm_expected_loss", cnt::host_counts(device, counts, m, n), loss, L, labels, loss_out, num_out, kernel_ms);
 }
 
 extern "C" int32_t rc_psm_expected_loss_ctx(rc_ctx *c, int64_t numsamples, int32_t loss, int64_t L, const int64_t *labels,
                                             double *loss_out, int64_t *num_out, double *kernel_ms)
 {
-    const char *who = "rc_psm_expected_loss_ctx";
-    if (!c) return fail(c, RC_ERR_ARG, "%s: NULL ctx", who);
-    int32_t rc = hcl::check_eloss_args(c, who, numsamples, c->n, loss, L, labels, loss_out, num_out);
-    if (rc != RC_OK) return rc;
-    rc = hcl::ctx_counts(c, who);
-    if (rc != RC_OK) return rc;
-    return hcl::run_eloss(c, c->sA, who, c->counts, c->ldc, numsamples, c->n, loss, L, labels, loss_out, num_out, kernel_ms);
+    return hcl::expected_loss("rc_psm_expected_loss_ctx", cnt::context(c, numsamples), loss, L, labels, loss_out, num_out, kernel_ms);
 }

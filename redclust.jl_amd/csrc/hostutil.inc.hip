@@ -1,10 +1,10 @@
 // Host utilities of the entry points that own their device memory for one call (most of them take a device number and no
 // context): a holder of device buffers, a pair of timing events, the check of a label matrix, the tests' environment switches,
 // the dynamic-LDS attribute, the device selection; and what the consumers of a co-clustering count matrix share: the n that fits
-// a workgroup's LDS, the capacity check and the device check of the matrix (k_check_counts, check_counts).  Included at the end
-// of redclust_hip.hip after labels.inc.hpp and before every other include (same translation unit: shares fail() and HIPCHK —
-// HIPCHK(nullptr, call) reports into the thread's error buffer).  Both holders release on scope exit, so a HIPCHK may return
-// from anywhere.
+// a workgroup's LDS, the capacity check and the device check of the matrix (k_check_counts, check_counts) — how the matrix
+// gets onto the device is cnt:: in samplecounts.inc.hip, not here.  Included at the end of redclust_hip.hip after
+// labels.inc.hpp and before every other include (same translation unit: shares fail() and HIPCHK — HIPCHK(nullptr, call)
+// reports into the thread's error buffer).  Both holders release on scope exit, so a HIPCHK may return from anywhere.
 
 struct DeviceBuffers {
     std::vector<void *> owned;

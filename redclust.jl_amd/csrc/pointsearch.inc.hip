@@ -2,10 +2,12 @@
 // under the posterior co-clustering counts C (n×n uint32, C_ii = m = number of samples) — the step the reference's
 // docs/src/index.md §"Point estimation" sends its users to R's SALSO for; getpointestimate(method = "MPEL")
 // (src/pointestimate.jl:49-58 of the reference) only ever looks at the clusterings the chain visited.
-// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, rc_ctx, the error buffer, the
-// holders and the count-matrix checks of hostutil.inc.hip, and from greedy.inc.hip everything of the search that does not
-// depend on the criterion: the order walk, the keys and the group argmin, the new-cluster candidate, and on the host the
-// shared argument checks, the staging of the runs and the result loop).  What is here: the two scores and their state.
+// Included at the end of redclust_hip.hip behind samplecounts.inc.hip (same translation unit: shares fail(), HIPCHK, rc_ctx,
+// the error buffer, the holders and the count-matrix checks of hostutil.inc.hip; cnt:: of samplecounts.inc.hip, which puts
+// the counts of all three entry points — host counts, samples, a live context — on the device; and from greedy.inc.hip
+// everything of the search that does not depend on the criterion: the order walk, the keys and the group argmin, the
+// new-cluster candidate, and on the host the shared argument checks, the staging of the runs and the result loop).  What is
+// here: the two scores and their state.
 //
 // Criterion (DESIGN.md §8 "Point-estimate search"):
 //   Binder   num(c) = Σ_{i<j} C_ij + Σ_{i<j, c_i=c_j} (m − 2·C_ij)                 loss = num / (m·n(n−1)/2)   exact integers
@@ -277,7 +279,7 @@ static hipError_t launch(int Q, int nruns, size_t lds, hipStream_t st, const Arg
     return hipGetLastError();
 }
 
-// Everything behind the two entry points.  c may be NULL (errors then go to the thread's buffer); dC is the device
+// Everything behind the three entry points.  c may be NULL (errors then go to the thread's buffer); dC is the device
 // count matrix (n × ld, ld a multiple of 4, rows 16-byte aligned), read in place.
 static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, int64_t m, int64_t n, int32_t loss, int32_t nruns,
                    const int64_t *init, const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out,
@@ -357,45 +359,41 @@ static int32_t check_args(rc_ctx *c, const char *who, int64_t m, int64_t n, int3
     return check_lds_capacity(c, who, n, m);
 }
 
+
+// The three entry points: cnt::with puts the counts of src on the device between check_args and run
+static int32_t search(const char *who, const cnt::Source &src, int32_t loss, int32_t nruns, const int64_t *init, const int32_t *order,
+                      int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out, int32_t *best, double *kernel_ms)
+{
+    return cnt::with(
+        who, src,
+        [&](rc_ctx *c, int64_t m, int64_t n) { return check_args(c, who, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best); },
+        [&](rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, int64_t m, int64_t n) {
+            return run(c, st, dC, ld, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out, (rc_psm_run_t *)runs_out, best, kernel_ms);
+        });
+}
+
 }  // namespace psm
 
 extern "C" int32_t rc_psm_search(int32_t device, const void *counts, int64_t m, int64_t n, int32_t loss, int32_t nruns,
                                  const int64_t *init, const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out,
                                  void *runs_out, int32_t *best, double *kernel_ms)
 {
-    if (!counts) return fail(nullptr, RC_ERR_ARG, "rc_psm_search: NULL argument");
-    int32_t rc = psm::check_args(nullptr, "rc_psm_search", m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best);
-    if (rc != RC_OK) return rc;
-    rc = select_device("rc_psm_search", device);
-    if (rc != RC_OK) return rc;
-    const int64_t ld = (n + 3) / 4 * 4;
-    DeviceBuffers B;
-    unsigned *d_C;
-    HIPCHK(nullptr, B.alloc(d_C, (size_t)n * ld));
-    if (ld != n) HIPCHK(nullptr, hipMemset(d_C, 0, (size_t)n * ld * sizeof(unsigned)));
-    HIPCHK(nullptr, hipMemcpy2D(d_C, (size_t)ld * sizeof(unsigned), counts, (size_t)n * sizeof(unsigned), (size_t)n * sizeof(unsigned), (size_t)n,
-                      hipMemcpyHostToDevice));
-    return psm::run(nullptr, nullptr, d_C, ld, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out,
-                    (rc_psm_run_t *)runs_out, best, kernel_ms);
+    return psm::search("rc_psm_search", cnt::host_counts(device, counts, m, n), loss, nruns, init, order, maxK, maxsweeps, labels_out, runs_out,
+                       best, kernel_ms);
+}
+
+extern "C" int32_t rc_psm_search_samples(int32_t device, const int64_t *samples, int64_t m, int64_t n, int32_t loss, int32_t nruns,
+                                         const int64_t *init, const int32_t *order, int32_t maxK, int32_t maxsweeps,
+                                         int64_t *labels_out, void *runs_out, int32_t *best, double *kernel_ms, double *counts_ms)
+{
+    return psm::search("rc_psm_search_samples", cnt::samples(device, samples, m, n, counts_ms), loss, nruns, init, order, maxK, maxsweeps,
+                       labels_out, runs_out, best, kernel_ms);
 }
 
 extern "C" int32_t rc_psm_search_ctx(rc_ctx *c, int64_t numsamples, int32_t loss, int32_t nruns, const int64_t *init,
                                      const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out,
                                      rc_psm_run_t *runs_out, int32_t *best, double *kernel_ms)
 {
-    if (!c) return fail(c, RC_ERR_ARG, "rc_psm_search_ctx: NULL ctx");
-    int32_t rc = psm::check_args(c, "rc_psm_search_ctx", numsamples, c->n, loss, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best);
-    if (rc != RC_OK) return rc;
-    HIPCHK(c, hipSetDevice(c->dev));
-    if (!c->counts) return fail(c, RC_ERR_STATE, "rc_psm_search_ctx: no sample has been recorded");
-    rc = flush_counts(c);
-    if (rc != RC_OK) return rc;
-    rc = sync_and_check(c);
-    if (rc != RC_OK) return rc;
-    unsigned d0 = 0;
-    HIPCHK(c, hipMemcpy(&d0, c->counts, sizeof(unsigned), hipMemcpyDeviceToHost));
-    if (d0 == 0) return fail(c, RC_ERR_STATE, "rc_psm_search_ctx: no sample has been recorded");
-    // the count matrix is read in place (caller's point order, leading dimension ldc); nothing of the context is written
-    return psm::run(c, c->sA, c->counts, c->ldc, numsamples, c->n, loss, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best,
-                    kernel_ms);
+    return psm::search("rc_psm_search_ctx", cnt::context(c, numsamples), loss, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best,
+                       kernel_ms);
 }

@@ -7825,9 +7825,9 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "mixture.inc.hip"
 #include "kmeans.inc.hip"
 #include "greedy.inc.hip"
+#include "samplecounts.inc.hip"
 #include "pointsearch.inc.hip"
 #include "visearch.inc.hip"
-#include "samplecounts.inc.hip"
 #include "hclust.inc.hip"
 #include "predict.inc.hip"
 #include "predictjoint.inc.hip"

@@ -1,10 +1,15 @@
 // Co-clustering counts from samples on the device: counts[i][j] = #{s : samples[s][i] == samples[s][j]} for an m×n label
-// matrix that is already there — a stored MCMCResult, several merged chains, another sampler's draws — and the point-estimate
-// search on those counts without the matrix ever reaching the host.  A live chain builds the same counts as it goes
+// matrix that is already there — a stored MCMCResult, several merged chains, another sampler's draws — without the matrix
+// ever reaching the host.  A live chain builds the same counts as it goes
 // (k_snapshot / k_cocluster_batch, 32 samples per read-modify-write pass over the matrix); here all m samples are present, so
 // every count is computed once from zero in registers and stored once.  DESIGN.md §8 "Counts from samples".
-// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK; the point search's psm::run and
-// psm::check_args; the holders, check_label_rows and select_device of hostutil.inc.hip).
+// Below the kernel, cnt:: — the one place where the counts of a consumer (the search, the dendrogram, the expected loss) reach
+// the device, whichever of the three forms the caller has them in: cnt::acquire owns the staging of a host matrix, the call of
+// sc::build for a consumer, and the flush-and-check sequence of a live context; cnt::with is the order of checks of all
+// eight entry points.  DESIGN.md §8 "One counts source".
+// Included at the end of redclust_hip.hip ahead of its consumers pointsearch.inc.hip and hclust.inc.hip (same translation
+// unit: shares fail(), HIPCHK, rc_ctx, flush_counts, sync_and_check; the holders, check_label_rows and select_device of
+// hostutil.inc.hip).
 //
 // Geometry.  The matrix is cut into TI × TJ = 128 × 128 tiles; a 256-thread workgroup computes one tile on or above the
 // diagonal and stores it to both triangles.  A thread owns 8 × 8 counts (64 u32 registers): rows h·64 + ty·4 + 0..3 and columns
@@ -168,6 +173,88 @@ static int32_t build(const char *who, const int64_t *samples, int64_t m, int64_t
 
 }  // namespace sc
 
+// ---- One counts source for the consumers of the matrix: the search (pointsearch.inc.hip), the dendrogram and the expected
+// loss (hclust.inc.hip).  DESIGN.md §8 "One counts source".
+namespace cnt {
+
+// Where the n × n counts of m samples come from: a host matrix or the samples themselves, for `device`, or a live context
+struct Source {
+    enum Kind { HOST, SAMPLES, CTX } kind;
+    int32_t device;
+    const void *host;                                      // HOST: n × n uint32; SAMPLES: m × n int64 labels 1..n
+    int64_t m, n;
+    double *counts_ms;                                     // SAMPLES (may be NULL): device time of k_sample_counts
+    rc_ctx *c;                                             // CTX
+};
+static Source host_counts(int32_t device, const void *counts, int64_t m, int64_t n) { return {Source::HOST, device, counts, m, n, nullptr, nullptr}; }
+static Source samples(int32_t device, const int64_t *samples, int64_t m, int64_t n, double *counts_ms)
+{
+    return {Source::SAMPLES, device, samples, m, n, counts_ms, nullptr};
+}
+static Source context(rc_ctx *c, int64_t numsamples) { return {Source::CTX, 0, nullptr, numsamples, c ? c->n : 0, nullptr, c}; }
+
+// The counts on the device: n × ld at d (ld a multiple of 4, pad columns zero for the device forms), read in place.  Errors go
+// to c and work to st: the context and its stream sA, or null and null — the thread's buffer, the null stream — for the
+// device forms, whose staged matrix B owns.
+struct OnDevice {
+    DeviceBuffers B;
+    const unsigned *d = nullptr;
+    int64_t ld = 0;
+    rc_ctx *c = nullptr;
+    hipStream_t st = nullptr;
+};
+
+// Selects the source's device and puts its counts there.  A context's counts are flushed, checked to hold a sample, and then
+// read where they are, at leading dimension ldc: nothing of the context is written.
+static int32_t acquire(const char *who, const Source &s, OnDevice &D)
+{
+    if (s.kind == Source::CTX) {
+        rc_ctx *c = s.c;
+        HIPCHK(c, hipSetDevice(c->dev));
+        unsigned d0 = 0;                                   // the first diagonal entry: the number of recorded samples
+        if (c->counts) {
+            int32_t rc = flush_counts(c);
+            if (rc != RC_OK) return rc;
+            rc = sync_and_check(c);
+            if (rc != RC_OK) return rc;
+            HIPCHK(c, hipMemcpy(&d0, c->counts, sizeof(unsigned), hipMemcpyDeviceToHost));
+        }
+        if (d0 == 0) return fail(c, RC_ERR_STATE, "%s: no sample has been recorded", who);
+        D.d = c->counts; D.ld = c->ldc; D.c = c; D.st = c->sA;
+        return RC_OK;
+    }
+    int32_t rc = select_device(who, s.device);
+    if (rc != RC_OK) return rc;
+    const int64_t n = s.n, ld = (n + 3) / 4 * 4;
+    unsigned *d;
+    if (s.kind == Source::SAMPLES) {
+        rc = sc::build(who, (const int64_t *)s.host, s.m, n, ld, D.B, d, s.counts_ms);
+        if (rc != RC_OK) return rc;
+    } else {
+        HIPCHK(nullptr, D.B.alloc(d, (size_t)n * ld));
+        if (ld != n) HIPCHK(nullptr, hipMemset(d, 0, (size_t)n * ld * sizeof(unsigned)));
+        HIPCHK(nullptr, hipMemcpy2D(d, (size_t)ld * sizeof(unsigned), s.host, (size_t)n * sizeof(unsigned), (size_t)n * sizeof(unsigned), (size_t)n,
+                                    hipMemcpyHostToDevice));
+    }
+    D.d = d; D.ld = ld;
+    return RC_OK;
+}
+
+// A consumer's entry point in the order every form keeps: the source is there; check(c, m, n), the consumer's own argument
+// checks; acquire; run(c, st, d, ld, m, n), which begins with its own checks and check_counts.
+template <typename Check, typename Run> static int32_t with(const char *who, const Source &s, Check check, Run run)
+{
+    if (s.kind == Source::CTX ? !s.c : !s.host) return fail(s.c, RC_ERR_ARG, s.kind == Source::CTX ? "%s: NULL ctx" : "%s: NULL argument", who);
+    int32_t rc = check(s.c, s.m, s.n);
+    if (rc != RC_OK) return rc;
+    OnDevice D;
+    rc = acquire(who, s, D);
+    if (rc != RC_OK) return rc;
+    return run(D.c, D.st, D.d, D.ld, s.m, s.n);
+}
+
+}  // namespace cnt
+
 extern "C" int32_t rc_samples_counts(int32_t device, const int64_t *samples, int64_t m, int64_t n, void *counts_out, double *kernel_ms)
 {
     const char *who = "rc_samples_counts";
@@ -185,23 +272,4 @@ extern "C" int32_t rc_samples_counts(int32_t device, const int64_t *samples, int
     HIPCHK(nullptr, hipMemcpy2D(counts_out, (size_t)n * sizeof(unsigned), d_counts, (size_t)ld * sizeof(unsigned), (size_t)n * sizeof(unsigned), (size_t)n,
                       hipMemcpyDeviceToHost));
     return RC_OK;
-}
-
-extern "C" int32_t rc_psm_search_samples(int32_t device, const int64_t *samples, int64_t m, int64_t n, int32_t loss, int32_t nruns,
-                                         const int64_t *init, const int32_t *order, int32_t maxK, int32_t maxsweeps,
-                                         int64_t *labels_out, void *runs_out, int32_t *best, double *kernel_ms, double *counts_ms)
-{
-    const char *who = "rc_psm_search_samples";
-    if (!samples) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
-    int32_t rc = psm::check_args(nullptr, who, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best);
-    if (rc != RC_OK) return rc;
-    rc = select_device(who, device);
-    if (rc != RC_OK) return rc;
-    const int64_t ld = (n + 3) / 4 * 4;
-    DeviceBuffers B;                                       // the counts stay on the device
-    unsigned *d_counts;
-    rc = sc::build(who, samples, m, n, ld, B, d_counts, counts_ms);
-    if (rc != RC_OK) return rc;
-    return psm::run(nullptr, nullptr, d_counts, ld, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out,
-                    (rc_psm_run_t *)runs_out, best, kernel_ms);
 }

@@ -359,6 +359,25 @@ def hclust(samples_or_counts=None, linkage="average", *, numsamples=None, ctx=No
     return out
 
 
+def _hclust_cuts(samples_or_counts, linkage, maxK, numsamples, ctx, device, *, lo=1, exact=False, vilb=False, cuts=True):
+    """What the criteria of hclustpointestimate share: the linkage and the input checked (exact: the samples only), maxK
+    defaulted to ⌈n/8⌉ (at least lo, n permitting) and checked to lie in lo..n, the dendrogram (vilb: with the VI bound of the
+    cuts 1..maxK) and, unless cuts=False, the stacked cuts of lo..maxK clusters.  Returns (res, cuts, S, m, n, maxK)."""
+    if linkage not in _LINKAGES:
+        raise ValueError("Invalid linkage specifier.")
+    if exact and ctx is not None:
+        raise ValueError("exact=True needs the samples; a Context keeps only their counts")
+    if exact and not hasattr(samples_or_counts, "clusts"):
+        raise ValueError("exact=True needs the samples (an MCMCResult), not a count matrix")
+    S, counts, m, n = _counts_input(samples_or_counts, numsamples, ctx)
+    maxK = int(maxK) if maxK else max(-(-n // 8), min(n, lo))
+    if not lo <= maxK <= n:
+        raise ValueError("maxK must lie in 1..n" if lo == 1 else "maxK must lie in 2..n with criterion='silhouette'")
+    res = _lib.hclust(counts, m, _LINKAGES[linkage], maxcut=maxK if vilb else 0, device=device, ctx=ctx, samples=S)
+    stacked = np.stack([_lib.hclust_cut(res["merges"], n, K) for K in range(lo, maxK + 1)]) if cuts else None
+    return res, stacked, S, m, n, maxK
+
+
 def hclustpointestimate(samples_or_counts=None, loss="VI", linkage="average", *, maxK: int = 0, numsamples=None, ctx=None,
                         device: int = 0, exact: bool = False, criterion: str = "loss", data=None, params=None, r=None, p=None):
     """The hierarchical point estimate: hclust's dendrogram cut at the number of clusters K in 1..maxK of minimum expected
@@ -384,20 +403,17 @@ def hclustpointestimate(samples_or_counts=None, loss="VI", linkage="average", *,
     binder_num, kernel_ms, profile_ms."""
     if criterion not in ("loss", "posterior", "silhouette"):
         raise ValueError("criterion must be 'loss', 'posterior' or 'silhouette'")
-    if criterion == "silhouette":
-        from .profiles import clusterprofiles
+    source = (samples_or_counts, linkage, maxK, numsamples, ctx, device)
+    if criterion != "loss":
         if exact:
-            raise ValueError("exact=True chooses by expected loss; it does not go with criterion='silhouette'")
+            raise ValueError(f"exact=True chooses by expected loss; it does not go with criterion='{criterion}'")
         if linkage not in _LINKAGES:
             raise ValueError("Invalid linkage specifier.")
         if data is None:
-            raise ValueError("criterion='silhouette' needs data= (a Context, an MCMCData or a dissimilarity matrix)")
-        S, counts, m, n = _counts_input(samples_or_counts, numsamples, ctx)
-        maxK = int(maxK) if maxK else max(-(-n // 8), min(n, 2))
-        if not 2 <= maxK <= n:
-            raise ValueError("maxK must lie in 2..n with criterion='silhouette'")
-        res = _lib.hclust(counts, m, _LINKAGES[linkage], device=device, ctx=ctx, samples=S)
-        cuts = np.stack([_lib.hclust_cut(res["merges"], n, K) for K in range(2, maxK + 1)])
+            raise ValueError(f"criterion='{criterion}' needs data= (a Context, an MCMCData or a dissimilarity matrix)")
+    if criterion == "silhouette":
+        from .profiles import clusterprofiles
+        res, cuts, _, _, _, _ = _hclust_cuts(*source, lo=2)
         prof = clusterprofiles(data, cuts, device=device)
         best = int(np.argmax(prof.mean_silhouette))                 # numpy's argmax is the first maximum: the fewest clusters
         info = dict(merges=res["merges"], binder_num=res["binder_num"], kernel_ms=res["kernel_ms"],
@@ -405,59 +421,28 @@ def hclustpointestimate(samples_or_counts=None, loss="VI", linkage="average", *,
         return cuts[best].copy(), info
     if criterion == "posterior":
         from .score import mapestimate
-        if exact:
-            raise ValueError("exact=True chooses by expected loss; it does not go with criterion='posterior'")
-        if linkage not in _LINKAGES:
-            raise ValueError("Invalid linkage specifier.")
-        if data is None:
-            raise ValueError("criterion='posterior' needs data= (a Context, an MCMCData or a dissimilarity matrix)")
         if r is None and p is None and hasattr(samples_or_counts, "r"):
             r, p = float(np.mean(samples_or_counts.r)), float(np.mean(samples_or_counts.p))
         if params is None and not isinstance(data, _lib.Context):
             params = getattr(samples_or_counts, "params", None)
         if r is None or p is None:
             raise ValueError("criterion='posterior' needs r and p")
-        S, counts, m, n = _counts_input(samples_or_counts, numsamples, ctx)
-        maxK = int(maxK) if maxK else -(-n // 8)
-        if not 1 <= maxK <= n:
-            raise ValueError("maxK must lie in 1..n")
-        res = _lib.hclust(counts, m, _LINKAGES[linkage], device=device, ctx=ctx, samples=S)
-        cuts = np.stack([_lib.hclust_cut(res["merges"], n, K) for K in range(1, maxK + 1)])
+        res, cuts, _, _, _, _ = _hclust_cuts(*source)
         clust, sc = mapestimate(data, cuts, params, r, p, device=device)
         info = dict(merges=res["merges"], binder_num=res["binder_num"], kernel_ms=res["kernel_ms"], score_ms=sc["kernel_ms"],
                     loglik=sc["loglik"], logprior=sc["logprior"], logposterior=sc["logposterior"], K=sc["index"] + 1)
         return clust, info
+    if loss not in (_DIST_LOSSES if exact else _PSM_LOSSES):
+        raise ValueError("Invalid loss function specifier.")
     if exact:
-        if loss not in _DIST_LOSSES:
-            raise ValueError("Invalid loss function specifier.")
-        if linkage not in _LINKAGES:
-            raise ValueError("Invalid linkage specifier.")
-        if ctx is not None:
-            raise ValueError("exact=True needs the samples; a Context keeps only their counts")
-        if not hasattr(samples_or_counts, "clusts"):
-            raise ValueError("exact=True needs the samples (an MCMCResult), not a count matrix")
-        S = _sample_matrix(samples_or_counts)
-        m, n = S.shape
-        maxK = int(maxK) if maxK else -(-n // 8)
-        if not 1 <= maxK <= n:
-            raise ValueError("maxK must lie in 1..n")
-        res = _lib.hclust(None, m, _LINKAGES[linkage], device=device, samples=S)
-        cuts = np.stack([_lib.hclust_cut(res["merges"], n, K) for K in range(1, maxK + 1)])
+        res, cuts, S, _, n, maxK = _hclust_cuts(*source, exact=True)
         dist = _lib.partition_distances(cuts, S, want_sq=loss == "binder", want_phi=loss != "binder", device=device)
         losses, num = _expected_from_parts(dist, loss, n)
         K = min(range(maxK), key=lambda k: (num[k], k)) + 1
         info = dict(merges=res["merges"], binder_num=res["binder_num"], kernel_ms=res["kernel_ms"], counts_ms=res["counts_ms"],
                     distances_ms=dist["kernel_ms"], loss=losses, loss_num=num, K=K)
         return cuts[K - 1].copy(), info
-    if loss not in _PSM_LOSSES:
-        raise ValueError("Invalid loss function specifier.")
-    if linkage not in _LINKAGES:
-        raise ValueError("Invalid linkage specifier.")
-    S, counts, m, n = _counts_input(samples_or_counts, numsamples, ctx)
-    maxK = int(maxK) if maxK else -(-n // 8)
-    if not 1 <= maxK <= n:
-        raise ValueError("maxK must lie in 1..n")
-    res = _lib.hclust(counts, m, _LINKAGES[linkage], maxcut=maxK if loss == "VI" else 0, device=device, ctx=ctx, samples=S)
+    res, _, _, m, n, maxK = _hclust_cuts(*source, vilb=loss == "VI", cuts=False)    # one cut, for the chosen K
     info = dict(merges=res["merges"], binder_num=res["binder_num"], kernel_ms=res["kernel_ms"])
     if loss == "binder":
         pairs = n * (n - 1) // 2

@@ -1,7 +1,7 @@
 // Host utilities of the entry points that own their device memory for one call (most of them take a device number and no
-// context): a holder of device buffers, a pair of timing events, the check of a label matrix, the tests' environment switches,
-// the dynamic-LDS attribute, the device selection; and what the consumers of a co-clustering count matrix share: the n that fits
-// a workgroup's LDS, the capacity check and the device check of the matrix (k_check_counts, check_counts) — how the matrix
+// context): a holder of device buffers, a pair of timing events, the checks of a label matrix, of its shape and of its rows' r
+// and p, the tests' environment switches, the dynamic-LDS attribute, the device selection; and what the consumers of a
+// co-clustering count matrix share: the n that fits a workgroup's LDS, the capacity check and the device check of the matrix (k_check_counts, check_counts) — how the matrix
 // gets onto the device is cnt:: in samplecounts.inc.hip, not here.  Included at the end of redclust_hip.hip after
 // labels.inc.hpp and before every other include (same translation unit: shares fail() and HIPCHK — HIPCHK(nullptr, call)
 // reports into the thread's error buffer).  Both holders release on scope exit, so a HIPCHK may return from anywhere.
@@ -60,6 +60,28 @@ static int32_t check_label_rows(rc_ctx *c, const char *who, const char *what, co
     if (!find_bad_label(rows, count, n, 1, &r, &j)) return RC_OK;
     return fail(c, RC_ERR_ARG, "%s: label %lld of %s %lld at position %lld outside 1..n", who, (long long)rows[(size_t)r * n + j], what,
                 (long long)r + 1, (long long)j + 1);
+}
+
+// The shape of a matrix of label rows whose point indices are kept in u16 with bit 15 free for a mark and whose entries are
+// indexed in 31 bits: n <= INDEX15_NMAX and rows·n < 2^31.  points: what the n are in the message ("points", "training
+// points"); sym: the letter the rows go by there ("m", "L").
+constexpr int64_t INDEX15_NMAX = 32767;
+static int32_t check_label_shape(rc_ctx *c, const char *who, int64_t n, const char *points, int64_t rows, const char *sym)
+{
+    if (n > INDEX15_NMAX) return fail(c, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %lld %s whose indices fit 15 bits", who, (long long)n, (long long)INDEX15_NMAX, points);
+    if (rows >= ((int64_t)1 << 31) / n + (((int64_t)1 << 31) % n != 0)) return fail(c, RC_ERR_CAPACITY, "%s: %s·n = %lld·%lld is not below 2^31", who, sym, (long long)rows, (long long)n);
+    return RC_OK;
+}
+
+// r positive and finite (normal: and no subnormal) and p in (0, 1) for each of `count` rows (each `what`); a null r or p passes
+static int32_t check_r_p(rc_ctx *c, const char *who, const char *what, int64_t count, const double *r, const double *p, bool normal = false)
+{
+    for (int64_t s = 0; s < count; ++s) {
+        if (r && !(r[s] <= 1.79769313486231570e308 && (normal ? r[s] >= 2.2250738585072014e-308 : r[s] > 0)))
+            return fail(c, RC_ERR_ARG, "%s: r of %s %lld must be %s", who, what, (long long)s + 1, normal ? "a positive, normal and finite number" : "positive and finite");
+        if (p && !(p[s] > 0 && p[s] < 1)) return fail(c, RC_ERR_ARG, "%s: p of %s %lld must lie in (0, 1)", who, what, (long long)s + 1);
+    }
+    return RC_OK;
 }
 
 // The switches the tests set in the environment, read per call: an integer (0 when unset), a flag, and a workspace in KiB that

@@ -17,6 +17,21 @@ static inline bool find_bad_label(const int64_t *rows, int64_t count, int64_t n,
     return false;
 }
 
+// K[r] = the number of distinct labels of row r, for `count` rows of n labels in 1..n (checked by the caller), up to and
+// including the first row with more than cap: returns that row, or count if there is none.  seen: n + 1 scratch, all -1.
+static inline int64_t count_clusters(const int64_t *rows, int64_t count, int64_t n, int64_t cap, std::vector<int> &seen, int *K)
+{
+    for (int64_t r = 0; r < count; ++r) {
+        const int64_t *z = rows + (size_t)r * n;
+        int k = 0;
+        for (int64_t j = 0; j < n; ++j)
+            if (seen[(size_t)z[j]] != (int)r) { seen[(size_t)z[j]] = (int)r; ++k; }
+        K[r] = k;
+        if (k > cap) return r;
+    }
+    return count;
+}
+
 // One labelling z (n labels in 1..n, checked by the caller) compacted to slots 0..K-1 in ascending label order: id[label] is
 // the slot, and slot(t, label, size) is called once per slot, in that order.  Returns K.  cnt: n + 1 zeros, left zeroed;
 // id: n + 1 scratch.

@@ -27,7 +27,6 @@
 
 namespace partdist {
 
-constexpr int64_t NMAX = 32767;                 // u16 point indices with bit 15 free for the end-of-cluster mark
 constexpr int64_t LMAX = 65536;
 constexpr int WPB = 8, TPB = WPB * 64;          // labellings (waves) per workgroup
 constexpr int KLDS = 1024;                      // cells of a wave's LDS histogram
@@ -232,10 +231,10 @@ extern "C" int32_t rc_partition_distances(int32_t device, const int64_t *samples
     const char *who = "rc_partition_distances";
     if (!samples || !labels) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
     if (m < 1 || n < 1 || L < 1) return fail(nullptr, RC_ERR_ARG, "%s: need m >= 1, n >= 1 and L >= 1 (got m=%lld n=%lld L=%lld)", who, (long long)m, (long long)n, (long long)L);
-    if (n > NMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %lld points whose indices fit 15 bits", who, (long long)n, (long long)NMAX);
-    if (m >= ((int64_t)1 << 31) / n + (((int64_t)1 << 31) % n != 0)) return fail(nullptr, RC_ERR_CAPACITY, "%s: m·n = %lld·%lld is not below 2^31", who, (long long)m, (long long)n);
+    int32_t rc = check_label_shape(nullptr, who, n, "points", m, "m");   // u16 point indices with bit 15 free for the end-of-cluster mark
+    if (rc != RC_OK) return rc;
     if (L > LMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: L = %lld exceeds %lld labellings per call", who, (long long)L, (long long)LMAX);
-    int32_t rc = check_label_rows(nullptr, who, "sample", samples, m, n);
+    rc = check_label_rows(nullptr, who, "sample", samples, m, n);
     if (rc != RC_OK) return rc;
     rc = check_label_rows(nullptr, who, "labelling", labels, L, n);
     if (rc != RC_OK) return rc;

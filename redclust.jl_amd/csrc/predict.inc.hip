@@ -4,116 +4,25 @@
 // points, grouped by the sample's labels, and a Gumbel-max draw.  New points are conditionally independent given a sample, so
 // every (sample, new point) pair is its own problem.  DESIGN.md §8 "Predict"; the contract is in include/redclust_hip.h.
 // Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, check_params, size_table, flog_table,
-// quant_exponent, rc_philox, rc_flog / rc_flog1p / rc_gumbel and the holders and select_device of hostutil.inc.hip).
+// quant_exponent, rc_philox, rc_flog / rc_flog1p / rc_gumbel, the holders, checks and select_device of hostutil.inc.hip).
 //
 // Fixed point, per new point: its row of D and its row of logD are quantised with exponents of their own (quant_exponent on
 // the row), so a point's result does not depend on which other points share the call.  Every sum is an exact int64.
 //
-// Host, per sample: the labels are compacted to slots 0..K-1 in ascending label order and the training points are sorted by
-// slot (counting sort).  The sorted order is stored transposed, perm[j][s] (u16: point index, bit 15 set on the last point
-// of its slot), so 64 lanes that own 64 consecutive samples read 128 contiguous bytes per step.  Everything of a score that
-// depends only on (sample, slot) — A[size] + (log p + log(size - 1 + r)) — and the new cluster's score are computed there
-// too, once, instead of once per new point.
+// The sums are the slab driver's (slab.inc.hip): the samples are its labellings, the new points' rows, quantised here on the
+// host, its rows; RC_PREDICT_WORKSPACE_KIB and RC_PREDICT_ROWS_GLOBAL are its switches for this entry point.  Everything of a
+// score that depends only on (sample, slot) — A[size] + (log p + log(size - 1 + r)) — and the new cluster's score are computed
+// on the host, once, instead of once per new point; k_predict_sums does no scoring either: at a slot boundary it would run one
+// lane at a time.
 //
-// k_predict_sums (phase 1, the q·m·n integer adds): one workgroup per new point.  Its row is staged in LDS as interleaved
-// (Dq, Lq) pairs, 16 bytes per training point, so one 128-bit LDS gather fetches both addends; rows beyond the LDS (n > 10240)
-// or RC_PREDICT_ROWS_GLOBAL=1 gather from global memory instead — the same integers.  A lane owns (sample, part of the sorted
-// order), adds into two int64 registers and at every slot boundary flushes them to the (point, sample, slot) sums: a plain
-// store when a sample is one part, 64-bit integer atomic adds when the workgroup has more lanes than samples and cuts every
-// sample into parts (exact in any order).  No scoring here: at a boundary it would run one lane at a time.
-// k_predict_draw (phase 2): one wave per (sample, new point), one lane per candidate: score, Philox, noise; then a wave
+// k_predict_draw: one wave per (sample, new point), one lane per candidate: score, Philox, noise; then a wave
 // argmax whose key (value, then smaller label, the new cluster last) gives the tie rule whatever the reduction order.
 
 namespace prd {
 
-constexpr int64_t NMAX = 32767;                 // u16 point indices with bit 15 free for the boundary mark
-constexpr int TPB1 = 1024, TPB2 = 256;
-constexpr int64_t LDS_ROW_MAX_N = 160 * 1024 / 16;
-constexpr size_t WORKSPACE = (size_t)1 << 30;   // device bytes per chunk that scale with the number of new points
-constexpr size_t PERM_BYTES = (size_t)1 << 29;  // ... and the most the sorted orders of one chunk of samples take
+constexpr int TPB2 = 256;
 constexpr unsigned TAG = 0x50524544u;           // "PRED": key (seed_lo, seed_hi ^ TAG), counter (label, point, sample_lo, sample_hi)
 constexpr unsigned KEY_NEW = 0x7FFFFFFFu, KEY_NONE = 0xFFFFFFFFu;
-
-template <bool ATOMIC> __device__ __forceinline__ void flush(ll2 *o, long long sd, long long sl)
-{
-    if (ATOMIC) {
-        atomicAdd((u64 *)o, (u64)sd);
-        atomicAdd((u64 *)o + 1, (u64)sl);
-    } else {
-        ll2 v; v.x = sd; v.y = sl;
-        *o = v;
-    }
-}
-
-// The walk of one row (in LDS or global memory) through the sorted orders of ms samples, shared with the scoring of labellings
-// (score.inc.hip): perm: [n][ms_pad]; koff: [ms] first slot of every sample; startslot: [parts][ms_pad] slot of a part's first
-// position (ATOMIC only); out: the row's [ktot] sums.
-template <bool ATOMIC>
-__device__ __forceinline__ void walk_sums(const ll2 *__restrict__ row, int n, const unsigned short *__restrict__ perm, int ms, int ms_pad, int parts,
-                                          const int *__restrict__ startslot, const long long *__restrict__ koff, ll2 *__restrict__ out)
-{
-    for (int w = threadIdx.x; w < ms_pad * parts; w += blockDim.x) {
-        const int part = w / ms_pad, s = w - part * ms_pad;
-        if (s >= ms) continue;
-        const int j0 = (int)((long long)part * n / parts), j1 = (int)((long long)(part + 1) * n / parts);
-        ll2 *o = out + koff[s] + (ATOMIC ? startslot[w] : 0);
-        const unsigned short *pp = perm + (size_t)j0 * (size_t)ms_pad + s;
-        long long sd = 0, sl = 0;
-        unsigned e = 0x8000u;
-        // Batches of NB steps: the NB entries of the sorted order are requested one batch ahead and the NB row gathers are
-        // issued together, so a lane waits once per batch for either memory, not once per step — a flush is a branch, and
-        // across a branch the compiler keeps no load in flight.  (The prefetch past the part's end re-reads its last entry.)
-        constexpr int NB = 8;
-        unsigned en[NB];
-        int j = j0;
-        if (j + NB <= j1) {
-#pragma unroll
-            for (int u = 0; u < NB; ++u) en[u] = pp[(size_t)u * ms_pad];
-        }
-        for (; j + NB <= j1; j += NB) {
-            unsigned ec[NB];
-            ll2 v[NB];
-#pragma unroll
-            for (int u = 0; u < NB; ++u) ec[u] = en[u];
-#pragma unroll
-            for (int u = 0; u < NB; ++u) en[u] = pp[(size_t)(min(j + NB + u, j1 - 1) - j) * ms_pad];
-#pragma unroll
-            for (int u = 0; u < NB; ++u) v[u] = row[ec[u] & 0x7FFFu];
-#pragma unroll
-            for (int u = 0; u < NB; ++u) {
-                sd += v[u].x; sl += v[u].y;
-                if (ec[u] & 0x8000u) { flush<ATOMIC>(o, sd, sl); ++o; sd = 0; sl = 0; }
-            }
-            e = ec[NB - 1];
-            pp += (size_t)NB * ms_pad;
-        }
-        for (; j < j1; ++j, pp += ms_pad) {
-            e = *pp;
-            const ll2 v = row[e & 0x7FFFu];
-            sd += v.x; sl += v.y;
-            if (e & 0x8000u) { flush<ATOMIC>(o, sd, sl); ++o; sd = 0; sl = 0; }
-        }
-        if (ATOMIC && !(e & 0x8000u)) flush<ATOMIC>(o, sd, sl);   // the part ends inside a slot
-    }
-}
-
-// rows: [points][n] (Dq, Lq); sums: [points][ktot]; the rest as walk_sums.  Grid: one block per point.
-template <bool LDSROW, bool ATOMIC>
-__global__ __launch_bounds__(TPB1) void k_predict_sums(const ll2 *__restrict__ rows, int n, const unsigned short *__restrict__ perm, int ms, int ms_pad,
-                                                       int parts, const int *__restrict__ startslot, const long long *__restrict__ koff, long long ktot,
-                                                       ll2 *__restrict__ sums)
-{
-    extern __shared__ __align__(16) unsigned char prd_lds[];
-    const ll2 *grow = rows + (size_t)blockIdx.x * (size_t)n;
-    const ll2 *row = grow;
-    if (LDSROW) {
-        ll2 *l = reinterpret_cast<ll2 *>(prd_lds);
-        for (int j = threadIdx.x; j < n; j += blockDim.x) l[j] = grow[j];
-        __syncthreads();
-        row = l;
-    }
-    walk_sums<ATOMIC>(row, n, perm, ms, ms_pad, parts, startslot, koff, sums + (size_t)blockIdx.x * (size_t)ktot);
-}
 
 struct DrawArgs {
     int ms, npts, Kmax;                     // Kmax: columns of the optional outputs (0 when neither is asked for)
@@ -214,88 +123,6 @@ struct Call {
     bool rows_global;
 };
 
-// The preparation of a run of samples that predict and the joint predict (predictjoint.inc.hip) share: the sorted orders on the
-// host and the device, and the launch of k_predict_sums over them.
-struct Orders {
-    int64_t n = 0, ms = 0;
-    int ms_pad = 0, parts = 1;
-    long long ktot = 0;
-    std::vector<unsigned short> perm;       // [n][ms_pad]
-    std::vector<int> startslot, Ks;         // [parts][ms_pad]; [ms]
-    std::vector<long long> koff;            // [ms]
-    std::vector<int2> szlab;                // [ktot] (size, label)
-    unsigned short *d_perm = nullptr; int *d_startslot = nullptr, *d_K = nullptr; long long *d_koff = nullptr; int2 *d_szlab = nullptr;
-
-    // samples s0 .. s0 + ms - 1 of the m×n matrix, K: the cluster counts of all m; slot(s, at, label, size) once per slot of
-    // sample s, `at` its index among the ktot slots.  false: no host memory.
-    template <typename Slot>
-    bool build(const int64_t *samples, int64_t n_, const int *K, int64_t s0, int64_t ms_, Slot slot)
-    {
-        n = n_; ms = ms_;
-        ms_pad = (int)((ms + 63) / 64 * 64);
-        parts = ms_pad >= TPB1 ? 1 : (int)std::min<int64_t>(TPB1 / ms_pad, n);
-        std::vector<int> partat, cnt, slot_of_label, pos;
-        ktot = 0;
-        try {
-            perm.assign((size_t)n * ms_pad, 0);
-            startslot.assign((size_t)parts * ms_pad, 0);
-            partat.assign((size_t)n, -1);
-            cnt.assign((size_t)n + 1, 0); slot_of_label.assign((size_t)n + 1, 0); pos.assign((size_t)n, 0);
-            koff.resize((size_t)ms); Ks.resize((size_t)ms);
-            for (int64_t s = 0; s < ms; ++s) ktot += K[s0 + s];
-            szlab.resize((size_t)ktot);
-        } catch (const std::bad_alloc &) { return false; }
-        for (int p = 0; p < parts; ++p) partat[(size_t)((long long)p * n / parts)] = p;
-        long long k0 = 0;
-        for (int64_t s = 0; s < ms; ++s) {
-            const int64_t *z = samples + (size_t)(s0 + s) * n;
-            const int Ks_ = cluster_order(z, n, cnt, slot_of_label, pos,
-                [&](int t, int64_t l, int sz) {
-                    szlab[(size_t)(k0 + t)] = make_int2(sz, (int)l);
-                    slot(s, k0 + t, l, sz);
-                },
-                [&](int at_, int64_t j, int t) {
-                    perm[(size_t)at_ * ms_pad + s] = (unsigned short)j;
-                    if (partat[(size_t)at_] >= 0) startslot[(size_t)partat[(size_t)at_] * ms_pad + s] = t;
-                });
-            koff[(size_t)s] = k0; Ks[(size_t)s] = Ks_;
-            // after the fill pos[t] is one past slot t's last position: mark those
-            for (int t = 0; t < Ks_; ++t) perm[(size_t)(pos[(size_t)t] - 1) * ms_pad + s] |= 0x8000u;
-            k0 += Ks_;
-        }
-        return true;
-    }
-
-    hipError_t upload(DeviceBuffers &B)
-    {
-        hipError_t e;
-        if ((e = B.alloc(d_perm, perm.size())) != hipSuccess) return e;
-        if ((e = B.alloc(d_startslot, startslot.size())) != hipSuccess) return e;
-        if ((e = B.alloc(d_K, (size_t)ms)) != hipSuccess) return e;
-        if ((e = B.alloc(d_koff, (size_t)ms)) != hipSuccess) return e;
-        if ((e = B.alloc(d_szlab, (size_t)ktot)) != hipSuccess) return e;
-        if ((e = hipMemcpy(d_perm, perm.data(), perm.size() * sizeof(unsigned short), hipMemcpyHostToDevice)) != hipSuccess) return e;
-        if ((e = hipMemcpy(d_startslot, startslot.data(), startslot.size() * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess) return e;
-        if ((e = hipMemcpy(d_K, Ks.data(), (size_t)ms * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess) return e;
-        if ((e = hipMemcpy(d_koff, koff.data(), (size_t)ms * sizeof(long long), hipMemcpyHostToDevice)) != hipSuccess) return e;
-        return hipMemcpy(d_szlab, szlab.data(), (size_t)ktot * sizeof(int2), hipMemcpyHostToDevice);
-    }
-
-    // the [np][ktot] sums of np rows ([np][n] (Dq, Lq)) on stream 0; rows_global: gather from global memory at any n
-    hipError_t launch_sums(const ll2 *d_rows, int64_t np, bool rows_global, ll2 *d_sums) const
-    {
-        const bool ldsrow = !rows_global && n <= LDS_ROW_MAX_N;
-        const size_t lds = ldsrow ? (size_t)n * sizeof(ll2) : 0;
-        auto kern = ldsrow ? (parts > 1 ? k_predict_sums<true, true> : k_predict_sums<true, false>)
-                           : (parts > 1 ? k_predict_sums<false, true> : k_predict_sums<false, false>);
-        hipError_t e = set_dynamic_lds(kern, lds);
-        if (e != hipSuccess) return e;
-        if (parts > 1 && (e = hipMemsetAsync(d_sums, 0, (size_t)np * ktot * sizeof(ll2), 0)) != hipSuccess) return e;   // the parts add into zeros
-        kern<<<(unsigned)np, TPB1, lds, 0>>>(d_rows, (int)n, d_perm, (int)ms, ms_pad, parts, d_startslot, d_koff, ktot, d_sums);
-        return hipGetLastError();
-    }
-};
-
 // samples s0 .. s0 + ms - 1 against every new point, the points in chunks of at most qc.  ms_acc: device milliseconds, added to.
 static int32_t run_samples(const char *who, const Call &c, int64_t s0, int64_t ms, int64_t qc, double &ms_acc)
 {
@@ -310,7 +137,7 @@ static int32_t run_samples(const char *who, const Call &c, int64_t s0, int64_t m
         for (int64_t s = 0; s < ms; ++s) kt += c.K[s0 + s];
         base.resize((size_t)kt); newscore.resize((size_t)ms);
     } catch (const std::bad_alloc &) { ok = false; }
-    ok = ok && O.build(c.samples, n, c.K, s0, ms, [&](int64_t s, long long at, int64_t, int sz) {
+    ok = ok && O.build(c.samples, n, c.K, s0, ms, false, [&](int64_t s, long long at, int64_t, int sz) {
         base[(size_t)at] = c.A[sz] + (std::log(c.p[s0 + s]) + std::log((double)sz - 1.0 + c.r[s0 + s]));
     });
     if (!ok) return fail(nullptr, RC_ERR_OOM, "%s: no host memory for the sorted orders of %lld samples", who, (long long)ms);
@@ -409,14 +236,12 @@ extern "C" int32_t rc_predict(int32_t device, int64_t n, int64_t q, const double
     const char *who = "rc_predict";
     if (!Dnew || !samples || !r || !p || !params || !labels_out) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
     if (n < 1 || q < 1 || m < 1) return fail(nullptr, RC_ERR_ARG, "%s: need n >= 1, q >= 1 and m >= 1 (got n=%lld q=%lld m=%lld)", who, (long long)n, (long long)q, (long long)m);
-    if (n > prd::NMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %lld training points whose indices fit 15 bits", who, (long long)n, (long long)prd::NMAX);
-    if (m >= ((int64_t)1 << 31) / n + (((int64_t)1 << 31) % n != 0)) return fail(nullptr, RC_ERR_CAPACITY, "%s: m·n = %lld·%lld is not below 2^31", who, (long long)m, (long long)n);
-    int32_t rc = check_params(nullptr, who, params);
+    int32_t rc = check_label_shape(nullptr, who, n, "training points", m, "m");
     if (rc != RC_OK) return rc;
-    for (int64_t s = 0; s < m; ++s) {
-        if (!(r[s] > 0 && r[s] <= 1.79769313486231570e308)) return fail(nullptr, RC_ERR_ARG, "%s: r of sample %lld must be positive and finite", who, (long long)s + 1);
-        if (!(p[s] > 0 && p[s] < 1)) return fail(nullptr, RC_ERR_ARG, "%s: p of sample %lld must lie in (0, 1)", who, (long long)s + 1);
-    }
+    rc = check_params(nullptr, who, params);
+    if (rc != RC_OK) return rc;
+    rc = check_r_p(nullptr, who, "sample", m, r, p);
+    if (rc != RC_OK) return rc;
     rc = check_label_rows(nullptr, who, "sample", samples, m, n);
     if (rc != RC_OK) return rc;
     const bool want_tab = scores_out || sums_out;
@@ -424,14 +249,8 @@ extern "C" int32_t rc_predict(int32_t device, int64_t n, int64_t q, const double
     std::vector<double> A;
     try { K.assign((size_t)m, 0); eD.resize((size_t)q); eL.resize((size_t)q); seen.assign((size_t)n + 1, -1); A.resize((size_t)n + 1); }
     catch (const std::bad_alloc &) { return fail(nullptr, RC_ERR_OOM, "%s: no host memory", who); }
-    for (int64_t s = 0; s < m; ++s) {
-        const int64_t *z = samples + (size_t)s * n;
-        int k = 0;
-        for (int64_t j = 0; j < n; ++j)
-            if (seen[(size_t)z[j]] != (int)s) { seen[(size_t)z[j]] = (int)s; ++k; }
-        K[(size_t)s] = k;
-        if (want_tab && k > Kmax) return fail(nullptr, RC_ERR_ARG, "%s: sample %lld has %d clusters, Kmax = %lld", who, (long long)s + 1, k, (long long)Kmax);
-    }
+    const int64_t over = count_clusters(samples, m, n, want_tab ? Kmax : n, seen, K.data());
+    if (over < m) return fail(nullptr, RC_ERR_ARG, "%s: sample %lld has %d clusters, Kmax = %lld", who, (long long)over + 1, K[(size_t)over], (long long)Kmax);
     for (int64_t i = 0; i < q; ++i) {
         const double *x = Dnew + (size_t)i * n, *lx = logDnew_or_null ? logDnew_or_null + (size_t)i * n : nullptr;
         double lo = INFINITY, hi = 0.0, lmax = 0.0;
@@ -467,23 +286,15 @@ extern "C" int32_t rc_predict(int32_t device, int64_t n, int64_t q, const double
     // Chunks.  Device bytes per new point for a run of samples: its row, and per sample its slots' sums, two labels and the
     // optional columns.  Samples are taken while 512 points (or all q) of them fit the workspace and their sorted orders fit
     // theirs; the points then go in chunks of what fits.
-    const size_t workspace = env_workspace_kib("RC_PREDICT_WORKSPACE_KIB", prd::WORKSPACE);
+    const size_t workspace = env_workspace_kib("RC_PREDICT_WORKSPACE_KIB", slab::WORKSPACE);
     const size_t per_sample = 16 + (scores_out ? 8 * ((size_t)c.Kmax + 1) : 0) + (sums_out ? 16 * (size_t)c.Kmax : 0);
-    const int64_t qt = std::min<int64_t>(q, 512);
-    const int64_t ms_cap = std::max<int64_t>(64, (int64_t)(prd::PERM_BYTES / 2 / (size_t)n) / 64 * 64);
+    const int64_t ms_cap = slab_ms_cap(slab::PERM_BYTES, 2, n);
     double ms_acc = 0.0;
     for (int64_t s0 = 0; s0 < m;) {
-        size_t bytes = 16 * (size_t)n;
-        int64_t ms = 0;
-        while (s0 + ms < m && ms < ms_cap) {
-            const size_t add = 16 * (size_t)K[(size_t)(s0 + ms)] + per_sample;
-            if (ms > 0 && (bytes + add) * (size_t)qt > workspace) break;
-            bytes += add; ++ms;
-        }
-        const int64_t qc = std::max<int64_t>(1, std::min<int64_t>(q, (int64_t)(workspace / bytes)));
-        rc = prd::run_samples(who, c, s0, ms, qc, ms_acc);
+        const SlabChunk ch = slab_plan(s0, K.data(), m, ms_cap, 16 * (size_t)n, per_sample, q, std::min<int64_t>(q, 512), workspace);
+        rc = prd::run_samples(who, c, s0, ch.ms, ch.qc, ms_acc);
         if (rc != RC_OK) return rc;
-        s0 += ms;
+        s0 += ch.ms;
     }
     if (kernel_ms) *kernel_ms = ms_acc;
     return RC_OK;

@@ -3,8 +3,10 @@
 // y_1..y_q of the new points, which start unallocated.  A visit of new point i is the Gibbs full conditional (src/mcmc.jl:192-252)
 // of point n+i of the (n+q)-point problem in which the unallocated points do not exist; pass 0 visits 1..q in order (sequential
 // allocation), `sweeps` further passes visit them again (Gibbs on the new labels given the training labels).  DESIGN.md §8
-// "Joint predict"; the contract is in include/redclust_hip.h.  Included at the end of redclust_hip.hip after predict.inc.hip,
-// whose sorted orders, k_predict_sums and tie rule (prd::Orders, prd::better) it uses.
+// "Joint predict"; the contract is in include/redclust_hip.h.  Included at the end of redclust_hip.hip after slab.inc.hip, whose
+// sorted orders and k_predict_sums give the base sums (the samples are its labellings, the new points' training parts its rows,
+// all q together; RC_PREDICT_WORKSPACE_KIB and RC_PREDICT_ROWS_GLOBAL are its switches here too), and after predict.inc.hip,
+// whose tie rule (prd::better) it uses.
 //
 // Fixed point: new point i's row is the n entries of Dnew[i] followed by the q entries of Dnn[i] (the diagonal entry counts as
 // 0), quantised with one exponent of its own for n + q addends; its logarithms likewise.  Every sum is an exact int64.
@@ -204,16 +206,14 @@ extern "C" int32_t rc_predict_joint(int32_t device, int64_t n, int64_t q, const 
     if ((logDnew_or_null == nullptr) != (logDnn_or_null == nullptr)) return fail(nullptr, RC_ERR_ARG, "%s: give logDnew and logDnn together or neither", who);
     if (n < 1 || q < 1 || m < 1) return fail(nullptr, RC_ERR_ARG, "%s: need n >= 1, q >= 1 and m >= 1 (got n=%lld q=%lld m=%lld)", who, (long long)n, (long long)q, (long long)m);
     if (sweeps < 0) return fail(nullptr, RC_ERR_ARG, "%s: sweeps must be >= 0 (got %lld)", who, (long long)sweeps);
-    if (n > prd::NMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %lld training points whose indices fit 15 bits", who, (long long)n, (long long)prd::NMAX);
-    if (m >= ((int64_t)1 << 31) / n + (((int64_t)1 << 31) % n != 0)) return fail(nullptr, RC_ERR_CAPACITY, "%s: m·n = %lld·%lld is not below 2^31", who, (long long)m, (long long)n);
+    int32_t rc = check_label_shape(nullptr, who, n, "training points", m, "m");
+    if (rc != RC_OK) return rc;
     if (q >= prdj::SLOT_MAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: q = %lld new points and a cluster do not fit the %lld slots of a sample; call in blocks", who, (long long)q, (long long)prdj::SLOT_MAX);
     if (sweeps >= (((int64_t)1 << 32) - 1) / q) return fail(nullptr, RC_ERR_ARG, "%s: (sweeps + 1)·q = (%lld + 1)·%lld is not below 2^32", who, (long long)sweeps, (long long)q);
-    int32_t rc = check_params(nullptr, who, params);
+    rc = check_params(nullptr, who, params);
     if (rc != RC_OK) return rc;
-    for (int64_t s = 0; s < m; ++s) {
-        if (!(r[s] >= 2.2250738585072014e-308 && r[s] <= 1.79769313486231570e308)) return fail(nullptr, RC_ERR_ARG, "%s: r of sample %lld must be a positive, normal and finite number", who, (long long)s + 1);
-        if (!(p[s] > 0 && p[s] < 1)) return fail(nullptr, RC_ERR_ARG, "%s: p of sample %lld must lie in (0, 1)", who, (long long)s + 1);
-    }
+    rc = check_r_p(nullptr, who, "sample", m, r, p, true);
+    if (rc != RC_OK) return rc;
     rc = check_label_rows(nullptr, who, "sample", samples, m, n);
     if (rc != RC_OK) return rc;
     const int64_t N = n + q;
@@ -222,15 +222,9 @@ extern "C" int32_t rc_predict_joint(int32_t device, int64_t n, int64_t q, const 
     std::vector<ll2> rowt, rown;
     try { K.assign((size_t)m, 0); seen.assign((size_t)n + 1, -1); }
     catch (const std::bad_alloc &) { return fail(nullptr, RC_ERR_OOM, "%s: no host memory", who); }
-    for (int64_t s = 0; s < m; ++s) {
-        const int64_t *z = samples + (size_t)s * n;
-        int k = 0;
-        for (int64_t j = 0; j < n; ++j)
-            if (seen[(size_t)z[j]] != (int)s) { seen[(size_t)z[j]] = (int)s; ++k; }
-        K[(size_t)s] = k;
-        if (k + q > prdj::SLOT_MAX)
-            return fail(nullptr, RC_ERR_CAPACITY, "%s: sample %lld has %d clusters; with q = %lld new points that exceeds the %lld slots of a sample; call in blocks", who, (long long)s + 1, k, (long long)q, (long long)prdj::SLOT_MAX);
-    }
+    const int64_t over = count_clusters(samples, m, n, prdj::SLOT_MAX - q, seen, K.data());
+    if (over < m)
+        return fail(nullptr, RC_ERR_CAPACITY, "%s: sample %lld has %d clusters; with q = %lld new points that exceeds the %lld slots of a sample; call in blocks", who, (long long)over + 1, K[(size_t)over], (long long)q, (long long)prdj::SLOT_MAX);
     try {
         eD.resize((size_t)q); eL.resize((size_t)q); A.resize((size_t)N + 1); scD.resize((size_t)q); scL.resize((size_t)q);
         rowt.resize((size_t)q * n); rown.resize((size_t)q * q);
@@ -301,30 +295,23 @@ extern "C" int32_t rc_predict_joint(int32_t device, int64_t n, int64_t q, const 
 
     // Chunks of samples: the base sums of a chunk, q·16·ΣK_s bytes, fit the workspace (one sample always goes), and its sorted
     // orders fit theirs.  The new points of a call always travel together.
-    const size_t workspace = env_workspace_kib("RC_PREDICT_WORKSPACE_KIB", prd::WORKSPACE);
-    const int64_t ms_cap = std::max<int64_t>(64, (int64_t)(prd::PERM_BYTES / 2 / (size_t)n) / 64 * 64);
+    const size_t workspace = env_workspace_kib("RC_PREDICT_WORKSPACE_KIB", slab::WORKSPACE);
+    const int64_t ms_cap = slab_ms_cap(slab::PERM_BYTES, 2, n);
     const bool rows_global = env_flag("RC_PREDICT_ROWS_GLOBAL");
     const size_t nm = (size_t)sweeps + 1;
     TimingEvents ev;
     HIPCHK(nullptr, ev.create());
     double ms_acc = 0.0;
     for (int64_t s0 = 0; s0 < m;) {
-        size_t bytes = 0;
-        int64_t ms = 0, Smax = 0;
-        while (s0 + ms < m && ms < ms_cap) {
-            const size_t add = 16 * (size_t)K[(size_t)(s0 + ms)] * (size_t)q;
-            if (ms > 0 && bytes + add > workspace) break;
-            bytes += add;
-            Smax = std::max<int64_t>(Smax, K[(size_t)(s0 + ms)] + q);
-            ++ms;
-        }
+        const int64_t ms = slab_plan(s0, K.data(), m, ms_cap, 0, 0, q, q, workspace).ms;   // no row of its own, q rows at once
+        const int64_t Smax = *std::max_element(K.begin() + s0, K.begin() + s0 + ms) + q;
         prd::Orders O;
         std::vector<int> freelab;
         std::vector<double> logp, log1mp;
         bool ok = true;
         try { freelab.resize((size_t)ms * q); logp.resize((size_t)ms); log1mp.resize((size_t)ms); seen.assign((size_t)N + 2, 0); }
         catch (const std::bad_alloc &) { ok = false; }
-        ok = ok && O.build(samples, n, K.data(), s0, ms, [](int64_t, long long, int64_t, int) {});
+        ok = ok && O.build(samples, n, K.data(), s0, ms, false, [](int64_t, long long, int64_t, int) {});
         if (!ok) return fail(nullptr, RC_ERR_OOM, "%s: no host memory for the sorted orders of %lld samples", who, (long long)ms);
         for (int64_t s = 0; s < ms; ++s) {
             // the q smallest labels of 1..n+q that sample s does not use, ascending

@@ -3,8 +3,8 @@
 // of L given labellings against a context's staged fixed-point D, without touching its state.  The silhouette width
 // (Rousseeuw 1987) is host arithmetic on these integers.  DESIGN.md §8 "Cluster profiles"; the contract is in
 // include/redclust_hip.h.
-// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, View, sync_and_check, the holders and
-// switches of hostutil.inc.hip, clu::check_ctx, and predict.inc.hip's Orders and k_predict_sums).
+// Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, View, sync_and_check, the holders,
+// checks and switches of hostutil.inc.hip, clu::check_ctx and slab.inc.hip).
 //
 // Definitions.  Dq is the integer matrix, D = Dq·2^-eD, caller's point order; the diagonal entry Dq[i][i] never counts.  A
 // labelling's K clusters are listed in ascending label order, slots 0..K−1 of sizes n_k; A(i) is the slot of point i.
@@ -15,22 +15,20 @@
 //   medoid of cluster k: its member of minimum within, ties to the smallest point index.
 // Everything is an exact integer, so every output is a pure function of (Dq, labelling) whatever the batch and the chunking.
 //
-// Host, per chunk of labellings: prd::Orders (the labellings compacted and counting-sorted, stored transposed) plus the dense
-// slot of every point, rslot[s][i].
-// k_profile_rows (staging): one workgroup per row of a chunk of rows.  Row i of the caller's order is gathered through View.pi
-// into (Dq, 0) pairs with a 0 at j = i: the diagonal drops out here and no logarithm is ever computed.
-// k_predict_sums (phase 1, the L·n² integer adds): predict's kernel as it stands; the second half of every pair stays zero.
-// k_profile_points: one wave per (row of the chunk, labelling).  Lanes stride over the labelling's slots, each keeps its best
-// (S, n_t, slot) under the exact comparison, a wave reduction with the same comparison finishes; lane 0 stores.
+// The sums S come out of the slab driver (slab.inc.hip): the context's rows, in the caller's order, are its rows, with the dense
+// slot of every point, rslot[s][i], from its sorted orders; RC_PROFILE_WORKSPACE_KIB and RC_PROFILE_ROWS_GLOBAL are its switches
+// for this entry point.
+// k_profile_rows (its staging kernel): one workgroup per row of a chunk of rows.  Row i of the caller's order is gathered through
+// View.pi into (Dq, 0) pairs with a 0 at j = i: the diagonal drops out here, no logarithm is ever computed and the second half of
+// every sum stays zero.
+// k_profile_points (its consumer): one wave per (row of the chunk, labelling).  Lanes stride over the labelling's slots, each
+// keeps its best (S, n_t, slot) under the exact comparison, a wave reduction with the same comparison finishes; lane 0 stores.
 // k_profile_medoids: after all rows of a chunk of labellings, one workgroup per labelling.  Two passes of LDS atomic minima
 // per cluster — on within, then on the point index among the points that attain it: exact in any order of arrival.
 
 namespace prf {
 
-constexpr int64_t KMAX = 4096;                  // clusters of one labelling: 12 B of LDS each in the medoid pass
-constexpr int TPB_ROWS = 256, TPB_POINTS = 256, TPB_MEDOIDS = 256;
-constexpr size_t WORKSPACE = (size_t)1 << 30;   // device bytes per chunk that scale with the number of rows
-constexpr size_t PERM_BYTES = (size_t)1 << 29;  // ... and the most the sorted orders of one chunk of labellings take
+constexpr int TPB_ROWS = 256, TPB_POINTS = 256, TPB_MEDOIDS = 256;   // (slab::KMAX clusters: 12 B of LDS each in the medoid pass)
 
 // rows[b][j] = (Dq[row0 + b][j], 0), caller's order, 0 on the diagonal.  Grid: one block per row of the chunk.
 __global__ __launch_bounds__(TPB_ROWS) void k_profile_rows(View V, int row0, ll2 *__restrict__ rows)
@@ -154,29 +152,14 @@ static int32_t run_labellings(const char *who, const Call &a, int64_t s0, int64_
     const int64_t n = a.n;
     const bool want_points = a.nearest_out || a.neighbour_out;
     prd::Orders O;
-    std::vector<unsigned short> rslot;
-    std::vector<int> slot_of_label;
-    bool ok = true;
-    try { rslot.resize((size_t)ms * n); slot_of_label.assign((size_t)n + 1, 0); } catch (const std::bad_alloc &) { ok = false; }
-    ok = ok && O.build(a.labels, n, a.K, s0, ms, [](int64_t, long long, int64_t, int) {});
-    if (!ok) return fail(c, RC_ERR_OOM, "%s: no host memory for the sorted orders of %lld labellings", who, (long long)ms);
+    if (!O.build(a.labels, n, a.K, s0, ms, true, [](int64_t, long long, int64_t, int) {}))
+        return fail(c, RC_ERR_OOM, "%s: no host memory for the sorted orders of %lld labellings", who, (long long)ms);
     const long long ktot = O.ktot;
-    int Kmax = 1;
-    for (int64_t s = 0; s < ms; ++s) {
-        const int K = O.Ks[(size_t)s];
-        Kmax = std::max(Kmax, K);
-        for (int t = 0; t < K; ++t) slot_of_label[(size_t)O.szlab[(size_t)(O.koff[(size_t)s] + t)].y] = t;
-        dense_ids(a.labels + (size_t)(s0 + s) * n, n, slot_of_label, rslot.data() + (size_t)s * n);
-    }
+    const int Kmax = *std::max_element(O.Ks.begin(), O.Ks.end());
 
     DeviceBuffers B;
-    unsigned short *d_rslot;
-    ll2 *d_rows, *d_sums;
     long long *d_within, *d_nearest = nullptr, *d_neighbour = nullptr, *d_medoid, *d_medoid_within;
     HIPCHK(c, O.upload(B));
-    HIPCHK(c, B.alloc(d_rslot, rslot.size()));
-    HIPCHK(c, B.alloc(d_rows, (size_t)qc * n));
-    HIPCHK(c, B.alloc(d_sums, (size_t)qc * ktot));
     HIPCHK(c, B.alloc(d_within, (size_t)ms * n));
     if (want_points) {
         HIPCHK(c, B.alloc(d_nearest, (size_t)ms * n));
@@ -184,27 +167,19 @@ static int32_t run_labellings(const char *who, const Call &a, int64_t s0, int64_
     }
     HIPCHK(c, B.alloc(d_medoid, (size_t)ktot));
     HIPCHK(c, B.alloc(d_medoid_within, (size_t)ktot));
-    HIPCHK(c, hipMemcpy(d_rslot, rslot.data(), rslot.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
 
+    const int32_t rc = slab::run_rows(c, O, B, qc, a.rows_global, k_profile_rows, TPB_ROWS, [&](const ll2 *d_sums, int64_t i0, int64_t np) {
+        PointArgs p{};
+        p.sums = d_sums; p.ktot = ktot; p.np = (int)np; p.row0 = (int)i0; p.n = (int)n; p.ms = (int)ms; p.rslot = O.d_rslot;
+        p.koff = O.d_koff; p.K = O.d_K; p.szlab = O.d_szlab; p.within = d_within; p.nearest = d_nearest; p.neighbour = d_neighbour;
+        k_profile_points<<<(unsigned)(((size_t)np * ms + TPB_POINTS / 64 - 1) / (TPB_POINTS / 64)), TPB_POINTS, 0, 0>>>(p);
+    }, ms_acc);
+    if (rc != RC_OK) return rc;
     const size_t lds_medoids = (size_t)Kmax * (sizeof(u64) + sizeof(unsigned));
-    const View V = make_view(c);
     TimingEvents ev;
     HIPCHK(c, ev.create());
-    for (int64_t i0 = 0; i0 < n; i0 += qc) {
-        const int64_t np = std::min(qc, n - i0);
-        PointArgs p{};
-        p.sums = d_sums; p.ktot = ktot; p.np = (int)np; p.row0 = (int)i0; p.n = (int)n; p.ms = (int)ms; p.rslot = d_rslot;
-        p.koff = O.d_koff; p.K = O.d_K; p.szlab = O.d_szlab; p.within = d_within; p.nearest = d_nearest; p.neighbour = d_neighbour;
-        HIPCHK(c, ev.begin(0));
-        k_profile_rows<<<(unsigned)np, TPB_ROWS, 0, 0>>>(V, (int)i0, d_rows);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, O.launch_sums(d_rows, np, a.rows_global, d_sums));
-        k_profile_points<<<(unsigned)(((size_t)np * ms + TPB_POINTS / 64 - 1) / (TPB_POINTS / 64)), TPB_POINTS, 0, 0>>>(p);
-        HIPCHK(c, ev.end(0));
-        HIPCHK(c, ev.elapsed_ms(ms_acc));
-    }
     HIPCHK(c, ev.begin(0));
-    k_profile_medoids<<<(unsigned)ms, TPB_MEDOIDS, lds_medoids, 0>>>(d_within, d_rslot, (int)n, O.d_koff, O.d_K, Kmax, d_medoid, d_medoid_within);
+    k_profile_medoids<<<(unsigned)ms, TPB_MEDOIDS, lds_medoids, 0>>>(d_within, O.d_rslot, (int)n, O.d_koff, O.d_K, Kmax, d_medoid, d_medoid_within);
     HIPCHK(c, ev.end(0));
     HIPCHK(c, ev.elapsed_ms(ms_acc));
 
@@ -230,23 +205,17 @@ extern "C" int32_t rc_cluster_profiles(rc_ctx *c, int64_t L, const int64_t *labe
     if (!labels) return fail(c, RC_ERR_ARG, "%s: NULL argument", who);
     if (L < 1) return fail(c, RC_ERR_ARG, "%s: need L >= 1 (got %lld)", who, (long long)L);
     const int64_t n = c->n;
-    if (n > prd::NMAX) return fail(c, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %lld points whose indices fit 15 bits", who, (long long)n, (long long)prd::NMAX);
-    if (L >= ((int64_t)1 << 31) / n + (((int64_t)1 << 31) % n != 0)) return fail(c, RC_ERR_CAPACITY, "%s: L·n = %lld·%lld is not below 2^31", who, (long long)L, (long long)n);
+    rc = check_label_shape(c, who, n, "points", L, "L");
+    if (rc != RC_OK) return rc;
     rc = check_label_rows(c, who, "labelling", labels, L, n);
     if (rc != RC_OK) return rc;
     std::vector<int> K, seen;
     std::vector<int64_t> moff;
     try { K.assign((size_t)L, 0); seen.assign((size_t)n + 1, -1); moff.assign((size_t)L + 1, 0); }
     catch (const std::bad_alloc &) { return fail(c, RC_ERR_OOM, "%s: no host memory", who); }
-    for (int64_t s = 0; s < L; ++s) {
-        const int64_t *z = labels + (size_t)s * n;
-        int k = 0;
-        for (int64_t j = 0; j < n; ++j)
-            if (seen[(size_t)z[j]] != (int)s) { seen[(size_t)z[j]] = (int)s; ++k; }
-        if (k > prf::KMAX) return fail(c, RC_ERR_CAPACITY, "%s: labelling %lld has %d clusters, more than the %lld whose minima fit the workgroup's LDS", who, (long long)s + 1, k, (long long)prf::KMAX);
-        K[(size_t)s] = k;
-        moff[(size_t)s + 1] = moff[(size_t)s] + k;
-    }
+    const int64_t over = count_clusters(labels, L, n, slab::KMAX, seen, K.data());
+    if (over < L) return fail(c, RC_ERR_CAPACITY, "%s: labelling %lld has %d clusters, more than the %lld whose minima fit the workgroup's LDS", who, (long long)over + 1, K[(size_t)over], (long long)slab::KMAX);
+    for (int64_t s = 0; s < L; ++s) moff[(size_t)s + 1] = moff[(size_t)s] + K[(size_t)s];
     const bool want_medoids = medoids_out || medoid_within_out;
     if (medoids_len != (want_medoids ? moff[(size_t)L] : 0))
         return fail(c, RC_ERR_ARG, "%s: medoids_len = %lld, the labellings have %lld clusters%s", who, (long long)medoids_len, (long long)moff[(size_t)L],
@@ -260,22 +229,15 @@ extern "C" int32_t rc_cluster_profiles(rc_ctx *c, int64_t L, const int64_t *labe
     // Chunks.  Device bytes per row for a run of labellings: the staged row and its slots' sums.  Labellings are taken while 512
     // rows (or all n) of them fit the workspace, their sorted orders fit theirs and their per-point results half the workspace;
     // the rows then go in chunks of what fits.
-    const size_t workspace = env_workspace_kib("RC_PROFILE_WORKSPACE_KIB", prf::WORKSPACE);
-    const int64_t qt = std::min<int64_t>(n, 512);
-    const int64_t ms_cap = std::max<int64_t>(64, (int64_t)(prf::PERM_BYTES / 4 / (size_t)n) / 64 * 64);
+    const size_t workspace = env_workspace_kib("RC_PROFILE_WORKSPACE_KIB", slab::WORKSPACE);
+    const int64_t ms_cap = slab_ms_cap(slab::PERM_BYTES, 4, n);
     double ms_acc = 0.0;
     for (int64_t s0 = 0; s0 < L;) {
-        size_t bytes = 16 * (size_t)n, out_bytes = 0;
-        int64_t ms = 0;
-        while (s0 + ms < L && ms < ms_cap) {
-            const size_t add = 16 * (size_t)K[(size_t)(s0 + ms)], out = 24 * (size_t)n + 16 * (size_t)K[(size_t)(s0 + ms)];
-            if (ms > 0 && ((bytes + add) * (size_t)qt > workspace || out_bytes + out > workspace / 2)) break;
-            bytes += add; out_bytes += out; ++ms;
-        }
-        const int64_t qc = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(workspace / bytes)));
-        rc = prf::run_labellings(who, a, s0, ms, qc, ms_acc);
+        const SlabChunk ch = slab_plan(s0, K.data(), L, ms_cap, 16 * (size_t)n, 0, n, std::min<int64_t>(n, 512), workspace,
+                                       [n](size_t k) { return 24 * (size_t)n + 16 * k; }, workspace / 2);
+        rc = prf::run_labellings(who, a, s0, ch.ms, ch.qc, ms_acc);
         if (rc != RC_OK) return rc;
-        s0 += ms;
+        s0 += ch.ms;
     }
     if (K_out) for (int64_t s = 0; s < L; ++s) K_out[s] = K[(size_t)s];
     if (eD_out) *eD_out = c->eD;

@@ -7829,6 +7829,8 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "pointsearch.inc.hip"
 #include "visearch.inc.hip"
 #include "hclust.inc.hip"
+#include "slabplan.inc.hpp"
+#include "slab.inc.hip"
 #include "predict.inc.hip"
 #include "predictjoint.inc.hip"
 #include "partdist.inc.hip"

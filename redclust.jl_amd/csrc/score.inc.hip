@@ -3,29 +3,22 @@
 // its cluster sizes and the K×K block sums of D and logD; for L labellings the matrices are still read once per chunk of
 // labellings, not once per labelling.  DESIGN.md §8 "Scoring labellings"; the contract is in include/redclust_hip.h.
 // Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, View, rc_load_L, rc_bin_add, the
-// per-term helpers of loglik and logprior, sync_and_check, the holders of hostutil.inc.hip, cluster_order of labels.inc.hpp and
-// predict.inc.hip's k_predict_sums).
+// per-term helpers of loglik and logprior, sync_and_check, the holders and checks of hostutil.inc.hip and slab.inc.hip).
 //
-// Host, per labelling: compacted to slots 0..K-1 in ascending label order and counting-sorted, the sorted order stored
-// transposed with the boundary mark — exactly predict's perm[j][s] — plus the dense slot of every point, rslot[s][i].  Points
-// are in the caller's order throughout; only k_score_rows looks at the layout.
-//
-// k_score_rows (staging): one workgroup per row of a chunk of rows.  Row i of the caller's order is gathered through View.pi
-// from the internal-order matrices, whatever their storage, into interleaved (Dq, Lq) pairs — a derived log is computed here,
-// once per entry and chunk of labellings.
-// k_predict_sums (phase 1, the L·n² integer adds): predict's kernel as it stands, the context's rows as its "new points":
-// slab[i][slot] = Σ_{j in slot} (Dq, Lq)[i][j], exact int64, for every slot of every labelling of the chunk.
-// k_score_blocks (phase 2): one workgroup per (labelling, column cluster t).  The slab's column is reduced over the rows,
+// The block sums come out of the slab driver (slab.inc.hip): the context's rows, in the caller's order, are its rows, with the
+// dense slot of every point, rslot[s][i], from its sorted orders; RC_SCORE_WORKSPACE_KIB and RC_SCORE_ROWS_GLOBAL are its
+// switches for this entry point.
+// k_score_rows (its staging kernel): one workgroup per row of a chunk of rows.  Row i of the caller's order is gathered through
+// View.pi from the internal-order matrices, whatever their storage, into interleaved (Dq, Lq) pairs — a derived log is computed
+// here, once per entry and chunk of labellings.
+// k_score_blocks (its consumer): one workgroup per (labelling, column cluster t).  The slab's column is reduced over the rows,
 // grouped by the row's own cluster k <= t, into LDS bins of (hi, lo) halves — k_blocksums' inner step, rc_bin_add — and added
 // to the labelling's upper-triangle blocks.  Chunks of rows accumulate there; sums of halves are exact in any grouping, so the
 // result does not depend on the chunking.
 
 namespace scr {
 
-constexpr int64_t KMAX = 4096;                  // clusters of one labelling: 32 B of LDS bins each, 128 KiB
-constexpr int TPB_ROWS = 256, TPB_BLOCKS = 256;
-constexpr size_t WORKSPACE = (size_t)1 << 30;   // device bytes per chunk that scale with the number of rows
-constexpr size_t PERM_BYTES = (size_t)1 << 29;  // ... and the most the sorted orders of one chunk of labellings take
+constexpr int TPB_ROWS = 256, TPB_BLOCKS = 256;   // (slab::KMAX clusters: 32 B of LDS bins each, 128 KiB)
 
 // rows[b][j] = (Dq, Lq)[row0 + b][j], caller's order.  Grid: one block per row of the chunk.
 __global__ __launch_bounds__(TPB_ROWS) void k_score_rows(View V, int row0, ll2 *__restrict__ rows)
@@ -128,96 +121,45 @@ struct Call {
 static int32_t run_labellings(const char *who, const Call &a, int64_t s0, int64_t ms, int64_t qc, double &ms_acc)
 {
     rc_ctx *c = a.c;
-    const int64_t n = a.n;
-    const int ms_pad = (int)((ms + 63) / 64 * 64);
-    const int parts = ms_pad >= prd::TPB1 ? 1 : (int)std::min<int64_t>(prd::TPB1 / ms_pad, n);
-    std::vector<unsigned short> perm, rslot;
-    std::vector<int> startslot, partat, cnt, slot_of_label, pos, Ks, sizes, col_lab;
-    std::vector<long long> koff, boff, h_blocks;
-    long long ktot = 0, btot = 0;
-    int Kmax = 1;
-    for (int64_t s = 0; s < ms; ++s) {
-        const long long K = a.K[s0 + s];
-        ktot += K; btot += K * (K + 1) / 2;
-        Kmax = std::max(Kmax, (int)K);
-    }
+    const int64_t n = a.n, btot = a.boff[s0 + ms] - a.boff[s0];
+    const int Kmax = *std::max_element(a.K + s0, a.K + s0 + ms);
+    prd::Orders O;
+    std::vector<int> sizes, col_lab;
+    std::vector<long long> boff, h_blocks;
+    bool ok = true;
     try {
-        perm.assign((size_t)n * ms_pad, 0); rslot.resize((size_t)ms * n);
-        startslot.assign((size_t)parts * ms_pad, 0);
-        partat.assign((size_t)n, -1);
-        cnt.assign((size_t)n + 1, 0); slot_of_label.assign((size_t)n + 1, 0); pos.assign((size_t)n, 0);
-        koff.resize((size_t)ms); boff.resize((size_t)ms); Ks.resize((size_t)ms);
-        sizes.resize((size_t)ktot); col_lab.resize((size_t)ktot);
-        h_blocks.resize((size_t)btot * 4);
-    } catch (const std::bad_alloc &) { return fail(c, RC_ERR_OOM, "%s: no host memory for the sorted orders of %lld labellings", who, (long long)ms); }
-    for (int q = 0; q < parts; ++q) partat[(size_t)((long long)q * n / parts)] = q;
-    long long k0 = 0, b0 = 0;
-    for (int64_t s = 0; s < ms; ++s) {
-        const int64_t *z = a.labels + (size_t)(s0 + s) * n;
-        unsigned short *rs = rslot.data() + (size_t)s * n;
-        const int K = cluster_order(z, n, cnt, slot_of_label, pos,
-            [&](int t, int64_t, int sz) { sizes[(size_t)(k0 + t)] = sz; col_lab[(size_t)(k0 + t)] = (int)s; },
-            [&](int at_, int64_t j, int t) {
-                perm[(size_t)at_ * ms_pad + s] = (unsigned short)j;
-                rs[j] = (unsigned short)t;
-                if (partat[(size_t)at_] >= 0) startslot[(size_t)partat[(size_t)at_] * ms_pad + s] = t;
-            });
-        koff[(size_t)s] = k0; boff[(size_t)s] = b0; Ks[(size_t)s] = K;
-        // after the fill pos[t] is one past slot t's last position: mark those
-        for (int t = 0; t < K; ++t) perm[(size_t)(pos[(size_t)t] - 1) * ms_pad + s] |= 0x8000u;
-        k0 += K; b0 += (long long)K * (K + 1) / 2;
-    }
+        boff.resize((size_t)ms); h_blocks.resize((size_t)btot * 4);
+        for (int64_t s = 0; s < ms; ++s) boff[(size_t)s] = a.boff[s0 + s] - a.boff[s0];
+        long long kt = 0;
+        for (int64_t s = 0; s < ms; ++s) kt += a.K[s0 + s];
+        sizes.resize((size_t)kt); col_lab.resize((size_t)kt);
+    } catch (const std::bad_alloc &) { ok = false; }
+    ok = ok && O.build(a.labels, n, a.K, s0, ms, true, [&](int64_t s, long long at, int64_t, int sz) { sizes[(size_t)at] = sz; col_lab[(size_t)at] = (int)s; });
+    if (!ok) return fail(c, RC_ERR_OOM, "%s: no host memory for the sorted orders of %lld labellings", who, (long long)ms);
 
     DeviceBuffers B;
-    unsigned short *d_perm, *d_rslot; int *d_startslot, *d_K, *d_col_lab; long long *d_koff, *d_boff, *d_blocks;
-    ll2 *d_rows, *d_sums;
-    HIPCHK(c, B.alloc(d_perm, perm.size()));
-    HIPCHK(c, B.alloc(d_rslot, rslot.size()));
-    HIPCHK(c, B.alloc(d_startslot, startslot.size()));
-    HIPCHK(c, B.alloc(d_K, (size_t)ms));
-    HIPCHK(c, B.alloc(d_col_lab, (size_t)ktot));
-    HIPCHK(c, B.alloc(d_koff, (size_t)ms));
+    int *d_col_lab; long long *d_boff, *d_blocks;
+    HIPCHK(c, O.upload(B));
+    HIPCHK(c, B.alloc(d_col_lab, col_lab.size()));
     HIPCHK(c, B.alloc(d_boff, (size_t)ms));
     HIPCHK(c, B.alloc(d_blocks, (size_t)btot * 4));
-    HIPCHK(c, B.alloc(d_rows, (size_t)qc * n));
-    HIPCHK(c, B.alloc(d_sums, (size_t)qc * ktot));
-    HIPCHK(c, hipMemcpy(d_perm, perm.data(), perm.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_rslot, rslot.data(), rslot.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_startslot, startslot.data(), startslot.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_K, Ks.data(), (size_t)ms * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_col_lab, col_lab.data(), (size_t)ktot * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_koff, koff.data(), (size_t)ms * sizeof(long long), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_col_lab, col_lab.data(), col_lab.size() * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(d_boff, boff.data(), (size_t)ms * sizeof(long long), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemset(d_blocks, 0, (size_t)btot * 4 * sizeof(long long)));
 
-    const bool ldsrow = !a.rows_global && n <= prd::LDS_ROW_MAX_N;
-    const size_t lds = ldsrow ? (size_t)n * sizeof(ll2) : 0, lds_bins = (size_t)Kmax * 4 * sizeof(u64);
-    auto kern = ldsrow ? (parts > 1 ? prd::k_predict_sums<true, true> : prd::k_predict_sums<true, false>)
-                       : (parts > 1 ? prd::k_predict_sums<false, true> : prd::k_predict_sums<false, false>);
-    HIPCHK(c, set_dynamic_lds(kern, lds));
+    const size_t lds_bins = (size_t)Kmax * 4 * sizeof(u64);
     HIPCHK(c, set_dynamic_lds(k_score_blocks, lds_bins));
-    const View V = make_view(c);
-    TimingEvents ev;
-    HIPCHK(c, ev.create());
-    for (int64_t i0 = 0; i0 < n; i0 += qc) {
-        const int64_t np = std::min(qc, n - i0);
+    const int32_t rc = slab::run_rows(c, O, B, qc, a.rows_global, k_score_rows, TPB_ROWS, [&](const ll2 *d_sums, int64_t i0, int64_t np) {
         BlockArgs b{};
-        b.sums = d_sums; b.ktot = ktot; b.np = (int)np; b.row0 = (int)i0; b.n = (int)n; b.rslot = d_rslot; b.col_lab = d_col_lab;
-        b.koff = d_koff; b.boff = d_boff; b.K = d_K; b.blocks = d_blocks;
-        HIPCHK(c, ev.begin(0));
-        k_score_rows<<<(unsigned)np, TPB_ROWS, 0, 0>>>(V, (int)i0, d_rows);
-        HIPCHK(c, hipGetLastError());
-        if (parts > 1) HIPCHK(c, hipMemsetAsync(d_sums, 0, (size_t)np * ktot * sizeof(ll2), 0));   // the parts add into zeros
-        kern<<<(unsigned)np, prd::TPB1, lds, 0>>>(d_rows, (int)n, d_perm, (int)ms, ms_pad, parts, d_startslot, d_koff, ktot, d_sums);
-        HIPCHK(c, hipGetLastError());
-        k_score_blocks<<<(unsigned)ktot, TPB_BLOCKS, lds_bins, 0>>>(b);
-        HIPCHK(c, ev.end(0));
-        HIPCHK(c, ev.elapsed_ms(ms_acc));
-    }
+        b.sums = d_sums; b.ktot = O.ktot; b.np = (int)np; b.row0 = (int)i0; b.n = (int)n; b.rslot = O.d_rslot; b.col_lab = d_col_lab;
+        b.koff = O.d_koff; b.boff = d_boff; b.K = O.d_K; b.blocks = d_blocks;
+        k_score_blocks<<<(unsigned)O.ktot, TPB_BLOCKS, lds_bins, 0>>>(b);
+    }, ms_acc);
+    if (rc != RC_OK) return rc;
     HIPCHK(c, hipMemcpy(h_blocks.data(), d_blocks, h_blocks.size() * sizeof(long long), hipMemcpyDeviceToHost));
     for (int64_t s = 0; s < ms; ++s) {
-        const int K = Ks[(size_t)s];
-        const int *sz = sizes.data() + koff[(size_t)s];
+        const int K = O.Ks[(size_t)s];
+        const int *sz = sizes.data() + O.koff[(size_t)s];
         const long long *blk = h_blocks.data() + boff[(size_t)s] * 4;
         a.loglik_out[s0 + s] = loglik_blocks(*a.P, c->eD, c->eL, K, sz, blk, *a.memo);
         if (a.logprior_out) {
@@ -244,31 +186,23 @@ extern "C" int32_t rc_score_labellings(rc_ctx *c, int64_t L, const int64_t *labe
     if (L < 1) return fail(c, RC_ERR_ARG, "%s: need L >= 1 (got %lld)", who, (long long)L);
     if (logprior_out && (!r || !p)) return fail(c, RC_ERR_ARG, "%s: the log-prior needs r and p", who);
     const int64_t n = c->n;
-    if (n > prd::NMAX) return fail(c, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %lld points whose indices fit 15 bits", who, (long long)n, (long long)prd::NMAX);
-    if (L >= ((int64_t)1 << 31) / n + (((int64_t)1 << 31) % n != 0)) return fail(c, RC_ERR_CAPACITY, "%s: L·n = %lld·%lld is not below 2^31", who, (long long)L, (long long)n);
+    rc = check_label_shape(c, who, n, "points", L, "L");
+    if (rc != RC_OK) return rc;
     if (!params && !c->have_params) return fail(c, RC_ERR_STATE, "%s: params is NULL and the context has no parameters set", who);
     const rc_params P = params ? *params : c->P;
     rc = check_params(c, who, &P);
     if (rc != RC_OK) return rc;
-    for (int64_t s = 0; s < L; ++s) {
-        if (r && !(r[s] > 0 && r[s] <= 1.79769313486231570e308)) return fail(c, RC_ERR_ARG, "%s: r of labelling %lld must be positive and finite", who, (long long)s + 1);
-        if (p && !(p[s] > 0 && p[s] < 1)) return fail(c, RC_ERR_ARG, "%s: p of labelling %lld must lie in (0, 1)", who, (long long)s + 1);
-    }
+    rc = check_r_p(c, who, "labelling", L, r, p);
+    if (rc != RC_OK) return rc;
     rc = check_label_rows(c, who, "labelling", labels, L, n);
     if (rc != RC_OK) return rc;
     std::vector<int> K, seen;
     std::vector<int64_t> boff;
     try { K.assign((size_t)L, 0); seen.assign((size_t)n + 1, -1); boff.assign((size_t)L + 1, 0); }
     catch (const std::bad_alloc &) { return fail(c, RC_ERR_OOM, "%s: no host memory", who); }
-    for (int64_t s = 0; s < L; ++s) {
-        const int64_t *z = labels + (size_t)s * n;
-        int k = 0;
-        for (int64_t j = 0; j < n; ++j)
-            if (seen[(size_t)z[j]] != (int)s) { seen[(size_t)z[j]] = (int)s; ++k; }
-        if (k > scr::KMAX) return fail(c, RC_ERR_CAPACITY, "%s: labelling %lld has %d clusters, more than the %lld whose bins fit the workgroup's LDS", who, (long long)s + 1, k, (long long)scr::KMAX);
-        K[(size_t)s] = k;
-        boff[(size_t)s + 1] = boff[(size_t)s] + (int64_t)k * (k + 1) / 2;
-    }
+    const int64_t over = count_clusters(labels, L, n, slab::KMAX, seen, K.data());
+    if (over < L) return fail(c, RC_ERR_CAPACITY, "%s: labelling %lld has %d clusters, more than the %lld whose bins fit the workgroup's LDS", who, (long long)over + 1, K[(size_t)over], (long long)slab::KMAX);
+    for (int64_t s = 0; s < L; ++s) boff[(size_t)s + 1] = boff[(size_t)s] + (int64_t)K[(size_t)s] * (K[(size_t)s] + 1) / 2;
     if (blocks_len != (blocks_out ? boff[(size_t)L] : 0))
         return fail(c, RC_ERR_ARG, "%s: blocks_len = %lld, the labellings have %lld blocks%s", who, (long long)blocks_len, (long long)boff[(size_t)L],
                     blocks_out ? "" : " (and blocks_out is NULL: pass 0)");
@@ -279,25 +213,18 @@ extern "C" int32_t rc_score_labellings(rc_ctx *c, int64_t L, const int64_t *labe
     scr::LgMemo memo;
     scr::Call a{c, n, L, labels, r, p, &P, loglik_out, logprior_out, blocks_out, K.data(), boff.data(),
                 env_flag("RC_SCORE_ROWS_GLOBAL"),                             // tests: gather from the rows in global memory at small n
-                env_workspace_kib("RC_SCORE_WORKSPACE_KIB", scr::WORKSPACE), &memo};
+                env_workspace_kib("RC_SCORE_WORKSPACE_KIB", slab::WORKSPACE), &memo};
     // Chunks.  Device bytes per row for a run of labellings: the staged row and its slots' sums.  Labellings are taken while 512
     // rows (or all n) of them fit the workspace, their sorted orders fit theirs and their blocks a quarter of the workspace; the
     // rows then go in chunks of what fits.
-    const int64_t qt = std::min<int64_t>(n, 512);
-    const int64_t ms_cap = std::max<int64_t>(64, (int64_t)(scr::PERM_BYTES / 4 / (size_t)n) / 64 * 64);
+    const int64_t ms_cap = slab_ms_cap(slab::PERM_BYTES, 4, n);
     double ms_acc = 0.0;
     for (int64_t s0 = 0; s0 < L;) {
-        size_t bytes = 16 * (size_t)n, blk_bytes = 0;
-        int64_t ms = 0;
-        while (s0 + ms < L && ms < ms_cap) {
-            const size_t add = 16 * (size_t)K[(size_t)(s0 + ms)], blk = 32 * (size_t)(boff[(size_t)(s0 + ms) + 1] - boff[(size_t)(s0 + ms)]);
-            if (ms > 0 && ((bytes + add) * (size_t)qt > a.workspace || blk_bytes + blk > a.workspace / 4)) break;
-            bytes += add; blk_bytes += blk; ++ms;
-        }
-        const int64_t qc = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(a.workspace / bytes)));
-        rc = scr::run_labellings(who, a, s0, ms, qc, ms_acc);
+        const SlabChunk ch = slab_plan(s0, K.data(), L, ms_cap, 16 * (size_t)n, 0, n, std::min<int64_t>(n, 512), a.workspace,
+                                       [](size_t k) { return 32 * (k * (k + 1) / 2); }, a.workspace / 4);
+        rc = scr::run_labellings(who, a, s0, ch.ms, ch.qc, ms_acc);
         if (rc != RC_OK) return rc;
-        s0 += ms;
+        s0 += ch.ms;
     }
     if (K_out) for (int64_t s = 0; s < L; ++s) K_out[s] = K[(size_t)s];
     if (eD_out) *eD_out = c->eD;

@@ -76,6 +76,23 @@ static bool check_bad(std::vector<int64_t> rows, int64_t count, int64_t n, int64
     return true;
 }
 
+// count_clusters on `count` rows against sorting each row's labels: the counts up to and including the first row above cap, the
+// rows behind it untouched
+static bool check_counts(const std::vector<int64_t> &rows, int64_t count, int64_t n, int64_t cap, int kase)
+{
+    std::vector<int> want((size_t)count), got((size_t)count, -7), seen((size_t)n + 1, -1);
+    int64_t first = count;
+    for (int64_t r = count - 1; r >= 0; --r) {
+        std::vector<int64_t> z(rows.begin() + r * n, rows.begin() + (r + 1) * n);
+        std::sort(z.begin(), z.end());
+        want[(size_t)r] = (int)(std::unique(z.begin(), z.end()) - z.begin());
+        if (want[(size_t)r] > cap) first = r;
+    }
+    REQUIRE(count_clusters(rows.data(), count, n, cap, seen, got.data()) == first);
+    for (int64_t r = 0; r < count; ++r) REQUIRE(got[(size_t)r] == (r <= first ? want[(size_t)r] : -7));
+    return true;
+}
+
 int main()
 {
     std::mt19937_64 rng(20240611);
@@ -91,6 +108,17 @@ int main()
                        : kind == 2 ? std::max<int64_t>(1, n - (int64_t)(rng() % 2))   // labels from {n − 1, n} only
                                    : 1 + (int64_t)(rng() % (uint64_t)hi);
             if (!check_labelling(z, kase)) return 1;
+        }
+        // count_clusters: 5 rows of few or many clusters; no row above the cap, every row, or only the rows of many
+        for (int kase = 0; kase < 60; ++kase, ++cases) {
+            const int64_t count = 5;
+            std::vector<int64_t> rows((size_t)(count * n));
+            for (int64_t r = 0; r < count; ++r) {
+                const int64_t hi = (kase + r) % 3 == 0 ? n : std::max<int64_t>(1, n / 4);
+                for (int64_t j = 0; j < n; ++j) rows[(size_t)(r * n + j)] = 1 + (int64_t)(rng() % (uint64_t)hi);
+            }
+            for (int64_t cap : {n, (int64_t)0, std::max<int64_t>(1, n / 4)})
+                if (!check_counts(rows, count, n, cap, kase)) return 1;
         }
         // find_bad_label: 3 rows; the offender first, last, both, twice in between, or absent
         const int64_t count = 3, total = count * n;

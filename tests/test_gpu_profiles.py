@@ -118,6 +118,27 @@ def test_a_labelling_profiles_the_same_alone_and_in_any_company(wide_batch):
     assert same(ctx.profiles(labs[order]), ref, order)
 
 
+def test_1025_labellings_in_one_chunk_take_plain_stores_and_agree_with_batches_of_65(monkeypatch):
+    """n = 65, L = 1025 in the default 1 GiB workspace is one chunk of labellings and all 65 rows at once: the planner's recorded
+    plan "profiles,65,1025,<pattern>,1048576" is "1025:65*1" at every number of clusters (tests/golden/slab_plans.json, held in
+    tests/test_slabplan_cpu.py).  1025 labellings pad to 1088, no fewer than the 1024 lanes of k_predict_sums' workgroup, so a
+    lane owns a whole labelling: plain stores into a slab that was never zeroed.  Batches of 65 pad to 128 — 8 parts per
+    labelling that add with atomics into zeros, the path the tests above hold against the reference.  Every output (same():
+    K, within, nearest, neighbour, labels, sizes, medoids, medoid_within) must be equal."""
+    monkeypatch.delenv("RC_PROFILE_WORKSPACE_KIB", raising=False)
+    n, L = 65, 1025
+    ctx = context("derived64", n, "mixed")
+    try:
+        labs = batch(n, L)
+        whole = ctx.profiles(labs)
+        assert whole["within"].shape == (L, n) and len(whole["medoids"]) == L
+        for s in range(0, L, 65):
+            rows = slice(s, min(s + 65, L))
+            assert same(ctx.profiles(labs[rows]), whole, rows), s
+    finally:
+        ctx.close()
+
+
 def test_ties_go_to_the_smaller_label_and_the_smallest_index():
     """all off-diagonal entries equal: every other cluster ties in mean, every member ties in within"""
     n = 131

@@ -248,6 +248,34 @@ def test_a_labelling_scores_the_same_alone_and_in_any_company(wide_batch):
     assert same(out, dict(loglik=np.roll(ref["loglik"], 23), K=np.roll(ref["K"], 23), blocks=ref["blocks"][-23:] + ref["blocks"][:-23]))
 
 
+def test_1025_labellings_in_one_chunk_take_plain_stores_and_agree_with_batches_of_65(monkeypatch):
+    """n = 65, L = 1025 in the default 1 GiB workspace is one chunk of labellings and all 65 rows at once: the planner's recorded
+    plan "score,65,1025,<pattern>,1048576" is "1025:65*1" at every number of clusters (tests/golden/slab_plans.json, held in
+    tests/test_slabplan_cpu.py).  1025 labellings pad to 1088, no fewer than the 1024 lanes of k_predict_sums' workgroup, so a
+    lane owns a whole labelling: plain stores into a slab that was never zeroed.  Batches of 65 pad to 128 — 8 parts per
+    labelling that add with atomics into zeros, the path the tests above hold against the reference.  Every output must be
+    equal."""
+    monkeypatch.delenv("RC_SCORE_WORKSPACE_KIB", raising=False)
+    n, L = 65, 1025
+    ctx = context("derived64", n)
+    try:
+        ctx.set_params(**P0)
+        labs = batch(n, L)
+        rng = np.random.default_rng(9)
+        r, p = rng.uniform(0.3, 3.0, L), rng.uniform(0.05, 0.95, L)
+        whole = ctx.score(labs, r, p, want_blocks=True)
+        assert len(whole["blocks"]) == L and len(whole["sizes"]) == L
+        for s in range(0, L, 65):
+            e = min(s + 65, L)
+            part = ctx.score(labs[s:e], r[s:e], p[s:e], want_blocks=True)
+            for key in ("loglik", "logprior", "K"):
+                assert np.array_equal(part[key], whole[key][s:e]), (key, s)
+            for key in ("blocks", "sizes"):
+                assert all(np.array_equal(x, y) for x, y in zip(part[key], whole[key][s:e])), (key, s)
+    finally:
+        ctx.close()
+
+
 def test_argument_errors_come_before_any_device_work(wide_batch):
     ctx, labs, _ = wide_batch
     n = ctx.n

@@ -1,7 +1,7 @@
 """The host label toolkit (csrc/labels.inc.hpp) in a program of its own, tests/labels_host.cpp: compiled with the host compiler under
 AddressSanitizer and UndefinedBehaviorSanitizer (without them where their runtimes are missing) and run as an ordinary
-executable.  The program checks compact_labels, dense_ids, cluster_order and find_bad_label against brute-force restatements for
-n = 1, 2, 7, 64."""
+executable.  The program checks compact_labels, dense_ids, cluster_order, count_clusters and find_bad_label against brute-force
+restatements for n = 1, 2, 7, 64."""
 import os
 import subprocess
 

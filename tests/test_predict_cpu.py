@@ -145,6 +145,8 @@ def test_the_source_is_part_of_the_build():
     assert os.path.join(csrc, "predict.inc.hip") in _lib._sources()  # build() watches it
     src = open(os.path.join(csrc, "predict.inc.hip")).read()
     assert "asm" not in re.sub(r"//.*", "", src)                    # plain C++ and vector memory operations only
+    assert '#include "slab.inc.hip"' in open(os.path.join(csrc, "redclust_hip.hip")).read()   # ... k_predict_sums' file too
+    assert "asm" not in re.sub(r"//.*", "", open(os.path.join(csrc, "slab.inc.hip")).read())
 
 
 def test_argument_errors_raise_before_any_device_work():

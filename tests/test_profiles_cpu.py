@@ -110,7 +110,9 @@ def test_the_source_is_part_of_the_build():
     assert os.path.join(csrc, "profile.inc.hip") in _lib._sources()        # build() watches it
     src = re.sub(r"//.*", "", open(os.path.join(csrc, "profile.inc.hip")).read())
     assert "asm" not in src                                                # plain C++ and vector memory operations only
-    assert "launch_sums" in src and "k_predict_sums<" not in src           # phase 1 is shared, not copied or instantiated anew
+    assert "slab::run_rows" in src and "k_predict_sums" not in src         # phase 1 is shared, not copied or instantiated anew:
+    slab = re.sub(r"//.*", "", open(os.path.join(csrc, "slab.inc.hip")).read())
+    assert "asm" not in slab and "launch_sums" in slab.split("run_rows(", 1)[1]   # the slab driver launches it
     assert "rc_load_L" not in src and "rc_qlog" not in src                 # no logarithm is involved
 
 

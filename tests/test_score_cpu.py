@@ -230,4 +230,7 @@ def test_the_source_is_part_of_the_build():
     assert os.path.join(csrc, "score.inc.hip") in _lib._sources()     # build() watches it
     src = re.sub(r"//.*", "", open(os.path.join(csrc, "score.inc.hip")).read())
     assert "asm" not in src                                           # plain C++ and vector memory operations only
-    assert "prd::k_predict_sums" in src and "rc_bin_add" in src       # the two halves are shared, not copied
+    assert "slab::run_rows" in src and "rc_bin_add" in src            # the two halves are shared, not copied:
+    assert "k_predict_sums" not in src and "launch_sums" not in src   # the sums come through the slab driver, which launches them
+    slab = re.sub(r"//.*", "", open(os.path.join(csrc, "slab.inc.hip")).read())
+    assert "asm" not in slab and "launch_sums" in slab.split("run_rows(", 1)[1]

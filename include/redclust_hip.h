@@ -871,6 +871,66 @@ int32_t rc_cluster_profiles(rc_ctx *ctx, int64_t L, const int64_t *labels /* L×
                             int64_t *within_out /* L×n or NULL */, int64_t *nearest_out /* L×n or NULL */,
                             int64_t *neighbour_out /* L×n or NULL */, int32_t *eD_out, double *kernel_ms);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * MAP search: the greedy search of rc_psm_search and rc_vi_search (one run = starting labels, a point order, maxsweeps; the
+ * same tie rules) over ALL partitions for the labelling of maximum log-posterior lp(c) = loglik + logprior — what
+ * rc_score_labellings computes and mapestimate ranks candidates by — under the context's matrices as they are (64- or 32-bit
+ * storage, logD stored or derived, the current internal point order read through its index map).  DESIGN.md §8 "MAP search".
+ *
+ * Criterion.  With rc_score_labellings' block sums B_D, B_L of the allocated points (D's stored diagonal entry travels with
+ * its point into B_D[k][k], logD's diagonal is 0; D is taken as symmetric, which rc_create demands) and P_k = n_k(n_k−1)/2:
+ *   within(k)    = (δ1−1)·B_L[k][k]/2 − P_k·lgΓ(δ1) + α·log β − lgΓ(α) + lgΓ(α+δ1·P_k) − (α+δ1·P_k)·log(β + B_D[k][k]/2)
+ *   between(k,t) = (δ2−1)·B_L[k][t] − n_k·n_t·lgΓ(δ2) + ζ·log γ − lgΓ(ζ) + lgΓ(ζ+δ2·n_k·n_t) − (ζ+δ2·n_k·n_t)·log(γ + B_D[k][t])
+ * (between only with repulsion), evaluated in the regrouped log1p(B/β) form of rc_loglik, and the prior's terms of
+ * rc_logprior over the n' allocated points.  One visit takes point i out of its slot a, reduces row i into the exact int64
+ * sums s_t = Σ_{j in t, j != i} Dq[i][j] and l_t (logD), and scores
+ *   Δ_k   = [within(k ∪ i) − within(k)] + Σ_{t != k} [between(k ∪ i, t) − between(k, t)] + log(n_k+1) − log n_k + log(n_k+r−1) + log p
+ *   Δ_new = within({i}) + Σ_t between({i}, t) + log(K+1) + r·log(1−p)            (K: the occupied slots with i out)
+ * with B_D[k][k] += 2·s_k + Dq[i][i] and B_D[k][t] += s_t (B_L alike, without a diagonal).  The point goes to the maximum,
+ * "stay" included, so every accepted move raises lp.  Equal scores: the own slot first, then the lowest slot; a new cluster
+ * takes the slot just emptied, else the lowest free one.
+ *
+ * What is exact and what is not.  The row sums and the run's K×K block state are exact integers (a block as two halves,
+ * value = hi·2^24 + lo, updated by adding and subtracting row sums, never reduced again).  The Δ are f64, with the library's
+ * own lgamma (Stirling's series) and log1p (one log, corrected); they decide moves only, and a candidate's sum over its partners has a fixed shape, so a run is a
+ * deterministic function of its arguments whatever else shares the call.  Everything reported is recomputed by the exact
+ * path: loglik, logprior and logposterior of labels_out, and start_logposterior of a fully allocated start, are
+ * rc_score_labellings' values for (labelling, r, p) under the same parameters, bit for bit.  A run's logposterior is never
+ * below its start_logposterior up to the f64 error of a Δ.
+ *
+ * One run is rc_vi_search's: starting labels 0..n (0 = unallocated) compacted to slots by first appearance, the order a
+ * permutation of 1..n, at most maxsweeps sweeps, the run ends after a sweep without a move (converged); each run has its own
+ * r and p.  The slot cap Kcap is maxK when that is positive, else min(n, 1024); a new cluster is not offered at K = Kcap, and
+ * `capped` counts the visits at which only the implicit cap (maxK = 0) withheld the offer.  params->maxK plays no part.
+ * labels_out: sortlabels'd (src/utils.jl:69-74).  best: the first run of maximal logposterior (0-based).  blocks_out (may be
+ * NULL): per run Kcap×Kcap×4 int64, the kernel's own final cells (D_hi, D_lo, L_hi, L_lo) of the ordered pair of slots
+ * (k, t), cell ((k−1)·Kcap + (t−1)); slots_out (may be NULL): nruns×n, the kernel's final slots, 1-based — the two exist so
+ * that the incremental state can be checked against rc_score_labellings' blocks (the halves may differ, the values may not).
+ * kernel_ms (may be NULL): device time of the search kernel alone — the starting cells and the sweeps; neither the zeroing of
+ * the cells nor the copy of blocks_out — summed over its launches (one for the runs whose cells fit 1 GiB, else several).
+ *
+ * The call waits for the context's streams first and leaves the chain state, the layout, the row-sum tables, the
+ * co-clustering counts and the choice of kernels untouched; a context with no state set is fine.
+ *
+ * Errors, all before any device work, in this order.  RC_ERR_ARG: a NULL ctx or pointer; nruns < 1, maxsweeps < 1, maxK < 0;
+ * a starting label outside 0..n; an order that is not a permutation; an r that is <= 0 or not finite; a p outside (0, 1);
+ * params that rc_set_params would reject.  RC_ERR_STATE: params NULL on a context without parameters.  RC_ERR_CAPACITY:
+ * n > 8192, 2·nruns·n >= 2^31, Kcap > 1024.  RC_ERR_ARG: a run that starts with more than Kcap clusters.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct rc_map_run_t {
+    double loglik, logprior, logposterior; /* of labels_out: rc_score_labellings' values, bit for bit */
+    double start_logposterior;             /* NaN when the start had unallocated points */
+    int32_t sweeps, converged, K, capped;
+    int64_t moves;
+} rc_map_run_t;
+
+int32_t rc_map_search(rc_ctx *ctx, int32_t nruns, const int64_t *init /* nruns×n, 0 = unallocated */,
+                      const int32_t *order /* nruns×n, 1-based */, const double *r /* nruns */, const double *p /* nruns */,
+                      const rc_params *params /* NULL: the context's */, int32_t maxK, int32_t maxsweeps,
+                      int64_t *labels_out /* nruns×n, sortlabels'd */, void *runs_out /* rc_map_run_t[nruns] */,
+                      int64_t *blocks_out /* may be NULL: nruns×Kcap×Kcap×4 */, int64_t *slots_out /* may be NULL: nruns×n */,
+                      int32_t *best /* first run of maximal logposterior */, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

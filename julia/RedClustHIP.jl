@@ -808,6 +808,90 @@ end
 
 export scorelabellings, mapestimate
 
+struct RcMapRun                      # struct rc_map_run_t
+    loglik::Cdouble; logprior::Cdouble; logposterior::Cdouble
+    start_logposterior::Cdouble
+    sweeps::Int32; converged::Int32; K::Int32; capped::Int32
+    moves::Int64
+end
+
+"""
+    searchmapestimate(HIPBackend(), data, candidates, params; r, p, nruns = 16, maxK = 0, maxsweeps = 100, seed = 0, init = nothing) -> (clust, info)
+
+Search ALL partitions for the labelling of maximum log-posterior (rc_map_search): a one-point-at-a-time climb of
+loglik + logprior from the `nruns` distinct candidates of highest log-posterior, each under its own `r` and `p` (scalars or one
+per candidate), from every column of `init` (an n × k matrix of labels, 0 = unallocated) and from empty labels, these under the
+best candidate's pair.  The moves are decided in Float64 on exact integer block sums; everything reported is
+rc_score_labellings' value of the labelling it belongs to.  Never worse than `mapestimate` on the same candidates: when no run
+beats the best candidate, that candidate is returned and `info.best` is 0.  `info`: `index` (the best candidate),
+`candidate_logposterior`, and per run `start_logposterior` (NaN for a start with unallocated points), `logposterior`, `loglik`,
+`logprior`, `sweeps`, `converged`, `moves`, `K`, `capped`, all `labels` (n × runs), `runs` (the starts), `best`, `kernel_ms`.
+"""
+function searchmapestimate(b::HIPBackend, data::MCMCData, candidates::Vector{<:AbstractVector{<:Integer}},
+                           params::PriorHyperparamsList; r, p, nruns::Integer = 16, maxK::Integer = 0, maxsweeps::Integer = 100,
+                           seed::Integer = 0, init::Union{Matrix{Int64},Nothing} = nothing)
+    n = size(data.D, 1)
+    L = length(candidates)
+    L >= 1 || throw(ArgumentError("No candidates."))
+    sc = scorelabellings(b, data, candidates, params; r = r, p = p)
+    rv = r isa Real ? fill(Float64(r), L) : Vector{Float64}(r)
+    pv = p isa Real ? fill(Float64(p), L) : Vector{Float64}(p)
+    top = argmax(sc.logposterior)                                 # the first maximum
+    starts = Vector{Vector{Int64}}(); rs = Float64[]; ps = Float64[]
+    seen = Set{Vector{Int64}}()
+    for c in sortperm(sc.logposterior; rev = true, alg = MergeSort)   # the highest first, the smaller index on ties
+        length(starts) == nruns && break
+        key = Vector{Int64}(RedClust.sortlabels(Vector{Int64}(candidates[c])))
+        key in seen && continue
+        push!(seen, key)
+        push!(starts, Vector{Int64}(candidates[c])); push!(rs, rv[c]); push!(ps, pv[c])
+    end
+    if init !== nothing
+        size(init, 1) == n || throw(ArgumentError("Every labelling in init must have n entries."))
+        for k in 1:size(init, 2)
+            push!(starts, init[:, k]); push!(rs, rv[top]); push!(ps, pv[top])
+        end
+    end
+    push!(starts, zeros(Int64, n)); push!(rs, rv[top]); push!(ps, pv[top])
+    R = length(starts)
+    initm = Matrix{Int64}(undef, n, R)                            # column q = run q: row-major R×n for the library
+    order = Matrix{Int32}(undef, n, R)
+    rng = Random.MersenneTwister(seed)
+    for q in 1:R
+        initm[:, q] .= starts[q]
+        order[:, q] .= Random.randperm(rng, n)                    # every run in a permutation of its own, drawn in run order
+    end
+    labels = Matrix{Int64}(undef, n, R)
+    runs = Vector{RcMapRun}(undef, R)
+    best = Int32[0]
+    ms = Cdouble[0]
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = ccall((:rc_create, LIB), Int32,
+               (Int64, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Int32, Int64, Ref{Ptr{Cvoid}}),
+               n, data.D, Ptr{Cdouble}(C_NULL), 64, b.device, 0, h)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    ctx = h[]
+    try
+        rc = ccall((:rc_map_search, LIB), Int32,
+                   (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{RcParams}, Int32, Int32, Ptr{Int64},
+                    Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}, Ptr{Cdouble}),
+                   ctx, R, initm, order, rs, ps, Ref(RcParams(params)), maxK, maxsweeps, labels, runs, C_NULL, C_NULL, best, ms)
+        check(ctx, rc)
+    finally
+        ccall((:rc_destroy, LIB), Int32, (Ptr{Cvoid},), ctx)
+    end
+    w = Int(best[1]) + 1
+    beaten = runs[w].logposterior > sc.logposterior[top]
+    info = (index = top, candidate_logposterior = sc.logposterior, start_logposterior = [x.start_logposterior for x in runs],
+            logposterior = [x.logposterior for x in runs], loglik = [x.loglik for x in runs], logprior = [x.logprior for x in runs],
+            sweeps = [Int(x.sweeps) for x in runs], converged = [x.converged != 0 for x in runs], moves = [Int(x.moves) for x in runs],
+            K = [Int(x.K) for x in runs], capped = [Int(x.capped) for x in runs], labels = labels, runs = initm,
+            best = beaten ? w : 0, kernel_ms = ms[1])
+    return (beaten ? labels[:, w] : Vector{Int64}(candidates[top]), info)
+end
+
+export searchmapestimate
+
 """
     clusterprofiles(HIPBackend(), data, labellings; points = true) -> (K, medoids, medoid_within, within, nearest, neighbour, silhouette, eD, kernel_ms)
 

@@ -86,6 +86,11 @@ class RcPsmRun(C.Structure):
                 ("moves", C.c_int64), ("K", C.c_int32)]
 
 
+class RcMapRun(C.Structure):
+    _fields_ = [("loglik", C.c_double), ("logprior", C.c_double), ("logposterior", C.c_double), ("start_logposterior", C.c_double),
+                ("sweeps", C.c_int32), ("converged", C.c_int32), ("K", C.c_int32), ("capped", C.c_int32), ("moves", C.c_int64)]
+
+
 class RcSweepStats(C.Structure):
     _fields_ = [("n_changes", C.c_int64), ("n_rounds", C.c_int64), ("K", C.c_int64)]
 
@@ -233,6 +238,8 @@ SIGNATURES = {
                                           C.POINTER(C.c_double)]),
     "rc_cluster_profiles": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_map_search": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RcParams), C.c_int32,
+                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rc_layout_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rc_event_overhead_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "rc_kernel_timing": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -601,6 +608,41 @@ class Context:
             per = [blocks[off[i]:off[i + 1]] for i in range(nl)]
         return dict(loglik=ll[:nl], logprior=None if lp is None else lp[:nl], logposterior=None if lp is None else ll[:nl] + lp[:nl],
                     K=K[:nl], sizes=sizes, blocks=per, eD=int(eD.value), eL=int(eL.value), kernel_ms=float(ms.value))
+
+    def map_search(self, init, order, r, p, params=None, maxK: int = 0, maxsweeps: int = 100, want_state: bool = False) -> dict:
+        """rc_map_search: the greedy search over all partitions for the labelling of maximum log-posterior under this context's
+        matrices; its state, layout and counts are untouched.  init: nruns×n labels (0 = unallocated); order: nruns×n 1-based
+        permutations; r, p: a scalar or one value per run; params: a dict of hyperparameters (None: the context's).  Returns a
+        dict: labels (nruns×n, sortlabels'd), the per-run arrays loglik, logprior, logposterior (rc_score_labellings' values of
+        labels), start_logposterior (NaN for a start with unallocated points), sweeps, converged, K, capped, moves, and best
+        (the first run of maximal logposterior), kernel_ms, Kcap (the slot cap); with want_state also blocks (nruns×Kcap×Kcap×4
+        int64: the kernel's own final cells (D_hi, D_lo, L_hi, L_lo) by ordered pair of slots, value = hi·2^24 + lo) and
+        slots (nruns×n: the kernel's final 1-based slots) — else None."""
+        init = np.ascontiguousarray(init, dtype=np.int64)
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        if init.ndim != 2 or init.shape != order.shape or init.shape[1] != self.n:
+            raise ValueError("init and order must be nruns×n arrays of the same shape, n the context's")
+        nruns, n = init.shape
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(r, dtype=np.float64).reshape(-1), (nruns,)))
+        p = np.ascontiguousarray(np.broadcast_to(np.asarray(p, dtype=np.float64).reshape(-1), (nruns,)))
+        prm = None if params is None else _params_struct(params)
+        Kcap = int(maxK) if int(maxK) > 0 else min(n, 1024)
+        labels = np.zeros((max(nruns, 1), n), np.int64)
+        runs = (RcMapRun * max(nruns, 1))()
+        state = want_state and 1 <= Kcap <= 1024 and n <= 8192                     # otherwise the library refuses the call
+        blocks = np.zeros((max(nruns, 1), Kcap, Kcap, 4), np.int64) if state else None
+        slots = np.zeros((max(nruns, 1), n), np.int64) if state else None
+        best, ms = C.c_int32(-1), C.c_double()
+        self._chk(self.L.rc_map_search(self.h, nruns, init.ctypes.data, order.ctypes.data, r.ctypes.data, p.ctypes.data,
+                                       None if prm is None else C.byref(prm), int(maxK), int(maxsweeps), labels.ctypes.data, runs,
+                                       None if blocks is None else blocks.ctypes.data, None if slots is None else slots.ctypes.data,
+                                       C.byref(best), C.byref(ms)))
+        out = dict(labels=labels[:nruns], best=int(best.value), kernel_ms=float(ms.value), Kcap=Kcap,
+                   blocks=None if blocks is None else blocks[:nruns], slots=None if slots is None else slots[:nruns])
+        for k, ty in RcMapRun._fields_:
+            out[k] = np.array([getattr(x, k) for x in runs[:nruns]], dtype=np.float64 if ty is C.c_double else np.int64)
+        out["converged"] = out["converged"].astype(bool)
+        return out
 
     def profiles(self, labellings, points=True) -> dict:
         """rc_cluster_profiles: the medoids and the per-point sums behind the silhouette of each of L labellings (L×n int64

@@ -61,6 +61,7 @@
 #include <cstring>
 #include <condition_variable>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -7836,4 +7837,6 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "partdist.inc.hip"
 #include "relabel.inc.hip"
 #include "score.inc.hip"
+#include "mapmath.inc.hpp"
+#include "mapsearch.inc.hip"
 #include "profile.inc.hip"

@@ -173,6 +173,52 @@ static int32_t run_labellings(const char *who, const Call &a, int64_t s0, int64_
     return RC_OK;
 }
 
+// rc_score_labellings behind its argument checks — L labellings of labels in 1..n, r and p valid or null, P checked — for the
+// entry points that score labellings of their own through the same path (rc_map_search): the capacity in clusters, the
+// blocks_len, the wait for the context's streams, the chunks of the slab driver and the outputs.
+static int32_t score_valid(rc_ctx *c, const char *who, int64_t L, const int64_t *labels, const double *r, const double *p, const rc_params &P,
+                           double *loglik_out, double *logprior_out, int64_t *K_out, int64_t *blocks_out, int64_t blocks_len,
+                           double *kernel_ms, int32_t *eD_out = nullptr, int32_t *eL_out = nullptr)
+{
+    const int64_t n = c->n;
+    int32_t rc;
+    std::vector<int> K, seen;
+    std::vector<int64_t> boff;
+    try { K.assign((size_t)L, 0); seen.assign((size_t)n + 1, -1); boff.assign((size_t)L + 1, 0); }
+    catch (const std::bad_alloc &) { return fail(c, RC_ERR_OOM, "%s: no host memory", who); }
+    const int64_t over = count_clusters(labels, L, n, slab::KMAX, seen, K.data());
+    if (over < L) return fail(c, RC_ERR_CAPACITY, "%s: labelling %lld has %d clusters, more than the %lld whose bins fit the workgroup's LDS", who, (long long)over + 1, K[(size_t)over], (long long)slab::KMAX);
+    for (int64_t s = 0; s < L; ++s) boff[(size_t)s + 1] = boff[(size_t)s] + (int64_t)K[(size_t)s] * (K[(size_t)s] + 1) / 2;
+    if (blocks_len != (blocks_out ? boff[(size_t)L] : 0))
+        return fail(c, RC_ERR_ARG, "%s: blocks_len = %lld, the labellings have %lld blocks%s", who, (long long)blocks_len, (long long)boff[(size_t)L],
+                    blocks_out ? "" : " (and blocks_out is NULL: pass 0)");
+    HIPCHK(c, hipSetDevice(c->dev));
+    rc = sync_and_check(c, true);
+    if (rc != RC_OK) return rc;
+    if (c->sC) HIPCHK(c, hipStreamSynchronize(c->sC));
+    LgMemo memo;
+    Call a{c, n, L, labels, r, p, &P, loglik_out, logprior_out, blocks_out, K.data(), boff.data(),
+           env_flag("RC_SCORE_ROWS_GLOBAL"),                                  // tests: gather from the rows in global memory at small n
+           env_workspace_kib("RC_SCORE_WORKSPACE_KIB", slab::WORKSPACE), &memo};
+    // Chunks.  Device bytes per row for a run of labellings: the staged row and its slots' sums.  Labellings are taken while 512
+    // rows (or all n) of them fit the workspace, their sorted orders fit theirs and their blocks a quarter of the workspace; the
+    // rows then go in chunks of what fits.
+    const int64_t ms_cap = slab_ms_cap(slab::PERM_BYTES, 4, n);
+    double ms_acc = 0.0;
+    for (int64_t s0 = 0; s0 < L;) {
+        const SlabChunk ch = slab_plan(s0, K.data(), L, ms_cap, 16 * (size_t)n, 0, n, std::min<int64_t>(n, 512), a.workspace,
+                                       [](size_t k) { return 32 * (k * (k + 1) / 2); }, a.workspace / 4);
+        rc = run_labellings(who, a, s0, ch.ms, ch.qc, ms_acc);
+        if (rc != RC_OK) return rc;
+        s0 += ch.ms;
+    }
+    if (K_out) for (int64_t s = 0; s < L; ++s) K_out[s] = K[(size_t)s];
+    if (eD_out) *eD_out = c->eD;
+    if (eL_out) *eL_out = c->eL;
+    if (kernel_ms) *kernel_ms = ms_acc;
+    return RC_OK;
+}
+
 }  // namespace scr
 
 extern "C" int32_t rc_score_labellings(rc_ctx *c, int64_t L, const int64_t *labels, const double *r, const double *p,
@@ -196,41 +242,7 @@ extern "C" int32_t rc_score_labellings(rc_ctx *c, int64_t L, const int64_t *labe
     if (rc != RC_OK) return rc;
     rc = check_label_rows(c, who, "labelling", labels, L, n);
     if (rc != RC_OK) return rc;
-    std::vector<int> K, seen;
-    std::vector<int64_t> boff;
-    try { K.assign((size_t)L, 0); seen.assign((size_t)n + 1, -1); boff.assign((size_t)L + 1, 0); }
-    catch (const std::bad_alloc &) { return fail(c, RC_ERR_OOM, "%s: no host memory", who); }
-    const int64_t over = count_clusters(labels, L, n, slab::KMAX, seen, K.data());
-    if (over < L) return fail(c, RC_ERR_CAPACITY, "%s: labelling %lld has %d clusters, more than the %lld whose bins fit the workgroup's LDS", who, (long long)over + 1, K[(size_t)over], (long long)slab::KMAX);
-    for (int64_t s = 0; s < L; ++s) boff[(size_t)s + 1] = boff[(size_t)s] + (int64_t)K[(size_t)s] * (K[(size_t)s] + 1) / 2;
-    if (blocks_len != (blocks_out ? boff[(size_t)L] : 0))
-        return fail(c, RC_ERR_ARG, "%s: blocks_len = %lld, the labellings have %lld blocks%s", who, (long long)blocks_len, (long long)boff[(size_t)L],
-                    blocks_out ? "" : " (and blocks_out is NULL: pass 0)");
-    HIPCHK(c, hipSetDevice(c->dev));
-    rc = sync_and_check(c, true);
-    if (rc != RC_OK) return rc;
-    if (c->sC) HIPCHK(c, hipStreamSynchronize(c->sC));
-    scr::LgMemo memo;
-    scr::Call a{c, n, L, labels, r, p, &P, loglik_out, logprior_out, blocks_out, K.data(), boff.data(),
-                env_flag("RC_SCORE_ROWS_GLOBAL"),                             // tests: gather from the rows in global memory at small n
-                env_workspace_kib("RC_SCORE_WORKSPACE_KIB", slab::WORKSPACE), &memo};
-    // Chunks.  Device bytes per row for a run of labellings: the staged row and its slots' sums.  Labellings are taken while 512
-    // rows (or all n) of them fit the workspace, their sorted orders fit theirs and their blocks a quarter of the workspace; the
-    // rows then go in chunks of what fits.
-    const int64_t ms_cap = slab_ms_cap(slab::PERM_BYTES, 4, n);
-    double ms_acc = 0.0;
-    for (int64_t s0 = 0; s0 < L;) {
-        const SlabChunk ch = slab_plan(s0, K.data(), L, ms_cap, 16 * (size_t)n, 0, n, std::min<int64_t>(n, 512), a.workspace,
-                                       [](size_t k) { return 32 * (k * (k + 1) / 2); }, a.workspace / 4);
-        rc = scr::run_labellings(who, a, s0, ch.ms, ch.qc, ms_acc);
-        if (rc != RC_OK) return rc;
-        s0 += ch.ms;
-    }
-    if (K_out) for (int64_t s = 0; s < L; ++s) K_out[s] = K[(size_t)s];
-    if (eD_out) *eD_out = c->eD;
-    if (eL_out) *eL_out = c->eL;
-    if (kernel_ms) *kernel_ms = ms_acc;
-    return RC_OK;
+    return scr::score_valid(c, who, L, labels, r, p, P, loglik_out, logprior_out, K_out, blocks_out, blocks_len, kernel_ms, eD_out, eL_out);
 }
 
 extern "C" int32_t rc_loglik_from_blocks(int64_t n, int64_t K, const int64_t *sizes, const int64_t *blocks, int32_t eD, int32_t eL,

@@ -379,7 +379,8 @@ def _hclust_cuts(samples_or_counts, linkage, maxK, numsamples, ctx, device, *, l
 
 
 def hclustpointestimate(samples_or_counts=None, loss="VI", linkage="average", *, maxK: int = 0, numsamples=None, ctx=None,
-                        device: int = 0, exact: bool = False, criterion: str = "loss", data=None, params=None, r=None, p=None):
+                        device: int = 0, exact: bool = False, criterion: str = "loss", data=None, params=None, r=None, p=None,
+                        polish: bool = False):
     """The hierarchical point estimate: hclust's dendrogram cut at the number of clusters K in 1..maxK of minimum expected
     loss (ties: the smaller K).  loss: "binder" — from the exact curve binder_num — or "VI", the lower bound expectedloss(…,
     "VI") evaluates, computed for every cut on the device.  maxK = 0 means ⌈n/8⌉.  Returns (clust, info): the cut
@@ -394,7 +395,9 @@ def hclustpointestimate(samples_or_counts=None, loss="VI", linkage="average", *,
     criterion="posterior": the cut of highest log-posterior under the model instead of lowest expected loss — mapestimate
     (score.py) over the maxK cuts, one device pass over the matrices of data (a Context, an MCMCData or a dissimilarity
     matrix) with params and r, p (scalars or one per cut; None: the posterior means of an MCMCResult's r and p).  info has K,
-    loglik, logprior, logposterior (per K = 1..maxK), merges, binder_num, kernel_ms, score_ms.
+    loglik, logprior, logposterior (per K = 1..maxK), merges, binder_num, kernel_ms, score_ms.  polish=True (this criterion
+    only; the default is off) passes the chosen cut through searchmapestimate under its r and p — a climb over all partitions
+    from the cut and from empty labels; the result is never worse than the cut, and info["polish"] is that search's info.
 
     criterion="silhouette": the best separated cut — the one of highest mean silhouette width (profiles.py: exact integer
     sums of D on the device, the quotients on the host) among the cuts of 2..maxK clusters (one cluster has silhouette 0 by
@@ -403,6 +406,8 @@ def hclustpointestimate(samples_or_counts=None, loss="VI", linkage="average", *,
     binder_num, kernel_ms, profile_ms."""
     if criterion not in ("loss", "posterior", "silhouette"):
         raise ValueError("criterion must be 'loss', 'posterior' or 'silhouette'")
+    if polish and criterion != "posterior":
+        raise ValueError("polish=True goes with criterion='posterior'")
     source = (samples_or_counts, linkage, maxK, numsamples, ctx, device)
     if criterion != "loss":
         if exact:
@@ -431,6 +436,10 @@ def hclustpointestimate(samples_or_counts=None, loss="VI", linkage="average", *,
         clust, sc = mapestimate(data, cuts, params, r, p, device=device)
         info = dict(merges=res["merges"], binder_num=res["binder_num"], kernel_ms=res["kernel_ms"], score_ms=sc["kernel_ms"],
                     loglik=sc["loglik"], logprior=sc["logprior"], logposterior=sc["logposterior"], K=sc["index"] + 1)
+        if polish:
+            from .score import searchmapestimate
+            rk, pk = (np.broadcast_to(np.asarray(x, dtype=np.float64).reshape(-1), (len(cuts),))[sc["index"]] for x in (r, p))
+            clust, info["polish"] = searchmapestimate(data, [clust], params, float(rk), float(pk), nruns=1, device=device)
         return clust, info
     if loss not in (_DIST_LOSSES if exact else _PSM_LOSSES):
         raise ValueError("Invalid loss function specifier.")

@@ -115,6 +115,96 @@ def mapestimate(data_or_ctx, candidates, params=None, r=None, p=None, *, scores:
     return S[best].copy(), info
 
 
+def searchmapestimate(data_or_ctx, candidates=None, params=None, r=None, p=None, *, nruns: int = 16, maxK: int = 0, maxsweeps: int = 100,
+                      seed: int = 0, init=None, scores: dict | None = None, device: int = 0):
+    """Search ALL partitions for the clustering of maximum log-posterior (csrc/mapsearch.inc.hip through rc_map_search; DESIGN.md
+    §8 "MAP search"): a one-point-at-a-time climb of loglik + logprior from the best candidates, where mapestimate only picks
+    among them.  Runs on the GPU, every run one workgroup; there is no CPU fallback.
+
+    data_or_ctx, candidates, params, r, p, scores: as mapestimate's (an MCMCResult brings its r and p, and its params for data
+    that is not a Context).  The candidates are scored and the climb starts from the nruns distinct ones of highest
+    log-posterior, each under its own r and p; every row of init (labels 0..n, 0 = unallocated) is a start too, and so is the
+    empty labelling — a sequential allocation — these under the best candidate's r and p.  candidates=None: r and p must be
+    given (scalars) and the starts are init and the empty labelling.  Every run visits the points in a permutation of its own,
+    drawn from seed in run order as _search_starts draws them (Philox, key = seed).  maxK: the cap on the number of
+    clusters (0: min(n, 1024)); a start with more clusters than the cap is an error; maxsweeps bounds the sweeps.
+
+    Returns (clust, info) shaped like mapestimate's: info has index (of the best candidate, None without candidates),
+    start_logposterior and logposterior (per run; the first is NaN for a start with unallocated points), loglik, logprior,
+    sweeps, converged, moves, K, capped, labels (per run), runs (the starts as rows of labels), best (the run returned, or −1
+    when no run beat the best candidate, which is then returned as mapestimate would), candidate_logposterior and kernel_ms.
+    The result is never worse than mapestimate's on the same candidates."""
+    ctx, own = _context(data_or_ctx, device)
+    try:
+        if params is None and own:
+            params = getattr(candidates, "params", None)
+            if params is None:
+                raise ValueError("params are needed with data that is not a Context")
+        P = None if params is None else _params_dict(params)
+        n = ctx.n
+        starts, rs, ps = [], [], []
+        cand_best, cand_lp, S = None, None, None
+        if candidates is not None:
+            S = _labellings(candidates)
+            if S.shape[1] != n:
+                raise ValueError("the candidates must have the data's n columns")
+            if r is None and p is None and hasattr(candidates, "clusts"):
+                r, p = getattr(candidates, "r", None), getattr(candidates, "p", None)
+            if r is None or p is None:
+                raise ValueError("the log-posterior needs r and p")
+            rc_, pc_ = _per_labelling(r, len(S), "r"), _per_labelling(p, len(S), "p")
+            sc = scores if scores is not None else ctx.score(S, rc_, pc_, P)
+            cand_lp = np.asarray(sc["logposterior"], dtype=np.float64)
+            if cand_lp.shape != (len(S),):
+                raise ValueError("the scores are not of these candidates")
+            cand_best = int(np.argmax(cand_lp))
+            seen = set()
+            for c in np.argsort(-cand_lp, kind="stable"):               # the highest first, the smaller index on ties
+                key = _lib_sortlabels(S[c]).tobytes()
+                if key in seen:
+                    continue
+                seen.add(key)
+                if len(starts) == int(nruns):
+                    break
+                starts.append(S[c]); rs.append(rc_[c]); ps.append(pc_[c])
+            r0, p0 = float(rc_[cand_best]), float(pc_[cand_best])
+        else:
+            if r is None or p is None:
+                raise ValueError("without candidates r and p must be given")
+            r0, p0 = float(np.asarray(r).reshape(-1)[0]), float(np.asarray(p).reshape(-1)[0])
+        for lab in ([] if init is None else np.atleast_2d(np.asarray(init))):
+            if len(lab) != n:
+                raise ValueError("every labelling in init must have n entries")
+            starts.append(np.asarray(lab, np.int64)); rs.append(r0); ps.append(p0)
+        starts.append(np.zeros(n, np.int64)); rs.append(r0); ps.append(p0)
+        rng = np.random.Generator(np.random.Philox(key=int(seed)))
+        orders = [rng.permutation(n).astype(np.int32) + 1 for _ in range(len(starts))]
+        runs = np.stack(starts)
+        need = max(len(np.unique(x[x > 0])) for x in runs)
+        if maxK and need > maxK:
+            raise ValueError(f"a start has {need} clusters, more than maxK = {maxK}")
+        res = ctx.map_search(runs, np.stack(orders), np.asarray(rs), np.asarray(ps), P, maxK=maxK, maxsweeps=maxsweeps)
+        best = res["best"]
+        info = {k: res[k] for k in ("start_logposterior", "logposterior", "loglik", "logprior", "sweeps", "converged", "moves", "K",
+                                    "capped", "labels", "kernel_ms")}
+        info.update(runs=runs, index=cand_best, candidate_logposterior=cand_lp, best=best)
+        if cand_lp is not None and not res["logposterior"][best] > cand_lp[cand_best]:
+            info["best"] = -1                                           # no run beat the best candidate: mapestimate's answer
+            return S[cand_best].copy(), info
+        return res["labels"][best].copy(), info
+    finally:
+        if own:
+            ctx.close()
+
+
+def _lib_sortlabels(z) -> np.ndarray:
+    """labels renamed 1..K by first appearance: equal for equal partitions"""
+    _, first, inv = np.unique(z, return_index=True, return_inverse=True)
+    rank = np.empty(len(first), np.int64)
+    rank[np.argsort(first)] = np.arange(1, len(first) + 1)
+    return rank[inv.reshape(-1)]
+
+
 def reweight(data_or_ctx, result, new_params, *, scores: dict | None = None, device: int = 0):
     """Prior-sensitivity analysis without running the chain again: importance weights of the samples of an MCMCResult under
     other hyperparameters.  One device pass gives every sample's block sums (scores: that pass's dict, if the caller has it —

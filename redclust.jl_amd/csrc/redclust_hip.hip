@@ -1682,9 +1682,9 @@ __global__ __launch_bounds__(256, RC_SYML_MINWAVES) void k_bulk_syml32(View V, i
 #endif
 
 // sums of two / four 64-bit values over each group of 8 consecutive lanes (all lanes of the group receive the totals)
-__device__ __forceinline__ void row8_sum2_dpp(long long &a, long long &b)
+// (on the 32-bit halves the instructions work on: r0 | r1 << 32 and r2 | r3 << 32)
+__device__ __forceinline__ void row8_sum2_dpp_halves(unsigned &r0, unsigned &r1, unsigned &r2, unsigned &r3)
 {
-    unsigned r0 = (unsigned)(u64)a, r1 = (unsigned)((u64)a >> 32), r2 = (unsigned)(u64)b, r3 = (unsigned)((u64)b >> 32);
 #define RC_DPP_STEP2(ctrl)                                           \
     "v_add_co_u32_dpp %0, vcc, %0, %0 " ctrl "\n\t"                  \
     "v_addc_co_u32_dpp %1, vcc, %1, %1, vcc " ctrl "\n\t"            \
@@ -1699,7 +1699,37 @@ __device__ __forceinline__ void row8_sum2_dpp(long long &a, long long &b)
                  :
                  : "vcc");
 #undef RC_DPP_STEP2
+}
+__device__ __forceinline__ void row8_sum2_dpp(long long &a, long long &b)
+{
+    unsigned r0 = (unsigned)(u64)a, r1 = (unsigned)((u64)a >> 32), r2 = (unsigned)(u64)b, r3 = (unsigned)((u64)b >> 32);
+    row8_sum2_dpp_halves(r0, r1, r2, r3);
     a = (long long)(((u64)r1 << 32) | r0); b = (long long)(((u64)r3 << 32) | r2);
+}
+
+// A lane's direction-2 total of its row in a 64-row half, from the halves row8_sum2_dpp_halves leaves.  Of the eight 8-row groups of
+// a half exactly one is the lane's (`mine`), so the total is that group's sum: HALVES keeps it as two 32-bit registers and takes it
+// with one select each.  Otherwise it is added under the lane's condition as one 64-bit value: the halves are first moved into
+// an aligned register pair for the 64-bit add (gfx950's v_lshl_add_u64), four moves and more per total.
+template <bool HALVES> struct S2Sum;
+template <> struct S2Sum<false> {
+    long long v = 0;
+    __device__ __forceinline__ void take(bool mine, unsigned lo, unsigned hi) { if (mine) v += (long long)(((u64)hi << 32) | lo); }
+    __device__ __forceinline__ long long get() const { return v; }
+    __device__ __forceinline__ void clear() { v = 0; }
+};
+template <> struct S2Sum<true> {
+    unsigned lo = 0, hi = 0;
+    __device__ __forceinline__ void take(bool mine, unsigned alo, unsigned ahi) { lo = mine ? alo : lo; hi = mine ? ahi : hi; }
+    __device__ __forceinline__ long long get() const { return (long long)(((u64)hi << 32) | lo); }
+    __device__ __forceinline__ void clear() { lo = hi = 0; }
+};
+
+// lane l's 64-bit value, to every lane (l uniform): two v_readlane_b32 into a scalar pair
+__device__ __forceinline__ long long rc_readlane64(long long v, int l)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u64)v, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((u64)v >> 32), l);
+    return (long long)(((u64)hi << 32) | lo);
 }
 
 // storage of D as the fast path streams it: int64 entries (16 B per lane and row), or — PACK — the 48-bit packed copy (12 B per
@@ -1769,9 +1799,11 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
 {
     typedef typename S2Raw<PACK>::T raw_t;
 #ifndef RC_S2_STEPS
-#define RC_S2_STEPS 14   // what rides on the folded table, for per-step measurements (tools/build_variants.sh): 2 bias per flush, 4 atomic addresses behind the branch, 8 no selects in units of whole lanes
+#define RC_S2_STEPS 126  // for per-step measurements (tools/build_variants.sh).  What rides on the folded table: 2 bias per flush, 4 atomic addresses behind the branch, 8 no selects in units of whole lanes.
+                         // Direction 2 of every instantiation: 16 two-cluster units split by class without per-lane branches, 32 the donor's hand-over as a single-lane operation, 64 totals kept as 32-bit halves
 #endif
     constexpr bool LATE = FOLD && (RC_S2_STEPS & 2), BR3 = FOLD && (RC_S2_STEPS & 4), BR4 = FOLD && (RC_S2_STEPS & 8);
+    constexpr bool STEPA = (RC_S2_STEPS & 16) != 0, STEPB = (RC_S2_STEPS & 32) != 0, STEPC = (RC_S2_STEPS & 64) != 0;
     RC_PF(long long pf_wait = 0; long long pf_tiles = 0; long long pf_setup = 0; long long pf_log = 0; long long pf_d2 = 0; long long pf_issue = 0; long long pf_ldsw = 0; long long pf_d1 = 0;)
     RC_PF(const long long pf_t0 = __builtin_amdgcn_s_memtime(); const long long pf_r0 = __builtin_amdgcn_s_memrealtime();)
     (void)pf_out;
@@ -1895,13 +1927,40 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
         const bool donor = !whole0 && in0 && in1 && lane < 63 && r_whole != 0 && r_cs0 == cs1;
         const bool whole = whole0 || donor;                               // contributes a value of class(cs0) through LDS
         const bool any_odd = __ballot(!whole) != 0;                       // uniform
-        const bool any_donor = __ballot(donor) != 0;                      // uniform
+        const u64 bDonor = __ballot(donor);
+        const bool any_donor = bDonor != 0;                               // uniform
+        // One donor (a labelling in contiguous runs has at most one per unit; strays left by moves can make more): its lane number
+        // is a scalar, and the hand-over is two readlanes and an add in the one lane to its right instead of a wave-wide shift
+        const bool one_donor = STEPB && __popcll(bDonor) == 1;            // uniform
+        const int dlane = __builtin_amdgcn_readfirstlane(any_donor ? __ffsll((long long)bDonor) - 1 : 0);
+        int more_donors = any_donor && !one_donor;                        // uniform; opaque, so that the two branches of hand_over are not merged into an if / else again
+        asm volatile("" : "+v"(more_donors));
+        more_donors = __builtin_amdgcn_readfirstlane(more_donors);
+        const bool takes = one_donor && lane == dlane + 1;
         // class of the source lanes: bit l set = lane l's pre-added value belongs to cluster B.  Kept as the (scalar) ballot and cut
         // to the eight source lanes 8 tq .. 8 tq + 7 of a transposed value where it is used: a per-lane copy is one more long-lived
         // vector register, and a spilled register in this loop is fatal — its reload waits on the counter the prefetched rows use
         const u64 bB = __ballot(whole && cs0 == dsB);
+        // Two clusters, the common case (a 128-column block is narrower than a cluster): when the lanes of one class are all above
+        // the whole lanes of the other — lanes that are not whole write zeros and may count as either — every lane octet but one
+        // belongs to one class, and which octet is split (`oct`), at which of its eight values (`cut`: the case of the switch in the
+        // transposed read, + 8 when the octet reads its pieces swizzled) and which class is the upper one are all scalars.  Any
+        // other arrangement of the B lanes keeps the per-lane class masks (`straight` false).
+        bool straight = false, upperB = true;                             // uniform
+        int oct = 8, cut = 0;
+        if (STEPA && hasB) {
+            const u64 mA = __ballot(whole) & ~bB;
+            const int firstB = bB ? __ffsll((long long)bB) - 1 : 64, firstA = mA ? __ffsll((long long)mA) - 1 : 64;
+            const bool runB = firstB == 64 || (mA >> firstB) == 0, runA = firstA == 64 || (bB >> firstA) == 0;
+            const int first = runB ? firstB : firstA;
+            straight = runB || runA; upperB = runB;
+            oct = __builtin_amdgcn_readfirstlane(first >> 3);
+            cut = __builtin_amdgcn_readfirstlane((first & 7) | ((RC_S2_SWZ && (first & 32)) ? 8 : 0));
+        }
+        const bool in_oct = tq == oct, above_oct = tq > oct;
         long long aD0 = 0, aD1 = 0, aL0 = 0, aL1 = 0;                   // direction 1, slot `cur`
-        long long rDA = 0, rLA = 0, rDB = 0, rLB = 0;                   // direction 2: row h0 + 8 (lane & 7) + (lane >> 3)
+        // direction 2, row h0 + 8 (lane & 7) + (lane >> 3): cluster A's (all columns' in a `straight` unit) and cluster B's (the upper class's)
+        S2Sum<STEPC> rDA, rLA, rDB, rLB;
         int cur = -1;
         // The 64-bit atomics execute at the memory side, 64-byte request by 64-byte request, at about a fifth of the read rate
         // — so every atomic instruction should fill its requests.  A lane's direction-1 sums are two adjacent columns (16 contiguous
@@ -1955,6 +2014,23 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
             cntA = 2 * __popcll(mA) - __popcll(bDn & mA) + __popcll((bDn << 1) & mA);
             cntB = 2 * __popcll(bB) - __popcll(bDn & bB) + __popcll((bDn << 1) & bB);
         }
+        // the donors' second columns go to the lanes on their right, and the donors keep their first (units with a donor only)
+        auto hand_over = [&](long long (&vd)[2], long long (&vl)[2], const ll2 (&x)[2], const ll2 (&y)[2]) {
+            // (two uniform branches that change the values in place, not an if / else: the join of two definitions cost eight moves)
+            if (one_donor) {
+                const long long gd0 = rc_readlane64(x[0].y, dlane), gl0 = rc_readlane64(y[0].y, dlane),
+                                gd1 = rc_readlane64(x[1].y, dlane), gl1 = rc_readlane64(y[1].y, dlane);
+                if (takes) { vd[0] += gd0; vl[0] += gl0; vd[1] += gd1; vl[1] += gl1; }
+                if (donor) { vd[0] = x[0].x; vl[0] = y[0].x; vd[1] = x[1].x; vl[1] = y[1].x; }
+            }
+            if (more_donors) {
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const long long gd = wave_from_prev64(donor ? x[u].y : 0), gl = wave_from_prev64(donor ? y[u].y : 0);
+                    vd[u] = (donor ? x[u].x : vd[u]) + gd; vl[u] = (donor ? y[u].x : vl[u]) + gl;
+                }
+            }
+        };
         for (int h0 = a0; h0 < a1; h0 += 64) {                            // 64-row halves (direction-2 totals live one row per lane)
             const int h1 = min(h0 + 64, a1);
             const int rowslots = (h0 + lane < h1) ? slot[h0 + lane] : -1; // slot of row h0 + lane (read back with readlane)
@@ -2029,13 +2105,8 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
                     if constexpr (BR4) {
                         long long vd[2], vl[2];
 #pragma unroll
-                        for (int u = 0; u < 2; ++u) {
-                            vd[u] = x[u].x + x[u].y; vl[u] = y[u].x + y[u].y;
-                            if (any_donor) {
-                                const long long gd = wave_from_prev64(donor ? x[u].y : 0), gl = wave_from_prev64(donor ? y[u].y : 0);
-                                vd[u] = (donor ? x[u].x : vd[u]) + gd; vl[u] = (donor ? y[u].x : vl[u]) + gl;
-                            }
-                        }
+                        for (int u = 0; u < 2; ++u) { vd[u] = x[u].x + x[u].y; vl[u] = y[u].x + y[u].y; }
+                        if (any_donor) hand_over(vd, vl, x, y);
                         if (any_odd) {   // uniform, rare (a real branch: the asm statements keep the selects and the address arithmetic from being hoisted in front of it)
                             asm volatile("; lanes that are not whole");
                             if (!whole) {
@@ -2060,16 +2131,15 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
                         }
                     } else {
                     if (!(RC_S2_EXP & 4)) {
+                        long long vd[2], vl[2];
+#pragma unroll
+                        for (int u = 0; u < 2; ++u) { vd[u] = x[u].x + x[u].y; vl[u] = y[u].x + y[u].y; }
+                        if (any_donor) hand_over(vd, vl, x, y);
 #pragma unroll
                         for (int u = 0; u < 2; ++u) {
-                            long long vd = x[u].x + x[u].y, vl = y[u].x + y[u].y;
-                            if (any_donor) {
-                                const long long gd = wave_from_prev64(donor ? x[u].y : 0), gl = wave_from_prev64(donor ? y[u].y : 0);
-                                vd = (donor ? x[u].x : vd) + gd; vl = (donor ? y[u].x : vl) + gl;
-                            }
-                            if (any_odd && !whole) { vd = 0; vl = 0; }
-                            pD[(2 * q + u) * RC_S2_PITCH + lane] = vd;
-                            pL[(2 * q + u) * RC_S2_PITCH + lane] = vl;
+                            if (any_odd && !whole) { vd[u] = 0; vl[u] = 0; }
+                            pD[(2 * q + u) * RC_S2_PITCH + lane] = vd[u];
+                            pL[(2 * q + u) * RC_S2_PITCH + lane] = vl[u];
                         }
                     }
                     if (any_odd) {   // uniform, rare: the elements of the lanes that are not whole
@@ -2115,11 +2185,54 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
                 }
                 __builtin_amdgcn_wave_barrier();
                 const bool mine = tq == ((a - h0) >> 3);
+                auto lo32 = [](long long v) { return (unsigned)(u64)v; };
+                auto hi32 = [](long long v) { return (unsigned)((u64)v >> 32); };
                 if (!hasB) {
-                    long long sD = ((vD[0] + vD[1]) + (vD[2] + vD[3])) + ((vD[4] + vD[5]) + (vD[6] + vD[7]));
-                    long long sL = ((vL[0] + vL[1]) + (vL[2] + vL[3])) + ((vL[4] + vL[5]) + (vL[6] + vL[7]));
-                    row8_sum2_dpp(sD, sL);
-                    if (mine) { rDA += sD; rLA += sL; }
+                    const long long sD = ((vD[0] + vD[1]) + (vD[2] + vD[3])) + ((vD[4] + vD[5]) + (vD[6] + vD[7]));
+                    const long long sL = ((vL[0] + vL[1]) + (vL[2] + vL[3])) + ((vL[4] + vL[5]) + (vL[6] + vL[7]));
+                    unsigned s0 = lo32(sD), s1 = hi32(sD), s2 = lo32(sL), s3 = hi32(sL);
+                    row8_sum2_dpp_halves(s0, s1, s2, s3);
+                    rDA.take(mine, s0, s1); rLA.take(mine, s2, s3);
+                } else if (straight) {
+                    // One octet total per matrix in every lane.  The upper class's part of it is the whole total above the split octet,
+                    // nothing below it and, in the split octet, the values from the cut on: the total, or its upper half h1 when the cut
+                    // lies there, less the values of that half in front of the cut (value j came from source lane 8 tq + j, swizzled:
+                    // + (j ^ 2)).  Those are picked before the sum tree — afterwards only h1 and the total are alive: the partial sums
+                    // of both matrices kept for this choice cost the registers the kernel does not have.  The other class is what is
+                    // left of the total: taken off once per 64 rows, where the totals are written out.
+                    long long lowD = 0, lowL = 0;
+#define RC_S2_CUT(n, e) case n: { { const long long (&v)[8] = vD; lowD = (e); } { const long long (&v)[8] = vL; lowL = (e); } } break;
+                    switch (cut) {                                        // (0, 4, 8, 12: the cut starts a half)
+                    RC_S2_CUT(1, v[0])
+                    RC_S2_CUT(2, v[0] + v[1])
+                    RC_S2_CUT(3, (v[0] + v[1]) + v[2])
+                    RC_S2_CUT(5, v[4])
+                    RC_S2_CUT(6, v[4] + v[5])
+                    RC_S2_CUT(7, (v[4] + v[5]) + v[6])
+                    RC_S2_CUT(9, v[2])
+                    RC_S2_CUT(10, v[2] + v[3])
+                    RC_S2_CUT(11, (v[2] + v[3]) + v[0])
+                    RC_S2_CUT(13, v[6])
+                    RC_S2_CUT(14, v[6] + v[7])
+                    RC_S2_CUT(15, (v[6] + v[7]) + v[4])
+                    default: break;
+                    }
+#undef RC_S2_CUT
+                    struct Tree { long long h1, tot; };
+                    auto tree = [](const long long (&v)[8]) {
+                        Tree T;
+                        T.h1 = (v[4] + v[5]) + (v[6] + v[7]); T.tot = ((v[0] + v[1]) + (v[2] + v[3])) + T.h1;
+                        return T;
+                    };
+                    const Tree TD = tree(vD), TL = tree(vL);
+                    const bool upper_half = (cut & 4) != 0;               // uniform
+                    long long uD = (upper_half ? TD.h1 : TD.tot) - lowD, uL = (upper_half ? TL.h1 : TL.tot) - lowL;
+                    uD = above_oct ? TD.tot : in_oct ? uD : 0ll; uL = above_oct ? TL.tot : in_oct ? uL : 0ll;
+                    unsigned s0 = lo32(TD.tot), s1 = hi32(TD.tot), s2 = lo32(TL.tot), s3 = hi32(TL.tot);
+                    unsigned u0 = lo32(uD), u1 = hi32(uD), u2 = lo32(uL), u3 = hi32(uL);
+                    row8_sum2_dpp_halves(s0, s1, s2, s3);
+                    row8_sum2_dpp_halves(u0, u1, u2, u3);
+                    rDA.take(mine, s0, s1); rLA.take(mine, s2, s3); rDB.take(mine, u0, u1); rLB.take(mine, u2, u3);
                 } else {
                     unsigned mB = (unsigned)(bB >> (8 * tq)) & 0xFFu;
                     if (jsw) mB = ((mB & 0x33u) << 2) | ((mB >> 2) & 0x33u);   // value j of this lane came from source lane 8 tq + (j ^ 2)
@@ -2136,9 +2249,11 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
                             if ((mB >> j) & 1) { sDB += vD[j]; sLB += vL[j]; } else { sDA += vD[j]; sLA += vL[j]; }
                         }
                     }
-                    row8_sum2_dpp(sDA, sLA);
-                    row8_sum2_dpp(sDB, sLB);
-                    if (mine) { rDA += sDA; rLA += sLA; rDB += sDB; rLB += sLB; }
+                    unsigned s0 = lo32(sDA), s1 = hi32(sDA), s2 = lo32(sLA), s3 = hi32(sLA);
+                    unsigned u0 = lo32(sDB), u1 = hi32(sDB), u2 = lo32(sLB), u3 = hi32(sLB);
+                    row8_sum2_dpp_halves(s0, s1, s2, s3);
+                    row8_sum2_dpp_halves(u0, u1, u2, u3);
+                    rDA.take(mine, s0, s1); rLA.take(mine, s2, s3); rDB.take(mine, u0, u1); rLB.take(mine, u2, u3);
                 }
                 RC_PF(asm volatile("" ::: "memory"); pf_d2 += __builtin_amdgcn_s_memtime() - pr0;)
             }
@@ -2146,8 +2261,13 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
             // direction 2 write-out: lane l holds the totals of row h0 + 8 (l & 7) + (l >> 3); through the bounce lane l gets row h0 + l
             {
                 const int mine_ = 8 * tq + tr, row = h0 + lane;
+                long long wDA = rDA.get(), wLA = rLA.get(), wDB = rDB.get(), wLB = rLB.get();
+                if (straight) {   // uniform: (all columns, upper class) -> (A, B)
+                    wDA -= wDB; wLA -= wLB;
+                    if (!upperB) { long long t_ = wDA; wDA = wDB; wDB = t_; t_ = wLA; wLA = wLB; wLB = t_; }
+                }
                 __builtin_amdgcn_wave_barrier();
-                bounce[mine_] = rDA; bounce[64 + mine_] = rLA;
+                bounce[mine_] = wDA; bounce[64 + mine_] = wLA;
                 __builtin_amdgcn_wave_barrier();
                 long long tD = bounce[lane], tL = bounce[64 + lane];
                 __builtin_amdgcn_wave_barrier();
@@ -2157,7 +2277,7 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
                     if (tL) add64(SL + (size_t)dsA * ld + row, tL);
                 }
                 if (hasB) {
-                    bounce[mine_] = rDB; bounce[64 + mine_] = rLB;
+                    bounce[mine_] = wDB; bounce[64 + mine_] = wLB;
                     __builtin_amdgcn_wave_barrier();
                     long long uD = bounce[lane], uL = bounce[64 + lane];
                     __builtin_amdgcn_wave_barrier();
@@ -2168,7 +2288,7 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
                     }
                 }
             }
-            rDA = rLA = rDB = rLB = 0;
+            rDA.clear(); rLA.clear(); rDB.clear(); rLB.clear();
         }
         flush1();
         // diagonal (S includes j = i): D[a][a] -> S[slot_a][a], added by the column block's first unit; logD's diagonal is 0

@@ -658,6 +658,64 @@ int32_t rc_predict(int32_t device, int64_t n, int64_t q,
                    int32_t *eD_out /* q or NULL */, int32_t *eL_out /* q or NULL */, double *kernel_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Predict from points: rc_predict for new observations given by their coordinates.  The distances, their logarithms, the
+ * quantisation and the per-cluster summary of the draws stay on the device, and the samples are uploaded once per chunk of
+ * samples, however many new points there are.  No context: errors through rc_last_error(NULL).  DESIGN.md §8 "Predict from
+ * points".
+ *
+ * Distance: d_ij = sqrt(Σ_k (y_ik − x_jk)²) of new point i (row i of new_points) and training point j (row j of points), the
+ * coordinates k in ascending order: acc = +0; per coordinate t = y_ik − x_jk (one subtraction) and acc = fma(t, t, acc) (one
+ * explicit fused multiply-add); d_ij = the correctly rounded square root of acc.  Direct differences, so a new point next to
+ * a training point does not cancel to zero; the bits are part of the contract (tests/predict_points_ref.py restates them).
+ * Logarithm: the resolver's own table-driven one: log_ij is what rc_debug_flog with which = 0 returns for d_ij.
+ * Quantisation, per new point, on the device: eD_i = 62 − ex − ceil(log2 n) with max_j d_ij < 2^ex, eL_i likewise from
+ * max_j |log_ij| over the whole row (rc_predict's rule when it is given logarithms), q_ij = the round-to-nearest-even integer
+ * of ldexp(·, e).
+ * Everything after that is rc_predict's: sums, scores, draws, counters, tie rules and the optional outputs scores_out,
+ * sums_out (Kmax as there), eD_out, eL_out and kernel_ms.  Defining property: with D = dist_out and L = log_out of a call,
+ * rc_predict(D, L, … the same arguments …) returns the same labels, map, scores, sums, eD and eL, bit for bit.
+ * dist_out, log_out (may be NULL; host q×n, filled chunk by chunk): the distances and logarithms; for tests and small q.
+ *
+ * Counts (counts_out for the draws, mapcounts_out for map; uint32 q×(K_p + 1); either may be NULL).  They need maps (the
+ * maps_out of rc_relabel for the same samples: maps[s][t] the pivot label that the t-th smallest label of sample s is sent
+ * to, 0 unmatched, −1 for t >= K_s; maps_width columns) and pivot_labels (the pivot's K_p labels, ascending).  The label of
+ * (sample s, new point i) is 0 or the t-th smallest label of sample s; it counts in column k of row i when maps[s][t] is the
+ * k-th pivot label (k = 1..K_p) and in column 0 otherwise (a cluster of its own, or a cluster of the sample without a
+ * counterpart).  Every row sums to m.  The counts of the whole call (4·q·(K_p + 1) bytes each) live on the device and
+ * accumulate there across chunks of samples.  labels_out and map_out may both be NULL when a counts output is given — then
+ * nothing of size m×q crosses the bus; at least one of the four must be given.
+ *
+ * q is unbounded: the new points go through rc_predict's workspace plan in chunks, a new point costing its coordinates, its
+ * f64 distances (and logarithms when log_out is given) beside what it costs there; the sorted orders of a chunk of samples
+ * are built and uploaded once for all chunks of points.  RC_PREDICT_WORKSPACE_KIB and RC_PREDICT_ROWS_GLOBAL apply as for
+ * rc_predict.  A new point's outputs are a pure function of its own coordinates, the training points, the samples and the
+ * offsets.
+ *
+ * Errors.  RC_ERR_ARG: a NULL required pointer (points, new_points, samples, r, p, params); none of labels_out, map_out,
+ * counts_out, mapcounts_out given; n, q or m < 1; dim outside 1..2^20; a counts output without maps or pivot_labels; and,
+ * as for rc_predict, a label outside 1..n, r, p, params, Kmax below a K_s, a device that is not there; with a counts output
+ * also maps_width below a K_s, pivot_labels not strictly ascending in 1..n, a maps entry that is neither 0, nor −1 at
+ * t >= K_s, nor a pivot label.  RC_ERR_CAPACITY (checked before any array is read): n > 32767 or m·n >= 2^31.
+ * RC_ERR_DOMAIN: a coordinate that is not finite (checked on the host before any device work); a squared distance that is
+ * 0, subnormal or not finite — a new point that coincides with a training point, or coordinates whose scale underflows or
+ * overflows the square — found on the device through a flag word, never by a fault: the message names the first such (new
+ * point, training point) pair, 1-based, in row-major order; outputs of earlier chunks may have been written by then.
+ * ------------------------------------------------------------------------------------------------------------- */
+int32_t rc_predict_points(int32_t device, int64_t n, int64_t dim, const double *points /* n×dim row-major */,
+                          int64_t q, const double *new_points /* q×dim row-major */,
+                          int64_t m, const int64_t *samples /* m×n, labels 1..n */,
+                          const double *r /* m */, const double *p /* m */, const rc_params *params,
+                          uint64_t seed, uint64_t sample_offset, uint64_t point_offset,
+                          int64_t *labels_out /* m×q or NULL */, int64_t *map_out /* m×q or NULL */,
+                          const int64_t *maps /* m×maps_width or NULL */, int64_t maps_width,
+                          const int64_t *pivot_labels /* Kp, ascending, or NULL */, int64_t Kp,
+                          void *counts_out /* uint32_t q×(Kp+1) or NULL */, void *mapcounts_out /* uint32_t q×(Kp+1) or NULL */,
+                          int64_t Kmax, double *scores_out /* m×q×(Kmax+1) or NULL */,
+                          int64_t *sums_out /* m×q×Kmax×2 or NULL */,
+                          double *dist_out /* q×n or NULL */, double *log_out /* q×n or NULL */,
+                          int32_t *eD_out /* q or NULL */, int32_t *eL_out /* q or NULL */, double *kernel_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Joint predict: new observations that may form clusters with each other.  One posterior sample (training labels z over n
  * points, r_s, p_s) defines an independent problem whose state is z, which never changes, and the labels y_1..y_q of the q
  * new observations, which start unallocated.  No context: errors through rc_last_error(NULL).  DESIGN.md §8 "Joint predict".

@@ -602,6 +602,60 @@ end
 export predict
 
 """
+    predict_points(HIPBackend(), result, points, new_points; relabelling = nothing, seed = 0)
+
+Allocate any number of new observations given by their coordinates to the clusters of every sample of `result` on the GPU
+(rc_predict_points): `points` is n×dim, the training observations one per row, `new_points` q×dim.  The distances (direct
+differences, one fused multiply-add per coordinate, a correctly rounded root), their logarithms and the quantisation are taken
+on the device, and the samples are uploaded once.  Without `relabelling` it returns `(labels, map_labels)` as `predict`.  With
+`relabelling` (what `relabel(HIPBackend(), result, pivot)` returned for the same samples) it returns
+`(counts = …, map_counts = …, pivot_labels = …)`: `counts[i, k]`, k = 1..K_p+1, is the number of samples in which new
+observation `i`'s draw lands in the pivot's cluster `pivot_labels[k-1]` (column 1: a cluster of its own, or one without a
+counterpart); nothing of size m×q leaves the device.
+"""
+function predict_points(b::HIPBackend, result, points::Matrix{Float64}, new_points::Matrix{Float64}; relabelling = nothing, seed = 0)
+    samples = samplematrix(result)
+    n, m = size(samples)
+    dim = size(points, 2)
+    q = size(new_points, 1)
+    size(points, 1) == n || throw(ArgumentError("points must have one row per training observation."))
+    size(new_points, 2) == dim || throw(ArgumentError("new_points must have the dimension of points."))
+    X = permutedims(points)                                       # dim×n column-major = n×dim row-major
+    Y = permutedims(new_points)
+    r = Vector{Float64}(result.r); p = Vector{Float64}(result.p)
+    ms = Cdouble[0]
+    if relabelling === nothing
+        labels = Matrix{Int64}(undef, q, m)                       # column s = sample s: row-major m×q for the library
+        maplabels = Matrix{Int64}(undef, q, m)
+        rc = ccall((:rc_predict_points, LIB), Int32,
+                   (Int32, Int64, Int64, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{RcParams},
+                    UInt64, UInt64, UInt64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Cvoid}, Ptr{Cvoid},
+                    Int64, Ptr{Cdouble}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}),
+                   b.device, n, dim, X, q, Y, m, samples, r, p, Ref(RcParams(result.params)), seed % UInt64, UInt64(0), UInt64(0),
+                   labels, maplabels, C_NULL, 0, C_NULL, 0, C_NULL, C_NULL, 0, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, ms)
+        check(Ptr{Cvoid}(C_NULL), rc)
+        return (labels, maplabels)
+    end
+    names = Vector{Int64}(relabelling.pivot_labels)
+    Kp = length(names)
+    col = Dict(l => k for (k, l) in enumerate(names))             # the library wants pivot labels in 1..n: pass the columns
+    maps = permutedims(map(l -> l > 0 ? Int64(col[l]) : Int64(l), relabelling.maps))      # W×m column-major = m×W row-major
+    cols = Vector{Int64}(1:Kp)
+    counts = Matrix{UInt32}(undef, Kp + 1, q)                     # row-major q×(K_p+1)
+    mapcounts = Matrix{UInt32}(undef, Kp + 1, q)
+    rc = ccall((:rc_predict_points, LIB), Int32,
+               (Int32, Int64, Int64, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{RcParams},
+                UInt64, UInt64, UInt64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Cvoid}, Ptr{Cvoid},
+                Int64, Ptr{Cdouble}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}),
+               b.device, n, dim, X, q, Y, m, samples, r, p, Ref(RcParams(result.params)), seed % UInt64, UInt64(0), UInt64(0),
+               C_NULL, C_NULL, maps, size(maps, 1), cols, Kp, counts, mapcounts, 0, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, ms)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return (counts = permutedims(counts), map_counts = permutedims(mapcounts), pivot_labels = names, kernel_ms = ms[1])
+end
+
+export predict_points
+
+"""
     predict_joint(HIPBackend(), result, Dnew, Dnn; sweeps = 2, seed = 0) -> (labels, first_labels, K, moves)
 
 Allocate new observations to the clusters of every sample of `result` jointly, on the GPU (rc_predict_joint): under one sample

@@ -224,6 +224,10 @@ SIGNATURES = {
     "rc_predict": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.POINTER(RcParams), C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "rc_predict_points": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.POINTER(RcParams), C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "rc_predict_joint": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.POINTER(RcParams), C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
@@ -1012,6 +1016,67 @@ def predict(Dnew, samples, r, p, params: dict, seed: int = 0, sample_offset: int
         out["scores"] = sc[:m, :q]
     if want_sums:
         out["sums"] = sm[:m, :q, :int(Kmax)]
+    return out
+
+
+def predict_points(points, new_points, samples, r, p, params: dict, seed: int = 0, sample_offset: int = 0, point_offset: int = 0,
+                   want_labels: bool = True, want_map: bool = True, maps=None, pivot_labels=None, want_counts: bool = False,
+                   want_mapcounts: bool = False, Kmax: int = 0, want_scores: bool = False, want_sums: bool = False,
+                   want_dist: bool = False, want_log: bool = False, device: int = 0) -> dict:
+    """rc_predict_points: as predict for q×dim new points and the n×dim training points, the distances and their logarithms
+    taken on the device: labels and map (m×q, or None), eD / eL (q), kernel_ms and, when asked for, scores and sums (with Kmax),
+    dist and log (q×n), and — with maps (m×W, rc_relabel's) and pivot_labels (K_p, ascending) — counts and mapcounts
+    (q×(K_p+1) uint32)."""
+    L = lib()
+    X = np.ascontiguousarray(points, dtype=np.float64)
+    Y = np.ascontiguousarray(new_points, dtype=np.float64)
+    S = np.ascontiguousarray(samples, dtype=np.int64)
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    if X.ndim != 2 or Y.ndim != 2 or S.ndim != 2 or X.shape[0] != S.shape[1] or Y.shape[1] != X.shape[1]:
+        raise ValueError("points must be n×dim, new_points q×dim and samples m×n")
+    (n, dim), q, m = X.shape, Y.shape[0], S.shape[0]
+    if r.shape != (m,) or p.shape != (m,):
+        raise ValueError("r and p must hold one value per sample")
+    mp_ = pv = None
+    W = Kp = 0
+    if maps is not None:
+        mp_ = np.ascontiguousarray(maps, dtype=np.int64)
+        if mp_.ndim != 2 or mp_.shape[0] != m:
+            raise ValueError("maps must be m×W")
+        W = mp_.shape[1]
+    if pivot_labels is not None:
+        pv = np.ascontiguousarray(pivot_labels, dtype=np.int64).reshape(-1)
+        Kp = len(pv)
+    prm = _params_struct(params)
+    labels = np.zeros((max(m, 1), max(q, 1)), np.int64) if want_labels else None
+    mp = np.zeros((max(m, 1), max(q, 1)), np.int64) if want_map else None
+    cnt = np.zeros((max(q, 1), Kp + 1), np.uint32) if want_counts else None
+    mcnt = np.zeros((max(q, 1), Kp + 1), np.uint32) if want_mapcounts else None
+    sc = np.zeros((max(m, 1), max(q, 1), int(Kmax) + 1)) if want_scores else None
+    sm = np.zeros((max(m, 1), max(q, 1), max(int(Kmax), 1), 2), np.int64) if want_sums else None
+    dist = np.zeros((max(q, 1), max(n, 1))) if want_dist else None
+    lg = np.zeros((max(q, 1), max(n, 1))) if want_log else None
+    eD, eL = np.zeros(max(q, 1), np.int32), np.zeros(max(q, 1), np.int32)
+    ms = C.c_double()
+    M64 = 0xFFFFFFFFFFFFFFFF
+    ptr = lambda a: None if a is None else a.ctypes.data
+    rc = L.rc_predict_points(int(device), n, dim, X.ctypes.data, q, Y.ctypes.data, m, S.ctypes.data, r.ctypes.data, p.ctypes.data,
+                             C.byref(prm), int(seed) & M64, int(sample_offset) & M64, int(point_offset) & M64, ptr(labels), ptr(mp),
+                             ptr(mp_), W, ptr(pv), Kp, ptr(cnt), ptr(mcnt), int(Kmax), ptr(sc), ptr(sm), ptr(dist), ptr(lg),
+                             eD.ctypes.data, eL.ctypes.data, C.byref(ms))
+    _check(rc)
+    cut = lambda a: None if a is None else a[:m, :q]
+    out = dict(labels=cut(labels), map=cut(mp), eD=eD[:q], eL=eL[:q], kernel_ms=float(ms.value),
+               counts=None if cnt is None else cnt[:q], mapcounts=None if mcnt is None else mcnt[:q])
+    if want_scores:
+        out["scores"] = sc[:m, :q]
+    if want_sums:
+        out["sums"] = sm[:m, :q, :int(Kmax)]
+    if want_dist:
+        out["dist"] = dist[:q, :n]
+    if want_log:
+        out["log"] = lg[:q, :n]
     return out
 
 

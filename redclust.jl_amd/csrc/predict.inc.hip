@@ -17,6 +17,10 @@
 //
 // k_predict_draw: one wave per (sample, new point), one lane per candidate: score, Philox, noise; then a wave
 // argmax whose key (value, then smaller label, the new cluster last) gives the tie rule whatever the reduction order.
+//
+// prd::Run holds a chunk of samples on the device and does everything that follows once a chunk of new points has its rows
+// there; rc_predict fills them from the host (run_samples below), rc_predict_points on the device (predictpoints.inc.hip),
+// which also asks for k_draw_counts, the per-cluster summary of the draws.
 
 namespace prd {
 
@@ -109,7 +113,7 @@ __global__ __launch_bounds__(TPB2) void k_predict_draw(const DrawArgs a)
 // what the caller passed, after the checks
 struct Call {
     int64_t n, q, m, Kmax;
-    const double *Dnew, *logDnew;
+    const double *Dnew, *logDnew;    // rc_predict's host rows (null for rc_predict_points, whose rows are filled on the device)
     const int64_t *samples;
     const double *r, *p;
     const rc_params *P;
@@ -121,76 +125,125 @@ struct Call {
     const double *A;                 // [n + 1]
     const double2 *d_flt;
     bool rows_global;
+    // the per-cluster summary of rc_predict_points (predictpoints.inc.hip): maps [m][maps_width], the Kp pivot labels
+    // ascending, and the device [q][Kp + 1] counts of the whole call that the draws (the arg-maxes) are added to
+    const int64_t *maps = nullptr, *pivot = nullptr;
+    int64_t maps_width = 0, Kp = 0;
+    unsigned *d_counts = nullptr, *d_mapcounts = nullptr;
 };
 
-// samples s0 .. s0 + ms - 1 against every new point, the points in chunks of at most qc.  ms_acc: device milliseconds, added to.
-static int32_t run_samples(const char *who, const Call &c, int64_t s0, int64_t ms, int64_t qc, double &ms_acc)
+// counts[point0 + i][col] += the samples s whose label of new point i sits in a slot of column col: labels [ms][npts] as
+// k_predict_draw wrote them (0: column 0), a sample's slots in ascending label order, colslot [ktot] the column of every slot.
+// One block per new point, the histogram in LDS (Kp + 1 counters); the launches of one stream follow each other, so the
+// block adds to its own row of the counts without atomics.
+__global__ __launch_bounds__(TPB2) void k_draw_counts(const long long *__restrict__ labels, int ms, int npts, const long long *__restrict__ koff,
+                                                         const int *__restrict__ K, const int2 *__restrict__ szlab, const int *__restrict__ colslot,
+                                                         int ncols, unsigned *__restrict__ counts)
 {
-    const int64_t n = c.n;
-    const bool want_tab = c.scores_out || c.sums_out;
-    const int Kcols = want_tab ? (int)c.Kmax : 0;
+    extern __shared__ unsigned prd_hist[];
+    const int i = blockIdx.x;
+    for (int k = threadIdx.x; k < ncols; k += TPB2) prd_hist[k] = 0;
+    __syncthreads();
+    for (int s = threadIdx.x; s < ms; s += TPB2) {
+        const int l = (int)labels[(size_t)s * npts + i];
+        int col = 0;
+        if (l > 0) {
+            const long long k0 = koff[s];
+            int lo = 0, hi = K[s] - 1;              // the label is one of the sample's: the search ends on it
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (szlab[k0 + mid].y < l) lo = mid + 1; else hi = mid;
+            }
+            col = colslot[k0 + lo];
+        }
+        atomicAdd(&prd_hist[col], 1u);
+    }
+    __syncthreads();
+    unsigned *row = counts + (size_t)i * (size_t)ncols;
+    for (int k = threadIdx.x; k < ncols; k += TPB2) {
+        const unsigned h = prd_hist[k];
+        if (h) row[k] += h;
+    }
+}
+
+// A chunk of samples s0 .. s0 + ms - 1 on the device — their sorted orders, the host's part of their scores, the buffers of at
+// most qc new points — and everything that follows once the (Dq, Lq) rows and the scales of a chunk of new points are in
+// d_rows, d_scD and d_scL: rc_predict fills them from the host, rc_predict_points on the device.
+struct Run {
     Orders O;
-    std::vector<double> base, newscore;
-    bool ok = true;
-    try {
-        long long kt = 0;
-        for (int64_t s = 0; s < ms; ++s) kt += c.K[s0 + s];
-        base.resize((size_t)kt); newscore.resize((size_t)ms);
-    } catch (const std::bad_alloc &) { ok = false; }
-    ok = ok && O.build(c.samples, n, c.K, s0, ms, false, [&](int64_t s, long long at, int64_t, int sz) {
-        base[(size_t)at] = c.A[sz] + (std::log(c.p[s0 + s]) + std::log((double)sz - 1.0 + c.r[s0 + s]));
-    });
-    if (!ok) return fail(nullptr, RC_ERR_OOM, "%s: no host memory for the sorted orders of %lld samples", who, (long long)ms);
-    const long long ktot = O.ktot;
-    for (int64_t s = 0; s < ms; ++s) {
-        const double r = c.r[s0 + s], p = c.p[s0 + s];
-        const int K = O.Ks[(size_t)s];
-        newscore[(size_t)s] = (c.P->maxK == 0 || K < c.P->maxK) ? std::log((double)(K + 1)) + r * std::log(1 - p) : -INFINITY;
+    DeviceBuffers B;
+    TimingEvents ev;
+    int64_t s0 = 0, ms = 0;
+    int Kcols = 0;
+    long long ktot = 0;
+    double *d_base = nullptr, *d_newscore = nullptr, *d_scD = nullptr, *d_scL = nullptr, *d_scores = nullptr;
+    ll2 *d_rows = nullptr, *d_sums = nullptr;
+    long long *d_labels = nullptr, *d_map = nullptr, *d_sums_out = nullptr;
+    int *d_colslot = nullptr;
+    std::vector<long long> h_lab, h_tab;
+    std::vector<double> h_sc;
+
+    int32_t begin(const char *who, const Call &c, int64_t s0_, int64_t ms_, int64_t qc)
+    {
+        s0 = s0_; ms = ms_;
+        const int64_t n = c.n;
+        const bool want_tab = c.scores_out || c.sums_out;
+        Kcols = want_tab ? (int)c.Kmax : 0;
+        std::vector<double> base, newscore;
+        std::vector<int> colslot;
+        bool ok = true;
+        try {
+            long long kt = 0;
+            for (int64_t s = 0; s < ms; ++s) kt += c.K[s0 + s];
+            base.resize((size_t)kt); newscore.resize((size_t)ms);
+            if (c.d_counts || c.d_mapcounts) colslot.resize((size_t)kt);
+        } catch (const std::bad_alloc &) { ok = false; }
+        ok = ok && O.build(c.samples, n, c.K, s0, ms, false, [&](int64_t s, long long at, int64_t, int sz) {
+            base[(size_t)at] = c.A[sz] + (std::log(c.p[s0 + s]) + std::log((double)sz - 1.0 + c.r[s0 + s]));
+        });
+        if (!ok) return fail(nullptr, RC_ERR_OOM, "%s: no host memory for the sorted orders of %lld samples", who, (long long)ms);
+        ktot = O.ktot;
+        for (int64_t s = 0; s < ms; ++s) {
+            const double r = c.r[s0 + s], p = c.p[s0 + s];
+            const int K = O.Ks[(size_t)s];
+            newscore[(size_t)s] = (c.P->maxK == 0 || K < c.P->maxK) ? std::log((double)(K + 1)) + r * std::log(1 - p) : -INFINITY;
+            if (colslot.empty()) continue;
+            for (int t = 0; t < K; ++t) {           // checked by the entry point: 0 or a pivot label
+                const int64_t to = c.maps[(size_t)(s0 + s) * c.maps_width + t];
+                colslot[(size_t)(O.koff[(size_t)s] + t)] = to > 0 ? (int)(std::lower_bound(c.pivot, c.pivot + c.Kp, to) - c.pivot) + 1 : 0;
+            }
+        }
+
+        HIPCHK(nullptr, O.upload(B));
+        HIPCHK(nullptr, B.alloc(d_base, (size_t)ktot));
+        HIPCHK(nullptr, B.alloc(d_newscore, (size_t)ms));
+        HIPCHK(nullptr, B.alloc(d_scD, (size_t)qc));
+        HIPCHK(nullptr, B.alloc(d_scL, (size_t)qc));
+        HIPCHK(nullptr, B.alloc(d_rows, (size_t)qc * n));
+        HIPCHK(nullptr, B.alloc(d_sums, (size_t)qc * ktot));
+        HIPCHK(nullptr, B.alloc(d_labels, (size_t)qc * ms));
+        HIPCHK(nullptr, B.alloc(d_map, (size_t)qc * ms));
+        if (c.scores_out) HIPCHK(nullptr, B.alloc(d_scores, (size_t)qc * ms * (Kcols + 1)));
+        if (c.sums_out) HIPCHK(nullptr, B.alloc(d_sums_out, (size_t)qc * ms * std::max(Kcols, 1) * 2));
+        HIPCHK(nullptr, hipMemcpy(d_base, base.data(), (size_t)ktot * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(nullptr, hipMemcpy(d_newscore, newscore.data(), (size_t)ms * sizeof(double), hipMemcpyHostToDevice));
+        if (!colslot.empty()) {
+            HIPCHK(nullptr, B.alloc(d_colslot, (size_t)ktot));
+            HIPCHK(nullptr, hipMemcpy(d_colslot, colslot.data(), (size_t)ktot * sizeof(int), hipMemcpyHostToDevice));
+        }
+        try {
+            if (c.labels_out || c.map_out) h_lab.resize((size_t)qc * ms);
+            if (c.scores_out) h_sc.resize((size_t)qc * ms * (Kcols + 1));
+            if (c.sums_out) h_tab.resize((size_t)qc * ms * std::max(Kcols, 1) * 2);
+        } catch (const std::bad_alloc &) { return fail(nullptr, RC_ERR_OOM, "%s: no host memory for a chunk of %lld new points", who, (long long)qc); }
+        HIPCHK(nullptr, ev.create());
+        return RC_OK;
     }
 
-    DeviceBuffers B;
-    double *d_base, *d_newscore, *d_scD, *d_scL;
-    ll2 *d_rows, *d_sums; long long *d_labels, *d_map, *d_sums_out = nullptr; double *d_scores = nullptr;
-    HIPCHK(nullptr, O.upload(B));
-    HIPCHK(nullptr, B.alloc(d_base, (size_t)ktot));
-    HIPCHK(nullptr, B.alloc(d_newscore, (size_t)ms));
-    HIPCHK(nullptr, B.alloc(d_scD, (size_t)qc));
-    HIPCHK(nullptr, B.alloc(d_scL, (size_t)qc));
-    HIPCHK(nullptr, B.alloc(d_rows, (size_t)qc * n));
-    HIPCHK(nullptr, B.alloc(d_sums, (size_t)qc * ktot));
-    HIPCHK(nullptr, B.alloc(d_labels, (size_t)qc * ms));
-    HIPCHK(nullptr, B.alloc(d_map, (size_t)qc * ms));
-    if (c.scores_out) HIPCHK(nullptr, B.alloc(d_scores, (size_t)qc * ms * (Kcols + 1)));
-    if (c.sums_out) HIPCHK(nullptr, B.alloc(d_sums_out, (size_t)qc * ms * std::max(Kcols, 1) * 2));
-    HIPCHK(nullptr, hipMemcpy(d_base, base.data(), (size_t)ktot * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(nullptr, hipMemcpy(d_newscore, newscore.data(), (size_t)ms * sizeof(double), hipMemcpyHostToDevice));
-
-    std::vector<ll2> rows;
-    std::vector<long long> h_lab, h_tab;
-    std::vector<double> h_sc, scD, scL;
-    try {
-        rows.resize((size_t)qc * n); h_lab.resize((size_t)qc * ms); scD.resize((size_t)qc); scL.resize((size_t)qc);
-        if (c.scores_out) h_sc.resize((size_t)qc * ms * (Kcols + 1));
-        if (c.sums_out) h_tab.resize((size_t)qc * ms * std::max(Kcols, 1) * 2);
-    } catch (const std::bad_alloc &) { return fail(nullptr, RC_ERR_OOM, "%s: no host memory for a chunk of %lld new points", who, (long long)qc); }
-    TimingEvents ev;
-    HIPCHK(nullptr, ev.create());
-    const rc_params &P = *c.P;
-    for (int64_t i0 = 0; i0 < c.q; i0 += qc) {
-        const int64_t np = std::min(qc, c.q - i0);
-        for (int64_t i = 0; i < np; ++i) {
-            const double *x = c.Dnew + (size_t)(i0 + i) * n, *lx = c.logDnew ? c.logDnew + (size_t)(i0 + i) * n : nullptr;
-            const int eD = c.eD[i0 + i], eL = c.eL[i0 + i];
-            ll2 *dst = rows.data() + (size_t)i * n;
-            for (int64_t j = 0; j < n; ++j) {
-                dst[j].x = std::llrint(std::ldexp(x[j], eD));
-                dst[j].y = std::llrint(std::ldexp(lx ? lx[j] : std::log(x[j]), eL));
-            }
-            scD[(size_t)i] = std::ldexp(1.0, -eD); scL[(size_t)i] = std::ldexp(1.0, -eL);
-        }
-        HIPCHK(nullptr, hipMemcpy(d_rows, rows.data(), (size_t)np * n * sizeof(ll2), hipMemcpyHostToDevice));
-        HIPCHK(nullptr, hipMemcpy(d_scD, scD.data(), (size_t)np * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(nullptr, hipMemcpy(d_scL, scL.data(), (size_t)np * sizeof(double), hipMemcpyHostToDevice));
+    // new points i0 .. i0 + np - 1, their rows and scales on the device: sums, draws, the outputs.  ms_acc: device milliseconds, added to.
+    int32_t finish(const Call &c, int64_t i0, int64_t np, double &ms_acc)
+    {
+        const rc_params &P = *c.P;
         DrawArgs a{};
         a.ms = (int)ms; a.npts = (int)np; a.Kmax = Kcols; a.ktot = ktot; a.sums = d_sums; a.koff = O.d_koff; a.K = O.d_K; a.szlab = O.d_szlab;
         a.base = d_base; a.newscore = d_newscore; a.scD = d_scD; a.scL = d_scL; a.flt = c.d_flt;
@@ -203,6 +256,15 @@ static int32_t run_samples(const char *who, const Call &c, int64_t s0, int64_t m
         HIPCHK(nullptr, ev.begin(0));
         HIPCHK(nullptr, O.launch_sums(d_rows, np, c.rows_global, d_sums));
         k_predict_draw<<<(unsigned)(((size_t)np * ms + TPB2 / 64 - 1) / (TPB2 / 64)), TPB2, 0, 0>>>(a);
+        for (int pass = 0; pass < 2; ++pass) {
+            unsigned *cnt = pass ? c.d_mapcounts : c.d_counts;
+            if (!cnt) continue;
+            const int ncols = (int)c.Kp + 1;
+            const size_t lds = (size_t)ncols * sizeof(unsigned);
+            HIPCHK(nullptr, set_dynamic_lds(k_draw_counts, lds));
+            k_draw_counts<<<(unsigned)np, TPB2, lds, 0>>>(pass ? d_map : d_labels, (int)ms, (int)np, O.d_koff, O.d_K, O.d_szlab, d_colslot, ncols,
+                                                             cnt + (size_t)i0 * (size_t)ncols);
+        }
         HIPCHK(nullptr, ev.end(0));
         HIPCHK(nullptr, ev.elapsed_ms(ms_acc));
         // device [ms][np][..] into the caller's [m][q][..]
@@ -222,6 +284,39 @@ static int32_t run_samples(const char *who, const Call &c, int64_t s0, int64_t m
             HIPCHK(nullptr, hipMemcpy(h_tab.data(), d_sums_out, (size_t)np * ms * w * sizeof(long long), hipMemcpyDeviceToHost));
             for (int64_t s = 0; s < ms; ++s) memcpy(c.sums_out + ((size_t)(s0 + s) * c.q + i0) * w, h_tab.data() + (size_t)s * np * w, (size_t)np * w * sizeof(int64_t));
         }
+        return RC_OK;
+    }
+};
+
+// rc_predict: samples s0 .. s0 + ms - 1 against every new point, the points in chunks of at most qc whose rows are quantised
+// here on the host.  ms_acc: device milliseconds, added to.
+static int32_t run_samples(const char *who, const Call &c, int64_t s0, int64_t ms, int64_t qc, double &ms_acc)
+{
+    const int64_t n = c.n;
+    Run R;
+    int32_t rc = R.begin(who, c, s0, ms, qc);
+    if (rc != RC_OK) return rc;
+    std::vector<ll2> rows;
+    std::vector<double> scD, scL;
+    try { rows.resize((size_t)qc * n); scD.resize((size_t)qc); scL.resize((size_t)qc); }
+    catch (const std::bad_alloc &) { return fail(nullptr, RC_ERR_OOM, "%s: no host memory for a chunk of %lld new points", who, (long long)qc); }
+    for (int64_t i0 = 0; i0 < c.q; i0 += qc) {
+        const int64_t np = std::min(qc, c.q - i0);
+        for (int64_t i = 0; i < np; ++i) {
+            const double *x = c.Dnew + (size_t)(i0 + i) * n, *lx = c.logDnew ? c.logDnew + (size_t)(i0 + i) * n : nullptr;
+            const int eD = c.eD[i0 + i], eL = c.eL[i0 + i];
+            ll2 *dst = rows.data() + (size_t)i * n;
+            for (int64_t j = 0; j < n; ++j) {
+                dst[j].x = std::llrint(std::ldexp(x[j], eD));
+                dst[j].y = std::llrint(std::ldexp(lx ? lx[j] : std::log(x[j]), eL));
+            }
+            scD[(size_t)i] = std::ldexp(1.0, -eD); scL[(size_t)i] = std::ldexp(1.0, -eL);
+        }
+        HIPCHK(nullptr, hipMemcpy(R.d_rows, rows.data(), (size_t)np * n * sizeof(ll2), hipMemcpyHostToDevice));
+        HIPCHK(nullptr, hipMemcpy(R.d_scD, scD.data(), (size_t)np * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(nullptr, hipMemcpy(R.d_scL, scL.data(), (size_t)np * sizeof(double), hipMemcpyHostToDevice));
+        rc = R.finish(c, i0, np, ms_acc);
+        if (rc != RC_OK) return rc;
     }
     return RC_OK;
 }

@@ -5205,6 +5205,24 @@ static int quant_exponent(long long n, double maxabs, int bits)
     std::frexp(maxabs, &ex);
     return bits == 64 ? 62 - ex - ceil_log2_ll(n) : 30 - ex;
 }
+// ... restated for the kernels that derive a row's exponent on the device (predictpoints.inc.hip): frexp's exponent read from
+// the bits of a finite maxabs >= 0, a subnormal normalised first.  The same integer as quant_exponent, which rc_predict's
+// equality with rc_predict_points holds it to (tests/test_gpu_predict_points.py).
+static __host__ __device__ inline int quant_exponent_hd(long long n, double maxabs, int bits)
+{
+    if (maxabs == 0.0) return 0;
+    unsigned long long u;
+    __builtin_memcpy(&u, &maxabs, 8);
+    int ex = (int)((u >> 52) & 0x7FFu) - 1022;
+    if (ex == -1022) {                                                    // subnormal: 2^54 makes it normal, exactly
+        maxabs *= 18014398509481984.0;
+        __builtin_memcpy(&u, &maxabs, 8);
+        ex = (int)((u >> 52) & 0x7FFu) - 1022 - 54;
+    }
+    int b = 0;
+    while (((long long)1 << b) < n) ++b;
+    return bits == 64 ? 62 - ex - b : 30 - ex;
+}
 
 extern "C" const char *rc_last_error(const rc_ctx *ctx) { return ctx ? ctx->err : g_err; }
 
@@ -7953,6 +7971,7 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "slabplan.inc.hpp"
 #include "slab.inc.hip"
 #include "predict.inc.hip"
+#include "predictpoints.inc.hip"
 #include "predictjoint.inc.hip"
 #include "partdist.inc.hip"
 #include "relabel.inc.hip"

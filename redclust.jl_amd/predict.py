@@ -20,11 +20,35 @@ class Prediction:
     """labels[s, i]: the label new point i drew under sample s, in that sample's own label names; 0 = a cluster of its own.
     map_labels: the most probable label instead of a draw.  scores (optional, m×q×(Kmax+1)): the noise-free log weights —
     column t < K_s belongs to the t-th smallest label of sample s, the last column to a new cluster (-inf when maxK forbids
-    it), NaN between.  kernel_ms: device time of the kernels."""
-    labels: np.ndarray
-    map_labels: np.ndarray
+    it), NaN between.  kernel_ms: device time of the kernels.  From predict_points with a relabelling: counts and map_counts
+    (q×(K_p+1) uint32: in how many samples the draw / the most probable label of each new point lands in each of the pivot's
+    clusters, column 0 a cluster of its own or one without a counterpart) and pivot_labels (the K_p names of columns 1..K_p);
+    labels and map_labels are then None unless kept."""
+    labels: np.ndarray | None
+    map_labels: np.ndarray | None
     scores: np.ndarray | None = None
     kernel_ms: float = 0.0
+    counts: np.ndarray | None = None
+    map_counts: np.ndarray | None = None
+    pivot_labels: np.ndarray | None = None
+
+    def allocation_counts(self) -> np.ndarray:
+        """q×(K_p + 1) uint32: the samples in which each new observation's draw goes to each of the pivot's clusters (column
+        k >= 1: pivot_labels[k - 1]; column 0: a cluster of its own or one the pivot has no counterpart for).  Every row sums
+        to m.  Needs a prediction made by predict_points with a relabelling."""
+        if self.counts is None:
+            raise ValueError("this prediction holds no counts: use predict_points with a relabelling")
+        return self.counts
+
+    def probabilities(self) -> np.ndarray:
+        """allocation_counts() / m: what allocation(relabelling, samples) returns, without the m×q labels."""
+        c = self.allocation_counts()
+        return c / float(c[0].sum())
+
+    def hard_allocation(self) -> np.ndarray:
+        """Per new observation the pivot label of largest count, the smaller column on a tie; 0 is possible."""
+        c = self.allocation_counts()
+        return np.concatenate([[0], self.pivot_labels]).astype(np.int64)[np.argmax(c, axis=1)]
 
     def new_cluster_frequency(self) -> np.ndarray:
         """Per new point: the share of samples in which it opened a cluster of its own."""
@@ -167,7 +191,8 @@ def predict(result_or_samples, Dnew=None, *, new_points=None, points=None, r=Non
     sample) and params (a PriorHyperparamsList or a dict of the likelihood hyperparameters) given.  The new data: Dnew
     (q×n, distances of every new observation to every training observation) or new_points with the training points, one
     observation per row — the distances are then computed on the host in row chunks, so q×n never exists at once; every new
-    point is quantised by itself and keyed by its own index, so the chunked result equals the unchunked one."""
+    point is quantised by itself and keyed by its own index, so the chunked result equals the unchunked one.  For many new
+    points given by coordinates use predict_points, which takes the distances and their logarithms on the device."""
     S, r, p, P = _sample_inputs(result_or_samples, r, p, params)
     m, n = S.shape
     if (Dnew is None) == (new_points is None):
@@ -209,6 +234,56 @@ def predict(result_or_samples, Dnew=None, *, new_points=None, points=None, r=Non
             sc[:, i0:i0 + step] = out["scores"]
         ms += out["kernel_ms"]
     return Prediction(labels, maps, sc, ms)
+
+
+def predict_points(result_or_samples, points, new_points, *, relabelling=None, keep_labels=None, r=None, p=None, params=None,
+                   seed: int = 0, scores: bool = False, device: int = 0) -> Prediction:
+    """Allocate any number of new observations, given by their coordinates, to the clusters of every posterior sample
+    (rc_predict_points): the distances to the n training points (one observation per row of `points`), their logarithms, the
+    quantisation and the draws never leave the device, and the samples are uploaded once.  The distance is the Euclidean one,
+    accumulated coordinate by coordinate with fused multiply-adds (include/redclust_hip.h has the exact arithmetic), so the
+    labels are those of predict on those distances with the device's logarithm — not bit for bit those of
+    predict(new_points=…, points=…), whose distances and logarithms are NumPy's and libm's.
+
+    result_or_samples, r, p, params, seed, scores as for predict.  relabelling (pointestimate.relabel of the same samples onto
+    a point estimate): the prediction then carries counts and map_counts, q×(K_p+1), per new observation the number of samples
+    in which it lands in each of the pivot's clusters — Prediction.allocation without the m×q labels.  keep_labels (default:
+    relabelling is None): whether labels and map_labels come back; without them only the counts cross the bus, which is what
+    makes q in the millions practical.  scores needs keep_labels."""
+    S, r, p, P = _sample_inputs(result_or_samples, r, p, params)
+    m, n = S.shape
+    keep = (relabelling is None) if keep_labels is None else bool(keep_labels)
+    if not keep and relabelling is None:
+        raise ValueError("keep_labels=False needs a relabelling: nothing would come back")
+    if scores and not keep:
+        raise ValueError("scores come with the labels: keep_labels must be true")
+    X = np.ascontiguousarray(points, dtype=np.float64)
+    Y = np.ascontiguousarray(new_points, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] != n or X.shape[1] < 1:
+        raise ValueError(f"points must hold the n = {n} training observations, one per row")
+    if Y.ndim != 2 or Y.shape[1] != X.shape[1] or Y.shape[0] < 1:
+        raise ValueError("new_points must hold q >= 1 observations of the training points' dimension, one per row")
+    if not (np.all(np.isfinite(X)) and np.all(np.isfinite(Y))):
+        raise ValueError("points must be finite")
+    maps = names = cols = None
+    if relabelling is not None:
+        names = np.asarray(relabelling.pivot_labels, dtype=np.int64).reshape(-1)
+        maps = np.asarray(relabelling.maps)
+        if maps.ndim != 2 or maps.shape[0] != m:
+            raise ValueError(f"the relabelling must be of the {m} samples")
+        if len(names) < 1 or np.any(np.diff(names) <= 0):
+            raise ValueError("the relabelling's pivot_labels must be ascending")
+        at = np.searchsorted(names, np.maximum(maps, 1))
+        if not np.all((maps <= 0) | (names[np.minimum(at, len(names) - 1)] == maps)):
+            raise ValueError("the relabelling's maps must hold pivot labels")
+        # the library wants pivot labels in 1..n; a pivot may carry any names: pass the columns 1..K_p instead
+        maps = np.where(maps > 0, at + 1, maps).astype(np.int64)
+        cols = np.arange(1, len(names) + 1, dtype=np.int64)
+    Kmax = int(max(len(np.unique(row)) for row in S)) if scores else 0
+    out = _lib.predict_points(X, Y, S, r, p, P, seed=seed, want_labels=keep, want_map=keep, maps=maps, pivot_labels=cols,
+                              want_counts=maps is not None, want_mapcounts=maps is not None, Kmax=Kmax, want_scores=scores,
+                              device=device)
+    return Prediction(out["labels"], out["map"], out.get("scores"), out["kernel_ms"], out["counts"], out["mapcounts"], names)
 
 
 def predict_joint(result_or_samples, Dnew=None, Dnn=None, *, new_points=None, points=None, sweeps: int = 2, r=None, p=None,

@@ -4,6 +4,8 @@ with --joint also of the joint predict (rc_predict_joint; csrc/predictjoint.inc.
     python tools/time_predict.py                       # n = 8192, K = 50, m = 1000 samples, q = 1024 new points
     python tools/time_predict.py --n 2048 --q 256 --reps 3
     python tools/time_predict.py --joint --sweeps 0 2  # rc_predict, then rc_predict_joint with 0 and with 2 Gibbs passes
+    python tools/time_predict.py --points              # predict_points from coordinates (dim = 50): q = 1024 with the labels,
+                                                       # q = 65536 counts only, and predict(new_points=, points=) at q = 1024
 
 Inputs (seed 0): n + q observations from K Gaussian groups in 8 dimensions, the last q held out; the m samples are the true
 training labels with 2 % of the points relabelled at random in each; r and p drawn once per sample; the likelihood
@@ -93,8 +95,58 @@ def joint(a, Dnew, Dnn, S, r, p, P):
                           device_labels_equal=f"{agree}/{k}")), flush=True)
 
 
+def _rss_mib():
+    import resource
+    return round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0, 1)   # the process's peak so far
+
+
+def points(a):
+    """--points: rc.predict_points from coordinates (dim = 50) at q = a.q with the labels kept and at q = a.q_large with only the
+    counts coming back, then, for comparison at q = a.q, rc.predict(new_points=, points=), which builds the distances on the
+    host in chunks and calls rc_predict per chunk.  Peak host RSS is read after each stage, in this order, so a later stage's
+    figure is at least the earlier one's."""
+    dim = 50
+    big = max(a.q, a.q_large)
+    tr, new, truth, S, r, p = planted(a.n, big, a.K, a.m, a.noise, dim=dim)
+    sub = min(a.n, 1024)
+    P = rc.likelihood_hyperparams(distances(tr[:sub], tr[:sub]), truth[:sub] + 1)
+    kw = dict(r=r, p=p, params=P)
+    rc.predict_points(S[:3, :64] % 64 + 1, tr[:64], new[:2], r=r[:3], p=p[:3], params=P)       # module load, first launches
+    rel = rc.relabel(S, truth[:a.n] + 1)
+
+    def timed(what, q, call, reps):
+        first = call()
+        walls, kms = [], []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            o = call()
+            walls.append(time.perf_counter() - t0)
+            kms.append(o.kernel_ms)
+        print(json.dumps(dict(what=what, n=a.n, dim=dim, q=q, m=a.m, K=a.K, reps=reps, kernel_ms_median=round(statistics.median(kms), 3),
+                              kernel_ms_min=round(min(kms), 3), kernel_ms_max=round(max(kms), 3),
+                              wall_s_median=round(statistics.median(walls), 4), wall_s_min=round(min(walls), 4),
+                              wall_s_max=round(max(walls), 4), peak_rss_mib=_rss_mib())), flush=True)
+        return first
+
+    kept = timed("predict_points, labels kept", a.q, lambda: rc.predict_points(S, tr, new[:a.q], **kw), a.reps)
+    hit = float((kept.map_labels == (truth[a.n:a.n + a.q] + 1)[None, :]).mean())
+    only = timed("predict_points, counts only", a.q_large, lambda: rc.predict_points(S, tr, new[:a.q_large], relabelling=rel, **kw),
+                 max(1, min(a.reps, 3)))
+    hard = only.hard_allocation()
+    print(json.dumps(dict(what="predict_points checks", map_equals_truth=round(hit, 4),
+                          hard_allocation_equals_truth=round(float((hard == truth[a.n:a.n + a.q_large] + 1).mean()), 4),
+                          rows_sum_to_m=bool(np.all(only.counts.sum(axis=1) == a.m)))), flush=True)
+    host = timed("predict(new_points=, points=): host distances, rc_predict per chunk", a.q,
+                 lambda: rc.predict(S, new_points=new[:a.q], points=tr, **kw), max(1, min(a.reps, 2)))
+    print(json.dumps(dict(what="predict_points against predict(new_points=, points=)", q=a.q,
+                          labels_equal_share=round(float((host.labels == kept.labels).mean()), 6),
+                          map_labels_equal_share=round(float((host.map_labels == kept.map_labels).mean()), 6))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--points", action="store_true")
+    ap.add_argument("--q-large", type=int, default=65536)
     ap.add_argument("--n", type=int, default=8192)
     ap.add_argument("--q", type=int, default=1024)
     ap.add_argument("--m", type=int, default=1000)
@@ -107,6 +159,8 @@ def main():
     ap.add_argument("--sweeps", type=int, nargs="+", default=[2])
     ap.add_argument("--ref-visits", type=int, default=24)
     a = ap.parse_args()
+    if a.points:
+        return points(a)
     tr, new, truth, S, r, p = planted(a.n, a.q, a.K, a.m, a.noise)
     sub = min(a.n, 1024)
     P = rc.likelihood_hyperparams(distances(tr[:sub], tr[:sub]), truth[:sub] + 1)

@@ -47,9 +47,14 @@ def sqdist(X: np.ndarray, M: np.ndarray) -> np.ndarray:
     return acc
 
 
+def draw_weights(w: np.ndarray, shift: int) -> np.ndarray:
+    """q = floor(w · 2^shift), the integer weights of a draw."""
+    return np.floor(np.ldexp(w, shift)).astype(np.int64)
+
+
 def weighted_draw(w: np.ndarray, shift: int, u: int) -> int:
     """The first index whose inclusive prefix sum of q = floor(w · 2^shift) exceeds (u · W) >> 53, W = Σ q."""
-    q = np.floor(np.ldexp(w, shift)).astype(np.int64)
+    q = draw_weights(w, shift)
     W = int(q.sum(dtype=np.int64))
     if W <= 0:
         raise ValueError("every weight of the draw is zero")
@@ -82,6 +87,22 @@ def ordered_mean(X: np.ndarray, members: np.ndarray) -> np.ndarray:
     return np.cumsum(X[members], axis=0)[-1] / float(len(members))
 
 
+def kmpp_seeds(X: np.ndarray, k: int, seed: int) -> list:
+    """The k-means++ seeds (0-based point indices) in the order they are drawn."""
+    n = X.shape[0]
+    shift = draw_shift(X)
+    p = (u53(seed, k, 0) * n) >> 53
+    seeds = [p]
+    mincost = sqdist(X, X[p:p + 1])[:, 0]
+    mincost[p] = 0.0
+    for s in range(1, k):
+        p = weighted_draw(mincost, shift, u53(seed, k, s))
+        seeds.append(p)
+        mincost = np.minimum(mincost, sqdist(X, X[p:p + 1])[:, 0])
+        mincost[p] = 0.0
+    return seeds
+
+
 def kmeans(X, k: int, maxiter: int = 100, tol: float = 1e-6, seed: int = 0, init=None) -> dict:
     X = np.ascontiguousarray(X, dtype=np.float64)
     n = X.shape[0]
@@ -90,16 +111,7 @@ def kmeans(X, k: int, maxiter: int = 100, tol: float = 1e-6, seed: int = 0, init
     if init is not None:
         M = X[np.asarray(init, dtype=np.int64) - 1].copy()
     else:
-        p = (u53(seed, k, 0) * n) >> 53
-        seeds = [p]
-        mincost = sqdist(X, X[p:p + 1])[:, 0]
-        mincost[p] = 0.0
-        for s in range(1, k):
-            p = weighted_draw(mincost, shift, u53(seed, k, s))
-            seeds.append(p)
-            mincost = np.minimum(mincost, sqdist(X, X[p:p + 1])[:, 0])
-            mincost[p] = 0.0
-        M = X[np.asarray(seeds)].copy()
+        M = X[np.asarray(kmpp_seeds(X, k, seed))].copy()
         ndraw = k
     a, costs, counts, objv = assign(X, M)
     t, conv, repicks = 0, False, 0

@@ -232,40 +232,62 @@ def _seqsum(M, x, mem):
     return s
 
 
-def restricted_scan(D, logD, clusts, sizes, P, r, p, items, cand, final_clusts, seed, it, mh, scan):
+def restricted_item(D, logD, clusts, sizes, P, r, p, x, cand, C, cinds):
+    """One visit of sample_labels_Gibbs_restricted! (mcmc.jl:283-336): item x leaves its cluster (clusts / sizes are
+    modified in place) and the two candidates' logprobs are returned, before sample_logweights or quirk Q2 touch them."""
     d1, d2, al, be, ze, ga = (P[k] for k in ("delta1", "delta2", "alpha", "beta", "zeta", "gamma"))
     abratio = al * np.log(be) - gammaln(al)
     zgratio = ze * np.log(ga) - gammaln(ze)
-    C = np.flatnonzero(sizes > 0) + 1                       # frozen at entry (:273)
-    cinds = [int(np.flatnonzero(C == c)[0]) for c in cand]  # indexin(candidate_clusts, C)
+    sizes[clusts[x] - 1] -= 1
+    clusts[x] = -1
+    a_i = np.zeros(2); b_i = np.zeros(2)
+    for k in range(2):
+        mem = np.flatnonzero(clusts == cand[k])
+        a_i[k] = al + d1 * sizes[cand[k] - 1]
+        b_i[k] = be + _seqsum(D, x, mem)
+    need = sorted(set([0, 1] + cinds))              # only these entries of the K-vectors are ever read
+    z_i = {}; g_i = {}; sl = {}
+    for t in need:
+        mem = np.flatnonzero(clusts == C[t])
+        z_i[t] = ze + d2 * sizes[C[t] - 1]
+        g_i[t] = ga + _seqsum(D, x, mem)
+        sl[t] = _seqsum(logD, x, mem)
+    L1 = np.zeros(2); lpr = np.zeros(2)
+    for k in range(2):
+        sz = sizes[cand[k] - 1]
+        L1[k] = gammaln(a_i[k]) + abratio - a_i[k] * np.log(b_i[k]) + (d1 - 1) * sl[cinds[k]] - sz * gammaln(d1)
+        lpr[k] = np.log(sz + 1) + np.log(p) + np.log(sz - 1 + r) - np.log(sz)
+    L2p = {t: gammaln(z_i[t]) - z_i[t] * np.log(g_i[t]) + zgratio + (d2 - 1) * sl[t] - sizes[C[t] - 1] * gammaln(d2)
+           for t in need}
+    L2_i = L2p[0] + L2p[1]                          # Q3
+    L2 = np.array([L2_i - L2p[cinds[0]], L2_i - L2p[cinds[1]]])
+    return lpr + (L1 + (L2 if P["repulsion"] else 0.0))
+
+
+def restricted_place(clusts, sizes, x, cand, k, logprobs):
+    """Item x joins candidate k; returns the log transition probability the reference accumulates for it (mcmc.jl:338-351),
+    from logprobs as they stand at that line: shifted by sample_logweights after a draw, untouched after a forced choice."""
+    clusts[x] = cand[k]
+    sizes[cand[k] - 1] += 1
+    logprobs = logprobs + logprobs.min()            # Q2 (np.min propagates NaN like Julia's minimum)
+    probs = np.exp(logprobs)
+    probs = probs / (probs[0] + probs[1])
+    return np.log(probs[k])
+
+
+def restricted_frame(sizes, cand):
+    """(C, cinds): the non-empty labels frozen at a scan's entry (:273) and indexin(candidate_clusts, C)."""
+    C = np.flatnonzero(sizes > 0) + 1
+    return C, [int(np.flatnonzero(C == c)[0]) for c in cand]
+
+
+def restricted_scan(D, logD, clusts, sizes, P, r, p, items, cand, final_clusts, seed, it, mh, scan):
+    C, cinds = restricted_frame(sizes, cand)
     m = len(items)
     ltp = 0.0
     with np.errstate(all="ignore"):
         for q, x in enumerate(items):
-            sizes[clusts[x] - 1] -= 1
-            clusts[x] = -1
-            a_i = np.zeros(2); b_i = np.zeros(2)
-            for k in range(2):
-                mem = np.flatnonzero(clusts == cand[k])
-                a_i[k] = al + d1 * sizes[cand[k] - 1]
-                b_i[k] = be + _seqsum(D, x, mem)
-            need = sorted(set([0, 1] + cinds))              # only these entries of the K-vectors are ever read
-            z_i = {}; g_i = {}; sl = {}
-            for t in need:
-                mem = np.flatnonzero(clusts == C[t])
-                z_i[t] = ze + d2 * sizes[C[t] - 1]
-                g_i[t] = ga + _seqsum(D, x, mem)
-                sl[t] = _seqsum(logD, x, mem)
-            L1 = np.zeros(2); lpr = np.zeros(2)
-            for k in range(2):
-                sz = sizes[cand[k] - 1]
-                L1[k] = gammaln(a_i[k]) + abratio - a_i[k] * np.log(b_i[k]) + (d1 - 1) * sl[cinds[k]] - sz * gammaln(d1)
-                lpr[k] = np.log(sz + 1) + np.log(p) + np.log(sz - 1 + r) - np.log(sz)
-            L2p = {t: gammaln(z_i[t]) - z_i[t] * np.log(g_i[t]) + zgratio + (d2 - 1) * sl[t] - sizes[C[t] - 1] * gammaln(d2)
-                   for t in need}
-            L2_i = L2p[0] + L2p[1]                          # Q3
-            L2 = np.array([L2_i - L2p[cinds[0]], L2_i - L2p[cinds[1]]])
-            logprobs = lpr + (L1 + (L2 if P["repulsion"] else 0.0))
+            logprobs = restricted_item(D, logD, clusts, sizes, P, r, p, x, cand, C, cinds)
             if final_clusts is None:
                 logprobs = logprobs - logprobs.min()        # sample_logweights mutates its argument
                 base = 4 + m + 2 * m * scan + 2 * q
@@ -273,25 +295,16 @@ def restricted_scan(D, logD, clusts, sizes, P, r, p, items, cand, final_clusts, 
                 k = int(np.argmax(g))
             else:
                 k = 0 if final_clusts[x] == cand[0] else 1
-            clusts[x] = cand[k]
-            sizes[cand[k] - 1] += 1
-            logprobs = logprobs + logprobs.min()            # Q2 (np.min propagates NaN like Julia's minimum)
-            probs = np.exp(logprobs)
-            probs = probs / (probs[0] + probs[1])
-            ltp += np.log(probs[k])
+            ltp += restricted_place(clusts, sizes, x, cand, k, logprobs)
     return float(ltp)
 
 
-def mh_proposal(D, logD, clusts, sizes, K, P, r, p, numGibbs, seed, it, mh):
-    """One proposal (mcmc.jl:374-473).  Returns (accept, split, skipped, final (clusts, sizes, K) or None, info)."""
-    n = len(clusts)
-    i = min(int(np.floor(uniform_mh(seed, it, mh, 0) * n)), n - 1)
-    j = min(int(np.floor(uniform_mh(seed, it, mh, 1) * (n - 1))), n - 2)
-    if j >= i:
-        j += 1
+def mh_launch(clusts, sizes, K, P, i, j):
+    """The chaperones' launch state before the items of S are allocated (mcmc.jl:380-404): None when the proposal is
+    skipped (maxK), else (S, claunch, szlaunch, Klaunch, cand)."""
     ci, cj = int(clusts[i]), int(clusts[j])
     if P["maxK"] > 0 and ci == cj and int(np.sum(sizes > 0)) >= P["maxK"]:
-        return False, False, True, None, {}
+        return None
     S = [k for k in np.flatnonzero((clusts == ci) | (clusts == cj)) if k != i and k != j]
     claunch, szlaunch, Klaunch = clusts.copy(), sizes.copy(), K
     if ci == cj:
@@ -300,17 +313,26 @@ def mh_proposal(D, logD, clusts, sizes, K, P, r, p, numGibbs, seed, it, mh):
         szlaunch[ci - 1] -= 1
         szlaunch[new - 1] += 1
         Klaunch = K + 1
-    cand = (int(claunch[i]), int(claunch[j]))
-    for q, k in enumerate(S):
-        claunch[k] = cand[0 if uniform_mh(seed, it, mh, 4 + q) < 0.5 else 1]
-        szlaunch[clusts[k] - 1] -= 1
-        szlaunch[claunch[k] - 1] += 1
-    for s in range(numGibbs):
-        restricted_scan(D, logD, claunch, szlaunch, P, r, p, S, cand, None, seed, it, mh, s)
+    return S, claunch, szlaunch, Klaunch, (int(claunch[i]), int(claunch[j]))
+
+
+def mh_allocate(clusts, claunch, szlaunch, k, c):
+    """Item k of S starts in cluster c (mcmc.jl:405-412)."""
+    claunch[k] = c
+    szlaunch[clusts[k] - 1] -= 1
+    szlaunch[c - 1] += 1
+
+
+def mh_finish(D, logD, clusts, sizes, K, P, r, p, i, j, S, claunch, szlaunch, Klaunch, cand, final_scan):
+    """Everything after the numGibbs intermediate scans (mcmc.jl:420-466).  final_scan(claunch, szlaunch, final_clusts)
+    runs the last restricted scan in place and returns its log transition probability: free (final_clusts None) for a
+    split, forced towards the present labels for a merge.  Returns (split, (cfinal, szfinal, Kfinal), lpr, llr, lprop, x)
+    with x the log acceptance ratio before min(0, ·)."""
+    ci, cj = int(clusts[i]), int(clusts[j])
     lg = gammaln
     if ci == cj:
         split = True
-        ltp = restricted_scan(D, logD, claunch, szlaunch, P, r, p, S, cand, None, seed, it, mh, numGibbs)
+        ltp = final_scan(claunch, szlaunch, None)
         cfinal, szfinal, Kfinal = claunch, szlaunch, Klaunch
         lpr = (np.log(K + 1) + r * np.log(1 - p) - np.log(p) - lg(r) + lg(szfinal[cfinal[i] - 1] - 1 + r)
                + lg(szfinal[cfinal[j] - 1] - 1 + r) + np.log(szfinal[cfinal[i] - 1]) + np.log(szfinal[cfinal[j] - 1])
@@ -326,15 +348,35 @@ def mh_proposal(D, logD, clusts, sizes, K, P, r, p, numGibbs, seed, it, mh):
         Kfinal -= 1
         lpr = (-(np.log(K) + r * np.log(1 - p) - np.log(p) - lg(r)) + lg(szfinal[cj - 1] - 1 + r) + np.log(szfinal[cj - 1])
                - (lg(sizes[ci - 1] - 1 + r) + lg(sizes[cj - 1] - 1 + r) + np.log(sizes[ci - 1]) + np.log(sizes[cj - 1])))
-        ltp = restricted_scan(D, logD, claunch, szlaunch, P, r, p, S, cand, clusts, seed, it, mh, numGibbs)
+        ltp = final_scan(claunch, szlaunch, clusts)
         lprop = -ltp
     llr = loglik(D, logD, cfinal, szfinal, P) - loglik(D, logD, clusts, sizes, P)
-    x = lpr + llr - lprop
+    return split, (cfinal, szfinal, Kfinal), lpr, llr, lprop, lpr + llr - lprop
+
+
+def mh_proposal(D, logD, clusts, sizes, K, P, r, p, numGibbs, seed, it, mh):
+    """One proposal (mcmc.jl:374-473).  Returns (accept, split, skipped, final (clusts, sizes, K) or None, info)."""
+    n = len(clusts)
+    i = min(int(np.floor(uniform_mh(seed, it, mh, 0) * n)), n - 1)
+    j = min(int(np.floor(uniform_mh(seed, it, mh, 1) * (n - 1))), n - 2)
+    if j >= i:
+        j += 1
+    launch = mh_launch(clusts, sizes, K, P, i, j)
+    if launch is None:
+        return False, False, True, None, {}
+    S, claunch, szlaunch, Klaunch, cand = launch
+    for q, k in enumerate(S):
+        mh_allocate(clusts, claunch, szlaunch, k, cand[0 if uniform_mh(seed, it, mh, 4 + q) < 0.5 else 1])
+    for s in range(numGibbs):
+        restricted_scan(D, logD, claunch, szlaunch, P, r, p, S, cand, None, seed, it, mh, s)
+    split, final, lpr, llr, lprop, x = mh_finish(
+        D, logD, clusts, sizes, K, P, r, p, i, j, S, claunch, szlaunch, Klaunch, cand,
+        lambda cl, sz, fc: restricted_scan(D, logD, cl, sz, P, r, p, S, cand, fc, seed, it, mh, numGibbs))
     lar = np.nan if np.isnan(x) else min(0.0, x)
     lu = np.log(uniform_mh(seed, it, mh, 2))
     accept = bool(lu < lar)
     info = dict(i=i, j=j, nS=len(S), log_prior_ratio=float(lpr), log_lik_ratio=float(llr), log_proposal_ratio=float(lprop))
-    return accept, split, False, (cfinal, szfinal, Kfinal), info
+    return accept, split, False, final, info
 
 
 def sample_labels(D, logD, clusts, sizes, K, P, r, p, numMH, numGibbs, seed, it):

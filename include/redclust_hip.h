@@ -219,8 +219,14 @@ int32_t rc_set_bulk_kernel(rc_ctx *ctx, int32_t which);
  *   "fold_log_table" 1 (default): a context that derives logD and whose entries span at most four binades runs the row reduction
  *                    that reads the exponent from its log table (k_bulk_syml2); 0: always the one that derives it per entry
  *                    (k_bulk_syml2w; same integers)
+ *   "syml2_unit_rows" (tests) 0 (default): k_bulk_syml2's plan chooses the rows per work unit; 8..128, a multiple of 8: fixes
+ *                    them and plans the unit lists again (the pipeline is drained first; same integers) — with 8-row units a
+ *                    problem of n = 2560 has more units than resident waves, which the plan's own choice reaches from n ~ 14 000
  * No reference counterpart (the reference has no tuning knobs on this path). */
 int32_t rc_set_option(rc_ctx *ctx, const char *name, int64_t value);
+/* The plan of k_bulk_syml2's fast path (contexts with 64-bit storage): resident waves, fast work units, rows per unit and the
+ * most units dealt to one wave.  Any pointer may be NULL.  No reference counterpart. */
+int32_t rc_bulk_plan_info(rc_ctx *ctx, int32_t *waves, int32_t *fast_units, int32_t *unit_rows, int32_t *max_units_per_wave);
 /* Internal point layout.  rc_set_state stores D and logD with the points of a cluster contiguous (a stable sort of
  * the caller's points by label), so that k_bulk_sym applies whatever order the caller's points come in; the sweep
  * still visits the points in the caller's order and every output is in the caller's order.  Label movement

@@ -245,6 +245,7 @@ SIGNATURES = {
     "rc_map_search": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RcParams), C.c_int32,
                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rc_layout_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rc_bulk_plan_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rc_event_overhead_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "rc_kernel_timing": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "rc_capacity_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -466,7 +467,8 @@ class Context:
 
     def set_option(self, name, value):
         """rc_set_option: "prune" (-1 automatic / 0 / 1), "lds_point_cache" (0 / 1), "chain_workers", "chain_depth" (0 = automatic), "chain_pipeline" (0 / 1),
-        "fold_log_table" (1 / 0: 0 keeps a derived context on k_bulk_syml2w, the row reduction that derives the exponent per entry)."""
+        "fold_log_table" (1 / 0: 0 keeps a derived context on k_bulk_syml2w, the row reduction that derives the exponent per entry),
+        "syml2_unit_rows" (tests: 0 automatic, or 8..128 rows per work unit of k_bulk_syml2; plans its unit lists again)."""
         self._chk(self.L.rc_set_option(self.h, name.encode(), int(value)))
 
     def run_chain(self, numiters, burnin, thin, numGibbs, numMH, seed, r0, p0, proposalsd_r, splitmerge="as_written",
@@ -679,6 +681,12 @@ class Context:
                     medoid_within=[medw[off[i]:off[i + 1]] for i in range(nl)],
                     within=None if per[0] is None else per[0][:nl], nearest=None if per[1] is None else per[1][:nl],
                     neighbour=None if per[2] is None else per[2][:nl], eD=int(eD.value), kernel_ms=float(ms.value))
+
+    def syml2_plan_info(self) -> dict:
+        """rc_bulk_plan_info: resident waves, fast units, rows per unit and the most units in one wave of k_bulk_syml2's plan"""
+        v = [C.c_int32(0) for _ in range(4)]
+        self._chk(self.L.rc_bulk_plan_info(self.h, *[C.byref(x) for x in v]))
+        return dict(waves=v[0].value, fast_units=v[1].value, unit_rows=v[2].value, max_units_per_wave=v[3].value)
 
     def layout_info(self):
         """(layouts built so far, label runs in the internal point order)"""

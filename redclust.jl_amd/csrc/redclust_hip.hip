@@ -212,6 +212,7 @@ struct View {
     const int4 *ufast, *uslow; // unit lists of k_bulk_syml2 (c0, first row, end row, 0), grouped by wave: the units its fast path takes / the rest
     const int *wfast, *wslow;  // [nwaves + 1] offsets of each wave's units in the two lists (build_syml2_lists: balanced by cost)
     int nfast, nslow;
+    int s2_touch;              // 1: this launch of the folded k_bulk_syml2 warms L2 ahead of its row requests (enqueue_bulk decides per launch)
     DevScalars *sc;
     HostSummary *hsum;         // device address of the host-mapped summary
     double scD, scL;           // 2^-eD, 2^-eL
@@ -1799,8 +1800,9 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
 {
     typedef typename S2Raw<PACK>::T raw_t;
 #ifndef RC_S2_STEPS
-#define RC_S2_STEPS 126  // for per-step measurements (tools/build_variants.sh).  What rides on the folded table: 2 bias per flush, 4 atomic addresses behind the branch, 8 no selects in units of whole lanes.
+#define RC_S2_STEPS 254  // for per-step measurements (tools/build_variants.sh).  What rides on the folded table: 2 bias per flush, 4 atomic addresses behind the branch, 8 no selects in units of whole lanes.
                          // Direction 2 of every instantiation: 16 two-cluster units split by class without per-lane branches, 32 the donor's hand-over as a single-lane operation, 64 totals kept as 32-bit halves
+                         // The folded kernel's row stream: 128 L2 warm-up touches 2 NP rows ahead of the requests
 #endif
     constexpr bool LATE = FOLD && (RC_S2_STEPS & 2), BR3 = FOLD && (RC_S2_STEPS & 4), BR4 = FOLD && (RC_S2_STEPS & 8);
     constexpr bool STEPA = (RC_S2_STEPS & 16) != 0, STEPB = (RC_S2_STEPS & 32) != 0, STEPC = (RC_S2_STEPS & 64) != 0;
@@ -1855,10 +1857,41 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
     const size_t pitchD = PACK ? ld / 2 * 3 : ld;                          // row pitch in elements of the streamed type's base pointer
     RC_GLOBAL_AS const unsigned *np48 = nullptr;
     RC_GLOBAL_AS const long long *npD = nullptr, *npL = nullptr;
-    auto set_next = [&](int row, int cb0) {
+    // L2 warm-up (RC_S2_STEPS 128, the folded kernel — the others have no register for it — in launches with View.s2_touch, i.e.
+    // beside the stationary pipeline's resolver, enqueue_bulk): behind every real request, one plain dword load into each
+    // 128-byte line of the row pair TW = 2 NP rows further down the same unit, the pair the next iteration requests.  One
+    // instruction: the lanes whose offset in the real loads starts a line (packed rows, 768 bytes: lanes 0, 11, 22, 32, 43, 54;
+    // unpacked, 1 KiB: every eighth lane) take the first row, the lanes to their right the second (+ the row pitch); every
+    // other lane is inactive.  Sweeps/s of the headline by distance, against the parent's 20.9-21.3 k: 4 -> 21.8 k, 6 -> 21.8 k,
+    // 8 -> 21.5 k, 12 -> 18.8 k, 16 -> 16.6 k (3 072 waves x (W + 2 NP) rows x 768 B: 19 MB at 4; 38 MB, more than the eight
+    // L2s hold, at 12; profiles/r10).
+    // The value lands in `tscr`, which nothing reads but the never-true store at the end of this function.  That store only
+    // steers the register allocation: it keeps `tscr` ONE register, rewritten only by the next touch (loads return in order: no
+    // wait between two of them).  A free register would be taken by the next VALU result, and the compiler would put a wait for
+    // the touch — with the in-order counter, for every row requested before it — in front of that instruction.  Nothing in the
+    // language guarantees this: another compiler may allocate differently, and tests/test_touch_isa.py reads the listing (one
+    // destination register for every touch, no scratch, 128 registers at most) so that it does not go unnoticed.
+    // Only rows of the unit being requested are touched (`trem`: its rows from the running pointer on, 0 in launches without
+    // touches): in bounds by construction; a unit's last TW rows touch nothing.
+    constexpr bool TOUCH = FOLD && (RC_S2_STEPS & 128) != 0;
+    constexpr int TW = 2 * NP;
+    constexpr u64 TLANES0 = PACK ? 0x0040080100400801ull : 0x0101010101010101ull;   // first row of the pair; the lanes to their right take the second
+    const bool t_second = (TLANES0 << 1 >> lane) & 1, t_lane = t_second || ((TLANES0 >> lane) & 1);
+    const unsigned pitch_b = (unsigned)(pitchD * (PACK ? 4 : 8)), lane_b = PACK ? 4u * lane3 : 8u * lane2;   // bytes
+    const bool touch_on = TOUCH && V.s2_touch != 0;                        // uniform
+    int trem = 0, tscr = 0;
+    auto touch = [&](int rows_on) {                                        // the row pair rows_on rows past the running pointer
+        if (t_lane) {
+            RC_GLOBAL_AS const char *const base = (RC_GLOBAL_AS const char *)(PACK ? (RC_GLOBAL_AS const void *)np48 : (RC_GLOBAL_AS const void *)npD) + (size_t)rows_on * pitch_b;
+            // (a relaxed atomic load of wave scope: a plain global_load_dword without cache bits that the compiler may neither drop nor merge, and counts)
+            tscr = __hip_atomic_load((RC_GLOBAL_AS const int *)(base + (lane_b + (t_second ? pitch_b : 0u))), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        }
+    };
+    auto set_next = [&](int row, int cb0, int rows) {
         const size_t e = (size_t)row * ld + (size_t)cb0;
         if (PACK) np48 = rc_uniform_ptr(D48 + e / 2 * 3); else npD = rc_uniform_ptr(Dq + e);
         if (!DERIVED) npL = rc_uniform_ptr(Lq + e);
+        trem = touch_on ? rows : 0;
     };
     auto issue_pair = [&](int sl) {
 #pragma unroll
@@ -1867,6 +1900,7 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
             else { d[sl][u] = __builtin_nontemporal_load((RC_GLOBAL_AS const typename std::conditional<PACK, rc_u3a4, ll2>::type *)(npD + lane2)); npD += pitchD; }
             if (!DERIVED) { l[sl][u] = __builtin_nontemporal_load((RC_GLOBAL_AS const ll2 *)(npL + lane2)); npL += ld; }
         }
+        if (TOUCH) { trem -= 2; if (trem >= TW) touch(TW - 2); }           // (behind the request: no real row queues behind a touch of its own iteration)
     };
     // (uniform by construction — the wave number is a scalar — but say so: unit bounds, row loops and row addresses stay in SGPRs)
     RC_CONST_AS const int *const ufast_w = (RC_CONST_AS const int *)(u64)V.ufast;   // scalar loads (a vector load here would make the wave wait for all its prefetched rows: one counter)
@@ -1879,7 +1913,7 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
     int cs0 = -1, cs1 = -1;
     if (unit < end_unit) {
         U = load_unit(unit);
-        set_next(U.y, U.x);
+        set_next(U.y, U.x, U.z - U.y);
 #pragma unroll
         for (int q = 0; q < NP; ++q) issue_pair(q);
         cs0 = slot[min(U.x + 2 * lane, V.n - 1)]; cs1 = slot[min(U.x + 2 * lane + 1, V.n - 1)];   // (a ragged last block: padding columns take the last point's slot and carry zeros)
@@ -2043,14 +2077,18 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {                             // the group's four row pairs
                     const int sl = q % NP, ar = a + 2 * q;
-                    RC_PF({ const long long w0 = __builtin_amdgcn_s_memtime(); if (NP == 4) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); pf_wait += __builtin_amdgcn_s_memtime() - w0; pf_tiles += 1; })
+                    RC_PF(long long pf_tk0;)
+                    RC_PF({ const long long w0 = __builtin_amdgcn_s_memtime(); if (NP == 4) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else if (TOUCH) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); pf_tk0 = __builtin_amdgcn_s_memtime(); pf_wait += pf_tk0 - w0; pf_tiles += 1; })
                     ll2 x[2], y[2];
 #pragma unroll
                     for (int u = 0; u < 2; ++u) { x[u] = S2Raw<PACK>::unpack(d[sl][u]); if (!DERIVED) y[u] = l[sl][u]; }
+                    // (pf_issue: from the hand-counted wait to both rows unpacked.  The compiler's own waits for these rows lie in between; they
+                    // are stricter — the requests are conditional, so it waits for the pair requested one iteration ago as well — and show here)
+                    RC_PF({ asm volatile("" : "+v"(x[0].x), "+v"(x[0].y), "+v"(x[1].x), "+v"(x[1].y) :: "memory"); pf_issue += __builtin_amdgcn_s_memtime() - pf_tk0; })
                     // the pair NP pairs ahead goes into the registers this one leaves: of this unit, or of the wave's next unit
                     if (ar + 2 * NP < a1) issue_pair(sl);
                     else if (have_next) {
-                        if (ar + 2 * NP == a1) set_next(Un.y, Un.x);     // the first rows of the wave's next unit
+                        if (ar + 2 * NP == a1) set_next(Un.y, Un.x, Un.z - Un.y);   // the first rows of the wave's next unit
                         issue_pair(sl);
                         if (q == 3) { ncs0 = slot[min(Un.x + 2 * lane, V.n - 1)]; ncs1 = slot[min(Un.x + 2 * lane + 1, V.n - 1)]; }
                     }
@@ -2301,6 +2339,7 @@ __device__ __forceinline__ void syml2_fast(const View &V, long long *pb /* [2][8
         unit = nunit; U = Un; cs0 = ncs0; cs1 = ncs1;
         RC_PF(pf_setup += __builtin_amdgcn_s_memtime() - pf_u0;)
     }
+    if (TOUCH && V.n < 0) SD[lane] = tscr;   // never true, and no part of the result: it only steers the register allocation (see `touch`)
     RC_PF(if (lane == 0 && pf_out) { pf_out[0] = __builtin_amdgcn_s_memtime() - pf_t0; pf_out[1] = pf_wait; pf_out[2] = pf_tiles; pf_out[3] = pf_setup;
                                      pf_out[4] = __builtin_amdgcn_s_memrealtime() - pf_r0; pf_out[5] = pf_log; pf_out[6] = pf_d2;
                                      pf_out[7] = (pf_r0 << 20) | (long long)((__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11)) & 0xF) << 16) |
@@ -4984,7 +5023,7 @@ __global__ void k_nop() {}
 // ===================================================================================================
 // One set of k_bulk_syml2's unit lists on the device (build_syml2_lists) and the grid that reads it: every resident wave has its
 // (possibly empty) share, so `blocks` is the number of resident 4-wave blocks the lists were dealt to; g: rows per fast unit.
-struct S2Lists { int4 *ufast = nullptr, *uslow = nullptr; int *wfast = nullptr, *wslow = nullptr; int nfast = 0, nslow = 0, blocks = 0, g = 0; };
+struct S2Lists { int4 *ufast = nullptr, *uslow = nullptr; int *wfast = nullptr, *wslow = nullptr; int nfast = 0, nslow = 0, blocks = 0, g = 0, maxw = 0 /* most fast units in one wave */; };
 
 struct rc_ctx {
     int dev = 0;
@@ -5753,7 +5792,8 @@ static int32_t build_syml2_lists(rc_ctx *c, int per_cu, S2Lists *out)
     const int slow_factor = rc_env_diag("RC_S2_SLOW_COST") ? std::max(1, atoi(rc_env_diag("RC_S2_SLOW_COST"))) : 3;
     const S2Plan p = s2_plan(c->n, cap_blocks, c->sw_coarse, slow_factor);
     S2Lists L;
-    L.nfast = (int)p.fast.size(); L.nslow = (int)p.slow.size(); L.g = p.g; L.blocks = cap_blocks;   // (every resident wave has its possibly empty share)
+    L.nfast = (int)p.fast.size(); L.nslow = (int)p.slow.size(); L.g = p.g; L.blocks = cap_blocks;
+    for (size_t w = 0; w + 1 < p.wfast.size(); ++w) L.maxw = std::max(L.maxw, p.wfast[w + 1] - p.wfast[w]);   // (every resident wave has its possibly empty share)
     const auto upload = [](void **dst, const void *src, size_t bytes) {
         hipError_t e = hipMalloc(dst, std::max<size_t>(16, bytes));
         if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
@@ -6380,6 +6420,12 @@ static int32_t enqueue_bulk(rc_ctx *c, const View &V, long long t)
         const S2Lists &L = c->s2[(c->hsum->n_changes > 32 && c->s2[1].ufast) ? 1 : 0];
         View V2 = V;
         view_lists(V2, L);
+        // L2 touches ahead of the row requests (syml2_fast) only beside the stationary pipeline's resolver — the 256-thread blocks
+        // sweep_enqueue chooses up to 32 label changes per sweep, three reduction blocks per CU.  What the touches buy is the
+        // resolver's time beside a reduction that parks in one wait per iteration (profiles/r10: reduction 54.8 -> 60.8 us,
+        // resolver 27.2 -> 20.8 us); while labels move the resolver's rounds are the critical path and the longer reduction only
+        // costs (moving regime: 4.60-4.65 k -> 4.50-4.55 k sweeps/s with touches in every launch).
+        V2.s2_touch = c->hsum->n_changes <= 32 ? 1 : 0;
         // (in this order the five are instantiated as they always were — innermost pair first — and the device listing keeps its labels)
         const auto kf = id == BK_SYML2_STORED ? k_bulk_syml2<false, false> : id == BK_SYML2_DERIVED ? k_bulk_syml2<true, false> : id == BK_SYML2_PACK ? k_bulk_syml2<true, true>
                       : id == BK_SYML2W_PACK ? k_bulk_syml2w<true, true> : k_bulk_syml2w<true, false>;
@@ -7868,13 +7914,41 @@ extern "C" int32_t rc_set_option(rc_ctx *c, const char *name, int64_t value)
     } else if (!strcmp(name, "fold_log_table")) {
         if (value != 0 && value != 1) return fail(c, RC_ERR_ARG, "rc_set_option: fold_log_table must be 0 or 1");
         c->opt_fold = (int)value;
+    } else if (!strcmp(name, "syml2_unit_rows")) {
+        // for tests: plans k_bulk_syml2's unit lists again with units of `value` rows (0: the plan's own choice), so that a small
+        // problem reaches what only n > 14 000 reaches otherwise — more fast units than resident waves (rc_bulk_plan_info)
+        if (value != 0 && (value < 8 || value > 128 || value % 8)) return fail(c, RC_ERR_ARG, "rc_set_option: syml2_unit_rows must be 0 (automatic) or a multiple of 8 in 8..128");
+        if (!c->s2[0].ufast) return fail(c, RC_ERR_STATE, "rc_set_option: syml2_unit_rows needs a context with 64-bit storage");
+        HIPCHK(c, hipSetDevice(c->dev));
+        const int32_t rcs = sync_and_check(c);
+        if (rcs != RC_OK) return rcs;
+        HIPCHK(c, hipDeviceSynchronize());   // (a prefetched reduction may still read the lists freed below)
+        const int before = c->sw_coarse;
+        c->sw_coarse = (int)value;
+        int32_t rcl = build_syml2_lists(c, c->symw_per_cu, &c->s2[0]);
+        if (rcl == RC_OK && c->s2[1].ufast) rcl = build_syml2_lists(c, c->s2[1].blocks / c->num_cus, &c->s2[1]);
+        if (rcl != RC_OK) { c->sw_coarse = before; return rcl; }
 #ifdef RC_DIAG
     } else if (!strcmp(name, "debug_flags")) {   // timing ablations (SweepArgs.dbg): results are wrong on purpose
         c->dbg = (int)value;
 #endif
     } else {
-        return fail(c, RC_ERR_ARG, "rc_set_option: unknown option '%s' (prune, lds_point_cache, chain_workers, chain_depth, chain_pipeline, fold_log_table)", name);
+        return fail(c, RC_ERR_ARG, "rc_set_option: unknown option '%s' (prune, lds_point_cache, chain_workers, chain_depth, chain_pipeline, fold_log_table, syml2_unit_rows)", name);
     }
+    return RC_OK;
+}
+
+// The plan of k_bulk_syml2's fast path that the stationary pipeline launches: resident waves, fast units, rows per unit, and the
+// most units one wave holds (a wave with more than one requests, and touches, across a unit boundary)
+extern "C" int32_t rc_bulk_plan_info(rc_ctx *c, int32_t *waves, int32_t *fast_units, int32_t *unit_rows, int32_t *max_units_per_wave)
+{
+    if (!c) return fail(c, RC_ERR_ARG, "rc_bulk_plan_info: NULL ctx");
+    if (!c->s2[0].ufast) return fail(c, RC_ERR_STATE, "rc_bulk_plan_info: the context has no k_bulk_syml2 plan (64-bit storage only)");
+    const S2Lists &L = c->s2[0];
+    if (waves) *waves = 4 * L.blocks;
+    if (fast_units) *fast_units = L.nfast;
+    if (unit_rows) *unit_rows = L.g;
+    if (max_units_per_wave) *max_units_per_wave = L.maxw;
     return RC_OK;
 }
 

@@ -2,7 +2,7 @@
 # diagnostic builds of the library into build_r4/ (git-ignored; travels to the GPU box): bash tools/build_variants.sh [names...]
 # names: prof (per-phase stamps + batch_sim counters), chaos15 (block-dependent random delays in the resolver's rounds), simold
 # (the one-entry-at-a-time batch simulation of round 3 everywhere), profold (prof + simold), profcommit (column 2 = table rebuild inside the commit),
-# steps<N> (product flags with -DRC_S2_STEPS=N: one step of syml2_fast at a time, e.g. steps14 none of direction 2's, steps30 / steps46 / steps78 one each)
+# steps<N> (product flags with -DRC_S2_STEPS=N: one step of syml2_fast at a time, e.g. steps14 none of direction 2's, steps30 / steps46 / steps78 one each, steps126 no L2 touches)
 cd "$(dirname "$0")/../redclust.jl_amd/csrc" || exit 1
 B=../../build_r4; mkdir -p $B
 CC="hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared"

@@ -31,4 +31,9 @@ for gen in (0, 1):
           f" | cycles/tile {np.median(tot/np.maximum(tiles,1)):.0f}  wait/tile {np.median(wait/np.maximum(tiles,1)):.0f}"
           f" | clock {np.median(tot/np.maximum(real,1))*100:.0f} MHz  wave lifetime {np.median(real)/100:.1f} us  start spread {(r0.max()-r0.min())/100:.1f} us"
           f" | log share {lg.sum()/tot.sum():.2f}  dir2 share {d2.sum()/tot.sum():.2f}  issue {iss.sum()/tot.sum():.2f}  ldswrite {ldsw.sum()/tot.sum():.2f}  dir1 {d1.sum()/tot.sum():.2f}")
+    # per-wave medians, in s_memtime ticks (the wave's timeline: what a change to the set-up or to the row waits can move at most)
+    print(f"gen {gen}: per-wave medians  total {np.median(tot):.0f}  pf_setup {np.median(setup):.0f}  pf_wait {np.median(wait):.0f}  pf_log {np.median(lg):.0f}"
+          f"  pf_ldsw {np.median(ldsw):.0f}  pf_d2 {np.median(d2):.0f}  pf_d1 {np.median(d1):.0f}  pf_take (hand-counted wait to both rows unpacked: the compiler's waits) {np.median(iss):.0f}  row pairs {np.median(tiles):.0f}"
+          f"  | waves with exactly 44 row pairs: {(tiles == 44).sum()}, their medians  total {np.median(tot[tiles == 44]) if (tiles == 44).any() else 0:.0f}"
+          f"  pf_wait {np.median(wait[tiles == 44]) if (tiles == 44).any() else 0:.0f}  pf_setup {np.median(setup[tiles == 44]) if (tiles == 44).any() else 0:.0f}")
 print("(s_memtime ticks: 100 MHz constant clock on gfx9? — compare shares, not absolutes)")

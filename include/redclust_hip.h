@@ -512,6 +512,43 @@ int32_t rc_psm_search_samples(int32_t device, const int64_t *samples /* m×n, la
                               int32_t *best, double *kernel_ms, double *counts_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * PEAR search: the same greedy search over ALL partitions for the clustering of maximum posterior expected adjusted Rand
+ * index in Fritsch & Ickstadt's form (mcclust's pear / maxpear, SALSO's omARI.approx) under the counts — the adjusted Rand
+ * index with the sample's pair indicators replaced by their posterior means C_ij/m.  DESIGN.md §8 "PEAR search".
+ *
+ * With T = n(n−1)/2, P = Σ_{i<j} C_ij and, for a labelling c (0 = unallocated counts as a singleton),
+ * X = Σ_{i<j, c_i=c_j≠0} C_ij and A = Σ_k n_k(n_k−1)/2:
+ *   PEAR(c) = num/den,  num = 2·(T·X − A·P),  den = T·(m·A + P) − 2·A·P >= 0;  0 (num = 0, den = 1) where den = 0.
+ * A run, its arguments, the tie rules (own slot, then the lowest slot; the new cluster with the priority of the slot it
+ * would take), maxK, maxsweeps, the moved rule and labels_out are rc_psm_search's; the point goes to the MAXIMUM of the
+ * fraction of (X₀ + S_ik, A₀ + n_k) over the clusters k and (X₀, A₀) for a new one, X₀, A₀ the state without the point.
+ * Fractions are compared exactly, a/b > c/d ⇔ a·d > c·b in signed 128 bits, so every accepted move raises PEAR strictly
+ * and a run is a pure integer function of its arguments.  num and den of a run are recomputed from the matrix at its end.
+ * best: the first run of maximal fraction (0-based), by the exact comparison.
+ * Capacity (RC_ERR_CAPACITY beyond, before any device work): n <= 8192, m·n < 2^31 and m·T² < 2^62 (m <= 4097 at n = 8192),
+ * which keeps |num| and den below 2^63.  RC_ERR_ARG as rc_psm_search, in its order (there is no loss specifier).
+ * The _samples and _ctx forms are to this entry what rc_psm_search_samples and rc_psm_search_ctx are to rc_psm_search: equal
+ * to it on rc_samples_counts' / rc_cocluster_counts' matrix bit for bit; the context's state, layout and counts stay untouched.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct rc_pear_run_t {
+    double pear; /* num / den */
+    int64_t num, den;
+    int32_t sweeps, converged;
+    int64_t moves;
+    int32_t K;
+} rc_pear_run_t;
+int32_t rc_pear_search(int32_t device, const void *counts /* uint32_t n×n */, int64_t m, int64_t n, int32_t nruns,
+                       const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */, int32_t maxK,
+                       int32_t maxsweeps, int64_t *labels_out /* nruns×n */, void *runs_out /* rc_pear_run_t[nruns] */, int32_t *best,
+                       double *kernel_ms);
+int32_t rc_pear_search_ctx(rc_ctx *ctx, int64_t numsamples, int32_t nruns, const int64_t *init, const int32_t *order, int32_t maxK,
+                           int32_t maxsweeps, int64_t *labels_out, rc_pear_run_t *runs_out, int32_t *best, double *kernel_ms);
+int32_t rc_pear_search_samples(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n, int32_t nruns,
+                               const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */,
+                               int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */, void *runs_out /* rc_pear_run_t[nruns] */,
+                               int32_t *best, double *kernel_ms, double *counts_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Exact expected-VI search: the same greedy search (one run = starting labels, a point order, maxsweeps; the same scoring
  * of every non-empty cluster and a new one, the same tie rules) for the posterior expected Variation of Information itself
  * — the mean over the m samples of VI(c, sample), SALSO's "VI" — instead of RC_PSM_VILB's lower bound.  It needs the

@@ -497,6 +497,123 @@ end
 
 export searchpointestimate, posteriorcounts
 
+# rc_pear_run_t
+struct RcPearRun
+    pear::Cdouble
+    num::Int64; den::Int64
+    sweeps::Int32; converged::Int32
+    moves::Int64
+    K::Int32; pad_::Int32
+end
+
+# (num, den) of PEAR as Int128: num = 2(T·X − A·P), den = T(m·A + P) − 2·A·P, T = n(n−1)/2; (0, 1) where den = 0
+function pearfraction(clust::AbstractVector{<:Integer}, counts::Matrix{UInt32}, numsamples::Integer)
+    n = length(clust)
+    size(counts) == (n, n) || throw(ArgumentError("counts must be an n×n matrix matching clust"))
+    X = Int128(0); P = Int128(0)
+    for j in 2:n, i in 1:j-1
+        P += counts[i, j]
+        clust[i] == clust[j] && (X += counts[i, j])
+    end
+    sizes = Dict{Int,Int}()
+    for l in clust
+        sizes[l] = get(sizes, l, 0) + 1
+    end
+    A = Int128(sum(s * (s - 1) ÷ 2 for s in values(sizes)))
+    T = Int128(n) * (n - 1) ÷ 2
+    den = T * (Int128(numsamples) * A + P) - 2 * A * P
+    return den == 0 ? (Int128(0), Int128(1)) : (2 * (T * X - A * P), den)
+end
+
+"""
+    expectedpear(clust, counts, numsamples) -> Float64
+
+The posterior expected adjusted Rand index of `clust` in Fritsch & Ickstadt's form (mcclust's `pear`) from the n × n
+co-clustering counts (`posteriorcounts`), evaluated as one exact ratio of two integers on the host; 0 where the denominator is 0.
+What `searchmaxpear` maximises.
+"""
+function expectedpear(clust::AbstractVector{<:Integer}, counts::Matrix{UInt32}, numsamples::Integer)
+    num, den = pearfraction(clust, counts, numsamples)
+    return Float64(num) / Float64(den)
+end
+
+pearinfo(runs, labels, best) =
+    (pear = [x.pear for x in runs], num = [x.num for x in runs], den = [x.den for x in runs], sweeps = [Int(x.sweeps) for x in runs],
+     converged = [x.converged != 0 for x in runs], moves = [Int(x.moves) for x in runs], K = [Int(x.K) for x in runs],
+     labels = labels, best = Int(best[1]) + 1)
+
+# nruns Mersenne-Twister orders from empty labels, then one run per column of starts in the identity order
+function pearruns(n, nruns, seed, starts)
+    R = Int(nruns) + length(starts)
+    R >= 1 || throw(ArgumentError("no run: nruns = 0 and no init"))
+    inits = zeros(Int64, n, R)                                    # column r = run r: row-major R×n for the library
+    order = Matrix{Int32}(undef, n, R)
+    rng = Random.MersenneTwister(seed)
+    for r in 1:nruns
+        order[:, r] .= Random.randperm(rng, n)
+    end
+    for (k, s) in enumerate(starts)
+        inits[:, nruns + k] .= s
+        order[:, nruns + k] .= 1:n
+    end
+    return R, inits, order
+end
+
+"""
+    searchmaxpear(HIPBackend(), result; nruns = 16, maxK = 0, maxsweeps = 100, seed = 0) -> (clust, info)
+    searchmaxpear(HIPBackend(), counts, numsamples; nruns = 16, maxK = 0, maxsweeps = 100, seed = 0, init = nothing)
+
+A greedy search over all partitions for the clustering of maximum posterior expected adjusted Rand index (`expectedpear`;
+mcclust's `maxpear`, SALSO's `omARI.approx`) under the co-clustering counts (rc_pear_search_samples / rc_pear_search): every
+comparison is an exact cross-multiplication of integers, so a run is a pure function of its inputs.  Runs: `nruns` from empty
+labels in random point orders; with a `result`, one more from the sample of highest PEAR (mcclust's `method = "draws"`), so the
+answer is never below the best sample; with counts, one per column of `init`.  `info`: named tuple of the per-run `pear`,
+`num`, `den`, `sweeps`, `converged`, `moves`, `K`, all `labels` (n × runs) and `best` (the first run of maximal num/den).
+"""
+function searchmaxpear(b::HIPBackend, result; nruns::Integer = 16, maxK::Integer = 0, maxsweeps::Integer = 100, seed::Integer = 0)
+    samples = samplematrix(result)                                # the counts are built from these on the device and stay there
+    n, m = size(samples)
+    counts = posteriorcounts(b, result)
+    draw = 1
+    bnum, bden = pearfraction(result.clusts[1], counts, m)
+    for s in 2:m
+        num, den = pearfraction(result.clusts[s], counts, m)
+        if num * bden > bnum * den
+            draw, bnum, bden = s, num, den
+        end
+    end
+    R, inits, order = pearruns(n, nruns, seed, [result.clusts[draw]])
+    cap = maxK == 0 ? 0 : max(Int(maxK), length(unique(result.clusts[draw])))
+    labels = Matrix{Int64}(undef, n, R)
+    runs = Vector{RcPearRun}(undef, R)
+    best = Int32[0]
+    rc = ccall((:rc_pear_search_samples, LIB), Int32,
+               (Int32, Ptr{Int64}, Int64, Int64, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
+                Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}),
+               b.device, samples, m, n, R, inits, order, cap, maxsweeps, labels, runs, best, C_NULL, C_NULL)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return (labels[:, best[1] + 1], pearinfo(runs, labels, best))
+end
+
+function searchmaxpear(b::HIPBackend, counts::Matrix{UInt32}, numsamples::Integer; nruns::Integer = 16, maxK::Integer = 0,
+                       maxsweeps::Integer = 100, seed::Integer = 0, init::Union{Matrix{Int64},Nothing} = nothing)
+    n = size(counts, 1)
+    size(counts, 2) == n || throw(ArgumentError("counts must be a square matrix"))
+    starts = init === nothing ? Vector{Int64}[] : [init[:, k] for k in 1:size(init, 2)]
+    R, inits, order = pearruns(n, nruns, seed, starts)
+    labels = Matrix{Int64}(undef, n, R)
+    runs = Vector{RcPearRun}(undef, R)
+    best = Int32[0]
+    rc = ccall((:rc_pear_search, LIB), Int32,
+               (Int32, Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
+                Ptr{Int32}, Ptr{Cdouble}),
+               b.device, counts, numsamples, n, R, inits, order, maxK, maxsweeps, labels, runs, best, C_NULL)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return (labels[:, best[1] + 1], pearinfo(runs, labels, best))
+end
+
+export searchmaxpear, expectedpear
+
 # rc_hclust_merge_t
 struct RcHclustMerge
     a::Int32; b::Int32

@@ -15,7 +15,8 @@ from .pointestimate import (getpointestimate, lossmatrix, binderloss, infodist, 
                             summarise, searchpointestimate, expectedloss, expectedvi, expectedid, cocluster_counts,
                             posterior_counts, posterior_coclustering, hclust, hclustpointestimate, expectedlosses,
                             linkage_matrix, leaf_order, partitiondistances, expecteddistances, credibleball,
-                            credibleball_from_distances, relabel, Relabelling)
+                            credibleball_from_distances, relabel, Relabelling, expectedpear, pearfraction, expectedpears,
+                            searchmaxpear, maxpear, expectedari)
 from .predict import predict, predict_points, Prediction, predict_joint, JointPrediction  # noqa: F401
 from .score import scorelabellings, loglik_from_blocks, mapestimate, searchmapestimate, reweight  # noqa: F401
 from .profiles import clusterprofiles, ClusterProfiles, silhouettes_from_sums, exemplars  # noqa: F401

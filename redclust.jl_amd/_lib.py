@@ -86,6 +86,11 @@ class RcPsmRun(C.Structure):
                 ("moves", C.c_int64), ("K", C.c_int32)]
 
 
+class RcPearRun(C.Structure):
+    _fields_ = [("pear", C.c_double), ("num", C.c_int64), ("den", C.c_int64), ("sweeps", C.c_int32), ("converged", C.c_int32),
+                ("moves", C.c_int64), ("K", C.c_int32)]
+
+
 class RcMapRun(C.Structure):
     _fields_ = [("loglik", C.c_double), ("logprior", C.c_double), ("logposterior", C.c_double), ("start_logposterior", C.c_double),
                 ("sweeps", C.c_int32), ("converged", C.c_int32), ("K", C.c_int32), ("capped", C.c_int32), ("moves", C.c_int64)]
@@ -201,6 +206,13 @@ SIGNATURES = {
                                   C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rc_psm_search_ctx": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_pear_search": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                   C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_pear_search_ctx": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_pear_search_samples": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                           C.POINTER(C.c_double)]),
     "rc_vi_gtable": (C.c_int32, [C.c_int64, C.c_void_p]),
     "rc_vi_search": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
@@ -817,9 +829,10 @@ def _label_matrix(x, what="samples"):
 
 
 def _psm_result(labels, runs, nruns, n, best, ms, **extra) -> dict:
-    """The dict of the searches: labels (nruns×n), one array per field of RcPsmRun, best, kernel_ms and what extra names."""
+    """The dict of the searches: labels (nruns×n), one array per field of the runs' record (RcPsmRun, or RcPearRun), best,
+    kernel_ms and what extra names."""
     out = dict(labels=labels[:nruns, :n], best=int(best.value), kernel_ms=float(ms.value), **extra)
-    for k, ty in RcPsmRun._fields_:
+    for k, ty in type(runs)._type_._fields_:
         out[k] = np.array([getattr(r, k) for r in runs[:nruns]], dtype=np.float64 if ty is C.c_double else np.int64)
     out["converged"] = out["converged"].astype(bool)
     return out
@@ -838,8 +851,8 @@ def loss_matrix(samples, loss: int, device: int = 0, want_matrix: bool = True):
     return M, cs, int(am.value), float(ms.value)
 
 
-def _search_runs(init, order, maxK, maxsweeps, call, n=None) -> dict:
-    """What the four searches share: init (nruns×n labels, 0 = unallocated) and order (nruns×n 1-based permutations) coerced and
+def _search_runs(init, order, maxK, maxsweeps, call, n=None, record=RcPsmRun) -> dict:
+    """What the searches share (record: the type of a run's record): init (nruns×n labels, 0 = unallocated) and order (nruns×n 1-based permutations) coerced and
     checked — n given: the samples' length, which init must have — the output buffers, and the dict of the results.
     call(n, *tail) makes the library call and checks its return code; tail is what every search entry point ends with: nruns,
     init, order, maxK, maxsweeps, labels_out, runs_out, best, kernel_ms.  What it returns (a dict or None) is added to the result."""
@@ -849,7 +862,7 @@ def _search_runs(init, order, maxK, maxsweeps, call, n=None) -> dict:
         raise ValueError("init and order must be nruns×n arrays of the same shape" + (", n the samples' length" if n is not None else ""))
     nruns, n = init.shape
     labels = np.zeros((max(nruns, 1), max(n, 1)), np.int64)
-    runs = (RcPsmRun * max(nruns, 1))()
+    runs = (record * max(nruns, 1))()
     best, ms = C.c_int32(-1), C.c_double()
     extra = call(n, nruns, init.ctypes.data, order.ctypes.data, int(maxK), int(maxsweeps), labels.ctypes.data, runs, C.byref(best),
                  C.byref(ms))
@@ -878,14 +891,16 @@ def _counts_form(family, counts, numsamples, ctx, samples, device, n=None, what=
 
 
 def _psm_search(counts, numsamples, ctx, samples, loss, init, order, maxK, maxsweeps, device) -> dict:
-    """psm_search and psm_search_samples (samples: the label matrix) behind their parameter lists"""
+    """psm_search and psm_search_samples (samples: the label matrix) behind their parameter lists; loss None: the PEAR
+    search's three entry points, which have the same lists without the loss"""
     cms = C.c_double()
+    family, crit, record = ("pear_search", [], RcPearRun) if loss is None else ("psm_search", [int(loss)], RcPsmRun)
 
     def call(n, *tail):
-        fn, head, handle, _, timed = _counts_form("psm_search", counts, numsamples, ctx, samples, device, n, "init")
-        _check(fn(*head, int(loss), *tail, *([C.byref(cms)] if timed else [])), handle)
+        fn, head, handle, _, timed = _counts_form(family, counts, numsamples, ctx, samples, device, n, "init")
+        _check(fn(*head, *crit, *tail, *([C.byref(cms)] if timed else [])), handle)
         return dict(counts_ms=float(cms.value)) if timed else None
-    return _search_runs(init, order, maxK, maxsweeps, call, n=None if samples is None else samples.shape[1])
+    return _search_runs(init, order, maxK, maxsweeps, call, n=None if samples is None else samples.shape[1], record=record)
 
 
 def psm_search(counts, numsamples: int, loss: int, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0, ctx=None):
@@ -911,6 +926,19 @@ def psm_search_samples(samples, loss: int, init, order, maxK: int = 0, maxsweeps
     """rc_psm_search_samples: psm_search on the counts of an m×n int64 label matrix (labels 1..n), which are built on the
     device and stay there.  Returns psm_search's dict and counts_ms, the device time of the counts kernel."""
     return _psm_search(None, None, None, _label_matrix(samples), loss, init, order, maxK, maxsweeps, device)
+
+
+def pear_search(counts, numsamples: int, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0, ctx=None):
+    """rc_pear_search (counts: n×n uint32) or, with ctx, rc_pear_search_ctx on that context's device counts.  Arguments as
+    psm_search without the loss.  Returns a dict: labels (nruns×n, sortlabels'd), the per-run arrays pear, num, den, sweeps,
+    converged, moves, K, and best (the first run of maximal num/den), kernel_ms."""
+    return _psm_search(counts, numsamples, ctx, None, None, init, order, maxK, maxsweeps, device)
+
+
+def pear_search_samples(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
+    """rc_pear_search_samples: pear_search on the counts of an m×n int64 label matrix (labels 1..n), which are built on the
+    device and stay there.  Returns pear_search's dict and counts_ms."""
+    return _psm_search(None, None, None, _label_matrix(samples), None, init, order, maxK, maxsweeps, device)
 
 
 def vi_gtable(n: int) -> np.ndarray:

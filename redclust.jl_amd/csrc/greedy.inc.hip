@@ -1,4 +1,4 @@
-// The greedy search over all partitions that the three criteria share — Binder / the VI bound on the co-clustering counts
+// The greedy search over all partitions that the criteria share — Binder / the VI bound / PEAR on the co-clustering counts
 // (pointsearch.inc.hip, k_search) and the exact expected VI / ID on the samples' contingency tables (visearch.inc.hip,
 // k_visearch): what is the same whatever the score.  DESIGN.md §8 "Point-estimate search", "One run".
 // Included at the end of redclust_hip.hip in front of pointsearch.inc.hip (same translation unit: shares fail(), HIPCHK and
@@ -98,9 +98,68 @@ __device__ inline unsigned offer_new(Cand &best, unsigned long long key_new, uns
     return 1u;
 }
 
+// ---- a criterion that is a fraction and is maximised (k_search's PEAR, DESIGN.md §8 "PEAR search"): the same ties and the same
+// reduction, on (num, den) pairs compared exactly by cross-multiplication in 128 bits
+
+// den > 0 for a candidate (a fraction whose den is 0 is stored as 0/1); den = 0 marks "no candidate yet", which loses to any
+struct FCand { long long num, den; unsigned pr, slot, S; };
+constexpr FCand FCAND_NONE{0, 0, ~0u, 0u, 0u};
+
+__device__ inline FCand fraction(long long num, long long den, unsigned pr, unsigned slot, unsigned S)
+{
+    return den ? FCand{num, den, pr, slot, S} : FCand{0, 1, pr, slot, S};
+}
+
+// x before b: the larger fraction, then the lower priority (|num|, den < 2^63, so the products fit)
+__device__ inline bool fbetter(const FCand &x, const FCand &b)
+{
+    if (!x.den) return false;
+    if (!b.den) return true;
+    const __int128 l = (__int128)x.num * b.den, r = (__int128)b.num * x.den;
+    return l > r || (l == r && x.pr < b.pr);
+}
+
+__device__ inline long long shfl_xor_i64(long long v, int off) { return (long long)shfl_xor_u64((unsigned long long)v, off); }
+
+struct FPartials { long long *num, *den; unsigned *pr, *slot, *free, *S; };
+
+// group_argmin's shape for fractions: the argmax of the threads' candidates and the lowest free slot, in every thread
+__device__ inline void group_argmax(FCand &best, unsigned &minfree, const FPartials &P, int lane, int wave)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const FCand o{shfl_xor_i64(best.num, off), shfl_xor_i64(best.den, off), (unsigned)__shfl_xor((int)best.pr, off),
+                      (unsigned)__shfl_xor((int)best.slot, off), (unsigned)__shfl_xor((int)best.S, off)};
+        if (fbetter(o, best)) best = o;
+        minfree = min(minfree, (unsigned)__shfl_xor((int)minfree, off));
+    }
+    if (lane == 0) {
+        P.num[wave] = best.num; P.den[wave] = best.den; P.pr[wave] = best.pr; P.slot[wave] = best.slot; P.S[wave] = best.S;
+        P.free[wave] = minfree;
+    }
+    __syncthreads();
+    best = FCand{P.num[0], P.den[0], P.pr[0], P.slot[0], P.S[0]};
+    minfree = P.free[0];
+#pragma unroll
+    for (int w = 1; w < NWAVE; ++w) {
+        const FCand o{P.num[w], P.den[w], P.pr[w], P.slot[w], P.S[w]};
+        if (fbetter(o, best)) best = o;
+        minfree = min(minfree, P.free[w]);
+    }
+}
+
+// offer_new for fractions: the new cluster's fraction num/den against the group's best
+__device__ inline unsigned offer_new(FCand &best, long long num, long long den, unsigned emptied, unsigned a, unsigned minfree)
+{
+    const FCand c = fraction(num, den, emptied ? 0u : minfree, emptied ? a : minfree, 0u);
+    if (!fbetter(c, best)) return 0u;
+    best = c;
+    return 1u;
+}
+
 // ---- host side
 
-// What the five entry points check first and alike (rc_psm_search, _ctx, _samples, rc_vi_search, rc_id_search); each goes on
+// What the entry points check first and alike (rc_psm_search, _ctx, _samples, rc_vi_search, rc_id_search, rc_pear_search*); each goes on
 // with its own checks in its own order (the loss specifier, the capacities, the samples)
 static int32_t check_args(rc_ctx *c, const char *who, int64_t m, int64_t n, int32_t nruns, const int64_t *init, const int32_t *order,
                           int32_t maxK, int32_t maxsweeps, const int64_t *labels_out, const void *runs_out, const int32_t *best)
@@ -177,11 +236,12 @@ struct Staging {
     }
 };
 
-// The results of the runs: sortlabels (utils.jl:69-74) of the final slots into labels_out, the runs' records, and in *best
-// the first run of minimal key.  loss(o, R, cnt, K) sets R.loss and R.loss_num from the kernel's record o — cnt[1..K] are the
-// sizes of the sorted clusters — and returns the key the runs are compared by.
-template <typename RunOut, typename Loss>
-static void results(const Staging &S, const std::vector<RunOut> &out, int64_t *labels_out, rc_psm_run_t *runs_out, int32_t *best, Loss loss)
+// The results of the runs: sortlabels (utils.jl:69-74) of the final slots into labels_out, the runs' records (rc_psm_run_t, or
+// rc_pear_run_t for the PEAR search), and in *best the first run of minimal key.  loss(o, R, cnt, K) sets R's criterion fields
+// from the kernel's record o — cnt[1..K] are the sizes of the sorted clusters — and returns the key the runs are compared by
+// with <: a number that is minimised, or a type whose < says "better".
+template <typename RunOut, typename Run, typename Loss>
+static void results(const Staging &S, const std::vector<RunOut> &out, int64_t *labels_out, Run *runs_out, int32_t *best, Loss loss)
 {
     const int64_t n = S.n;
     std::vector<int> map((size_t)n + 1), cnt((size_t)n + 1);
@@ -198,7 +258,7 @@ static void results(const Staging &S, const std::vector<RunOut> &out, int64_t *l
             cnt[(size_t)map[l]]++;
         }
         const RunOut &o = out[(size_t)r];
-        rc_psm_run_t &R = runs_out[r];
+        Run &R = runs_out[r];
         R.sweeps = o.sweeps; R.converged = o.converged; R.moves = o.moves; R.K = o.K;
         const auto key = loss(o, R, cnt.data(), next);
         if (r == 0 || key < least) { b = r; least = key; }

@@ -29,6 +29,13 @@
 // 1..hi is covered in passes of W slots (VI, n > 8104, and only while a slot above W is or has been in use).
 //
 // Ties: greedy.inc.hip.
+//
+// PEAR (DESIGN.md §8 "PEAR search"; rc_pear_search*) is a third, internal instantiation of the same kernel: the criterion is
+// the fraction num/den of include/redclust_hip.h, maximised.  Phase A is Binder's; besides S it sums row i over the point's own
+// cluster (S_ia, one LDS word per step parity), which turns the run's X into X₀.  Phase B scores slot k as the pair (num_k, den_k)
+// of (X₀ + S_ik, A₀ + n_k); the argmax is greedy::group_argmax.  X, A (of the current labelling) and P sit in front of S in LDS:
+// X and A are written in phase C by the thread that writes sz and read behind the next step's first barrier; P = Σ_{i<j} C_ij
+// and the X of the start come from one pass over the matrix before the first step, the reported X and P from one after the last.
 
 #include <algorithm>
 #include <cmath>
@@ -39,9 +46,11 @@ namespace psm {
 using greedy::TPB, greedy::NWAVE, greedy::Cand, greedy::better, greedy::key_i64, greedy::key_f64, greedy::shfl_xor_u64;
 constexpr double QUANT = 1099511627776.0;            // 2^40
 constexpr size_t LDS_BUDGET = 160 * 1024 - 1024;     // dynamic part; the static reduction scratch is below 1 KiB
+constexpr int LOSS_PEAR = 2;                         // k_search's third criterion; not a loss specifier of rc_psm_search
+constexpr size_t PEAR_HEAD = 4;                      // u64 words in front of S: X, A, P and the two S_ia accumulators
 
 struct RunOut {
-    long long tot, same, moves;   // Binder: Σ_{i<j} C_ij and Σ_{i<j, same cluster} C_ij of the final labelling
+    long long tot, same, moves;   // Binder, PEAR: Σ_{i<j} C_ij and Σ_{i<j, same cluster} C_ij of the final labelling
     double f;                     // VI: f(c)
     int sweeps, converged, K, pad_;
 };
@@ -69,15 +78,42 @@ __device__ inline void load_row(const unsigned *__restrict__ row, int n, int tid
     }
 }
 
+// This wave's share of Σ_{i<j} C_ij (tot) and Σ_{i<j, same cluster} C_ij (same) over the upper triangle: one wave per row,
+// 16-byte loads (ld is a multiple of 4).  ZEROS: lab may hold 0 (unallocated: a cluster of its own)
+template <bool ZEROS>
+__device__ inline void upper_sums(const unsigned *__restrict__ C, size_t ld, int n, const unsigned short *lab, int lane, int wave,
+                                  unsigned long long &tot, unsigned long long &same)
+{
+    for (int r = wave; r < n; r += NWAVE) {
+        const unsigned lr = lab[r];
+        const uint4 *row = reinterpret_cast<const uint4 *>(C + (size_t)r * ld);
+        for (int j = (((r + 1) >> 8) << 8) + 4 * lane; j < n; j += 256) {
+            const uint4 v = row[j >> 2];
+            const unsigned x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int jj = j + e;
+                if (jj > r && jj < n) {
+                    tot += x[e];
+                    if (lab[jj] == lr && (!ZEROS || lr)) same += x[e];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { tot += shfl_xor_u64(tot, off); same += shfl_xor_u64(same, off); }
+}
+
 template <int LOSS, int Q>
 __global__ __launch_bounds__(TPB) void k_search(Args A)
 {
-    constexpr bool VI = LOSS == RC_PSM_VILB;
+    constexpr bool VI = LOSS == RC_PSM_VILB, PEAR = LOSS == LOSS_PEAR;
     extern __shared__ unsigned long long psm_lds[];
     __shared__ unsigned long long r_sc[NWAVE];
     __shared__ unsigned r_pr[NWAVE], r_slot[NWAVE], r_S[NWAVE], r_free[NWAVE];
     __shared__ double r_f[NWAVE];
     __shared__ unsigned long long r_a[NWAVE], r_b[NWAVE];
+    __shared__ long long r_num[NWAVE], r_den[NWAVE];                     // PEAR's partials (not allocated where unused)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = A.n, W = A.W, run = blockIdx.x;
@@ -87,7 +123,9 @@ __global__ __launch_bounds__(TPB) void k_search(Args A)
 
     // carve the dynamic LDS: 8-byte items first
     unsigned long long *L = psm_lds;
-    unsigned *S = reinterpret_cast<unsigned *>(L + (VI ? W : 0));
+    long long *XA = reinterpret_cast<long long *>(psm_lds);              // PEAR: X, A, P
+    unsigned *Sa = reinterpret_cast<unsigned *>(psm_lds + 3);            // PEAR: S_ia of the even and the odd steps
+    unsigned *S = reinterpret_cast<unsigned *>(L + (VI ? (size_t)W : PEAR ? PEAR_HEAD : 0));
     unsigned *T = S + W;
     unsigned short *sz = reinterpret_cast<unsigned short *>(T + (VI ? n : 0));
     unsigned short *lab = sz + (n + 2);
@@ -111,9 +149,31 @@ __global__ __launch_bounds__(TPB) void k_search(Args A)
         __syncthreads();
     }
 
+    long long Pall = 0;
+    const long long Tall = (long long)n * (n - 1) / 2;
+    if (PEAR) {
+        // P, and X and A of the starting labels
+        unsigned long long tot = 0, same = 0, within = 0;
+        upper_sums<true>(C, ld, n, lab, lane, wave, tot, same);
+        for (int k = 1 + tid; k <= n; k += TPB) within += (unsigned long long)sz[k] * (sz[k] - 1u) / 2u;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) within += shfl_xor_u64(within, off);
+        if (lane == 0) { r_a[wave] = tot; r_b[wave] = same; r_sc[wave] = within; }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned long long ta = 0, tb = 0, tc = 0;
+            for (int w = 0; w < NWAVE; ++w) { ta += r_a[w]; tb += r_b[w]; tc += r_sc[w]; }
+            XA[0] = (long long)tb; XA[1] = (long long)tc; XA[2] = (long long)ta;
+            Sa[0] = Sa[1] = 0;
+        }
+        __syncthreads();
+        Pall = XA[2];
+    }
+
     const greedy::Partials red{r_sc, r_pr, r_slot, r_free, r_S};
     greedy::Visit v(A.order + (size_t)run * n, n);
     int K = A.K0[run], hi = A.hi0[run];
+    int par = 0;                                                         // PEAR: which S_ia accumulator this step adds to
     unsigned cur[Q], nxt[Q];
     load_row<Q>(C + (size_t)v.i * ld, n, tid, cur);
     long long moves = 0;
@@ -131,11 +191,14 @@ __global__ __launch_bounds__(TPB) void k_search(Args A)
             const unsigned a = v.slot_of(lab);
             const int scan_hi = min(hi + 1, n);                          // slots above hi are free; hi + 1 is the lowest of them
             Cand best{~0ull, ~0u, 0u, 0u};
+            greedy::FCand fbest = greedy::FCAND_NONE;
+            long long X0 = 0, A0 = 0;                                    // PEAR: X and A with i out
             unsigned minfree = ~0u;
             unsigned emptied = 0;
             for (int base = 0, pass = 0; base < scan_hi; base += W, ++pass) {
                 // phase A: row i into the per-slot accumulators of this window; the first pass also takes i out of T
                 if (pass) __syncthreads();
+                unsigned sa = 0;
 #pragma unroll
                 for (int q = 0; q < Q; ++q) {
                     const int j = tid + q * TPB;
@@ -143,6 +206,7 @@ __global__ __launch_bounds__(TPB) void k_search(Args A)
                     const unsigned l = lab[j];
                     if (!l) continue;
                     const unsigned c = cur[q];
+                    if (PEAR && l == a) sa += c;
                     unsigned Tj = 0;
                     if (VI) {
                         Tj = T[j];
@@ -154,9 +218,14 @@ __global__ __launch_bounds__(TPB) void k_search(Args A)
                         if (VI) atomicAdd(&L[idx], __double2ull_rn(log1p((double)c / (double)Tj) * QUANT));
                     }
                 }
+                if (PEAR && pass == 0 && sa) atomicAdd(&Sa[par], sa);
                 __syncthreads();
                 // phase B: score the slots of this window (and clear their accumulators)
                 emptied = (a && sz[a] == 1) ? 1u : 0u;
+                if (PEAR && pass == 0) {
+                    X0 = XA[0] - (long long)Sa[par];
+                    A0 = XA[1] - (a ? (long long)sz[a] - 1 : 0ll);
+                }
                 const int kend = min(base + W, scan_hi);
                 for (int k = base + 1 + tid; k <= kend; k += TPB) {
                     const int nk = (int)sz[k] - ((unsigned)k == a ? 1 : 0);
@@ -164,6 +233,15 @@ __global__ __launch_bounds__(TPB) void k_search(Args A)
                     const int idx = k - 1 - base;
                     const unsigned s = S[idx];
                     S[idx] = 0;
+                    const unsigned pr = ((unsigned)k == a) ? 0u : (unsigned)k;
+                    if constexpr (PEAR) {
+                        // (num_k, den_k) of X = X₀ + S_ik, A = A₀ + n_k: below 2^63 in magnitude while m·T² < 2^62
+                        const long long Xk = X0 + (long long)s, Ak = A0 + nk;
+                        const greedy::FCand cand = greedy::fraction(2 * (Tall * Xk - Ak * Pall), Tall * ((long long)m * Ak + Pall) - 2 * Ak * Pall,
+                                                                    pr, (unsigned)k, s);
+                        if (greedy::fbetter(cand, fbest)) fbest = cand;
+                        continue;
+                    }
                     unsigned long long sc;
                     if (VI) {
                         const double ls = (double)L[idx] * (1.0 / QUANT);
@@ -174,15 +252,18 @@ __global__ __launch_bounds__(TPB) void k_search(Args A)
                     } else {
                         sc = key_i64((long long)m * nk - 2ll * (long long)s);
                     }
-                    const unsigned pr = ((unsigned)k == a) ? 0u : (unsigned)k;
                     if (better(sc, pr, best)) best = Cand{sc, pr, (unsigned)k, s};
                 }
             }
             // argmin across the group (the second barrier; only VI's phase C needs the winner's S), then the new-cluster candidate
-            greedy::group_argmin<VI>(best, minfree, red, lane, wave);
+            if constexpr (PEAR) greedy::group_argmax(fbest, minfree, greedy::FPartials{r_num, r_den, r_pr, r_slot, r_free, r_S}, lane, wave);
+            else greedy::group_argmin<VI>(best, minfree, red, lane, wave);
             const int Know = K - (int)emptied;
-            const unsigned isnew = (A.maxK == 0 || Know < A.maxK) ? greedy::offer_new(best, key_new, emptied, a, minfree) : 0u;
-            const unsigned w = best.slot;
+            unsigned isnew = 0;
+            if (A.maxK == 0 || Know < A.maxK)
+                isnew = PEAR ? greedy::offer_new(fbest, 2 * (Tall * X0 - A0 * Pall), Tall * ((long long)m * A0 + Pall) - 2 * A0 * Pall, emptied, a, minfree)
+                             : greedy::offer_new(best, key_new, emptied, a, minfree);
+            const unsigned w = PEAR ? fbest.slot : best.slot;
             // phase C: put i into w.  Per-point entries are written by the thread that owns them, sz by the owner of i;
             // the next step reads sz only behind its first barrier
             if (VI) {
@@ -195,12 +276,14 @@ __global__ __launch_bounds__(TPB) void k_search(Args A)
             if (tid == (i & (TPB - 1))) {
                 lab[i] = (unsigned short)w;
                 if (a) sz[a] = (unsigned short)(sz[a] - 1);
+                if (PEAR) { XA[0] = X0 + (long long)fbest.S; XA[1] = A0 + (long long)sz[w]; Sa[par] = 0; }
                 sz[w] = (unsigned short)(sz[w] + 1);
                 if (VI) T[i] = best.S + m;
             }
             moved += v.moved_to(a, w, inext);
             K = Know + (int)isnew;
             hi = max(hi, (int)w);
+            par ^= 1;
 #pragma unroll
             for (int q = 0; q < Q; ++q) cur[q] = nxt[q];
         }
@@ -224,25 +307,8 @@ __global__ __launch_bounds__(TPB) void k_search(Args A)
         for (int off = 32; off > 0; off >>= 1) f += __shfl_xor(f, off);
         if (lane == 0) r_f[wave] = f;
     } else {
-        // the Binder numerator's two sums over the upper triangle: one wave per row, 16-byte loads (ld is a multiple of 4)
-        for (int r = wave; r < n; r += NWAVE) {
-            const unsigned lr = lab[r];
-            const uint4 *row = reinterpret_cast<const uint4 *>(C + (size_t)r * ld);
-            for (int j = (((r + 1) >> 8) << 8) + 4 * lane; j < n; j += 256) {
-                const uint4 v = row[j >> 2];
-                const unsigned x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int jj = j + e;
-                    if (jj > r && jj < n) {
-                        tot += x[e];
-                        if (lab[jj] == lr) same += x[e];
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { tot += shfl_xor_u64(tot, off); same += shfl_xor_u64(same, off); }
+        // the two sums of the Binder numerator and of PEAR's X and P, from the matrix
+        upper_sums<false>(C, ld, n, lab, lane, wave, tot, same);
         if (lane == 0) { r_a[wave] = tot; r_b[wave] = same; }
     }
     __syncthreads();
@@ -260,6 +326,17 @@ __global__ __launch_bounds__(TPB) void k_search(Args A)
         o.moves = moves; o.sweeps = sweeps; o.converged = converged; o.K = K;
         A.out[run] = o;
     }
+}
+
+// PEAR(c) = num/den from X, A, P (include/redclust_hip.h), 0/1 where den = 0; a < b: a is the larger fraction
+struct Fraction {
+    long long num, den;
+    bool operator<(const Fraction &o) const { return (__int128)num * o.den > (__int128)o.num * den; }
+};
+static Fraction pear_fraction(long long X, long long A, long long P, long long m, long long T)
+{
+    const long long den = T * (m * A + P) - 2 * A * P;
+    return den ? Fraction{2 * (T * X - A * P), den} : Fraction{0, 1};
 }
 
 template <int LOSS>
@@ -281,9 +358,10 @@ static hipError_t launch(int Q, int nruns, size_t lds, hipStream_t st, const Arg
 
 // Everything behind the three entry points.  c may be NULL (errors then go to the thread's buffer); dC is the device
 // count matrix (n × ld, ld a multiple of 4, rows 16-byte aligned), read in place.
+// loss: RC_PSM_BINDER, RC_PSM_VILB (runs_out: rc_psm_run_t[nruns]) or LOSS_PEAR (runs_out: rc_pear_run_t[nruns]).
 static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, int64_t m, int64_t n, int32_t loss, int32_t nruns,
                    const int64_t *init, const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out,
-                   rc_psm_run_t *runs_out, int32_t *best, double *kernel_ms)
+                   void *runs_out, int32_t *best, double *kernel_ms)
 {
     // ---- the caller's runs: labels in 0..n, orders permutations of 1..n, cluster counts within maxK
     // (the slots are the caller's labels; hi: the highest one in use)
@@ -309,8 +387,8 @@ static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, in
     DeviceBuffers B;
 
     // ---- geometry
-    const bool vi = loss == RC_PSM_VILB;
-    const size_t fixed = (vi ? 4 * (size_t)n : 0) + 2 * (size_t)(n + 2) + 2 * (size_t)n + 16;
+    const bool vi = loss == RC_PSM_VILB, pear = loss == LOSS_PEAR;
+    const size_t fixed = (vi ? 4 * (size_t)n : 0) + (pear ? 8 * PEAR_HEAD : 0) + 2 * (size_t)(n + 2) + 2 * (size_t)n + 16;
     const size_t per_slot = vi ? 12 : 4;
     int64_t W = std::min<int64_t>(n + 1, (int64_t)((LDS_BUDGET - fixed) / per_slot));
     if (const long long v = env_int("RC_PSM_WINDOW"); v >= 1 && v < W) W = v;   // tests: force the windowed passes at small n
@@ -326,14 +404,28 @@ static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, in
     A.out = (RunOut *)S.d_out; A.n = (int)n; A.W = (int)W; A.maxK = maxK; A.maxsweeps = maxsweeps; A.m = (unsigned)m;
     HIPCHK(c, S.begin(st));
     const int Q = (int)((n + TPB - 1) / TPB);
-    const hipError_t le = vi ? launch<RC_PSM_VILB>(Q, nruns, lds, st, A) : launch<RC_PSM_BINDER>(Q, nruns, lds, st, A);
+    const hipError_t le = vi ? launch<RC_PSM_VILB>(Q, nruns, lds, st, A) : pear ? launch<LOSS_PEAR>(Q, nruns, lds, st, A)
+                                                                                : launch<RC_PSM_BINDER>(Q, nruns, lds, st, A);
     if (le != hipSuccess) return fail(c, RC_ERR_HIP, "point search: launch failed: %s", hipGetErrorString(le));
     std::vector<RunOut> h_out;
     HIPCHK(c, S.collect(st, h_out, kernel_ms));
 
-    // ---- results: the losses; the best run is the first of minimal loss
     const long long pairs = (long long)n * (n - 1) / 2;
-    greedy::results(S, h_out, labels_out, runs_out, best, [&](const RunOut &o, rc_psm_run_t &R, const int *cnt, int K) {
+    if (pear) {
+        // ---- results: num and den from the epilogue's X (same) and P (tot) and the final sizes; the best run is the first of
+        // maximal fraction, compared as the kernel compares
+        greedy::results(S, h_out, labels_out, (rc_pear_run_t *)runs_out, best, [&](const RunOut &o, rc_pear_run_t &R, const int *cnt, int K) {
+            long long within = 0;
+            for (int k = 1; k <= K; ++k) within += (long long)cnt[k] * (cnt[k] - 1) / 2;
+            const Fraction f = pear_fraction(o.same, within, o.tot, m, pairs);
+            R.num = f.num; R.den = f.den;
+            R.pear = (double)f.num / (double)f.den;
+            return f;
+        });
+        return RC_OK;
+    }
+    // ---- results: the losses; the best run is the first of minimal loss
+    greedy::results(S, h_out, labels_out, (rc_psm_run_t *)runs_out, best, [&](const RunOut &o, rc_psm_run_t &R, const int *cnt, int K) {
         if (vi) {
             R.loss_num = 0;
             R.loss = o.f / (double)n + 2.0 * std::log((double)m);
@@ -368,11 +460,56 @@ static int32_t search(const char *who, const cnt::Source &src, int32_t loss, int
         who, src,
         [&](rc_ctx *c, int64_t m, int64_t n) { return check_args(c, who, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best); },
         [&](rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, int64_t m, int64_t n) {
-            return run(c, st, dC, ld, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out, (rc_psm_run_t *)runs_out, best, kernel_ms);
+            return run(c, st, dC, ld, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best, kernel_ms);
+        });
+}
+
+// rc_pear_search*: rc_psm_search*'s checks in their order without the loss specifier, then PEAR's own capacity — m·T² < 2^62,
+// T = n(n−1)/2, keeps |num| and den below 2^63
+static int32_t pear_search(const char *who, const cnt::Source &src, int32_t nruns, const int64_t *init, const int32_t *order, int32_t maxK,
+                           int32_t maxsweeps, int64_t *labels_out, void *runs_out, int32_t *best, double *kernel_ms)
+{
+    return cnt::with(
+        who, src,
+        [&](rc_ctx *c, int64_t m, int64_t n) {
+            int32_t rc = greedy::check_args(c, who, m, n, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best);
+            if (rc == RC_OK) rc = check_lds_capacity(c, who, n, m);
+            if (rc != RC_OK) return rc;
+            const long long T = (long long)n * (n - 1) / 2;
+            if ((__int128)m * T * T >= ((__int128)1 << 62))
+                return fail(c, RC_ERR_CAPACITY, "%s: m*T^2 does not fit 62 bits, T = n(n-1)/2 (m=%lld n=%lld)", who, (long long)m, (long long)n);
+            return (int32_t)RC_OK;
+        },
+        [&](rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, int64_t m, int64_t n) {
+            return run(c, st, dC, ld, m, n, LOSS_PEAR, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best, kernel_ms);
         });
 }
 
 }  // namespace psm
+
+extern "C" int32_t rc_pear_search(int32_t device, const void *counts, int64_t m, int64_t n, int32_t nruns, const int64_t *init,
+                                  const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out,
+                                  int32_t *best, double *kernel_ms)
+{
+    return psm::pear_search("rc_pear_search", cnt::host_counts(device, counts, m, n), nruns, init, order, maxK, maxsweeps, labels_out, runs_out,
+                            best, kernel_ms);
+}
+
+extern "C" int32_t rc_pear_search_samples(int32_t device, const int64_t *samples, int64_t m, int64_t n, int32_t nruns, const int64_t *init,
+                                          const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out,
+                                          int32_t *best, double *kernel_ms, double *counts_ms)
+{
+    return psm::pear_search("rc_pear_search_samples", cnt::samples(device, samples, m, n, counts_ms), nruns, init, order, maxK, maxsweeps,
+                            labels_out, runs_out, best, kernel_ms);
+}
+
+extern "C" int32_t rc_pear_search_ctx(rc_ctx *c, int64_t numsamples, int32_t nruns, const int64_t *init, const int32_t *order,
+                                      int32_t maxK, int32_t maxsweeps, int64_t *labels_out, rc_pear_run_t *runs_out, int32_t *best,
+                                      double *kernel_ms)
+{
+    return psm::pear_search("rc_pear_search_ctx", cnt::context(c, numsamples), nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best,
+                            kernel_ms);
+}
 
 extern "C" int32_t rc_psm_search(int32_t device, const void *counts, int64_t m, int64_t n, int32_t loss, int32_t nruns,
                                  const int64_t *init, const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out,

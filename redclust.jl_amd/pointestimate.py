@@ -483,6 +483,201 @@ def expectedlosses(labellings, counts_or_samples=None, numsamples=None, loss="VI
     return out_loss, num
 
 
+def _pear_fraction(X, A, P, m, n):
+    """(num, den) of PEAR from X = Σ_{i<j, same cluster} C_ij, A = Σ_k n_k(n_k−1)/2, P = Σ_{i<j} C_ij in Python integers:
+    num = 2·(T·X − A·P), den = T·(m·A + P) − 2·A·P with T = n(n−1)/2 (include/redclust_hip.h); (0, 1) where den = 0."""
+    X, A, P, m, T = int(X), int(A), int(P), int(m), int(n) * (int(n) - 1) // 2
+    den = T * (m * A + P) - 2 * A * P
+    return (2 * (T * X - A * P), den) if den else (0, 1)
+
+
+def _within_pairs(c):
+    s = np.bincount(c).astype(np.int64)
+    return int((s * (s - 1) // 2).sum())
+
+
+def pearfraction(clust, counts, numsamples: int):
+    """expectedpear's exact value as the pair of Python integers (num, den), den > 0 — compare two labellings with
+    fractions.Fraction(num, den), or by cross-multiplication, as searchmaxpear does."""
+    c = _labels(clust)
+    C = np.asarray(counts)
+    n = len(c)
+    if C.shape != (n, n):
+        raise ValueError("counts must be an n×n matrix matching clust")
+    iu = np.triu_indices(n, 1)
+    upper = C[iu].astype(np.int64)
+    same = (c[:, None] == c[None, :])[iu]
+    return _pear_fraction(upper[same].sum(), _within_pairs(c), upper.sum(), numsamples, n)
+
+
+def expectedpear(clust, counts, numsamples: int) -> float:
+    """The posterior expected adjusted Rand index of `clust` in Fritsch & Ickstadt's form (mcclust's pear, SALSO's omARI.approx)
+    from the n×n co-clustering counts C (C_ii = numsamples = m): the adjusted Rand index with each sample's pair indicators
+    replaced by π_ij = C_ij/m,
+        [Σ I_ij·π_ij − Σ I_ij·Σ π_ij / T] / [½(Σ I_ij + Σ π_ij) − Σ I_ij·Σ π_ij / T],  sums over i < j, T = n(n−1)/2,
+    evaluated exactly as one ratio of two integers (pearfraction) and divided once; 0 where the denominator is 0 (n = 1, or
+    every sample and clust all singletons or all one cluster).  What searchmaxpear maximises.  Host only."""
+    num, den = pearfraction(clust, counts, numsamples)
+    return num / den
+
+
+def expectedpears(labellings, counts_or_samples=None, numsamples=None, *, ctx=None, device: int = 0):
+    """expectedpear for a batch of labellings (L×n, or one labelling) from the exact Binder numerators the GPU returns
+    (rc_psm_expected_loss, as expectedlosses — the input forms are its): a Binder numerator is P + m·A − 2·X, the all-singletons
+    labelling (evaluated with the batch) gives P, and A comes from the cluster sizes, so X and with it the fraction follow in
+    integers.  Returns (pear[L] f64, num[L], den[L]); num and den are int64 arrays, or object arrays of Python integers where
+    a value passes 2^63 (only beyond searchmaxpear's capacity m·T² < 2^62)."""
+    labs = np.stack([_labels(c) for c in np.atleast_2d(np.asarray(labellings))])
+    S, counts, m, n = _counts_input(counts_or_samples, numsamples, ctx)
+    if labs.shape[1] != n:
+        raise ValueError("every labelling must have n entries")
+    if S is not None:
+        counts = _lib.samples_counts(S, device=device)[0]
+    singletons = np.arange(1, n + 1, dtype=np.int64)[None, :]
+    _, binder, _ = _lib.psm_expected_loss(np.concatenate([labs, singletons]), counts, m, _PSM_LOSSES["binder"], device=device, ctx=ctx)
+    return _pears_from_binder(binder[:-1], [_within_pairs(c) for c in labs], binder[-1], m, n)
+
+
+def _pears_from_binder(binder, within, P, m, n):
+    """(pear, num, den) per labelling from its Binder numerator P + m·A − 2·X, its A and P"""
+    fr = [_pear_fraction((int(P) + int(m) * A - int(b)) // 2, A, P, m, n) for b, A in zip(binder, within)]
+    fits = all(abs(x) < 2 ** 63 for f in fr for x in f)
+    num, den = (np.array([f[k] for f in fr], dtype=np.int64 if fits else object) for k in (0, 1))
+    return np.array([f[0] / f[1] for f in fr]), num, den
+
+
+def _first_max_fraction(num, den):
+    """index of the first largest num/den (den > 0), compared exactly"""
+    best = 0
+    for k in range(1, len(num)):
+        if int(num[k]) * int(den[best]) > int(num[best]) * int(den[k]):
+            best = k
+    return best
+
+
+_PEAR_INFO = ("pear", "num", "den", "sweeps", "converged", "moves", "K", "labels", "best", "kernel_ms")
+
+
+def _pear_cuts(samples_or_counts, linkage, maxK, numsamples, ctx, device):
+    """The cuts of 1..maxK clusters (maxK = 0: ⌈n/8⌉) of hclust's dendrogram and their (pear, num, den), from the exact Binder
+    numerators of the dendrogram: binder_num[0] is P.  Returns (cuts, pear, num, den)."""
+    res, cuts, _, m, n, maxK = _hclust_cuts(samples_or_counts, linkage, maxK, numsamples, ctx, device)
+    binder = res["binder_num"][::-1][:maxK]                             # K clusters = n − K merges
+    return (cuts,) + _pears_from_binder(binder, [_within_pairs(c) for c in cuts], res["binder_num"][0], m, n)
+
+
+def _pear_draws(samples, device):
+    """(the samples as a matrix, pear, num, den of every sample)"""
+    S = _sample_matrix(samples)
+    return (S,) + expectedpears(S, samples, device=device)
+
+
+def searchmaxpear(samples_or_counts=None, *, nruns: int = 16, maxK: int = 0, maxsweeps: int = 100, seed: int = 0, init=None,
+                  numsamples=None, ctx=None, device: int = 0):
+    """Search ALL partitions for the clustering of maximum posterior expected adjusted Rand index (expectedpear; mcclust's
+    maxpear and SALSO's omARI.approx look for the same optimum) under the posterior co-clustering counts, on the GPU
+    (csrc/pointsearch.inc.hip, rc_pear_search*): searchpointestimate's greedy search with the exact fraction as the criterion.
+    Every comparison is an exact cross-multiplication of integers, so a run is a pure function of its inputs; there is no CPU
+    fallback.  getpointestimate(method="MPEL", loss="omARI") only looks at the sampled clusterings.
+
+    Inputs as searchpointestimate: an MCMCResult (anything with `.clusts`; the counts are built on the device), an n×n count
+    matrix with numsamples, or ctx= with numsamples.  Capacity: n <= 8192, m·n < 2^31 and m·T² < 2^62 with T = n(n−1)/2.
+    Runs: nruns runs from empty labels in the Philox orders of searchpointestimate; one per labelling in init; given the
+    samples, one from the sample of highest PEAR (mcclust's method="draws"); and always one from the average-linkage cut of
+    highest PEAR among 1..⌈n/8⌉ clusters (method="avg") — the last three kinds in the identity order, with maxK widened to a
+    start's cluster count where that is larger.  So the result is never below any of those starts in the exact fraction.
+    Returns (clust, info): the best labelling (sortlabels'd) and a dict with the per-run pear, num, den, sweeps, converged,
+    moves, K, all labellings (labels), best (the first run of maximal num/den), kernel_ms, and counts_ms for an MCMCResult."""
+    S, counts, m, n = _counts_input(samples_or_counts, numsamples, ctx)
+    starts = [] if init is None else list(np.atleast_2d(np.asarray(init)))
+    if S is not None:
+        _, _, dnum, dden = _pear_draws(samples_or_counts, device)
+        starts.append(S[_first_max_fraction(dnum, dden)])
+    cuts, _, cnum, cden = _pear_cuts(samples_or_counts, "average", 0, numsamples, ctx, device)
+    starts.append(cuts[_first_max_fraction(cnum, cden)])
+    inits, orders = _search_starts(n, nruns, seed, starts)
+    if maxK:
+        maxK = max(int(maxK), max(len(np.unique(x[x > 0])) for x in inits))
+    if S is not None:
+        res = _lib.pear_search_samples(S, inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device)
+    else:
+        res = _lib.pear_search(counts, m, inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device, ctx=ctx)
+    info = {k: res[k] for k in _PEAR_INFO}
+    if S is not None:
+        info["counts_ms"] = res["counts_ms"]
+    return res["labels"][res["best"]].copy(), info
+
+
+_MAXPEAR_METHODS = ("avg", "comp", "draws", "search")
+
+
+def maxpear(samples_or_counts=None, method: str = "avg", *, maxK: int = 0, numsamples=None, ctx=None, device: int = 0, **search):
+    """mcclust's maxpear: the clustering of highest PEAR (expectedpear) among the candidates of `method` —
+      "avg" / "comp":  the cuts of 1..maxK clusters (maxK = 0: ⌈n/8⌉, mcclust's max.k) of hclust's average / complete linkage;
+      "draws":         the samples themselves (an MCMCResult or anything with `.clusts` only);
+      "search":        searchmaxpear over all partitions (keywords in **search: nruns, maxsweeps, seed, init; maxK is not a cap
+                       of the search) — not in mcclust;
+      "all":           every method the input admits ("draws" needs the samples); the best of them.
+    The PEAR of every cut comes from the exact Binder numerators of the dendrogram and every choice is made on the exact
+    fraction, the first maximum winning (the fewest clusters; the earliest sample; for "all" the order above).
+    Returns (clust, info): the labelling (sortlabels'd) and a dict with pear, num, den, method (the one that won) and, per
+    method that ran, info[method] = dict(pear, num, den, and K / index / the search's info)."""
+    if method not in _MAXPEAR_METHODS + ("all",):
+        raise ValueError("Invalid method specifier.")
+    has_samples = ctx is None and hasattr(samples_or_counts, "clusts")
+    if method == "draws" and not has_samples:
+        raise ValueError('method="draws" needs the samples (an MCMCResult), not a count matrix')
+    if search and method not in ("search", "all"):
+        raise ValueError('search keywords go with method="search" or "all"')
+    source = dict(numsamples=numsamples, ctx=ctx, device=device)
+    found, per = [], {}
+    for meth in [x for x in _MAXPEAR_METHODS if method in (x, "all")]:
+        if meth in ("avg", "comp"):
+            cuts, pear, num, den = _pear_cuts(samples_or_counts, "average" if meth == "avg" else "complete", maxK, numsamples, ctx, device)
+            k = _first_max_fraction(num, den)
+            clust, per[meth] = cuts[k].copy(), dict(pear=pear, num=num, den=den, K=k + 1)
+        elif meth == "draws":
+            if not has_samples:
+                continue
+            S, pear, num, den = _pear_draws(samples_or_counts, device)
+            k = _first_max_fraction(num, den)
+            clust, per[meth] = _sortlabels(S[k]), dict(pear=pear, num=num, den=den, index=k)
+        else:
+            clust, sinfo = searchmaxpear(samples_or_counts, **source, **search)
+            k = sinfo["best"]
+            num, den = sinfo["num"], sinfo["den"]
+            per[meth] = dict(pear=sinfo["pear"], num=num, den=den, info=sinfo)
+        found.append((meth, clust, int(num[k]), int(den[k])))
+    b = _first_max_fraction([f[2] for f in found], [f[3] for f in found])
+    meth, clust, num, den = found[b]
+    return clust, dict(pear=num / den, num=num, den=den, method=meth, **per)
+
+
+def _ari_from_sums(sq, lab_sq, smp_sq, n):
+    """The L×m adjusted Rand indices (Hubert & Arabie) in f64 from the integer sums sq[l, s] = Σ_kl N_kl², lab_sq[l] = Σ_k n_k²,
+    smp_sq[s] = Σ_l n_l²; 0 where the denominator is 0"""
+    both = (np.asarray(sq) - n).astype(np.float64) / 2.0                                # Σ_kl C(N_kl, 2)
+    a = ((np.asarray(lab_sq) - n).astype(np.float64) / 2.0)[:, None]
+    b = ((np.asarray(smp_sq) - n).astype(np.float64) / 2.0)[None, :]
+    pairs = n * (n - 1) / 2.0
+    chance = a * b / pairs if pairs else np.zeros_like(both)
+    den = 0.5 * (a + b) - chance
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den != 0.0, (both - chance) / den, 0.0)
+
+
+def expectedari(labellings, samples, device: int = 0):
+    """The posterior mean of the adjusted Rand index itself — the mean over the samples (an MCMCResult, anything with `.clusts`,
+    or an m×n label matrix) of ARI(labelling, sample), Hubert & Arabie's as evaluateclustering's `ari` — for each of L
+    labellings (L×n, or one): the quantity PEAR approximates.  The integer sums Σ_kl N_kl² and the marginals Σ n_k², Σ n_l² of
+    every pair come from the GPU (rc_partition_distances, as partitiondistances(…, "binder")); the index is formed from them in
+    f64 on the host, 0 for a pair whose denominator is 0 (n = 1; both partitions all singletons or all one cluster).
+    Returns ari[L]."""
+    labs, S = _distance_inputs(labellings, samples)
+    dist = _lib.partition_distances(labs, S, want_sq=True, want_phi=False, device=device)
+    return _ari_from_sums(dist["sq"], dist["lab_marg"][:, 0], dist["smp_marg"][:, 0], S.shape[1]).mean(axis=1)
+
+
 _DIST_LOSSES = ("binder", "VI", "ID")
 
 

@@ -85,6 +85,59 @@ int32_t rc_create(int64_t n, const double *D, const double *logD_or_null, int32_
  * everything proceeds as in rc_create.  SURVEY.md §8f-2. */
 int32_t rc_create_from_points(int64_t n, int64_t dim, const double *points, int32_t storage_bits, int32_t device_id,
                               int64_t kcap, rc_ctx **out);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Metrics from coordinates (DESIGN.md §8 "Metrics from coordinates").  The names are SciPy's and Distances.jl's.  There is no
+ * Minkowski-p: pow is not correctly rounded on the device, so it could not be restated bit for bit.
+ *
+ * The arithmetic of a pair (y, x) is part of the contract: the coordinates k are walked in ascending order, every
+ * accumulator starts at +0.0, every operation is one IEEE-754 binary64 operation rounded to nearest even, nothing is fused
+ * unless written fma, nothing is reassociated and nothing is split across threads.
+ *   EUCLIDEAN    t = y_k − x_k; acc = fma(t, t, acc); d = sqrt(acc)                       (what rc_predict_points always did)
+ *   SQEUCLIDEAN  the same chain; d = acc
+ *   CITYBLOCK    t = y_k − x_k; acc = acc + |t|; d = acc
+ *   CHEBYSHEV    t = y_k − x_k; acc = max(acc, |t|); d = acc
+ *   COSINE       per point, once: nn = fma(x_k, x_k, nn); norm = sqrt(nn).  Per pair: dot = fma(y_k, x_k, dot);
+ *                s = norm_y·norm_x; c = dot / s; d = max(1 − c, 0)
+ *   CORRELATION  COSINE on centred coordinates: per point sum = sum + x_k; mu = sum / (double)dim; x'_k = x_k − mu.
+ *                Needs dim >= 2 (RC_ERR_ARG otherwise).
+ * Each is symmetric in (y, x) bit for bit.  Note for the two angular metrics: the arithmetic above does not return 0 for
+ * every point against itself or against an exact multiple — norm·norm may round an ulp or two off nn, and d is then 2^-53 or
+ * 2^-52 instead of 0 (one coincident pair in four on random vectors); it never exceeds 2^-51 there.
+ *
+ * Bad pairs (where a call refuses them: rc_predict_points_metric; rc_pairwise refuses nothing): EUCLIDEAN keeps its rule on
+ * the squared distance; for every other metric a pair is bad when d is 0, subnormal or not finite, and for COSINE /
+ * CORRELATION also when s is 0, subnormal or not finite (a zero, or constant, vector) and when d <= 2^-51, the arithmetic's
+ * zero by the note above — so that a coincident pair is refused whatever its coordinates.  A context
+ * (rc_create_from_points_metric) refuses zero entries of its matrix as rc_create does, no more: two identical training
+ * points under an angular metric pass there when their entry comes out 2^-53 or 2^-52. */
+#define RC_METRIC_EUCLIDEAN 0
+#define RC_METRIC_SQEUCLIDEAN 1
+#define RC_METRIC_CITYBLOCK 2
+#define RC_METRIC_CHEBYSHEV 3
+#define RC_METRIC_COSINE 4
+#define RC_METRIC_CORRELATION 5
+
+/* The raw distances as doubles, in the arithmetic above.  new_points_or_null == NULL: out is the symmetric n×n matrix of
+ * points (row-major n×dim) with a zero diagonal (q is ignored); one triangle is computed and mirrored, and n² doubles must fit
+ * on the device (RC_ERR_OOM otherwise).  Otherwise out is q×n, new point (row of new_points, q×dim) against training point, by
+ * the kernel of rc_predict_points_metric, the rows in chunks sized by the workspace (RC_PREDICT_WORKSPACE_KIB shrinks it).
+ * Nothing about the values is refused: zero distances are legal here, and a zero vector under COSINE gives what the
+ * arithmetic gives.  No context: errors through rc_last_error(NULL).  RC_ERR_ARG: a NULL points or out, n < 1 or n > 2^24,
+ * q < 1 with new points, dim outside 1..2^20, an unknown metric, CORRELATION with dim < 2, a device that is not there.
+ * RC_ERR_DOMAIN: a coordinate that is not finite.  kernel_ms (may be NULL): the kernels' time by device events. */
+int32_t rc_pairwise(int32_t device, int32_t metric, int64_t n, int64_t dim, const double *points /* n×dim row-major */,
+                    int64_t q, const double *new_points_or_null /* q×dim row-major */, double *out /* n×n or q×n */,
+                    double *kernel_ms);
+
+/* rc_create_from_points with D in the given metric, in the arithmetic above (one triangle computed, mirrored, zero
+ * diagonal); everything after D is rc_create_from_points'.  RC_METRIC_EUCLIDEAN here is the direct-difference chain, not
+ * rc_create_from_points' |a|² + |b|² − 2a·b: the context's matrix then agrees with the distances of rc_predict_points to the
+ * same points.  The points are kept for the k-means entry points as before; k-means clusters the observations themselves
+ * and stays Euclidean whatever the metric.  A zero off-diagonal entry fails with rc_create's RC_ERR_DOMAIN text.
+ * RC_ERR_ARG besides rc_create_from_points': an unknown metric, CORRELATION with dim < 2. */
+int32_t rc_create_from_points_metric(int64_t n, int64_t dim, const double *points, int32_t metric, int32_t storage_bits,
+                                     int32_t device_id, int64_t kcap, rc_ctx **out);
 /* The matrix the device actually holds (which = 0: D, 1: logD), as doubles: value = q·2^-e exactly. */
 int32_t rc_get_matrix(rc_ctx *ctx, int32_t which, double *out_n_by_n);
 /* Selected rows (0-based, caller's point order) of the same matrix: out is nrows×n row-major.  For sizes where the
@@ -389,7 +442,8 @@ typedef struct rc_chains_input {
     int64_t n;
     const double *D;             /* n×n, or NULL when points are given */
     const double *logD_or_null;  /* as rc_create */
-    const double *points;        /* n×dim (rc_create_from_points), used when D == NULL */
+    const double *points;        /* n×dim (rc_create_from_points: Euclidean — the layout is ABI and carries no metric; hand
+                                    data in another metric over as D), used when D == NULL */
     int64_t dim;
     int32_t storage_bits;        /* 64 or 32 */
     int32_t pad_;
@@ -757,6 +811,23 @@ int32_t rc_predict_points(int32_t device, int64_t n, int64_t dim, const double *
                           int64_t *sums_out /* m×q×Kmax×2 or NULL */,
                           double *dist_out /* q×n or NULL */, double *log_out /* q×n or NULL */,
                           int32_t *eD_out /* q or NULL */, int32_t *eL_out /* q or NULL */, double *kernel_ms);
+/* rc_predict_points with the distances in the given metric (RC_METRIC_*, "Metrics from coordinates" above);
+ * rc_predict_points is this call with RC_METRIC_EUCLIDEAN.  RC_ERR_ARG also for an unknown metric and for CORRELATION with
+ * dim < 2.  RC_ERR_DOMAIN for the first bad pair by the rules stated there; the message names the pair, the metric and the
+ * cause (coincident points, parallel points, a zero or constant vector, a scale that underflows or overflows). */
+int32_t rc_predict_points_metric(int32_t metric, int32_t device, int64_t n, int64_t dim, const double *points /* n×dim row-major */,
+                                 int64_t q, const double *new_points /* q×dim row-major */,
+                                 int64_t m, const int64_t *samples /* m×n, labels 1..n */,
+                                 const double *r /* m */, const double *p /* m */, const rc_params *params,
+                                 uint64_t seed, uint64_t sample_offset, uint64_t point_offset,
+                                 int64_t *labels_out /* m×q or NULL */, int64_t *map_out /* m×q or NULL */,
+                                 const int64_t *maps /* m×maps_width or NULL */, int64_t maps_width,
+                                 const int64_t *pivot_labels /* Kp, ascending, or NULL */, int64_t Kp,
+                                 void *counts_out /* uint32_t q×(Kp+1) or NULL */, void *mapcounts_out /* uint32_t q×(Kp+1) or NULL */,
+                                 int64_t Kmax, double *scores_out /* m×q×(Kmax+1) or NULL */,
+                                 int64_t *sums_out /* m×q×Kmax×2 or NULL */,
+                                 double *dist_out /* q×n or NULL */, double *log_out /* q×n or NULL */,
+                                 int32_t *eD_out /* q or NULL */, int32_t *eL_out /* q or NULL */, double *kernel_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Joint predict: new observations that may form clusters with each other.  One posterior sample (training labels z over n

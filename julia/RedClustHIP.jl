@@ -127,15 +127,20 @@ updates come from the library's counter-based streams keyed by `seed` (drawn fro
 `splitmerge = :intended` keeps accepted proposals (the reference as written discards them, SURVEY.md §3.2 Q1).
 A distance matrix with zero off-diagonal entries is refused with an ArgumentError (the reference would carry
 log(0) = -Inf into every log-weight): remove duplicate observations or jitter them.
+
+`points = X, metric = :cityblock` (together; X is n×dim, a name of `METRICS`): the device computes its matrix from the
+coordinates in that metric (rc_create_from_points_metric) instead of taking `data.D`; `data` is then
+`MCMCData(pairwise(HIPBackend(), X; metric = :cityblock))`, whose D and logD the split–merge scans and `fitprior` read.
 """
 function runsampler_hip(data::MCMCData,
     options::MCMCOptionsList=MCMCOptionsList(),
     params::Union{PriorHyperparamsList,Nothing}=nothing,
     init::Union{MCMCState,Nothing}=nothing;
     verbose=true, seed::Integer=rand(UInt64), device::Integer=0, kcap::Integer=0, exact_logD::Bool=false,
-    splitmerge::Symbol=:as_written)::MCMCResult
+    splitmerge::Symbol=:as_written, points::Union{Matrix{Float64},Nothing}=nothing, metric=nothing)::MCMCResult
     ostream = verbose ? stdout : devnull
     splitmerge in (:as_written, :intended) || throw(ArgumentError("splitmerge must be :as_written or :intended"))
+    (points === nothing) == (metric === nothing) || throw(ArgumentError("points and metric go together."))
     params, init = default_params_init(data, params, init; verbose=verbose)
     n = size(data.D, 1)
     ns = options.numsamples
@@ -149,10 +154,21 @@ function runsampler_hip(data::MCMCData,
     # sweep; each entry within 2^-33 ≈ 1.2e-10 of the package's value, within 1e-12 for entries near the largest).
     # exact_logD = true hands data.logD over instead: the device copy is then the package's logD rounded to the
     # fixed-point grid.  D is symmetric, so column-major == row-major.
-    GC.@preserve data begin
-        rc = ccall((:rc_create, LIB), Int32,
-                   (Int64, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Int32, Int64, Ref{Ptr{Cvoid}}),
-                   n, data.D, exact_logD ? pointer(data.logD) : Ptr{Cdouble}(C_NULL), 64, device, kcap, h)
+    # points with a metric (n×dim, one observation per row; `data` then holds pairwise(HIPBackend(), points; metric) for the
+    # host side): the device computes its matrix from the coordinates in that metric (rc_create_from_points_metric)
+    if points !== nothing
+        size(points, 1) == n || throw(ArgumentError("points must have one row per observation of data."))
+        code = metric_code(metric, size(points, 2))
+        X = permutedims(points)                                   # dim×n column-major = n×dim row-major
+        rc = ccall((:rc_create_from_points_metric, LIB), Int32,
+                   (Int64, Int64, Ptr{Cdouble}, Int32, Int32, Int32, Int64, Ref{Ptr{Cvoid}}),
+                   n, size(points, 2), X, code, 64, device, kcap, h)
+    else
+        GC.@preserve data begin
+            rc = ccall((:rc_create, LIB), Int32,
+                       (Int64, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Int32, Int64, Ref{Ptr{Cvoid}}),
+                       n, data.D, exact_logD ? pointer(data.logD) : Ptr{Cdouble}(C_NULL), 64, device, kcap, h)
+        end
     end
     check(Ptr{Cvoid}(C_NULL), rc)
     ctx = h[]
@@ -718,8 +734,50 @@ end
 
 export predict
 
+# include/redclust_hip.h's RC_METRIC_* by their names (SciPy's and Distances.jl's)
+const METRICS = Dict(:euclidean => 0, :sqeuclidean => 1, :cityblock => 2, :chebyshev => 3, :cosine => 4, :correlation => 5)
+
+function metric_code(metric, dim::Integer)
+    haskey(METRICS, Symbol(metric)) || throw(ArgumentError("unknown metric $(metric): one of $(join(sort(collect(keys(METRICS))), ", "))"))
+    (Symbol(metric) == :correlation && dim < 2) && throw(ArgumentError("the correlation metric needs dim >= 2."))
+    return Int32(METRICS[Symbol(metric)])
+end
+
 """
-    predict_points(HIPBackend(), result, points, new_points; relabelling = nothing, seed = 0)
+    pairwise(HIPBackend(), points[, new_points]; metric = :euclidean)
+
+The raw distances as the device computes them (rc_pairwise), in the arithmetic the header states for each metric: the
+symmetric n×n matrix of the n×dim `points` with a zero diagonal, or, with `new_points` (q×dim), the q×n matrix of new point
+against training point.  Nothing about the values is refused.
+"""
+function pairwise(b::HIPBackend, points::Matrix{Float64}, new_points::Union{Matrix{Float64},Nothing} = nothing; metric = :euclidean)
+    n, dim = size(points)
+    code = metric_code(metric, dim)
+    X = permutedims(points)                                       # dim×n column-major = n×dim row-major
+    ms = Cdouble[0]
+    if new_points === nothing
+        out = Matrix{Float64}(undef, n, n)                        # symmetric: column-major == row-major
+        rc = ccall((:rc_pairwise, LIB), Int32,
+                   (Int32, Int32, Int64, Int64, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                   b.device, code, n, dim, X, 0, C_NULL, out, ms)
+        check(Ptr{Cvoid}(C_NULL), rc)
+        return out
+    end
+    size(new_points, 2) == dim || throw(ArgumentError("new_points must have the dimension of points."))
+    q = size(new_points, 1)
+    Y = permutedims(new_points)
+    out = Matrix{Float64}(undef, n, q)                            # n×q column-major = q×n row-major
+    rc = ccall((:rc_pairwise, LIB), Int32,
+               (Int32, Int32, Int64, Int64, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+               b.device, code, n, dim, X, q, Y, out, ms)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return permutedims(out)
+end
+
+export pairwise
+
+"""
+    predict_points(HIPBackend(), result, points, new_points; relabelling = nothing, seed = 0, metric = :euclidean)
 
 Allocate any number of new observations given by their coordinates to the clusters of every sample of `result` on the GPU
 (rc_predict_points): `points` is n×dim, the training observations one per row, `new_points` q×dim.  The distances (direct
@@ -728,15 +786,18 @@ on the device, and the samples are uploaded once.  Without `relabelling` it retu
 `relabelling` (what `relabel(HIPBackend(), result, pivot)` returned for the same samples) it returns
 `(counts = …, map_counts = …, pivot_labels = …)`: `counts[i, k]`, k = 1..K_p+1, is the number of samples in which new
 observation `i`'s draw lands in the pivot's cluster `pivot_labels[k-1]` (column 1: a cluster of its own, or one without a
-counterpart); nothing of size m×q leaves the device.
+counterpart); nothing of size m×q leaves the device.  `metric`: the distance (a name of `METRICS`), the one the training
+matrix was made in (rc_predict_points_metric; `:euclidean` is rc_predict_points' own arithmetic).
 """
-function predict_points(b::HIPBackend, result, points::Matrix{Float64}, new_points::Matrix{Float64}; relabelling = nothing, seed = 0)
+function predict_points(b::HIPBackend, result, points::Matrix{Float64}, new_points::Matrix{Float64}; relabelling = nothing, seed = 0,
+                        metric = :euclidean)
     samples = samplematrix(result)
     n, m = size(samples)
     dim = size(points, 2)
     q = size(new_points, 1)
     size(points, 1) == n || throw(ArgumentError("points must have one row per training observation."))
     size(new_points, 2) == dim || throw(ArgumentError("new_points must have the dimension of points."))
+    code = metric_code(metric, dim)
     X = permutedims(points)                                       # dim×n column-major = n×dim row-major
     Y = permutedims(new_points)
     r = Vector{Float64}(result.r); p = Vector{Float64}(result.p)
@@ -744,11 +805,11 @@ function predict_points(b::HIPBackend, result, points::Matrix{Float64}, new_poin
     if relabelling === nothing
         labels = Matrix{Int64}(undef, q, m)                       # column s = sample s: row-major m×q for the library
         maplabels = Matrix{Int64}(undef, q, m)
-        rc = ccall((:rc_predict_points, LIB), Int32,
-                   (Int32, Int64, Int64, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{RcParams},
+        rc = ccall((:rc_predict_points_metric, LIB), Int32,
+                   (Int32, Int32, Int64, Int64, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{RcParams},
                     UInt64, UInt64, UInt64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Cvoid}, Ptr{Cvoid},
                     Int64, Ptr{Cdouble}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}),
-                   b.device, n, dim, X, q, Y, m, samples, r, p, Ref(RcParams(result.params)), seed % UInt64, UInt64(0), UInt64(0),
+                   code, b.device, n, dim, X, q, Y, m, samples, r, p, Ref(RcParams(result.params)), seed % UInt64, UInt64(0), UInt64(0),
                    labels, maplabels, C_NULL, 0, C_NULL, 0, C_NULL, C_NULL, 0, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, ms)
         check(Ptr{Cvoid}(C_NULL), rc)
         return (labels, maplabels)
@@ -760,11 +821,11 @@ function predict_points(b::HIPBackend, result, points::Matrix{Float64}, new_poin
     cols = Vector{Int64}(1:Kp)
     counts = Matrix{UInt32}(undef, Kp + 1, q)                     # row-major q×(K_p+1)
     mapcounts = Matrix{UInt32}(undef, Kp + 1, q)
-    rc = ccall((:rc_predict_points, LIB), Int32,
-               (Int32, Int64, Int64, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{RcParams},
+    rc = ccall((:rc_predict_points_metric, LIB), Int32,
+               (Int32, Int32, Int64, Int64, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{RcParams},
                 UInt64, UInt64, UInt64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Cvoid}, Ptr{Cvoid},
                 Int64, Ptr{Cdouble}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}),
-               b.device, n, dim, X, q, Y, m, samples, r, p, Ref(RcParams(result.params)), seed % UInt64, UInt64(0), UInt64(0),
+               code, b.device, n, dim, X, q, Y, m, samples, r, p, Ref(RcParams(result.params)), seed % UInt64, UInt64(0), UInt64(0),
                C_NULL, C_NULL, maps, size(maps, 1), cols, Kp, counts, mapcounts, 0, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, ms)
     check(Ptr{Cvoid}(C_NULL), rc)
     return (counts = permutedims(counts), map_counts = permutedims(mapcounts), pivot_labels = names, kernel_ms = ms[1])

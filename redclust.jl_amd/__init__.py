@@ -18,5 +18,6 @@ from .pointestimate import (getpointestimate, lossmatrix, binderloss, infodist, 
                             credibleball_from_distances, relabel, Relabelling, expectedpear, pearfraction, expectedpears,
                             searchmaxpear, maxpear, expectedari)
 from .predict import predict, predict_points, Prediction, predict_joint, JointPrediction  # noqa: F401
+from .metrics import pairwise, METRICS  # noqa: F401
 from .score import scorelabellings, loglik_from_blocks, mapestimate, searchmapestimate, reweight  # noqa: F401
 from .profiles import clusterprofiles, ClusterProfiles, silhouettes_from_sums, exemplars  # noqa: F401

@@ -131,6 +131,19 @@ def build_diag(extra_defines=(), name="libredclust_hip_diag.so", verbose: bool =
     return _compile(os.path.join(out_dir, name), ("RC_DIAG", *extra_defines), verbose)
 
 
+# include/redclust_hip.h's RC_METRIC_* by their names (SciPy's and Distances.jl's)
+METRICS = {"euclidean": 0, "sqeuclidean": 1, "cityblock": 2, "chebyshev": 3, "cosine": 4, "correlation": 5}
+
+
+def check_metric(metric, dim=None) -> str:
+    """The metric's name, or a ValueError before the library is touched: an unknown name; correlation with dim < 2."""
+    if not isinstance(metric, str) or metric not in METRICS:
+        raise ValueError(f"unknown metric {metric!r}: one of {', '.join(METRICS)}")
+    if metric == "correlation" and dim is not None and dim < 2:
+        raise ValueError("the correlation metric needs dim >= 2: a single coordinate has nothing left after centring")
+    return metric
+
+
 _dp = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 _ip = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
 _up = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
@@ -139,6 +152,10 @@ _up = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
 SIGNATURES = {
     "rc_create": (C.c_int32, [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
     "rc_create_from_points": (C.c_int32, [C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
+    "rc_create_from_points_metric": (C.c_int32, [C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                                 C.POINTER(C.c_void_p)]),
+    "rc_pairwise": (C.c_int32, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                C.POINTER(C.c_double)]),
     "rc_get_matrix": (C.c_int32, [C.c_void_p, C.c_int32, _dp]),
     "rc_get_matrix_rows": (C.c_int32, [C.c_void_p, C.c_int32, _ip, C.c_int64, _dp]),
     "rc_destroy": (C.c_int32, [C.c_void_p]),
@@ -240,6 +257,10 @@ SIGNATURES = {
                                       C.c_void_p, C.POINTER(RcParams), C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "rc_predict_points_metric": (C.c_int32, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.POINTER(RcParams), C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "rc_predict_joint": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.POINTER(RcParams), C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
@@ -305,18 +326,28 @@ class Context:
         self.h = h
 
     @classmethod
-    def from_points(cls, points, device: int = 0, kcap: int = 0, storage_bits: int = 64):
-        """MCMCData(points) on the device: pairwise Euclidean distances are computed there (types.jl:159-162)."""
-        self = cls.__new__(cls)
-        self.L = lib()
+    def from_points(cls, points, device: int = 0, kcap: int = 0, storage_bits: int = 64, metric=None):
+        """MCMCData(points) on the device: the pairwise distances are computed there.  metric None: Euclidean as the reference
+        evaluates it (types.jl:159-162, rc_create_from_points).  A name of METRICS: the matrix of pairwise(points, metric=...)
+        (rc_create_from_points_metric; "euclidean" is then predict_points' direct-difference arithmetic).  The context
+        remembers .metric; its k-means entry points stay Euclidean on the points themselves."""
         pts = np.ascontiguousarray(points, dtype=np.float64)
         if pts.ndim != 2:
             raise ValueError("points must be an n×dim array (one observation per row)")
+        if metric is not None:
+            check_metric(metric, int(pts.shape[1]))
+        self = cls.__new__(cls)
+        self.L = lib()
         self.n = int(pts.shape[0])
         self.dim = int(pts.shape[1])
+        self.metric = metric
         h = C.c_void_p()
-        _check(self.L.rc_create_from_points(self.n, int(pts.shape[1]), pts.ctypes.data_as(C.c_void_p), storage_bits, device,
-                                            kcap, C.byref(h)))
+        if metric is None:
+            _check(self.L.rc_create_from_points(self.n, int(pts.shape[1]), pts.ctypes.data_as(C.c_void_p), storage_bits, device,
+                                                kcap, C.byref(h)))
+        else:
+            _check(self.L.rc_create_from_points_metric(self.n, int(pts.shape[1]), pts.ctypes.data_as(C.c_void_p), METRICS[metric],
+                                                       storage_bits, device, kcap, C.byref(h)))
         self.h = h
         return self
 
@@ -1058,14 +1089,16 @@ def predict(Dnew, samples, r, p, params: dict, seed: int = 0, sample_offset: int
 def predict_points(points, new_points, samples, r, p, params: dict, seed: int = 0, sample_offset: int = 0, point_offset: int = 0,
                    want_labels: bool = True, want_map: bool = True, maps=None, pivot_labels=None, want_counts: bool = False,
                    want_mapcounts: bool = False, Kmax: int = 0, want_scores: bool = False, want_sums: bool = False,
-                   want_dist: bool = False, want_log: bool = False, device: int = 0) -> dict:
+                   want_dist: bool = False, want_log: bool = False, device: int = 0, *, metric=None) -> dict:
     """rc_predict_points: as predict for q×dim new points and the n×dim training points, the distances and their logarithms
     taken on the device: labels and map (m×q, or None), eD / eL (q), kernel_ms and, when asked for, scores and sums (with Kmax),
     dist and log (q×n), and — with maps (m×W, rc_relabel's) and pivot_labels (K_p, ascending) — counts and mapcounts
-    (q×(K_p+1) uint32)."""
-    L = lib()
+    (q×(K_p+1) uint32).  metric: None for rc_predict_points itself, or a name of METRICS (rc_predict_points_metric)."""
     X = np.ascontiguousarray(points, dtype=np.float64)
     Y = np.ascontiguousarray(new_points, dtype=np.float64)
+    if metric is not None:
+        check_metric(metric, X.shape[1] if X.ndim == 2 else None)
+    L = lib()
     S = np.ascontiguousarray(samples, dtype=np.int64)
     r = np.ascontiguousarray(r, dtype=np.float64)
     p = np.ascontiguousarray(p, dtype=np.float64)
@@ -1097,10 +1130,11 @@ def predict_points(points, new_points, samples, r, p, params: dict, seed: int = 
     ms = C.c_double()
     M64 = 0xFFFFFFFFFFFFFFFF
     ptr = lambda a: None if a is None else a.ctypes.data
-    rc = L.rc_predict_points(int(device), n, dim, X.ctypes.data, q, Y.ctypes.data, m, S.ctypes.data, r.ctypes.data, p.ctypes.data,
-                             C.byref(prm), int(seed) & M64, int(sample_offset) & M64, int(point_offset) & M64, ptr(labels), ptr(mp),
-                             ptr(mp_), W, ptr(pv), Kp, ptr(cnt), ptr(mcnt), int(Kmax), ptr(sc), ptr(sm), ptr(dist), ptr(lg),
-                             eD.ctypes.data, eL.ctypes.data, C.byref(ms))
+    rest = (int(device), n, dim, X.ctypes.data, q, Y.ctypes.data, m, S.ctypes.data, r.ctypes.data, p.ctypes.data,
+            C.byref(prm), int(seed) & M64, int(sample_offset) & M64, int(point_offset) & M64, ptr(labels), ptr(mp),
+            ptr(mp_), W, ptr(pv), Kp, ptr(cnt), ptr(mcnt), int(Kmax), ptr(sc), ptr(sm), ptr(dist), ptr(lg),
+            eD.ctypes.data, eL.ctypes.data, C.byref(ms))
+    rc = L.rc_predict_points(*rest) if metric is None else L.rc_predict_points_metric(METRICS[metric], *rest)
     _check(rc)
     cut = lambda a: None if a is None else a[:m, :q]
     out = dict(labels=cut(labels), map=cut(mp), eD=eD[:q], eL=eL[:q], kernel_ms=float(ms.value),
@@ -1114,6 +1148,25 @@ def predict_points(points, new_points, samples, r, p, params: dict, seed: int = 
     if want_log:
         out["log"] = lg[:q, :n]
     return out
+
+
+def pairwise(points, new_points=None, metric: str = "euclidean", device: int = 0, want_ms: bool = False):
+    """rc_pairwise: the n×n matrix of the n×dim points (new_points None) or the q×n matrix of q×dim new points against them, as
+    doubles in the metric's stated arithmetic; with want_ms also the kernels' time in ms."""
+    X = np.ascontiguousarray(points, dtype=np.float64)
+    Y = None if new_points is None else np.ascontiguousarray(new_points, dtype=np.float64)
+    if X.ndim != 2 or (Y is not None and (Y.ndim != 2 or Y.shape[1] != X.shape[1])):
+        raise ValueError("points must be n×dim and new_points q×dim")
+    check_metric(metric, X.shape[1])
+    L = lib()
+    n, dim = X.shape
+    q = 0 if Y is None else Y.shape[0]
+    out = np.zeros((n if Y is None else max(q, 1), max(n, 1)))
+    ms = C.c_double()
+    _check(L.rc_pairwise(int(device), METRICS[metric], n, dim, X.ctypes.data, q, None if Y is None else Y.ctypes.data, out.ctypes.data,
+                         C.byref(ms)))
+    out = out if Y is None else out[:q, :n]
+    return (out, float(ms.value)) if want_ms else out
 
 
 def predict_joint(Dnew, Dnn, samples, r, p, params: dict, sweeps: int = 2, seed: int = 0, sample_offset: int = 0, logDnew=None,

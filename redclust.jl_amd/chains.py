@@ -118,7 +118,7 @@ def run_chains(data, options, params, init, *, base_seed: int = 1, verbose: bool
     if local >= ndev:
         raise RuntimeError(f"run_chains: LOCAL_RANK={local} but only {ndev} GPU(s) are visible — launch one process per GPU")
     torch.cuda.set_device(local)      # the object collectives below stage through the current device under nccl
-    ctx = (Context.from_points(data.points, device=local, kcap=kcap) if data.points is not None
+    ctx = (Context.from_points(data.points, device=local, kcap=kcap, metric=data.metric) if data.points is not None
            else Context(data.D, device=local, kcap=kcap))
     try:
         res = runsampler(data, options, params, init, verbose=verbose and rank == 0,
@@ -143,7 +143,8 @@ def run_chains_single_process(data, options, params, init, device_ids, *, base_s
     P = dict(delta1=params.delta1, delta2=params.delta2, alpha=params.alpha, beta=params.beta, zeta=params.zeta,
              gamma=params.gamma, eta=params.eta, sigma=params.sigma, u=params.u, v=params.v,
              repulsion=params.repulsion, maxK=params.maxK)
-    kw = dict(points=data.points) if data.points is not None and options.numMH == 0 else dict(D=data.D)
+    # rc_run_chains computes Euclidean distances from points (rc_chains_input's layout is ABI): data in a metric goes as its host D
+    kw = dict(points=data.points) if data.points is not None and data.metric is None and options.numMH == 0 else dict(D=data.D)
     chains, merged, total, _ms = _native(device_ids, P, init.clusts, options.numiters, options.burnin, options.thin,
                                          options.numGibbs, options.numMH, base_seed, init.r, init.p, params.proposalsd_r,
                                          kcap=kcap, splitmerge=splitmerge, **kw)

@@ -11,6 +11,9 @@
 // reassociated and never split across threads.  A correctly rounded square root finishes the distance; the row's largest
 // distance is folded with integer atomic maxima on the bit patterns (positive doubles order as their bits), and a squared
 // distance that is 0, subnormal or not finite lowers the call's "first bad pair" word to its row-major index (atomic minimum).
+// The kernel is a template over the metric (metric.inc.hip: met::step per coordinate, met::finish and met::bad at the end; the
+// norms of the two angular metrics come from met::k_metric_prep, which has also centred both point sets for CORRELATION); the
+// EUCLIDEAN instantiation is the kernel described above, operation for operation.
 //
 // k_points_rows: one block per new point: rc_flog of the row (twice: once for the largest |log|, once to quantise — cheaper
 // than a round trip through memory), the exponents by quant_exponent_hd, the (Dq, Lq) row and the scales 2^-eD, 2^-eL where
@@ -25,9 +28,12 @@ constexpr u64 NO_PAIR = ~(u64)0;
 constexpr int64_t DIM_MAX = (int64_t)1 << 20;
 
 // XT: [dim][n]; Y: [np][dim]; dist: [np][n]; maxd: [np] bit patterns, zero before the launch; firstbad: min over the bad pairs
-// of pair0 + i·n + j.  Grid: (groups of R new points, strips of TPB training points).
+// of pair0 + i·n + j; nX: [n], nY: [np] the norms (angular metrics, else unused).  Grid: (groups of R new points, strips of TPB
+// training points).
+template <int M>
 __global__ __launch_bounds__(TPB) void k_points_dist(const double *__restrict__ XT, int n, int dim, const double *__restrict__ Y, int np, u64 pair0,
-                                                     double *__restrict__ dist, u64 *__restrict__ maxd, u64 *__restrict__ firstbad)
+                                                     double *__restrict__ dist, u64 *__restrict__ maxd, u64 *__restrict__ firstbad,
+                                                     const double *__restrict__ nX, const double *__restrict__ nY)
 {
     __shared__ double ys[DT * R];
     const int ib = blockIdx.x * R;
@@ -50,21 +56,19 @@ __global__ __launch_bounds__(TPB) void k_points_dist(const double *__restrict__ 
             for (int kk = 0; kk < dt; ++kk) {
                 const double x = xp[(size_t)kk * (size_t)n];
 #pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const double t = ys[kk * R + r] - x;
-                    acc[r] = fma(t, t, acc[r]);
-                }
+                for (int r = 0; r < R; ++r) acc[r] = met::step<M>(acc[r], ys[kk * R + r], x);
             }
         }
     }
+    const double nx = (met::angular(M) && j < n) ? nX[j] : 1.0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         u64 bits = 0;
         if (j < n && r < nr) {
-            const double sq = acc[r];
-            const double d = __dsqrt_rn(sq);
+            double s;
+            const double d = met::finish<M>(acc[r], met::angular(M) ? nY[ib + r] : 1.0, nx, s);
             dist[(size_t)(ib + r) * (size_t)n + j] = d;
-            if (sq >= 2.2250738585072014e-308 && sq <= 1.79769313486231570e308) bits = (u64)__double_as_longlong(d);
+            if (!met::bad<M>(acc[r], d, s)) bits = (u64)__double_as_longlong(d);
             else atomicMin(firstbad, pair0 + (u64)(ib + r) * (u64)n + (u64)j);
         }
 #pragma unroll
@@ -113,26 +117,81 @@ __global__ __launch_bounds__(TPB) void k_points_rows(const double *__restrict__ 
 struct Points {
     int64_t dim;
     const double *points, *new_points;      // host: n×dim, q×dim
-    const double *d_XT;                     // device: dim×n
+    const double *d_XT;                     // device: dim×n (centred for CORRELATION)
     u64 *d_firstbad;
     double *dist_out, *log_out;             // host q×n or null
     int32_t *eD_out, *eL_out;               // host q or null
+    int32_t metric;
+    const double *d_nX;                     // device: the training points' norms (angular metrics, else null)
 };
 
-// the library's error for the first pair (row-major, 0-based index into q×n) whose squared distance is not a positive normal number
+// the q×n (here np×n) distances of one chunk in the call's metric
+static void launch_dist(int32_t metric, const double *d_XT, int64_t n, int64_t dim, const double *d_Y, int64_t np, u64 pair0, double *d_dist, u64 *d_maxd,
+                        u64 *d_firstbad, const double *d_nX, const double *d_nY)
+{
+    const dim3 grid((unsigned)((np + R - 1) / R), (unsigned)((n + TPB - 1) / TPB));
+#define RC_POINTS_DIST(M) k_points_dist<M><<<grid, TPB, 0, 0>>>(d_XT, (int)n, (int)dim, d_Y, (int)np, pair0, d_dist, d_maxd, d_firstbad, d_nX, d_nY)
+    switch (metric) {
+    case RC_METRIC_EUCLIDEAN:   RC_POINTS_DIST(RC_METRIC_EUCLIDEAN); break;
+    case RC_METRIC_SQEUCLIDEAN: RC_POINTS_DIST(RC_METRIC_SQEUCLIDEAN); break;
+    case RC_METRIC_CITYBLOCK:   RC_POINTS_DIST(RC_METRIC_CITYBLOCK); break;
+    case RC_METRIC_CHEBYSHEV:   RC_POINTS_DIST(RC_METRIC_CHEBYSHEV); break;
+    case RC_METRIC_COSINE:      RC_POINTS_DIST(RC_METRIC_COSINE); break;
+    default:                    RC_POINTS_DIST(RC_METRIC_CORRELATION); break;
+    }
+#undef RC_POINTS_DIST
+}
+
+// a point's coordinates as the angular metrics see them (centred for CORRELATION) and their norm, in the header's arithmetic
+static double host_prepared(int32_t metric, const double *x, int64_t dim, std::vector<double> &out)
+{
+    double mu = 0.0;
+    if (metric == RC_METRIC_CORRELATION) {
+        double sum = 0.0;
+        for (int64_t k = 0; k < dim; ++k) sum += x[k];
+        mu = sum / (double)dim;
+    }
+    double nn = 0.0;
+    out.resize((size_t)dim);
+    for (int64_t k = 0; k < dim; ++k) {
+        const double v = metric == RC_METRIC_CORRELATION ? x[k] - mu : x[k];
+        out[(size_t)k] = v;
+        nn = std::fma(v, v, nn);
+    }
+    return std::sqrt(nn);
+}
+
+// the library's error for the first bad pair (row-major, 0-based index into q×n): it names the pair, the metric and the cause
 static int32_t bad_pair(const char *who, const prd::Call &c, const Points &pt, u64 pair)
 {
     const int64_t i = (int64_t)(pair / (u64)c.n), j = (int64_t)(pair % (u64)c.n);
-    double sq = 0.0;
+    const double *y = pt.new_points + (size_t)i * pt.dim, *x = pt.points + (size_t)j * pt.dim;
+    const char *name = met::NAMES[pt.metric];
+    const long long i1 = (long long)i + 1, j1 = (long long)j + 1;
     bool same = true;
-    for (int64_t k = 0; k < pt.dim; ++k) {
-        const double t = pt.new_points[(size_t)i * pt.dim + k] - pt.points[(size_t)j * pt.dim + k];
-        same = same && t == 0.0;
-        sq = std::fma(t, t, sq);
+    for (int64_t k = 0; k < pt.dim; ++k) same = same && y[k] == x[k];
+    if (met::angular(pt.metric)) {
+        std::vector<double> yc, xc;
+        const double ny = host_prepared(pt.metric, y, pt.dim, yc), nx = host_prepared(pt.metric, x, pt.dim, xc);
+        const char *flat = pt.metric == RC_METRIC_COSINE ? "is the zero vector" : "has constant coordinates";
+        if (ny == 0.0) return fail(nullptr, RC_ERR_DOMAIN, "%s: new point %lld %s: its %s distance is undefined", who, i1, flat, name);
+        if (nx == 0.0) return fail(nullptr, RC_ERR_DOMAIN, "%s: training point %lld %s: its %s distance is undefined (met at new point %lld)", who, j1, flat, name, i1);
+        const double s = ny * nx;
+        if (!met::positive_normal(s))
+            return fail(nullptr, RC_ERR_DOMAIN, "%s: the product of the norms of new point %lld and training point %lld is %g (metric %s): the coordinates' scale %s it",
+                        who, i1, j1, s, name, s < 1.0 ? "underflows" : "overflows");
+        if (same) return fail(nullptr, RC_ERR_DOMAIN, "%s: new point %lld coincides with training point %lld (metric %s): the distances must be positive", who, i1, j1, name);
+        return fail(nullptr, RC_ERR_DOMAIN, "%s: new point %lld is parallel to training point %lld: their %s distance is 0 to within the rounding of the norms, and the distances must be positive", who, i1, j1, name);
     }
-    if (same) return fail(nullptr, RC_ERR_DOMAIN, "%s: new point %lld coincides with training point %lld: the distances must be positive", who, (long long)i + 1, (long long)j + 1);
-    return fail(nullptr, RC_ERR_DOMAIN, "%s: the squared distance of new point %lld to training point %lld is %g: the coordinates' scale %s the square",
-                who, (long long)i + 1, (long long)j + 1, sq, sq < 1.0 ? "underflows" : "overflows");
+    if (same) return fail(nullptr, RC_ERR_DOMAIN, "%s: new point %lld coincides with training point %lld (metric %s): the distances must be positive", who, i1, j1, name);
+    double acc = 0.0;
+    for (int64_t k = 0; k < pt.dim; ++k) {
+        const double t = y[k] - x[k];
+        acc = pt.metric == RC_METRIC_CITYBLOCK ? acc + std::fabs(t) : pt.metric == RC_METRIC_CHEBYSHEV ? std::fmax(acc, std::fabs(t)) : std::fma(t, t, acc);
+    }
+    const bool squared = pt.metric == RC_METRIC_EUCLIDEAN || pt.metric == RC_METRIC_SQEUCLIDEAN;
+    return fail(nullptr, RC_ERR_DOMAIN, "%s: the %s distance of new point %lld to training point %lld is %g (metric %s): the coordinates' scale %s %s",
+                who, squared ? "squared" : name, i1, j1, acc, name, acc < 1.0 ? "underflows" : "overflows", squared ? "the square" : "it");
 }
 
 // samples s0 .. s0 + ms - 1 against every new point, the points in chunks of at most qc whose rows are filled on the device.
@@ -150,6 +209,8 @@ static int32_t run_samples(const char *who, const prd::Call &c, const Points &pt
     HIPCHK(nullptr, B.alloc(d_maxd, (size_t)qc));
     HIPCHK(nullptr, B.alloc(d_eD, (size_t)qc));
     HIPCHK(nullptr, B.alloc(d_eL, (size_t)qc));
+    double *d_nY = nullptr;
+    if (met::angular(pt.metric)) HIPCHK(nullptr, B.alloc(d_nY, (size_t)qc));
     TimingEvents ev;
     HIPCHK(nullptr, ev.create());
     for (int64_t i0 = 0; i0 < c.q; i0 += qc) {
@@ -157,8 +218,8 @@ static int32_t run_samples(const char *who, const prd::Call &c, const Points &pt
         HIPCHK(nullptr, hipMemcpy(d_Y, pt.new_points + (size_t)i0 * dim, (size_t)np * dim * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(nullptr, hipMemsetAsync(d_maxd, 0, (size_t)np * sizeof(u64), 0));
         HIPCHK(nullptr, ev.begin(0));
-        k_points_dist<<<dim3((unsigned)((np + R - 1) / R), (unsigned)((n + TPB - 1) / TPB)), TPB, 0, 0>>>(pt.d_XT, (int)n, (int)dim, d_Y, (int)np, (u64)i0 * (u64)n,
-                                                                                                    d_dist, d_maxd, pt.d_firstbad);
+        met::launch_prep(pt.metric, d_Y, np, dim, d_nY, 0);
+        launch_dist(pt.metric, pt.d_XT, n, dim, d_Y, np, (u64)i0 * (u64)n, d_dist, d_maxd, pt.d_firstbad, pt.d_nX, d_nY);
         k_points_rows<<<(unsigned)np, TPB, 0, 0>>>(d_dist, (int)n, d_maxd, c.d_flt, run.d_rows, d_log, run.d_scD, run.d_scL, d_eD, d_eL);
         HIPCHK(nullptr, ev.end(0));
         HIPCHK(nullptr, ev.elapsed_ms(ms_acc));
@@ -175,22 +236,54 @@ static int32_t run_samples(const char *who, const prd::Call &c, const Points &pt
     return RC_OK;
 }
 
+// The training points on the device as k_points_dist reads them: uploaded, through the metric's pre-pass (d_nX: their norms,
+// null unless the metric is angular) and transposed to dim×n (d_XT); both are owned by B.
+static int32_t stage_training(int32_t metric, const double *points, int64_t n, int64_t dim, DeviceBuffers &B, double *&d_XT, double *&d_nX)
+{
+    DeviceBuffers T;                            // the points as given, until they are transposed
+    double *d_X;
+    d_nX = nullptr;
+    HIPCHK(nullptr, T.alloc(d_X, (size_t)n * dim));
+    HIPCHK(nullptr, B.alloc(d_XT, (size_t)n * dim));
+    if (met::angular(metric)) HIPCHK(nullptr, B.alloc(d_nX, (size_t)n));
+    HIPCHK(nullptr, hipMemcpy(d_X, points, (size_t)n * dim * sizeof(double), hipMemcpyHostToDevice));
+    met::launch_prep(metric, d_X, n, dim, d_nX, 0);
+    k_transpose_points<<<(unsigned)std::min<size_t>(((size_t)n * (size_t)dim + 255) / 256, 65535), 256, 0, 0>>>(d_X, (int)n, (int)dim, d_XT);
+    HIPCHK(nullptr, hipGetLastError());
+    HIPCHK(nullptr, hipStreamSynchronize(0));
+    return RC_OK;
+}
+
+// the first coordinate of n×dim points and q×dim new points (null: none) that is not finite: the library's error
+static int32_t check_finite(const char *who, const double *points, int64_t n, const double *new_points, int64_t q, int64_t dim)
+{
+    for (int pass = 0; pass < (new_points ? 2 : 1); ++pass) {
+        const double *x = pass ? new_points : points;
+        const int64_t rows = pass ? q : n;
+        for (size_t e = 0; e < (size_t)rows * (size_t)dim; ++e)
+            if (!(std::fabs(x[e]) <= 1.79769313486231570e308))
+                return fail(nullptr, RC_ERR_DOMAIN, "%s: coordinate %lld of %s %lld is not finite", who, (long long)(e % (size_t)dim) + 1, pass ? "new point" : "training point", (long long)(e / (size_t)dim) + 1);
+    }
+    return RC_OK;
+}
+
 }  // namespace pp
 
-extern "C" int32_t rc_predict_points(int32_t device, int64_t n, int64_t dim, const double *points, int64_t q, const double *new_points, int64_t m,
-                                     const int64_t *samples, const double *r, const double *p, const rc_params *params, uint64_t seed,
-                                     uint64_t sample_offset, uint64_t point_offset, int64_t *labels_out, int64_t *map_out, const int64_t *maps,
-                                     int64_t maps_width, const int64_t *pivot_labels, int64_t Kp, void *counts_out, void *mapcounts_out, int64_t Kmax,
-                                     double *scores_out, int64_t *sums_out, double *dist_out, double *log_out, int32_t *eD_out, int32_t *eL_out,
-                                     double *kernel_ms)
+static int32_t predict_points_impl(const char *who, int32_t metric, int32_t device, int64_t n, int64_t dim, const double *points, int64_t q, const double *new_points, int64_t m,
+                                   const int64_t *samples, const double *r, const double *p, const rc_params *params, uint64_t seed,
+                                   uint64_t sample_offset, uint64_t point_offset, int64_t *labels_out, int64_t *map_out, const int64_t *maps,
+                                   int64_t maps_width, const int64_t *pivot_labels, int64_t Kp, void *counts_out, void *mapcounts_out, int64_t Kmax,
+                                   double *scores_out, int64_t *sums_out, double *dist_out, double *log_out, int32_t *eD_out, int32_t *eL_out,
+                                   double *kernel_ms)
 {
-    const char *who = "rc_predict_points";
     if (!points || !new_points || !samples || !r || !p || !params) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
     if (!labels_out && !map_out && !counts_out && !mapcounts_out) return fail(nullptr, RC_ERR_ARG, "%s: one of labels_out, map_out, counts_out and mapcounts_out must be given", who);
     if (n < 1 || q < 1 || m < 1) return fail(nullptr, RC_ERR_ARG, "%s: need n >= 1, q >= 1 and m >= 1 (got n=%lld q=%lld m=%lld)", who, (long long)n, (long long)q, (long long)m);
     int32_t rc = check_label_shape(nullptr, who, n, "training points", m, "m");
     if (rc != RC_OK) return rc;
     if (dim < 1 || dim > pp::DIM_MAX) return fail(nullptr, RC_ERR_ARG, "%s: dim = %lld outside 1..%lld", who, (long long)dim, (long long)pp::DIM_MAX);
+    rc = met::check_metric(nullptr, who, metric, dim);
+    if (rc != RC_OK) return rc;
     const bool want_counts = counts_out || mapcounts_out;
     if (want_counts && (!maps || !pivot_labels)) return fail(nullptr, RC_ERR_ARG, "%s: the counts need maps and pivot_labels", who);
     rc = check_params(nullptr, who, params);
@@ -220,13 +313,8 @@ extern "C" int32_t rc_predict_points(int32_t device, int64_t n, int64_t dim, con
             }
         }
     }
-    for (int pass = 0; pass < 2; ++pass) {
-        const double *x = pass ? new_points : points;
-        const int64_t rows = pass ? q : n;
-        for (size_t e = 0; e < (size_t)rows * (size_t)dim; ++e)
-            if (!(std::fabs(x[e]) <= 1.79769313486231570e308))
-                return fail(nullptr, RC_ERR_DOMAIN, "%s: coordinate %lld of %s %lld is not finite", who, (long long)(e % (size_t)dim) + 1, pass ? "new point" : "training point", (long long)(e / (size_t)dim) + 1);
-    }
+    rc = pp::check_finite(who, points, n, new_points, q, dim);
+    if (rc != RC_OK) return rc;
     rc = select_device(who, device);
     if (rc != RC_OK) return rc;
     size_table(params, n, A.data());
@@ -238,18 +326,10 @@ extern "C" int32_t rc_predict_points(int32_t device, int64_t n, int64_t dim, con
         HIPCHK(nullptr, B.alloc(d_flt, 128));
         HIPCHK(nullptr, hipMemcpy(d_flt, ft, sizeof(ft), hipMemcpyHostToDevice));
     }
-    double *d_XT;
+    double *d_XT, *d_nX;
     u64 *d_firstbad;
-    {
-        DeviceBuffers T;                            // the points as given, until they are transposed
-        double *d_X;
-        HIPCHK(nullptr, T.alloc(d_X, (size_t)n * dim));
-        HIPCHK(nullptr, B.alloc(d_XT, (size_t)n * dim));
-        HIPCHK(nullptr, hipMemcpy(d_X, points, (size_t)n * dim * sizeof(double), hipMemcpyHostToDevice));
-        k_transpose_points<<<(unsigned)std::min<size_t>(((size_t)n * (size_t)dim + 255) / 256, 65535), 256, 0, 0>>>(d_X, (int)n, (int)dim, d_XT);
-        HIPCHK(nullptr, hipGetLastError());
-        HIPCHK(nullptr, hipStreamSynchronize(0));
-    }
+    rc = pp::stage_training(metric, points, n, dim, B, d_XT, d_nX);
+    if (rc != RC_OK) return rc;
     HIPCHK(nullptr, B.alloc(d_firstbad, 1));
     HIPCHK(nullptr, hipMemset(d_firstbad, 0xFF, sizeof(u64)));
     prd::Call c{n, q, m, want_tab ? Kmax : 0, nullptr, nullptr, samples, r, p, params, seed, sample_offset, point_offset,
@@ -264,7 +344,7 @@ extern "C" int32_t rc_predict_points(int32_t device, int64_t n, int64_t dim, con
         HIPCHK(nullptr, B.alloc(c.d_mapcounts, (size_t)q * ncols));
         HIPCHK(nullptr, hipMemset(c.d_mapcounts, 0, (size_t)q * ncols * sizeof(unsigned)));
     }
-    const pp::Points pt{dim, points, new_points, d_XT, d_firstbad, dist_out, log_out, eD_out, eL_out};
+    const pp::Points pt{dim, points, new_points, d_XT, d_firstbad, dist_out, log_out, eD_out, eL_out, metric, d_nX};
     // Chunks: rc_predict's plan with, per new point, its coordinates, its f64 distances and, when asked for, its logarithms
     // beside its row.
     const size_t workspace = env_workspace_kib("RC_PREDICT_WORKSPACE_KIB", slab::WORKSPACE);
@@ -282,4 +362,28 @@ extern "C" int32_t rc_predict_points(int32_t device, int64_t n, int64_t dim, con
     if (mapcounts_out) HIPCHK(nullptr, hipMemcpy(mapcounts_out, c.d_mapcounts, (size_t)q * ncols * sizeof(unsigned), hipMemcpyDeviceToHost));
     if (kernel_ms) *kernel_ms = ms_acc;
     return RC_OK;
+}
+
+extern "C" int32_t rc_predict_points(int32_t device, int64_t n, int64_t dim, const double *points, int64_t q, const double *new_points, int64_t m,
+                                     const int64_t *samples, const double *r, const double *p, const rc_params *params, uint64_t seed,
+                                     uint64_t sample_offset, uint64_t point_offset, int64_t *labels_out, int64_t *map_out, const int64_t *maps,
+                                     int64_t maps_width, const int64_t *pivot_labels, int64_t Kp, void *counts_out, void *mapcounts_out, int64_t Kmax,
+                                     double *scores_out, int64_t *sums_out, double *dist_out, double *log_out, int32_t *eD_out, int32_t *eL_out,
+                                     double *kernel_ms)
+{
+    return predict_points_impl("rc_predict_points", RC_METRIC_EUCLIDEAN, device, n, dim, points, q, new_points, m, samples, r, p, params, seed, sample_offset,
+                               point_offset, labels_out, map_out, maps, maps_width, pivot_labels, Kp, counts_out, mapcounts_out, Kmax, scores_out,
+                               sums_out, dist_out, log_out, eD_out, eL_out, kernel_ms);
+}
+
+extern "C" int32_t rc_predict_points_metric(int32_t metric, int32_t device, int64_t n, int64_t dim, const double *points, int64_t q, const double *new_points,
+                                            int64_t m, const int64_t *samples, const double *r, const double *p, const rc_params *params, uint64_t seed,
+                                            uint64_t sample_offset, uint64_t point_offset, int64_t *labels_out, int64_t *map_out, const int64_t *maps,
+                                            int64_t maps_width, const int64_t *pivot_labels, int64_t Kp, void *counts_out, void *mapcounts_out,
+                                            int64_t Kmax, double *scores_out, int64_t *sums_out, double *dist_out, double *log_out, int32_t *eD_out,
+                                            int32_t *eL_out, double *kernel_ms)
+{
+    return predict_points_impl("rc_predict_points_metric", metric, device, n, dim, points, q, new_points, m, samples, r, p, params, seed, sample_offset,
+                               point_offset, labels_out, map_out, maps, maps_width, pivot_labels, Kp, counts_out, mapcounts_out, Kmax, scores_out,
+                               sums_out, dist_out, log_out, eD_out, eL_out, kernel_ms);
 }

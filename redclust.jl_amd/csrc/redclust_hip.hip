@@ -5472,8 +5472,12 @@ static int kmeans_shift(const double *points, int64_t n, int64_t dim)
     return std::max(-2000, std::min(2000, 61 - ceil_log2_ll((long long)n) - ex));
 }
 
+// metric.inc.hip: D of the staged points in an RC_METRIC_* (the stated arithmetic of the header)
+static hipError_t metric_matrix_for_context(int32_t metric, const double *d_pts, int64_t n, int64_t dim, double *d_D, hipStream_t st);
+
+// metric < 0: rc_create_from_points' own k_pairwise
 static int32_t create_impl(rc_ctx *c, int64_t n, const double *D, const double *logD, const double *points = nullptr,
-                           int64_t dim = 0)
+                           int64_t dim = 0, int32_t metric = -1)
 {
     HIPCHK(c, hipSetDevice(c->dev));
     hipDeviceProp_t prop;
@@ -5574,7 +5578,8 @@ static int32_t create_impl(rc_ctx *c, int64_t n, const double *D, const double *
         // MCMCData(points): distances are computed on the device, no n×n host matrix is involved
         HIPCHK2(hipMemcpyAsync(tmpL, points, (size_t)n * (size_t)dim * sizeof(double), hipMemcpyHostToDevice, s));  // tmpL as staging
         const unsigned nt = (unsigned)((n + 63) / 64);
-        k_pairwise<<<dim3(nt, nt), 256, 0, s>>>(tmpL, (int)n, (int)dim, tmpD);
+        if (metric < 0) k_pairwise<<<dim3(nt, nt), 256, 0, s>>>(tmpL, (int)n, (int)dim, tmpD);
+        else HIPCHK2(metric_matrix_for_context(metric, tmpL, n, dim, tmpD, s));
         // the k-means entry points (kmeans.inc.hip) work on the points themselves: keep them, row-major and transposed
         HIPCHK2(hipMalloc(&c->pts, (size_t)n * (size_t)dim * sizeof(double)));
         HIPCHK2(hipMalloc(&c->ptsT, (size_t)n * (size_t)dim * sizeof(double)));
@@ -8045,7 +8050,9 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "slabplan.inc.hpp"
 #include "slab.inc.hip"
 #include "predict.inc.hip"
+#include "metric.inc.hip"
 #include "predictpoints.inc.hip"
+#include "pairwise.inc.hip"
 #include "predictjoint.inc.hip"
 #include "partdist.inc.hip"
 #include "relabel.inc.hip"

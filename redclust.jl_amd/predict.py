@@ -183,8 +183,21 @@ def _sample_inputs(result_or_samples, r, p, params):
     return S, r, p, _params_dict(params)
 
 
+def _dim(points):
+    """the number of coordinates of points given as rows, None when they are not (their own check says so)"""
+    return int(np.shape(points)[1]) if points is not None and np.ndim(points) == 2 else None
+
+
+def _host_distances(Y, X, metric):
+    """the host's q×n distances: the Euclidean ones as they always were here, the other metrics by metrics.host_pairwise"""
+    if metric == "euclidean":
+        return np.sqrt(((Y[:, None, :] - X[None, :, :]) ** 2).sum(axis=2))
+    from .metrics import host_pairwise
+    return host_pairwise(Y, X, metric)
+
+
 def predict(result_or_samples, Dnew=None, *, new_points=None, points=None, r=None, p=None, params=None, seed: int = 0,
-            scores: bool = False, device: int = 0) -> Prediction:
+            scores: bool = False, device: int = 0, metric: str = "euclidean") -> Prediction:
     """Allocate new observations to the clusters of every posterior sample.
 
     result_or_samples: an MCMCResult (its clusts, r, p and params are used) or an m×n label matrix with r, p (one per
@@ -192,7 +205,9 @@ def predict(result_or_samples, Dnew=None, *, new_points=None, points=None, r=Non
     (q×n, distances of every new observation to every training observation) or new_points with the training points, one
     observation per row — the distances are then computed on the host in row chunks, so q×n never exists at once; every new
     point is quantised by itself and keyed by its own index, so the chunked result equals the unchunked one.  For many new
-    points given by coordinates use predict_points, which takes the distances and their logarithms on the device."""
+    points given by coordinates use predict_points, which takes the distances and their logarithms on the device.  metric (with
+    new_points; a name of METRICS): the distance the host evaluates, the one the training matrix was made in."""
+    _lib.check_metric(metric, _dim(points))
     S, r, p, P = _sample_inputs(result_or_samples, r, p, params)
     m, n = S.shape
     if (Dnew is None) == (new_points is None):
@@ -225,9 +240,11 @@ def predict(result_or_samples, Dnew=None, *, new_points=None, points=None, r=Non
     ms = 0.0
     for i0 in range(0, q, step):
         Yc = Y[i0:i0 + step]
-        Dc = np.sqrt(((Yc[:, None, :] - X[None, :, :]) ** 2).sum(axis=2))
+        Dc = _host_distances(Yc, X, metric)
         if not np.all(Dc > 0):
-            raise ValueError("a new point coincides with a training point: the distances must be positive")
+            raise ValueError("a new point coincides with a training point: the distances must be positive" if metric == "euclidean" else
+                             f"a {metric} distance of a new point to a training point is not positive (coincident or parallel points, "
+                             "a zero or constant vector): the distances must be positive")
         out = _lib.predict(Dc, S, r, p, P, seed=seed, point_offset=i0, Kmax=Kmax, want_scores=scores, device=device)
         labels[:, i0:i0 + step], maps[:, i0:i0 + step] = out["labels"], out["map"]
         if scores:
@@ -237,7 +254,7 @@ def predict(result_or_samples, Dnew=None, *, new_points=None, points=None, r=Non
 
 
 def predict_points(result_or_samples, points, new_points, *, relabelling=None, keep_labels=None, r=None, p=None, params=None,
-                   seed: int = 0, scores: bool = False, device: int = 0) -> Prediction:
+                   seed: int = 0, scores: bool = False, device: int = 0, metric: str = "euclidean") -> Prediction:
     """Allocate any number of new observations, given by their coordinates, to the clusters of every posterior sample
     (rc_predict_points): the distances to the n training points (one observation per row of `points`), their logarithms, the
     quantisation and the draws never leave the device, and the samples are uploaded once.  The distance is the Euclidean one,
@@ -249,7 +266,10 @@ def predict_points(result_or_samples, points, new_points, *, relabelling=None, k
     a point estimate): the prediction then carries counts and map_counts, q×(K_p+1), per new observation the number of samples
     in which it lands in each of the pivot's clusters — Prediction.allocation without the m×q labels.  keep_labels (default:
     relabelling is None): whether labels and map_labels come back; without them only the counts cross the bus, which is what
-    makes q in the millions practical.  scores needs keep_labels."""
+    makes q in the millions practical.  scores needs keep_labels.  metric (a name of METRICS): the distance, in the arithmetic
+    the header states for it — use the one the training matrix was made in (MCMCData(points, metric=...)); the default is the
+    Euclidean call as before (rc_predict_points), any other name goes through rc_predict_points_metric."""
+    _lib.check_metric(metric, _dim(points))
     S, r, p, P = _sample_inputs(result_or_samples, r, p, params)
     m, n = S.shape
     keep = (relabelling is None) if keep_labels is None else bool(keep_labels)
@@ -282,12 +302,12 @@ def predict_points(result_or_samples, points, new_points, *, relabelling=None, k
     Kmax = int(max(len(np.unique(row)) for row in S)) if scores else 0
     out = _lib.predict_points(X, Y, S, r, p, P, seed=seed, want_labels=keep, want_map=keep, maps=maps, pivot_labels=cols,
                               want_counts=maps is not None, want_mapcounts=maps is not None, Kmax=Kmax, want_scores=scores,
-                              device=device)
+                              device=device, **({} if metric == "euclidean" else dict(metric=metric)))
     return Prediction(out["labels"], out["map"], out.get("scores"), out["kernel_ms"], out["counts"], out["mapcounts"], names)
 
 
 def predict_joint(result_or_samples, Dnew=None, Dnn=None, *, new_points=None, points=None, sweeps: int = 2, r=None, p=None,
-                  params=None, seed: int = 0, device: int = 0) -> JointPrediction:
+                  params=None, seed: int = 0, device: int = 0, metric: str = "euclidean") -> JointPrediction:
     """Allocate new observations to the clusters of every posterior sample jointly: under every sample the new observations
     are allocated one after the other in the order given, each seeing the training labels and the new observations before
     it, and then visited again in `sweeps` Gibbs passes with every other new observation allocated — so a group that the
@@ -297,7 +317,9 @@ def predict_joint(result_or_samples, Dnew=None, Dnn=None, *, new_points=None, po
     symmetric, distances among the new observations; the diagonal is ignored), or new_points with the training points, one
     observation per row — both blocks are then computed on the host.  A sample's clusters and the new observations must fit
     4096 slots together (K_s + q <= 4096); allocate more observations in blocks, each block's extended_samples being the
-    next block's training samples (with its Dnew extended by the earlier blocks)."""
+    next block's training samples (with its Dnew extended by the earlier blocks).  metric (with new_points; a name of METRICS):
+    the distance the host evaluates for both blocks."""
+    _lib.check_metric(metric, _dim(points))
     S, r, p, P = _sample_inputs(result_or_samples, r, p, params)
     m, n = S.shape
     if int(sweeps) != sweeps or sweeps < 0:
@@ -337,8 +359,7 @@ def predict_joint(result_or_samples, Dnew=None, Dnn=None, *, new_points=None, po
         if not (np.all(np.isfinite(X)) and np.all(np.isfinite(Y))):
             raise ValueError("points must be finite")
         q = Y.shape[0]
-        Dnew = np.sqrt(((Y[:, None, :] - X[None, :, :]) ** 2).sum(axis=2))
-        Dnn = np.sqrt(((Y[:, None, :] - Y[None, :, :]) ** 2).sum(axis=2))
+        Dnew, Dnn = _host_distances(Y, X, metric), _host_distances(Y, Y, metric)
         if not np.all(Dnew > 0):
             raise ValueError("a new point coincides with a training point: the distances must be positive")
         if not np.all(Dnn[~np.eye(q, dtype=bool)] > 0):

@@ -185,8 +185,10 @@ def _clusterer(ctx, algo):
     return (ctx.kmeans_scan, ctx.kmeans) if algo == "k-means" else (ctx.kmedoids_scan, ctx.kmedoids)
 
 
-def _stage(kind, x, device):
-    return Context.from_points(x, device=device) if kind == "points" else Context(x, device=device)
+def _stage(kind, x, device, data=None):
+    """the context of the staged input; an MCMCData with points brings its metric"""
+    metric = data.metric if isinstance(data, MCMCData) else None
+    return Context.from_points(x, device=device, metric=metric) if kind == "points" else Context(x, device=device)
 
 
 def _partition_prior(notional, verbose, seed):
@@ -231,7 +233,7 @@ def _fitprior(data, algo, diss, Kmin, Kmax, verbose, seed, device, ctx, kmeans_b
     N, kind, x, Kmax = _prepare("fitprior", data, algo, diss, Kmin, Kmax, ctx, out, kmeans_built)
     own = ctx is None
     if own:
-        ctx = _stage(kind, x, device)
+        ctx = _stage(kind, x, device, data)
     try:
         out("Computing notional clustering.")
         scan_fn, run_fn = _clusterer(ctx, algo)
@@ -376,7 +378,7 @@ def _fitprior2(data, algo, diss, Kmin, Kmax, verbose, seed, device, ctx, kmeans_
     N, kind, x, Kmax = _prepare("fitprior2", data, algo, diss, Kmin, Kmax, ctx, out, kmeans_built)
     own = ctx is None
     if own:
-        ctx = _stage(kind, x, device)
+        ctx = _stage(kind, x, device, data)
     try:
         out("Computing notional clustering.")
         scan_fn, run_fn = _clusterer(ctx, algo)

@@ -104,7 +104,7 @@ def runsampler(data: MCMCData, options: MCMCOptionsList | None = None, params: P
     numiters, burnin, thin, numsamples = options.numiters, options.burnin, options.thin, options.numsamples
     own_ctx = ctx is None
     if own_ctx:
-        ctx = (Context.from_points(data.points, device=device, kcap=kcap) if data.points is not None
+        ctx = (Context.from_points(data.points, device=device, kcap=kcap, metric=data.metric) if data.points is not None
                else Context(data.D, device=device, kcap=kcap))
     try:
         if params is None or init is None:

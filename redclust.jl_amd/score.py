@@ -38,7 +38,7 @@ def _context(data_or_ctx, device):
         return data_or_ctx, False
     if isinstance(data_or_ctx, MCMCData):
         d = data_or_ctx
-        return (Context.from_points(d.points, device=device) if d.points is not None else Context(d.D, device=device)), True
+        return (Context.from_points(d.points, device=device, metric=d.metric) if d.points is not None else Context(d.D, device=device)), True
     return Context(np.asarray(data_or_ctx, dtype=np.float64), device=device), True
 
 

@@ -79,20 +79,34 @@ class MCMCState:
 
 class MCMCData:
     """src/types.jl:145-162.  D is stored as given; logD = log.(D - Diagonal(D) + I) is computed lazily on the
-    host only if somebody reads it — the device derives its own copy (rc_create)."""
+    host only if somebody reads it — the device derives its own copy (rc_create).
 
-    def __init__(self, D_or_points):
+    metric (points only; None: Euclidean as the reference evaluates it): a name of redclust_amd.METRICS.  The contexts made
+    from this data then hold the matrix of pairwise(points, metric=metric) (rc_create_from_points_metric), and .D on the
+    host evaluates the metric with plain NumPy: close to the device's matrix and not bit-equal to it, as the Euclidean .D is
+    not."""
+
+    def __init__(self, D_or_points, metric=None):
         x = D_or_points
         self.points = None
+        self.metric = None
         self._D = None
         self._logD = None
+        if metric is not None:
+            from ._lib import check_metric
+            check_metric(metric)
         if isinstance(x, (list, tuple)) or (isinstance(x, np.ndarray) and x.ndim == 2 and x.shape[0] != x.shape[1]):
             # points (one observation per row): the device computes the distances (rc_create_from_points); the host
             # matrix is only materialised if somebody reads .D (e.g. the split–merge step)
             self.points = np.ascontiguousarray(x, dtype=np.float64)
             if self.points.ndim != 2:
                 raise ValueError("points must be a vector of equal-length vectors")
+            if metric is not None:
+                from ._lib import check_metric
+                self.metric = check_metric(metric, self.points.shape[1])
             return
+        if metric is not None:
+            raise ValueError("metric applies to points: a square matrix is taken as the dissimilarities themselves")
         D = np.asarray(x, dtype=np.float64)
         if D.ndim != 2 or D.shape[0] != D.shape[1]:
             raise ValueError("D must be a square matrix.")
@@ -115,6 +129,9 @@ class MCMCData:
 
     @property
     def D(self):
+        if self._D is None and self.metric is not None:
+            from .metrics import host_matrix
+            self._D = host_matrix(self.points, self.metric)
         if self._D is None:  # pairwise(Euclidean(), makematrix(pnts), dims=2), types.jl:159-162
             pts = self.points
             sq = np.einsum("ij,ij->i", pts, pts)

@@ -1,6 +1,7 @@
 // rc_run_chain — the iteration loop of runsampler (/root/reference/src/mcmc.jl:533-556) as native host code around
 // the device sweep: sample_r!, sample_p!, sample_labels! (split–merge proposals + Gibbs sweep), recording rule.
-// Included at the end of redclust_hip.hip (same translation unit).
+// Included at the end of redclust_hip.hip (same translation unit); the model's host statistics it calls — loglik_host_c,
+// logprior_host, proposal_core, finish_decision — live in hostmodel.inc.hpp and read a HostModel, host_model(c).
 //
 // Why native: the loop is scalar work between kernels of ~100 µs; run from an interpreter it costs more than the
 // sweep it drives.  Here one iteration of the host side is: wait for sweep t (its K and cluster sizes arrive in
@@ -162,7 +163,7 @@ static int32_t record_finish(rc_ctx *c, Pending &R, rc_chain_outputs *out)
         }
     }
     const double ll = loglik_host(c, R.hi, R.ssize.data(), c->pinB[REC_SLOT], R.slabel.data());                    // mcmc.jl:551
-    const double lp = logprior_host(c, R.ssize.data(), R.slabel.data(), R.r, R.p, (int)R.ssize.size());   // (the sample's own slot count: the context may have narrowed since)
+    const double lp = logprior_host(host_model(c), R.ssize.data(), R.slabel.data(), R.r, R.p, (int)R.ssize.size());   // (the sample's own slot count: the context may have narrowed since)
     if (out->K) out->K[j] = R.K;
     if (out->r) out->r[j] = R.r;
     if (out->p) out->p[j] = R.p;
@@ -177,7 +178,7 @@ static int32_t record_finish(rc_ctx *c, Pending &R, rc_chain_outputs *out)
 // sweep, and it is almost always rejected.  A rejected proposal leaves the state untouched, so the loop SPECULATES that
 // every proposal of an iteration is rejected: it takes a snapshot of the state an iteration starts from (labels, slot
 // tables, block sums), launches the sweep at once and hands the proposals to a worker thread, which decides them on the
-// snapshot alone (proposal_core: no device, no context state).  Several iterations are in flight.  Iterations are
+// snapshot alone (proposal_core, hostmodel.inc.hpp: no device, no context state).  Several iterations are in flight.  Iterations are
 // confirmed in order; a sample is recorded only from confirmed iterations (labels and block sums of the following
 // snapshot).  When a proposal turns out to be accepted — or is a split, whose likelihood needs the device — the loop rolls
 // back: workers are drained, the device returns to the snapshot's labels (exact integer corrections, as
@@ -207,7 +208,7 @@ struct SpecSlot {
 
 // host part of a recorded sample (mcmc.jl:546-553), from the snapshot of the state the iteration ended in: pure function of the
 // snapshot — run by a worker (the log-likelihood's K² scalar terms are 1-2 ms of long-double arithmetic when the chain moves)
-static void spec_record_host(const rc_ctx *c, rc_ctx::LLCache &cache, const SpecSlot &after, int64_t j, double r, double p, rc_chain_outputs *out)
+static void spec_record_host(const rc_ctx *c, LLCache &cache, const SpecSlot &after, int64_t j, double r, double p, rc_chain_outputs *out)
 {
     const int nslots = (int)after.ssize.size();
     if (out->clusts) {   // sortlabels (utils.jl:69-74): relabel by order of first appearance
@@ -220,8 +221,8 @@ static void spec_record_host(const rc_ctx *c, rc_ctx::LLCache &cache, const Spec
             dst[i] = m;
         }
     }
-    const double ll = loglik_host_c(c, cache, after.hi, after.ssize.data(), after.pin_B, after.slabel.data());         // mcmc.jl:551
-    const double lp = logprior_host(c, after.ssize.data(), after.slabel.data(), r, p, nslots);
+    const double ll = loglik_host_c(host_model(c), cache, after.hi, after.ssize.data(), after.pin_B, after.slabel.data());         // mcmc.jl:551
+    const double lp = logprior_host(host_model(c), after.ssize.data(), after.slabel.data(), r, p, nslots);
     if (out->K) out->K[j] = after.K;
     if (out->r) out->r[j] = r;
     if (out->p) out->p[j] = p;
@@ -250,7 +251,7 @@ struct SpecPool {
     }
     void run()
     {
-        rc_ctx::LLCache cache;
+        LLCache cache;
         (void)hipSetDevice(c->dev);          // (the worker waits for snapshot events)
         for (;;) {
             int si = -1;
@@ -289,7 +290,7 @@ struct SpecPool {
             for (int64_t mh = 0; mh < o->numMH && clean; ++mh) {
                 ProposalSnapshot S0{s.labels.data(), s.sizes.data(), (int64_t)s.K, s.hi, s.ssize.data(), s.slabel.data(), s.pin_B};
                 ProposalResult R;
-                proposal_core(c, cache, S0, s.r, s.p, o->numGibbs, o->seed, o->first_iter + (uint64_t)(s.it - 1), (uint64_t)mh, R, false);
+                proposal_core(host_model(c), cache, S0, s.r, s.p, o->numGibbs, o->seed, o->first_iter + (uint64_t)(s.it - 1), (uint64_t)mh, R, [](int) {});
                 if (R.err != RC_OK) { s.err = R.err; s.errmsg = R.errmsg; clean = false; break; }
                 s.acc[(size_t)mh] = 0; s.spl[(size_t)mh] = R.split ? 1 : 0;
                 if (R.needs_device) { s.split_pending = true; s.pend_mh = mh; s.pend = std::move(R); clean = false; }
@@ -429,7 +430,7 @@ struct SplitScratch {
     ~SplitScratch() { if (d_bucket) (void)hipFree(d_bucket); if (d_rows) (void)hipFree(d_rows); release_out(); }   // every early return of the loop frees it
 };
 
-static int32_t spec_eval_split(rc_ctx *c, rc_ctx::LLCache &cache, SplitScratch &X, const SpecSlot &s, ProposalResult &R)
+static int32_t spec_eval_split(rc_ctx *c, LLCache &cache, SplitScratch &X, const SpecSlot &s, ProposalResult &R)
 {
     const int n = c->n, hi = s.hi;
     int f = -1;
@@ -493,7 +494,7 @@ static int32_t spec_eval_split(rc_ctx *c, rc_ctx::LLCache &cache, SplitScratch &
     std::vector<int> lab2(s.slabel.begin(), s.slabel.begin() + std::min<size_t>(s.slabel.size(), (size_t)h2));
     lab2.resize((size_t)h2, 0);
     lab2[(size_t)f] = new_label;
-    R.ll_fin = loglik_host_c(c, cache, h2, sz2.data(), B2.data(), lab2.data());
+    R.ll_fin = loglik_host_c(host_model(c), cache, h2, sz2.data(), B2.data(), lab2.data());
     return RC_OK;
 }
 
@@ -659,7 +660,7 @@ static int32_t run_chain_speculative(rc_ctx *c, const rc_chain_options *o, rc_ch
                     // the remaining proposals of the iteration see the same (unchanged) state
                     ProposalSnapshot S0{s.labels.data(), s.sizes.data(), (int64_t)s.K, s.hi, s.ssize.data(), s.slabel.data(), s.pin_B};
                     Rtmp = ProposalResult();
-                    proposal_core(c, c->llc, S0, s.r, s.p, o->numGibbs, o->seed, o->first_iter + (uint64_t)(conf - 1), (uint64_t)mh, Rtmp, false);
+                    proposal_core(host_model(c), c->llc, S0, s.r, s.p, o->numGibbs, o->seed, o->first_iter + (uint64_t)(conf - 1), (uint64_t)mh, Rtmp, [](int) {});
                     if (Rtmp.err != RC_OK) return fail(c, Rtmp.err, "%s", Rtmp.errmsg);
                     R = &Rtmp;
                 }

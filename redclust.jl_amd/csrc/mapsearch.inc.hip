@@ -11,7 +11,7 @@
 // B_D[k][k], logD's is 0; D is symmetric, so B[k][t] = B[t][k] and both are kept).  With P_k = n_k(n_k−1)/2,
 //   within(k)     = (δ1−1)·B_L[k][k]/2 − P_k·lgΓ(δ1) + lgΓ(α+δ1·P_k) − lgΓ(α) − δ1·P_k·log β − (α+δ1·P_k)·log1p(B_D[k][k]/(2β))
 //   between(k, t) = (δ2−1)·B_L[k][t] − n_k·n_t·lgΓ(δ2) + lgΓ(ζ+δ2·n_k·n_t) − lgΓ(ζ) − δ2·n_k·n_t·log γ − (ζ+δ2·n_k·n_t)·log1p(B_D[k][t]/γ)
-// (ll_within_term / ll_between_term's regrouping, in f64), between counted only with repulsion.
+// (the regrouping of ll_within_term / ll_between_term, hostmodel.inc.hpp, in f64), between counted only with repulsion.
 //
 // One visit of point i, taken out of its slot a.  (A) row i is reduced into exact per-slot sums over j != i, s_t = Σ_{j in t}
 // Dq[i][j] and l_t for Lq, with 64-bit integer LDS atomics (order-free); barrier.  (B) every occupied slot k is scored,

@@ -3,7 +3,7 @@
 // its cluster sizes and the K×K block sums of D and logD; for L labellings the matrices are still read once per chunk of
 // labellings, not once per labelling.  DESIGN.md §8 "Scoring labellings"; the contract is in include/redclust_hip.h.
 // Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK, View, rc_load_L, rc_bin_add, the
-// per-term helpers of loglik and logprior, sync_and_check, the holders and checks of hostutil.inc.hip and slab.inc.hip).
+// per-term helpers of loglik and logprior in hostmodel.inc.hpp, sync_and_check, the holders and checks of hostutil.inc.hip and slab.inc.hip).
 //
 // The block sums come out of the slab driver (slab.inc.hip): the context's rows, in the caller's order, are its rows, with the
 // dense slot of every point, rslot[s][i], from its sorted orders; RC_SCORE_WORKSPACE_KIB and RC_SCORE_ROWS_GLOBAL are its

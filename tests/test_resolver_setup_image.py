@@ -5,7 +5,6 @@ block, of another block and of the last block.  n = 96 / 257: 3 / 9 chunks of 32
 one point wide.  (The packed set-up image for the resolver's prologue, which this file was also meant for, did not move the
 prologue's time and was taken out again with its option and tests: DESIGN.md §3 "Which limit a change moves".)"""
 import os
-import re
 import shutil
 import subprocess
 import tempfile
@@ -19,6 +18,7 @@ from isa import one, resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "redclust.jl_amd", "csrc", "redclust_hip.hip")
+RESLAYOUT = os.path.join(ROOT, "redclust.jl_amd", "csrc", "reslayout.inc.hpp")
 
 
 @pytest.fixture(scope="module")
@@ -92,17 +92,13 @@ TAB_BYTES = {(64, 8192, 4, 512): 24160, (128, 8192, 4, 512): 26912, (256, 32768,
 
 
 def test_tab_bytes_did_not_grow():
-    """The resolver's dynamic LDS (tab_layout, compiled here as host code) is what it was — the announcement flag lives in a
+    """The resolver's dynamic LDS (tab_layout of csrc/reslayout.inc.hpp, compiled here as host code) is what it was — the announcement flag lives in a
     spare misc word — and the headline's tables still fit 39 KiB beside three reduction blocks."""
     cxx = shutil.which("g++") or shutil.which("c++")
     if cxx is None:
         pytest.skip("no host C++ compiler")
-    src = open(SRC).read()
-    m = re.search(r"#define RC_A16.*?\n    return o;\n}\n", src, re.S)
-    assert m, "tab_layout not found"
-    defs = "".join(re.findall(r"^#define (?:RC_PTS|RC_USED_LDS_MAX_N|RC_MAXB|RC_CPB_LDS) .*\n", src, re.M))
-    prog = ("#include <cstdio>\n#include <cstddef>\ntypedef unsigned long long u64;\nstruct double2 { double x, y; };\n"
-            "#define __host__\n#define __device__\n" + defs + m.group(0) +
+    assert '#include "reslayout.inc.hpp"' in open(SRC).read()
+    prog = ('#include <cstdio>\n#define __host__\n#define __device__\n#include "' + RESLAYOUT + '"\n'
             "int main() { size_t off[RC_TAB_NOFF];\n" +
             "".join(f'  std::printf("%zu\\n", tab_layout({k}, {n}, {nw}, off, {mb}));\n' for (k, n, nw, mb) in TAB_BYTES) + "  return 0; }\n")
     tmp = tempfile.mkdtemp(prefix="rc_tab_")

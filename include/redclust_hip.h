@@ -652,6 +652,36 @@ int32_t rc_id_search(int32_t device, const int64_t *samples /* m×n, labels 1..n
                      int32_t *best, double *kernel_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Grouped exact expected-VI search: many rc_vi_search searches over disjoint subsets of one sample set in one launch — the
+ * update step of the several-partition summary (DESIGN.md §8 "Several-partition summary").  group[s] in 0..ngroups−1 names the
+ * group of sample s, −1 leaves it out; run r searches the group run_group[r].
+ *
+ * Contract: run r — labels, loss_num, loss, sweeps, converged, moves, K — is bit for bit what rc_vi_search returns for the same
+ * init row, order row, maxK and maxsweeps on the sub-array samples[group == run_group[r]] (rows in their order).  So the factor m
+ * of the criterion, the constant and the divisor of loss are the group's, and with maxK = 0 a run's slot cap is the largest
+ * cluster count among its own group's samples.  Nothing else is defined here.
+ * best[g]: the first run of minimal loss_num among the runs of group g (0-based), −1 for a group no run searches.
+ *
+ * Checked before any device work, in this order.  RC_ERR_ARG: a NULL pointer; m, n or nruns < 1; maxsweeps < 1 or maxK < 0;
+ * ngroups < 1.  RC_ERR_CAPACITY: n > 8192; m·n >= 2^31.  RC_ERR_ARG: a group id outside −1..ngroups−1; a run_group outside
+ * 0..ngroups−1 or naming a group without samples.  RC_ERR_CAPACITY: a group with m_g·n > 2^26.  RC_ERR_ARG: a sample label
+ * outside 1..n (every sample, grouped or not).  RC_ERR_CAPACITY: a searched group's slot cap min(Kcap_g, n) > 1024; the table
+ * budget, below.  Then run by run, RC_ERR_ARG: a starting label outside 0..n, a start with more clusters than its group's cap,
+ * an order that is not a permutation.
+ * Table budget: run r keeps m_g × Lmax_g × Kcap4 cells of 2 bytes (g = run_group[r], Lmax_g the largest cluster count among
+ * group g's samples, Kcap4 the LARGEST slot cap of any searched group rounded up to a multiple of 4: the thread geometry is
+ * the launch's); the sum over the runs must not exceed rc_vi_search's 4 GiB.
+ * ------------------------------------------------------------------------------------------------------------- */
+int32_t rc_vi_search_groups(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n,
+                            const int32_t *group /* m: 0..ngroups-1, or -1 = in no group */, int32_t ngroups,
+                            int32_t nruns, const int32_t *run_group /* nruns: the group each run searches */,
+                            const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */,
+                            int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */,
+                            void *runs_out /* rc_psm_run_t[nruns] */,
+                            int32_t *best /* ngroups: first run of minimal loss_num within the group, -1 = no run */,
+                            double *kernel_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Hierarchical point estimates: agglomerative clustering of the co-clustering counts (Medvedovic's method; mcclust's
  * minbinder and mcclust.ext's minVI with method = "avg" / "comp"), the whole dendrogram in one launch, and the expected
  * loss of given labellings on the device.  DESIGN.md §8 "Hierarchical point estimates".

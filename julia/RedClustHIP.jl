@@ -1194,4 +1194,158 @@ clusterprofiles(b::HIPBackend, data::MCMCData, result::MCMCResult; points::Bool 
 
 export clusterprofiles
 
+"""
+    visearchgroups(HIPBackend(), result, group, inits, orders, rungroup; maxK = 0, maxsweeps = 100) -> info
+
+Many exact expected-VI searches in one launch (rc_vi_search_groups): run r searches all partitions for the minimum expected VI
+over the samples s of `result` with `group[s] == rungroup[r]` (groups 0-based as in the library, -1 = in no group), from the
+labels `inits[r]` (0 = unallocated) in the order `orders[r]` (a permutation of 1:n) — bit for bit rc_vi_search on that
+sub-array.  `info.best[g + 1]` is the 1-based run of least `loss_num` of group g, 0 where no run searches it.
+"""
+function visearchgroups(b::HIPBackend, result, group::AbstractVector{<:Integer}, inits::Vector{<:AbstractVector{<:Integer}},
+                        orders::Vector{<:AbstractVector{<:Integer}}, rungroup::AbstractVector{<:Integer};
+                        maxK::Integer = 0, maxsweeps::Integer = 100)
+    samples = samplematrix(result)
+    n, m = size(samples)
+    R = length(inits)
+    (length(orders) == R && length(rungroup) == R) || throw(ArgumentError("inits, orders and rungroup must have one entry per run"))
+    length(group) == m || throw(ArgumentError("group must hold one group id per sample"))
+    init = Matrix{Int64}(undef, n, R); order = Matrix{Int32}(undef, n, R)   # column r = run r: row-major R×n for the library
+    for r in 1:R
+        init[:, r] .= inits[r]; order[:, r] .= orders[r]
+    end
+    grp = Vector{Int32}(group); rg = Vector{Int32}(rungroup)
+    ngroups = max(Int(maximum(grp)) + 1, 1)
+    labels = Matrix{Int64}(undef, n, R)
+    runs = Vector{RcPsmRun}(undef, R)
+    best = fill(Int32(-1), ngroups)
+    ms = Cdouble[0]
+    rc = ccall((:rc_vi_search_groups, LIB), Int32,
+               (Int32, Ptr{Int64}, Int64, Int64, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Int32, Int32,
+                Ptr{Int64}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Cdouble}),
+               b.device, samples, m, n, grp, ngroups, R, rg, init, order, maxK, maxsweeps, labels, runs, best, ms)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return (loss = [x.loss for x in runs], loss_num = [x.loss_num for x in runs], sweeps = [Int(x.sweeps) for x in runs],
+            converged = [x.converged != 0 for x in runs], moves = [Int(x.moves) for x in runs], K = [Int(x.K) for x in runs],
+            labels = labels, best = Int.(best) .+ 1, kernel_ms = ms[1])
+end
+
+# every sample to its nearest particle (ties: the lowest index): (assignment, the samples' distances, W)
+function wasabiassign(num::Matrix{Int64})
+    L, m = size(num)
+    a = [argmin(view(num, :, s)) for s in 1:m]
+    d = [num[a[s], s] for s in 1:m]
+    return (a, d, sum(Int128.(d)))
+end
+
+# the unused sample of greatest positive distance, ties to the lowest index; 0 when there is none
+function wasabifarthest(d::Vector{Int64}, used::Set{Int})
+    best = 0
+    for s in eachindex(d)
+        (s in used || d[s] <= 0) && continue
+        (best == 0 || d[s] > d[best]) && (best = s)
+    end
+    return best
+end
+
+"""
+    wasabi(HIPBackend(), result, L; nstarts = 4, maxiter = 50, nruns = 1, maxK = 0, maxsweeps = 100, seed = 0)
+
+Summarise the samples of `result` by `L` weighted partitions that minimise the Wasserstein distance to the sample distribution
+with VI as ground metric (Balocchi & Wade's WASABI): the loop of the Python package's `wasabi` (DESIGN.md §8 "Several-partition
+summary") on `partitiondistances` and `visearchgroups` — assignment to the nearest particle, repair of empty groups by the
+farthest samples, one grouped exact-VI search per iteration, the start of least final W.  The random draws are Julia's
+(`MersenneTwister(seed)`: the `nruns` orders first, then per start the L seeding draws), not NumPy's Philox, so the two
+languages agree in law, not draw by draw.  Returns a named tuple: particles (by descending weight), weights, assignment,
+group_num, objective_num, wasserstein, trace, iterations, converged, start, starts.
+"""
+function wasabi(b::HIPBackend, result, L::Integer; nstarts::Integer = 4, maxiter::Integer = 50, nruns::Integer = 1,
+                maxK::Integer = 0, maxsweeps::Integer = 100, seed::Integer = 0)
+    (L >= 1 && nstarts >= 1 && maxiter >= 1) || throw(ArgumentError("L, nstarts and maxiter must be at least 1"))
+    S = [Vector{Int64}(c) for c in result.clusts]
+    m = length(S); n = length(S[1])
+    cap = maxK > 0 ? Int(maxK) : maximum(length(unique(c)) for c in S)
+    rng = Random.MersenneTwister(seed)
+    orders = [Vector{Int32}(Random.randperm(rng, n)) for _ in 1:nruns]
+    dist(P) = partitiondistances(b, P, result; loss = "VI")[2].num
+    runs = []
+    for t in 1:nstarts
+        # k-medoids++ on partition space
+        chosen = [rand(rng, 1:m)]
+        dmin = dist([S[chosen[1]]])[1, :]
+        for j in 2:L
+            W = sum(Int128.(dmin))
+            W == 0 && break
+            thr = (Int128(rand(rng, UInt64) >> 11) * W) >> 53
+            acc = Int128(0); idx = m
+            for s in 1:m
+                acc += dmin[s]
+                if acc > thr
+                    idx = s
+                    break
+                end
+            end
+            push!(chosen, idx)
+            dmin = min.(dmin, dist([S[idx]])[1, :])
+        end
+        P = [Vector{Int64}(RedClust.sortlabels(S[i])) for i in chosen]
+        # the iteration
+        trace = Int128[]; prev = nothing; converged = false; it = 0
+        a, d, W = wasabiassign(dist(P)); push!(trace, W)
+        while it < maxiter
+            it += 1
+            repaired = false
+            empty = [l for l in eachindex(P) if !(l in a)]
+            if !isempty(empty)
+                W == 0 && break
+                used = Set{Int}()
+                for l in empty
+                    s = wasabifarthest(d, used)
+                    s == 0 && break
+                    push!(used, s)
+                    P[l] = Vector{Int64}(RedClust.sortlabels(S[s])); repaired = true
+                end
+                if repaired
+                    a, d, W = wasabiassign(dist(P)); push!(trace, W)
+                end
+            end
+            groups = sort(unique(a))
+            inits = Vector{Int64}[]; ords = Vector{Int32}[]; rungroup = Int32[]
+            for l in groups
+                push!(inits, P[l]); push!(ords, Vector{Int32}(1:n)); push!(rungroup, l - 1)
+                for o in orders
+                    push!(inits, zeros(Int64, n)); push!(ords, o); push!(rungroup, l - 1)
+                end
+            end
+            info = visearchgroups(b, result, a .- 1, inits, ords, rungroup; maxK = cap, maxsweeps = maxsweeps)
+            changed = false
+            for l in groups
+                new = info.labels[:, info.best[l]]
+                if new != P[l]
+                    P[l] = new; changed = true
+                end
+            end
+            if !changed && !repaired && prev == a
+                converged = true
+                break
+            end
+            prev = a
+            a, d, W = wasabiassign(dist(P)); push!(trace, W)
+        end
+        push!(runs, (P = P, a = a, d = d, W = W, trace = trace, iterations = it, converged = converged || W == 0))
+    end
+    starts = [r.W for r in runs]
+    win = argmin(starts)
+    r = runs[win]
+    sizes = [count(==(l), r.a) for l in eachindex(r.P)]
+    keep = sort([l for l in eachindex(r.P) if sizes[l] > 0]; by = l -> (-sizes[l], l))
+    assignment = [findfirst(==(l), keep) for l in r.a]
+    return (particles = [r.P[l] for l in keep], weights = [sizes[l] / m for l in keep], assignment = assignment,
+            group_num = [sum(Int128.(r.d[assignment .== l])) for l in eachindex(keep)], objective_num = r.W,
+            wasserstein = Float64(r.W) / (2.0^32 * n * m), trace = r.trace, iterations = r.iterations, converged = r.converged,
+            start = win, starts = starts)
+end
+
+export visearchgroups, wasabi
+
 end # module

@@ -17,6 +17,7 @@ from .pointestimate import (getpointestimate, lossmatrix, binderloss, infodist, 
                             linkage_matrix, leaf_order, partitiondistances, expecteddistances, credibleball,
                             credibleball_from_distances, relabel, Relabelling, expectedpear, pearfraction, expectedpears,
                             searchmaxpear, maxpear, expectedari)
+from .wasabi import searchvigroups, wasabi, wasabi_scan, WasabiResult  # noqa: F401
 from .predict import predict, predict_points, Prediction, predict_joint, JointPrediction  # noqa: F401
 from .metrics import pairwise, METRICS  # noqa: F401
 from .score import scorelabellings, loglik_from_blocks, mapestimate, searchmapestimate, reweight  # noqa: F401

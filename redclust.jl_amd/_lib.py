@@ -235,6 +235,8 @@ SIGNATURES = {
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rc_id_search": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_vi_search_groups": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "rc_samples_counts": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_double)]),
     "rc_psm_search_samples": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double),
@@ -998,6 +1000,35 @@ def id_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device:
     """rc_id_search: the exact expected-ID search.  Arguments and the returned dict as vi_search; loss is the expected
     information distance (nats), loss_num the integer Q_ID."""
     return _exact_search(lib().rc_id_search, samples, init, order, maxK, maxsweeps, device)
+
+
+def vi_search_groups(samples, group, init, order, run_group, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
+    """rc_vi_search_groups: many exact expected-VI searches over disjoint groups of the samples in one launch.  samples: m×n
+    labels in 1..n; group: m group ids in 0..ngroups−1 (−1: in no group), ngroups = the largest id + 1 (at least 1); init, order:
+    as vi_search; run_group: the group each of the nruns runs searches.  Run r is vi_search's run on samples[group ==
+    run_group[r]].  Returns vi_search's dict, except that best is an int array with one entry per group: the first run of minimal
+    loss_num among the group's runs, −1 where it has none."""
+    S = _label_matrix(samples)
+    grp = np.ascontiguousarray(group, dtype=np.int32)
+    rg = np.ascontiguousarray(run_group, dtype=np.int32)
+    if grp.ndim != 1 or grp.shape[0] != S.shape[0]:
+        raise ValueError("group must hold one group id per sample")
+    init = np.ascontiguousarray(init, dtype=np.int64)
+    order = np.ascontiguousarray(order, dtype=np.int32)
+    if init.ndim != 2 or init.shape != order.shape or init.shape[1] != S.shape[1]:
+        raise ValueError("init and order must be nruns×n arrays of the same shape, n the samples' length")
+    if rg.ndim != 1 or rg.shape[0] != init.shape[0]:
+        raise ValueError("run_group must hold one group id per run")
+    (m, n), nruns = S.shape, init.shape[0]
+    ngroups = max(int(grp.max()) + 1 if m else 1, 1)
+    labels = np.zeros((max(nruns, 1), max(n, 1)), np.int64)
+    runs = (RcPsmRun * max(nruns, 1))()
+    best, ms = np.full(ngroups, -1, np.int32), C.c_double()
+    _check(lib().rc_vi_search_groups(int(device), S.ctypes.data, m, n, grp.ctypes.data, ngroups, nruns, rg.ctypes.data, init.ctypes.data,
+                                     order.ctypes.data, int(maxK), int(maxsweeps), labels.ctypes.data, runs, best.ctypes.data, C.byref(ms)))
+    out = _psm_result(labels, runs, nruns, n, C.c_int32(-1), ms)
+    out["best"] = best.astype(np.int64)
+    return out
 
 
 # rc_hclust_merge_t

@@ -7522,6 +7522,10 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "greedy.inc.hip"
 #include "samplecounts.inc.hip"
 #include "pointsearch.inc.hip"
+#include "visearch_kernel.inc.hip"   // the declarations and k_visearch<PQ, LOSS>
+#define VIS_GROUPED
+#include "visearch_kernel.inc.hip"   // the same text again: k_vigroups<PQ>
+#undef VIS_GROUPED
 #include "visearch.inc.hip"
 #include "hclust.inc.hip"
 #include "slabplan.inc.hpp"

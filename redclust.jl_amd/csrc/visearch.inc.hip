@@ -1,337 +1,20 @@
-// Exact posterior expected VI search on the device: the greedy search of greedy.inc.hip (the mechanism and tie rules
-// pointsearch.inc.hip has) for the criterion SALSO calls "VI" proper — the mean over the m samples of VI(c, sample) —
-// instead of Wade & Ghahramani's lower bound.  Included at the end of redclust_hip.hip (same translation unit: shares fail(),
-// HIPCHK, the error buffer; the holders, check_label_rows, check_lds_capacity and select_device of hostutil.inc.hip; and from
-// greedy.inc.hip the order walk, the sortable keys and the group argmin, the new-cluster candidate, and on the host the
-// shared argument checks, the staging of the runs and the result loop).  What is here: the two scores and their tables.
-//
-// Criterion (DESIGN.md §8 "Exact expected VI search"), φ(x) = x·log x:
-//   n·m·E[VI](c) = m·Σ_k φ(n_k) + Σ_s Σ_l φ(n^s_l) − 2·Σ_s Σ_{k,l} φ(N^s_kl),   N^s_kl = #{j : c_j = k, c^s_j = l}
-// in fixed point: Gq[x] = llrint((φ(x+1) − φ(x))·2^32), Φq(x) = Σ_{y<x} Gq[y], and the search minimises the integer
-//   Q(c) = m·Σ_k Φq(n_k) − 2·Σ_s Σ_kl Φq(N^s_kl).
-// With point i out of its cluster, putting it into k changes Q by exactly  Δ_k = m·Gq[n_k] − 2·Σ_s Gq[N^s[l_s(i)][k]]
-// (Δ_new = 0), so a run is a pure integer function of its inputs and every accepted move lowers Q strictly.
-//
-// One run = one workgroup of 1024 threads, persistent over its sweeps; nruns workgroups per launch.
-// Global memory, per run: the contingency tables u16 N[s][l][kpad] (kpad = Kcap rounded up to 4; a point's m rows
-// N[s][l_s(i)][·] are each contiguous over k).  Shared by the runs: the samples, re-labelled per sample to 0..L_s−1 and
-// transposed to SL[i][s], so the m labels of the visited point are contiguous.
-// A table row is covered by G = kpad/4 threads of 8 bytes (4 slots) each; thread (r, c) = (tid / G, tid % G) takes the
-// samples r, r + R, … (R = 1024 / G rows per pass) and the slots 4c..4c+3 of each.  Every table element is only ever
-// read (phase A) and written (phase C) by that one thread, so the tables need no barrier of their own.
-// A step: (A) each thread adds Gq[N] of its slots over its samples into four registers, then into the per-slot LDS
-// accumulators with 64-bit integer atomics (order-free); barrier; (B) thread k − 1 scores slot k, argmin by greedy's
-// sortable keys; barrier; (C) every thread reads the 16 partials, adds the new-cluster candidate; lab / sz are written
-// by thread 0, N[s][l][a] −= 1 and N[s][l][w] += 1 by the owners of those slots (nothing when a = w).  Two barriers per
-// step.  The next point's m sample labels are loaded into registers at the top of a step and parked in the other half
-// of an LDS double buffer behind the first barrier (m ≤ 4096; beyond that they are read from global memory in place).
-//
-// LDS (dynamic, carved at 16-byte offsets): Gq i64[n+1] (64 KiB at n = 8192; Φq at the end), acc u64[kpad], the
-// reduction partials, sz u16[Kcap+2], lab u16[n], the label double buffer u16[2][1024·PQ]: 109 024 B at the largest sizes.
-//
-// The same kernel searches the posterior expected information distance (LOSS = LOSS_ID, rc_id_search; DESIGN.md §8 "Exact
-// expected ID search"):  n·m·E[ID](c) = F(A(c)) − Σ_s Σ_kl φ(N^s_kl),  A(c) = Σ_k φ(n_k),  F(x) = Σ_s max(x, B_s),
-// B_s = Σ_l φ(n^s_l).  In fixed point Q_ID(c) = Σ_s max(Aq(c), Bq_s) − Σ_s Σ_kl Φq(N^s_kl), and with Bs the Bq_s sorted
-// ascending, Pre their prefix sums and p(x) = #{t : Bs[t] <= x}:  F(x) = x·p(x) + Pre[m] − Pre[p(x)].  Phase A is the VI
-// search's; phase B scores slot k as F(A₀ + Gq[n_k]) − F(A₀) − acc_k, A₀ = Aq without the visited point; thread 0 keeps Aq
-// (LDS) up to date in phase C under sz's discipline.  Behind the carve above: Aq, then Bs i64[m] and Pre i64[m+1] — 16·(m+1)
-// bytes with Aq — when that fits the 160 KiB, else 16 bytes for Aq and the two tables are read from global memory.
+// The host side of the exact searches (rc_vi_search, rc_id_search, rc_vi_search_groups): the launch, the fixed-point table, the
+// checks, the staging of the samples and the runs, the results.  The kernels and their arguments are visearch_kernel.inc.hip's,
+// included in front of this file.  Same translation unit as redclust_hip.hip: shares fail(), HIPCHK, the error buffer; the
+// holders, check_label_rows, check_lds_capacity and select_device of hostutil.inc.hip; and from greedy.inc.hip the shared
+// argument checks, the staging of the runs and the result loop.
 
 namespace visearch {
 
-using greedy::TPB, greedy::NWAVE, greedy::Cand, greedy::key_i64;
-constexpr int KCAP_MAX = 1024;                        // one slot per thread in phase B
-constexpr int VEC = 4;                                // slots per thread in a table row (8 bytes)
-constexpr long long MN_MAX = 1ll << 26;               // |Q| <= 2·m·n·log(n)·2^32 < 2^63
-constexpr size_t TABLE_BUDGET = (size_t)4 << 30;      // bytes of contingency tables, all runs together
-constexpr int STAGE_Q = 4;                            // labels of the next point staged in LDS while m <= 1024·STAGE_Q
-constexpr size_t LDS_MAX = 160 * 1024;                // of a gfx950 CU, all of which one workgroup may take
-constexpr int LOSS_VI = 0, LOSS_ID = 1;
-
-struct RunOut {
-    long long Q, moves;
-    int sweeps, converged, K, pad_;
-};
-
-struct Args {
-    const long long *Gq;          // n entries
-    const long long *Phi;         // n + 1 entries
-    const unsigned short *SL;     // n × m per-sample labels, 0-based
-    unsigned short *N;            // nruns × m × Lmax × kpad, zeroed
-    const unsigned short *init;   // nruns × n slots, 0 = unallocated
-    const unsigned short *sz0;    // nruns × (Kcap + 2) slot sizes of init
-    const int *K0;                // clusters of init
-    const int *order;             // nruns × n, 0-based
-    unsigned short *labels;       // nruns × n out (slots)
-    RunOut *out;
-    int n, m, Lmax, kpad, Kcap, maxsweeps;
-    // LOSS_ID only
-    const long long *Bs;          // m: the samples' Σ_l Φq(n^s_l), ascending
-    const long long *Pre;         // m + 1: Pre[p] = Σ_{t<p} Bs[t]
-    const long long *Aq0;         // nruns: Σ_k Φq(n_k) of init
-    int nbits;                    // trip count of the search for p(x): ceil(log2(m + 1))
-    int tab_lds;                  // Bs and Pre are copied to LDS behind Aq
-};
-
-__host__ __device__ inline size_t up16(size_t x) { return (x + 15) / 16 * 16; }
-
-struct Carve {
-    size_t gq, acc, red, sz, lab, stage, total;
-    __host__ __device__ Carve(int n, int kpad, int Kcap, int PQ)
-    {
-        gq = 0;
-        acc = gq + up16(8 * (size_t)(n + 1));
-        red = acc + up16(8 * (size_t)kpad);
-        sz = red + up16((size_t)NWAVE * (8 + 8 + 4 + 4 + 4));
-        lab = sz + up16(2 * (size_t)(Kcap + 2));
-        stage = lab + up16(2 * (size_t)n);
-        total = stage + up16(2 * 2 * (size_t)TPB * PQ);
-    }
-};
-
-// ID: (F(x0), F(x1)) from the sorted table, both searches in one loop of nbits trips (the same for every thread)
-template <typename P>
-__device__ inline void id_F2(P Bs, P Pre, int m, int nbits, long long x0, long long x1, long long &F0, long long &F1)
-{
-    int p0 = 0, p1 = 0;
-    for (int b = nbits - 1; b >= 0; --b) {
-        const int q0 = p0 + (1 << b), q1 = p1 + (1 << b);
-        const long long b0 = Bs[min(q0, m) - 1], b1 = Bs[min(q1, m) - 1];
-        if (q0 <= m && b0 <= x0) p0 = q0;
-        if (q1 <= m && b1 <= x1) p1 = q1;
-    }
-    const long long tot = Pre[m];
-    F0 = x0 * p0 + tot - Pre[p0];
-    F1 = x1 * p1 + tot - Pre[p1];
-}
-
-__device__ inline void add_row(const uint2 v, int ka, const long long *Gq, long long (&acc)[VEC])
-{
-    // ka: where the visited point's own slot sits in this thread's four, if it does — the point itself is out
-    const unsigned x0 = (v.x & 0xFFFFu) - (ka == 0 ? 1u : 0u), x1 = (v.x >> 16) - (ka == 1 ? 1u : 0u);
-    const unsigned x2 = (v.y & 0xFFFFu) - (ka == 2 ? 1u : 0u), x3 = (v.y >> 16) - (ka == 3 ? 1u : 0u);
-    acc[0] += Gq[x0]; acc[1] += Gq[x1]; acc[2] += Gq[x2]; acc[3] += Gq[x3];
-}
-
-template <int PQ, int LOSS>
-__global__ __launch_bounds__(TPB) void k_visearch(Args A)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char vis_lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = A.n, m = A.m, Lmax = A.Lmax, kpad = A.kpad, Kcap = A.Kcap, run = blockIdx.x;
-
-    const Carve cv(n, kpad, Kcap, PQ);
-    long long *Gq = reinterpret_cast<long long *>(vis_lds + cv.gq);
-    unsigned long long *acc = reinterpret_cast<unsigned long long *>(vis_lds + cv.acc);
-    unsigned long long *r_sc = reinterpret_cast<unsigned long long *>(vis_lds + cv.red);
-    unsigned long long *r_q = r_sc + NWAVE;
-    unsigned *r_pr = reinterpret_cast<unsigned *>(r_q + NWAVE), *r_slot = r_pr + NWAVE, *r_free = r_slot + NWAVE;
-    unsigned short *sz = reinterpret_cast<unsigned short *>(vis_lds + cv.sz);
-    unsigned short *lab = reinterpret_cast<unsigned short *>(vis_lds + cv.lab);
-    unsigned short *stage = reinterpret_cast<unsigned short *>(vis_lds + cv.stage);   // [2][TPB·PQ]
-    long long *Aq = reinterpret_cast<long long *>(vis_lds + cv.total);                // ID: Aq, Bs[m], Pre[m + 1]
-    long long *Bs_l = Aq + 1, *Pre_l = Bs_l + m;
-
-    const unsigned short *__restrict__ SL = A.SL;
-    unsigned short *Nrun = A.N + (size_t)run * m * Lmax * kpad;
-    const size_t lstride = (size_t)Lmax * kpad;                       // elements per sample
-
-    for (int x = tid; x < n; x += TPB) Gq[x] = A.Gq[x];
-    for (int k = tid; k < kpad; k += TPB) acc[k] = 0;
-    for (int k = tid; k < Kcap + 2; k += TPB) sz[k] = A.sz0[(size_t)run * (Kcap + 2) + k];
-    for (int j = tid; j < n; j += TPB) lab[j] = A.init[(size_t)run * n + j];
-    if (LOSS == LOSS_ID) {
-        if (tid == 0) Aq[0] = A.Aq0[run];
-        if (A.tab_lds) {
-            for (int s = tid; s < m; s += TPB) Bs_l[s] = A.Bs[s];
-            for (int s = tid; s <= m; s += TPB) Pre_l[s] = A.Pre[s];
-        }
-    }
-    __syncthreads();
-    int K = A.K0[run];
-    if (K) {
-        // the tables of the starting labels: one thread per sample (the only pass in which a thread writes elements
-        // it does not own; the barrier below orders it before everything else)
-        for (int s = tid; s < m; s += TPB) {
-            unsigned short *Ns = Nrun + (size_t)s * lstride;
-            for (int j = 0; j < n; ++j) {
-                const unsigned l = lab[j];
-                if (l) Ns[(size_t)SL[(size_t)j * m + s] * kpad + (l - 1)] += 1;
-            }
-        }
-    }
-
-    const int G = kpad / VEC, R = TPB / G;
-    const int r = tid / G, c = tid - r * G;
-    const bool active = r < R;
-    const greedy::Partials red{r_sc, r_pr, r_slot, r_free, nullptr};
-    greedy::Visit v(A.order + (size_t)run * n, n);
-    int buf = 0;
-    if (PQ) {
-#pragma unroll
-        for (int q = 0; q < PQ; ++q) {
-            const int s = tid + q * TPB;
-            if (s < m) stage[s] = SL[(size_t)v.i * m + s];
-        }
-    }
-    __syncthreads();
-
-    long long moves = 0;
-    int sweeps = 0, converged = 0;
-    const unsigned long long key_new = key_i64(0);
-
-    for (;;) {
-        int moved = 0;
-        for (int t = 0; t < n; ++t) {
-            // the next point's sample labels: issued now, parked in LDS behind the first barrier
-            const int i = v.i, inext = v.ahead(t);
-            unsigned short nxt[PQ ? PQ : 1];
-            if (PQ) {
-#pragma unroll
-                for (int q = 0; q < PQ; ++q) {
-                    const int s = tid + q * TPB;
-                    nxt[q] = (s < m) ? SL[(size_t)inext * m + s] : (unsigned short)0;
-                }
-            }
-            const unsigned short *cur = PQ ? stage + (size_t)buf * TPB * PQ : SL + (size_t)i * m;
-
-            const unsigned a = v.slot_of(lab);
-
-            // phase A: Σ_s Gq[N^s[l_s(i)][k]] for this thread's four slots over its samples
-            if (active) {
-                const int ka = (int)a - 1 - c * VEC;
-                const unsigned short *Nc = Nrun + (size_t)c * VEC;
-                long long part[VEC] = {0, 0, 0, 0};
-                int s = r;
-                for (; s + 3 * R < m; s += 4 * R) {
-                    const unsigned l0 = cur[s], l1 = cur[s + R], l2 = cur[s + 2 * R], l3 = cur[s + 3 * R];
-                    const uint2 v0 = *reinterpret_cast<const uint2 *>(Nc + (size_t)s * lstride + (size_t)l0 * kpad);
-                    const uint2 v1 = *reinterpret_cast<const uint2 *>(Nc + (size_t)(s + R) * lstride + (size_t)l1 * kpad);
-                    const uint2 v2 = *reinterpret_cast<const uint2 *>(Nc + (size_t)(s + 2 * R) * lstride + (size_t)l2 * kpad);
-                    const uint2 v3 = *reinterpret_cast<const uint2 *>(Nc + (size_t)(s + 3 * R) * lstride + (size_t)l3 * kpad);
-                    add_row(v0, ka, Gq, part); add_row(v1, ka, Gq, part); add_row(v2, ka, Gq, part); add_row(v3, ka, Gq, part);
-                }
-                for (; s < m; s += R) {
-                    const unsigned l0 = cur[s];
-                    add_row(*reinterpret_cast<const uint2 *>(Nc + (size_t)s * lstride + (size_t)l0 * kpad), ka, Gq, part);
-                }
-#pragma unroll
-                for (int e = 0; e < VEC; ++e)
-                    if (part[e]) atomicAdd(&acc[c * VEC + e], (unsigned long long)part[e]);
-            }
-            __syncthreads();
-
-            // phase B: score the slots (and clear their accumulators); thread k − 1 owns slot k
-            if (PQ) {
-#pragma unroll
-                for (int q = 0; q < PQ; ++q) {
-                    const int s = tid + q * TPB;
-                    if (s < m) stage[(size_t)(buf ^ 1) * TPB * PQ + s] = nxt[q];
-                }
-            }
-            const unsigned emptied = (a && sz[a] == 1) ? 1u : 0u;
-            Cand best{~0ull, ~0u, 0u, 0u};
-            unsigned minfree = ~0u;
-            if (tid < kpad) {
-                const unsigned k = (unsigned)tid + 1u;
-                const long long sum = (long long)acc[tid];
-                acc[tid] = 0;
-                if (k <= (unsigned)Kcap) {
-                    const int nk = (int)sz[k] - (k == a ? 1 : 0);
-                    long long idsc = 0;
-                    if (LOSS == LOSS_ID) {
-                        // F(A0 + Gq[n_k]) − F(A0) − acc_k; an empty slot runs the search too (nk = 0) and drops the result
-                        const long long A0 = Aq[0] - (a ? Gq[sz[a] - 1] : 0ll);
-                        long long F0, F1;
-                        if (A.tab_lds) id_F2(Bs_l, Pre_l, m, A.nbits, A0, A0 + Gq[nk], F0, F1);
-                        else id_F2(A.Bs, A.Pre, m, A.nbits, A0, A0 + Gq[nk], F0, F1);
-                        idsc = F1 - F0 - sum;
-                    }
-                    if (nk <= 0) minfree = k;
-                    else best = Cand{key_i64(LOSS == LOSS_ID ? idsc : (long long)m * Gq[nk] - 2 * sum), (k == a) ? 0u : k, k, 0u};
-                }
-            }
-            // argmin across the group (the second barrier), then the new-cluster candidate: while the cluster count is below
-            // the cap there is a free slot in 1..Kcap
-            greedy::group_argmin<false>(best, minfree, red, lane, wave);
-            const int Know = K - (int)emptied;
-            const unsigned isnew = Know < Kcap ? greedy::offer_new(best, key_new, emptied, a, minfree) : 0u;
-            const unsigned w = best.slot;
-
-            // phase C: put i into w.  A table element is touched only by the thread that reads it in phase A; lab and sz
-            // are read by the other threads only behind the next step's first barrier
-            if (a != w && active) {
-                const bool da = a && (int)(a - 1u) / VEC == c, dw = (int)(w - 1u) / VEC == c;
-                if (da || dw) {
-                    for (int s = r; s < m; s += R) {
-                        unsigned short *row = Nrun + (size_t)s * lstride + (size_t)cur[s] * kpad;
-                        if (da) row[a - 1u] = (unsigned short)(row[a - 1u] - 1u);
-                        if (dw) row[w - 1u] = (unsigned short)(row[w - 1u] + 1u);
-                    }
-                }
-            }
-            if (tid == 0) {
-                lab[i] = (unsigned short)w;
-                if (LOSS == LOSS_ID && a != w) Aq[0] += Gq[sz[w]] - (a ? Gq[sz[a] - 1] : 0ll);
-                if (a) sz[a] = (unsigned short)(sz[a] - 1);
-                sz[w] = (unsigned short)(sz[w] + 1);
-            }
-            moved += v.moved_to(a, w, inext);
-            K = Know + (int)isnew;
-            buf ^= 1;
-        }
-        ++sweeps;
-        moves += moved;
-        if (!moved) { converged = 1; break; }
-        if (sweeps >= A.maxsweeps) break;
-    }
-    __syncthreads();
-
-    // Q of the final labelling from the tables, with Φq in place of Gq
-    for (int j = tid; j < n; j += TPB) A.labels[(size_t)run * n + j] = lab[j];
-    for (int x = tid; x <= n; x += TPB) Gq[x] = A.Phi[x];
-    __syncthreads();
-    unsigned long long q = 0;
-    if (LOSS == LOSS_ID) {
-        if (tid == 0) {
-            long long F0, F1;
-            if (A.tab_lds) id_F2(Bs_l, Pre_l, m, A.nbits, Aq[0], Aq[0], F0, F1);
-            else id_F2(A.Bs, A.Pre, m, A.nbits, Aq[0], Aq[0], F0, F1);
-            q = (unsigned long long)F0;
-        }
-    } else if (tid < Kcap) q = (unsigned long long)((long long)m * Gq[sz[tid + 1]]);
-    {
-        unsigned long long t2 = 0;
-        const uint2 *N2 = reinterpret_cast<const uint2 *>(Nrun);
-        const size_t cnt = (size_t)m * lstride / VEC;
-        for (size_t x = tid; x < cnt; x += TPB) {
-            const uint2 v = N2[x];
-            t2 += (unsigned long long)Gq[v.x & 0xFFFFu] + (unsigned long long)Gq[v.x >> 16] +
-                  (unsigned long long)Gq[v.y & 0xFFFFu] + (unsigned long long)Gq[v.y >> 16];
-        }
-        q -= (LOSS == LOSS_ID ? 1 : 2) * t2;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) q += greedy::shfl_xor_u64(q, off);
-    if (lane == 0) r_q[wave] = q;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long s = 0;
-        for (int w = 0; w < NWAVE; ++w) s += r_q[w];
-        RunOut o{};
-        o.Q = (long long)s; o.moves = moves; o.sweeps = sweeps; o.converged = converged; o.K = K;
-        A.out[run] = o;
-    }
-}
-
-template <int LOSS>
+template <int LOSS, bool GROUPED = false>
 static hipError_t launch(int PQ, int nruns, size_t lds, const Args &A)
 {
 #define VIS_LAUNCH(QQ)                                                                                                    \
     do {                                                                                                                  \
-        hipError_t e = hipFuncSetAttribute((const void *)k_visearch<QQ, LOSS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        void (*kernel)(Args) = GROUPED ? k_vigroups<QQ> : k_visearch<QQ, LOSS>;                                           \
+        hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   \
         if (e != hipSuccess) return e;                                                                                    \
-        k_visearch<QQ, LOSS><<<nruns, TPB, lds, 0>>>(A);                                                                  \
+        kernel<<<nruns, TPB, lds, 0>>>(A);                                                                                \
     } while (0)
     if (PQ == 0) VIS_LAUNCH(0);
     else if (PQ == 1) VIS_LAUNCH(1);
@@ -348,6 +31,81 @@ static void gtable(int64_t n, int64_t *out)
         out[x] = (int64_t)std::llrint(std::ldexp(std::log(d + 1.0) + d * std::log1p(1.0 / d), 32));
     }
 }
+
+// the label-staging depth for the largest sample count any run of the launch sums over
+static int stage_depth(int64_t m) { return m <= TPB ? 1 : (m <= (int64_t)TPB * STAGE_Q ? STAGE_Q : 0); }
+
+// What run and run_groups do alike on the host: the tables Gq and Φq, one sample's relabelling, one run's staging, the upload
+struct Host {
+    const int64_t n;
+    std::vector<int64_t> Gq, Phi;
+    std::vector<int> map, cnt;
+
+    explicit Host(int64_t n_) : n(n_), Gq((size_t)n_), Phi((size_t)n_ + 1), map((size_t)n_ + 1), cnt((size_t)n_ + 1)
+    {
+        gtable(n, Gq.data());
+        Phi[0] = 0;
+        for (int64_t x = 0; x < n; ++x) Phi[(size_t)x + 1] = Phi[(size_t)x] + Gq[(size_t)x];
+    }
+    // one sample (labels 1..n, checked) re-labelled to 0..L−1 by first appearance into out[j·stride]; returns Σ_l Φq(n^s_l)
+    long long take_sample(const int64_t *sample, unsigned short *out, size_t stride, int &L)
+    {
+        std::fill(map.begin(), map.end(), 0);
+        std::fill(cnt.begin(), cnt.end(), 0);
+        L = 0;
+        for (int64_t j = 0; j < n; ++j) {
+            const int64_t l = sample[j];
+            if (!map[(size_t)l]) map[(size_t)l] = ++L;
+            out[(size_t)j * stride] = (unsigned short)(map[(size_t)l] - 1);
+            cnt[(size_t)map[(size_t)l]]++;
+        }
+        long long bq = 0;
+        for (int l = 1; l <= L; ++l) bq += Phi[(size_t)cnt[(size_t)l]];
+        return bq;
+    }
+    // run r into S: its labels in 0..n compacted to slots 1..K0 by first appearance (K0 <= Kcap), its order a permutation of
+    // 1..n; Aq = Σ_k Φq(n_k) of the start
+    int32_t take_run(greedy::Staging &S, const char *who, int r, const int64_t *init, const int32_t *order, int Kcap, long long &Aq)
+    {
+        int64_t row, at;
+        if (find_bad_label(init + (size_t)r * n, 1, n, 0, &row, &at))
+            return fail(nullptr, RC_ERR_ARG, "%s: label %lld of run %d outside 0..n", who, (long long)init[(size_t)r * n + at], r + 1);
+        std::fill(map.begin(), map.end(), 0);
+        int K = 0;
+        for (int64_t j = 0; j < n; ++j) {
+            const int64_t l = init[(size_t)r * n + j];
+            if (l && !map[(size_t)l]) map[(size_t)l] = ++K;
+        }
+        if (K > Kcap) return fail(nullptr, RC_ERR_ARG, "%s: run %d starts with %d clusters, more than the slot cap %d", who, r + 1, K, Kcap);
+        unsigned short *szr = S.sz_row(r);
+        for (int64_t j = 0; j < n; ++j) {
+            const int slot = map[(size_t)init[(size_t)r * n + j]];      // map[0] = 0
+            S.init_row(r)[j] = (unsigned short)slot;
+            if (slot) szr[slot]++;
+        }
+        S.K[(size_t)r] = K;
+        Aq = 0;
+        for (int k = 1; k <= K; ++k) Aq += Phi[(size_t)szr[k]];
+        return S.take_order(nullptr, who, r, order);
+    }
+    // the device copies of the tables, the transposed samples and the staged runs, and table_elems zeroed contingency cells, into A
+    hipError_t upload(DeviceBuffers &B, greedy::Staging &S, const std::vector<unsigned short> &h_SL, size_t table_elems, Args &A)
+    {
+        long long *d_G = nullptr, *d_Phi = nullptr; unsigned short *d_SL = nullptr, *d_N = nullptr;
+        hipError_t e = B.alloc(d_G, Gq.size());
+        if (e == hipSuccess) e = B.alloc(d_Phi, Phi.size());
+        if (e == hipSuccess) e = B.alloc(d_SL, h_SL.size());
+        if (e == hipSuccess) e = B.alloc(d_N, table_elems);
+        if (e == hipSuccess) e = hipMemcpy(d_G, Gq.data(), Gq.size() * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_Phi, Phi.data(), Phi.size() * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_SL, h_SL.data(), h_SL.size() * 2, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(d_N, 0, table_elems * 2);
+        if (e == hipSuccess) e = S.upload(B, 0, sizeof(RunOut));
+        A.Gq = d_G; A.Phi = d_Phi; A.SL = d_SL; A.N = d_N; A.init = S.d_init; A.sz0 = S.d_sz; A.K0 = S.d_K; A.order = S.d_order;
+        A.labels = S.d_labels; A.out = (RunOut *)S.d_out;
+        return e;
+    }
+};
 
 // The host side of rc_vi_search (loss = LOSS_VI) and rc_id_search (LOSS_ID): the same arguments, checks, staging and results
 static int32_t run(int loss, const char *who, int32_t device, const int64_t *samples, int64_t m, int64_t n, int32_t nruns,
@@ -367,26 +125,13 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
     rc = check_label_rows(nullptr, who, "sample", samples, m, n);
     if (rc != RC_OK) return rc;
     std::vector<unsigned short> h_SL((size_t)n * m);
-    std::vector<int> map((size_t)n + 1), cnt((size_t)n + 1);
-    std::vector<int64_t> Gq((size_t)n), Phi((size_t)n + 1);
-    gtable(n, Gq.data());
-    Phi[0] = 0;
-    for (int64_t x = 0; x < n; ++x) Phi[(size_t)x + 1] = Phi[(size_t)x] + Gq[(size_t)x];
+    Host H(n);
     int Lmax = 0;
     __int128 constant = 0;                                              // Σ_s Σ_l Φq(n^s_l)
     std::vector<long long> Bs(loss == LOSS_ID ? (size_t)m : 0);         // ID: the same sum per sample (Bq_s)
     for (int64_t s = 0; s < m; ++s) {
-        std::fill(map.begin(), map.end(), 0);
-        std::fill(cnt.begin(), cnt.end(), 0);
-        int L = 0;
-        for (int64_t j = 0; j < n; ++j) {
-            const int64_t l = samples[(size_t)s * n + j];
-            if (!map[(size_t)l]) map[(size_t)l] = ++L;
-            h_SL[(size_t)j * m + s] = (unsigned short)(map[(size_t)l] - 1);
-            cnt[(size_t)map[(size_t)l]]++;
-        }
-        long long bq = 0;
-        for (int l = 1; l <= L; ++l) bq += Phi[(size_t)cnt[(size_t)l]];
+        int L;
+        const long long bq = H.take_sample(samples + (size_t)s * n, h_SL.data() + s, (size_t)m, L);
         constant += bq;
         if (loss == LOSS_ID) Bs[(size_t)s] = bq;
         Lmax = std::max(Lmax, L);
@@ -406,25 +151,7 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
     greedy::Staging S(nruns, n, (size_t)Kcap + 2);
     std::vector<long long> h_Aq((size_t)nruns, 0);                      // ID: Σ_k Φq(n_k) of the start
     for (int r = 0; r < nruns; ++r) {
-        int64_t row, at;                                                // (per run: an earlier run's other errors come first)
-        if (find_bad_label(init + (size_t)r * n, 1, n, 0, &row, &at))
-            return fail(nullptr, RC_ERR_ARG, "%s: label %lld of run %d outside 0..n", who, (long long)init[(size_t)r * n + at], r + 1);
-        std::fill(map.begin(), map.end(), 0);
-        int K = 0;
-        for (int64_t j = 0; j < n; ++j) {
-            const int64_t l = init[(size_t)r * n + j];
-            if (l && !map[(size_t)l]) map[(size_t)l] = ++K;
-        }
-        if (K > Kcap) return fail(nullptr, RC_ERR_ARG, "%s: run %d starts with %d clusters, more than the slot cap %d", who, r + 1, K, Kcap);
-        unsigned short *szr = S.sz_row(r);
-        for (int64_t j = 0; j < n; ++j) {
-            const int slot = map[(size_t)init[(size_t)r * n + j]];      // map[0] = 0
-            S.init_row(r)[j] = (unsigned short)slot;
-            if (slot) szr[slot]++;
-        }
-        S.K[(size_t)r] = K;
-        for (int k = 1; k <= K; ++k) h_Aq[(size_t)r] += Phi[(size_t)szr[k]];
-        rc = S.take_order(nullptr, who, r, order);
+        rc = H.take_run(S, who, r, init, order, Kcap, h_Aq[(size_t)r]);  // (per run: an earlier run's other errors come first)
         if (rc != RC_OK) return rc;
     }
 
@@ -432,21 +159,10 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
     if (rc != RC_OK) return rc;
 
     DeviceBuffers B;
-    long long *d_G, *d_Phi; unsigned short *d_SL, *d_N;
-    HIPCHK(nullptr, B.alloc(d_G, Gq.size()));
-    HIPCHK(nullptr, B.alloc(d_Phi, Phi.size()));
-    HIPCHK(nullptr, B.alloc(d_SL, h_SL.size()));
-    HIPCHK(nullptr, B.alloc(d_N, table_elems * (size_t)nruns));
-    HIPCHK(nullptr, hipMemcpy(d_G, Gq.data(), Gq.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(nullptr, hipMemcpy(d_Phi, Phi.data(), Phi.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(nullptr, hipMemcpy(d_SL, h_SL.data(), h_SL.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(nullptr, hipMemset(d_N, 0, table_elems * 2 * (size_t)nruns));
-    HIPCHK(nullptr, S.upload(B, 0, sizeof(RunOut)));
-
     Args A{};
-    A.Gq = d_G; A.Phi = d_Phi; A.SL = d_SL; A.N = d_N; A.init = S.d_init; A.sz0 = S.d_sz; A.K0 = S.d_K; A.order = S.d_order; A.labels = S.d_labels;
-    A.out = (RunOut *)S.d_out; A.n = (int)n; A.m = (int)m; A.Lmax = Lmax; A.kpad = kpad; A.Kcap = Kcap; A.maxsweeps = maxsweeps;
-    const int PQ = m <= TPB ? 1 : (m <= (int64_t)TPB * STAGE_Q ? STAGE_Q : 0);
+    HIPCHK(nullptr, H.upload(B, S, h_SL, table_elems * (size_t)nruns, A));
+    A.n = (int)n; A.m = (int)m; A.Lmax = Lmax; A.kpad = kpad; A.Kcap = Kcap; A.maxsweeps = maxsweeps;
+    const int PQ = stage_depth(m);
     size_t lds = Carve((int)n, kpad, Kcap, PQ).total;
     if (loss == LOSS_ID) {
         // F's table: the Bq_s ascending and their prefix sums; in LDS behind Aq where that fits, else read from global memory
@@ -481,7 +197,138 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
     return RC_OK;
 }
 
+// The host side of rc_vi_search_groups: run's checks, per group where run's are per call, one staging, one upload and one launch
+// of the grouped instantiation.  Run r is rc_vi_search's run on samples[group == run_group[r]].
+static int32_t run_groups(int32_t device, const int64_t *samples, int64_t m, int64_t n, const int32_t *group, int32_t ngroups, int32_t nruns,
+                          const int32_t *run_group, const int64_t *init, const int32_t *order, int32_t maxK, int32_t maxsweeps,
+                          int64_t *labels_out, void *runs_out_, int32_t *best, double *kernel_ms)
+{
+    const char *who = "rc_vi_search_groups";
+    rc_psm_run_t *runs_out = (rc_psm_run_t *)runs_out_;
+    if (!samples || !group || !run_group) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
+    int32_t rc = greedy::check_args(nullptr, who, m, n, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best);
+    if (rc != RC_OK) return rc;
+    if (ngroups < 1) return fail(nullptr, RC_ERR_ARG, "%s: need ngroups >= 1 (got %d)", who, ngroups);
+    // the capacity in n and m·n before anything is read
+    rc = check_lds_capacity(nullptr, who, n, m);
+    if (rc != RC_OK) return rc;
+
+    // ---- the groups: their sizes, and where each sample goes in its group's block
+    std::vector<int64_t> mg((size_t)ngroups, 0), first((size_t)ngroups + 1, 0);   // first[g]: the samples in groups below g
+    std::vector<int64_t> at((size_t)m);                                           // a sample's index within its group
+    for (int64_t s = 0; s < m; ++s) {
+        const int32_t g = group[(size_t)s];
+        if (g < -1 || g >= ngroups) return fail(nullptr, RC_ERR_ARG, "%s: group %d of sample %lld outside -1..ngroups-1", who, g, (long long)s + 1);
+        if (g >= 0) at[(size_t)s] = mg[(size_t)g]++;
+    }
+    std::vector<char> searched((size_t)ngroups, 0);
+    for (int r = 0; r < nruns; ++r) {
+        const int32_t g = run_group[r];
+        if (g < 0 || g >= ngroups) return fail(nullptr, RC_ERR_ARG, "%s: group %d of run %d outside 0..ngroups-1", who, g, r + 1);
+        if (!mg[(size_t)g]) return fail(nullptr, RC_ERR_ARG, "%s: run %d searches group %d, which has no samples", who, r + 1, g);
+        searched[(size_t)g] = 1;
+    }
+    for (int g = 0; g < ngroups; ++g) {
+        if (mg[(size_t)g] > MN_MAX / n)
+            return fail(nullptr, RC_ERR_CAPACITY, "%s: m*n of group %d exceeds 2^26 = %lld (m=%lld n=%lld)", who, g, MN_MAX, (long long)mg[(size_t)g], (long long)n);
+        first[(size_t)g + 1] = first[(size_t)g] + mg[(size_t)g];
+    }
+
+    // ---- the samples, group by group: block g is n × m_g, a sample's labels as in run
+    rc = check_label_rows(nullptr, who, "sample", samples, m, n);
+    if (rc != RC_OK) return rc;
+    std::vector<unsigned short> h_SL((size_t)n * (size_t)std::max<int64_t>(first[(size_t)ngroups], 1));
+    Host H(n);
+    std::vector<int> Lmax((size_t)ngroups, 0);
+    std::vector<__int128> constant((size_t)ngroups, 0);                           // Σ_s Σ_l Φq(n^s_l) over the group
+    for (int64_t s = 0; s < m; ++s) {
+        const int32_t g = group[(size_t)s];
+        if (g < 0) continue;
+        int L;
+        constant[(size_t)g] += H.take_sample(samples + (size_t)s * n, h_SL.data() + (size_t)n * first[(size_t)g] + at[(size_t)s], (size_t)mg[(size_t)g], L);
+        Lmax[(size_t)g] = std::max(Lmax[(size_t)g], L);
+    }
+    // ---- the slot caps of the groups that are searched, always positive; the launch's geometry from the largest
+    std::vector<int> Kcap((size_t)ngroups, 0);
+    int Kcap_max = 0, Lmax_max = 0;
+    int64_t m_max = 0;
+    for (int g = 0; g < ngroups; ++g) {
+        if (!searched[(size_t)g]) continue;
+        const int64_t K64 = std::min<int64_t>(maxK > 0 ? maxK : Lmax[(size_t)g], n);
+        if (K64 > KCAP_MAX)
+            return fail(nullptr, RC_ERR_CAPACITY, "%s: the slot cap %lld of group %d (maxK, or the largest cluster count among its samples) exceeds %d", who,
+                        (long long)K64, g, KCAP_MAX);
+        Kcap[(size_t)g] = (int)K64;
+        Kcap_max = std::max(Kcap_max, (int)K64);
+        Lmax_max = std::max(Lmax_max, Lmax[(size_t)g]);
+        m_max = std::max(m_max, mg[(size_t)g]);
+    }
+    const int kpad = (Kcap_max + VEC - 1) / VEC * VEC;
+    std::vector<GroupRun> h_runs((size_t)nruns);
+    double table_elems = 0.0;                                                     // every term < 2^26 · 1024: exact in f64
+    for (int r = 0; r < nruns; ++r) {
+        const size_t g = (size_t)run_group[r];
+        GroupRun &gr = h_runs[(size_t)r];
+        gr.sl = (unsigned long long)n * (unsigned long long)first[g];
+        gr.tab = (unsigned long long)table_elems;
+        gr.m = (int)mg[g]; gr.Lmax = Lmax[g]; gr.Kcap = Kcap[g]; gr.pad_ = 0;
+        table_elems += (double)mg[g] * Lmax[g] * kpad;
+        if (table_elems * 2.0 > (double)TABLE_BUDGET)
+            return fail(nullptr, RC_ERR_CAPACITY, "%s: the contingency tables (2 B x Kcap4 x the sum over the runs of m_g x Lmax_g; Kcap4 = %d, the largest slot cap rounded up to 4) exceed the budget of %llu MiB at run %d",
+                        who, kpad, (unsigned long long)(TABLE_BUDGET >> 20), r + 1);
+    }
+
+    // ---- the runs, each against its own group's cap
+    greedy::Staging S(nruns, n, (size_t)Kcap_max + 2);
+    for (int r = 0; r < nruns; ++r) {
+        long long Aq;
+        rc = H.take_run(S, who, r, init, order, h_runs[(size_t)r].Kcap, Aq);
+        if (rc != RC_OK) return rc;
+    }
+
+    rc = select_device(who, device);
+    if (rc != RC_OK) return rc;
+
+    DeviceBuffers B;
+    Args A{};
+    HIPCHK(nullptr, H.upload(B, S, h_SL, (size_t)table_elems, A));
+    GroupRun *d_runs;
+    HIPCHK(nullptr, B.alloc(d_runs, h_runs.size()));
+    HIPCHK(nullptr, hipMemcpy(d_runs, h_runs.data(), h_runs.size() * sizeof(GroupRun), hipMemcpyHostToDevice));
+    A.runs = d_runs;
+    A.n = (int)n; A.m = (int)m_max; A.Lmax = Lmax_max; A.kpad = kpad; A.Kcap = Kcap_max; A.maxsweeps = maxsweeps;
+    const int PQ = stage_depth(m_max);
+    const size_t lds = Carve((int)n, kpad, Kcap_max, PQ).total;
+    HIPCHK(nullptr, S.begin(0));
+    HIPCHK(nullptr, (launch<LOSS_VI, true>(PQ, nruns, lds, A)));
+    std::vector<RunOut> h_out;
+    HIPCHK(nullptr, S.collect(0, h_out, kernel_ms));
+
+    // ---- results: a run's loss with its group's constant and m; per group the first run of minimal Q
+    int32_t any;
+    greedy::results(S, h_out, labels_out, runs_out, &any, [&](const RunOut &o, rc_psm_run_t &R, const int *, int) {
+        const size_t g = (size_t)run_group[&R - runs_out];
+        R.loss_num = o.Q;
+        R.loss = (double)((__int128)o.Q + constant[g]) / std::ldexp((double)n * (double)mg[g], 32);
+        return R.loss_num;
+    });
+    std::fill(best, best + ngroups, -1);
+    for (int r = 0; r < nruns; ++r) {
+        int32_t &b = best[run_group[r]];
+        if (b < 0 || runs_out[r].loss_num < runs_out[b].loss_num) b = r;
+    }
+    return RC_OK;
+}
+
 }  // namespace visearch
+
+extern "C" int32_t rc_vi_search_groups(int32_t device, const int64_t *samples, int64_t m, int64_t n, const int32_t *group, int32_t ngroups,
+                                       int32_t nruns, const int32_t *run_group, const int64_t *init, const int32_t *order, int32_t maxK,
+                                       int32_t maxsweeps, int64_t *labels_out, void *runs_out, int32_t *best, double *kernel_ms)
+{
+    return visearch::run_groups(device, samples, m, n, group, ngroups, nruns, run_group, init, order, maxK, maxsweeps, labels_out, runs_out,
+                                best, kernel_ms);
+}
 
 extern "C" int32_t rc_vi_gtable(int64_t n, int64_t *out)
 {

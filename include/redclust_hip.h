@@ -565,6 +565,28 @@ int32_t rc_psm_search_samples(int32_t device, const int64_t *samples /* m×n, la
                               int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */, void *runs_out /* rc_psm_run_t[nruns] */,
                               int32_t *best, double *kernel_ms, double *counts_ms);
 
+/* The Binder and VI-bound searches beyond the n whose whole state fits one workgroup's LDS (DESIGN.md §8 "Point-estimate
+ * search, large n"): arguments, rc_psm_run_t, run semantics, tie rules, maxK, the moved rule, labels_out and best are
+ * rc_psm_search's, and so are the results — a Binder run is the same exact integer function of its arguments, a VI run sums
+ * the same fixed-point terms, so for n <= 8192 these entries return rc_psm_search's bits.  Another kernel behind them: the
+ * slots and their sizes stay in LDS, the per-slot accumulators are a window moved over the occupied slots in passes, VI's T
+ * lives in a per-run device workspace, and a thread reads four adjacent columns of a row at a time.  They launch that kernel
+ * at every n.  Capacity: n <= 32767 (slots are 16 bits) and m·n < 2^31, RC_ERR_CAPACITY beyond, before any device work and
+ * after the RC_ERR_ARG checks, which are rc_psm_search's in its order.  The _samples and _ctx forms are what
+ * rc_psm_search_samples and rc_psm_search_ctx are to rc_psm_search.  PEAR (m·T² < 2^62 leaves m <= 15 at n = 32767), the exact
+ * VI / ID searches (m·n <= 2^26, per-run contingency tables) and the dendrogram (an n×n u64 matrix) keep their limits. */
+int32_t rc_psm_search_large(int32_t device, const void *counts /* uint32_t n×n */, int64_t m, int64_t n, int32_t loss,
+                            int32_t nruns, const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */,
+                            int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */, void *runs_out /* rc_psm_run_t[nruns] */,
+                            int32_t *best, double *kernel_ms);
+int32_t rc_psm_search_large_samples(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n, int32_t loss,
+                                    int32_t nruns, const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */,
+                                    int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */, void *runs_out /* rc_psm_run_t[nruns] */,
+                                    int32_t *best, double *kernel_ms, double *counts_ms);
+int32_t rc_psm_search_large_ctx(rc_ctx *ctx, int64_t numsamples, int32_t loss, int32_t nruns, const int64_t *init,
+                                const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out,
+                                void *runs_out /* rc_psm_run_t[nruns] */, int32_t *best, double *kernel_ms);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * PEAR search: the same greedy search over ALL partitions for the clustering of maximum posterior expected adjusted Rand
  * index in Fritsch & Ickstadt's form (mcclust's pear / maxpear, SALSO's omARI.approx) under the counts — the adjusted Rand

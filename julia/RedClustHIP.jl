@@ -334,6 +334,8 @@ expected VI and `info.loss_num` the integer criterion.
 (rc_id_search); `exact` may be either value.  Its runs are the `nruns` orders from empty labels, one from the MPEL ID sample
 and one from the result of `exact = true, loss = "VI"` with the same arguments; `info.loss` is the expected ID.
 """
+const LDS_NMAX = 8192          # the searches whose whole state sits in one workgroup's LDS; "binder" and "VI" go on to 32767
+
 struct RcPsmRun
     loss::Cdouble
     loss_num::Int64
@@ -359,6 +361,8 @@ psminfo(runs, labels, best) =
 function searchpointestimate(b::HIPBackend, result; loss::String = "VI", nruns::Integer = 16, maxK::Integer = 0,
                              maxsweeps::Integer = 100, seed::Integer = 0, exact::Bool = false)
     code = Dict("binder" => 0, "VI" => 1)
+    (loss == "ID" || exact) && length(result.clusts[1]) > LDS_NMAX &&
+        throw(ArgumentError("loss = \"ID\" and exact = true are limited to n <= $LDS_NMAX; above that only loss = \"binder\" or \"VI\" with exact = false runs, up to n = 32767"))
     loss == "ID" && return searchexactid(b, result, nruns, maxK, maxsweeps, seed)
     haskey(code, loss) || throw(ArgumentError("Invalid loss function specifier."))
     if exact
@@ -380,10 +384,17 @@ function searchpointestimate(b::HIPBackend, result; loss::String = "VI", nruns::
     labels = Matrix{Int64}(undef, n, R)
     runs = Vector{RcPsmRun}(undef, R)
     best = Int32[0]
-    rc = ccall((:rc_psm_search_samples, LIB), Int32,
-               (Int32, Ptr{Int64}, Int64, Int64, Int32, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
-                Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}),
-               b.device, samples, m, n, code[loss], R, init, order, maxK, maxsweeps, labels, runs, best, C_NULL, C_NULL)
+    rc = if n > LDS_NMAX                                         # the same search by the kernel for n <= 32767
+        ccall((:rc_psm_search_large_samples, LIB), Int32,
+              (Int32, Ptr{Int64}, Int64, Int64, Int32, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
+               Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}),
+              b.device, samples, m, n, code[loss], R, init, order, maxK, maxsweeps, labels, runs, best, C_NULL, C_NULL)
+    else
+        ccall((:rc_psm_search_samples, LIB), Int32,
+              (Int32, Ptr{Int64}, Int64, Int64, Int32, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
+               Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}),
+              b.device, samples, m, n, code[loss], R, init, order, maxK, maxsweeps, labels, runs, best, C_NULL, C_NULL)
+    end
     check(Ptr{Cvoid}(C_NULL), rc)
     return (labels[:, best[1] + 1], psminfo(runs, labels, best))
 end
@@ -418,11 +429,47 @@ function searchpointestimate(b::HIPBackend, counts::Matrix{UInt32}, numsamples::
     labels = Matrix{Int64}(undef, n, R)
     runs = Vector{RcPsmRun}(undef, R)
     best = Int32[0]
-    rc = ccall((:rc_psm_search, LIB), Int32,
-               (Int32, Ptr{Cvoid}, Int64, Int64, Int32, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
-                Ptr{Int32}, Ptr{Cdouble}),
-               b.device, counts, numsamples, n, code[loss], R, inits, order, maxK, maxsweeps, labels, runs, best, C_NULL)
+    rc = if n > LDS_NMAX
+        ccall((:rc_psm_search_large, LIB), Int32,
+              (Int32, Ptr{Cvoid}, Int64, Int64, Int32, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
+               Ptr{Int32}, Ptr{Cdouble}),
+              b.device, counts, numsamples, n, code[loss], R, inits, order, maxK, maxsweeps, labels, runs, best, C_NULL)
+    else
+        ccall((:rc_psm_search, LIB), Int32,
+              (Int32, Ptr{Cvoid}, Int64, Int64, Int32, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
+               Ptr{Int32}, Ptr{Cdouble}),
+              b.device, counts, numsamples, n, code[loss], R, inits, order, maxK, maxsweeps, labels, runs, best, C_NULL)
+    end
     check(Ptr{Cvoid}(C_NULL), rc)
+    return (labels[:, best[1] + 1], psminfo(runs, labels, best))
+end
+
+"""
+    searchpointestimate(HIPBackend(), ctx, numsamples, n; loss = "VI", nruns = 16, maxK = 0, maxsweeps = 100, seed = 0)
+
+The same search on the device counts of a live context `ctx` (the handle of `rc_create`, with `numsamples` recorded samples of
+`n` points), read in place (rc_psm_search_large_ctx: the kernel for n <= 32767, which returns rc_psm_search_ctx's results at every n).
+Runs: `nruns` from empty labels in random point orders.
+"""
+function searchpointestimate(b::HIPBackend, ctx::Ptr{Cvoid}, numsamples::Integer, n::Integer; loss::String = "VI",
+                             nruns::Integer = 16, maxK::Integer = 0, maxsweeps::Integer = 100, seed::Integer = 0)
+    code = Dict("binder" => 0, "VI" => 1)
+    haskey(code, loss) || throw(ArgumentError("Invalid loss function specifier."))
+    R = Int(nruns)
+    R >= 1 || throw(ArgumentError("no run: nruns = 0"))
+    inits = zeros(Int64, n, R)
+    order = Matrix{Int32}(undef, n, R)
+    rng = Random.MersenneTwister(seed)
+    for r in 1:R
+        order[:, r] .= Random.randperm(rng, n)
+    end
+    labels = Matrix{Int64}(undef, n, R)
+    runs = Vector{RcPsmRun}(undef, R)
+    best = Int32[0]
+    rc = ccall((:rc_psm_search_large_ctx, LIB), Int32,
+               (Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Cdouble}),
+               ctx, numsamples, code[loss], R, inits, order, maxK, maxsweeps, labels, runs, best, C_NULL)
+    check(ctx, rc)
     return (labels[:, best[1] + 1], psminfo(runs, labels, best))
 end
 

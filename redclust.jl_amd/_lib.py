@@ -223,6 +223,13 @@ SIGNATURES = {
                                   C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rc_psm_search_ctx": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_psm_search_large": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_psm_search_large_ctx": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                            C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_psm_search_large_samples": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
+                                                C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rc_pear_search": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                    C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rc_pear_search_ctx": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
@@ -923,11 +930,11 @@ def _counts_form(family, counts, numsamples, ctx, samples, device, n=None, what=
     return getattr(L, f"rc_{family}"), (int(device), cnt.ctypes.data_as(C.c_void_p), int(numsamples), cnt.shape[0]), None, cnt.shape[0], False
 
 
-def _psm_search(counts, numsamples, ctx, samples, loss, init, order, maxK, maxsweeps, device) -> dict:
+def _psm_search(counts, numsamples, ctx, samples, loss, init, order, maxK, maxsweeps, device, large=False) -> dict:
     """psm_search and psm_search_samples (samples: the label matrix) behind their parameter lists; loss None: the PEAR
-    search's three entry points, which have the same lists without the loss"""
+    search's three entry points, which have the same lists without the loss; large: rc_psm_search_large*, likewise"""
     cms = C.c_double()
-    family, crit, record = ("pear_search", [], RcPearRun) if loss is None else ("psm_search", [int(loss)], RcPsmRun)
+    family, crit, record = ("pear_search", [], RcPearRun) if loss is None else ("psm_search_large" if large else "psm_search", [int(loss)], RcPsmRun)
 
     def call(n, *tail):
         fn, head, handle, _, timed = _counts_form(family, counts, numsamples, ctx, samples, device, n, "init")
@@ -959,6 +966,17 @@ def psm_search_samples(samples, loss: int, init, order, maxK: int = 0, maxsweeps
     """rc_psm_search_samples: psm_search on the counts of an m×n int64 label matrix (labels 1..n), which are built on the
     device and stay there.  Returns psm_search's dict and counts_ms, the device time of the counts kernel."""
     return _psm_search(None, None, None, _label_matrix(samples), loss, init, order, maxK, maxsweeps, device)
+
+
+def psm_search_large(counts, numsamples: int, loss: int, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0, ctx=None):
+    """rc_psm_search_large or, with ctx, rc_psm_search_large_ctx: psm_search — arguments, results, bits — by the kernel whose
+    capacity is n <= 32767 (csrc/pointsearch_large.inc.hip), at every n."""
+    return _psm_search(counts, numsamples, ctx, None, loss, init, order, maxK, maxsweeps, device, large=True)
+
+
+def psm_search_large_samples(samples, loss: int, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
+    """rc_psm_search_large_samples: psm_search_samples by the large-n kernel."""
+    return _psm_search(None, None, None, _label_matrix(samples), loss, init, order, maxK, maxsweeps, device, large=True)
 
 
 def pear_search(counts, numsamples: int, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0, ctx=None):

@@ -356,17 +356,11 @@ static hipError_t launch(int Q, int nruns, size_t lds, hipStream_t st, const Arg
     return hipGetLastError();
 }
 
-// Everything behind the three entry points.  c may be NULL (errors then go to the thread's buffer); dC is the device
-// count matrix (n × ld, ld a multiple of 4, rows 16-byte aligned), read in place.
-// loss: RC_PSM_BINDER, RC_PSM_VILB (runs_out: rc_psm_run_t[nruns]) or LOSS_PEAR (runs_out: rc_pear_run_t[nruns]).
-static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, int64_t m, int64_t n, int32_t loss, int32_t nruns,
-                   const int64_t *init, const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out,
-                   void *runs_out, int32_t *best, double *kernel_ms)
+// The caller's runs into S, shared with pointsearch_large.inc.hip: labels in 0..n, orders permutations of 1..n, cluster counts
+// within maxK (the slots are the caller's labels; hi: the highest one in use)
+static int32_t stage_runs(rc_ctx *c, greedy::Staging &S, std::vector<int> &h_hi, int64_t n, int32_t nruns, const int64_t *init,
+                          const int32_t *order, int32_t maxK)
 {
-    // ---- the caller's runs: labels in 0..n, orders permutations of 1..n, cluster counts within maxK
-    // (the slots are the caller's labels; hi: the highest one in use)
-    greedy::Staging S(nruns, n, (size_t)n + 2);
-    std::vector<int> h_hi((size_t)nruns);
     for (int r = 0; r < nruns; ++r) {
         unsigned short *szr = S.sz_row(r);
         int K = 0, hi = 0;
@@ -381,6 +375,41 @@ static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, in
         const int32_t orc = S.take_order(c, "point search", r, order);
         if (orc != RC_OK) return orc;
     }
+    return RC_OK;
+}
+
+// A run's losses from the kernel's record, for greedy::results (shared with pointsearch_large.inc.hip); the best run is the first of
+// minimal loss
+struct Losses {
+    bool vi;
+    int64_t m, n;
+    double operator()(const RunOut &o, rc_psm_run_t &R, const int *cnt, int K) const
+    {
+        const long long pairs = (long long)n * (n - 1) / 2;
+        if (vi) {
+            R.loss_num = 0;
+            R.loss = o.f / (double)n + 2.0 * std::log((double)m);
+        } else {
+            long long within = 0;
+            for (int k = 1; k <= K; ++k) within += (long long)cnt[k] * (cnt[k] - 1) / 2;
+            R.loss_num = o.tot + (long long)m * within - 2 * o.same;
+            R.loss = pairs ? (double)R.loss_num / (double)((long long)m * pairs) : 0.0;
+        }
+        return R.loss;
+    }
+};
+
+// Everything behind the three entry points.  c may be NULL (errors then go to the thread's buffer); dC is the device
+// count matrix (n × ld, ld a multiple of 4, rows 16-byte aligned), read in place.
+// loss: RC_PSM_BINDER, RC_PSM_VILB (runs_out: rc_psm_run_t[nruns]) or LOSS_PEAR (runs_out: rc_pear_run_t[nruns]).
+static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, int64_t m, int64_t n, int32_t loss, int32_t nruns,
+                   const int64_t *init, const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out,
+                   void *runs_out, int32_t *best, double *kernel_ms)
+{
+    greedy::Staging S(nruns, n, (size_t)n + 2);
+    std::vector<int> h_hi((size_t)nruns);
+    const int32_t src = stage_runs(c, S, h_hi, n, nruns, init, order, maxK);
+    if (src != RC_OK) return src;
     // ---- the counts: symmetric, diagonal m, nothing above m
     const int32_t crc = check_counts(c, st, "point search", dC, ld, m, n);
     if (crc != RC_OK) return crc;
@@ -424,19 +453,8 @@ static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, in
         });
         return RC_OK;
     }
-    // ---- results: the losses; the best run is the first of minimal loss
-    greedy::results(S, h_out, labels_out, (rc_psm_run_t *)runs_out, best, [&](const RunOut &o, rc_psm_run_t &R, const int *cnt, int K) {
-        if (vi) {
-            R.loss_num = 0;
-            R.loss = o.f / (double)n + 2.0 * std::log((double)m);
-        } else {
-            long long within = 0;
-            for (int k = 1; k <= K; ++k) within += (long long)cnt[k] * (cnt[k] - 1) / 2;
-            R.loss_num = o.tot + (long long)m * within - 2 * o.same;
-            R.loss = pairs ? (double)R.loss_num / (double)((long long)m * pairs) : 0.0;
-        }
-        return R.loss;
-    });
+    // ---- results: the losses
+    greedy::results(S, h_out, labels_out, (rc_psm_run_t *)runs_out, best, Losses{vi, m, n});
     return RC_OK;
 }
 

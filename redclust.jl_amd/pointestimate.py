@@ -60,6 +60,14 @@ def getpointestimate(samples, method: str = "MAP", loss="VI", device: int = 0):
 
 
 _PSM_LOSSES = {"binder": 0, "VI": 1}   # RC_PSM_BINDER, RC_PSM_VILB
+_LDS_NMAX = 8192                       # the searches whose whole state sits in one workgroup's LDS (hostutil.inc.hip LDS_NMAX)
+
+
+def _check_lds_n(n, what):
+    """Above 8192 points only searchpointestimate's "binder" and "VI" bound have a kernel (rc_psm_search_large*)."""
+    if n > _LDS_NMAX:
+        raise ValueError(f'{what} is limited to n <= {_LDS_NMAX} (got n = {n}); above that only '
+                         'searchpointestimate(loss="binder" or "VI", exact=False) runs, up to n = 32767')
 
 
 def cocluster_counts(clusts) -> np.ndarray:
@@ -223,6 +231,7 @@ def _exact_search(samples, loss, nruns, maxK, maxsweeps, seed, init, device):
     with the key its info is kept under."""
     search, key = (_lib.id_search, "vi") if loss == "ID" else (_lib.vi_search, "lower_bound")
     S = _sample_matrix(samples)
+    _check_lds_n(S.shape[1], 'searchpointestimate(loss="ID")' if loss == "ID" else "searchpointestimate(exact=True)")
     start, prior = searchpointestimate(samples, "VI", nruns=nruns, maxK=maxK, maxsweeps=maxsweeps, seed=seed, init=init, device=device,
                                        exact=loss == "ID")
     inits, orders = _search_starts(S.shape[1], nruns, seed, init, samples, loss, start, device)
@@ -291,10 +300,12 @@ def searchpointestimate(samples_or_counts=None, loss="VI", *, nruns: int = 16, m
     S, counts, numsamples, n = _counts_input(samples_or_counts, numsamples, ctx)
     samples = None if S is None else samples_or_counts                  # the counts are built from S on the device
     inits, orders = _search_starts(n, nruns, seed, init, samples, "binder" if loss == "binder" else "VI", device=device)
+    # above 8192 points: the kernel that keeps only the slots in LDS (rc_psm_search_large*); the same search, n <= 32767
+    by_samples, by_counts = (_lib.psm_search_large_samples, _lib.psm_search_large) if n > _LDS_NMAX else (_lib.psm_search_samples, _lib.psm_search)
     if samples is not None:
-        res = _lib.psm_search_samples(S, _PSM_LOSSES[loss], inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device)
+        res = by_samples(S, _PSM_LOSSES[loss], inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device)
     else:
-        res = _lib.psm_search(counts, numsamples, _PSM_LOSSES[loss], inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device, ctx=ctx)
+        res = by_counts(counts, numsamples, _PSM_LOSSES[loss], inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device, ctx=ctx)
     info = {k: res[k] for k in _INFO_KEYS}
     if samples is not None:
         info["counts_ms"] = res["counts_ms"]
@@ -350,7 +361,8 @@ def hclust(samples_or_counts=None, linkage="average", *, numsamples=None, ctx=No
     order (leaf_order(Z)), kernel_ms.  There is no CPU fallback."""
     if linkage not in _LINKAGES:
         raise ValueError("Invalid linkage specifier.")
-    S, counts, m, _ = _counts_input(samples_or_counts, numsamples, ctx)
+    S, counts, m, n = _counts_input(samples_or_counts, numsamples, ctx)
+    _check_lds_n(n, "hclust")
     res = _lib.hclust(counts, m, _LINKAGES[linkage], device=device, ctx=ctx, samples=S)
     Z = linkage_matrix(res["merges"], m, linkage)
     out = dict(merges=res["merges"], binder_num=res["binder_num"], Z=Z, order=leaf_order(Z), kernel_ms=res["kernel_ms"])
@@ -370,6 +382,7 @@ def _hclust_cuts(samples_or_counts, linkage, maxK, numsamples, ctx, device, *, l
     if exact and not hasattr(samples_or_counts, "clusts"):
         raise ValueError("exact=True needs the samples (an MCMCResult), not a count matrix")
     S, counts, m, n = _counts_input(samples_or_counts, numsamples, ctx)
+    _check_lds_n(n, "hclustpointestimate")
     maxK = int(maxK) if maxK else max(-(-n // 8), min(n, lo))
     if not lo <= maxK <= n:
         raise ValueError("maxK must lie in 1..n" if lo == 1 else "maxK must lie in 2..n with criterion='silhouette'")
@@ -589,6 +602,7 @@ def searchmaxpear(samples_or_counts=None, *, nruns: int = 16, maxK: int = 0, max
     Returns (clust, info): the best labelling (sortlabels'd) and a dict with the per-run pear, num, den, sweeps, converged,
     moves, K, all labellings (labels), best (the first run of maximal num/den), kernel_ms, and counts_ms for an MCMCResult."""
     S, counts, m, n = _counts_input(samples_or_counts, numsamples, ctx)
+    _check_lds_n(n, "searchmaxpear")
     starts = [] if init is None else list(np.atleast_2d(np.asarray(init)))
     if S is not None:
         _, _, dnum, dden = _pear_draws(samples_or_counts, device)

@@ -4,6 +4,8 @@
     python tools/time_pointsearch.py                  # n = 2000 and 8192, both losses, 16 runs, median of 5 repetitions
     python tools/time_pointsearch.py --n 2000 --reps 7
     python tools/time_pointsearch.py --no-ref         # skip the NumPy restatement
+    python tools/time_pointsearch.py --large          # the large-n kernel (csrc/pointsearch_large.inc.hip): n = 8192 beside
+                                                      # rc_psm_search on the same counts, then n = 16384 and 32767 alone
 
 Inputs: a planted partition with K = 50 clusters, 20 % of the points relabelled at random in each of m = 1000 samples
 (seed 0); the counts are Σ_s adjacency(sample_s), formed as one-hot products (on the device through torch when it is
@@ -50,6 +52,34 @@ def planted_counts(n, m, K, noise, seed=0):
     return acc.cpu().numpy().astype(np.uint32)
 
 
+def time_large(a):
+    """rc_psm_search_large from empty labels in the Philox orders of searchpointestimate; at n <= 8192 rc_psm_search beside it on
+    the same counts, alternating, with the ratio of the kernel medians"""
+    from redclust_amd import _lib
+    for n in (a.n if a.n != [2000, 8192] else [8192, 16384, 32767]):
+        C = planted_counts(n, a.m, a.K, a.noise)
+        rng = np.random.Generator(np.random.Philox(key=0))
+        order = np.stack([rng.permutation(n).astype(np.int32) + 1 for _ in range(a.nruns)])
+        init = np.zeros((a.nruns, n), np.int64)
+        for loss, code in (("binder", 0), ("VI", 1)):
+            entries = dict(large=_lib.psm_search_large, **(dict(lds=_lib.psm_search) if n <= 8192 else {}))
+            kms, res = {k: [] for k in entries}, {}
+            for _ in range(a.reps + 1):                                             # the first repetition warms up
+                for k, fn in entries.items():
+                    res[k] = fn(C, a.m, code, init, order)
+                    kms[k].append(res[k]["kernel_ms"])
+            med = {k: statistics.median(v[1:]) for k, v in kms.items()}
+            for k in entries:
+                sw = res[k]["sweeps"]
+                print(json.dumps(dict(what=k, n=n, m=a.m, loss=loss, nruns=a.nruns, reps=a.reps, kernel_ms_median=round(med[k], 3),
+                                      kernel_ms_min=round(min(kms[k][1:]), 3), kernel_ms_max=round(max(kms[k][1:]), 3),
+                                      sweeps=[int(x) for x in sw], K=[int(x) for x in res[k]["K"]],
+                                      us_per_step=round(1e3 * med[k] / (n * int(sw.max())), 3))), flush=True)
+            if "lds" in entries:
+                same = all(res["large"][k].tobytes() == res["lds"][k].tobytes() for k in ("labels", "loss", "sweeps", "moves"))
+                print(json.dumps(dict(what="large/lds", n=n, loss=loss, ratio=round(med["large"] / med["lds"], 3), same_runs=same)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="*", default=[2000, 8192])
@@ -59,10 +89,13 @@ def main():
     ap.add_argument("--nruns", type=int, default=16)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-ref", action="store_true")
+    ap.add_argument("--large", action="store_true")
     a = ap.parse_args()
     warm = planted_counts(64, 5, 3, 0.1)
     for loss in ("binder", "VI"):
         rc.searchpointestimate(warm, loss, numsamples=5, nruns=2)                   # module load, first launches
+    if a.large:
+        return time_large(a)
     for n in a.n:
         t0 = time.perf_counter()
         C = planted_counts(n, a.m, a.K, a.noise)

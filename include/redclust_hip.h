@@ -704,6 +704,30 @@ int32_t rc_vi_search_groups(int32_t device, const int64_t *samples /* m×n, labe
                             double *kernel_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * The exact expected-VI search and its grouped form beyond n = 8192 (DESIGN.md §8 "Exact expected VI search, large n"):
+ * rc_vi_search's and rc_vi_search_groups' arguments, checks in their order, messages (under these names), run semantics and
+ * results — a run is the same integer function of its arguments, so wherever both run these entries return the others' bytes.
+ * Another kernel behind them: the run's labels live in its row of the output in global memory, the workgroup's LDS holds the low
+ * 32 bits of rc_vi_gtable's table, and the high word is counted from at most 11 thresholds read off that table.  They launch that
+ * kernel at every n.  Capacity: n <= 32767 in place of n <= 8192 — RC_ERR_CAPACITY with "32767" in the message, at the
+ * same place in the order of the checks; the grouped entry's m·n < 2^31, m·n <= 2^26 (per group in the grouped form), the slot cap
+ * <= 1024 and the 4 GiB table budget are unchanged.  RC_ERR_STATE: the table could not be split (an internal error: it is not
+ * non-decreasing below 12·2^32) — never a wrong answer.  rc_id_search keeps n <= 8192.
+ * ------------------------------------------------------------------------------------------------------------- */
+int32_t rc_vi_search_large(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n, int32_t nruns,
+                           const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */,
+                           int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */, void *runs_out /* rc_psm_run_t[nruns] */,
+                           int32_t *best, double *kernel_ms);
+int32_t rc_vi_search_groups_large(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n,
+                                  const int32_t *group /* m: 0..ngroups-1, or -1 = in no group */, int32_t ngroups,
+                                  int32_t nruns, const int32_t *run_group /* nruns: the group each run searches */,
+                                  const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */,
+                                  int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */,
+                                  void *runs_out /* rc_psm_run_t[nruns] */,
+                                  int32_t *best /* ngroups: first run of minimal loss_num within the group, -1 = no run */,
+                                  double *kernel_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Hierarchical point estimates: agglomerative clustering of the co-clustering counts (Medvedovic's method; mcclust's
  * minbinder and mcclust.ext's minVI with method = "avg" / "comp"), the whole dendrogram in one launch, and the expected
  * loss of given labellings on the device.  DESIGN.md §8 "Hierarchical point estimates".

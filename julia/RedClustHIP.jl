@@ -513,16 +513,35 @@ function searchexactvi(b::HIPBackend, result, nruns::Integer, maxK::Integer, max
     labels = Matrix{Int64}(undef, n, R)
     runs = Vector{RcPsmRun}(undef, R)
     best = Int32[0]
-    rc = ccall((:rc_vi_search, LIB), Int32,
-               (Int32, Ptr{Int64}, Int64, Int64, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
-                Ptr{Int32}, Ptr{Cdouble}),
-               b.device, samples, m, n, R, init, order, cap, maxsweeps, labels, runs, best, C_NULL)
+    rc = if n > LDS_NMAX                                         # the same search by the kernel for n <= 32767 (searchvi)
+        ccall((:rc_vi_search_large, LIB), Int32,
+              (Int32, Ptr{Int64}, Int64, Int64, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
+               Ptr{Int32}, Ptr{Cdouble}),
+              b.device, samples, m, n, R, init, order, cap, maxsweeps, labels, runs, best, C_NULL)
+    else
+        ccall((:rc_vi_search, LIB), Int32,
+              (Int32, Ptr{Int64}, Int64, Int64, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
+               Ptr{Int32}, Ptr{Cdouble}),
+              b.device, samples, m, n, R, init, order, cap, maxsweeps, labels, runs, best, C_NULL)
+    end
     check(Ptr{Cvoid}(C_NULL), rc)
     info = (loss = [x.loss for x in runs], loss_num = [x.loss_num for x in runs], sweeps = [Int(x.sweeps) for x in runs],
             converged = [x.converged != 0 for x in runs], moves = [Int(x.moves) for x in runs], K = [Int(x.K) for x in runs],
             labels = labels, best = Int(best[1]) + 1)
     return (labels[:, best[1] + 1], info)
 end
+
+"""
+    searchvi(HIPBackend(), result; nruns = 16, maxK = 0, maxsweeps = 100, seed = 0) -> (clust, info)
+
+The exact expected-VI search at any n <= 32767: `searchpointestimate(…; loss = "VI", exact = true)` — its runs, its results, its
+bytes up to n = 8192 — and above that the same search by rc_vi_search_large, with the lower-bound start from
+rc_psm_search_large_samples.
+"""
+searchvi(b::HIPBackend, result; nruns::Integer = 16, maxK::Integer = 0, maxsweeps::Integer = 100, seed::Integer = 0) =
+    searchexactvi(b, result, nruns, maxK, maxsweeps, seed)
+
+export searchvi
 
 function searchexactid(b::HIPBackend, result, nruns::Integer, maxK::Integer, maxsweeps::Integer, seed::Integer)
     samples = samplematrix(result)
@@ -1244,7 +1263,7 @@ export clusterprofiles
 """
     visearchgroups(HIPBackend(), result, group, inits, orders, rungroup; maxK = 0, maxsweeps = 100) -> info
 
-Many exact expected-VI searches in one launch (rc_vi_search_groups): run r searches all partitions for the minimum expected VI
+Many exact expected-VI searches in one launch (rc_vi_search_groups; above n = 8192 rc_vi_search_groups_large, n <= 32767): run r searches all partitions for the minimum expected VI
 over the samples s of `result` with `group[s] == rungroup[r]` (groups 0-based as in the library, -1 = in no group), from the
 labels `inits[r]` (0 = unallocated) in the order `orders[r]` (a permutation of 1:n) — bit for bit rc_vi_search on that
 sub-array.  `info.best[g + 1]` is the 1-based run of least `loss_num` of group g, 0 where no run searches it.
@@ -1267,10 +1286,17 @@ function visearchgroups(b::HIPBackend, result, group::AbstractVector{<:Integer},
     runs = Vector{RcPsmRun}(undef, R)
     best = fill(Int32(-1), ngroups)
     ms = Cdouble[0]
-    rc = ccall((:rc_vi_search_groups, LIB), Int32,
-               (Int32, Ptr{Int64}, Int64, Int64, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Int32, Int32,
-                Ptr{Int64}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Cdouble}),
-               b.device, samples, m, n, grp, ngroups, R, rg, init, order, maxK, maxsweeps, labels, runs, best, ms)
+    rc = if n > LDS_NMAX                                         # the same searches by the kernel for n <= 32767
+        ccall((:rc_vi_search_groups_large, LIB), Int32,
+              (Int32, Ptr{Int64}, Int64, Int64, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Int32, Int32,
+               Ptr{Int64}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Cdouble}),
+              b.device, samples, m, n, grp, ngroups, R, rg, init, order, maxK, maxsweeps, labels, runs, best, ms)
+    else
+        ccall((:rc_vi_search_groups, LIB), Int32,
+              (Int32, Ptr{Int64}, Int64, Int64, Ptr{Int32}, Int32, Int32, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Int32, Int32,
+               Ptr{Int64}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Cdouble}),
+              b.device, samples, m, n, grp, ngroups, R, rg, init, order, maxK, maxsweeps, labels, runs, best, ms)
+    end
     check(Ptr{Cvoid}(C_NULL), rc)
     return (loss = [x.loss for x in runs], loss_num = [x.loss_num for x in runs], sweeps = [Int(x.sweeps) for x in runs],
             converged = [x.converged != 0 for x in runs], moves = [Int(x.moves) for x in runs], K = [Int(x.K) for x in runs],

@@ -244,6 +244,11 @@ SIGNATURES = {
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rc_vi_search_groups": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "rc_vi_search_large": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_vi_search_groups_large": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_double)]),
     "rc_samples_counts": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_double)]),
     "rc_psm_search_samples": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double),
@@ -1014,18 +1019,24 @@ def vi_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device:
     return _exact_search(lib().rc_vi_search, samples, init, order, maxK, maxsweeps, device)
 
 
+def vi_search_large(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
+    """rc_vi_search_large: vi_search — arguments, results, bits — by the kernel whose capacity is n <= 32767
+    (csrc/visearch_large.inc.hip), at every n."""
+    return _exact_search(lib().rc_vi_search_large, samples, init, order, maxK, maxsweeps, device)
+
+
 def id_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
     """rc_id_search: the exact expected-ID search.  Arguments and the returned dict as vi_search; loss is the expected
     information distance (nats), loss_num the integer Q_ID."""
     return _exact_search(lib().rc_id_search, samples, init, order, maxK, maxsweeps, device)
 
 
-def vi_search_groups(samples, group, init, order, run_group, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
+def vi_search_groups(samples, group, init, order, run_group, maxK: int = 0, maxsweeps: int = 100, device: int = 0, large: bool = False):
     """rc_vi_search_groups: many exact expected-VI searches over disjoint groups of the samples in one launch.  samples: m×n
     labels in 1..n; group: m group ids in 0..ngroups−1 (−1: in no group), ngroups = the largest id + 1 (at least 1); init, order:
     as vi_search; run_group: the group each of the nruns runs searches.  Run r is vi_search's run on samples[group ==
     run_group[r]].  Returns vi_search's dict, except that best is an int array with one entry per group: the first run of minimal
-    loss_num among the group's runs, −1 where it has none."""
+    loss_num among the group's runs, −1 where it has none.  large: rc_vi_search_groups_large, the same by the large-n kernel."""
     S = _label_matrix(samples)
     grp = np.ascontiguousarray(group, dtype=np.int32)
     rg = np.ascontiguousarray(run_group, dtype=np.int32)
@@ -1042,11 +1053,17 @@ def vi_search_groups(samples, group, init, order, run_group, maxK: int = 0, maxs
     labels = np.zeros((max(nruns, 1), max(n, 1)), np.int64)
     runs = (RcPsmRun * max(nruns, 1))()
     best, ms = np.full(ngroups, -1, np.int32), C.c_double()
-    _check(lib().rc_vi_search_groups(int(device), S.ctypes.data, m, n, grp.ctypes.data, ngroups, nruns, rg.ctypes.data, init.ctypes.data,
-                                     order.ctypes.data, int(maxK), int(maxsweeps), labels.ctypes.data, runs, best.ctypes.data, C.byref(ms)))
+    entry = lib().rc_vi_search_groups_large if large else lib().rc_vi_search_groups
+    _check(entry(int(device), S.ctypes.data, m, n, grp.ctypes.data, ngroups, nruns, rg.ctypes.data, init.ctypes.data,
+                 order.ctypes.data, int(maxK), int(maxsweeps), labels.ctypes.data, runs, best.ctypes.data, C.byref(ms)))
     out = _psm_result(labels, runs, nruns, n, C.c_int32(-1), ms)
     out["best"] = best.astype(np.int64)
     return out
+
+
+def vi_search_groups_large(samples, group, init, order, run_group, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
+    """rc_vi_search_groups_large: vi_search_groups by the large-n kernel (n <= 32767), at every n."""
+    return vi_search_groups(samples, group, init, order, run_group, maxK, maxsweeps, device, large=True)
 
 
 # rc_hclust_merge_t

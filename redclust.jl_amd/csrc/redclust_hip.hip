@@ -7527,6 +7527,11 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #define VIS_GROUPED
 #include "visearch_kernel.inc.hip"   // the same text again: k_vigroups<PQ>
 #undef VIS_GROUPED
+#include "gqsplit.inc.hpp"           // the thresholds of the split Gq table: no device code of its own
+#include "visearch_large.inc.hip"    // k_vilarge<PQ>: the same search with n <= 32767
+#define VISL_GROUPED
+#include "visearch_large.inc.hip"    // the same text again: k_vilarge_groups<PQ>
+#undef VISL_GROUPED
 #include "visearch.inc.hip"
 #include "hclust.inc.hip"
 #include "slabplan.inc.hpp"

@@ -1,6 +1,6 @@
-// The host side of the exact searches (rc_vi_search, rc_id_search, rc_vi_search_groups): the launch, the fixed-point table, the
-// checks, the staging of the samples and the runs, the results.  The kernels and their arguments are visearch_kernel.inc.hip's,
-// included in front of this file.  Same translation unit as redclust_hip.hip: shares fail(), HIPCHK, the error buffer; the
+// The host side of the exact searches (rc_vi_search, rc_id_search, rc_vi_search_groups and the two _large entries): the launch, the
+// fixed-point table, the checks, the staging of the samples and the runs, the results.  The kernels and their arguments are
+// visearch_kernel.inc.hip's and visearch_large.inc.hip's, included in front of this file.  Same translation unit as redclust_hip.hip: shares fail(), HIPCHK, the error buffer; the
 // holders, check_label_rows, check_lds_capacity and select_device of hostutil.inc.hip; and from greedy.inc.hip the shared
 // argument checks, the staging of the runs and the result loop.
 
@@ -21,6 +21,41 @@ static hipError_t launch(int PQ, int nruns, size_t lds, const Args &A)
     else VIS_LAUNCH(STAGE_Q);
 #undef VIS_LAUNCH
     return hipGetLastError();
+}
+
+// The large-n kernels (visearch_large.inc.hip) behind the same arguments, with the thresholds of the split table beside them
+static hipError_t launch_large(bool grouped, int PQ, int nruns, size_t lds, const Args &A, const GqSplit &split)
+{
+    const ArgsL AL{A, split};
+#define VISL_LAUNCH(QQ)                                                                                                   \
+    do {                                                                                                                  \
+        void (*kernel)(ArgsL) = grouped ? k_vilarge_groups<QQ> : k_vilarge<QQ>;                                    \
+        hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   \
+        if (e != hipSuccess) return e;                                                                                    \
+        kernel<<<nruns, TPB, lds, 0>>>(AL);                                                                               \
+    } while (0)
+    if (PQ == 0) VISL_LAUNCH(0);
+    else if (PQ == 1) VISL_LAUNCH(1);
+    else VISL_LAUNCH(STAGE_Q);
+#undef VISL_LAUNCH
+    return hipGetLastError();
+}
+
+// the capacity in n of the _large entries, where the others have check_lds_capacity: the cells, the labels and the slots are u16
+constexpr int64_t LARGE_NMAX = 32767;
+static int32_t check_large_capacity(const char *who, int64_t n, int64_t m = 0)
+{
+    if (n > LARGE_NMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %lld points whose table cells and labels fit 15 bits", who, (long long)n, (long long)LARGE_NMAX);
+    if (m > 0x7FFFFFFFll / n) return fail(nullptr, RC_ERR_CAPACITY, "%s: m*n does not fit 31 bits (m=%lld n=%lld)", who, (long long)m, (long long)n);
+    return RC_OK;
+}
+
+// the thresholds of the table the host just built; a table they cannot be read from is the library's own fault
+static int32_t take_split(const char *who, const std::vector<int64_t> &Gq, GqSplit &split)
+{
+    const GqSplitError e = build_gq_split(Gq.data(), (int64_t)Gq.size(), split);
+    if (e != GQ_SPLIT_OK) return fail(nullptr, RC_ERR_STATE, "%s: internal error: the fixed-point table cannot be split into low words and thresholds (code %d)", who, (int)e);
+    return RC_OK;
 }
 
 static void gtable(int64_t n, int64_t *out)
@@ -108,7 +143,7 @@ struct Host {
 };
 
 // The host side of rc_vi_search (loss = LOSS_VI) and rc_id_search (LOSS_ID): the same arguments, checks, staging and results
-static int32_t run(int loss, const char *who, int32_t device, const int64_t *samples, int64_t m, int64_t n, int32_t nruns,
+static int32_t run(int loss, bool large, const char *who, int32_t device, const int64_t *samples, int64_t m, int64_t n, int32_t nruns,
                    const int64_t *init, const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out_,
                    int32_t *best, double *kernel_ms)
 {
@@ -117,7 +152,7 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
     int32_t rc = greedy::check_args(nullptr, who, m, n, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best);
     if (rc != RC_OK) return rc;
     // the capacity in n and m·n before anything is read
-    rc = check_lds_capacity(nullptr, who, n);
+    rc = large ? check_large_capacity(who, n) : check_lds_capacity(nullptr, who, n);
     if (rc != RC_OK) return rc;
     if (m > MN_MAX / n) return fail(nullptr, RC_ERR_CAPACITY, "%s: m*n exceeds 2^26 = %lld (m=%lld n=%lld)", who, MN_MAX, (long long)m, (long long)n);
 
@@ -126,6 +161,8 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
     if (rc != RC_OK) return rc;
     std::vector<unsigned short> h_SL((size_t)n * m);
     Host H(n);
+    GqSplit split{};
+    if (large && (rc = take_split(who, H.Gq, split)) != RC_OK) return rc;
     int Lmax = 0;
     __int128 constant = 0;                                              // Σ_s Σ_l Φq(n^s_l)
     std::vector<long long> Bs(loss == LOSS_ID ? (size_t)m : 0);         // ID: the same sum per sample (Bq_s)
@@ -163,7 +200,7 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
     HIPCHK(nullptr, H.upload(B, S, h_SL, table_elems * (size_t)nruns, A));
     A.n = (int)n; A.m = (int)m; A.Lmax = Lmax; A.kpad = kpad; A.Kcap = Kcap; A.maxsweeps = maxsweeps;
     const int PQ = stage_depth(m);
-    size_t lds = Carve((int)n, kpad, Kcap, PQ).total;
+    size_t lds = large ? CarveL((int)n, kpad, Kcap, PQ).total : Carve((int)n, kpad, Kcap, PQ).total;
     if (loss == LOSS_ID) {
         // F's table: the Bq_s ascending and their prefix sums; in LDS behind Aq where that fits, else read from global memory
         std::sort(Bs.begin(), Bs.end());
@@ -183,7 +220,8 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
         lds += A.tab_lds ? 16 * ((size_t)m + 1) : 16;
     }
     HIPCHK(nullptr, S.begin(0));
-    HIPCHK(nullptr, loss == LOSS_ID ? launch<LOSS_ID>(PQ, nruns, lds, A) : launch<LOSS_VI>(PQ, nruns, lds, A));
+    HIPCHK(nullptr, large ? launch_large(false, PQ, nruns, lds, A, split)
+                          : loss == LOSS_ID ? launch<LOSS_ID>(PQ, nruns, lds, A) : launch<LOSS_VI>(PQ, nruns, lds, A));
     std::vector<RunOut> h_out;
     HIPCHK(nullptr, S.collect(0, h_out, kernel_ms));
 
@@ -199,18 +237,17 @@ static int32_t run(int loss, const char *who, int32_t device, const int64_t *sam
 
 // The host side of rc_vi_search_groups: run's checks, per group where run's are per call, one staging, one upload and one launch
 // of the grouped instantiation.  Run r is rc_vi_search's run on samples[group == run_group[r]].
-static int32_t run_groups(int32_t device, const int64_t *samples, int64_t m, int64_t n, const int32_t *group, int32_t ngroups, int32_t nruns,
+static int32_t run_groups(bool large, const char *who, int32_t device, const int64_t *samples, int64_t m, int64_t n, const int32_t *group, int32_t ngroups, int32_t nruns,
                           const int32_t *run_group, const int64_t *init, const int32_t *order, int32_t maxK, int32_t maxsweeps,
                           int64_t *labels_out, void *runs_out_, int32_t *best, double *kernel_ms)
 {
-    const char *who = "rc_vi_search_groups";
     rc_psm_run_t *runs_out = (rc_psm_run_t *)runs_out_;
     if (!samples || !group || !run_group) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
     int32_t rc = greedy::check_args(nullptr, who, m, n, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best);
     if (rc != RC_OK) return rc;
     if (ngroups < 1) return fail(nullptr, RC_ERR_ARG, "%s: need ngroups >= 1 (got %d)", who, ngroups);
     // the capacity in n and m·n before anything is read
-    rc = check_lds_capacity(nullptr, who, n, m);
+    rc = large ? check_large_capacity(who, n, m) : check_lds_capacity(nullptr, who, n, m);
     if (rc != RC_OK) return rc;
 
     // ---- the groups: their sizes, and where each sample goes in its group's block
@@ -239,6 +276,8 @@ static int32_t run_groups(int32_t device, const int64_t *samples, int64_t m, int
     if (rc != RC_OK) return rc;
     std::vector<unsigned short> h_SL((size_t)n * (size_t)std::max<int64_t>(first[(size_t)ngroups], 1));
     Host H(n);
+    GqSplit split{};
+    if (large && (rc = take_split(who, H.Gq, split)) != RC_OK) return rc;
     std::vector<int> Lmax((size_t)ngroups, 0);
     std::vector<__int128> constant((size_t)ngroups, 0);                           // Σ_s Σ_l Φq(n^s_l) over the group
     for (int64_t s = 0; s < m; ++s) {
@@ -298,9 +337,9 @@ static int32_t run_groups(int32_t device, const int64_t *samples, int64_t m, int
     A.runs = d_runs;
     A.n = (int)n; A.m = (int)m_max; A.Lmax = Lmax_max; A.kpad = kpad; A.Kcap = Kcap_max; A.maxsweeps = maxsweeps;
     const int PQ = stage_depth(m_max);
-    const size_t lds = Carve((int)n, kpad, Kcap_max, PQ).total;
+    const size_t lds = large ? CarveL((int)n, kpad, Kcap_max, PQ).total : Carve((int)n, kpad, Kcap_max, PQ).total;
     HIPCHK(nullptr, S.begin(0));
-    HIPCHK(nullptr, (launch<LOSS_VI, true>(PQ, nruns, lds, A)));
+    HIPCHK(nullptr, large ? launch_large(true, PQ, nruns, lds, A, split) : (launch<LOSS_VI, true>(PQ, nruns, lds, A)));
     std::vector<RunOut> h_out;
     HIPCHK(nullptr, S.collect(0, h_out, kernel_ms));
 
@@ -326,7 +365,7 @@ extern "C" int32_t rc_vi_search_groups(int32_t device, const int64_t *samples, i
                                        int32_t nruns, const int32_t *run_group, const int64_t *init, const int32_t *order, int32_t maxK,
                                        int32_t maxsweeps, int64_t *labels_out, void *runs_out, int32_t *best, double *kernel_ms)
 {
-    return visearch::run_groups(device, samples, m, n, group, ngroups, nruns, run_group, init, order, maxK, maxsweeps, labels_out, runs_out,
+    return visearch::run_groups(false, "rc_vi_search_groups", device, samples, m, n, group, ngroups, nruns, run_group, init, order, maxK, maxsweeps, labels_out, runs_out,
                                 best, kernel_ms);
 }
 
@@ -342,7 +381,7 @@ extern "C" int32_t rc_vi_search(int32_t device, const int64_t *samples, int64_t 
                                 const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out,
                                 int32_t *best, double *kernel_ms)
 {
-    return visearch::run(visearch::LOSS_VI, "rc_vi_search", device, samples, m, n, nruns, init, order, maxK, maxsweeps, labels_out,
+    return visearch::run(visearch::LOSS_VI, false, "rc_vi_search", device, samples, m, n, nruns, init, order, maxK, maxsweeps, labels_out,
                          runs_out, best, kernel_ms);
 }
 
@@ -350,6 +389,23 @@ extern "C" int32_t rc_id_search(int32_t device, const int64_t *samples, int64_t 
                                 const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out,
                                 int32_t *best, double *kernel_ms)
 {
-    return visearch::run(visearch::LOSS_ID, "rc_id_search", device, samples, m, n, nruns, init, order, maxK, maxsweeps, labels_out,
+    return visearch::run(visearch::LOSS_ID, false, "rc_id_search", device, samples, m, n, nruns, init, order, maxK, maxsweeps, labels_out,
                          runs_out, best, kernel_ms);
+}
+
+extern "C" int32_t rc_vi_search_large(int32_t device, const int64_t *samples, int64_t m, int64_t n, int32_t nruns, const int64_t *init,
+                                      const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out,
+                                      int32_t *best, double *kernel_ms)
+{
+    return visearch::run(visearch::LOSS_VI, true, "rc_vi_search_large", device, samples, m, n, nruns, init, order, maxK, maxsweeps,
+                         labels_out, runs_out, best, kernel_ms);
+}
+
+extern "C" int32_t rc_vi_search_groups_large(int32_t device, const int64_t *samples, int64_t m, int64_t n, const int32_t *group,
+                                             int32_t ngroups, int32_t nruns, const int32_t *run_group, const int64_t *init,
+                                             const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out,
+                                             int32_t *best, double *kernel_ms)
+{
+    return visearch::run_groups(true, "rc_vi_search_groups_large", device, samples, m, n, group, ngroups, nruns, run_group, init, order,
+                                maxK, maxsweeps, labels_out, runs_out, best, kernel_ms);
 }

@@ -225,13 +225,16 @@ def _search_starts(n, nruns, seed, init, samples=None, mpel_loss=None, extra=Non
 _INFO_KEYS = ("loss", "sweeps", "converged", "moves", "K", "labels", "best", "kernel_ms", "loss_num")
 
 
-def _exact_search(samples, loss, nruns, maxK, maxsweeps, seed, init, device):
+def _exact_search(samples, loss, nruns, maxK, maxsweeps, seed, init, device, large=False):
     """searchpointestimate(loss="VI", exact=True) and searchpointestimate(loss="ID"): see there.  Two things differ: the
     library's search, and the call whose result is the last start — the bound's search for VI, the exact VI search for ID —
-    with the key its info is kept under."""
+    with the key its info is kept under.  large (searchvi): no limit of 8192 points here, and above it rc_vi_search_large."""
     search, key = (_lib.id_search, "vi") if loss == "ID" else (_lib.vi_search, "lower_bound")
     S = _sample_matrix(samples)
-    _check_lds_n(S.shape[1], 'searchpointestimate(loss="ID")' if loss == "ID" else "searchpointestimate(exact=True)")
+    if large and S.shape[1] > _LDS_NMAX:
+        search = _lib.vi_search_large
+    else:
+        _check_lds_n(S.shape[1], 'searchpointestimate(loss="ID")' if loss == "ID" else "searchpointestimate(exact=True)")
     start, prior = searchpointestimate(samples, "VI", nruns=nruns, maxK=maxK, maxsweeps=maxsweeps, seed=seed, init=init, device=device,
                                        exact=loss == "ID")
     inits, orders = _search_starts(S.shape[1], nruns, seed, init, samples, loss, start, device)
@@ -280,7 +283,9 @@ def searchpointestimate(samples_or_counts=None, loss="VI", *, nruns: int = 16, m
     Runs: the nruns Philox orders from empty labels, one per init labelling, one from the MPEL ID sample and one from the
     result of searchpointestimate(samples, "VI", exact=True) with the same arguments (info["vi"] is that call's info), so the
     result is never worse in the integer criterion info["loss_num"] than either.  info["loss"] = Q_ID/(2^32·n·m) is within
-    2^-32 ≈ 2.3e-10 of expectedid's f64 value.  maxK = 0 is widened as for exact=True."""
+    2^-32 ≈ 2.3e-10 of expectedid's f64 value.  maxK = 0 is widened as for exact=True.
+
+    exact=True and loss="ID" stop at n = 8192; searchvi is the exact expected-VI search at any n <= 32767."""
     if loss == "ID":
         if ctx is not None:
             raise ValueError('loss="ID" needs the samples; a Context keeps only their counts')
@@ -313,6 +318,25 @@ def searchpointestimate(samples_or_counts=None, loss="VI", *, nruns: int = 16, m
             sizes = np.stack([np.bincount(s, minlength=n + 1)[s] for s in S])
             info["vi_constant"] = float(np.mean(np.log(sizes)))
     return res["labels"][res["best"]].copy(), info
+
+
+def searchvi(samples, *, nruns: int = 16, init=None, maxK: int = 0, maxsweeps: int = 100, seed: int = 0, device: int = 0):
+    """Search ALL partitions for the clustering of minimum posterior expected VI (expectedvi; SALSO's "VI") at any n <= 32767.
+    samples: an MCMCResult, anything with `.clusts`, or an m×n label matrix.  The search, its runs — nruns Philox orders from
+    empty labels, one per init labelling, the MPEL VI sample, the lower-bound search's result — and the returned (clust, info) are
+    those of searchpointestimate(samples, "VI", exact=True), whose bytes this returns up to n = 8192.  Above that the kernel is
+    csrc/visearch_large.inc.hip (rc_vi_search_large: the same integer function of a run's inputs) and the lower-bound result
+    comes through rc_psm_search_large_samples.  Capacity: m·n <= 2^26, at most 1024 clusters, the 4 GiB table budget."""
+    if not hasattr(samples, "clusts"):
+        samples = _Samples(_sample_matrix(samples))
+    return _exact_search(samples, "VI", nruns, maxK, maxsweeps, seed, init, device, large=True)
+
+
+class _Samples:
+    """a label matrix where an MCMCResult is expected"""
+
+    def __init__(self, clusts):
+        self.clusts = clusts
 
 
 _LINKAGES = {"average": 0, "complete": 1, "single": 2}   # RC_HCLUST_AVERAGE, _COMPLETE, _SINGLE

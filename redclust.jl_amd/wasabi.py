@@ -10,9 +10,14 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from .pointestimate import (_sample_matrix, _labels, _sortlabels, _numerators, credibleball, expecteddistances)
+from .pointestimate import (_sample_matrix, _labels, _sortlabels, _numerators, credibleball, expecteddistances, _LDS_NMAX)
 
 _U53 = 1 << 53
+
+
+def _grouped_search(n):
+    """rc_vi_search_groups up to 8192 points, above that its large-n twin (n <= 32767): the same search, the same bits"""
+    return _lib.vi_search_groups_large if n > _LDS_NMAX else _lib.vi_search_groups
 
 
 def searchvigroups(samples, group, inits, orders, run_group, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
@@ -20,10 +25,11 @@ def searchvigroups(samples, group, inits, orders, run_group, maxK: int = 0, maxs
     expected VI over the samples s with group[s] == run_group[r], from the labels inits[r] (0 = unallocated) in the order
     orders[r] (a 1-based permutation) — bit for bit what searchpointestimate's exact search does on that sub-array.  samples:
     an MCMCResult, anything with `.clusts`, or an m×n label matrix; group: m ids in 0..G−1, −1 for a sample in no group.
+    Above n = 8192 the launch is rc_vi_search_groups_large's (n <= 32767).
     Returns (labels, info): labels[g] is the best labelling of group g (sortlabels'd; zeros where no run searches g); info
     has the per-run labels, loss, loss_num, sweeps, converged, moves, K, the per-group best (−1 = no run) and kernel_ms."""
     S = _sample_matrix(samples)
-    res = _lib.vi_search_groups(S, group, inits, orders, run_group, maxK=maxK, maxsweeps=maxsweeps, device=device)
+    res = _grouped_search(S.shape[1])(S, group, inits, orders, run_group, maxK=maxK, maxsweeps=maxsweeps, device=device)
     out = np.zeros((len(res["best"]), S.shape[1]), np.int64)
     for g, b in enumerate(res["best"]):
         if b >= 0:
@@ -83,7 +89,7 @@ class _Device:
         return num
 
     def search(self, assign, inits, orders, run_group):
-        res = _lib.vi_search_groups(self.S, assign, inits, orders, run_group, maxK=self.cap, maxsweeps=self.maxsweeps, device=self.device)
+        res = _grouped_search(self.S.shape[1])(self.S, assign, inits, orders, run_group, maxK=self.cap, maxsweeps=self.maxsweeps, device=self.device)
         self.ms += res["kernel_ms"]
         return res
 
@@ -193,7 +199,7 @@ def wasabi(samples, L: int, *, nstarts: int = 4, maxiter: int = 50, nruns: int =
 
     Each start alternates (1) assigning every sample to its nearest particle, ties to the lowest particle index, and (2)
     replacing every particle by the partition of minimum expected VI over its own samples, searched over ALL partitions: one
-    rc_vi_search_groups launch for all groups, per group one run from the current particle in identity order and nruns runs from
+    rc_vi_search_groups launch (above n = 8192 rc_vi_search_groups_large, n <= 32767) for all groups, per group one run from the current particle in identity order and nruns runs from
     empty labels, of which the first of least loss wins.  The current particle is a start and a run only accepts strictly
     improving moves, so no group's sum rises and W never increases.  A particle left without samples is replaced by the sample
     farthest from its own particle (ties: the lowest index; a sample serves one repair per iteration; only samples at positive

@@ -7,6 +7,7 @@ tests/id_search_ref.py) doing ONE run's work on the host — the only yardstick 
     python tools/time_visearch.py --no-ref         # skip the NumPy restatement
     python tools/time_visearch.py --loss ID        # the same input through rc_id_search
     python tools/time_visearch.py --maxsweeps 1    # the first sweep alone (sequential allocation: every point moves)
+    python tools/time_visearch.py --large          # rc_vi_search_large at n = 8192, 16384, 32767; at 8192 alternating with rc_vi_search
 
 Inputs: a planted partition with K = 50 clusters, 20 % of the points relabelled at random in each of m = 1000 samples
 (seed 0).  The timed call is _lib.vi_search (_lib.id_search) with 16 runs from empty labels in the orders searchpointestimate draws
@@ -37,6 +38,31 @@ def planted_samples(n, m, K, noise, seed=0):
     return samples.astype(np.int64) + 1
 
 
+def time_large(a):
+    """k_vilarge at the sizes of a.n; where rc_vi_search runs too (n <= 8192) the two alternate on the same inputs in this
+    process and the runs are compared.  µs per step = the kernel's median over n · (the largest sweep count of any run)."""
+    for n in a.n:
+        S = planted_samples(n, a.m, a.K, a.noise)
+        rng = np.random.Generator(np.random.Philox(key=0))
+        order = np.stack([rng.permutation(n).astype(np.int32) + 1 for _ in range(a.nruns)])
+        init = np.zeros((a.nruns, n), np.int64)
+        new, old, res, res_old = [], [], None, None
+        for _ in range(a.reps):
+            res = _lib.vi_search_large(S, init, order, maxsweeps=a.maxsweeps)
+            new.append(res["kernel_ms"])
+            if n <= 8192:
+                res_old = _lib.vi_search(S, init, order, maxsweeps=a.maxsweeps)
+                old.append(res_old["kernel_ms"])
+        out = dict(what="large", n=n, m=a.m, nruns=a.nruns, reps=a.reps, kernel_ms_median=round(statistics.median(new), 3),
+                   kernel_ms_min=round(min(new), 3), kernel_ms_max=round(max(new), 3), sweeps_max=int(res["sweeps"].max()),
+                   us_per_step=round(1e3 * statistics.median(new) / (n * int(res["sweeps"].max())), 3))
+        if old:
+            out.update(old_kernel_ms_median=round(statistics.median(old), 3), old_kernel_ms_min=round(min(old), 3),
+                       old_kernel_ms_max=round(max(old), 3), new_over_old=round(statistics.median(new) / statistics.median(old), 4),
+                       same_bytes=bool(all(np.array_equal(res[k], res_old[k]) for k in ("labels", "loss_num", "sweeps", "moves", "K"))))
+        print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="*", default=[2000, 8192])
@@ -48,11 +74,16 @@ def main():
     ap.add_argument("--no-ref", action="store_true")
     ap.add_argument("--loss", choices=["VI", "ID"], default="VI")
     ap.add_argument("--maxsweeps", type=int, default=100)
+    ap.add_argument("--large", action="store_true", help="rc_vi_search_large; default sizes 8192 16384 32767")
     a = ap.parse_args()
+    if a.large and a.n == [2000, 8192]:
+        a.n = [8192, 16384, 32767]
     search = _lib.vi_search if a.loss == "VI" else _lib.id_search
     expected = rc.expectedvi if a.loss == "VI" else rc.expectedid
     warm = planted_samples(64, 5, 3, 0.1)
     search(warm, np.zeros((2, 64), np.int64), np.tile(np.arange(1, 65, dtype=np.int32), (2, 1)))   # module load, first launch
+    if a.large:
+        return time_large(a)
     for n in a.n:
         S = planted_samples(n, a.m, a.K, a.noise)
         rng = np.random.Generator(np.random.Philox(key=0))

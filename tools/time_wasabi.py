@@ -121,12 +121,16 @@ def main():
     ap.add_argument("--no-wasabi", action="store_true")
     ap.add_argument("--against", help="a libredclust_hip.so built from the parent commit: only the rc_vi_search comparison is run")
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--large", action="store_true", help="one wasabi call with L = 4 at n = 32767 (rc_vi_search_groups_large), nothing else")
     a = ap.parse_args()
     if a.against:
         vi_search_vs_parent(os.path.abspath(a.against), a.rounds, a.n)
         return
     warm = two_mode_samples(64, 6, 3, 0.1)
     rc.wasabi(warm, 2, nstarts=1)                                        # module load, first launches
+    if a.large:
+        wasabi_wall(two_mode_samples(32767, a.m, a.K, a.noise), 4, a.nstarts, a.maxiter)
+        return
     S = two_mode_samples(a.n, a.m, a.K, a.noise)
     for L in a.L:
         grouped_vs_sequential(S, L, a.reps)

@@ -786,6 +786,32 @@ int32_t rc_psm_expected_loss_ctx(rc_ctx *ctx, int64_t numsamples, int32_t loss, 
                                  double *loss_out /* L */, int64_t *num_out /* L */, double *kernel_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Hierarchical point estimates, large n: the entry points above — arguments, order of checks, results, bits — by kernels
+ * whose capacity is n <= 32767 with m·n < 2^31 (RC_ERR_CAPACITY beyond, the message names 32767, before any device work).
+ * DESIGN.md §8 "Hierarchical point estimates, large n".  They run at every n; wherever rc_hclust / rc_psm_expected_loss run
+ * too, the merges, binder_num, vilb, loss_out and num_out are theirs byte for byte.  The linkage keeps a partner and a size
+ * per point in LDS (4 bytes) and the cached values in device memory; the expected loss stages 8, 4 or 2 labellings per LDS
+ * group, by n (the environment variable RC_ELOSS_GROUP, read at every call, lowers that to a power of two: the results do not
+ * change).  Device memory of a linkage: S 8·n² bytes, M 4·n² (complete and single only), beside the counts' 4·n² — 8.6 + 4.3
+ * + 4.3 GB at n = 32767; every allocation is made before the first kernel, and a failure is RC_ERR_OOM.
+ * rc_hclust_cut_large: rc_hclust_cut with n <= 32767.
+ * ------------------------------------------------------------------------------------------------------------- */
+int32_t rc_hclust_large(int32_t device, const void *counts /* uint32_t n×n */, int64_t m, int64_t n, int32_t linkage,
+                        void *merges_out /* rc_hclust_merge_t[n-1] */, int64_t *binder_num /* n */, int32_t maxcut,
+                        double *vilb /* maxcut */, double *kernel_ms);
+int32_t rc_hclust_large_samples(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n, int32_t linkage,
+                                void *merges_out /* rc_hclust_merge_t[n-1] */, int64_t *binder_num /* n */, int32_t maxcut,
+                                double *vilb /* maxcut */, double *kernel_ms, double *counts_ms);
+int32_t rc_hclust_large_ctx(rc_ctx *ctx, int64_t numsamples, int32_t linkage, void *merges_out /* rc_hclust_merge_t[n-1] */,
+                            int64_t *binder_num /* n */, int32_t maxcut, double *vilb /* maxcut */, double *kernel_ms);
+int32_t rc_hclust_cut_large(const void *merges /* rc_hclust_merge_t[n-1] */, int64_t n, int64_t K, int64_t *labels_out /* n */);
+int32_t rc_psm_expected_loss_large(int32_t device, const void *counts /* uint32_t n×n */, int64_t m, int64_t n, int32_t loss, int64_t L,
+                                   const int64_t *labels /* L×n */, double *loss_out /* L */, int64_t *num_out /* L */,
+                                   double *kernel_ms);
+int32_t rc_psm_expected_loss_large_ctx(rc_ctx *ctx, int64_t numsamples, int32_t loss, int64_t L, const int64_t *labels /* L×n */,
+                                       double *loss_out /* L */, int64_t *num_out /* L */, double *kernel_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Predict: where do observations go that were not in the fit?  For every posterior sample s and every new point i, the
  * Gibbs full conditional (src/mcmc.jl:192-252) of an (n+1)-th point whose own cluster is empty, and a draw from it.  New
  * points are allocated independently of each other given a sample.  No context: errors through rc_last_error(NULL).

@@ -706,15 +706,72 @@ end
 
 const HCLUST_LINKAGES = Dict("average" => 0, "complete" => 1, "single" => 2)
 
-# the cut of minimum loss among K = 1..maxK (ties: the smaller K), its labels from the library's own rc_hclust_cut
-function hclustchoose(merges, binder_num, vilb, n::Integer, m::Integer, loss::String, maxK::Integer, kernel_ms)
+# the cut of minimum loss among K = 1..maxK (ties: the smaller K), its labels from the library's own rc_hclust_cut (large: _large)
+function hclustchoose(merges, binder_num, vilb, n::Integer, m::Integer, loss::String, maxK::Integer, kernel_ms, large::Bool = false)
     pairs = n * (n - 1) ÷ 2
     losses = loss == "binder" ? [pairs == 0 ? 0.0 : binder_num[n - K + 1] / (m * pairs) for K in 1:maxK] : vilb
     K = loss == "binder" ? argmin([binder_num[n - K + 1] for K in 1:maxK]) : argmin(vilb)
     labels = Vector{Int64}(undef, n)
-    rc = ccall((:rc_hclust_cut, LIB), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}), merges, n, K, labels)
+    rc = if large
+        ccall((:rc_hclust_cut_large, LIB), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}), merges, n, K, labels)
+    else
+        ccall((:rc_hclust_cut, LIB), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}), merges, n, K, labels)
+    end
     check(Ptr{Cvoid}(C_NULL), rc)
     return (labels, (loss = losses, K = K, merges = merges[1:n-1], binder_num = binder_num, kernel_ms = kernel_ms[1]))
+end
+
+# The dendrogram of a count matrix (rc_hclust; large: rc_hclust_large) with the VI bound of the cuts 1:maxcut:
+# (merges, binder_num, vilb, kernel_ms)
+function hclustcounts(b::HIPBackend, counts::Matrix{UInt32}, numsamples::Integer, linkage::String, maxcut::Integer, large::Bool)
+    haskey(HCLUST_LINKAGES, linkage) || throw(ArgumentError("Invalid linkage specifier."))
+    n = size(counts, 1)
+    size(counts, 2) == n || throw(ArgumentError("counts must be a square matrix"))
+    merges = Vector{RcHclustMerge}(undef, max(n - 1, 1))
+    binder_num = Vector{Int64}(undef, n)
+    vilb = Vector{Cdouble}(undef, max(maxcut, 1))
+    ms = Cdouble[0]
+    rc = if large
+        ccall((:rc_hclust_large, LIB), Int32,
+              (Int32, Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Int64}, Int32, Ptr{Cdouble}, Ptr{Cdouble}),
+              b.device, counts, numsamples, n, HCLUST_LINKAGES[linkage], merges, binder_num, maxcut, vilb, ms)
+    else
+        ccall((:rc_hclust, LIB), Int32,
+              (Int32, Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Int64}, Int32, Ptr{Cdouble}, Ptr{Cdouble}),
+              b.device, counts, numsamples, n, HCLUST_LINKAGES[linkage], merges, binder_num, maxcut, vilb, ms)
+    end
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return (merges, binder_num, vilb[1:maxcut], ms)
+end
+
+# ... and of the samples of a result, whose counts are built on the device and stay there (rc_hclust_samples; large:
+# rc_hclust_large_samples).  samples: n × m, as samplematrix returns them
+function hclustsamples(b::HIPBackend, samples::Matrix{Int64}, linkage::String, maxcut::Integer, large::Bool)
+    haskey(HCLUST_LINKAGES, linkage) || throw(ArgumentError("Invalid linkage specifier."))
+    n, m = size(samples)
+    merges = Vector{RcHclustMerge}(undef, max(n - 1, 1))
+    binder_num = Vector{Int64}(undef, n)
+    vilb = Vector{Cdouble}(undef, max(maxcut, 1))
+    ms = Cdouble[0]
+    rc = if large
+        ccall((:rc_hclust_large_samples, LIB), Int32,
+              (Int32, Ptr{Int64}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Int64}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+              b.device, samples, m, n, HCLUST_LINKAGES[linkage], merges, binder_num, maxcut, vilb, ms, C_NULL)
+    else
+        ccall((:rc_hclust_samples, LIB), Int32,
+              (Int32, Ptr{Int64}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Int64}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+              b.device, samples, m, n, HCLUST_LINKAGES[linkage], merges, binder_num, maxcut, vilb, ms, C_NULL)
+    end
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return (merges, binder_num, vilb[1:maxcut], ms)
+end
+
+# maxK = 0 means ⌈n/8⌉; the VI bound needs the cuts evaluated on the device, the Binder curve comes with the dendrogram
+function hclustmaxk(n::Integer, maxK::Integer, loss::String)
+    loss in ("binder", "VI") || throw(ArgumentError("Invalid loss function specifier."))
+    maxK = maxK == 0 ? cld(n, 8) : Int(maxK)
+    1 <= maxK <= n || throw(ArgumentError("maxK must lie in 1:n"))
+    return (maxK, loss == "VI" ? maxK : 0)
 end
 
 """
@@ -727,48 +784,66 @@ of clusters `K` in `1:maxK` of minimum expected loss, ties going to the smaller 
 "single", on similarities; ties between pairs go to the smallest cluster name (its smallest member), then the smallest partner,
 and every decision is exact integer arithmetic.  `loss`: "binder" (from the exact curve `info.binder_num`, index t + 1 = after t
 merges) or "VI" (the lower bound, evaluated for every cut on the device).  `maxK = 0` means ⌈n/8⌉.  `info.merges` holds one
-`RcHclustMerge` per step.
+`RcHclustMerge` per step.  n <= 8192; `dendrogrampointestimate` is the same without that limit.
 """
 function hclustpointestimate(b::HIPBackend, counts::Matrix{UInt32}, numsamples::Integer; loss::String = "VI",
                              linkage::String = "average", maxK::Integer = 0)
-    loss in ("binder", "VI") || throw(ArgumentError("Invalid loss function specifier."))
-    haskey(HCLUST_LINKAGES, linkage) || throw(ArgumentError("Invalid linkage specifier."))
     n = size(counts, 1)
-    size(counts, 2) == n || throw(ArgumentError("counts must be a square matrix"))
-    maxK = maxK == 0 ? cld(n, 8) : Int(maxK)
-    1 <= maxK <= n || throw(ArgumentError("maxK must lie in 1:n"))
-    merges = Vector{RcHclustMerge}(undef, max(n - 1, 1))
-    binder_num = Vector{Int64}(undef, n)
-    maxcut = loss == "VI" ? maxK : 0
-    vilb = Vector{Cdouble}(undef, max(maxcut, 1))
-    ms = Cdouble[0]
-    rc = ccall((:rc_hclust, LIB), Int32,
-               (Int32, Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Int64}, Int32, Ptr{Cdouble}, Ptr{Cdouble}),
-               b.device, counts, numsamples, n, HCLUST_LINKAGES[linkage], merges, binder_num, maxcut, vilb, ms)
-    check(Ptr{Cvoid}(C_NULL), rc)
-    return hclustchoose(merges, binder_num, vilb[1:maxcut], n, numsamples, loss, maxK, ms)
+    maxK, maxcut = hclustmaxk(n, maxK, loss)
+    merges, binder_num, vilb, ms = hclustcounts(b, counts, numsamples, linkage, maxcut, false)
+    return hclustchoose(merges, binder_num, vilb, n, numsamples, loss, maxK, ms)
 end
 
 function hclustpointestimate(b::HIPBackend, result; loss::String = "VI", linkage::String = "average", maxK::Integer = 0)
-    loss in ("binder", "VI") || throw(ArgumentError("Invalid loss function specifier."))
-    haskey(HCLUST_LINKAGES, linkage) || throw(ArgumentError("Invalid linkage specifier."))
     samples = samplematrix(result)                                # the counts are built from these on the device and stay there
     n, m = size(samples)
-    maxK = maxK == 0 ? cld(n, 8) : Int(maxK)
-    1 <= maxK <= n || throw(ArgumentError("maxK must lie in 1:n"))
-    merges = Vector{RcHclustMerge}(undef, max(n - 1, 1))
-    binder_num = Vector{Int64}(undef, n)
-    maxcut = loss == "VI" ? maxK : 0
-    vilb = Vector{Cdouble}(undef, max(maxcut, 1))
-    ms = Cdouble[0]
-    rc = ccall((:rc_hclust_samples, LIB), Int32,
-               (Int32, Ptr{Int64}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Int64}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
-               b.device, samples, m, n, HCLUST_LINKAGES[linkage], merges, binder_num, maxcut, vilb, ms, C_NULL)
-    check(Ptr{Cvoid}(C_NULL), rc)
-    return hclustchoose(merges, binder_num, vilb[1:maxcut], n, m, loss, maxK, ms)
+    maxK, maxcut = hclustmaxk(n, maxK, loss)
+    merges, binder_num, vilb, ms = hclustsamples(b, samples, linkage, maxcut, false)
+    return hclustchoose(merges, binder_num, vilb, n, m, loss, maxK, ms)
 end
 
-export hclustpointestimate
+"""
+    dendrogrampointestimate(HIPBackend(), counts, numsamples; loss = "VI", linkage = "average", maxK = 0) -> (clust, info)
+    dendrogrampointestimate(HIPBackend(), result; loss = "VI", linkage = "average", maxK = 0) -> (clust, info)
+
+`hclustpointestimate` for any n <= 32767 (m·n < 2^31): up to n = 8192 its call and its bytes, above that the same integer
+function of the counts by the kernels that keep a partner and a size per point in LDS (rc_hclust_large, rc_hclust_large_samples,
+rc_hclust_cut_large).  Device memory at n = 32767: 8.6 GB of pair sums, 4.3 GB more for "complete" / "single", beside the counts.
+"""
+function dendrogrampointestimate(b::HIPBackend, counts::Matrix{UInt32}, numsamples::Integer; loss::String = "VI",
+                                 linkage::String = "average", maxK::Integer = 0)
+    n = size(counts, 1)
+    maxK, maxcut = hclustmaxk(n, maxK, loss)
+    merges, binder_num, vilb, ms = hclustcounts(b, counts, numsamples, linkage, maxcut, n > LDS_NMAX)
+    return hclustchoose(merges, binder_num, vilb, n, numsamples, loss, maxK, ms, n > LDS_NMAX)
+end
+
+function dendrogrampointestimate(b::HIPBackend, result; loss::String = "VI", linkage::String = "average", maxK::Integer = 0)
+    samples = samplematrix(result)
+    n, m = size(samples)
+    maxK, maxcut = hclustmaxk(n, maxK, loss)
+    merges, binder_num, vilb, ms = hclustsamples(b, samples, linkage, maxcut, n > LDS_NMAX)
+    return hclustchoose(merges, binder_num, vilb, n, m, loss, maxK, ms, n > LDS_NMAX)
+end
+
+"""
+    dendrogram(HIPBackend(), counts, numsamples; linkage = "average") -> (merges, binder_num, kernel_ms)
+    dendrogram(HIPBackend(), result; linkage = "average") -> (merges, binder_num, kernel_ms)
+
+The dendrogram alone, n <= 32767: one `RcHclustMerge` per step and the exact Binder numerator after t merges at index t + 1.
+"""
+function dendrogram(b::HIPBackend, counts::Matrix{UInt32}, numsamples::Integer; linkage::String = "average")
+    merges, binder_num, _, ms = hclustcounts(b, counts, numsamples, linkage, 0, size(counts, 1) > LDS_NMAX)
+    return (merges[1:size(counts, 1)-1], binder_num, ms[1])
+end
+
+function dendrogram(b::HIPBackend, result; linkage::String = "average")
+    samples = samplematrix(result)
+    merges, binder_num, _, ms = hclustsamples(b, samples, linkage, 0, size(samples, 1) > LDS_NMAX)
+    return (merges[1:size(samples, 1)-1], binder_num, ms[1])
+end
+
+export hclustpointestimate, dendrogrampointestimate, dendrogram
 
 """
     predict(HIPBackend(), result, Dnew; seed = 0) -> (labels, map_labels)

@@ -264,6 +264,17 @@ SIGNATURES = {
                                          C.c_void_p, C.POINTER(C.c_double)]),
     "rc_psm_expected_loss_ctx": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.POINTER(C.c_double)]),
+    "rc_hclust_large": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                    C.c_void_p, C.POINTER(C.c_double)]),
+    "rc_hclust_large_samples": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                            C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rc_hclust_large_ctx": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                        C.POINTER(C.c_double)]),
+    "rc_hclust_cut_large": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "rc_psm_expected_loss_large": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "rc_psm_expected_loss_large_ctx": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.POINTER(C.c_double)]),
     "rc_predict": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.POINTER(RcParams), C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
@@ -1070,12 +1081,12 @@ def vi_search_groups_large(samples, group, init, order, run_group, maxK: int = 0
 HCLUST_MERGE = np.dtype([("a", np.int32), ("b", np.int32), ("size", np.int32), ("m_ab", np.uint32), ("s_ab", np.int64)], align=True)
 
 
-def hclust(counts, numsamples, linkage: int, maxcut: int = 0, device: int = 0, ctx=None, samples=None):
+def hclust(counts, numsamples, linkage: int, maxcut: int = 0, device: int = 0, ctx=None, samples=None, large: bool = False):
     """rc_hclust (counts: n×n uint32), rc_hclust_samples (samples: m×n int64 labels; counts and numsamples are ignored) or,
     with ctx, rc_hclust_ctx on that context's device counts.  Returns a dict: merges (n − 1 records of HCLUST_MERGE),
     binder_num (n int64; index t = after t merges), vilb (maxcut f64: the VI-bound loss of the cuts K = 1..maxcut), kernel_ms,
-    and counts_ms for the samples form."""
-    fn, head, handle, n, timed = _counts_form("hclust", counts, numsamples, ctx, samples, device)
+    and counts_ms for the samples form.  large: rc_hclust_large*, the same by the large-n kernels."""
+    fn, head, handle, n, timed = _counts_form("hclust_large" if large else "hclust", counts, numsamples, ctx, samples, device)
     merges = np.zeros(max(n - 1, 1), HCLUST_MERGE)
     bnum = np.zeros(max(n, 1), np.int64)
     vilb = np.zeros(max(int(maxcut), 1))
@@ -1087,26 +1098,44 @@ def hclust(counts, numsamples, linkage: int, maxcut: int = 0, device: int = 0, c
     return out
 
 
-def hclust_cut(merges, n: int, K: int) -> np.ndarray:
-    """rc_hclust_cut (host only): the labelling with K clusters, labels 1..K in sortlabels order."""
+def hclust_large(counts, numsamples, linkage: int, maxcut: int = 0, device: int = 0, ctx=None, samples=None):
+    """rc_hclust_large, rc_hclust_large_samples or rc_hclust_large_ctx: hclust — arguments, results, bits — by the kernels whose
+    capacity is n <= 32767 (csrc/hclust_large.inc.hip), at every n."""
+    return hclust(counts, numsamples, linkage, maxcut, device, ctx, samples, large=True)
+
+
+def hclust_cut(merges, n: int, K: int, large: bool = False) -> np.ndarray:
+    """rc_hclust_cut (host only): the labelling with K clusters, labels 1..K in sortlabels order.  large: rc_hclust_cut_large."""
     L = lib()
     mg = np.ascontiguousarray(merges, dtype=HCLUST_MERGE)
     labels = np.zeros(max(int(n), 1), np.int64)
-    _check(L.rc_hclust_cut(mg.ctypes.data, int(n), int(K), labels.ctypes.data))
+    _check((L.rc_hclust_cut_large if large else L.rc_hclust_cut)(mg.ctypes.data, int(n), int(K), labels.ctypes.data))
     return labels[:int(n)]
 
 
-def psm_expected_loss(labels, counts, numsamples: int, loss: int, device: int = 0, ctx=None):
+def hclust_cut_large(merges, n: int, K: int) -> np.ndarray:
+    """rc_hclust_cut_large: hclust_cut with n <= 32767."""
+    return hclust_cut(merges, n, K, large=True)
+
+
+def psm_expected_loss(labels, counts, numsamples: int, loss: int, device: int = 0, ctx=None, large: bool = False):
     """rc_psm_expected_loss (counts: n×n uint32) or, with ctx, rc_psm_expected_loss_ctx: (loss f64[L], num int64[L], kernel ms)
-    of the L×n labellings `labels` (1..n)."""
+    of the L×n labellings `labels` (1..n).  large: rc_psm_expected_loss_large*, the same by the large-n kernel."""
     lab = np.ascontiguousarray(labels, dtype=np.int64)
     if lab.ndim != 2:
         raise ValueError("labels must be an L×n matrix")
     nl, n = lab.shape
     loss_out, num_out, ms = np.zeros(max(nl, 1)), np.zeros(max(nl, 1), np.int64), C.c_double()
-    fn, head, handle, _, _ = _counts_form("psm_expected_loss", counts, numsamples, ctx, None, device, n, "labels")
+    fn, head, handle, _, _ = _counts_form("psm_expected_loss_large" if large else "psm_expected_loss", counts, numsamples, ctx, None,
+                                          device, n, "labels")
     _check(fn(*head, int(loss), nl, lab.ctypes.data, loss_out.ctypes.data, num_out.ctypes.data, C.byref(ms)), handle)
     return loss_out[:nl], num_out[:nl], float(ms.value)
+
+
+def psm_expected_loss_large(labels, counts, numsamples: int, loss: int, device: int = 0, ctx=None):
+    """rc_psm_expected_loss_large or, with ctx, rc_psm_expected_loss_large_ctx: psm_expected_loss by the kernel whose capacity
+    is n <= 32767, at every n."""
+    return psm_expected_loss(labels, counts, numsamples, loss, device, ctx, large=True)
 
 
 def predict(Dnew, samples, r, p, params: dict, seed: int = 0, sample_offset: int = 0, point_offset: int = 0, logDnew=None,

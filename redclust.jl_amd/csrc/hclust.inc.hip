@@ -306,11 +306,21 @@ __global__ __launch_bounds__(TPB) void k_eloss(const unsigned *__restrict__ C, s
 
 // ---- host side
 
-static int32_t check_capacity(rc_ctx *c, const char *who, int64_t m, int64_t n)
+// large: the entries of hclust_large.inc.hip, whose kernels keep 4 bytes per point in LDS
+constexpr int LARGE_NMAX = 32767;
+static int32_t check_capacity(rc_ctx *c, const char *who, int64_t m, int64_t n, bool large = false)
 {
     if (m < 1 || n < 1) return fail(c, RC_ERR_ARG, "%s: need m >= 1 and n >= 1 (got m=%lld n=%lld)", who, (long long)m, (long long)n);
-    return check_lds_capacity(c, who, n, m);
+    if (!large) return check_lds_capacity(c, who, n, m);
+    if (n > LARGE_NMAX) return fail(c, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %d points whose partners and sizes fit the workgroup's LDS", who, (long long)n, LARGE_NMAX);
+    if (m > 0x7FFFFFFFll / n) return fail(c, RC_ERR_CAPACITY, "%s: m*n does not fit 31 bits (m=%lld n=%lld; n <= %d)", who, (long long)m, (long long)n, LARGE_NMAX);
+    return RC_OK;
 }
+
+// hclust_large.inc.hip: the linkage and the T of labellings by the kernels whose capacity is n <= 32767
+static hipError_t launch_large(int32_t linkage, const unsigned *dC, int64_t ldc, hipStream_t st, unsigned long long *d_val, unsigned short *d_part0,
+                               const Args &A);
+static hipError_t launch_eloss_large(hipStream_t st, const unsigned *dC, int64_t ldc, int64_t n, const unsigned short *d_lab, int64_t L, unsigned *d_T);
 
 // The partition after the first n − K merges as labels 1..K in sortlabels order: names are smallest members, so a cluster's
 // rank among the names is the order of its first appearance.  A parent is always a smaller name than its child, so one
@@ -338,7 +348,7 @@ static bool cut_labels(const Merge *mg, int64_t n, int64_t K, std::vector<int> &
 
 // T of L labellings (slots 1..n as u16, L × n) under the device counts; ms: device time of the kernel, added to *ms
 static int32_t eloss_T(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ldc, int64_t n, const std::vector<unsigned short> &labs,
-                       int64_t L, std::vector<unsigned> &T, double &ms)
+                       int64_t L, std::vector<unsigned> &T, double &ms, bool large = false)
 {
     DeviceBuffers B;
     unsigned short *d_lab;
@@ -347,12 +357,15 @@ static int32_t eloss_T(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld
     HIPCHK(c, B.alloc(d_T, labs.size()));
     HIPCHK(c, hipMemcpyAsync(d_lab, labs.data(), labs.size() * 2, hipMemcpyHostToDevice, st));
     const size_t lds = (size_t)std::min<int64_t>(EG, L) * (size_t)n * 2;
-    HIPCHK(c, hipFuncSetAttribute((const void *)k_eloss, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (!large) HIPCHK(c, hipFuncSetAttribute((const void *)k_eloss, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     TimingEvents ev;
     HIPCHK(c, ev.create());
     HIPCHK(c, ev.begin(st));
-    k_eloss<<<dim3((unsigned)std::min<int64_t>((n + NWAVE - 1) / NWAVE, 256), (unsigned)((L + EG - 1) / EG)), TPB, lds, st>>>(
-        dC, (size_t)ldc, (int)n, d_lab, (int)L, d_T);
+    if (large)
+        HIPCHK(c, launch_eloss_large(st, dC, ldc, n, d_lab, L, d_T));
+    else
+        k_eloss<<<dim3((unsigned)std::min<int64_t>((n + NWAVE - 1) / NWAVE, 256), (unsigned)((L + EG - 1) / EG)), TPB, lds, st>>>(
+            dC, (size_t)ldc, (int)n, d_lab, (int)L, d_T);
     HIPCHK(c, ev.end(st));
     T.resize(labs.size());
     HIPCHK(c, hipMemcpyAsync(T.data(), d_T, T.size() * sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -403,12 +416,12 @@ static hipError_t launch(const unsigned *dC, int64_t ldc, size_t lds, hipStream_
 }
 
 static int32_t check_args(rc_ctx *c, const char *who, int64_t m, int64_t n, int32_t linkage, const void *merges_out, const int64_t *binder_num,
-                          int32_t maxcut, const double *vilb)
+                          int32_t maxcut, const double *vilb, bool large = false)
 {
     if (!merges_out || !binder_num) return fail(c, RC_ERR_ARG, "%s: NULL argument", who);
     if (linkage != RC_HCLUST_AVERAGE && linkage != RC_HCLUST_COMPLETE && linkage != RC_HCLUST_SINGLE)
         return fail(c, RC_ERR_ARG, "%s: invalid linkage specifier %d", who, linkage);
-    const int32_t rc = check_capacity(c, who, m, n);
+    const int32_t rc = check_capacity(c, who, m, n, large);
     if (rc != RC_OK) return rc;
     if (maxcut < 0 || maxcut > n || (maxcut > 0 && !vilb)) return fail(c, RC_ERR_ARG, "%s: need 0 <= maxcut <= n and vilb with maxcut > 0 (got %d)", who, maxcut);
     return RC_OK;
@@ -416,21 +429,22 @@ static int32_t check_args(rc_ctx *c, const char *who, int64_t m, int64_t n, int3
 
 // Everything behind the three entry points.  dC: the device counts (n × ldc), read in place.
 static int32_t run(rc_ctx *c, hipStream_t st, const char *who, const unsigned *dC, int64_t ldc, int64_t m, int64_t n, int32_t linkage,
-                   rc_hclust_merge_t *merges_out, int64_t *binder_num, int32_t maxcut, double *vilb, double *kernel_ms)
+                   rc_hclust_merge_t *merges_out, int64_t *binder_num, int32_t maxcut, double *vilb, double *kernel_ms, bool large = false)
 {
-    int32_t rc = check_counts(c, st, who, dC, ldc, m, n);
-    if (rc != RC_OK) return rc;
+    // every allocation comes before the first kernel: S alone is 8.6 GB at n = 32767, and a failure is RC_ERR_OOM
     DeviceBuffers B;
     Args A{};
     unsigned long long *d_val0, *d_tot;
     unsigned short *d_part0;
     HIPCHK(c, B.alloc(A.S, (size_t)n * n));
     if (linkage != RC_HCLUST_AVERAGE) HIPCHK(c, B.alloc(A.M, (size_t)n * n));
-    HIPCHK(c, B.alloc(d_val0, (size_t)n));
+    HIPCHK(c, B.alloc(d_val0, (size_t)(n + 31) / 32 * 32));             // (whole blocks of 32 rows: the large kernel reads them so)
     HIPCHK(c, B.alloc(d_part0, (size_t)n));
     HIPCHK(c, B.alloc(d_tot, 1));
     HIPCHK(c, B.alloc(A.merges, (size_t)n));                            // (n − 1 used)
     HIPCHK(c, B.alloc(A.bnum, (size_t)n));
+    int32_t rc = check_counts(c, st, who, dC, ldc, m, n);
+    if (rc != RC_OK) return rc;
     HIPCHK(c, hipMemsetAsync(A.merges, 0, (size_t)n * sizeof(Merge), st));
     A.val0 = d_val0; A.part0 = d_part0; A.tot = d_tot; A.n = (int)n; A.m = (unsigned)m;
     const size_t lds = ((size_t)n * 14 + 15) / 16 * 16;
@@ -439,7 +453,8 @@ static int32_t run(rc_ctx *c, hipStream_t st, const char *who, const unsigned *d
     HIPCHK(c, ev.begin(st));
     rc = triu_sum(c, st, dC, ldc, n, d_tot);
     if (rc != RC_OK) return rc;
-    const hipError_t le = linkage == RC_HCLUST_AVERAGE    ? launch<RC_HCLUST_AVERAGE>(dC, ldc, lds, st, d_val0, d_part0, A)
+    const hipError_t le = large                           ? launch_large(linkage, dC, ldc, st, d_val0, d_part0, A)
+                          : linkage == RC_HCLUST_AVERAGE  ? launch<RC_HCLUST_AVERAGE>(dC, ldc, lds, st, d_val0, d_part0, A)
                           : linkage == RC_HCLUST_COMPLETE ? launch<RC_HCLUST_COMPLETE>(dC, ldc, lds, st, d_val0, d_part0, A)
                                                           : launch<RC_HCLUST_SINGLE>(dC, ldc, lds, st, d_val0, d_part0, A);
     if (le != hipSuccess) return fail(c, RC_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(le));
@@ -464,7 +479,7 @@ static int32_t run(rc_ctx *c, hipStream_t st, const char *who, const unsigned *d
             if (!cut_labels(h_mg.data(), n, K, work, nullptr, labs.data() + (size_t)(K - 1) * n))
                 return fail(c, RC_ERR_STATE, "%s: the kernel returned an invalid merge sequence", who);
         std::vector<unsigned> T;
-        rc = eloss_T(c, st, dC, ldc, n, labs, maxcut, T, ms);
+        rc = eloss_T(c, st, dC, ldc, n, labs, maxcut, T, ms, large);
         if (rc != RC_OK) return rc;
         std::vector<long long> cnt((size_t)n + 1);
         for (int64_t K = 1; K <= maxcut; ++K)
@@ -476,7 +491,7 @@ static int32_t run(rc_ctx *c, hipStream_t st, const char *who, const unsigned *d
 
 // rc_psm_expected_loss and its context form behind their argument checks
 static int32_t run_eloss(rc_ctx *c, hipStream_t st, const char *who, const unsigned *dC, int64_t ldc, int64_t m, int64_t n, int32_t loss,
-                         int64_t L, const int64_t *labels, double *loss_out, int64_t *num_out, double *kernel_ms)
+                         int64_t L, const int64_t *labels, double *loss_out, int64_t *num_out, double *kernel_ms, bool large = false)
 {
     int32_t rc = check_label_rows(c, who, "labelling", labels, L, n);
     if (rc != RC_OK) return rc;
@@ -490,7 +505,7 @@ static int32_t run_eloss(rc_ctx *c, hipStream_t st, const char *who, const unsig
     if (rc != RC_OK) return rc;
     std::vector<unsigned> T;
     double ms = 0.0;
-    rc = eloss_T(c, st, dC, ldc, n, labs, L, T, ms);
+    rc = eloss_T(c, st, dC, ldc, n, labs, L, T, ms, large);
     if (rc != RC_OK) return rc;
     long long tot = 0;
     HIPCHK(c, hipMemcpy(&tot, d_tot, sizeof(long long), hipMemcpyDeviceToHost));
@@ -502,12 +517,12 @@ static int32_t run_eloss(rc_ctx *c, hipStream_t st, const char *who, const unsig
 }
 
 static int32_t check_eloss_args(rc_ctx *c, const char *who, int64_t m, int64_t n, int32_t loss, int64_t L, const int64_t *labels,
-                                const double *loss_out, const int64_t *num_out)
+                                const double *loss_out, const int64_t *num_out, bool large = false)
 {
     if (!labels || !loss_out || !num_out) return fail(c, RC_ERR_ARG, "%s: NULL argument", who);
     if (loss != RC_PSM_BINDER && loss != RC_PSM_VILB) return fail(c, RC_ERR_ARG, "%s: invalid loss specifier %d", who, loss);
     if (L < 1) return fail(c, RC_ERR_ARG, "%s: need at least one labelling (got %lld)", who, (long long)L);
-    const int32_t rc = check_capacity(c, who, m, n);
+    const int32_t rc = check_capacity(c, who, m, n, large);
     if (rc != RC_OK) return rc;
     if (L > LMAX) return fail(c, RC_ERR_CAPACITY, "%s: %lld labellings exceed the %lld of one call", who, (long long)L, (long long)LMAX);
     return RC_OK;
@@ -515,22 +530,22 @@ static int32_t check_eloss_args(rc_ctx *c, const char *who, int64_t m, int64_t n
 
 // The entry points of both consumers: cnt::with puts the counts of src on the device between the argument checks and the run
 static int32_t dendrogram(const char *who, const cnt::Source &src, int32_t linkage, void *merges_out, int64_t *binder_num, int32_t maxcut,
-                          double *vilb, double *kernel_ms)
+                          double *vilb, double *kernel_ms, bool large = false)
 {
     return cnt::with(
-        who, src, [&](rc_ctx *c, int64_t m, int64_t n) { return check_args(c, who, m, n, linkage, merges_out, binder_num, maxcut, vilb); },
+        who, src, [&](rc_ctx *c, int64_t m, int64_t n) { return check_args(c, who, m, n, linkage, merges_out, binder_num, maxcut, vilb, large); },
         [&](rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ldc, int64_t m, int64_t n) {
-            return run(c, st, who, dC, ldc, m, n, linkage, (rc_hclust_merge_t *)merges_out, binder_num, maxcut, vilb, kernel_ms);
+            return run(c, st, who, dC, ldc, m, n, linkage, (rc_hclust_merge_t *)merges_out, binder_num, maxcut, vilb, kernel_ms, large);
         });
 }
 
 static int32_t expected_loss(const char *who, const cnt::Source &src, int32_t loss, int64_t L, const int64_t *labels, double *loss_out,
-                             int64_t *num_out, double *kernel_ms)
+                             int64_t *num_out, double *kernel_ms, bool large = false)
 {
     return cnt::with(
-        who, src, [&](rc_ctx *c, int64_t m, int64_t n) { return check_eloss_args(c, who, m, n, loss, L, labels, loss_out, num_out); },
+        who, src, [&](rc_ctx *c, int64_t m, int64_t n) { return check_eloss_args(c, who, m, n, loss, L, labels, loss_out, num_out, large); },
         [&](rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ldc, int64_t m, int64_t n) {
-            return run_eloss(c, st, who, dC, ldc, m, n, loss, L, labels, loss_out, num_out, kernel_ms);
+            return run_eloss(c, st, who, dC, ldc, m, n, loss, L, labels, loss_out, num_out, kernel_ms, large);
         });
 }
 
@@ -555,15 +570,21 @@ extern "C" int32_t rc_hclust_ctx(rc_ctx *c, int64_t numsamples, int32_t linkage,
     return hcl::dendrogram("rc_hclust_ctx", cnt::context(c, numsamples), linkage, merges_out, binder_num, maxcut, vilb, kernel_ms);
 }
 
-extern "C" int32_t rc_hclust_cut(const void *merges, int64_t n, int64_t K, int64_t *labels_out)
+namespace hcl {
+static int32_t cut(const char *who, int nmax, const void *merges, int64_t n, int64_t K, int64_t *labels_out)
 {
-    const char *who = "rc_hclust_cut";
     if (!labels_out || (!merges && n > 1)) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
-    if (n < 1 || n > LDS_NMAX || K < 1 || K > n) return fail(nullptr, RC_ERR_ARG, "%s: need 1 <= K <= n <= %d (got K=%lld n=%lld)", who, LDS_NMAX, (long long)K, (long long)n);
+    if (n < 1 || n > nmax || K < 1 || K > n) return fail(nullptr, RC_ERR_ARG, "%s: need 1 <= K <= n <= %d (got K=%lld n=%lld)", who, nmax, (long long)K, (long long)n);
     std::vector<int> work;
-    if (!hcl::cut_labels((const hcl::Merge *)merges, n, K, work, labels_out, nullptr))
+    if (!cut_labels((const Merge *)merges, n, K, work, labels_out, nullptr))
         return fail(nullptr, RC_ERR_ARG, "%s: the merges are not a sequence of merges of active clusters a < b", who);
     return RC_OK;
+}
+}  // namespace hcl
+
+extern "C" int32_t rc_hclust_cut(const void *merges, int64_t n, int64_t K, int64_t *labels_out)
+{
+    return hcl::cut("rc_hclust_cut", LDS_NMAX, merges, n, K, labels_out);
 }
 
 extern "C" int32_t rc_psm_expected_loss(int32_t device, const void *counts, int64_t m, int64_t n, int32_t loss, int64_t L,

@@ -7534,6 +7534,7 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #undef VISL_GROUPED
 #include "visearch.inc.hip"
 #include "hclust.inc.hip"
+#include "hclust_large.inc.hip"      // k_hclust_large<LINK>, k_eloss_large<EGT>: the same with n <= 32767
 #include "slabplan.inc.hpp"
 #include "slab.inc.hip"
 #include "predict.inc.hip"

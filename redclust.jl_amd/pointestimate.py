@@ -382,12 +382,26 @@ def hclust(samples_or_counts=None, linkage="average", *, numsamples=None, ctx=No
     member), then the smallest partner; everything is exact integer arithmetic, so a run is reproducible bit for bit.
     Returns a dict: merges (records a, b, size, m_ab, s_ab per step, names 1-based), binder_num (the exact Binder numerator
     of the partition after t merges, t = 0..n−1), Z (linkage_matrix: usable with scipy.cluster.hierarchy.dendrogram),
-    order (leaf_order(Z)), kernel_ms.  There is no CPU fallback."""
+    order (leaf_order(Z)), kernel_ms.  There is no CPU fallback.  n <= 8192; dendrogram is the same without that limit."""
+    return _dendrogram(samples_or_counts, linkage, numsamples, ctx, device, large=False)
+
+
+def dendrogram(samples_or_counts=None, linkage="average", *, numsamples=None, ctx=None, device: int = 0):
+    """hclust — arguments, result — for any n <= 32767 (m·n < 2^31).  Up to n = 8192 it is hclust's call and returns its bytes;
+    above that the kernel is csrc/hclust_large.inc.hip (rc_hclust_large*): the same integer function of the counts, with a
+    partner and a size per point in LDS and the cached values in device memory.  Device memory at n = 32767: 8.6 GB for the
+    pair sums, 4.3 GB more for "complete" / "single", beside the counts' 4.3 GB."""
+    return _dendrogram(samples_or_counts, linkage, numsamples, ctx, device, large=True)
+
+
+def _dendrogram(samples_or_counts, linkage, numsamples, ctx, device, large):
+    """hclust (large=False: n <= 8192) and dendrogram (large=True: the large entries above 8192 points)"""
     if linkage not in _LINKAGES:
         raise ValueError("Invalid linkage specifier.")
     S, counts, m, n = _counts_input(samples_or_counts, numsamples, ctx)
-    _check_lds_n(n, "hclust")
-    res = _lib.hclust(counts, m, _LINKAGES[linkage], device=device, ctx=ctx, samples=S)
+    if not large:
+        _check_lds_n(n, "hclust")
+    res = _lib.hclust(counts, m, _LINKAGES[linkage], device=device, ctx=ctx, samples=S, large=n > _LDS_NMAX)
     Z = linkage_matrix(res["merges"], m, linkage)
     out = dict(merges=res["merges"], binder_num=res["binder_num"], Z=Z, order=leaf_order(Z), kernel_ms=res["kernel_ms"])
     if "counts_ms" in res:
@@ -395,10 +409,12 @@ def hclust(samples_or_counts=None, linkage="average", *, numsamples=None, ctx=No
     return out
 
 
-def _hclust_cuts(samples_or_counts, linkage, maxK, numsamples, ctx, device, *, lo=1, exact=False, vilb=False, cuts=True):
+def _hclust_cuts(samples_or_counts, linkage, maxK, numsamples, ctx, device, large=False, *, lo=1, exact=False, vilb=False, cuts=True,
+                 polish=False):
     """What the criteria of hclustpointestimate share: the linkage and the input checked (exact: the samples only), maxK
     defaulted to ⌈n/8⌉ (at least lo, n permitting) and checked to lie in lo..n, the dendrogram (vilb: with the VI bound of the
-    cuts 1..maxK) and, unless cuts=False, the stacked cuts of lo..maxK clusters.  Returns (res, cuts, S, m, n, maxK)."""
+    cuts 1..maxK) and, unless cuts=False, the stacked cuts of lo..maxK clusters.  Returns (res, cuts, S, m, n, maxK).  large:
+    no limit of 8192 points here, and above it rc_hclust_large* and rc_hclust_cut_large."""
     if linkage not in _LINKAGES:
         raise ValueError("Invalid linkage specifier.")
     if exact and ctx is not None:
@@ -406,12 +422,16 @@ def _hclust_cuts(samples_or_counts, linkage, maxK, numsamples, ctx, device, *, l
     if exact and not hasattr(samples_or_counts, "clusts"):
         raise ValueError("exact=True needs the samples (an MCMCResult), not a count matrix")
     S, counts, m, n = _counts_input(samples_or_counts, numsamples, ctx)
-    _check_lds_n(n, "hclustpointestimate")
+    if not large:
+        _check_lds_n(n, "hclustpointestimate")
+    big = n > _LDS_NMAX
+    if polish and big:
+        raise ValueError(f"polish=True runs searchmapestimate, which is limited to n <= {_LDS_NMAX} (got n = {n})")
     maxK = int(maxK) if maxK else max(-(-n // 8), min(n, lo))
     if not lo <= maxK <= n:
         raise ValueError("maxK must lie in 1..n" if lo == 1 else "maxK must lie in 2..n with criterion='silhouette'")
-    res = _lib.hclust(counts, m, _LINKAGES[linkage], maxcut=maxK if vilb else 0, device=device, ctx=ctx, samples=S)
-    stacked = np.stack([_lib.hclust_cut(res["merges"], n, K) for K in range(lo, maxK + 1)]) if cuts else None
+    res = _lib.hclust(counts, m, _LINKAGES[linkage], maxcut=maxK if vilb else 0, device=device, ctx=ctx, samples=S, large=big)
+    stacked = np.stack([_lib.hclust_cut(res["merges"], n, K, large=big) for K in range(lo, maxK + 1)]) if cuts else None
     return res, stacked, S, m, n, maxK
 
 
@@ -440,12 +460,32 @@ def hclustpointestimate(samples_or_counts=None, loss="VI", linkage="average", *,
     sums of D on the device, the quotients on the host) among the cuts of 2..maxK clusters (one cluster has silhouette 0 by
     convention and is not a candidate; maxK >= 2), the fewest clusters on a float tie.  One device pass over the matrix of
     data (as above) for all cuts; it needs no params, r or p.  info has K, mean_silhouette (per K = 2..maxK), merges,
-    binder_num, kernel_ms, profile_ms."""
+    binder_num, kernel_ms, profile_ms.
+
+    n <= 8192; dendrogrampointestimate is the same without that limit."""
+    return _hclustpointestimate(samples_or_counts, loss, linkage, maxK, numsamples, ctx, device, exact, criterion, data, params, r, p,
+                                polish, large=False)
+
+
+def dendrogrampointestimate(samples_or_counts=None, loss="VI", linkage="average", *, maxK: int = 0, numsamples=None, ctx=None,
+                            device: int = 0, exact: bool = False, criterion: str = "loss", data=None, params=None, r=None, p=None,
+                            polish: bool = False):
+    """hclustpointestimate — arguments, every criterion, exact=, results — for any n <= 32767 (m·n < 2^31).  Up to n = 8192 it is
+    hclustpointestimate's call and returns its bytes; above that the dendrogram and the VI bound of its cuts come from
+    csrc/hclust_large.inc.hip (rc_hclust_large*, rc_hclust_cut_large) — the deterministic init= for searchpointestimate and
+    searchvi at that size.  polish=True stays bound by searchmapestimate's n <= 8192 (ValueError above)."""
+    return _hclustpointestimate(samples_or_counts, loss, linkage, maxK, numsamples, ctx, device, exact, criterion, data, params, r, p,
+                                polish, large=True)
+
+
+def _hclustpointestimate(samples_or_counts, loss, linkage, maxK, numsamples, ctx, device, exact, criterion, data, params, r, p, polish,
+                         large):
+    """hclustpointestimate (large=False) and dendrogrampointestimate (large=True)"""
     if criterion not in ("loss", "posterior", "silhouette"):
         raise ValueError("criterion must be 'loss', 'posterior' or 'silhouette'")
     if polish and criterion != "posterior":
         raise ValueError("polish=True goes with criterion='posterior'")
-    source = (samples_or_counts, linkage, maxK, numsamples, ctx, device)
+    source = (samples_or_counts, linkage, maxK, numsamples, ctx, device, large)
     if criterion != "loss":
         if exact:
             raise ValueError(f"exact=True chooses by expected loss; it does not go with criterion='{criterion}'")
@@ -469,7 +509,7 @@ def hclustpointestimate(samples_or_counts=None, loss="VI", linkage="average", *,
             params = getattr(samples_or_counts, "params", None)
         if r is None or p is None:
             raise ValueError("criterion='posterior' needs r and p")
-        res, cuts, _, _, _, _ = _hclust_cuts(*source)
+        res, cuts, _, _, _, _ = _hclust_cuts(*source, polish=polish)
         clust, sc = mapestimate(data, cuts, params, r, p, device=device)
         info = dict(merges=res["merges"], binder_num=res["binder_num"], kernel_ms=res["kernel_ms"], score_ms=sc["kernel_ms"],
                     loglik=sc["loglik"], logprior=sc["logprior"], logposterior=sc["logposterior"], K=sc["index"] + 1)
@@ -499,7 +539,7 @@ def hclustpointestimate(samples_or_counts=None, loss="VI", linkage="average", *,
         info["loss"] = res["vilb"]
         K = int(np.argmin(info["loss"])) + 1
     info["K"] = K
-    return _lib.hclust_cut(res["merges"], n, K), info
+    return _lib.hclust_cut(res["merges"], n, K, large=n > _LDS_NMAX), info
 
 
 def expectedlosses(labellings, counts_or_samples=None, numsamples=None, loss="VI", *, ctx=None, device: int = 0):
@@ -507,7 +547,8 @@ def expectedlosses(labellings, counts_or_samples=None, numsamples=None, loss="VI
     (copied to the device once for the batch), against ctx= with numsamples (its device counts, in place, no copy), or against an
     MCMCResult — its counts are built on the device, but come back to the host and go in again as a count matrix: there is no
     samples entry point for this call, so hold the counts (posterior_counts) when evaluating several batches.
-    Returns (loss[L], num[L]): num is the exact Binder numerator (0 for "VI")."""
+    Returns (loss[L], num[L]): num is the exact Binder numerator (0 for "VI").  n <= 32767: up to 8192 points the kernel stages 8
+    labellings per LDS group (rc_psm_expected_loss), above that 4 or 2 (rc_psm_expected_loss_large)."""
     if loss not in _PSM_LOSSES:
         raise ValueError("Invalid loss function specifier.")
     labs = np.stack([_labels(c) for c in np.atleast_2d(np.asarray(labellings))])
@@ -516,7 +557,7 @@ def expectedlosses(labellings, counts_or_samples=None, numsamples=None, loss="VI
         raise ValueError("every labelling must have n entries")
     if S is not None:
         counts = _lib.samples_counts(S, device=device)[0]
-    out_loss, num, _ = _lib.psm_expected_loss(labs, counts, m, _PSM_LOSSES[loss], device=device, ctx=ctx)
+    out_loss, num, _ = _lib.psm_expected_loss(labs, counts, m, _PSM_LOSSES[loss], device=device, ctx=ctx, large=n > _LDS_NMAX)
     return out_loss, num
 
 

@@ -5,6 +5,7 @@ NumPy's expectedloss for one labelling.
     python tools/time_hclust.py                    # n = 2000 and 8192, median of 5 repetitions
     python tools/time_hclust.py --n 2000 --reps 7
     python tools/time_hclust.py --no-host          # skip SciPy and NumPy
+    python tools/time_hclust.py --large            # the large-n kernels: n = 8192, 16384, 32767 (see large() below)
 
 Inputs: a planted partition with K = 50 clusters, 20 % of the points relabelled at random in each of m = 1000 samples
 (seed 0); the counts are built on the device (rc_samples_counts) and handed to the timed calls as a host matrix, so every
@@ -49,9 +50,63 @@ def timed(reps, fn):
     return walls, outs
 
 
+def large(a):
+    """--large: the kernels for n <= 32767 (csrc/hclust_large.inc.hip).  Per n (default 8192, 16384, 32767) and linkage the
+    median kernel time of _lib.hclust_large after a warm-up run; at n <= 8192 also rc_hclust's in the same process and the
+    ratio; the Binder curve against expectedlosses' numerators at a handful of cuts; dendrogrampointestimate(…, "VI") end to
+    end with the default maxK at the largest n; and, unless --no-host, SciPy's linkage on the host at n = 16384."""
+    for n in a.n or [8192, 16384, 32767]:
+        S = planted_samples(n, a.m, a.K, a.noise)
+        C = _lib.samples_counts(S)[0]
+        runs = {}
+        for name, l in LINKAGES.items():
+            _lib.hclust_large(C, a.m, l)                                            # warm-up
+            _, outs = timed(a.reps, lambda: _lib.hclust_large(C, a.m, l))
+            ms = statistics.median(o["kernel_ms"] for o in outs)
+            rec = dict(what="linkage, large kernel", linkage=name, n=n, m=a.m, reps=a.reps, kernel_ms_median=round(ms, 3),
+                       us_per_step=round(1e3 * ms / (n - 1), 3))
+            if n <= 8192:
+                _lib.hclust(C, a.m, l)
+                _, old = timed(a.reps, lambda: _lib.hclust(C, a.m, l))
+                oms = statistics.median(o["kernel_ms"] for o in old)
+                rec.update(rc_hclust_kernel_ms_median=round(oms, 3), ratio_to_rc_hclust=round(ms / oms, 3),
+                           same_bytes=old[-1]["merges"].tobytes() == outs[-1]["merges"].tobytes())
+            runs[name] = outs[-1]
+            print(json.dumps(rec), flush=True)
+        ks = sorted({1, 2, a.K, 1024, n})
+        cuts = np.stack([_lib.hclust_cut_large(runs["average"]["merges"], n, K) for K in ks])
+        num = _lib.psm_expected_loss_large(cuts, C, a.m, 0)[1]
+        print(json.dumps(dict(what="check", n=n, cuts=ks, num=[int(x) for x in num], binder_curve_equals_expectedlosses=bool(
+            all(int(x) == int(runs["average"]["binder_num"][n - K]) for x, K in zip(num, ks))))), flush=True)
+        if n == max(a.n or [32767]):
+            walls, outs = timed(a.reps, lambda: rc.dendrogrampointestimate(C, "VI", "average", numsamples=a.m))
+            info = outs[-1][1]
+            print(json.dumps(dict(what="dendrogrampointestimate", loss="VI", linkage="average", n=n, m=a.m, cuts=len(info["loss"]),
+                                  K=info["K"], kernel_ms=round(info["kernel_ms"], 3), wall_s_median=round(statistics.median(walls), 3))),
+                  flush=True)
+        if n == 16384 and not a.no_host:
+            try:
+                from scipy.cluster.hierarchy import linkage
+                from scipy.spatial.distance import squareform
+            except ImportError:
+                print(json.dumps(dict(what="scipy linkage", n=n, skipped="SciPy is not installed")), flush=True)
+                continue
+            D = 1.0 - C.astype(np.float64) / a.m
+            np.fill_diagonal(D, 0.0)
+            y = squareform(D, checks=False)
+            for name in LINKAGES:
+                t0 = time.perf_counter()
+                Z = linkage(y, name)
+                t_sp = time.perf_counter() - t0
+                ours = rc.linkage_matrix(runs[name]["merges"], a.m, name)[:, 2]
+                print(json.dumps(dict(what="scipy linkage", linkage=name, n=n, wall_s=round(t_sp, 3), heights_equal_as_multiset=bool(
+                    np.allclose(np.sort(Z[:, 2]), np.sort(ours), rtol=0, atol=1e-12)))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--n", type=int, nargs="*", default=[2000, 8192])
+    ap.add_argument("--large", action="store_true")
+    ap.add_argument("--n", type=int, nargs="*", default=None)
     ap.add_argument("--m", type=int, default=1000)
     ap.add_argument("--K", type=int, default=50)
     ap.add_argument("--noise", type=float, default=0.2)
@@ -61,7 +116,9 @@ def main():
     warm = _lib.samples_counts(planted_samples(64, 5, 3, 0.1))[0]
     for l in LINKAGES.values():
         _lib.hclust(warm, 5, l, maxcut=8)                                   # module load, first launches
-    for n in a.n:
+    if a.large:
+        return large(a)
+    for n in a.n or [2000, 8192]:
         S = planted_samples(n, a.m, a.K, a.noise)
         C = _lib.samples_counts(S)[0]
         runs = {}

@@ -712,7 +712,7 @@ int32_t rc_vi_search_groups(int32_t device, const int64_t *samples /* m×n, labe
  * kernel at every n.  Capacity: n <= 32767 in place of n <= 8192 — RC_ERR_CAPACITY with "32767" in the message, at the
  * same place in the order of the checks; the grouped entry's m·n < 2^31, m·n <= 2^26 (per group in the grouped form), the slot cap
  * <= 1024 and the 4 GiB table budget are unchanged.  RC_ERR_STATE: the table could not be split (an internal error: it is not
- * non-decreasing below 12·2^32) — never a wrong answer.  rc_id_search keeps n <= 8192.
+ * non-decreasing below 12·2^32) — never a wrong answer.  rc_id_search keeps n <= 8192; rc_id_search_large is below.
  * ------------------------------------------------------------------------------------------------------------- */
 int32_t rc_vi_search_large(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n, int32_t nruns,
                            const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */,
@@ -726,6 +726,24 @@ int32_t rc_vi_search_groups_large(int32_t device, const int64_t *samples /* m×n
                                   void *runs_out /* rc_psm_run_t[nruns] */,
                                   int32_t *best /* ngroups: first run of minimal loss_num within the group, -1 = no run */,
                                   double *kernel_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * The exact expected-ID search beyond n = 8192 (DESIGN.md §8 "Exact expected ID search, large n"): rc_id_search's arguments,
+ * checks in their order, messages (under this name), run semantics and results — a run is the same integer function of its
+ * arguments, so wherever both run this entry returns rc_id_search's bytes — by rc_vi_search_large's kernel layout (labels in
+ * the output row, the split table) with the information distance's score.  It launches that kernel at every n.
+ * Capacity is rc_vi_search_large's: n <= 32767 (RC_ERR_CAPACITY with "32767" in the message), m·n <= 2^26, the slot cap <= 1024,
+ * the 4 GiB table budget; RC_ERR_STATE as there.
+ * The sorted Bq_s and their prefix sums sit whole in the workgroup's LDS where their 16·(m+1) bytes fit beside the rest; else
+ * LDS keeps a fence of every 2^s-th Bq_s (s the smallest for which it fits), the search for p(x) = #{t : Bq_t <= x} ends with s
+ * probes of the sorted array in global memory and reads one prefix sum there — p(x), and so every result, is the same integer
+ * either way.  RC_ID_TABLE_GLOBAL=1 in the environment (read at every call) forces the fence, with s >= max(1, nbits − 2),
+ * nbits = ceil(log2(m + 1)): a search then probes at both levels.  For tests.
+ * ------------------------------------------------------------------------------------------------------------- */
+int32_t rc_id_search_large(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n, int32_t nruns,
+                           const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */,
+                           int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */, void *runs_out /* rc_psm_run_t[nruns] */,
+                           int32_t *best, double *kernel_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Hierarchical point estimates: agglomerative clustering of the co-clustering counts (Medvedovic's method; mcclust's

@@ -362,7 +362,8 @@ function searchpointestimate(b::HIPBackend, result; loss::String = "VI", nruns::
                              maxsweeps::Integer = 100, seed::Integer = 0, exact::Bool = false)
     code = Dict("binder" => 0, "VI" => 1)
     (loss == "ID" || exact) && length(result.clusts[1]) > LDS_NMAX &&
-        throw(ArgumentError("loss = \"ID\" and exact = true are limited to n <= $LDS_NMAX; above that only loss = \"binder\" or \"VI\" with exact = false runs, up to n = 32767"))
+        throw(ArgumentError("loss = \"ID\" and exact = true are limited to n <= $LDS_NMAX; above that loss = \"binder\" or \"VI\" with exact = false runs here, " *
+                            "and searchvi / searchid are the two exact searches, up to n = 32767"))
     loss == "ID" && return searchexactid(b, result, nruns, maxK, maxsweeps, seed)
     haskey(code, loss) || throw(ArgumentError("Invalid loss function specifier."))
     if exact
@@ -566,10 +567,17 @@ function searchexactid(b::HIPBackend, result, nruns::Integer, maxK::Integer, max
     labels = Matrix{Int64}(undef, n, R)
     runs = Vector{RcPsmRun}(undef, R)
     best = Int32[0]
-    rc = ccall((:rc_id_search, LIB), Int32,
-               (Int32, Ptr{Int64}, Int64, Int64, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
-                Ptr{Int32}, Ptr{Cdouble}),
-               b.device, samples, m, n, R, init, order, cap, maxsweeps, labels, runs, best, C_NULL)
+    rc = if n > LDS_NMAX                                         # the same search by the kernel for n <= 32767 (searchid)
+        ccall((:rc_id_search_large, LIB), Int32,
+              (Int32, Ptr{Int64}, Int64, Int64, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
+               Ptr{Int32}, Ptr{Cdouble}),
+              b.device, samples, m, n, R, init, order, cap, maxsweeps, labels, runs, best, C_NULL)
+    else
+        ccall((:rc_id_search, LIB), Int32,
+              (Int32, Ptr{Int64}, Int64, Int64, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
+               Ptr{Int32}, Ptr{Cdouble}),
+              b.device, samples, m, n, R, init, order, cap, maxsweeps, labels, runs, best, C_NULL)
+    end
     check(Ptr{Cvoid}(C_NULL), rc)
     info = (loss = [x.loss for x in runs], loss_num = [x.loss_num for x in runs], sweeps = [Int(x.sweeps) for x in runs],
             converged = [x.converged != 0 for x in runs], moves = [Int(x.moves) for x in runs], K = [Int(x.K) for x in runs],
@@ -577,6 +585,16 @@ function searchexactid(b::HIPBackend, result, nruns::Integer, maxK::Integer, max
     return (labels[:, best[1] + 1], info)
 end
 
+"""
+    searchid(HIPBackend(), result; nruns = 16, maxK = 0, maxsweeps = 100, seed = 0) -> (clust, info)
+
+The exact expected-ID search at any n <= 32767: `searchpointestimate(…; loss = "ID")` — its runs, its results, its bytes up to
+n = 8192 — and above that the same search by rc_id_search_large, with the exact-VI start from `searchvi`.
+"""
+searchid(b::HIPBackend, result; nruns::Integer = 16, maxK::Integer = 0, maxsweeps::Integer = 100, seed::Integer = 0) =
+    searchexactid(b, result, nruns, maxK, maxsweeps, seed)
+
+export searchid
 export searchpointestimate, posteriorcounts
 
 # rc_pear_run_t

@@ -246,6 +246,8 @@ SIGNATURES = {
                                         C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "rc_vi_search_large": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_id_search_large": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rc_vi_search_groups_large": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.POINTER(C.c_double)]),
@@ -1040,6 +1042,12 @@ def id_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device:
     """rc_id_search: the exact expected-ID search.  Arguments and the returned dict as vi_search; loss is the expected
     information distance (nats), loss_num the integer Q_ID."""
     return _exact_search(lib().rc_id_search, samples, init, order, maxK, maxsweeps, device)
+
+
+def id_search_large(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
+    """rc_id_search_large: id_search — arguments, results, bits — by the kernel whose capacity is n <= 32767 (k_idlarge of
+    csrc/visearch_large.inc.hip), at every n."""
+    return _exact_search(lib().rc_id_search_large, samples, init, order, maxK, maxsweeps, device)
 
 
 def vi_search_groups(samples, group, init, order, run_group, maxK: int = 0, maxsweeps: int = 100, device: int = 0, large: bool = False):

@@ -7532,6 +7532,9 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #define VISL_GROUPED
 #include "visearch_large.inc.hip"    // the same text again: k_vilarge_groups<PQ>
 #undef VISL_GROUPED
+#define VISL_ID
+#include "visearch_large.inc.hip"    // and once more: k_idlarge<PQ>, the expected information distance
+#undef VISL_ID
 #include "visearch.inc.hip"
 #include "hclust.inc.hip"
 #include "hclust_large.inc.hip"      // k_hclust_large<LINK>, k_eloss_large<EGT>: the same with n <= 32767

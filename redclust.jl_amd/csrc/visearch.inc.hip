@@ -1,4 +1,4 @@
-// The host side of the exact searches (rc_vi_search, rc_id_search, rc_vi_search_groups and the two _large entries): the launch, the
+// The host side of the exact searches (rc_vi_search, rc_id_search, rc_vi_search_groups and the three _large entries): the launch, the
 // fixed-point table, the checks, the staging of the samples and the runs, the results.  The kernels and their arguments are
 // visearch_kernel.inc.hip's and visearch_large.inc.hip's, included in front of this file.  Same translation unit as redclust_hip.hip: shares fail(), HIPCHK, the error buffer; the
 // holders, check_label_rows, check_lds_capacity and select_device of hostutil.inc.hip; and from greedy.inc.hip the shared
@@ -24,12 +24,13 @@ static hipError_t launch(int PQ, int nruns, size_t lds, const Args &A)
 }
 
 // The large-n kernels (visearch_large.inc.hip) behind the same arguments, with the thresholds of the split table beside them
-static hipError_t launch_large(bool grouped, int PQ, int nruns, size_t lds, const Args &A, const GqSplit &split)
+// (and, for k_idlarge's fenced table, the fence's shift)
+static hipError_t launch_large(bool grouped, bool id, int PQ, int nruns, size_t lds, const Args &A, const GqSplit &split, int fshift = 0)
 {
-    const ArgsL AL{A, split};
+    const ArgsL AL{A, split, fshift};
 #define VISL_LAUNCH(QQ)                                                                                                   \
     do {                                                                                                                  \
-        void (*kernel)(ArgsL) = grouped ? k_vilarge_groups<QQ> : k_vilarge<QQ>;                                    \
+        void (*kernel)(ArgsL) = grouped ? k_vilarge_groups<QQ> : id ? k_idlarge<QQ> : k_vilarge<QQ>;               \
         hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   \
         if (e != hipSuccess) return e;                                                                                    \
         kernel<<<nruns, TPB, lds, 0>>>(AL);                                                                               \
@@ -201,8 +202,10 @@ static int32_t run(int loss, bool large, const char *who, int32_t device, const 
     A.n = (int)n; A.m = (int)m; A.Lmax = Lmax; A.kpad = kpad; A.Kcap = Kcap; A.maxsweeps = maxsweeps;
     const int PQ = stage_depth(m);
     size_t lds = large ? CarveL((int)n, kpad, Kcap, PQ).total : Carve((int)n, kpad, Kcap, PQ).total;
+    int fshift = 0;
     if (loss == LOSS_ID) {
-        // F's table: the Bq_s ascending and their prefix sums; in LDS behind Aq where that fits, else read from global memory
+        // F's table: the Bq_s ascending and their prefix sums; in LDS behind Aq where that fits, else read from global memory —
+        // large: from global memory behind a fence of every 2^fshift-th Bq_s in what LDS is left
         std::sort(Bs.begin(), Bs.end());
         std::vector<long long> Pre((size_t)m + 1, 0);
         for (int64_t s = 0; s < m; ++s) Pre[(size_t)s + 1] = Pre[(size_t)s] + Bs[(size_t)s];
@@ -216,11 +219,19 @@ static int32_t run(int loss, bool large, const char *who, int32_t device, const 
         A.Bs = d_Bs; A.Pre = d_Pre; A.Aq0 = d_Aq;
         while ((1ll << A.nbits) < m + 1) ++A.nbits;                     // p(x) is in 0..m
         const bool force_global = env_flag("RC_ID_TABLE_GLOBAL");       // tests: force the global-memory table at small m
-        A.tab_lds = (!force_global && lds + 16 * ((size_t)m + 1) <= LDS_MAX) ? 1 : 0;
-        lds += A.tab_lds ? 16 * ((size_t)m + 1) : 16;
+        const size_t room = LDS_MAX - (large ? STATIC_L : 0);
+        A.tab_lds = (!force_global && lds + 16 * ((size_t)m + 1) <= room) ? 1 : 0;
+        if (large && !A.tab_lds) {
+            // the smallest shift whose fence fits (m >> nbits = 0 does); forced: one that leaves trips at both levels
+            while (fshift < A.nbits && lds + 16 + 8 * ((size_t)m >> fshift) > room) ++fshift;
+            if (force_global) fshift = std::max(fshift, std::max(1, A.nbits - 2));
+            fshift = std::min(fshift, A.nbits);
+            lds += 16 + 8 * ((size_t)m >> fshift);
+        } else
+            lds += A.tab_lds ? 16 * ((size_t)m + 1) : 16;
     }
     HIPCHK(nullptr, S.begin(0));
-    HIPCHK(nullptr, large ? launch_large(false, PQ, nruns, lds, A, split)
+    HIPCHK(nullptr, large ? launch_large(false, loss == LOSS_ID, PQ, nruns, lds, A, split, fshift)
                           : loss == LOSS_ID ? launch<LOSS_ID>(PQ, nruns, lds, A) : launch<LOSS_VI>(PQ, nruns, lds, A));
     std::vector<RunOut> h_out;
     HIPCHK(nullptr, S.collect(0, h_out, kernel_ms));
@@ -339,7 +350,7 @@ static int32_t run_groups(bool large, const char *who, int32_t device, const int
     const int PQ = stage_depth(m_max);
     const size_t lds = large ? CarveL((int)n, kpad, Kcap_max, PQ).total : Carve((int)n, kpad, Kcap_max, PQ).total;
     HIPCHK(nullptr, S.begin(0));
-    HIPCHK(nullptr, large ? launch_large(true, PQ, nruns, lds, A, split) : (launch<LOSS_VI, true>(PQ, nruns, lds, A)));
+    HIPCHK(nullptr, large ? launch_large(true, false, PQ, nruns, lds, A, split) : (launch<LOSS_VI, true>(PQ, nruns, lds, A)));
     std::vector<RunOut> h_out;
     HIPCHK(nullptr, S.collect(0, h_out, kernel_ms));
 
@@ -398,6 +409,14 @@ extern "C" int32_t rc_vi_search_large(int32_t device, const int64_t *samples, in
                                       int32_t *best, double *kernel_ms)
 {
     return visearch::run(visearch::LOSS_VI, true, "rc_vi_search_large", device, samples, m, n, nruns, init, order, maxK, maxsweeps,
+                         labels_out, runs_out, best, kernel_ms);
+}
+
+extern "C" int32_t rc_id_search_large(int32_t device, const int64_t *samples, int64_t m, int64_t n, int32_t nruns, const int64_t *init,
+                                      const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out,
+                                      int32_t *best, double *kernel_ms)
+{
+    return visearch::run(visearch::LOSS_ID, true, "rc_id_search_large", device, samples, m, n, nruns, init, order, maxK, maxsweeps,
                          labels_out, runs_out, best, kernel_ms);
 }
 

@@ -1,6 +1,8 @@
 // The exact expected VI search of visearch_kernel.inc.hip for n <= 32767 (DESIGN.md §8 "Exact expected VI search, large n"): the
-// device side of rc_vi_search_large and rc_vi_search_groups_large.  Included behind visearch_kernel.inc.hip TWICE, as that file is:
-// plainly it defines the declarations and k_vilarge<PQ>; with VISL_GROUPED defined, from the same text, k_vilarge_groups<PQ>.
+// device side of rc_vi_search_large, rc_vi_search_groups_large and rc_id_search_large.  Included behind visearch_kernel.inc.hip THREE
+// times: plainly it defines the declarations and k_vilarge<PQ>; with VISL_GROUPED defined, from the same text, k_vilarge_groups<PQ>;
+// with VISL_ID defined, k_idlarge<PQ> (below, "ID").  GROUPED and ID are constants folded at the top of the kernel, not template
+// parameters: the names and the instructions of the first two do not depend on the third being there.
 //
 // The criterion (LOSS_VI), a run, the tie rules, maxK, the moves / sweeps / converged bookkeeping, the final Q from Φq, the 1024
 // threads of one persistent workgroup per run, the (r, c) ownership of the table cells, the two barriers of a step and the LDS
@@ -21,14 +23,29 @@
 //
 // LDS (dynamic, 16-byte offsets): lo u32[n+1], acc u64[kpad], the reduction partials, sz u16[Kcap+2], the label double buffer
 // u16[2][1024·PQ]: 158 160 B at n = 32767, Kcap = 1024, PQ = 4; static: oct u32[32] and pub u32[2].
+//
+// ID (k_idlarge<PQ>, rc_id_search_large; DESIGN.md §8 "Exact expected ID search, large n"): the step above with k_visearch<LOSS_ID>'s
+// additions.  Phase B scores slot k as F(A0 + Gq[n_k]) − F(A0) − acc_k, Gq[·] from gq_at (there is no i64 table in LDS), A0 = Aq
+// without the visited point; thread 0 keeps Aq (LDS, behind the carve) up to date in phase C under sz's discipline; the final Q is
+// F(Aq) − Σ Φq(N).  F(x) = x·p(x) + Pre[m] − Pre[p(x)], p(x) = #{t : Bs[t] <= x}, needs the sorted Bs i64[m] and Pre i64[m+1]:
+//   whole (A.tab_lds)  both in LDS behind Aq, 16·(m+1) B with it, where that fits beside the carve and the static LDS — every
+//                      m <= 1024 at any n; id_F2 as it stands.
+//   fenced             otherwise (at n = 32767, m = 2048, PQ = 4, Kcap = 1024 the carve leaves 5 520 B): LDS holds Aq (16 B) and the
+//                      fence Fn[t] = Bs[(t+1)·2^s − 1], t < m >> s, s = AL.fshift the smallest shift for which it fits (the host's
+//                      choice); the search for p(x) does its first nbits − s trips on the fence and its last s on Bs in global
+//                      memory, then reads Pre[p] there: id_F2_fenced.  p(x), and so every byte of a run, is the same either way.
 
 namespace visearch {
 
-#ifndef VISL_GROUPED
+#if !defined(VISL_GROUPED) && !defined(VISL_ID)
 struct ArgsL {
-    Args a;                       // k_visearch's, LOSS_VI's part of it (and runs, grouped)
+    Args a;                       // k_visearch's: LOSS_VI's part of it (and runs, grouped), all of LOSS_ID's for k_idlarge
     GqSplit split;                // the thresholds of a.Gq
+    int fshift;                   // k_idlarge with a.tab_lds = 0: the fence keeps every 2^fshift-th entry of Bs (behind everything
+                                  // else: the other kernels' arguments stay where they were)
 };
+
+constexpr size_t STATIC_L = 144;                      // oct u32[32] and pub u32[2] as the compiler lays them out, beside the dynamic LDS
 
 struct CarveL {
     size_t lo, acc, red, sz, stage, total;
@@ -70,17 +87,47 @@ __device__ inline void add_row_l(const uint2 v, int ka, const unsigned *lo, cons
     add_cell((v.y >> 16) - (ka == 3 ? 1u : 0u), lo, oct, sum[3], cnt[3]);
 }
 
+// ID, fenced placement: (F(x0), F(x1)) − Pre[m] as id_F2 finds them — the same trips, the same p — with the first nbits − sh trips
+// on the fence Fn[t] = Bs[(t + 1)·2^sh − 1] in LDS (a probe at q = p + 2^b, b >= sh, is a multiple of 2^sh) and the last sh trips on
+// Bs itself, within the 2^sh − 1 entries behind p; mfl = m rounded down to a multiple of 2^sh, so q <= m exactly when q <= mfl, and
+// while a trip is left on the fence 2^sh <= 2^(nbits−1) <= m: the fence is not empty.  Pre[m] is left out: it cancels in a step
+__device__ inline void id_F2_fenced(const long long *Fn, const long long *__restrict__ Bs, const long long *__restrict__ Pre, int m, int nbits,
+                                    int sh, long long x0, long long x1, long long &F0, long long &F1)
+{
+    const int mfl = (m >> sh) << sh;
+    int p0 = 0, p1 = 0;
+    for (int b = nbits - 1; b >= sh; --b) {
+        const int q0 = p0 + (1 << b), q1 = p1 + (1 << b);
+        const long long b0 = Fn[(min(q0, mfl) >> sh) - 1], b1 = Fn[(min(q1, mfl) >> sh) - 1];
+        if (q0 <= m && b0 <= x0) p0 = q0;
+        if (q1 <= m && b1 <= x1) p1 = q1;
+    }
+    for (int b = min(sh, nbits) - 1; b >= 0; --b) {
+        const int q0 = p0 + (1 << b), q1 = p1 + (1 << b);
+        const long long b0 = Bs[min(q0, m) - 1], b1 = Bs[min(q1, m) - 1];
+        if (q0 <= m && b0 <= x0) p0 = q0;
+        if (q1 <= m && b1 <= x1) p1 = q1;
+    }
+    F0 = x0 * p0 - Pre[p0];
+    F1 = x1 * p1 - Pre[p1];
+}
+
 #endif
-#ifdef VISL_GROUPED
+#if defined(VISL_GROUPED)
 template <int PQ>
 __global__ __launch_bounds__(TPB) void k_vilarge_groups(ArgsL AL)
 {
-    constexpr bool GROUPED = true;
+    constexpr bool GROUPED = true, ID = false;
+#elif defined(VISL_ID)
+template <int PQ>
+__global__ __launch_bounds__(TPB) void k_idlarge(ArgsL AL)
+{
+    constexpr bool GROUPED = false, ID = true;
 #else
 template <int PQ>
 __global__ __launch_bounds__(TPB) void k_vilarge(ArgsL AL)
 {
-    constexpr bool GROUPED = false;
+    constexpr bool GROUPED = false, ID = false;
 #endif
     extern __shared__ __attribute__((aligned(16))) unsigned char visl_lds[];
     __shared__ unsigned oct[32], pub[2];
@@ -100,6 +147,12 @@ __global__ __launch_bounds__(TPB) void k_vilarge(ArgsL AL)
     unsigned *r_pr = reinterpret_cast<unsigned *>(r_q + NWAVE), *r_slot = r_pr + NWAVE, *r_free = r_slot + NWAVE;
     unsigned short *sz = reinterpret_cast<unsigned short *>(visl_lds + cv.sz);
     unsigned short *stage = reinterpret_cast<unsigned short *>(visl_lds + cv.stage);  // [2][TPB·PQ]
+    // ID, behind the carve: Aq, then Bs[m] and Pre[m + 1] (whole), or at 16 bytes the fence i64[m >> fshift] (fenced)
+    long long *Aq = nullptr, *Bs_l = nullptr, *Pre_l = nullptr, *Fn = nullptr;
+    if (ID) {
+        Aq = reinterpret_cast<long long *>(visl_lds + cv.total);
+        Bs_l = Aq + 1; Pre_l = Bs_l + A.m; Fn = Aq + 2;
+    }
 
     const unsigned short *__restrict__ SL = GROUPED ? A.SL + g.sl : A.SL;
     unsigned short *Nrun = GROUPED ? A.N + g.tab : A.N + (size_t)run * m * Lmax * kpad;
@@ -113,6 +166,15 @@ __global__ __launch_bounds__(TPB) void k_vilarge(ArgsL AL)
     for (int k = tid; k < kpad; k += TPB) acc[k] = 0;
     for (int k = tid; k < Kcap + 2; k += TPB) sz[k] = A.sz0[(size_t)run * (Kstride + 2) + k];
     for (int j = tid; j < n; j += TPB) lab[j] = start[j];
+    if (ID) {
+        if (tid == 0) Aq[0] = A.Aq0[run];
+        if (A.tab_lds) {
+            for (int s = tid; s < m; s += TPB) Bs_l[s] = A.Bs[s];
+            for (int s = tid; s <= m; s += TPB) Pre_l[s] = A.Pre[s];
+        } else {
+            for (int t = tid; t < (m >> AL.fshift); t += TPB) Fn[t] = A.Bs[((t + 1) << AL.fshift) - 1];
+        }
+    }
     __syncthreads();
     int K = A.K0[run];
     if (K) {
@@ -213,8 +275,18 @@ __global__ __launch_bounds__(TPB) void k_vilarge(ArgsL AL)
                 acc[tid] = 0;
                 if (k <= (unsigned)Kcap) {
                     const int nk = (int)sz[k] - (k == a ? 1 : 0);
+                    long long idsc = 0;
+                    if (ID) {
+                        // F(A0 + Gq[n_k]) − F(A0) − acc_k; an empty slot runs the search too (nk = 0) and drops the result
+                        const long long A0 = Aq[0] - (a ? gq_at((unsigned)sz[a] - 1u, lo, oct) : 0ll);
+                        const long long A1 = A0 + gq_at((unsigned)nk, lo, oct);
+                        long long F0, F1;
+                        if (A.tab_lds) id_F2(Bs_l, Pre_l, m, A.nbits, A0, A1, F0, F1);
+                        else id_F2_fenced(Fn, A.Bs, A.Pre, m, A.nbits, AL.fshift, A0, A1, F0, F1);
+                        idsc = F1 - F0 - sum;
+                    }
                     if (nk <= 0) minfree = k;
-                    else best = Cand{key_i64((long long)m * gq_at((unsigned)nk, lo, oct) - 2 * sum), (k == a) ? 0u : k, k, 0u};
+                    else best = Cand{key_i64(ID ? idsc : (long long)m * gq_at((unsigned)nk, lo, oct) - 2 * sum), (k == a) ? 0u : k, k, 0u};
                 }
             }
             // argmin across the group (the second barrier), then the new-cluster candidate: while the cluster count is below
@@ -238,6 +310,7 @@ __global__ __launch_bounds__(TPB) void k_vilarge(ArgsL AL)
             }
             if (tid == 0) {
                 lab[i] = (unsigned short)w;
+                if (ID && a != w) Aq[0] += gq_at(sz[w], lo, oct) - (a ? gq_at((unsigned)sz[a] - 1u, lo, oct) : 0ll);
                 if (a) sz[a] = (unsigned short)(sz[a] - 1);
                 sz[w] = (unsigned short)(sz[w] + 1);
             }
@@ -255,7 +328,14 @@ __global__ __launch_bounds__(TPB) void k_vilarge(ArgsL AL)
     // Q of the final labelling from the tables, with Φq (global memory: most cells are small, and the pass runs once)
     const long long *__restrict__ Phi = A.Phi;
     unsigned long long q = 0;
-    if (tid < Kcap) q = (unsigned long long)((long long)m * Phi[sz[tid + 1]]);
+    if (ID) {
+        if (tid == 0) {
+            long long F0, F1;
+            if (A.tab_lds) id_F2(Bs_l, Pre_l, m, A.nbits, Aq[0], Aq[0], F0, F1);
+            else { id_F2_fenced(Fn, A.Bs, A.Pre, m, A.nbits, AL.fshift, Aq[0], Aq[0], F0, F1); F0 += A.Pre[m]; }
+            q = (unsigned long long)F0;
+        }
+    } else if (tid < Kcap) q = (unsigned long long)((long long)m * Phi[sz[tid + 1]]);
     {
         unsigned long long t2 = 0;
         const uint2 *N2 = reinterpret_cast<const uint2 *>(Nrun);
@@ -265,7 +345,7 @@ __global__ __launch_bounds__(TPB) void k_vilarge(ArgsL AL)
             t2 += (unsigned long long)Phi[c4.x & 0xFFFFu] + (unsigned long long)Phi[c4.x >> 16] +
                   (unsigned long long)Phi[c4.y & 0xFFFFu] + (unsigned long long)Phi[c4.y >> 16];
         }
-        q -= 2 * t2;
+        q -= (ID ? 1 : 2) * t2;
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) q += greedy::shfl_xor_u64(q, off);

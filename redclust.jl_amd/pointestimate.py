@@ -228,15 +228,16 @@ _INFO_KEYS = ("loss", "sweeps", "converged", "moves", "K", "labels", "best", "ke
 def _exact_search(samples, loss, nruns, maxK, maxsweeps, seed, init, device, large=False):
     """searchpointestimate(loss="VI", exact=True) and searchpointestimate(loss="ID"): see there.  Two things differ: the
     library's search, and the call whose result is the last start — the bound's search for VI, the exact VI search for ID —
-    with the key its info is kept under.  large (searchvi): no limit of 8192 points here, and above it rc_vi_search_large."""
+    with the key its info is kept under.  large (searchvi, searchid): no limit of 8192 points here, and above it
+    rc_vi_search_large / rc_id_search_large, the exact-VI start then coming from searchvi."""
     search, key = (_lib.id_search, "vi") if loss == "ID" else (_lib.vi_search, "lower_bound")
     S = _sample_matrix(samples)
     if large and S.shape[1] > _LDS_NMAX:
-        search = _lib.vi_search_large
+        search = _lib.id_search_large if loss == "ID" else _lib.vi_search_large
     else:
         _check_lds_n(S.shape[1], 'searchpointestimate(loss="ID")' if loss == "ID" else "searchpointestimate(exact=True)")
-    start, prior = searchpointestimate(samples, "VI", nruns=nruns, maxK=maxK, maxsweeps=maxsweeps, seed=seed, init=init, device=device,
-                                       exact=loss == "ID")
+    kw = dict(nruns=nruns, maxK=maxK, maxsweeps=maxsweeps, seed=seed, init=init, device=device)
+    start, prior = searchvi(samples, **kw) if large and loss == "ID" else searchpointestimate(samples, "VI", exact=loss == "ID", **kw)
     inits, orders = _search_starts(S.shape[1], nruns, seed, init, samples, loss, start, device)
     if not maxK:
         # the library's default cap is the samples' largest cluster count, which a start with more clusters widens
@@ -285,7 +286,7 @@ def searchpointestimate(samples_or_counts=None, loss="VI", *, nruns: int = 16, m
     result is never worse in the integer criterion info["loss_num"] than either.  info["loss"] = Q_ID/(2^32·n·m) is within
     2^-32 ≈ 2.3e-10 of expectedid's f64 value.  maxK = 0 is widened as for exact=True.
 
-    exact=True and loss="ID" stop at n = 8192; searchvi is the exact expected-VI search at any n <= 32767."""
+    exact=True and loss="ID" stop at n = 8192; searchvi and searchid are the two exact searches at any n <= 32767."""
     if loss == "ID":
         if ctx is not None:
             raise ValueError('loss="ID" needs the samples; a Context keeps only their counts')
@@ -330,6 +331,19 @@ def searchvi(samples, *, nruns: int = 16, init=None, maxK: int = 0, maxsweeps: i
     if not hasattr(samples, "clusts"):
         samples = _Samples(_sample_matrix(samples))
     return _exact_search(samples, "VI", nruns, maxK, maxsweeps, seed, init, device, large=True)
+
+
+def searchid(samples, *, nruns: int = 16, init=None, maxK: int = 0, maxsweeps: int = 100, seed: int = 0, device: int = 0):
+    """Search ALL partitions for the clustering of minimum posterior expected information distance (expectedid; the `id` of
+    evaluateclustering, SALSO's "ID") at any n <= 32767.  samples: an MCMCResult, anything with `.clusts`, or an m×n label matrix.
+    The search, its runs — nruns Philox orders from empty labels, one per init labelling, the MPEL ID sample, searchvi's result
+    with the same arguments (info["vi"] is its info) — and the returned (clust, info) are those of searchpointestimate(samples,
+    "ID"), whose bytes this returns up to n = 8192.  Above that the kernel is k_idlarge of csrc/visearch_large.inc.hip
+    (rc_id_search_large: the same integer function of a run's inputs).  Capacity: m·n <= 2^26, at most 1024 clusters, the 4 GiB
+    table budget.  A cut of dendrogrampointestimate(…, "ID", exact=True) is a start (init=) at these sizes."""
+    if not hasattr(samples, "clusts"):
+        samples = _Samples(_sample_matrix(samples))
+    return _exact_search(samples, "ID", nruns, maxK, maxsweeps, seed, init, device, large=True)
 
 
 class _Samples:

@@ -573,8 +573,8 @@ int32_t rc_psm_search_samples(int32_t device, const int64_t *samples /* m×n, la
  * lives in a per-run device workspace, and a thread reads four adjacent columns of a row at a time.  They launch that kernel
  * at every n.  Capacity: n <= 32767 (slots are 16 bits) and m·n < 2^31, RC_ERR_CAPACITY beyond, before any device work and
  * after the RC_ERR_ARG checks, which are rc_psm_search's in its order.  The _samples and _ctx forms are what
- * rc_psm_search_samples and rc_psm_search_ctx are to rc_psm_search.  PEAR (m·T² < 2^62 leaves m <= 15 at n = 32767), the exact
- * VI / ID searches (m·n <= 2^26, per-run contingency tables) and the dendrogram (an n×n u64 matrix) keep their limits. */
+ * rc_psm_search_samples and rc_psm_search_ctx are to rc_psm_search.  PEAR, the exact VI / ID searches and the dendrogram have
+ * large entries of their own (rc_pear_search_large, rc_vi_search_large, rc_id_search_large, rc_hclust_large). */
 int32_t rc_psm_search_large(int32_t device, const void *counts /* uint32_t n×n */, int64_t m, int64_t n, int32_t loss,
                             int32_t nruns, const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */,
                             int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */, void *runs_out /* rc_psm_run_t[nruns] */,
@@ -623,6 +623,40 @@ int32_t rc_pear_search_samples(int32_t device, const int64_t *samples /* m×n, l
                                const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */,
                                int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */, void *runs_out /* rc_pear_run_t[nruns] */,
                                int32_t *best, double *kernel_ms, double *counts_ms);
+
+/* The PEAR search beyond n = 8192 and beyond m·T² < 2^62 (DESIGN.md §8 "PEAR search, large n"): arguments, run semantics, tie
+ * rules, maxK, the moved rule, labels_out and best are rc_pear_search's, and a run is the same exact integer function of its
+ * arguments, so where rc_pear_search accepts the input these entries return its labels, num, den, sweeps, moves, converged and
+ * K.  Another kernel behind them (rc_psm_search_large's layout: slots and sizes in LDS, the accumulator window moved over the
+ * occupied slots, four adjacent columns per thread), launched at every n, and another arithmetic: a candidate is the state
+ * (X, A) it stands for, and two candidates are compared through num and den of up to 75 bits each, whose cross products are
+ * taken in 192 bits — exactly, with no floating point in any decision.
+ * num = num_hi·2^64 + num_lo and den = den_hi·2^64 + den_lo (two's complement, as a signed 128-bit integer); X, A and P are
+ * those of the final labelling, recomputed from the matrix; pear = num / den, one division of the two rounded to f64.
+ * Capacity: n <= 32767 and m·n < 2^31, RC_ERR_CAPACITY beyond, before any device work and after the RC_ERR_ARG checks, which are
+ * rc_psm_search_large's in its order (there is no loss specifier).  There is no m·T² condition.  The _samples and _ctx forms as
+ * rc_pear_search's; the context's state, layout and counts stay untouched. */
+typedef struct rc_pear_large_run_t {
+    double pear; /* num / den */
+    int64_t num_hi;
+    uint64_t num_lo;
+    int64_t den_hi;
+    uint64_t den_lo;
+    int64_t X, A, P;
+    int32_t sweeps, converged;
+    int64_t moves;
+    int32_t K;
+} rc_pear_large_run_t;
+int32_t rc_pear_search_large(int32_t device, const void *counts /* uint32_t n×n */, int64_t m, int64_t n, int32_t nruns,
+                             const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */, int32_t maxK,
+                             int32_t maxsweeps, int64_t *labels_out /* nruns×n */, void *runs_out /* rc_pear_large_run_t[nruns] */,
+                             int32_t *best, double *kernel_ms);
+int32_t rc_pear_search_large_ctx(rc_ctx *ctx, int64_t numsamples, int32_t nruns, const int64_t *init, const int32_t *order, int32_t maxK,
+                                 int32_t maxsweeps, int64_t *labels_out, rc_pear_large_run_t *runs_out, int32_t *best, double *kernel_ms);
+int32_t rc_pear_search_large_samples(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n, int32_t nruns,
+                                     const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */,
+                                     int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */,
+                                     void *runs_out /* rc_pear_large_run_t[nruns] */, int32_t *best, double *kernel_ms, double *counts_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Exact expected-VI search: the same greedy search (one run = starting labels, a point order, maxsweeps; the same scoring

@@ -714,6 +714,83 @@ end
 
 export searchmaxpear, expectedpear
 
+# rc_pear_large_run_t
+struct RcPearLargeRun
+    pear::Cdouble
+    num_hi::Int64; num_lo::UInt64
+    den_hi::Int64; den_lo::UInt64
+    X::Int64; A::Int64; P::Int64
+    sweeps::Int32; converged::Int32
+    moves::Int64
+    K::Int32; pad_::Int32
+end
+
+wide(hi::Int64, lo::UInt64) = (Int128(hi) << 64) | Int128(lo)
+
+pearlargeinfo(runs, labels, best) =
+    (pear = [x.pear for x in runs], num = [wide(x.num_hi, x.num_lo) for x in runs], den = [wide(x.den_hi, x.den_lo) for x in runs],
+     sweeps = [Int(x.sweeps) for x in runs], converged = [x.converged != 0 for x in runs], moves = [Int(x.moves) for x in runs],
+     K = [Int(x.K) for x in runs], labels = labels, best = Int(best[1]) + 1)
+
+# whether rc_pear_search accepts the input: n <= 8192 and m·T² < 2^62
+pearfitslds(n, m) = n <= 8192 && Int128(m) * (Int128(n) * (n - 1) ÷ 2)^2 < Int128(1) << 62
+
+"""
+    searchpear(HIPBackend(), result; nruns = 16, maxK = 0, maxsweeps = 100, seed = 0) -> (clust, info)
+    searchpear(HIPBackend(), counts, numsamples; nruns = 16, maxK = 0, maxsweeps = 100, seed = 0, init = nothing)
+
+`searchmaxpear` — arguments, runs, result — for any n <= 32767 and m·n < 2^31.  Wherever rc_pear_search accepts the input
+(n <= 8192 and m·T² < 2^62, T = n(n−1)/2) it is `searchmaxpear`'s call.  Otherwise the large-n kernel runs
+(rc_pear_search_large_samples / rc_pear_search_large): the same exact integer function of a run's inputs, with fractions of up
+to 75-bit numerator and denominator compared in 192 bits.  `info.num` and `info.den` are then `Int128`.
+"""
+function searchpear(b::HIPBackend, result; nruns::Integer = 16, maxK::Integer = 0, maxsweeps::Integer = 100, seed::Integer = 0)
+    samples = samplematrix(result)
+    n, m = size(samples)
+    pearfitslds(n, m) && return searchmaxpear(b, result; nruns = nruns, maxK = maxK, maxsweeps = maxsweeps, seed = seed)
+    counts = posteriorcounts(b, result)
+    draw = 1
+    bnum, bden = pearfraction(result.clusts[1], counts, m)
+    for s in 2:m
+        num, den = pearfraction(result.clusts[s], counts, m)
+        if big(num) * bden > big(bnum) * den                      # up to 75 bits each: the products pass Int128
+            draw, bnum, bden = s, num, den
+        end
+    end
+    R, inits, order = pearruns(n, nruns, seed, [result.clusts[draw]])
+    cap = maxK == 0 ? 0 : max(Int(maxK), length(unique(result.clusts[draw])))
+    labels = Matrix{Int64}(undef, n, R)
+    runs = Vector{RcPearLargeRun}(undef, R)
+    best = Int32[0]
+    rc = ccall((:rc_pear_search_large_samples, LIB), Int32,
+               (Int32, Ptr{Int64}, Int64, Int64, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
+                Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}),
+               b.device, samples, m, n, R, inits, order, cap, maxsweeps, labels, runs, best, C_NULL, C_NULL)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return (labels[:, best[1] + 1], pearlargeinfo(runs, labels, best))
+end
+
+function searchpear(b::HIPBackend, counts::Matrix{UInt32}, numsamples::Integer; nruns::Integer = 16, maxK::Integer = 0,
+                    maxsweeps::Integer = 100, seed::Integer = 0, init::Union{Matrix{Int64},Nothing} = nothing)
+    n = size(counts, 1)
+    size(counts, 2) == n || throw(ArgumentError("counts must be a square matrix"))
+    pearfitslds(n, numsamples) &&
+        return searchmaxpear(b, counts, numsamples; nruns = nruns, maxK = maxK, maxsweeps = maxsweeps, seed = seed, init = init)
+    starts = init === nothing ? Vector{Int64}[] : [init[:, k] for k in 1:size(init, 2)]
+    R, inits, order = pearruns(n, nruns, seed, starts)
+    labels = Matrix{Int64}(undef, n, R)
+    runs = Vector{RcPearLargeRun}(undef, R)
+    best = Int32[0]
+    rc = ccall((:rc_pear_search_large, LIB), Int32,
+               (Int32, Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
+                Ptr{Int32}, Ptr{Cdouble}),
+               b.device, counts, numsamples, n, R, inits, order, maxK, maxsweeps, labels, runs, best, C_NULL)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return (labels[:, best[1] + 1], pearlargeinfo(runs, labels, best))
+end
+
+export searchpear
+
 # rc_hclust_merge_t
 struct RcHclustMerge
     a::Int32; b::Int32

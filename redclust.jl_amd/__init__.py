@@ -16,7 +16,8 @@ from .pointestimate import (getpointestimate, lossmatrix, binderloss, infodist, 
                             posterior_counts, posterior_coclustering, hclust, hclustpointestimate, expectedlosses,
                             linkage_matrix, leaf_order, partitiondistances, expecteddistances, credibleball,
                             credibleball_from_distances, relabel, Relabelling, expectedpear, pearfraction, expectedpears,
-                            searchmaxpear, maxpear, expectedari, searchvi, searchid, dendrogram, dendrogrampointestimate)
+                            searchmaxpear, maxpear, expectedari, searchvi, searchid, dendrogram, dendrogrampointestimate,
+                            searchpear)
 from .wasabi import searchvigroups, wasabi, wasabi_scan, WasabiResult  # noqa: F401
 from .predict import predict, predict_points, Prediction, predict_joint, JointPrediction  # noqa: F401
 from .metrics import pairwise, METRICS  # noqa: F401

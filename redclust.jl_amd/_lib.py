@@ -91,6 +91,12 @@ class RcPearRun(C.Structure):
                 ("moves", C.c_int64), ("K", C.c_int32)]
 
 
+class RcPearLargeRun(C.Structure):
+    _fields_ = [("pear", C.c_double), ("num_hi", C.c_int64), ("num_lo", C.c_uint64), ("den_hi", C.c_int64), ("den_lo", C.c_uint64),
+                ("X", C.c_int64), ("A", C.c_int64), ("P", C.c_int64), ("sweeps", C.c_int32), ("converged", C.c_int32),
+                ("moves", C.c_int64), ("K", C.c_int32)]
+
+
 class RcMapRun(C.Structure):
     _fields_ = [("loglik", C.c_double), ("logprior", C.c_double), ("logposterior", C.c_double), ("start_logposterior", C.c_double),
                 ("sweeps", C.c_int32), ("converged", C.c_int32), ("K", C.c_int32), ("capped", C.c_int32), ("moves", C.c_int64)]
@@ -237,6 +243,13 @@ SIGNATURES = {
     "rc_pear_search_samples": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                            C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                            C.POINTER(C.c_double)]),
+    "rc_pear_search_large": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_pear_search_large_ctx": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_pear_search_large_samples": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                                 C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                                 C.POINTER(C.c_double)]),
     "rc_vi_gtable": (C.c_int32, [C.c_int64, C.c_void_p]),
     "rc_vi_search": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
@@ -891,7 +904,7 @@ def _psm_result(labels, runs, nruns, n, best, ms, **extra) -> dict:
     kernel_ms and what extra names."""
     out = dict(labels=labels[:nruns, :n], best=int(best.value), kernel_ms=float(ms.value), **extra)
     for k, ty in type(runs)._type_._fields_:
-        out[k] = np.array([getattr(r, k) for r in runs[:nruns]], dtype=np.float64 if ty is C.c_double else np.int64)
+        out[k] = np.array([getattr(r, k) for r in runs[:nruns]], dtype={C.c_double: np.float64, C.c_uint64: np.uint64}.get(ty, np.int64))
     out["converged"] = out["converged"].astype(bool)
     return out
 
@@ -952,13 +965,22 @@ def _psm_search(counts, numsamples, ctx, samples, loss, init, order, maxK, maxsw
     """psm_search and psm_search_samples (samples: the label matrix) behind their parameter lists; loss None: the PEAR
     search's three entry points, which have the same lists without the loss; large: rc_psm_search_large*, likewise"""
     cms = C.c_double()
-    family, crit, record = ("pear_search", [], RcPearRun) if loss is None else ("psm_search_large" if large else "psm_search", [int(loss)], RcPsmRun)
+    if loss is None:
+        family, crit, record = ("pear_search_large", [], RcPearLargeRun) if large else ("pear_search", [], RcPearRun)
+    else:
+        family, crit, record = "psm_search_large" if large else "psm_search", [int(loss)], RcPsmRun
 
     def call(n, *tail):
         fn, head, handle, _, timed = _counts_form(family, counts, numsamples, ctx, samples, device, n, "init")
         _check(fn(*head, *crit, *tail, *([C.byref(cms)] if timed else [])), handle)
         return dict(counts_ms=float(cms.value)) if timed else None
-    return _search_runs(init, order, maxK, maxsweeps, call, n=None if samples is None else samples.shape[1], record=record)
+    out = _search_runs(init, order, maxK, maxsweeps, call, n=None if samples is None else samples.shape[1], record=record)
+    if record is RcPearLargeRun:
+        # num and den from their limbs: int64 arrays, or object arrays of Python integers where a value passes 2^63 (expectedpears' convention)
+        wide = {k: [(int(hi) << 64) + int(lo) for hi, lo in zip(out.pop(k + "_hi"), out.pop(k + "_lo"))] for k in ("num", "den")}
+        fits = all(abs(v) < 2 ** 63 for k in wide for v in wide[k])
+        out.update({k: np.array(v, dtype=np.int64 if fits else object) for k, v in wide.items()})
+    return out
 
 
 def psm_search(counts, numsamples: int, loss: int, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0, ctx=None):
@@ -1008,6 +1030,19 @@ def pear_search_samples(samples, init, order, maxK: int = 0, maxsweeps: int = 10
     """rc_pear_search_samples: pear_search on the counts of an m×n int64 label matrix (labels 1..n), which are built on the
     device and stay there.  Returns pear_search's dict and counts_ms."""
     return _psm_search(None, None, None, _label_matrix(samples), None, init, order, maxK, maxsweeps, device)
+
+
+def pear_search_large(counts, numsamples: int, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0, ctx=None):
+    """rc_pear_search_large or, with ctx, rc_pear_search_large_ctx: pear_search — arguments, runs, results — by the kernel whose
+    capacity is n <= 32767 and m·n < 2^31 with no m·T² condition (csrc/pointsearch_large.inc.hip, k_pear_large), at every n.
+    Besides pear_search's dict: X, A, P of every run; num and den are int64 arrays, or object arrays of Python integers where a
+    value passes 2^63."""
+    return _psm_search(counts, numsamples, ctx, None, None, init, order, maxK, maxsweeps, device, large=True)
+
+
+def pear_search_large_samples(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
+    """rc_pear_search_large_samples: pear_search_samples by the large-n kernel."""
+    return _psm_search(None, None, None, _label_matrix(samples), None, init, order, maxK, maxsweeps, device, large=True)
 
 
 def vi_gtable(n: int) -> np.ndarray:

@@ -157,6 +157,67 @@ __device__ inline unsigned offer_new(FCand &best, long long num, long long den, 
     return 1u;
 }
 
+// ---- the same criterion where num and den pass 64 bits (k_pear_large, DESIGN.md §8 "PEAR search, large n"): a candidate travels
+// as the state (X, A) it stands for — five words, as Cand — and widefrac.inc.hpp rebuilds its fraction from the run's Step where
+// two candidates are compared.  Ties and the shape of the reduction are the ones above.
+
+struct WCand { unsigned long long X; unsigned A, pr, slot; };
+constexpr WCand WCAND_NONE{0, 0, ~0u, 0u};                      // no cluster lives in slot 0: "no candidate yet", which loses to any
+
+__device__ inline bool fbetter(const widefrac::Step &s, const WCand &x, const WCand &b)
+{
+    if (!x.slot) return false;
+    if (!b.slot) return true;
+    const int c = widefrac::compare(widefrac::fraction(s, x.X, x.A), widefrac::fraction(s, b.X, b.A));
+    return c > 0 || (c == 0 && x.pr < b.pr);
+}
+
+// a value every lane of the wave holds alike, moved to scalar registers: what is computed from it runs on the scalar unit, beside
+// the other waves' vector work, not sixteen times over on the vector units
+__device__ inline unsigned uniform(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ inline unsigned long long uniform(unsigned long long v)
+{
+    return ((unsigned long long)uniform((unsigned)(v >> 32)) << 32) | uniform((unsigned)v);
+}
+
+struct WPartials { unsigned long long *X; unsigned *A, *pr, *slot, *free; };
+
+// The xor tree over the wave compares in the vector units (a wave without candidates skips it); the 16-way merge behind the
+// barrier is the same in every lane, and so is the new-cluster candidate: both run on uniform values.
+__device__ inline void group_argmax(const widefrac::Step &s, WCand &best, unsigned &minfree, const WPartials &P, int lane, int wave)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const WCand o{shfl_xor_u64(best.X, off), (unsigned)__shfl_xor((int)best.A, off), (unsigned)__shfl_xor((int)best.pr, off),
+                      (unsigned)__shfl_xor((int)best.slot, off)};
+        if (fbetter(s, o, best)) best = o;
+        minfree = min(minfree, (unsigned)__shfl_xor((int)minfree, off));
+    }
+    if (lane == 0) { P.X[wave] = best.X; P.A[wave] = best.A; P.pr[wave] = best.pr; P.slot[wave] = best.slot; P.free[wave] = minfree; }
+    __syncthreads();
+    best = WCand{uniform(P.X[0]), uniform(P.A[0]), uniform(P.pr[0]), uniform(P.slot[0])};
+    minfree = P.free[0];
+#pragma unroll 1
+    for (int w = 1; w < NWAVE; ++w) {                               // rolled: one copy of the 192-bit comparison
+        minfree = min(minfree, P.free[w]);
+        const unsigned slot = uniform(P.slot[w]);
+        if (!slot) continue;
+        const WCand o{uniform(P.X[w]), uniform(P.A[w]), uniform(P.pr[w]), slot};
+        if (fbetter(s, o, best)) best = o;
+    }
+    minfree = uniform(minfree);
+}
+
+// the new cluster stands for the state without the point, (X0, A0)
+__device__ inline unsigned offer_new(const widefrac::Step &s, WCand &best, unsigned long long X0, unsigned A0, unsigned emptied, unsigned a,
+                                     unsigned minfree)
+{
+    const WCand c{X0, A0, emptied ? 0u : minfree, emptied ? a : minfree};
+    if (!fbetter(s, c, best)) return 0u;
+    best = c;
+    return 1u;
+}
+
 // ---- host side
 
 // What the entry points check first and alike (rc_psm_search, _ctx, _samples, rc_vi_search, rc_id_search, rc_pear_search*); each goes on

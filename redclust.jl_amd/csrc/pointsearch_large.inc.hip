@@ -290,6 +290,210 @@ static hipError_t launch(int Q4, int nruns, size_t lds, hipStream_t st, const Ar
     return hipGetLastError();
 }
 
+// ---- PEAR (rc_pear_search_large*; DESIGN.md §8 "PEAR search, large n"): k_search<LOSS_PEAR>'s criterion in this file's layout, as
+// a kernel of its own.  Rows, the quad loop with its runs of equal labels, the window passes and the prefetch are Binder's above.
+// PEAR's own parts:
+//   head     X, A, P as u64 words and the two S_ia accumulators in front of lab: head u64[4] | lab u16[n4] | S u32[W] | sz u16[n+2].
+//   S_ia     the row's sum over the point's own cluster, which turns the run's X into X₀, is summed in pass 0 only (slot a may lie
+//            outside the window of any one pass): per thread in a register, over the wave by shuffles, one LDS atomic per wave into
+//            the accumulator of the step's parity — the owner of i clears it in phase C while the other threads are already
+//            adding to the other one.
+//   score    slot k stands for the state (X₀ + S_ik, A₀ + n_k), a greedy::WCand; num and den (up to 75 bits each) are rebuilt from
+//            it where two candidates are compared, exactly, in widefrac.inc.hpp — m·T² need not fit anything.  The best candidate
+//            stays in registers across the window passes; X₀, A₀, P and the group's winner are wave-uniform and sit in scalar
+//            registers, so the merge of the waves' partials and the new-cluster comparison cost no vector work.
+//   P, X     one upper_sums pass before the first step (P and the start's X), one after the last (the reported X and P).
+// PF is the largest leading part with which an instantiation compiles without scratch and within 128 VGPRs: 1, 2, 4, 3 quads at
+// Q4 = 1, 2, 4, 8 (85, 97, 124, 123 VGPRs).  UNROLL_Q: how many of the streamed quads are loaded at a time — all of them, but two
+// at Q4 = 8, where the uniform state's scalar registers (100 are in use) already overflow into vector ones.
+template <int Q4, int PF, int UNROLL_Q = (Q4 > PF ? Q4 - PF : 1)>
+__global__ __launch_bounds__(TPB) void k_pear_large(Args AA)
+{
+    static_assert(PF >= 1 && PF <= Q4, "the prefetched part is a leading part of the row");
+    extern __shared__ unsigned long long pearl_lds[];
+    __shared__ unsigned long long r_X[NWAVE], r_a[NWAVE], r_b[NWAVE];
+    __shared__ unsigned r_A[NWAVE], r_pr[NWAVE], r_slot[NWAVE], r_free[NWAVE];
+
+    const psm::Args &A = AA.a;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = A.n, n4 = AA.n4, W = A.W, run = blockIdx.x;
+    const unsigned *__restrict__ C = A.C;
+    const size_t ld = (size_t)A.ld;
+
+    unsigned long long *XA = pearl_lds;                                  // X, A, P
+    unsigned *Sa = reinterpret_cast<unsigned *>(XA + 3);                 // S_ia of the even and the odd steps
+    unsigned short *lab = reinterpret_cast<unsigned short *>(XA + psm::PEAR_HEAD);
+    unsigned *S = reinterpret_cast<unsigned *>(lab + n4);
+    unsigned short *sz = reinterpret_cast<unsigned short *>(S + W);
+
+    for (int k = tid; k < W; k += TPB) S[k] = 0;
+    for (int k = tid; k < n + 2; k += TPB) sz[k] = A.sz0[(size_t)run * (n + 2) + k];
+    for (int j = tid; j < n4; j += TPB) lab[j] = (j < n) ? A.init[(size_t)run * n + j] : (unsigned short)0;
+    __syncthreads();
+    {
+        // P, and X and A of the starting labels
+        unsigned long long tot = 0, same = 0, within = 0;
+        psm::upper_sums<true>(C, ld, n, lab, lane, wave, tot, same);
+        for (int k = 1 + tid; k <= n; k += TPB) within += (unsigned long long)sz[k] * (sz[k] - 1u) / 2u;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) within += greedy::shfl_xor_u64(within, off);
+        if (lane == 0) { r_a[wave] = tot; r_b[wave] = same; r_X[wave] = within; }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned long long ta = 0, tb = 0, tc = 0;
+            for (int w = 0; w < NWAVE; ++w) { ta += r_a[w]; tb += r_b[w]; tc += r_X[w]; }
+            XA[0] = tb; XA[1] = tc; XA[2] = ta;
+            Sa[0] = Sa[1] = 0;
+        }
+        __syncthreads();
+    }
+    const widefrac::Step step = widefrac::make_step((long long)n * (n - 1) / 2, (long long)A.m, (long long)greedy::uniform(XA[2]));
+
+    const greedy::WPartials red{r_X, r_A, r_pr, r_slot, r_free};
+    greedy::Visit v(A.order + (size_t)run * n, n);
+    int K = A.K0[run], hi = A.hi0[run];
+    int par = 0;
+    uint4 cur[PF], nxt[PF];
+#pragma unroll
+    for (int q = 0; q < PF; ++q) nxt[q] = load_quad(C + (size_t)v.i * ld, n, tid, q);
+    long long moves = 0;
+    int sweeps = 0, converged = 0;
+
+    for (;;) {
+        int moved = 0;
+        for (int t = 0; t < n; ++t) {
+            const int i = v.i, inext = v.ahead(t);
+            const unsigned *__restrict__ rowi = C + (size_t)i * ld;
+#pragma unroll
+            for (int q = 0; q < PF; ++q) cur[q] = nxt[q];
+#pragma unroll
+            for (int q = 0; q < PF; ++q) nxt[q] = load_quad(C + (size_t)inext * ld, n, tid, q);
+
+            const unsigned a = greedy::uniform(v.slot_of(lab));
+            const int scan_hi = min(hi + 1, n);
+            greedy::WCand best = greedy::WCAND_NONE;
+            unsigned long long X0 = 0;                                   // X and A with i out
+            unsigned A0 = 0;
+            unsigned minfree = ~0u;
+            unsigned emptied = 0;
+            for (int base = 0, pass = 0; base < scan_hi; base += W, ++pass) {
+                // phase A: row i into the per-slot accumulators of this window; the first pass also sums it over i's own cluster
+                if (pass) __syncthreads();
+                unsigned sa = 0;
+                const auto quad = [&](int q, uint4 cq) {
+                    const int j0 = 4 * (tid + q * TPB);
+                    if (j0 >= n) return;
+                    const uint2 lw = *reinterpret_cast<const uint2 *>(lab + j0);
+                    unsigned long long ls = ((unsigned long long)lw.y << 32) | lw.x;   // pad slots hold 0
+                    unsigned pidx = ~0u, ps = 0;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const unsigned l = (j0 + e == i) ? 0u : (unsigned)(ls & 0xFFFFu);   // i itself is out
+                        const unsigned c = cq.x;
+                        if (pass == 0 && a && l == a) sa += c;
+                        const unsigned idx = l - 1u - (unsigned)base;   // l = 0 wraps beyond every W
+                        if (idx < (unsigned)W && c) {
+                            if (idx != pidx) {
+                                if (ps) atomicAdd(&S[pidx], ps);
+                                pidx = idx; ps = 0;
+                            }
+                            ps += c;
+                        }
+                        ls >>= 16;
+                        cq = make_uint4(cq.y, cq.z, cq.w, cq.x);
+                    }
+                    if (ps) atomicAdd(&S[pidx], ps);
+                };
+#pragma unroll
+                for (int q = 0; q < PF; ++q) quad(q, cur[q]);
+#pragma unroll UNROLL_Q
+                for (int q = PF; q < Q4; ++q) quad(q, load_quad(rowi, n, tid, q));
+                if (pass == 0 && a) {
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) sa += (unsigned)__shfl_xor((int)sa, off);
+                    if (lane == 0 && sa) atomicAdd(&Sa[par], sa);
+                }
+                __syncthreads();
+                // phase B: score the slots of this window (and clear their accumulators)
+                emptied = (a && sz[a] == 1) ? 1u : 0u;
+                if (pass == 0) {
+                    X0 = greedy::uniform(XA[0]) - greedy::uniform(Sa[par]);
+                    A0 = greedy::uniform((unsigned)XA[1]) - (a ? greedy::uniform((unsigned)sz[a]) - 1u : 0u);
+                }
+                const int kend = min(base + W, scan_hi);
+                for (int k = base + 1 + tid; k <= kend; k += TPB) {
+                    const int nk = (int)sz[k] - ((unsigned)k == a ? 1 : 0);
+                    if (nk <= 0) { minfree = min(minfree, (unsigned)k); continue; }
+                    const int idx = k - 1 - base;
+                    const unsigned s = S[idx];
+                    S[idx] = 0;
+                    const greedy::WCand cand{X0 + s, A0 + (unsigned)nk, ((unsigned)k == a) ? 0u : (unsigned)k, (unsigned)k};
+                    if (greedy::fbetter(step, cand, best)) best = cand;
+                }
+            }
+            // argmax across the group (the second barrier), then the new cluster: the state without the point
+            greedy::group_argmax(step, best, minfree, red, lane, wave);
+            const int Know = K - (int)emptied;
+            unsigned isnew = 0;
+            if (A.maxK == 0 || Know < A.maxK) isnew = greedy::offer_new(step, best, X0, A0, emptied, a, minfree);
+            const unsigned w = best.slot;
+            // phase C: put i into w — lab by the thread that owns the column, and sz, X, A and the used S_ia accumulator with it; the
+            // next step reads them only behind its first barrier
+            if (tid == ((i >> 2) & (TPB - 1))) {
+                lab[i] = (unsigned short)w;
+                if (a) sz[a] = (unsigned short)(sz[a] - 1);
+                sz[w] = (unsigned short)(sz[w] + 1);
+                XA[0] = best.X; XA[1] = best.A; Sa[par] = 0;
+            }
+            moved += v.moved_to(a, w, inext);
+            K = Know + (int)isnew;
+            hi = max(hi, (int)w);
+            par ^= 1;
+        }
+        ++sweeps;
+        moves += moved;
+        if (!moved) { converged = 1; break; }
+        if (sweeps >= A.maxsweeps) break;
+    }
+    __syncthreads();
+
+    for (int j = tid; j < n; j += TPB) A.labels[(size_t)run * n + j] = lab[j];
+    unsigned long long tot = 0, same = 0;
+    psm::upper_sums<false>(C, ld, n, lab, lane, wave, tot, same);
+    if (lane == 0) { r_a[wave] = tot; r_b[wave] = same; }
+    __syncthreads();
+    if (tid == 0) {
+        RunOut o{};
+        unsigned long long ta = 0, tb = 0;
+        for (int w = 0; w < NWAVE; ++w) { ta += r_a[w]; tb += r_b[w]; }
+        o.tot = (long long)ta; o.same = (long long)tb;
+        o.moves = moves; o.sweeps = sweeps; o.converged = converged; o.K = K;
+        A.out[run] = o;
+    }
+}
+
+static hipError_t launch_pear(int Q4, int nruns, size_t lds, hipStream_t st, const Args &A)
+{
+#define PEARL_LAUNCH(...)                                                                                                 \
+    do {                                                                                                                  \
+        hipError_t e = hipFuncSetAttribute((const void *)k_pear_large<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        if (e != hipSuccess) return e;                                                                                    \
+        k_pear_large<__VA_ARGS__><<<nruns, TPB, lds, st>>>(A);                                                            \
+    } while (0)
+    if (Q4 <= 1) PEARL_LAUNCH(1, 1);
+    else if (Q4 <= 2) PEARL_LAUNCH(2, 2);
+    else if (Q4 <= 4) PEARL_LAUNCH(4, 4);
+    else PEARL_LAUNCH(8, 3, 2);                                          // (8, 4) spills however few of the other quads are in flight
+#undef PEARL_LAUNCH
+    return hipGetLastError();
+}
+
+// A run's fraction for greedy::results; a < b: a is the larger fraction
+struct WideKey {
+    widefrac::Frac f;
+    bool operator<(const WideKey &o) const { return widefrac::compare(f, o.f) > 0; }
+};
+
 // psm::run for the large kernel: the same staging, counts check and results around another geometry and launch
 static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, int64_t m, int64_t n, int32_t loss, int32_t nruns,
                    const int64_t *init, const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out,
@@ -304,9 +508,9 @@ static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, in
     DeviceBuffers B;
 
     // ---- geometry: lab and sz fixed, the rest of the budget is the window
-    const bool vi = loss == RC_PSM_VILB;
+    const bool vi = loss == RC_PSM_VILB, pear = loss == psm::LOSS_PEAR;
     const int64_t n4 = (n + 3) / 4 * 4;
-    const size_t fixed = 2 * (size_t)n4 + 2 * (size_t)(n + 2) + 16;
+    const size_t fixed = 2 * (size_t)n4 + 2 * (size_t)(n + 2) + 16 + (pear ? 8 * psm::PEAR_HEAD : 0);
     const size_t per_slot = vi ? 12 : 4;
     int64_t W = std::min<int64_t>(n + 1, (int64_t)((LDS_BUDGET - fixed) / per_slot));
     if (const long long v = env_int("RC_PSM_WINDOW"); v >= 1 && v < W) W = v;   // tests: force many passes at small n
@@ -325,33 +529,51 @@ static int32_t run(rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, in
     A.a.m = (unsigned)m; A.T = d_T; A.n4 = (int)n4;
     HIPCHK(c, S.begin(st));
     const int Q4 = (int)((n4 / 4 + TPB - 1) / TPB);
-    const hipError_t le = vi ? launch<RC_PSM_VILB>(Q4, nruns, lds, st, A) : launch<RC_PSM_BINDER>(Q4, nruns, lds, st, A);
+    const hipError_t le = vi ? launch<RC_PSM_VILB>(Q4, nruns, lds, st, A) : pear ? launch_pear(Q4, nruns, lds, st, A)
+                                                                                 : launch<RC_PSM_BINDER>(Q4, nruns, lds, st, A);
     if (le != hipSuccess) return fail(c, RC_ERR_HIP, "point search: launch failed: %s", hipGetErrorString(le));
     std::vector<RunOut> h_out;
     HIPCHK(c, S.collect(st, h_out, kernel_ms));
+    if (pear) {
+        // num and den from the epilogue's X (same) and P (tot) and the final sizes; the best run is the first of maximal fraction,
+        // compared as the kernel compares
+        const long long pairs = (long long)n * (n - 1) / 2;
+        greedy::results(S, h_out, labels_out, (rc_pear_large_run_t *)runs_out, best, [&](const RunOut &o, rc_pear_large_run_t &R, const int *cnt, int K) {
+            long long within = 0;
+            for (int k = 1; k <= K; ++k) within += (long long)cnt[k] * (cnt[k] - 1) / 2;
+            const widefrac::Frac f = widefrac::fraction(widefrac::make_step(pairs, m, o.tot), (unsigned long long)o.same, (unsigned)within);
+            R.num_hi = (int64_t)(f.num >> 64); R.num_lo = (uint64_t)f.num;
+            R.den_hi = (int64_t)(f.den >> 64); R.den_lo = (uint64_t)f.den;
+            R.X = o.same; R.A = within; R.P = o.tot;
+            R.pear = (double)f.num / (double)f.den;
+            return WideKey{f};
+        });
+        return RC_OK;
+    }
     greedy::results(S, h_out, labels_out, (rc_psm_run_t *)runs_out, best, psm::Losses{vi, m, n});
     return RC_OK;
 }
 
-// rc_psm_search's checks in its order, with this kernel's capacity in place of the LDS one
+// rc_psm_search's checks in its order, with this kernel's capacity in place of the LDS one (loss LOSS_PEAR: rc_pear_search_large*,
+// which have no loss specifier)
 static int32_t check_args(rc_ctx *c, const char *who, int64_t m, int64_t n, int32_t loss, int32_t nruns, const int64_t *init,
                           const int32_t *order, int32_t maxK, int32_t maxsweeps, const int64_t *labels_out, const void *runs_out,
-                          const int32_t *best)
+                          const int32_t *best, bool pear = false)
 {
     const int32_t rc = greedy::check_args(c, who, m, n, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best);
     if (rc != RC_OK) return rc;
-    if (loss != RC_PSM_BINDER && loss != RC_PSM_VILB) return fail(c, RC_ERR_ARG, "%s: invalid loss specifier %d", who, loss);
+    if (!pear && loss != RC_PSM_BINDER && loss != RC_PSM_VILB) return fail(c, RC_ERR_ARG, "%s: invalid loss specifier %d", who, loss);
     if (n > NMAX) return fail(c, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %d points whose slots fit 16 bits and the workgroup's LDS", who, (long long)n, NMAX);
     if (m > 0x7FFFFFFFll / n) return fail(c, RC_ERR_CAPACITY, "%s: m*n does not fit 31 bits (m=%lld n=%lld)", who, (long long)m, (long long)n);
     return RC_OK;
 }
 
 static int32_t search(const char *who, const cnt::Source &src, int32_t loss, int32_t nruns, const int64_t *init, const int32_t *order,
-                      int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out, int32_t *best, double *kernel_ms)
+                      int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out, int32_t *best, double *kernel_ms, bool pear = false)
 {
     return cnt::with(
         who, src,
-        [&](rc_ctx *c, int64_t m, int64_t n) { return check_args(c, who, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best); },
+        [&](rc_ctx *c, int64_t m, int64_t n) { return check_args(c, who, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best, pear); },
         [&](rc_ctx *c, hipStream_t st, const unsigned *dC, int64_t ld, int64_t m, int64_t n) {
             return run(c, st, dC, ld, m, n, loss, nruns, init, order, maxK, maxsweeps, labels_out, runs_out, best, kernel_ms);
         });
@@ -381,4 +603,28 @@ extern "C" int32_t rc_psm_search_large_ctx(rc_ctx *c, int64_t numsamples, int32_
 {
     return psm_large::search("rc_psm_search_large_ctx", cnt::context(c, numsamples), loss, nruns, init, order, maxK, maxsweeps, labels_out,
                              runs_out, best, kernel_ms);
+}
+
+extern "C" int32_t rc_pear_search_large(int32_t device, const void *counts, int64_t m, int64_t n, int32_t nruns, const int64_t *init,
+                                        const int32_t *order, int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out,
+                                        int32_t *best, double *kernel_ms)
+{
+    return psm_large::search("rc_pear_search_large", cnt::host_counts(device, counts, m, n), psm::LOSS_PEAR, nruns, init, order, maxK, maxsweeps,
+                             labels_out, runs_out, best, kernel_ms, true);
+}
+
+extern "C" int32_t rc_pear_search_large_samples(int32_t device, const int64_t *samples, int64_t m, int64_t n, int32_t nruns,
+                                                const int64_t *init, const int32_t *order, int32_t maxK, int32_t maxsweeps,
+                                                int64_t *labels_out, void *runs_out, int32_t *best, double *kernel_ms, double *counts_ms)
+{
+    return psm_large::search("rc_pear_search_large_samples", cnt::samples(device, samples, m, n, counts_ms), psm::LOSS_PEAR, nruns, init, order,
+                             maxK, maxsweeps, labels_out, runs_out, best, kernel_ms, true);
+}
+
+extern "C" int32_t rc_pear_search_large_ctx(rc_ctx *c, int64_t numsamples, int32_t nruns, const int64_t *init, const int32_t *order,
+                                            int32_t maxK, int32_t maxsweeps, int64_t *labels_out, rc_pear_large_run_t *runs_out,
+                                            int32_t *best, double *kernel_ms)
+{
+    return psm_large::search("rc_pear_search_large_ctx", cnt::context(c, numsamples), psm::LOSS_PEAR, nruns, init, order, maxK, maxsweeps,
+                             labels_out, runs_out, best, kernel_ms, true);
 }

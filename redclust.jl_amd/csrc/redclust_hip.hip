@@ -7519,6 +7519,7 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "samplek.inc.hip"
 #include "mixture.inc.hip"
 #include "kmeans.inc.hip"
+#include "widefrac.inc.hpp"          // the PEAR search's exact fraction beyond 64 bits: no device code of its own
 #include "greedy.inc.hip"
 #include "samplecounts.inc.hip"
 #include "pointsearch.inc.hip"

@@ -619,6 +619,11 @@ def expectedpears(labellings, counts_or_samples=None, numsamples=None, *, ctx=No
     labelling (evaluated with the batch) gives P, and A comes from the cluster sizes, so X and with it the fraction follow in
     integers.  Returns (pear[L] f64, num[L], den[L]); num and den are int64 arrays, or object arrays of Python integers where
     a value passes 2^63 (only beyond searchmaxpear's capacity m·T² < 2^62)."""
+    return _expectedpears(labellings, counts_or_samples, numsamples, ctx, device)
+
+
+def _expectedpears(labellings, counts_or_samples, numsamples, ctx, device, large=False):
+    """expectedpears; large (searchpear): above 8192 points the numerators come through rc_psm_expected_loss_large"""
     labs = np.stack([_labels(c) for c in np.atleast_2d(np.asarray(labellings))])
     S, counts, m, n = _counts_input(counts_or_samples, numsamples, ctx)
     if labs.shape[1] != n:
@@ -626,7 +631,8 @@ def expectedpears(labellings, counts_or_samples=None, numsamples=None, *, ctx=No
     if S is not None:
         counts = _lib.samples_counts(S, device=device)[0]
     singletons = np.arange(1, n + 1, dtype=np.int64)[None, :]
-    _, binder, _ = _lib.psm_expected_loss(np.concatenate([labs, singletons]), counts, m, _PSM_LOSSES["binder"], device=device, ctx=ctx)
+    _, binder, _ = _lib.psm_expected_loss(np.concatenate([labs, singletons]), counts, m, _PSM_LOSSES["binder"], device=device, ctx=ctx,
+                                          large=large and n > _LDS_NMAX)
     return _pears_from_binder(binder[:-1], [_within_pairs(c) for c in labs], binder[-1], m, n)
 
 
@@ -650,18 +656,18 @@ def _first_max_fraction(num, den):
 _PEAR_INFO = ("pear", "num", "den", "sweeps", "converged", "moves", "K", "labels", "best", "kernel_ms")
 
 
-def _pear_cuts(samples_or_counts, linkage, maxK, numsamples, ctx, device):
+def _pear_cuts(samples_or_counts, linkage, maxK, numsamples, ctx, device, large=False):
     """The cuts of 1..maxK clusters (maxK = 0: ⌈n/8⌉) of hclust's dendrogram and their (pear, num, den), from the exact Binder
-    numerators of the dendrogram: binder_num[0] is P.  Returns (cuts, pear, num, den)."""
-    res, cuts, _, m, n, maxK = _hclust_cuts(samples_or_counts, linkage, maxK, numsamples, ctx, device)
+    numerators of the dendrogram: binder_num[0] is P.  Returns (cuts, pear, num, den).  large: _hclust_cuts'."""
+    res, cuts, _, m, n, maxK = _hclust_cuts(samples_or_counts, linkage, maxK, numsamples, ctx, device, large)
     binder = res["binder_num"][::-1][:maxK]                             # K clusters = n − K merges
     return (cuts,) + _pears_from_binder(binder, [_within_pairs(c) for c in cuts], res["binder_num"][0], m, n)
 
 
-def _pear_draws(samples, device):
+def _pear_draws(samples, device, large=False):
     """(the samples as a matrix, pear, num, den of every sample)"""
     S = _sample_matrix(samples)
-    return (S,) + expectedpears(S, samples, device=device)
+    return (S,) + _expectedpears(S, samples, None, None, device, large)
 
 
 def searchmaxpear(samples_or_counts=None, *, nruns: int = 16, maxK: int = 0, maxsweeps: int = 100, seed: int = 0, init=None,
@@ -680,21 +686,42 @@ def searchmaxpear(samples_or_counts=None, *, nruns: int = 16, maxK: int = 0, max
     start's cluster count where that is larger.  So the result is never below any of those starts in the exact fraction.
     Returns (clust, info): the best labelling (sortlabels'd) and a dict with the per-run pear, num, den, sweeps, converged,
     moves, K, all labellings (labels), best (the first run of maximal num/den), kernel_ms, and counts_ms for an MCMCResult."""
+    return _searchmaxpear(samples_or_counts, nruns, maxK, maxsweeps, seed, init, numsamples, ctx, device, large=False)
+
+
+def searchpear(samples_or_counts=None, *, nruns: int = 16, maxK: int = 0, maxsweeps: int = 100, seed: int = 0, init=None,
+               numsamples=None, ctx=None, device: int = 0):
+    """searchmaxpear — arguments, runs, result — for any n <= 32767 and m·n < 2^31.  Wherever rc_pear_search accepts the input
+    (n <= 8192 and m·T² < 2^62, T = n(n−1)/2) it is searchmaxpear's call and returns its bytes.  Otherwise the kernel is k_pear_large
+    of csrc/pointsearch_large.inc.hip (rc_pear_search_large*): the same exact integer function of a run's inputs, with fractions
+    of up to 75-bit numerator and denominator compared in 192 bits; num and den then come back as int64 arrays, or as object
+    arrays of Python integers where a value passes 2^63.  The starts are searchmaxpear's — above 8192 points the sample of highest
+    PEAR through rc_psm_expected_loss_large and the average-linkage cut of highest PEAR among 1..⌈n/8⌉ clusters through
+    rc_hclust_large* and rc_hclust_cut_large (the dendrogram takes most of the call's time and memory there: see dendrogram)."""
+    return _searchmaxpear(samples_or_counts, nruns, maxK, maxsweeps, seed, init, numsamples, ctx, device, large=True)
+
+
+def _searchmaxpear(samples_or_counts, nruns, maxK, maxsweeps, seed, init, numsamples, ctx, device, large):
+    """searchmaxpear (large=False) and searchpear (large=True)"""
     S, counts, m, n = _counts_input(samples_or_counts, numsamples, ctx)
-    _check_lds_n(n, "searchmaxpear")
+    pairs = n * (n - 1) // 2
+    large = large and (n > _LDS_NMAX or m * pairs * pairs >= 2 ** 62)     # the large entry only where rc_pear_search refuses
+    if not large:
+        _check_lds_n(n, "searchmaxpear")
     starts = [] if init is None else list(np.atleast_2d(np.asarray(init)))
     if S is not None:
-        _, _, dnum, dden = _pear_draws(samples_or_counts, device)
+        _, _, dnum, dden = _pear_draws(samples_or_counts, device, large)
         starts.append(S[_first_max_fraction(dnum, dden)])
-    cuts, _, cnum, cden = _pear_cuts(samples_or_counts, "average", 0, numsamples, ctx, device)
+    cuts, _, cnum, cden = _pear_cuts(samples_or_counts, "average", 0, numsamples, ctx, device, large)
     starts.append(cuts[_first_max_fraction(cnum, cden)])
     inits, orders = _search_starts(n, nruns, seed, starts)
     if maxK:
         maxK = max(int(maxK), max(len(np.unique(x[x > 0])) for x in inits))
+    by_samples, by_counts = (_lib.pear_search_large_samples, _lib.pear_search_large) if large else (_lib.pear_search_samples, _lib.pear_search)
     if S is not None:
-        res = _lib.pear_search_samples(S, inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device)
+        res = by_samples(S, inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device)
     else:
-        res = _lib.pear_search(counts, m, inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device, ctx=ctx)
+        res = by_counts(counts, m, inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device, ctx=ctx)
     info = {k: res[k] for k in _PEAR_INFO}
     if S is not None:
         info["counts_ms"] = res["counts_ms"]

@@ -4,6 +4,9 @@ the two alternating in one process, and the PEAR of the result against the best 
     python tools/time_pearsearch.py                   # n = 8192, m = 1000, K = 50, 16 runs, 7 repetitions of each
     python tools/time_pearsearch.py --n 2000 --reps 5 --no-quality
     python tools/time_pearsearch.py --maxsweeps 1 --no-quality   # with the default: time per sweep and time outside the sweeps
+    python tools/time_pearsearch.py --large           # rc_pear_search_large and rc_psm_search_large (Binder) beside them; above
+                                                      # n = 8192 those two alone.  --large --whole: one searchpear call besides,
+                                                      # split into counts, dendrogram start and search
     python tools/time_pearsearch.py --psm-only        # Binder and the VI bound only: for comparing two builds of the library
                                                       # (RC_LIB_PATH selects the build), alternating processes
 
@@ -16,6 +19,7 @@ import json
 import os
 import statistics
 import sys
+import time
 
 import numpy as np
 
@@ -50,6 +54,8 @@ def main():
     ap.add_argument("--maxsweeps", type=int, default=100)
     ap.add_argument("--psm-only", action="store_true")
     ap.add_argument("--no-quality", action="store_true")
+    ap.add_argument("--large", action="store_true")
+    ap.add_argument("--whole", action="store_true")
     a = ap.parse_args()
     S = planted_samples(a.n, a.m, a.K, a.noise)
     C, counts_ms = _lib.samples_counts(S)
@@ -60,6 +66,11 @@ def main():
         searches["VI"] = lambda: _lib.psm_search(C, a.m, 1, inits, orders, maxsweeps=a.maxsweeps)
     else:
         searches["PEAR"] = lambda: _lib.pear_search(C, a.m, inits, orders, maxsweeps=a.maxsweeps)
+    if a.large:
+        if a.n > 8192:
+            searches.clear()
+        searches["binder_large"] = lambda: _lib.psm_search_large(C, a.m, 0, inits, orders, maxsweeps=a.maxsweeps)
+        searches["PEAR_large"] = lambda: _lib.pear_search_large(C, a.m, inits, orders, maxsweeps=a.maxsweeps)
     for f in searches.values():                                      # module load, first launches, clocks
         f()
     ms, last = {k: [] for k in searches}, {}
@@ -73,6 +84,23 @@ def main():
                               labels_sha=hashlib.sha256(np.ascontiguousarray(r["labels"]).tobytes()).hexdigest()[:16],
                               sweeps=[int(x) for x in r["sweeps"]], converged=int(r["converged"].sum()), K=[int(x) for x in r["K"]])),
               flush=True)
+    if a.large:
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        sweeps = max(int(x) for x in last["PEAR_large"]["sweeps"])       # the runs are concurrent: the longest one sets the time
+        print(json.dumps(dict(base, what="large", us_per_step=round(1e3 * med["PEAR_large"] / (sweeps * a.n), 3),
+                              ratios={f"PEAR_large/{k}": round(med["PEAR_large"] / v, 3) for k, v in med.items() if k != "PEAR_large"})), flush=True)
+        if a.whole:
+            class Result:
+                clusts = list(S)
+            t0 = time.perf_counter()
+            den = rc.dendrogram(Result)
+            t1 = time.perf_counter()
+            _, info = rc.searchpear(Result, nruns=a.nruns, maxsweeps=a.maxsweeps)
+            t2 = time.perf_counter()
+            print(json.dumps(dict(base, what="searchpear", wall_s=round(t2 - t1, 3), search_kernel_ms=round(info["kernel_ms"], 3),
+                                  counts_ms=round(info["counts_ms"], 3), dendrogram_alone_wall_s=round(t1 - t0, 3),
+                                  dendrogram_kernel_ms=round(den["kernel_ms"], 3), pear=float(info["pear"][info["best"]]))), flush=True)
+        return
     if a.psm_only:
         return
     ratio = statistics.median(ms["PEAR"]) / statistics.median(ms["binder"])

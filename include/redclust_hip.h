@@ -1257,6 +1257,20 @@ int32_t rc_map_search(rc_ctx *ctx, int32_t nruns, const int64_t *init /* nruns×
                       int64_t *blocks_out /* may be NULL: nruns×Kcap×Kcap×4 */, int64_t *slots_out /* may be NULL: nruns×n */,
                       int32_t *best /* first run of maximal logposterior */, double *kernel_ms);
 
+/* MAP search, large n (DESIGN.md §8 "MAP search, large n"): rc_map_search — signature, contract, the order of the errors
+ * (their text starts with this name) and, wherever both accept the input, every byte of every output, blocks_out included —
+ * with the capacity n <= 32767 (the indices fit 15 bits), 2·nruns·n < 2^31, Kcap <= 1024; any n >= 1 is accepted.  The two
+ * share one host body.  The run's slots live in LDS in the context's internal point order, a visit reads its row
+ * contiguously in 16-byte loads with the next row's head prefetched (k_map_large), and the cells of the starting labels are
+ * built on the whole device beforehand (k_map_cells, 64-bit global atomics on the exact halves; runs that start from empty
+ * labels launch nothing); kernel_ms covers both kernels.  RC_ERR_OOM (host or device memory) comes before any kernel. */
+int32_t rc_map_search_large(rc_ctx *ctx, int32_t nruns, const int64_t *init /* nruns×n, 0 = unallocated */,
+                            const int32_t *order /* nruns×n, 1-based */, const double *r /* nruns */, const double *p /* nruns */,
+                            const rc_params *params /* NULL: the context's */, int32_t maxK, int32_t maxsweeps,
+                            int64_t *labels_out /* nruns×n, sortlabels'd */, void *runs_out /* rc_map_run_t[nruns] */,
+                            int64_t *blocks_out /* may be NULL: nruns×Kcap×Kcap×4 */, int64_t *slots_out /* may be NULL: nruns×n */,
+                            int32_t *best /* first run of maximal logposterior */, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

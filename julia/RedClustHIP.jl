@@ -1298,6 +1298,28 @@ beats the best candidate, that candidate is returned and `info.best` is 0.  `inf
 function searchmapestimate(b::HIPBackend, data::MCMCData, candidates::Vector{<:AbstractVector{<:Integer}},
                            params::PriorHyperparamsList; r, p, nruns::Integer = 16, maxK::Integer = 0, maxsweeps::Integer = 100,
                            seed::Integer = 0, init::Union{Matrix{Int64},Nothing} = nothing)
+    return mapsearchruns(b, data, candidates, params, false; r = r, p = p, nruns = nruns, maxK = maxK, maxsweeps = maxsweeps,
+                         seed = seed, init = init)
+end
+
+"""
+    searchmap(HIPBackend(), data, candidates, params; r, p, nruns = 16, maxK = 0, maxsweeps = 100, seed = 0, init = nothing) -> (clust, info)
+
+`searchmapestimate` — arguments, runs, result — for any n <= 32767.  It routes by n alone: up to 8192 points it is
+`searchmapestimate`'s call; above, the large-n kernels run (rc_map_search_large), the same function of a run's inputs.  Above
+8192 points a dendrogram's cut is polished by passing it here as a candidate.
+"""
+function searchmap(b::HIPBackend, data::MCMCData, candidates::Vector{<:AbstractVector{<:Integer}},
+                   params::PriorHyperparamsList; r, p, nruns::Integer = 16, maxK::Integer = 0, maxsweeps::Integer = 100,
+                   seed::Integer = 0, init::Union{Matrix{Int64},Nothing} = nothing)
+    return mapsearchruns(b, data, candidates, params, size(data.D, 1) > 8192; r = r, p = p, nruns = nruns, maxK = maxK,
+                         maxsweeps = maxsweeps, seed = seed, init = init)
+end
+
+# searchmapestimate's body; large: rc_map_search_large in place of rc_map_search
+function mapsearchruns(b::HIPBackend, data::MCMCData, candidates::Vector{<:AbstractVector{<:Integer}},
+                       params::PriorHyperparamsList, large::Bool; r, p, nruns::Integer, maxK::Integer, maxsweeps::Integer,
+                       seed::Integer, init::Union{Matrix{Int64},Nothing})
     n = size(data.D, 1)
     L = length(candidates)
     L >= 1 || throw(ArgumentError("No candidates."))
@@ -1340,10 +1362,17 @@ function searchmapestimate(b::HIPBackend, data::MCMCData, candidates::Vector{<:A
     check(Ptr{Cvoid}(C_NULL), rc)
     ctx = h[]
     try
-        rc = ccall((:rc_map_search, LIB), Int32,
-                   (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{RcParams}, Int32, Int32, Ptr{Int64},
-                    Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}, Ptr{Cdouble}),
-                   ctx, R, initm, order, rs, ps, Ref(RcParams(params)), maxK, maxsweeps, labels, runs, C_NULL, C_NULL, best, ms)
+        rc = if large
+            ccall((:rc_map_search_large, LIB), Int32,
+                  (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{RcParams}, Int32, Int32, Ptr{Int64},
+                   Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}, Ptr{Cdouble}),
+                  ctx, R, initm, order, rs, ps, Ref(RcParams(params)), maxK, maxsweeps, labels, runs, C_NULL, C_NULL, best, ms)
+        else
+            ccall((:rc_map_search, LIB), Int32,
+                  (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{RcParams}, Int32, Int32, Ptr{Int64},
+                   Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}, Ptr{Cdouble}),
+                  ctx, R, initm, order, rs, ps, Ref(RcParams(params)), maxK, maxsweeps, labels, runs, C_NULL, C_NULL, best, ms)
+        end
         check(ctx, rc)
     finally
         ccall((:rc_destroy, LIB), Int32, (Ptr{Cvoid},), ctx)
@@ -1358,7 +1387,7 @@ function searchmapestimate(b::HIPBackend, data::MCMCData, candidates::Vector{<:A
     return (beaten ? labels[:, w] : Vector{Int64}(candidates[top]), info)
 end
 
-export searchmapestimate
+export searchmapestimate, searchmap
 
 """
     clusterprofiles(HIPBackend(), data, labellings; points = true) -> (K, medoids, medoid_within, within, nearest, neighbour, silhouette, eD, kernel_ms)

@@ -317,6 +317,8 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rc_map_search": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RcParams), C.c_int32,
                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_map_search_large": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RcParams), C.c_int32,
+                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rc_layout_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rc_bulk_plan_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rc_event_overhead_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
@@ -698,7 +700,13 @@ class Context:
         return dict(loglik=ll[:nl], logprior=None if lp is None else lp[:nl], logposterior=None if lp is None else ll[:nl] + lp[:nl],
                     K=K[:nl], sizes=sizes, blocks=per, eD=int(eD.value), eL=int(eL.value), kernel_ms=float(ms.value))
 
-    def map_search(self, init, order, r, p, params=None, maxK: int = 0, maxsweeps: int = 100, want_state: bool = False) -> dict:
+    def map_search_large(self, init, order, r, p, params=None, maxK: int = 0, maxsweeps: int = 100, want_state: bool = False) -> dict:
+        """rc_map_search_large: map_search — arguments, runs, results, bit for bit — by the kernels whose capacity is
+        n <= 32767 (csrc/mapsearch_large.inc.hip: k_map_cells and k_map_large), at every n."""
+        return self.map_search(init, order, r, p, params, maxK, maxsweeps, want_state, _large=True)
+
+    def map_search(self, init, order, r, p, params=None, maxK: int = 0, maxsweeps: int = 100, want_state: bool = False, *,
+                   _large: bool = False) -> dict:
         """rc_map_search: the greedy search over all partitions for the labelling of maximum log-posterior under this context's
         matrices; its state, layout and counts are untouched.  init: nruns×n labels (0 = unallocated); order: nruns×n 1-based
         permutations; r, p: a scalar or one value per run; params: a dict of hyperparameters (None: the context's).  Returns a
@@ -718,14 +726,15 @@ class Context:
         Kcap = int(maxK) if int(maxK) > 0 else min(n, 1024)
         labels = np.zeros((max(nruns, 1), n), np.int64)
         runs = (RcMapRun * max(nruns, 1))()
-        state = want_state and 1 <= Kcap <= 1024 and n <= 8192                     # otherwise the library refuses the call
+        state = want_state and 1 <= Kcap <= 1024 and n <= (32767 if _large else 8192)   # otherwise the library refuses the call
         blocks = np.zeros((max(nruns, 1), Kcap, Kcap, 4), np.int64) if state else None
         slots = np.zeros((max(nruns, 1), n), np.int64) if state else None
         best, ms = C.c_int32(-1), C.c_double()
-        self._chk(self.L.rc_map_search(self.h, nruns, init.ctypes.data, order.ctypes.data, r.ctypes.data, p.ctypes.data,
-                                       None if prm is None else C.byref(prm), int(maxK), int(maxsweeps), labels.ctypes.data, runs,
-                                       None if blocks is None else blocks.ctypes.data, None if slots is None else slots.ctypes.data,
-                                       C.byref(best), C.byref(ms)))
+        entry = self.L.rc_map_search_large if _large else self.L.rc_map_search
+        self._chk(entry(self.h, nruns, init.ctypes.data, order.ctypes.data, r.ctypes.data, p.ctypes.data,
+                        None if prm is None else C.byref(prm), int(maxK), int(maxsweeps), labels.ctypes.data, runs,
+                        None if blocks is None else blocks.ctypes.data, None if slots is None else slots.ctypes.data,
+                        C.byref(best), C.byref(ms)))
         out = dict(labels=labels[:nruns], best=int(best.value), kernel_ms=float(ms.value), Kcap=Kcap,
                    blocks=None if blocks is None else blocks[:nruns], slots=None if slots is None else slots[:nruns])
         for k, ty in RcMapRun._fields_:

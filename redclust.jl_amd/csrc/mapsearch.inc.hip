@@ -356,14 +356,15 @@ static hipError_t launch(bool rep, int runs, size_t lds, const View &V, const Ar
     return hipGetLastError();
 }
 
-}  // namespace mapsearch
+// mapsearch_large.inc.hip: k_map_cells for the ncells runs of the launch in runlist, then k_map_large
+static hipError_t launch_large(bool rep, int runs, const View &V, const Args &A, const int *runlist, int ncells);
 
-extern "C" int32_t rc_map_search(rc_ctx *c, int32_t nruns, const int64_t *init, const int32_t *order, const double *r, const double *p,
-                                 const rc_params *params, int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out_,
-                                 int64_t *blocks_out, int64_t *slots_out, int32_t *best, double *kernel_ms)
+// The one host body of rc_map_search and rc_map_search_large (large): the staging, the checks, the cell budget and its launch
+// chunks, and the scoring pass that reports everything.  The two differ in the capacity in n and in the kernels they launch.
+static int32_t search(const char *who, bool large, rc_ctx *c, int32_t nruns, const int64_t *init, const int32_t *order, const double *r, const double *p,
+                      const rc_params *params, int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out_,
+                      int64_t *blocks_out, int64_t *slots_out, int32_t *best, double *kernel_ms)
 {
-    using namespace mapsearch;
-    const char *who = "rc_map_search";
     rc_map_run_t *runs_out = (rc_map_run_t *)runs_out_;
     int32_t rc = clu::check_ctx(c, who);
     if (rc != RC_OK) return rc;
@@ -410,7 +411,7 @@ extern "C" int32_t rc_map_search(rc_ctx *c, int32_t nruns, const int64_t *init, 
     } else if (!c->have_params) return fail(c, RC_ERR_STATE, "%s: params is NULL and the context has no parameters set", who);
     const rc_params P = params ? *params : c->P;
     // ---- the capacities
-    rc = check_lds_capacity(c, who, n);
+    rc = large ? RC_OK : check_lds_capacity(c, who, n);                            // (large: check_label_shape's 32767 is the limit)
     if (rc != RC_OK) return rc;
     rc = check_label_shape(c, who, n, "points", 2 * (int64_t)nruns, "2·nruns");   // the final labellings and the starts are scored in one batch
     if (rc != RC_OK) return rc;
@@ -434,6 +435,17 @@ extern "C" int32_t rc_map_search(rc_ctx *c, int32_t nruns, const int64_t *init, 
     HIPCHK(c, hipMemcpy(d_r, r, (size_t)nruns * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(d_p, p, (size_t)nruns * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(c, S.upload(B, 0, sizeof(RunOut)));
+    // large: the runs that start with clusters, in run order — k_map_cells builds their cells, a launch's are a stretch of the list
+    std::vector<int> cellruns;
+    int *d_cellruns = nullptr;
+    if (large) {
+        try {
+            for (int q = 0; q < nruns; ++q)
+                if (S.K[(size_t)q]) cellruns.push_back(q);
+        } catch (const std::bad_alloc &) { return fail(c, RC_ERR_OOM, "%s: no host memory", who); }
+        HIPCHK(c, B.alloc(d_cellruns, std::max<size_t>(1, cellruns.size())));
+        if (!cellruns.empty()) HIPCHK(c, hipMemcpy(d_cellruns, cellruns.data(), cellruns.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
 
     Args A{};
     A.C = Consts{P.delta1, P.delta2, P.alpha, P.beta, P.zeta, P.gamma, std::lgamma(P.delta1), std::lgamma(P.delta2), std::log(P.beta), std::log(P.gamma),
@@ -451,7 +463,10 @@ extern "C" int32_t rc_map_search(rc_ctx *c, int32_t nruns, const int64_t *init, 
         A.run0 = q0;
         HIPCHK(c, hipMemsetAsync(d_cells, 0, cell_elems * (size_t)runs * sizeof(long long), 0));
         HIPCHK(c, ev.begin(0));
-        HIPCHK(c, launch(P.repulsion != 0, runs, lds, V, A));
+        if (large) {
+            const auto lo = std::lower_bound(cellruns.begin(), cellruns.end(), q0), up = std::lower_bound(cellruns.begin(), cellruns.end(), q0 + runs);
+            HIPCHK(c, launch_large(P.repulsion != 0, runs, V, A, d_cellruns + (lo - cellruns.begin()), (int)(up - lo)));
+        } else HIPCHK(c, launch(P.repulsion != 0, runs, lds, V, A));
         HIPCHK(c, ev.end(0));
         HIPCHK(c, ev.elapsed_ms(ms_acc));
         if (blocks_out) HIPCHK(c, hipMemcpyAsync(blocks_out + (size_t)q0 * cell_elems, d_cells, cell_elems * (size_t)runs * sizeof(long long), hipMemcpyDeviceToHost, 0));
@@ -501,4 +516,14 @@ extern "C" int32_t rc_map_search(rc_ctx *c, int32_t nruns, const int64_t *init, 
     }
     *best = b;
     return RC_OK;
+}
+
+}  // namespace mapsearch
+
+extern "C" int32_t rc_map_search(rc_ctx *c, int32_t nruns, const int64_t *init, const int32_t *order, const double *r, const double *p,
+                                 const rc_params *params, int32_t maxK, int32_t maxsweeps, int64_t *labels_out, void *runs_out,
+                                 int64_t *blocks_out, int64_t *slots_out, int32_t *best, double *kernel_ms)
+{
+    return mapsearch::search("rc_map_search", false, c, nruns, init, order, r, p, params, maxK, maxsweeps, labels_out, runs_out, blocks_out,
+                             slots_out, best, kernel_ms);
 }

@@ -7551,4 +7551,5 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "score.inc.hip"
 #include "mapmath.inc.hpp"
 #include "mapsearch.inc.hip"
+#include "mapsearch_large.inc.hip"   // k_map_large<BITS, STORED, REP>, k_map_cells: the same search with n <= 32767
 #include "profile.inc.hip"

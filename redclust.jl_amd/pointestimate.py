@@ -487,7 +487,8 @@ def dendrogrampointestimate(samples_or_counts=None, loss="VI", linkage="average"
     """hclustpointestimate — arguments, every criterion, exact=, results — for any n <= 32767 (m·n < 2^31).  Up to n = 8192 it is
     hclustpointestimate's call and returns its bytes; above that the dendrogram and the VI bound of its cuts come from
     csrc/hclust_large.inc.hip (rc_hclust_large*, rc_hclust_cut_large) — the deterministic init= for searchpointestimate and
-    searchvi at that size.  polish=True stays bound by searchmapestimate's n <= 8192 (ValueError above)."""
+    searchvi at that size.  polish=True stays bound by searchmapestimate's n <= 8192 (ValueError above): above 8192 points the
+    cut is polished by passing it to searchmap (score.py) as a candidate."""
     return _hclustpointestimate(samples_or_counts, loss, linkage, maxK, numsamples, ctx, device, exact, criterion, data, params, r, p,
                                 polish, large=True)
 

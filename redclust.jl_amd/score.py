@@ -133,7 +133,22 @@ def searchmapestimate(data_or_ctx, candidates=None, params=None, r=None, p=None,
     start_logposterior and logposterior (per run; the first is NaN for a start with unallocated points), loglik, logprior,
     sweeps, converged, moves, K, capped, labels (per run), runs (the starts as rows of labels), best (the run returned, or −1
     when no run beat the best candidate, which is then returned as mapestimate would), candidate_logposterior and kernel_ms.
-    The result is never worse than mapestimate's on the same candidates."""
+    The result is never worse than mapestimate's on the same candidates.  n <= 8192; searchmap goes on to 32767."""
+    return _search_map(False, data_or_ctx, candidates, params, r, p, nruns, maxK, maxsweeps, seed, init, scores, device)
+
+
+def searchmap(data_or_ctx, candidates=None, params=None, r=None, p=None, *, nruns: int = 16, maxK: int = 0, maxsweeps: int = 100,
+              seed: int = 0, init=None, scores: dict | None = None, device: int = 0):
+    """searchmapestimate — arguments, runs, results — for any n <= 32767 (DESIGN.md §8 "MAP search, large n").  It routes by n
+    alone: up to 8192 points it is searchmapestimate's call and bytes; above, the large-n kernels run (rc_map_search_large:
+    k_map_cells and k_map_large of csrc/mapsearch_large.inc.hip), the same function of a run's inputs.  Above 8192 points a
+    dendrogram's cut is polished by passing it here as a candidate or a row of init (dendrogrampointestimate's polish=True
+    keeps searchmapestimate's limit)."""
+    return _search_map(True, data_or_ctx, candidates, params, r, p, nruns, maxK, maxsweeps, seed, init, scores, device)
+
+
+def _search_map(route, data_or_ctx, candidates, params, r, p, nruns, maxK, maxsweeps, seed, init, scores, device):
+    """searchmapestimate's body; route: beyond 8192 points call the large entry (searchmap)"""
     ctx, own = _context(data_or_ctx, device)
     try:
         if params is None and own:
@@ -183,7 +198,8 @@ def searchmapestimate(data_or_ctx, candidates=None, params=None, r=None, p=None,
         need = max(len(np.unique(x[x > 0])) for x in runs)
         if maxK and need > maxK:
             raise ValueError(f"a start has {need} clusters, more than maxK = {maxK}")
-        res = ctx.map_search(runs, np.stack(orders), np.asarray(rs), np.asarray(ps), P, maxK=maxK, maxsweeps=maxsweeps)
+        search = ctx.map_search_large if route and n > 8192 else ctx.map_search
+        res = search(runs, np.stack(orders), np.asarray(rs), np.asarray(ps), P, maxK=maxK, maxsweeps=maxsweeps)
         best = res["best"]
         info = {k: res[k] for k in ("start_logposterior", "logposterior", "loglik", "logprior", "sweeps", "converged", "moves", "K",
                                     "capped", "labels", "kernel_ms")}

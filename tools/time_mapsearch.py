@@ -6,6 +6,7 @@ is no earlier device implementation, and the reference has no such search.
     python tools/time_mapsearch.py --n 2048 --m 200    # a smaller chain case
     python tools/time_mapsearch.py --no-ref            # skip the NumPy restatement
     python tools/time_mapsearch.py --no-chain          # the worst case alone (--no-worst: the chain case alone)
+    python tools/time_mapsearch.py --large --n 32767   # rc_map_search_large on the chain case; at n <= 8192 beside rc_map_search
 
 Chain case (seed 0): n = 8192 points in 3 dimensions around 50 centres (from_points: the distances are computed on the device,
 the logarithms derived), the likelihood's hyperparameters fitted to the planted partition, an m = 1000 chain from the planted
@@ -64,7 +65,11 @@ def main():
     ap.add_argument("--no-ref", action="store_true")
     ap.add_argument("--no-worst", action="store_true")
     ap.add_argument("--no-chain", action="store_true")
+    ap.add_argument("--large", action="store_true")
+    ap.add_argument("--reps", type=int, default=5)
     a = ap.parse_args()
+    if a.large:
+        return large(a)
     if not a.no_chain:
         chain(a)
     if not a.no_worst:
@@ -106,6 +111,45 @@ def chain(a):
         ms = ref_per_visit(c2, P2, ir, np.random.default_rng(0).permutation(a.ref_n) + 1, 1.0, 0.5, a.ref_visits)
         print(json.dumps(dict(what="numpy_ref", case="chain", n=a.ref_n, K=a.K, visits_timed=a.ref_visits, ms_per_visit=round(ms, 2))), flush=True)
         c2.close()
+
+
+def large(a):
+    """--large: the chain case at --n (up to 32767) through rc_map_search_large — the starts searchmap takes, the --nruns best
+    distinct samples and empty labels, under Philox orders — with and without repulsion: the median kernel time (k_map_cells
+    and k_map_large together) of --reps calls after a warm-up, per visit of the longest run, and at n <= 8192 rc_map_search on
+    the same runs in the same process with the ratio.  k_map_cells' share is read from a kernel trace of this command."""
+    X, truth, init = chain_case(a.n, a.K)
+    ctx = rc.Context.from_points(X)
+    P = rc.likelihood_hyperparams_device(ctx, truth)
+    ctx.set_params(**P)
+    params = rc.PriorHyperparamsList(**{k: P[k] for k in ("delta1", "delta2", "alpha", "beta", "zeta", "gamma")})
+    options = rc.MCMCOptionsList(numiters=a.m, burnin=0, thin=1, numGibbs=1, numMH=0)
+    result = rc.runsampler(rc.MCMCData(X), options, params, rc.MCMCState(init, 1.0, 0.5), verbose=False, seed=0, ctx=ctx)
+    sc = rc.scorelabellings(ctx, result)
+    S, lp = np.stack([np.asarray(z, dtype=np.int64) for z in result.clusts]), np.asarray(sc["logposterior"])
+    starts, rs, ps, seen = [], [], [], set()
+    for c in np.argsort(-lp, kind="stable"):
+        key = np.unique(S[c], return_inverse=True)[1].tobytes()
+        if key not in seen and len(starts) < a.nruns:
+            seen.add(key); starts.append(S[c]); rs.append(float(np.asarray(result.r)[c])); ps.append(float(np.asarray(result.p)[c]))
+    starts.append(np.zeros(a.n, np.int64)); rs.append(rs[0]); ps.append(ps[0])
+    rng = np.random.Generator(np.random.Philox(key=0))
+    runs, orders = np.stack(starts).astype(np.int64), np.stack([rng.permutation(a.n).astype(np.int32) + 1 for _ in starts])
+    for rep in (True, False):
+        prm, med = dict(P, repulsion=rep), {}
+        for name, entry in (("rc_map_search_large", ctx.map_search_large),) + ((("rc_map_search", ctx.map_search),) if a.n <= 8192 else ()):
+            ms = []
+            for _ in range(1 + a.reps):                                  # the first call is the warm-up
+                res = entry(runs, orders, np.asarray(rs), np.asarray(ps), prm, maxsweeps=a.maxsweeps)
+                ms.append(res["kernel_ms"])
+            med[name] = float(np.median(ms[1:]))
+            visits = int(res["sweeps"].max()) * a.n
+            print(json.dumps(dict(what="device", case="large", entry=name, n=a.n, m=a.m, runs=len(runs), repulsion=rep, reps=a.reps,
+                                  kernel_ms_median=round(med[name], 2), kernel_ms=[round(x, 2) for x in ms[1:]],
+                                  sweeps=[int(x) for x in res["sweeps"]], us_per_visit_of_the_longest_run=round(1e3 * med[name] / visits, 2))), flush=True)
+        if "rc_map_search" in med:
+            print(json.dumps(dict(what="ratio", n=a.n, repulsion=rep, large_over_old=round(med["rc_map_search_large"] / med["rc_map_search"], 3))), flush=True)
+    ctx.close()
 
 
 def worst(a):

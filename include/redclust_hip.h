@@ -1103,6 +1103,17 @@ int32_t rc_relabel(int32_t device, const int64_t *samples /* m×n, labels 1..n *
                    int64_t *labels_out /* m×n or NULL */, int64_t *maps_out /* m×maps_width or NULL */, int64_t maps_width,
                    int64_t *overlap_out /* m */, void *counts_out /* uint32_t n×(Kp+1) */, double *kernel_ms);
 
+/* rc_relabel for pivots and samples of up to 4096 clusters: the same parameters, outputs, tie rule and errors, and where
+ * rc_relabel accepts the input the same bytes.  It always runs its own kernel (k_relabel_wide, csrc/relabel_wide.inc.hip;
+ * DESIGN.md §8 "Wide relabelling"), which keeps a sample's contingency table sparse — at most n non-zero cells, O(n + K)
+ * memory per resident workgroup — and spreads the assignment's column scan over a workgroup of 1024 threads.
+ * RC_ERR_CAPACITY: n > 32767, a pivot or a sample of more than 4096 clusters, m >= 2^31.  RC_RELABEL_WORKSPACE_KIB is
+ * honoured; RC_RELABEL_TABLE_GLOBAL has no meaning here. */
+int32_t rc_relabel_wide(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n,
+                        const int64_t *pivot /* n, labels 1..n */, int64_t Kp,
+                        int64_t *labels_out /* m×n or NULL */, int64_t *maps_out /* m×maps_width or NULL */, int64_t maps_width,
+                        int64_t *overlap_out /* m */, void *counts_out /* uint32_t n×(Kp+1) */, double *kernel_ms);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Scoring labellings: the log-likelihood (src/mcmc.jl:1-56) and log-prior (src/mcmc.jl:58-78) of each of L given labellings
  * under the model, against the context's fixed-point matrices as they are (64- or 32-bit storage, logD stored or derived,

@@ -1214,6 +1214,36 @@ end
 export relabel
 
 """
+    relabel_wide(HIPBackend(), result, pivot) -> (labels, maps, overlap, counts, pivot_labels, kernel_ms)
+
+`relabel` for a pivot and samples of up to 4096 clusters each.  With at most 1024 clusters everywhere it is `relabel`; otherwise
+rc_relabel_wide computes the same definition with the same tie rule on a sparse contingency table.
+"""
+function relabel_wide(b::HIPBackend, result, pivot::AbstractVector{<:Integer})
+    samples = samplematrix(result)
+    n, m = size(samples)
+    length(pivot) == n || throw(ArgumentError("Length of the input vectors must be equal."))
+    piv = Vector{Int64}(pivot)
+    names = sort(unique(piv))
+    Kp = length(names)
+    W = maximum(length(unique(view(samples, :, s))) for s in 1:m)
+    max(Kp, W) <= 1024 && return relabel(b, result, pivot)
+    labels = Matrix{Int64}(undef, n, m)                           # column s = sample s: row-major m×n for the library
+    maps = Matrix{Int64}(undef, W, m)
+    overlap = Vector{Int64}(undef, m)
+    counts = Matrix{UInt32}(undef, Kp + 1, n)                     # row-major n×(K_p+1)
+    ms = Cdouble[0]
+    rc = ccall((:rc_relabel_wide, LIB), Int32,
+               (Int32, Ptr{Int64}, Int64, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Cvoid}, Ptr{Cdouble}),
+               b.device, samples, m, n, piv, Kp, labels, maps, W, overlap, counts, ms)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    return (labels = permutedims(labels), maps = permutedims(maps), overlap = overlap, counts = permutedims(counts),
+            pivot_labels = names, kernel_ms = ms[1])
+end
+
+export relabel_wide
+
+"""
     scorelabellings(HIPBackend(), data, labellings, params; r = nothing, p = nothing) -> (loglik, logprior, logposterior, K, kernel_ms)
 
 The log-likelihood of each of `L` labellings (a vector of label vectors, or the `clusts` of a result) under the model with

@@ -15,7 +15,7 @@ from .pointestimate import (getpointestimate, lossmatrix, binderloss, infodist, 
                             summarise, searchpointestimate, expectedloss, expectedvi, expectedid, cocluster_counts,
                             posterior_counts, posterior_coclustering, hclust, hclustpointestimate, expectedlosses,
                             linkage_matrix, leaf_order, partitiondistances, expecteddistances, credibleball,
-                            credibleball_from_distances, relabel, Relabelling, expectedpear, pearfraction, expectedpears,
+                            credibleball_from_distances, relabel, relabel_wide, Relabelling, expectedpear, pearfraction, expectedpears,
                             searchmaxpear, maxpear, expectedari, searchvi, searchid, dendrogram, dendrogrampointestimate,
                             searchpear)
 from .wasabi import searchvigroups, wasabi, wasabi_scan, WasabiResult  # noqa: F401

@@ -308,6 +308,8 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "rc_relabel": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "rc_relabel_wide": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "rc_score_labellings": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RcParams), C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_double)]),
@@ -1386,9 +1388,16 @@ def partition_distances(labels, samples, want_sq: bool = True, want_phi: bool = 
                 kernel_ms=float(ms.value))
 
 
-def relabel(samples, pivot, want_labels: bool = True, want_maps: bool = True, device: int = 0) -> dict:
+def largest_sample(S) -> int:
+    """the largest cluster count of the rows of S (m×n int64), without a sort; 1 when a label is outside 1..n"""
+    valid = S.size > 0 and S.min() >= 1 and S.max() <= S.shape[1]   # otherwise the library names the label
+    return max(np.count_nonzero(np.bincount(row)) for row in S) if valid else 1
+
+
+def relabel(samples, pivot, want_labels: bool = True, want_maps: bool = True, device: int = 0, entry: str = "rc_relabel") -> dict:
     """rc_relabel for m×n samples and a pivot of n labels (int64 in 1..n): a dict with labels (m×n int64, or None), maps (m × the
-    largest K_s, or None), overlap (m), counts (n×(K_p+1) uint32), pivot_labels (the K_p names, ascending) and kernel_ms."""
+    largest K_s, or None), overlap (m), counts (n×(K_p+1) uint32), pivot_labels (the K_p names, ascending) and kernel_ms.
+    entry: the library's function of that parameter list to call."""
     L = lib()
     S = np.ascontiguousarray(samples, dtype=np.int64)
     c = np.ascontiguousarray(pivot, dtype=np.int64)
@@ -1397,17 +1406,21 @@ def relabel(samples, pivot, want_labels: bool = True, want_maps: bool = True, de
     m, n = S.shape
     names = np.unique(c).astype(np.int64)
     Kp = len(names)
-    valid = S.size > 0 and S.min() >= 1 and S.max() <= n            # otherwise the library names the label
-    W = max(np.count_nonzero(np.bincount(row)) for row in S) if valid else 1       # the largest K_s, without a sort
+    W = largest_sample(S)
     labels = np.zeros((max(m, 1), max(n, 1)), np.int64) if want_labels else None
     maps = np.zeros((max(m, 1), max(W, 1)), np.int64) if want_maps else None
     overlap = np.zeros(max(m, 1), np.int64)
     counts = np.zeros((max(n, 1), Kp + 1), np.uint32)
     ms = C.c_double()
-    rc = L.rc_relabel(int(device), S.ctypes.data, m, n, c.ctypes.data, Kp, None if labels is None else labels.ctypes.data,
-                      None if maps is None else maps.ctypes.data, W, overlap.ctypes.data, counts.ctypes.data, C.byref(ms))
+    rc = getattr(L, entry)(int(device), S.ctypes.data, m, n, c.ctypes.data, Kp, None if labels is None else labels.ctypes.data,
+                           None if maps is None else maps.ctypes.data, W, overlap.ctypes.data, counts.ctypes.data, C.byref(ms))
     _check(rc)
     return dict(labels=labels, maps=maps, overlap=overlap, counts=counts, pivot_labels=names, kernel_ms=float(ms.value))
+
+
+def relabel_wide(samples, pivot, want_labels: bool = True, want_maps: bool = True, device: int = 0) -> dict:
+    """rc_relabel_wide: relabel's arguments and dict for pivots and samples of up to 4096 clusters, always by k_relabel_wide."""
+    return relabel(samples, pivot, want_labels, want_maps, device, entry="rc_relabel_wide")
 
 
 def loglik_from_blocks(blocks, sizes, n: int, eD: int, eL: int, params: dict) -> float:

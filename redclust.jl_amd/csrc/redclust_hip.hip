@@ -7547,7 +7547,9 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "pairwise.inc.hip"
 #include "predictjoint.inc.hip"
 #include "partdist.inc.hip"
+#include "relabel_host.inc.hip"       // relabel::run: the host side of the two entries below
 #include "relabel.inc.hip"
+#include "relabel_wide.inc.hip"       // k_relabel_wide: the same on a sparse table, up to 4096 clusters
 #include "score.inc.hip"
 #include "mapmath.inc.hpp"
 #include "mapsearch.inc.hip"

@@ -4,7 +4,9 @@
 // contract is in include/redclust_hip.h.  Included at the end of redclust_hip.hip (same translation unit: shares fail(), HIPCHK,
 // the holders and select_device of hostutil.inc.hip, and compact_row / check_rows of partdist.inc.hip).
 //
-// Host: the pivot and every sample are compacted to dense u16 ids in ascending label order (compact_row).
+// Host: the pivot and every sample are compacted to dense u16 ids in ascending label order (compact_row).  The checks, the chunks,
+// the copies and the timing are relabel::run (relabel_host.inc.hip, included before this file), which rc_relabel_wide shares;
+// this file gives it k_relabel's launcher (Launch).
 //
 // k_relabel: one workgroup of TPB threads per sample (the grid is capped, workgroups loop), three phases.
 //   1. Table.  T[r][c], r over the side with fewer clusters (the pivot on a tie), c over the other: R rows of `stride` 16-bit
@@ -22,11 +24,9 @@
 
 namespace relabel {
 
-constexpr int64_t NMAX = 32767;                 // a cell of the table fits 15 bits
 constexpr int KMAX = 1024;                      // clusters of the pivot and of every sample
 constexpr int TPB = 256;                        // four waves: one per SIMD, up to eight workgroups per CU
 constexpr size_t LDS_BUDGET = 128 * 1024;       // vectors and table of one workgroup (the CU has 160 KiB)
-constexpr size_t WORKSPACE = (size_t)1 << 30;   // device bytes of one chunk of samples
 constexpr int GRID_MAX = 2048;                  // workgroups with the table in LDS
 constexpr int GLOBAL_GRID_MAX = 256;            // workgroups with the table in a global slab
 constexpr int INF = 0x3fffffff;
@@ -199,101 +199,37 @@ static inline size_t table_bytes(int Kp, int Ks, int &cols)
     return (size_t)R * (size_t)((cols + 1) & ~1) * 2;
 }
 
-}  // namespace relabel
+// k_relabel's launches: the table in LDS when it fits beside the vectors, else in one slab per resident workgroup
+struct Launch {
+    size_t slab_dwords = 0;
+    int grid_global = 1;
+    bool force_global = false;
+    unsigned *d_slab = nullptr;
 
-extern "C" int32_t rc_relabel(int32_t device, const int64_t *samples, int64_t m, int64_t n, const int64_t *pivot, int64_t Kp_in,
-                              int64_t *labels_out, int64_t *maps_out, int64_t maps_width, int64_t *overlap_out, void *counts_out,
-                              double *kernel_ms)
-{
-    using namespace relabel;
-    const char *who = "rc_relabel";
-    if (!samples || !pivot || !overlap_out || !counts_out) return fail(nullptr, RC_ERR_ARG, "%s: NULL argument", who);
-    if (m < 1 || n < 1) return fail(nullptr, RC_ERR_ARG, "%s: need m >= 1 and n >= 1 (got m=%lld n=%lld)", who, (long long)m, (long long)n);
-    if (n > NMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: n = %lld exceeds the %lld points whose counts fit 15 bits", who, (long long)n, (long long)NMAX);
-    if (m >= ((int64_t)1 << 31)) return fail(nullptr, RC_ERR_CAPACITY, "%s: m = %lld is not below 2^31", who, (long long)m);
-    int32_t rc = check_label_rows(nullptr, who, "pivot", pivot, 1, n);
-    if (rc != RC_OK) return rc;
-    rc = check_label_rows(nullptr, who, "sample", samples, m, n);
-    if (rc != RC_OK) return rc;
-
-    std::vector<int> cnt, id, Ks, names;
-    std::vector<unsigned short> h_piv;
-    try {
-        cnt.assign((size_t)n + 1, 0); id.assign((size_t)n + 1, 0); Ks.resize((size_t)m); h_piv.resize((size_t)n);
-    } catch (const std::bad_alloc &) { return fail(nullptr, RC_ERR_OOM, "%s: no host memory", who); }
-    const auto no_slot = [](int, int64_t, int) {};                    // only the ids and the cluster counts are wanted here
-    const int64_t Kp = compact_labels(pivot, n, cnt, id, no_slot);
-    dense_ids(pivot, n, id, h_piv.data());
-    if (Kp > KMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: the pivot has %lld clusters, more than %d", who, (long long)Kp, KMAX);
-    names.assign((size_t)Kp, 0);
-    for (int64_t j = 0; j < n; ++j) names[h_piv[(size_t)j]] = (int)pivot[j];
-    const size_t workspace = env_workspace_kib("RC_RELABEL_WORKSPACE_KIB", WORKSPACE);
-    // The samples are compacted here for their cluster counts, which the capacity checks need before any device work.  Their
-    // dense ids are kept for the chunks when all of them fit a workspace's worth of host memory, else made again per chunk.
-    const bool keep_ids = 2 * (size_t)m * (size_t)n <= workspace;
-    std::vector<unsigned short> h_zid;
-    if (keep_ids) {
-        try { h_zid.resize((size_t)m * n); } catch (const std::bad_alloc &) { return fail(nullptr, RC_ERR_OOM, "%s: no host memory for the ids of %lld samples", who, (long long)m); }
-    }
-    int64_t W = 0;
-    size_t slab_bytes = 0;                                            // the largest table of the call
-    for (int64_t s = 0; s < m; ++s) {
-        const int K = compact_labels(samples + (size_t)s * n, n, cnt, id, no_slot);
-        if (keep_ids) dense_ids(samples + (size_t)s * n, n, id, h_zid.data() + (size_t)s * n);
-        if (K > KMAX) return fail(nullptr, RC_ERR_CAPACITY, "%s: sample %lld has %lld clusters, more than %d", who, (long long)s + 1, (long long)K, KMAX);
-        Ks[(size_t)s] = K;
-        W = std::max<int64_t>(W, K);
-        int cols;
-        slab_bytes = std::max(slab_bytes, table_bytes((int)Kp, K, cols));
-    }
-    if (Kp_in != Kp) return fail(nullptr, RC_ERR_ARG, "%s: the pivot has %lld clusters, not %lld (counts is n x (K_p + 1))", who, (long long)Kp, (long long)Kp_in);
-    if (maps_out && maps_width < W) return fail(nullptr, RC_ERR_ARG, "%s: maps is %lld wide, the largest sample has %lld clusters", who, (long long)maps_width, (long long)W);
-    if (kernel_ms) *kernel_ms = 0.0;
-
-    rc = select_device(who, device);
-    if (rc != RC_OK) return rc;
-    const bool force_global = env_flag("RC_RELABEL_TABLE_GLOBAL");          // tests: the table in the global slab at every size
-    const int64_t Wd = maps_out ? maps_width : 0;
-    const size_t per_sample = 2 * (size_t)n + sizeof(int) + sizeof(long long) + (labels_out ? 8 * (size_t)n : 0) + 8 * (size_t)Wd;
-    const int64_t mc = std::max<int64_t>(1, std::min<int64_t>(m, (int64_t)(workspace / per_sample)));
-    // the slabs: one table per resident workgroup, within a quarter of the workspace (one workgroup at the least)
-    const size_t slab_dwords = (slab_bytes + 15) / 16 * 4;
-    const int grid_global = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(GLOBAL_GRID_MAX, mc),
-                                                                           (long long)(workspace / 4 / (slab_dwords * 4))));
-    if (!keep_ids) {
-        try { h_zid.resize((size_t)mc * n); } catch (const std::bad_alloc &) { return fail(nullptr, RC_ERR_OOM, "%s: no host memory for a chunk of %lld samples", who, (long long)mc); }
+    // once per call, before any device memory: Ks of all m samples, mc samples per chunk
+    void prepare(int64_t n, int Kp, const std::vector<int> &Ks, int64_t mc, size_t workspace)
+    {
+        (void)n;
+        size_t slab_bytes = 0;                                        // the largest table of the call
+        for (const int K : Ks) {
+            int cols;
+            slab_bytes = std::max(slab_bytes, table_bytes(Kp, K, cols));
+        }
+        force_global = env_flag("RC_RELABEL_TABLE_GLOBAL");           // tests: the table in the global slab at every size
+        // the slabs: one table per resident workgroup, within a quarter of the workspace (one workgroup at the least)
+        slab_dwords = (slab_bytes + 15) / 16 * 4;
+        grid_global = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(GLOBAL_GRID_MAX, mc),
+                                                                     (long long)(workspace / 4 / (slab_dwords * 4))));
     }
 
-    DeviceBuffers B;
-    unsigned short *d_piv, *d_zid; int *d_Ks, *d_names; unsigned *d_counts, *d_slab = nullptr;
-    long long *d_labels = nullptr, *d_maps = nullptr, *d_overlap;
-    const size_t ncounts = (size_t)n * (size_t)(Kp + 1);
-    HIPCHK(nullptr, B.alloc(d_piv, (size_t)n));
-    HIPCHK(nullptr, B.alloc(d_names, (size_t)Kp));
-    HIPCHK(nullptr, B.alloc(d_counts, ncounts));
-    HIPCHK(nullptr, B.alloc(d_zid, (size_t)mc * n));
-    HIPCHK(nullptr, B.alloc(d_Ks, (size_t)mc));
-    HIPCHK(nullptr, B.alloc(d_overlap, (size_t)mc));
-    if (labels_out) HIPCHK(nullptr, B.alloc(d_labels, (size_t)mc * n));
-    if (maps_out) HIPCHK(nullptr, B.alloc(d_maps, (size_t)mc * Wd));
-    HIPCHK(nullptr, hipMemcpy(d_piv, h_piv.data(), (size_t)n * sizeof(unsigned short), hipMemcpyHostToDevice));
-    HIPCHK(nullptr, hipMemcpy(d_names, names.data(), (size_t)Kp * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(nullptr, hipMemset(d_counts, 0, ncounts * sizeof(unsigned)));
-    TimingEvents ev;
-    HIPCHK(nullptr, ev.create());
-
-    double ms_acc = 0.0;
-    for (int64_t s0 = 0; s0 < m; s0 += mc) {
-        const int64_t ms = std::min(mc, m - s0);
+    // one chunk's kernel between the events' begin and end
+    int32_t launch(DeviceBuffers &B, TimingEvents &ev, const Chunk &c)
+    {
         size_t tab = 0;
         int cmax = 0;
-        for (int64_t s = 0; s < ms; ++s) {
-            if (!keep_ids) {
-                compact_labels(samples + (size_t)(s0 + s) * n, n, cnt, id, no_slot);
-                dense_ids(samples + (size_t)(s0 + s) * n, n, id, h_zid.data() + (size_t)s * n);
-            }
+        for (int s = 0; s < c.ms; ++s) {
             int cols;
-            tab = std::max(tab, table_bytes((int)Kp, Ks[(size_t)(s0 + s)], cols));
+            tab = std::max(tab, table_bytes(c.Kp, c.h_Ks[s], cols));
             cmax = std::max(cmax, cols);
         }
         const int vw = (cmax + 1 + 3) / 4 * 4;
@@ -301,24 +237,26 @@ extern "C" int32_t rc_relabel(int32_t device, const int64_t *samples, int64_t m,
         const bool tglobal = force_global || vec_bytes + tab > LDS_BUDGET;
         const size_t lds = vec_bytes + (tglobal ? 0 : tab);
         if (tglobal && !d_slab) HIPCHK(nullptr, B.alloc(d_slab, (size_t)grid_global * slab_dwords));
-        HIPCHK(nullptr, hipMemcpy(d_zid, h_zid.data() + (keep_ids ? (size_t)s0 * n : 0), (size_t)ms * n * sizeof(unsigned short), hipMemcpyHostToDevice));
-        HIPCHK(nullptr, hipMemcpy(d_Ks, Ks.data() + s0, (size_t)ms * sizeof(int), hipMemcpyHostToDevice));
         auto kern = tglobal ? k_relabel<true> : k_relabel<false>;
         HIPCHK(nullptr, set_dynamic_lds(kern, lds));
         Args a{};
-        a.piv = d_piv; a.zid = d_zid; a.Ks = d_Ks; a.names = d_names; a.slab = d_slab; a.labels = d_labels; a.maps = d_maps;
-        a.overlap = d_overlap; a.counts = d_counts; a.slab_dwords = slab_dwords;
-        a.n = (int)n; a.mc = (int)ms; a.Kp = (int)Kp; a.W = (int)Wd; a.vw = vw;
-        const unsigned grid = (unsigned)std::min<int64_t>(tglobal ? grid_global : GRID_MAX, ms);
+        a.piv = c.piv; a.zid = c.zid; a.Ks = c.Ks; a.names = c.names; a.slab = d_slab; a.labels = c.labels; a.maps = c.maps;
+        a.overlap = c.overlap; a.counts = c.counts; a.slab_dwords = slab_dwords;
+        a.n = c.n; a.mc = c.ms; a.Kp = c.Kp; a.W = c.W; a.vw = vw;
+        const unsigned grid = (unsigned)std::min<int64_t>(tglobal ? grid_global : GRID_MAX, c.ms);
         HIPCHK(nullptr, ev.begin(0));
         kern<<<grid, TPB, lds, 0>>>(a);
         HIPCHK(nullptr, ev.end(0));
-        HIPCHK(nullptr, ev.elapsed_ms(ms_acc));
-        HIPCHK(nullptr, hipMemcpy(overlap_out + s0, d_overlap, (size_t)ms * sizeof(long long), hipMemcpyDeviceToHost));
-        if (labels_out) HIPCHK(nullptr, hipMemcpy(labels_out + (size_t)s0 * n, d_labels, (size_t)ms * n * sizeof(long long), hipMemcpyDeviceToHost));
-        if (maps_out) HIPCHK(nullptr, hipMemcpy(maps_out + (size_t)s0 * Wd, d_maps, (size_t)ms * Wd * sizeof(long long), hipMemcpyDeviceToHost));
+        return RC_OK;
     }
-    HIPCHK(nullptr, hipMemcpy(counts_out, d_counts, ncounts * sizeof(unsigned), hipMemcpyDeviceToHost));
-    if (kernel_ms) *kernel_ms = ms_acc;
-    return RC_OK;
+};
+
+}  // namespace relabel
+
+extern "C" int32_t rc_relabel(int32_t device, const int64_t *samples, int64_t m, int64_t n, const int64_t *pivot, int64_t Kp_in,
+                              int64_t *labels_out, int64_t *maps_out, int64_t maps_width, int64_t *overlap_out, void *counts_out,
+                              double *kernel_ms)
+{
+    return relabel::run("rc_relabel", relabel::KMAX, relabel::Launch{}, device, samples, m, n, pivot, Kp_in, labels_out, maps_out, maps_width,
+                        overlap_out, counts_out, kernel_ms);
 }

@@ -910,11 +910,28 @@ def relabel(result_or_samples, pivot, *, device: int = 0) -> Relabelling:
     clusters are matched to the pivot's so that the number of points on which the two agree is largest (a linear assignment on
     their contingency table; among optimal matchings the one the fixed tie rule of DESIGN.md §8 "Relabelling" finds), and
     counts says per point how often it then lands in each of the pivot's clusters."""
+    return _relabel(result_or_samples, pivot, device, wide=False)
+
+
+RELABEL_KMAX = 1024     # rc_relabel's clusters per labelling; relabel_wide goes to rc_relabel_wide (4096) above it
+
+
+def relabel_wide(result_or_samples, pivot, *, device: int = 0) -> Relabelling:
+    """relabel for a pivot and samples of up to 4096 clusters each.  With at most 1024 clusters everywhere it is relabel, call
+    and bytes; otherwise rc_relabel_wide (csrc/relabel_wide.inc.hip) computes the same definition with the same tie rule on a
+    sparse contingency table."""
+    return _relabel(result_or_samples, pivot, device, wide=True)
+
+
+def _relabel(result_or_samples, pivot, device, wide):
     S = _sample_matrix(result_or_samples)
     c = _labels(pivot)
     if c.shape[0] != S.shape[1]:
         raise ValueError("the pivot must have as many labels as the samples")
-    out = _lib.relabel(S, c, device=device)
+    if wide and max(len(np.unique(c)), _lib.largest_sample(np.ascontiguousarray(S, dtype=np.int64))) > RELABEL_KMAX:
+        out = _lib.relabel_wide(S, c, device=device)
+    else:
+        out = _lib.relabel(S, c, device=device)
     names = np.unique(np.asarray(pivot).astype(np.int64))
     if not np.array_equal(names, out["pivot_labels"]):              # _labels compacted a pivot with names above n: give them back
         back = np.concatenate([[0], names])

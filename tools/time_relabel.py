@@ -3,6 +3,7 @@ inputs: a NumPy cross-tabulation, scipy.optimize.linear_sum_assignment and the r
 
     python tools/time_relabel.py                   # both cases, median of 10 repetitions after a warm-up
     python tools/time_relabel.py --reps 15 --no-host
+    python tools/time_relabel.py --wide            # rc_relabel against rc_relabel_wide at K ≈ 1000, then the latter at K = 2048, 4096
 
 Cases (seed 0): "planted K=50" — n = 8192, m = 1000, a planted partition of 50 clusters with 20 % of the points relabelled at
 random in every sample, the pivot the planted partition: the tables (50 × 50) are in LDS; and "large K" — n = 8192, a planted
@@ -12,7 +13,12 @@ call's kernels; the wall time adds the host preparation (dense ids) and the copi
 is timed after a call of its own (SciPy is imported above), on --host-samples samples (200 by default; all of them when 0 or
 when there are fewer) and extrapolated linearly to m, which is said in its line; SciPy's choice
 among tied optima is not specified, so only its optimum value is compared with the device's overlap.  One JSON line per
-measurement."""
+measurement.
+
+--wide (seed 0, n = 8192, --large-m samples, the pivot the planted partition): "large K" is timed by rc_relabel and by
+rc_relabel_wide (csrc/relabel_wide.inc.hip) in this one process, their outputs compared, then planted partitions of 2048 and 4096
+clusters by rc_relabel_wide alone; medians of 5 calls after a warm-up, kernel time and whole call, and the host route on all the
+samples beside them."""
 import argparse
 import json
 import os
@@ -44,6 +50,34 @@ def host_route(S, c):
     return labels, overlap
 
 
+def wide(a):
+    """the --wide report"""
+    warm = planted_samples(64, 5, 3, 0.1)
+    _lib.relabel(warm, warm[0]); _lib.relabel_wide(warm, warm[0]); host_route(warm, warm[0])
+    for K in (1000, 2048, 4096):
+        S = planted_samples(a.n, a.large_m, K, a.noise)
+        c = planted_samples(a.n, 1, K, 0.0)[0]
+        last = {}
+        for name, call in (("rc_relabel", _lib.relabel),) * (K == 1000) + (("rc_relabel_wide", _lib.relabel_wide),):
+            call(S, c)                                                     # warm-up at this shape
+            walls, outs = timed(5, lambda: call(S, c))
+            kms = [o["kernel_ms"] for o in outs]
+            last[name] = outs[-1]
+            print(json.dumps(dict(what=name, n=a.n, m=a.large_m, K_planted=K, K_pivot=len(np.unique(c)), K_samples_max=outs[-1]["maps"].shape[1],
+                                  reps=5, kernel_ms_median=round(statistics.median(kms), 3), kernel_ms_min=round(min(kms), 3),
+                                  kernel_ms_max=round(max(kms), 3), wall_s_median=round(statistics.median(walls), 4),
+                                  wall_s_min=round(min(walls), 4), wall_s_max=round(max(walls), 4))), flush=True)
+        if len(last) == 2:
+            print(json.dumps(dict(what="check", K_planted=K, wide_equals_rc_relabel=bool(all(
+                np.array_equal(last["rc_relabel"][k], last["rc_relabel_wide"][k]) for k in ("labels", "maps", "overlap", "counts"))))), flush=True)
+        if not a.no_host:
+            host_route(S[:2], c)
+            t0 = time.perf_counter()
+            _, ov = host_route(S, c)
+            print(json.dumps(dict(what="host route (numpy + scipy)", K_planted=K, samples_timed=len(S), wall_s=round(time.perf_counter() - t0, 3),
+                                  optimum_equals_device_overlap=bool(np.array_equal(ov, last["rc_relabel_wide"]["overlap"])))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=8192)
@@ -53,7 +87,10 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--host-samples", type=int, default=200)
     ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--wide", action="store_true")
     a = ap.parse_args()
+    if a.wide:
+        return wide(a)
     warm = planted_samples(64, 5, 3, 0.1)
     for env in ("1", "0"):
         os.environ["RC_RELABEL_TABLE_GLOBAL"] = env                        # read at every call

@@ -708,6 +708,34 @@ int32_t rc_id_search(int32_t device, const int64_t *samples /* m×n, labels 1..n
                      int32_t *best, double *kernel_ms);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Ratio-loss search: rc_vi_search's search — the same runs, slot cap, compaction of the start, tie rules, tables — for the three
+ * criteria that are a mean over the samples of a ratio: omARI, the posterior mean of 1 − ARI(c, sample) (the reference's fourth
+ * MPEL loss, src/pointestimate.jl:38-47; Hubert and Arabie's index per sample), NVI = VI / H(c, sample) and
+ * NID = 1 − I / max(H(c), H(sample)) (infodist's default).  DESIGN.md §8 "Ratio-loss search".
+ *
+ * With rc_vi_gtable's Gq and Phiq, C2(x) = x(x−1)/2 and N^s the contingency table of c with sample s, per sample:
+ *   NVI, NID:  T = Σ_kl Phiq(N^s_kl),  A = Σ_k Phiq(n_k),  B = Σ_l Phiq(n^s_l),  C = Phiq(n);
+ *              NVI: num = A + B − 2T, den = C − T;   NID: num = max(A, B) − T, den = C − min(A, B)
+ *   omARI:     T = Σ_kl C2(N^s_kl),  A = Σ_k C2(n_k),  B = Σ_l C2(n^s_l),  C = C2(n);
+ *              num = C·(A + B − 2T), den = C·(A + B) − 2·A·B
+ *   term = 0 where den = 0 (both partitions trivial and equal), else llrint(((double)num / (double)den)·2^40): int64 state (below
+ *   2^53 at n <= 8192, so the conversions are exact), one correctly rounded division, round-half-even.
+ * The search minimises the integer Q(c) = Σ_s term_s; a candidate's score is Σ_s term_s(candidate) − Σ_s term_s(point out), 0 for a
+ * new cluster, so a run is a pure function of its arguments that NumPy's float64 reproduces bit for bit.  While some points are
+ * unallocated B and C are those of the full samples.  Per run: loss_num = Q, loss = Q / (2^40·m).
+ * Arguments, RC_ERR_ARG and RC_ERR_CAPACITY (n <= 8192, m·n <= 2^26, slot cap <= 1024, the table budget) as rc_vi_search, and
+ * besides: RC_ERR_ARG for a loss that is none of the three; RC_ERR_CAPACITY for m > 2^21 (a term is at most 2·2^40, so
+ * Q <= 2^62), which binds only below n = 32.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define RC_RATIO_OMARI 0
+#define RC_RATIO_NVI 1
+#define RC_RATIO_NID 2
+int32_t rc_ratio_search(int32_t device, const int64_t *samples /* m×n, labels 1..n */, int64_t m, int64_t n, int32_t loss, int32_t nruns,
+                        const int64_t *init /* nruns×n, 0 = unallocated */, const int32_t *order /* nruns×n, 1-based */,
+                        int32_t maxK, int32_t maxsweeps, int64_t *labels_out /* nruns×n */, void *runs_out /* rc_psm_run_t[nruns] */,
+                        int32_t *best, double *kernel_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Grouped exact expected-VI search: many rc_vi_search searches over disjoint subsets of one sample set in one launch — the
  * update step of the several-partition summary (DESIGN.md §8 "Several-partition summary").  group[s] in 0..ngroups−1 names the
  * group of sample s, −1 leaves it out; run r searches the group run_group[r].

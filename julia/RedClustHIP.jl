@@ -594,6 +594,52 @@ n = 8192 — and above that the same search by rc_id_search_large, with the exac
 searchid(b::HIPBackend, result; nruns::Integer = 16, maxK::Integer = 0, maxsweeps::Integer = 100, seed::Integer = 0) =
     searchexactid(b, result, nruns, maxK, maxsweeps, seed)
 
+"""
+    searchratio(HIPBackend(), result, loss; nruns = 16, maxK = 0, maxsweeps = 100, seed = 0) -> (clust, info)
+
+Search all partitions for the minimum posterior mean of 1 − ARI (`loss = "omARI"`, the fourth loss of
+`getpointestimate(method = "MPEL")`), of the normalised VI (`"NVI"`) or of the normalised information distance (`"NID"`, what
+`infodist` returns by default): rc_ratio_search.  Runs: the `nruns` orders from empty labels and one from the result of the nearest
+existing search — `searchmaxpear` for omARI, `searchvi` for NVI, `searchid` for NID — so the result is
+never worse in the integer criterion `info.loss_num` than that partition.  `info.loss = loss_num / (2^40·m)`.  n <= 8192.
+"""
+function searchratio(b::HIPBackend, result, loss::AbstractString; nruns::Integer = 16, maxK::Integer = 0, maxsweeps::Integer = 100,
+                     seed::Integer = 0)
+    code = Dict("omARI" => 0, "NVI" => 1, "NID" => 2)             # RC_RATIO_OMARI, _NVI, _NID
+    haskey(code, loss) || throw(ArgumentError("loss must be \"omARI\", \"NVI\" or \"NID\""))
+    samples = samplematrix(result)
+    n, m = size(samples)
+    start, _ = loss == "omARI" ? searchmaxpear(b, result; nruns = nruns, maxK = maxK, maxsweeps = maxsweeps, seed = seed) :
+               loss == "NVI" ? searchexactvi(b, result, nruns, maxK, maxsweeps, seed) : searchexactid(b, result, nruns, maxK, maxsweeps, seed)
+    R = Int(nruns) + 1
+    init = zeros(Int64, n, R)                                     # column r = run r: row-major R×n for the library
+    order = Matrix{Int32}(undef, n, R)
+    rng = Random.MersenneTwister(seed)
+    for r in 1:nruns
+        order[:, r] .= Random.randperm(rng, n)
+    end
+    init[:, R] .= start; order[:, R] .= 1:n
+    cap = Int(maxK)
+    if cap == 0                                                   # the library's default cap, widened to the start's cluster count
+        lmax = maximum(length(unique(c)) for c in result.clusts)
+        need = length(unique(start))
+        cap = need > lmax ? need : 0
+    end
+    labels = Matrix{Int64}(undef, n, R)
+    runs = Vector{RcPsmRun}(undef, R)
+    best = Int32[0]
+    rc = ccall((:rc_ratio_search, LIB), Int32,
+               (Int32, Ptr{Int64}, Int64, Int64, Int32, Int32, Ptr{Int64}, Ptr{Int32}, Int32, Int32, Ptr{Int64}, Ptr{Cvoid},
+                Ptr{Int32}, Ptr{Cdouble}),
+               b.device, samples, m, n, code[loss], R, init, order, cap, maxsweeps, labels, runs, best, C_NULL)
+    check(Ptr{Cvoid}(C_NULL), rc)
+    info = (loss = [x.loss for x in runs], loss_num = [x.loss_num for x in runs], sweeps = [Int(x.sweeps) for x in runs],
+            converged = [x.converged != 0 for x in runs], moves = [Int(x.moves) for x in runs], K = [Int(x.K) for x in runs],
+            labels = labels, best = Int(best[1]) + 1)
+    return (labels[:, best[1] + 1], info)
+end
+
+export searchratio
 export searchid
 export searchpointestimate, posteriorcounts
 

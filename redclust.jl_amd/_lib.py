@@ -255,6 +255,8 @@ SIGNATURES = {
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rc_id_search": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "rc_ratio_search": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                    C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "rc_vi_search_groups": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "rc_vi_search_large": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
@@ -1088,6 +1090,21 @@ def id_search(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device:
     """rc_id_search: the exact expected-ID search.  Arguments and the returned dict as vi_search; loss is the expected
     information distance (nats), loss_num the integer Q_ID."""
     return _exact_search(lib().rc_id_search, samples, init, order, maxK, maxsweeps, device)
+
+
+RATIO_LOSSES = {"omARI": 0, "NVI": 1, "NID": 2}   # RC_RATIO_OMARI, _NVI, _NID
+
+
+def ratio_search(samples, loss: str, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0):
+    """rc_ratio_search: the search for the minimum posterior mean of 1 − ARI ("omARI"), of the normalised VI ("NVI") or of the
+    normalised information distance ("NID").  Arguments and the returned dict as vi_search; loss is Q / (2^40·m), loss_num the
+    integer Q."""
+    if loss not in RATIO_LOSSES:
+        raise ValueError('loss must be "omARI", "NVI" or "NID"')
+    S = _label_matrix(samples)
+    return _search_runs(init, order, maxK, maxsweeps,
+                        lambda n, *tail: _check(lib().rc_ratio_search(int(device), S.ctypes.data, S.shape[0], n, RATIO_LOSSES[loss], *tail)),
+                        n=S.shape[1])
 
 
 def id_search_large(samples, init, order, maxK: int = 0, maxsweeps: int = 100, device: int = 0):

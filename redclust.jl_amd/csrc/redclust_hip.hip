@@ -7537,6 +7537,7 @@ extern "C" int32_t rc_measure_read_ceiling(int32_t device, int64_t mib, int32_t 
 #include "visearch_large.inc.hip"    // and once more: k_idlarge<PQ>, the expected information distance
 #undef VISL_ID
 #include "visearch.inc.hip"
+#include "ratiosearch.inc.hip"       // k_ratiosearch<PQ, LOSS>: omARI, NVI and NID on the same tables
 #include "hclust.inc.hip"
 #include "hclust_large.inc.hip"      // k_hclust_large<LINK>, k_eloss_large<EGT>: the same with n <= 32767
 #include "slabplan.inc.hpp"

@@ -182,6 +182,46 @@ def expectedid(clust, samples) -> float:
     return total / (n * len(clusts))
 
 
+def _expected_ratio(clust, samples, weight, ratio) -> float:
+    """The mean over the samples of ratio(A, B, T, C) → (num, den), 0 where den = 0: A, B, T the sums of weight(counts) over the
+    clusters of clust, of the sample and over their contingency table, C = weight(n).  Plain f64 NumPy on the host."""
+    c = np.unique(_labels(clust), return_inverse=True)[1].astype(np.int64)
+    clusts = samples.clusts if hasattr(samples, "clusts") else samples
+    n = len(c)
+    if len(clusts) == 0:
+        raise ValueError("no samples")
+    total = lambda x: float(np.sum(weight(x[x > 0].astype(np.float64))))
+    A, C = total(np.bincount(c)), total(np.array([n]))
+    out = 0.0
+    for s in clusts:
+        s = np.asarray(s)
+        if len(s) != n:
+            raise ValueError("every sample must have as many labels as clust")
+        s = np.unique(_labels(s), return_inverse=True)[1].astype(np.int64)
+        num, den = ratio(A, total(np.bincount(s)), total(np.bincount(c * (int(s.max()) + 1) + s)), C)
+        out += num / den if den else 0.0
+    return out / len(clusts)
+
+
+def expectedomari(clust, samples) -> float:
+    """The posterior mean of 1 − ARI(clust, sample), ARI Hubert and Arabie's adjusted Rand index of each sample (the reference's
+    "omARI" loss; maxpear's PEAR takes both expectations before the ratio): what searchratio(loss="omARI") minimises."""
+    return _expected_ratio(clust, samples, lambda x: x * (x - 1.0) / 2.0,
+                           lambda P, Q, X, T: (T * (P + Q - 2.0 * X), T * (P + Q) - 2.0 * P * Q))
+
+
+def expectednvi(clust, samples) -> float:
+    """The posterior mean of the normalised VI, VI(clust, sample) / H(clust, sample) (SALSO's "NVI"; 0 where both partitions are
+    one cluster): what searchratio(loss="NVI") minimises."""
+    return _expected_ratio(clust, samples, lambda x: x * np.log(x), lambda A, B, T, C: (A + B - 2.0 * T, C - T))
+
+
+def expectednid(clust, samples) -> float:
+    """The posterior mean of the normalised information distance 1 − I / max(H(clust), H(sample)) — infodist's default,
+    evaluateclustering's `nid`, SALSO's "NID": what searchratio(loss="NID") minimises."""
+    return _expected_ratio(clust, samples, lambda x: x * np.log(x), lambda A, B, T, C: (max(A, B) - T, C - min(A, B)))
+
+
 def _counts_input(samples_or_counts, numsamples, ctx):
     """The three input forms of searchpointestimate as (samples matrix or None, counts or None, numsamples, n)."""
     if ctx is not None:
@@ -344,6 +384,65 @@ def searchid(samples, *, nruns: int = 16, init=None, maxK: int = 0, maxsweeps: i
     if not hasattr(samples, "clusts"):
         samples = _Samples(_sample_matrix(samples))
     return _exact_search(samples, "ID", nruns, maxK, maxsweeps, seed, init, device, large=True)
+
+
+def _ratio_q(clust, S, loss) -> int:
+    """rc_ratio_search's integer criterion Q of a complete labelling, on the host: Python ints and one f64 division per sample"""
+    n = S.shape[1]
+    if loss == "omARI":
+        W = np.arange(n + 1, dtype=np.int64)
+        W = W * (W - 1) // 2
+    else:
+        W = np.concatenate([[0], np.cumsum(_lib.vi_gtable(n))]).astype(np.int64)
+    c = np.unique(_labels(clust), return_inverse=True)[1].astype(np.int64)
+    A, C, q = int(W[np.bincount(c)].sum()), int(W[n]), 0
+    for s in S:
+        s = np.unique(s, return_inverse=True)[1].astype(np.int64)
+        B, T = int(W[np.bincount(s)].sum()), int(W[np.bincount(c * (int(s.max()) + 1) + s)].sum())
+        if loss == "omARI":
+            num, den = C * (A + B - 2 * T), C * (A + B) - 2 * A * B
+        elif loss == "NVI":
+            num, den = A + B - 2 * T, C - T
+        else:
+            num, den = max(A, B) - T, C - min(A, B)
+        if den:
+            q += int(np.rint(np.float64(num) / np.float64(den) * 2.0 ** 40))
+    return q
+
+
+def searchratio(samples, loss, *, nruns: int = 16, init=None, maxK: int = 0, maxsweeps: int = 100, seed: int = 0, device: int = 0):
+    """Search ALL partitions for the clustering of minimum posterior mean 1 − ARI (loss="omARI", the reference's fourth MPEL loss;
+    expectedomari), normalised VI ("NVI"; expectednvi) or normalised information distance ("NID"; expectednid) — SALSO's remaining
+    criteria.  samples: an MCMCResult, anything with `.clusts`, or an m×n label matrix, n <= 8192.  On the GPU (rc_ratio_search,
+    csrc/ratiosearch.inc.hip): int64 state and one correctly rounded f64 division per sample and candidate, so a run is an exact
+    function of its inputs; info["loss_num"] is the integer Q = Σ_s llrint(ratio_s·2^40), info["loss"] = Q / (2^40·m).
+    Runs: the nruns Philox orders from empty labels of the other searches, one per init labelling (identity order), and one from the
+    result of the nearest existing search with the same arguments — searchmaxpear for omARI, searchpointestimate(…, "VI",
+    exact=True) for NVI, searchpointestimate(…, "ID") for NID — so the result is never worse in Q than that partition:
+    info["start"] is that call's info, info["start_loss_num"] the Q of its partition.  maxK = 0 caps the clusters at the largest
+    cluster count among the samples (or a start's, if larger)."""
+    if loss not in _lib.RATIO_LOSSES:
+        raise ValueError('loss must be "omARI", "NVI" or "NID"')
+    if not hasattr(samples, "clusts"):
+        samples = _Samples(_sample_matrix(samples))
+    S = _sample_matrix(samples)
+    n = S.shape[1]
+    _check_lds_n(n, "searchratio")
+    kw = dict(nruns=nruns, maxK=maxK, maxsweeps=maxsweeps, seed=seed, init=init, device=device)
+    if loss == "omARI":
+        start, prior = searchmaxpear(samples, **kw)
+    else:
+        start, prior = searchpointestimate(samples, "VI" if loss == "NVI" else "ID", exact=True, **kw)
+    inits, orders = _search_starts(n, nruns, seed, init, extra=_labels(start))
+    if not maxK:
+        lmax = max(len(np.unique(s)) for s in S)
+        need = max(len(np.unique(x[x > 0])) for x in inits)
+        maxK = need if need > lmax else 0
+    res = _lib.ratio_search(S, loss, inits, orders, maxK=maxK, maxsweeps=maxsweeps, device=device)
+    info = {k: res[k] for k in _INFO_KEYS}
+    info["start"] = prior
+    info["start_loss_num"] = _ratio_q(start, S, loss)
+    return res["labels"][res["best"]].copy(), info
 
 
 class _Samples:

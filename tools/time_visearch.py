@@ -6,6 +6,8 @@ tests/id_search_ref.py) doing ONE run's work on the host — the only yardstick 
     python tools/time_visearch.py --n 2000 --reps 7
     python tools/time_visearch.py --no-ref         # skip the NumPy restatement
     python tools/time_visearch.py --loss ID        # the same input through rc_id_search
+    python tools/time_visearch.py --loss omARI     # or NVI, NID: rc_ratio_search (csrc/ratiosearch.inc.hip) on the same input, and for
+                                                   # comparison rc_vi_search alternating with it in the same process; no NumPy run
     python tools/time_visearch.py --maxsweeps 1    # the first sweep alone (sequential allocation: every point moves)
     python tools/time_visearch.py --large          # rc_vi_search_large at n = 8192, 16384, 32767; at 8192 alternating with rc_vi_search
     python tools/time_visearch.py --large --loss ID   # rc_id_search_large likewise, against rc_id_search; and at every size alternating
@@ -111,7 +113,7 @@ def main():
     ap.add_argument("--nruns", type=int, default=16)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-ref", action="store_true")
-    ap.add_argument("--loss", choices=["VI", "ID"], default="VI")
+    ap.add_argument("--loss", choices=["VI", "ID", "omARI", "NVI", "NID"], default="VI")
     ap.add_argument("--maxsweeps", type=int, default=100)
     ap.add_argument("--large", action="store_true", help="rc_vi_search_large / rc_id_search_large; default sizes 8192 16384 32767")
     ap.add_argument("--fence-probe", action="store_true", help="rc_id_search_large with the fence the host chooses against the forced one")
@@ -120,8 +122,11 @@ def main():
         return fence_probe(a)
     if a.large and a.n == [2000, 8192]:
         a.n = [8192, 16384, 32767]
-    search = _lib.vi_search if a.loss == "VI" else _lib.id_search
-    expected = rc.expectedvi if a.loss == "VI" else rc.expectedid
+    ratio = a.loss in _lib.RATIO_LOSSES
+    if ratio and a.large:
+        ap.error("--large has no ratio-loss kernel")
+    search = {"VI": _lib.vi_search, "ID": _lib.id_search}.get(a.loss, lambda S, *rest, **kw: _lib.ratio_search(S, a.loss, *rest, **kw))
+    expected = {"VI": rc.expectedvi, "ID": rc.expectedid, "omARI": rc.expectedomari, "NVI": rc.expectednvi, "NID": rc.expectednid}[a.loss]
     warm = planted_samples(64, 5, 3, 0.1)
     search(warm, np.zeros((2, 64), np.int64), np.tile(np.arange(1, 65, dtype=np.int32), (2, 1)))   # module load, first launch
     if a.large:
@@ -131,12 +136,17 @@ def main():
         rng = np.random.Generator(np.random.Philox(key=0))
         order = np.stack([rng.permutation(n).astype(np.int32) + 1 for _ in range(a.nruns)])
         init = np.zeros((a.nruns, n), np.int64)
-        walls, kms, res = [], [], None
+        walls, kms, vi_kms, res, vi = [], [], [], None, None
         for _ in range(a.reps):
             t0 = time.perf_counter()
             res = search(S, init, order, maxsweeps=a.maxsweeps)
             walls.append(time.perf_counter() - t0)
             kms.append(res["kernel_ms"])
+            if ratio:
+                vi = _lib.vi_search(S, init, order, maxsweeps=a.maxsweeps)
+                vi_kms.append(vi["kernel_ms"])
+        compare = {} if not ratio else dict(vi_kernel_ms_median=round(statistics.median(vi_kms), 3), vi_sweeps=[int(x) for x in vi["sweeps"]],
+                                            vi_us_per_step=round(1e3 * statistics.median(vi_kms) / (n * int(vi["sweeps"].max())), 3))
         sw = res["sweeps"]
         best = res["labels"][res["best"]]
         print(json.dumps(dict(what="device", loss=a.loss, maxsweeps=a.maxsweeps, n=n, m=a.m, nruns=a.nruns, reps=a.reps,
@@ -146,8 +156,8 @@ def main():
                               sweeps=[int(x) for x in sw], converged=int(res["converged"].sum()), K=[int(x) for x in res["K"]],
                               best_loss=float(res["loss"][res["best"]]), **{f"expected{a.loss.lower()}_of_best": expected(best, S)},
                               us_per_step=round(1e3 * statistics.median(kms) / (n * int(sw.max())), 3),
-                              table_reads_per_step=a.m * a.K)), flush=True)
-        if n <= 2000 and not a.no_ref:
+                              table_reads_per_step=a.m * a.K, **compare)), flush=True)
+        if n <= 2000 and not a.no_ref and not ratio:
             import id_search_ref
             import vi_search_ref
             run_ref = vi_search_ref.vi_search_ref if a.loss == "VI" else id_search_ref.id_search_ref
